@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — DiT denoise throughput on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--batch 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--batch 32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -18,7 +18,15 @@ starts a new utterance batch (fresh x_T and the step-invariant text work: cross-
 real 50-step sampling loop.  value = (B x world) x K / max-over-ranks wall time  ("scaling": "weak", B per GPU fixed;
 no collective in the data path, SURVEY.md §8e — the only collectives are the timing barrier and the max-reduce).
 
-Besides the contract's line the JSON carries:
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step and the workload's description); nothing else runs on the GPU.
+
+    --dump-outputs DIR   after the timed steps, write what the last timed step computed as DIR/latents.npy (fp32): the state
+                         x_{t-1} the step leaves, what a caller of p_sample receives.  Above 32 MB it is a fixed sample: the
+                         same seeded set of latent positions (DIR/latent_positions.npy) of every utterance of rank 0.  Inputs
+                         (weights, text, x_T, noise) depend only on the arguments, so two builds compare output for output.
+
+With --full the JSON also carries:
   loops        5 more timed loops of K steps, HIP-event-timed on the compute stream: their ms/step and the median
   sweep        B in {1, 8, 32} per GPU (N = 1 runs only)
   c3_strong    BASELINE config 3 as a STRONG-scaling point: rank 0 holds a global batch of 256 utterances, scatters
@@ -66,6 +74,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="C2", choices=["C1", "C2", "C4", "C5", "C5_bf16", "shipped"])
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU (default: the preset's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's latents (rank 0, fp32, <= 32 MB: a fixed sample of positions above) as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: extra loops, roofline, parity, B sweep, C3, other configs, "
+                         "CPU baseline (each still switched off by its --no-* / --loops 0 / --profile-steps 0 option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-steps", type=int, default=5)
     ap.add_argument("--loops", type=int, default=5, help="extra HIP-event-timed loops of K steps (median reported)")
@@ -73,7 +86,7 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=256, help="C3 strong-scaling point: utterances held by rank 0")
     ap.add_argument("--no-c3", action="store_true", help="skip the C3 strong-scaling point")
     ap.add_argument("--write-c3-expect", action="store_true",
-                    help="N = 1 only: record this tree's C3 latents digest in profiles/c3_digest_expect.json (what N = 2 / 4 / 8 must reproduce)")
+                    help="--full, N = 1 only: record this tree's C3 latents digest in profiles/c3_digest_expect.json (what N = 2 / 4 / 8 must reproduce)")
     ap.add_argument("--no-parity", action="store_true", help="skip the in-run oracle parity check of the timed shape")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the C4 / C5 / training-step side measurements (N = 1 runs of the default config only)")
@@ -85,7 +98,30 @@ def parse():
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="off",
                     help="replay the step from a HIP graph.  Measured: no gain at B = 1 / 8 (2.35 / 4.59 ms per step "
                          "either way: small batches are bound by per-kernel latency on sparse grids, not by launches)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.write_c3_expect and not args.full:
+        ap.error("--write-c3-expect needs --full (the C3 point runs only there)")
+    return args
+
+
+DUMP_BYTES = 32 << 20      # --dump-outputs: above this the latents are sampled by position
+
+
+def dump_outputs(out_dir, x):
+    """DIR/latents.npy: the state the last timed step left, (B, N, d) fp32, or (B, P, d) at P seeded, sorted latent positions
+    (DIR/latent_positions.npy) when the whole would pass DUMP_BYTES.  Returns the file names."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    B, N, d = x.shape
+    keep = max(1, min(N, DUMP_BYTES // (B * d * 4)))
+    files = ["latents.npy"]
+    if keep < N:
+        pos = torch.randperm(N, generator=torch.Generator().manual_seed(20261016))[:keep].sort().values
+        x = x[:, pos.to(x.device)]
+        np.save(os.path.join(out_dir, "latent_positions.npy"), pos.numpy().astype(np.float64))
+        files.append("latent_positions.npy")
+    np.save(os.path.join(out_dir, "latents.npy"), x.float().cpu().numpy())
+    return files
 
 
 def free_port():
@@ -651,10 +687,12 @@ def main():
         dist.all_reduce(per_rank, op=dist.ReduceOp.SUM)
         rank_ms = [float(v) / args.steps * 1e3 for v in per_rank.tolist()]
         elapsed = max_over_ranks(elapsed)
+        # ---- what the last timed step computed, before anything else runs on the state ----
+        dumped = dump_outputs(args.dump_outputs, main_run.x) if args.dump_outputs and rank == 0 else None
 
-        # ---- extra loops, HIP-event-timed on the compute stream (median of >= 5) ----
+        # ---- --full: extra loops, HIP-event-timed on the compute stream (median of >= 5) ----
         loop_ms = []
-        for _ in range(max(args.loops, 0)):
+        for _ in range(max(args.loops, 0) if args.full else 0):
             sync()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -665,17 +703,17 @@ def main():
 
         # ---- roofline pass (rank 0): per-kernel-class HIP-event timing of the same steps, eager ----
         roof, classes = None, {}
-        if rank == 0 and args.profile_steps > 0:
+        if rank == 0 and args.full and args.profile_steps > 0:
             roof, classes = profile_classes(eng, main_run, cfg, B, N, T, args.profile_steps)
         # ---- in-run parity of the timed shape against the oracle (rank 0; every world size) ----
         parity = None
-        if rank == 0 and not args.no_parity:
+        if rank == 0 and args.full and not args.no_parity:
             parity = parity_check(model, cfg, B, N, T, dev)
         dist.barrier()
 
         # ---- B sweep (N = 1 runs): the same step at B in {1, 8, 32} per GPU ----
         sweep = []
-        if world == 1 and not args.no_sweep:
+        if args.full and world == 1 and not args.no_sweep:
             for b in (1, 8, 32):
                 if b == B:
                     ms = sorted(loop_ms)[len(loop_ms) // 2] if loop_ms else elapsed / args.steps * 1e3
@@ -717,7 +755,7 @@ def main():
 
         # ---- C3 as a strong-scaling point: global batch on rank 0 -> scatter -> 50-step loops -> gather ----
         c3 = None
-        if not args.no_c3 and args.config == "C2":
+        if args.full and not args.no_c3 and args.config == "C2":
             G, mb = args.global_batch, p["B"]
             gen = torch.Generator(device=dev)
             gen.manual_seed(77)
@@ -786,7 +824,7 @@ def main():
 
     # ---- the other configurations and the training step, witnessed by this same run (N = 1, default config) ----
     other = None
-    if world == 1 and args.config == "C2" and not args.no_other_configs:
+    if args.full and world == 1 and args.config == "C2" and not args.no_other_configs:
         del main_run
         torch.cuda.empty_cache()
         cache = {(cfg.hidden_dim, cfg.num_layers, cfg.num_heads): model.state_dict()}
@@ -820,20 +858,26 @@ def main():
                        "noise": "per-utterance Philox4x32-10 inside the update kernel" if seeded_noise else "torch generator -> noise tensor"},
             "step_tflops_per_gpu": step_tflops, "step_frac_of_mfma_peak": step_frac,
             "per_rank_ms_per_step": rank_ms, "rank_min_ms": min(rank_ms), "rank_max_ms": max(rank_ms),
-            "loops": {"n": len(loop_ms), "timer": "HIP events on the compute stream, max over ranks",
-                      "ms_per_step": loop_ms,
-                      "median_ms_per_step": sorted(loop_ms)[len(loop_ms) // 2] if loop_ms else None,
-                      "median_value": (B * world / (sorted(loop_ms)[len(loop_ms) // 2] * 1e-3)) if loop_ms else None},
-            "sweep": sweep or None,
-            "c3_strong": c3,
-            "roofline": roof,
-            "floor": floor_table(cfg, B, N, T, classes) if classes else None,
             "residual_stream": "bf16 (fp32 in accumulators and LayerNorm statistics)" if stream_is_bf16(cfg, B, N) else "fp32",
-            "parity": parity,
-            "other_configs": other,
-            "kernel_classes": classes,
+            "full": args.full,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped}
+        if args.full:
+            out.update({
+                "loops": {"n": len(loop_ms), "timer": "HIP events on the compute stream, max over ranks",
+                          "ms_per_step": loop_ms,
+                          "median_ms_per_step": sorted(loop_ms)[len(loop_ms) // 2] if loop_ms else None,
+                          "median_value": (B * world / (sorted(loop_ms)[len(loop_ms) // 2] * 1e-3)) if loop_ms else None},
+                "sweep": sweep or None,
+                "c3_strong": c3,
+                "roofline": roof,
+                "floor": floor_table(cfg, B, N, T, classes) if classes else None,
+                "parity": parity,
+                "other_configs": other,
+                "kernel_classes": classes,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, N, T)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     dist.barrier()

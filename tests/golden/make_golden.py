@@ -263,9 +263,50 @@ def make_slp():
         save(name + ".npz", logits=logits, decoded=tap["decoded"])
 
 
+# the forward shapes of tests/test_oracle_vs_reference.py: (d, L, H, B, N, T)
+REF_FORWARD_SHAPES = [(256, 1, 4, 1, 64, 64), (128, 2, 2, 3, 40, 24), (192, 2, 1, 2, 33, 17)]
+
+
+def make_reference_checks():
+    """G9: what the reference computes for the CPU tests that used to import it live (tests/test_oracle_vs_reference.py,
+    tests/test_host_logic.py::test_state_dict_keys_match_live_reference): eval forwards of DiTTO at small shapes, the
+    rotary embedding's frequencies / table / rotation, which parameters a train-mode backward reaches, and the reference
+    DiTTO's state_dict key set with shapes.  Names are stored as unicode arrays (np.load needs no pickle)."""
+    ref_dit, ref_ditto = import_reference()
+    out = {}
+    for i, (d, L, H, B, N, T) in enumerate(REF_FORWARD_SHAPES):
+        cfg = DiTTOConfig(d, L, H, 64, d, 20)
+        m = build_reference_ditto(ref_ditto, cfg, synthetic_state_dict(cfg, seed=9))
+        x, text, t = synthetic_inputs(cfg, B, N, T, seed=3)
+        with torch.no_grad():
+            out[f"forward{i}"] = m(x, text, t)
+    rot = ref_dit.RotaryEmbedding(64)
+    q = hash_normal((2, 100, 3, 64), "rope_q", 9)
+    with torch.no_grad():
+        table = rot(100, "cpu")
+        out.update(rope_inv_freq=rot.inv_freq, rope_table=table, rope_q=q, rope_out=rot.apply_rope(table, q))
+    cfg = DiTTOConfig(128, 2, 2, 64, 128, 20)
+    m = build_reference_ditto(ref_ditto, cfg, synthetic_state_dict(cfg, seed=9))
+    x, text, t = synthetic_inputs(cfg, 2, 32, 16, seed=3)
+    with torch.no_grad():
+        out["train_eval_repeat_equal"] = np.array(bool(torch.equal(m(x, text, t), m(x, text, t))))
+    m.train()
+    m(x, text, t).square().mean().backward()
+    named = [(n, p) for n, p in m.named_parameters() if not n.startswith("nac.")]
+    out["train_with_grad"] = np.array([n for n, p in named if p.grad is not None])
+    out["train_without_grad"] = np.array([n for n, p in named if p.grad is None])
+    sd = build_reference_ditto(ref_ditto, cfg, synthetic_state_dict(cfg)).state_dict()
+    keys = [k for k in sd if not k.startswith("nac.")]
+    out["state_keys"] = np.array(keys)
+    out["state_shapes"] = np.array([",".join(str(s) for s in sd[k].shape) for k in keys])
+    save("G9_reference_checks.npz", **out)
+
+
 if __name__ == "__main__":
     if "--vq-only" in sys.argv:
         make_vq()
+    elif "--reference-checks-only" in sys.argv:
+        make_reference_checks()
     elif "--slp-only" in sys.argv:
         make_slp()
     elif "--loop768-only" in sys.argv:
@@ -275,3 +316,4 @@ if __name__ == "__main__":
         make_vq()
         make_slp()
         make_loop768()
+        make_reference_checks()

@@ -1,6 +1,9 @@
-"""The drop-in recipe of INTEGRATION.md §2, exercised with the reference's OWN import lines (CPU, skips without the
-reference tree).  Each case runs in a fresh interpreter so sys.path / sys.modules start clean.  Only what is absent
-from this image is stubbed: torchaudio, the BigVGAN checkout, `evaluate`."""
+"""The drop-in recipe of INTEGRATION.md §2 (CPU).  The caller's tree is a stand-in written by the `caller_src` fixture in the
+reference's src/ layout: `model/`, `components/`, `utils/` as namespace packages, the scripts' import blocks in their files.  The
+modules this package must SHADOW (model.DiTTO, model.SpeechGenerator, model.SpeechLP, components.DiT, components.VectorQuantizer)
+raise on import, so a recipe that lets one of them win fails loudly; the ones that must FALL THROUGH to the caller's tree
+(utils.*, model.NeuralAudioCodec, components.EnCodec) are small modules whose __file__ is checked.  Each case runs in a fresh
+interpreter so sys.path / sys.modules start clean."""
 import os
 import subprocess
 import sys
@@ -8,27 +11,96 @@ import textwrap
 
 import pytest
 
-from conftest import REFERENCE_SRC
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(REFERENCE_SRC), reason="reference tree not present")
 
-STUBS = """
-import sys, types, importlib.machinery
-import transformers                                   # before the stubs: its availability probes must see no torchaudio
-from transformers import AutoProcessor, AutoTokenizer  # noqa: F401
-for name in ("torchaudio", "torchaudio.transforms", "bigvgan_v2_24khz_100band_256x",
-             "bigvgan_v2_24khz_100band_256x.bigvgan", "bigvgan_v2_24khz_100band_256x.meldataset", "evaluate"):
-    m = types.ModuleType(name); m.__path__ = []; m.__spec__ = importlib.machinery.ModuleSpec(name, None)
-    sys.modules[name] = m
-sys.modules["bigvgan_v2_24khz_100band_256x"].bigvgan = sys.modules["bigvgan_v2_24khz_100band_256x.bigvgan"]
-sys.modules["bigvgan_v2_24khz_100band_256x.meldataset"].get_mel_spectrogram = lambda *a, **k: None
-sys.modules["evaluate"].load = lambda *a, **k: None
-"""
+SHADOWED = ("model/DiTTO.py", "model/SpeechLP.py", "components/DiT.py", "components/VectorQuantizer.py")
+CALLER_FILES = {
+    "utils/Config.py": '''
+        class BaseConfig:
+            SAMPLE_RATE = 24000
+
+
+        class ConfigDiTTO(BaseConfig):
+            MODEL_NAME = "DiTTO"
+            HIDDEN_DIM = 256
+            NUM_LAYERS = 2
+            NUM_HEADS = 4
+            TIME_DIM = 256
+            TEXT_EMBED_DIM = 256
+            DIFFUSION_STEPS = 50
+
+            @classmethod
+            def display(cls):
+                print("DiTTO Settings:", {k: v for k, v in vars(cls).items() if k.isupper()})
+
+
+        class ConfigNAC(BaseConfig):
+            LAMBDA_FACTOR = 0.1
+
+            @classmethod
+            def display(cls):
+                print("NAC Settings:", cls.LAMBDA_FACTOR)
+
+
+        class ConfigSLP(BaseConfig):
+            NB_CLASSES = 11
+            NUM_HEADS = 1
+            NUM_LAYERS = 1
+            EMBEDDING_DIM = 64
+
+            @classmethod
+            def display(cls):
+                print("SLP Settings:", cls.NB_CLASSES)
+    ''',
+    "utils/Trainer.py": '''
+        class Trainer:
+            def set_model(self, model, name):
+                self.model, self.name = model, name
+                return self
+    ''',
+    "utils/MLS.py": "MLS = object\n",
+    "model/NeuralAudioCodec.py": "class NAC:\n    pass\n",
+    "components/EnCodec.py": "class EnCodec:\n    pass\n",
+    # the scripts' import blocks come first, ended by a marker line; what follows must never run
+    "TrainDiTTO.py": '''
+        from model.DiTTO import DiTTO
+        from utils.Config import ConfigDiTTO, ConfigNAC
+        from utils.Trainer import Trainer
+        from utils.MLS import MLS
+        ConfigDiTTO.display()
+        # --- end of import block
+        raise SystemExit("the stand-in script body is not part of the test")
+    ''',
+    "model/SpeechGenerator.py": '''
+        import torch
+        from model.DiTTO import DiTTO
+        from model.SpeechLP import SLP
+        from utils.Config import ConfigDiTTO, ConfigSLP
+        # --- end of import block
+        raise ImportError("the caller's model.SpeechGenerator was imported: this package's alias should have won")
+    ''',
+}
+
+
+@pytest.fixture
+def caller_src(tmp_path):
+    src = tmp_path / "src"
+    for rel, body in CALLER_FILES.items():
+        (src / rel).parent.mkdir(parents=True, exist_ok=True)
+        (src / rel).write_text(textwrap.dedent(body).lstrip())
+    for rel in SHADOWED:
+        mod = rel[:-3].replace("/", ".")
+        (src / rel).write_text(f"raise ImportError('the caller\\'s {mod} was imported: this package\\'s alias should have won')\n")
+    return str(src)
+
+
+def import_block(path):
+    lines = open(path).read().splitlines()
+    return "\n".join(lines[:lines.index("# --- end of import block")])
 
 
 def run(body, cwd=None):
-    code = STUBS + textwrap.dedent(body)
+    code = textwrap.dedent(body)
     env = dict(os.environ, PYTHONPATH="")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=cwd or ROOT, env=env,
                        timeout=600)
@@ -36,33 +108,32 @@ def run(body, cwd=None):
     return r.stdout
 
 
-def test_traindito_import_block_under_the_recipe():
-    """sys.path exactly as INTEGRATION.md §2, then reference src/TrainDiTTO.py:1-11 verbatim (read from the reference
-    tree at test time), then the constructor call of :41-49 with the codec escape."""
+def test_traindito_import_block_under_the_recipe(caller_src):
+    """sys.path exactly as INTEGRATION.md §2, then the caller script's import block, then the constructor call with the
+    codec escape."""
+    src = import_block(os.path.join(caller_src, "TrainDiTTO.py"))
+    assert "from utils.Trainer import Trainer" in src and "ConfigDiTTO.display()" in src
     out = run(f"""
         import sys
-        sys.path.insert(0, {REFERENCE_SRC!r})                      # the caller's tree (scripts run from src/)
+        sys.path.insert(0, {caller_src!r})                         # the caller's tree (scripts run from src/)
         sys.path.insert(0, {ROOT!r})                               # the package
         sys.path.insert(0, {os.path.join(ROOT, "ditto_tts_amd", "compat")!r})
-        lines = open({os.path.join(REFERENCE_SRC, "TrainDiTTO.py")!r}).read().splitlines()[:11]
-        src = "\\n".join(lines)
-        assert "from utils.Trainer import Trainer" in src and "ConfigDiTTO.display()" in src
-        exec(compile(src, "TrainDiTTO.py:1-11", "exec"))
+        exec(compile({src!r}, "TrainDiTTO.py:import block", "exec"))
         import ditto_tts_amd.modules as M, utils.Config, utils.Trainer, utils.MLS
         assert DiTTO is M.DiTTO, DiTTO
-        assert utils.Config.__file__.startswith({REFERENCE_SRC!r}), utils.Config.__file__
-        assert utils.Trainer.__file__.startswith({REFERENCE_SRC!r}) and utils.MLS.__file__.startswith({REFERENCE_SRC!r})
+        assert utils.Config.__file__.startswith({caller_src!r}), utils.Config.__file__
+        assert utils.Trainer.__file__.startswith({caller_src!r}) and utils.MLS.__file__.startswith({caller_src!r})
         assert ConfigNAC.LAMBDA_FACTOR == 0.1
-        # modules.py's own `from model.NeuralAudioCodec import NAC` (reference src/model/DiTTO.py:4) resolves too
+        # modules.py's own `from model.NeuralAudioCodec import NAC` resolves to the caller's tree too
         import model.NeuralAudioCodec as NACmod
-        assert NACmod.__file__.startswith({REFERENCE_SRC!r})
+        assert NACmod.__file__.startswith({caller_src!r})
         from components.DiT import DiT, GlobalAdaLN, RotaryEmbedding
         assert DiT is M.DiT and GlobalAdaLN is M.GlobalAdaLN
         from components.VectorQuantizer import VectorQuantizer
         import ditto_tts_amd.around as A
         assert VectorQuantizer is A.VectorQuantizer
         import components.EnCodec as E
-        assert E.__file__.startswith({REFERENCE_SRC!r})
+        assert E.__file__.startswith({caller_src!r})
         m = DiTTO(hidden_dim=ConfigDiTTO.HIDDEN_DIM, num_layers=1, num_heads=ConfigDiTTO.NUM_HEADS,
                   time_dim=ConfigDiTTO.TIME_DIM, text_dim=ConfigDiTTO.TEXT_EMBED_DIM, diffusion_steps=20,
                   nac_model_path=None)
@@ -72,29 +143,30 @@ def test_traindito_import_block_under_the_recipe():
     assert "DiTTO Settings" in out and "ok-train" in out
 
 
-def test_speechgenerator_import_block_and_config_mutation():
-    """reference src/model/SpeechGenerator.py:1-13 verbatim under the recipe; then the notebook's flow
-    (src/Experiments.ipynb cells 1, 6): mutate ConfigDiTTO on the caller's module, build the sampler, and the loop
-    length follows the caller's global at call time (reference :161)."""
+def test_speechgenerator_import_block_and_config_mutation(caller_src):
+    """The caller's model/SpeechGenerator.py import block under the recipe; then a notebook's flow: mutate ConfigDiTTO on the
+    caller's module, build the sampler, and the loop length follows the caller's global at call time."""
+    src = import_block(os.path.join(caller_src, "model", "SpeechGenerator.py"))
+    assert "from model.SpeechLP import SLP" in src and "from utils.Config import ConfigDiTTO, ConfigSLP" in src
     out = run(f"""
         import sys
+        sys.path.insert(0, {ROOT!r})
         import ditto_tts_amd.compat as compat
-        compat.install(reference_src={REFERENCE_SRC!r})
-        lines = open({os.path.join(REFERENCE_SRC, "model", "SpeechGenerator.py")!r}).read().splitlines()[:13]
-        src = "\\n".join(lines)
-        assert "from model.SpeechLP import SLP" in src and "from utils.Config import ConfigDiTTO, ConfigSLP" in src
-        exec(compile(src, "SpeechGenerator.py:1-13", "exec"))
+        compat.install(reference_src={caller_src!r})
+        exec(compile({src!r}, "SpeechGenerator.py:import block", "exec"))
         import ditto_tts_amd.modules as M, ditto_tts_amd.slp as S, ditto_tts_amd.sampler as P
         assert DiTTO is M.DiTTO and SLP is S.SLP
         from model.SpeechGenerator import SpeechGenerator
         assert SpeechGenerator is P.SpeechGenerator
-        from utils.Config import ConfigSLP, ConfigNAC, ConfigDiTTO           # Experiments.ipynb cell 1
-        ConfigSLP.display(); ConfigNAC.display(); ConfigDiTTO.display()      # cell 2
-        ConfigDiTTO.DIFFUSION_STEPS = 40                                     # cell 6
+        from utils.Config import ConfigSLP, ConfigNAC, ConfigDiTTO
+        assert sys.modules["utils.Config"].__file__.startswith({caller_src!r})
+        ConfigSLP.display(); ConfigNAC.display(); ConfigDiTTO.display()
+        ConfigDiTTO.DIFFUSION_STEPS = 40
         ConfigDiTTO.NUM_LAYERS = 1
         sg = SpeechGenerator(lambda_factor=ConfigNAC.LAMBDA_FACTOR, nac_model_path=None, ditto_model_path=None,
                              slp_path=None, sample_rate=ConfigNAC.SAMPLE_RATE, device="cpu")
         assert sg.ditto_model.cfg.diffusion_steps == 40 and len(sg.betas) == 40 and sg._loop_steps() == 40
+        assert sg.ditto_model.cfg.hidden_dim == ConfigDiTTO.HIDDEN_DIM and sg.ditto_model.cfg.num_layers == 1
         ConfigDiTTO.DIFFUSION_STEPS = 25                  # mutated after construction: read at call time
         assert sg._loop_steps() == 25
         ConfigDiTTO.DIFFUSION_STEPS = 1000
@@ -109,25 +181,21 @@ def test_speechgenerator_import_block_and_config_mutation():
     assert "ok-sampler" in out
 
 
-def test_unmodified_script_through_the_launcher(tmp_path):
-    """`python -m ditto_tts_amd.run_reference <script>`: a script that sits in the reference's src/ layout and uses
-    the reference's import lines runs unchanged (sys.path[0] = its directory would otherwise make src/model/DiTTO.py
-    win).  The script here is a 6-line stand-in placed in a COPY-FREE overlay: a temp dir whose model/, components/,
-    utils/ are symlinks to the reference's."""
-    src = tmp_path / "src"
-    src.mkdir()
-    for d in ("model", "components", "utils"):
-        os.symlink(os.path.join(REFERENCE_SRC, d), src / d)
-    (src / "script.py").write_text(textwrap.dedent("""
-        from model.DiTTO import DiTTO
-        from utils.Config import ConfigDiTTO, ConfigNAC
-        from utils.Trainer import Trainer
-        import model.DiTTO as md, sys
-        print("DITTO_FROM", md.__file__)
-        print("ARGS", sys.argv[1:])
-    """))
-    code = STUBS + f"import sys; sys.path.insert(0, {ROOT!r}); sys.argv = ['x', {str(src / 'script.py')!r}, '--flag']\n" \
-                   "from ditto_tts_amd.run_reference import main; main(sys.argv[1:])\n"
+def test_unmodified_script_through_the_launcher(caller_src, tmp_path):
+    """`python -m ditto_tts_amd.run_reference <script>`: a script that sits in the caller's src/ layout and uses its import
+    lines runs unchanged (sys.path[0] = its directory would otherwise make src/model/DiTTO.py win)."""
+    script = os.path.join(caller_src, "script.py")
+    with open(script, "w") as f:
+        f.write(textwrap.dedent("""
+            from model.DiTTO import DiTTO
+            from utils.Config import ConfigDiTTO, ConfigNAC
+            from utils.Trainer import Trainer
+            import model.DiTTO as md, sys
+            print("DITTO_FROM", md.__file__)
+            print("ARGS", sys.argv[1:])
+        """))
+    code = f"import sys; sys.path.insert(0, {ROOT!r}); sys.argv = ['x', {script!r}, '--flag']\n" \
+           "from ditto_tts_amd.run_reference import main; main(sys.argv[1:])\n"
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=str(tmp_path), timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     assert os.path.join("ditto_tts_amd", "compat", "model", "DiTTO.py") in r.stdout and "ARGS ['--flag']" in r.stdout

@@ -3,10 +3,11 @@
 operation and NO compiler-inserted `s_waitcnt vmcnt` (only the counted waits of the asm statements).  Either one drains the
 LDS-DMA pipeline once per tile (a spilled register's reload counts on vmcnt with the DMA loads; a pending compiler-visible
 load in front of the loop leaves its wait inside the loop): measured 145 / 165 us against 102 / 110.
-    python tools/check_attn_loop.py          (compiles to /tmp; exit code 1 on a finding)"""
-import os, re, subprocess, sys
+    python tools/check_attn_loop.py          (compiles into a private temporary directory; exit code 1 on a finding)"""
+import os, re, subprocess, sys, tempfile
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = "/tmp/check_attn_loop.s"
+tmp = tempfile.TemporaryDirectory()
+out = os.path.join(tmp.name, "check_attn_loop.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", root + "/include", "-I",
                        root + "/ditto_tts_amd/csrc", "-w", "-fno-honor-nans", "-fno-slp-vectorize", "-S", "--cuda-device-only",
                        root + "/ditto_tts_amd/csrc/attention_p.hip", "-o", out])
