@@ -37,12 +37,15 @@
 // and a vector instruction's read of it; hipcc inserts them for its own instructions and NOT for an asm statement's.  In the loop
 // every slot is pinned by sched_barriers and an asm step reads a score block whose last MFMA lies >= 4 slots (128 cycles) back.
 // The prologue and the drain, which the compiler schedules freely, use the same step written in builtins (pair_step_c): the first
-// version's asm steps there read their accumulators one MFMA short (rel-L2 2e-2, block A only).
+// version's asm steps there read their accumulators one MFMA short (rel-L2 2e-2, block A only).  tools/check_attn_loop.py counts
+// the distance on the emitted ISA of every instantiation, on every path into each asm read (>= 12 wait states needed; 45 found).
 //
 // OPTIMISTIC SOFTMAX.  There is no running maximum: P = exp2(S) as it leaves the MFMA (q is pre-scaled: log2 units), O and l
 // accumulate unshifted and O / l at the end is the softmax — the same arithmetic as the shifted form as long as nothing leaves
-// fp32's range, i.e. for logits within +-88 of zero.  That frees the 32 registers of the -m accumulator blocks and every maximum,
-// raise and rescale.  Outside the range a row's l comes out 0, inf or NaN: every wave checks its rows at the end, the workgroup
+// fp32's range.  RANGE CONTRACT: the fast path stands for a row while the row sum of exp2(s) lies in [2^-100, 2^100], where
+// s = q.k * scale * log2(e) (in natural-log units: the row's log-sum-exp of q.k * scale lies within +-100 ln 2 = +-69.3); rows 2
+// octaves inside and outside both ends: tests/test_gpu_attention_resid.py::test_range_contract_boundary.  That frees the 32
+// registers of the -m accumulator blocks and every maximum, raise and rescale.  Outside the range a row's l comes out 0, inf or NaN: every wave checks its rows at the end, the workgroup
 // agrees through one LDS word, and if any row failed the WHOLE workgroup redoes its block with the exact tile loop (attn64p's:
 // running maximum, deferred raise) before anything is stored.  Fast path and exact path differ only by fp32 rounding.
 //

@@ -1045,6 +1045,24 @@ int ditto_attention_bf16(const void* q, int ldq, const void* k, int ldk, const v
     return DITTO_OK;
 }
 
+int ditto_attention_resid_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid_in,
+                               void* resid_out, int ldr, int resid_is_bf16, int B, int H, int Sq, int Skv, int dh, float scale,
+                               void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+    if (!q || !k || !v || !resid_out) return fail(DITTO_ERR_ARG, "null pointer to ditto_attention_resid_bf16");
+    if (dh % 64) return fail(DITTO_ERR_SHAPE, "head_dim must be a multiple of 64");
+    if (ldr < H * dh) return fail(DITTO_ERR_ARG, "ldr must cover H * dh columns");
+    if (dh != 64 && workspace_bytes < attention_workspace_bytes(B, H, Sq, Skv, dh))
+        return fail(DITTO_ERR_SIZE, "attention workspace too small");
+    AttnArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv;
+    a.resid_f32 = (float*)resid_out; a.ldr = ldr; a.resid_in = (const float*)resid_in; a.resid_bf16 = resid_is_bf16 != 0;
+    a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.dh = dh; a.scale = scale;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.q_prescaled = (g_attn_flags & 16) && dh == 64;   // as ditto_attention_bf16
+    HIP_TRY(launch_attention(a, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 int ditto_vq_argmin(const float* latents, const float* codebook, int64_t* idx, int R, int K, int D, float* scratch_k,
                     ditto_stream_t stream) {
     if (!latents || !codebook || !idx || !scratch_k || R <= 0 || K <= 0 || D <= 0)

@@ -273,6 +273,13 @@ int ditto_attention_bf16(const void* q, int ldq, const void* k, int ldk, const v
 /* scratch bytes ditto_attention_bf16 needs: 0 at dh = 64 (the fused kernels), the chunked score / probability / V^T arrays of the
  * GEMM-composed path otherwise */
 size_t ditto_attention_workspace_bytes(int B, int H, int Sq, int Skv, int dh);
+/* the self-attention's residual epilogue (src/components/DiT.py:131-139: the head merge added to the stream, no out-projection):
+ * resid_out[b*Sq+i, h*dh+c] = resid_in[b*Sq+i, h*dh+c] + (softmax(q k^T * scale) v)[...], rows of ldr elements, fp32 or (resid_is_bf16,
+ * head_dim 64 only) bf16.  resid_in NULL or == resid_out: in place (the model's case).  q / k / v, scale, workspace and attn_flags
+ * as ditto_attention_bf16; the same dispatch as the model's self-attention. */
+int ditto_attention_resid_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid_in,
+                               void* resid_out, int ldr, int resid_is_bf16, int B, int H, int Sq, int Skv, int dh, float scale,
+                               void* workspace, size_t workspace_bytes, ditto_stream_t stream);
 
 /* Full-row GEMM with the residual add and the FOLLOWING LayerNorm fused (N = 768: csrc/gemm_frd.hip, or its 64-row twin
  * csrc/gemm_fr64.hip under "fr_tile" 64 — 64 <= M < 128 always runs the 64-row twin, same fp32 bits;
