@@ -739,6 +739,8 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     const bool train_fwd = a.lse_out != nullptr || a.dropout_p > 0.f;
     if (a.resid_bf16 && (a.dh != DH || a.force_generic || a.causal || (train_fwd && (g_attn_flags & 8192))))
         return hipErrorInvalidValue;
+    const bool varlen = a.q_len || a.kv_len;
+    if (varlen && (a.dh != DH || a.force_generic || a.causal || train_fwd || !a.q_prescaled)) return hipErrorInvalidValue;
     if (a.dh == DH && !a.force_generic && !a.causal) {
         if ((a.ldq | a.ldk | a.ldv) % 8) return hipErrorInvalidValue;
         AttnParams p;
@@ -750,6 +752,11 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
         p.lse = a.lse_out; p.drop_thr = dropout_threshold(a.dropout_p);
         p.keep_scale = p.drop_thr ? 1.0f / (1.0f - a.dropout_p) : 1.0f;
         p.seed_lo = (unsigned)(a.seed & 0xFFFFFFFFu); p.seed_hi = (unsigned)(a.seed >> 32); p.layer = a.layer;
+        if (varlen) {   // per-utterance lengths: the 64-queries-per-wave family only (attention_p.hip), whatever the class rows
+            if (a.ldo % 8 || (a.resid_f32 && a.ldr % 8)) return hipErrorInvalidValue;   // 16-byte row pieces in the epilogue
+            p.q_len = a.q_len; p.kv_len = a.kv_len;
+            return launch_attn64p_varlen(p, a.resid_f32 != nullptr, s, (g_attn_flags & 1048576) != 0);
+        }
         if (a.lse_out || p.drop_thr) {   // training forward: log-sum-exp kept for the backward, dropout
             const dim3 gridt(p.nqb * a.H * a.B);
             if (g_attn_flags & 8192) {   // A/B: the older kernel (per-element scale and row sum in the vector pipe)

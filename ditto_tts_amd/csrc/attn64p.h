@@ -59,8 +59,10 @@ constexpr float SUM_RAISE_THR = 8192.0f;   // 2^13: a lane's 32 probabilities of
 // (P = the packed scores), bit 1 = no K/V DMA after the prologue (every ring slot holds a tile), bit 2 = no barrier / DMA wait in the
 // loop (with bit 1), bit 3 = no LDS fragment reads (Q fragments stand in), bit 4 = the exponentials replaced by adds, bit 7 = no MFMAs
 // the workgroup's whole job as a device function over a ring of NBUF x 16 KiB of LDS that is free on entry (attn64q.h runs it as
-// its exact path)
-template <bool RESID, int NBUF, int DIAG>
+// its exact path).  VARLEN: the utterance's own query / key lengths (p.q_len / p.kv_len) bound the rows; the padded Sq / Skv stay
+// the row strides.  A workgroup wholly past q_len exits before any load; key rows at or past kv_len are never read (clamped DMA,
+// masked scores in the last tile).
+template <bool RESID, int NBUF, int DIAG, bool VARLEN = false>
 DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
     static_assert(NBUF >= 2 && NBUF <= 4, "ring depth");
     constexpr int QWG = 256;                                      // queries per workgroup (p.nqb counts blocks of this size)
@@ -70,17 +72,19 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
     const int id = xcd_remap(bid, nwg);
     const int qb = id % p.nqb, bh = id / p.nqb;
     const int h = bh % p.H, b = bh / p.H;
+    const int sq = VARLEN ? attn_len(p.q_len, b, p.Sq) : p.Sq, skv = VARLEN ? attn_len(p.kv_len, b, p.Skv) : p.Skv;
+    if (VARLEN && qb * QWG >= sq) return;   // (workgroup-uniform)
     const int ql = lane & 31, hh = lane >> 5;
     int qrow[2];
     bool qvalid[2];
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
         qrow[x] = qb * QWG + wid * 64 + 32 * x + ql;
-        qvalid[x] = qrow[x] < p.Sq;
-        qrow[x] = qvalid[x] ? qrow[x] : p.Sq - 1;
+        qvalid[x] = qrow[x] < sq;
+        qrow[x] = qvalid[x] ? qrow[x] : sq - 1;
     }
-    const int nkt = (p.Skv + KBLK - 1) / KBLK;
-    const bool ragged = (p.Skv & (KBLK - 1)) != 0;
+    const int nkt = (skv + KBLK - 1) / KBLK;
+    const bool ragged = (skv & (KBLK - 1)) != 0;
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
     bf16x8 qf[2][4];   // Q^T B-operand fragments: lane holds Q[query ql of block x][d = 16 ks + 8 hh + 0..7]
     {
@@ -107,7 +111,7 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
                 const int piece = wid * 2 + i;
                 const int row = piece * 8 + (lane >> 3), cpos = lane & 7;
                 int key = kt * KBLK + row;
-                key = key < p.Skv ? key : p.Skv - 1;
+                key = key < skv ? key : skv - 1;
                 const int ck = cpos ^ ((row >> 1) & 7), cv = cpos ^ (((row >> 1) & 1) << 2);
                 glds16(p.k + ((size_t)b * p.Skv + key) * p.ldk + h * DH + ck * 8,
                        lds_base + (unsigned)(slot * 2 * KV_TILE_BYTES + piece * 1024));
@@ -211,7 +215,7 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int key = kbase_idx + kb2 * 32 + (r & 3) + 8 * (r >> 2);
-                            if (key >= p.Skv) st[x][kb2][r] = -1e30f;
+                            if (key >= skv) st[x][kb2][r] = -1e30f;
                         }
             }
         };
@@ -373,8 +377,8 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
     }
 }
 
-template <bool RESID, int NBUF = 4, int DIAG = 0>
+template <bool RESID, int NBUF = 4, int DIAG = 0, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn64p_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * KV_TILE_BYTES];  // [slot][K|V]
-    attn64p_body<RESID, NBUF, DIAG>(p, smem, threadIdx.x, blockIdx.x);
+    attn64p_body<RESID, NBUF, DIAG, VARLEN>(p, smem, threadIdx.x, blockIdx.x);
 }

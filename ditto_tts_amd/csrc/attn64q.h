@@ -51,6 +51,13 @@
 //
 // Contract: as attn64p, plus Skv >= 65 (at least two tiles; the last may be partial: its iteration is a second copy of the loop body
 // whose score chains start from -inf on the missing key rows); the launcher sends shorter key sequences to attn64p.
+//
+// VARLEN (with RAGGED): variable-length batches.  Every workgroup reads its own utterance's lengths (p.q_len / p.kv_len, clamped into
+// [1, Sq] / [1, Skv]); the padded Sq / Skv stay the row strides.  A workgroup wholly past q_len exits before any load; one whose
+// utterance has at most 64 keys runs attn64p's exact body instead (the same choice the launcher makes on the shape of a dense call);
+// the key loop runs ceil(kv_len / 64) tiles, the partial last one through the RAGGED copy, so a padded K / V row is never read
+// (0 * NaN = NaN in P V).  Query rows past q_len read row q_len - 1 instead, are not stored, and do not take part in the range check.
+// Every choice is a function of the workgroup's own lengths: an utterance's bits do not depend on its neighbours or on the padding.
 #pragma once
 
 constexpr int Q_QD = 4;   // fragments are requested this many slots ahead of their MFMA
@@ -68,7 +75,7 @@ template <int N, class F>
 DITTO_DEV void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 #endif
 
-template <bool RESID, int DIAG = 0, int QD = Q_QD, bool WRAP = true, int HOLD = Q_HOLD, bool RAGGED = false>
+template <bool RESID, int DIAG = 0, int QD = Q_QD, bool WRAP = true, int HOLD = Q_HOLD, bool RAGGED = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
     constexpr int NBUF = 4, QWG = 256;
     __shared__ __attribute__((aligned(16))) char smem[NBUF * 2 * KV_TILE_BYTES];  // [slot][K|V]
@@ -80,20 +87,29 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
     const int id = xcd_remap(blockIdx.x, nwg);
     const int qb = id % p.nqb, bh = id / p.nqb;
     const int h = bh % p.H, b = bh / p.H;
+    static_assert(!VARLEN || RAGGED, "a varlen key sequence may end anywhere");
+    const int sq = VARLEN ? attn_len(p.q_len, b, p.Sq) : p.Sq, skv = VARLEN ? attn_len(p.kv_len, b, p.Skv) : p.Skv;
+    if constexpr (VARLEN) {
+        if (qb * QWG >= sq) return;   // (workgroup-uniform: before any load)
+        if (skv <= KBLK) {            // one key tile: the exact body (attn64q needs two)
+            attn64p_body<RESID, NBUF, 0, true>(p, smem, threadIdx.x, blockIdx.x);
+            return;
+        }
+    }
     const int ql = lane & 31, hh = lane >> 5;
     int qrow[2];
     bool qvalid[2];
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
         qrow[x] = qb * QWG + wid * 64 + 32 * x + ql;
-        qvalid[x] = qrow[x] < p.Sq;
-        qrow[x] = qvalid[x] ? qrow[x] : p.Sq - 1;
+        qvalid[x] = qrow[x] < sq;
+        qrow[x] = qvalid[x] ? qrow[x] : sq - 1;
     }
-    const int nkt = (p.Skv + KBLK - 1) / KBLK;
+    const int nkt = (skv + KBLK - 1) / KBLK;
     // RAGGED instantiation: the last tile may be partial — its DMA rows are clamped, its scores start from -inf.  (Its own instantiation:
     // the second copy of the loop body raises the register pressure in front of the loop, and in the plain form that put a scratch
     // reload there whose vmcnt wait hipcc then keeps INSIDE the loop — a drain of the LDS-DMA pipeline per tile, 145 against 102 us.)
-    const bool ragged = RAGGED && (p.Skv % KBLK) != 0;
+    const bool ragged = RAGGED && (skv % KBLK) != 0;
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
     bf16x8 qf[2][4];
 #pragma unroll
@@ -118,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
                 const int piece = wid * 2 + i;
                 const int row = piece * 8 + (lane >> 3), cpos = lane & 7;
                 int key = kt * KBLK + row;
-                key = key < p.Skv ? key : p.Skv - 1;
+                key = key < skv ? key : skv - 1;
                 const int ck = cpos ^ ((row >> 1) & 7), cv = cpos ^ (((row >> 1) & 1) << 2);
                 glds16(p.k + ((size_t)b * p.Skv + key) * p.ldk + h * DH + ck * 8,
                        lds_base + (unsigned)(slot * 2 * KV_TILE_BYTES + piece * 1024));
@@ -261,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
         // pair steps, 32 registers that exist in this copy of the iteration only)
         f32x16 zmask[MASKED ? 2 : 1];
         if constexpr (MASKED) {
-            const int rem = p.Skv - (nkt - 1) * KBLK;
+            const int rem = skv - (nkt - 1) * KBLK;
 #pragma unroll
             for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
@@ -275,7 +291,7 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
                 for (int i = 0; i < 8; ++i) {
                     const int row = 8 * i + (lane >> 3);
                     int qr = qb * QWG + wid * 64 + row;
-                    qr = qr < p.Sq ? qr : p.Sq - 1;
+                    qr = qr < sq ? qr : sq - 1;
                     glds16(reinterpret_cast<const bf16*>(p.resid_in) + ((size_t)b * p.Sq + qr) * p.ldr + h * DH + (((lane & 7) ^ (row & 7)) << 3),
                            rdst + (unsigned)(i * 1024));
                 }
@@ -387,14 +403,14 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
             const float l = s0 + s1;
             // on the bits (positive floats order like their bit patterns; zero, negatives, inf and NaN fall outside): this file is
             // compiled with -fno-honor-nans, a float comparison may be folded into one that NaN passes
-            bad |= (__builtin_bit_cast(unsigned, l) - 0x0D800000u) > (0x71800000u - 0x0D800000u);   // 2^-100 .. 2^100
+            bad |= (!VARLEN || qvalid[x]) && (__builtin_bit_cast(unsigned, l) - 0x0D800000u) > (0x71800000u - 0x0D800000u);   // 2^-100 .. 2^100
             linv[x] = 1.0f / l;
         }
         if constexpr (!(DIAG & 31)) {
             if (__any(bad) && lane == 0) redo = 1;
             __syncthreads();
             if (redo) {
-                attn64p_body<RESID, NBUF, 0>(p, smem, threadIdx.x, blockIdx.x);
+                attn64p_body<RESID, NBUF, 0, VARLEN>(p, smem, threadIdx.x, blockIdx.x);
                 return;
             }
         }

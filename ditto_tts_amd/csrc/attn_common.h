@@ -21,10 +21,23 @@ struct AttnParams {
     // training forward (TRAIN instantiations only)
     float* lse;                    // [B, H, Sq] log2-domain log-sum-exp: m * scale_log2 + log2(l)
     unsigned drop_thr; float keep_scale; unsigned seed_lo, seed_hi; int layer;
+    // variable-length batches (VARLEN instantiations only): device int32 [B] valid query / key rows of each utterance, rows at or past
+    // them are padding (never read, never written).  nullptr: the whole padded length.  Appended last: the dense kernels' argument
+    // offsets stay where they were.
+    const int32_t* q_len = nullptr;
+    const int32_t* kv_len = nullptr;
 };
+
+// an utterance's valid length, clamped into [1, full] (a bad value cannot address out of bounds)
+DITTO_DEV int attn_len(const int32_t* len, int b, int full) {
+    if (!len) return full;
+    const int v = len[b];
+    return v < 1 ? 1 : (v > full ? full : v);
+}
 
 hipError_t launch_attention_train64(const AttnParams& p, bool resid, hipStream_t s);   // attention_train.hip
 hipError_t launch_attn64p(const AttnParams& p, bool resid, hipStream_t s, bool ring3 = false, int no_q = 0);   // attention_p.hip: 64 queries per wave (round 6: attn64p, attn64q)
+hipError_t launch_attn64p_varlen(const AttnParams& p, bool resid, hipStream_t s, bool exact_only);   // attention_varlen.hip: p.q_len / p.kv_len
 
 // the self-attention epilogue's stream update  h[row, col .. col+3] = h_in[...] + o  (src/components/DiT.py:139: no out-proj),
 // on an fp32 stream or a bf16 one (wave-uniform branch, outside every loop)

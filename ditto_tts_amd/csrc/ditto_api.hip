@@ -257,7 +257,8 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
                      void* attn_ws, size_t attn_ws_bytes, float* splitk_ws, size_t splitk_bytes, const char* kv, int kv_layer, int kv_ld,
                      const float* rope_cos, const float* rope_sin, int B, int N, int T, hipStream_t s,
                      float* tap_self = nullptr, float* tap_cross = nullptr, bool ln1_done = false,
-                     const float* next_g1 = nullptr, const float* next_be1 = nullptr, bool hb = false) {
+                     const float* next_g1 = nullptr, const float* next_be1 = nullptr, bool hb = false,
+                     const int32_t* speech_len = nullptr, const int32_t* text_len = nullptr) {
     const ditto_config& c = m->cfg;
     const int d = c.hidden_dim, H = c.num_heads, dh = d / H, M = B * N;
     const float scale = 1.0f / sqrtf((float)dh);
@@ -275,10 +276,18 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
     // also in the fp8 configuration, with the LayerNorm output written as fp8)
     const bool fr_out = lp.WcoP && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
     const bool fr_fc2 = !fp8 && lp.W2P && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
-    const int fr_rot = N % 128 == 0 ? N / 128 : 0;   // tiles per utterance: the K-loop rotation period (gemm_fr.hip)
+    // tiles per utterance: the K-loop rotation period (gemm_fr.hip).  A varlen batch runs unrotated (here and in gemm_lnq's): the
+    // rotation is a function of the PADDED N, and an utterance's bits must not depend on the padding
+    const bool varlen = speech_len || text_len;
+    const int fr_rot = !varlen && N % 128 == 0 ? N / 128 : 0;
     if (int rc = ditto::check_class_pin(M, d, fp8, !pad)) return rc;
     // hb: `h` holds BF16 rows (the bf16 residual stream; ditto_forward decides, and only where both fused launches run)
     if (hb && (!fr_out || !fr_fc2 || dh != 64 || tap_self || tap_cross)) return fail(DITTO_ERR_ARG, "internal: bf16 stream outside its class");
+    // variable-length batches: the attention kernels bound every utterance by its own lengths (attention_varlen.hip); every other
+    // launch is row-wise and computes the padding rows too (their results never reach a valid row)
+    if (varlen && (dh != 64 || pad)) {
+        return fail(DITTO_ERR_SHAPE, "variable-length batches need head_dim 64 (this model's is %d)", dh);
+    }
         // ---- self-attention (src/components/DiT.py:103-139) ----
         if (!ln1_done) {
             ProfScope ps(m, s, DITTO_KC_LAYERNORM);
@@ -332,6 +341,7 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             a.q = qkv; a.ldq = 3 * dp; a.k = qkv + (size_t)dp * 2; a.ldk = 3 * dp; a.v = qkv + (size_t)2 * dp * 2;
             a.ldv = 3 * dp; a.B = B; a.H = H; a.Sq = N; a.Skv = N; a.dh = dhp;
             a.scale = scale; a.workspace = attn_ws; a.workspace_bytes = attn_ws_bytes; a.q_prescaled = (dh == 64);
+            a.q_len = speech_len; a.kv_len = speech_len;
             if (pad) {   // O at the padded stride into `act` (free here), then h[:, hd dh + c] += O[:, hd dhp + c]
                 a.out_bf16 = act; a.ldo = dp;
                 HIP_TRY(launch_attention(a, s));
@@ -347,7 +357,7 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             ProfScope ps(m, s, DITTO_KC_GEMM_QPROJ);
             const int shape = d == 768 ? opt_lnq() : 32;
             HIP_TRY(launch_gemm_lnq(h, d, hb, lp.g2, lp.be2, shape == 16 ? lp.WcqP32 : lp.WcqP, lp.bcq, qkv, d, M, d, shape,
-                                    N % 64 == 0 ? N / 64 : 0, s));
+                                    !varlen && N % 64 == 0 ? N / 64 : 0, s));
         } else {
             {
                 ProfScope ps(m, s, DITTO_KC_LAYERNORM);
@@ -366,6 +376,7 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             a.v = kv + ((size_t)kv_layer * 2 * dp + dp) * 2; a.ldv = kv_ld; a.out_bf16 = u; a.ldo = dp;
             a.B = B; a.H = H; a.Sq = N; a.Skv = T; a.dh = dhp; a.scale = scale;
             a.workspace = attn_ws; a.workspace_bytes = attn_ws_bytes; a.q_prescaled = (dh == 64);
+            if (speech_len || text_len) { a.q_len = speech_len; a.kv_len = text_len; }
             HIP_TRY(launch_attention(a, s));
         }
         bool ln3_done = false;
@@ -641,8 +652,8 @@ int ditto_rope_tables(ditto_model_t m, int N, float* cos_out, float* sin_out, di
     return DITTO_OK;
 }
 
-int ditto_text_precompute(ditto_model_t m, const float* text, int B, int T, void* cond, size_t cond_bytes,
-                          void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+static int text_precompute(ditto_model_t m, const float* text, const int32_t* text_len, int B, int T, void* cond, size_t cond_bytes,
+                           void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
     if (!m || !text || !cond || !workspace || B <= 0 || T <= 0)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_text_precompute");
     const ditto_config& c = m->cfg;
@@ -662,8 +673,19 @@ int ditto_text_precompute(ditto_model_t m, const float* text, int B, int T, void
     g.A = textbf; g.lda = c.text_dim; g.W = m->Wkv; g.bias = m->bkv; g.out = kv; g.ldo = L * 2 * dp;
     g.M = B * T; g.N = L * 2 * dp; g.K = d;
     HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
-    if (!m->blocks_only) HIP_TRY(launch_text_mod(text, m->wx, m->bx, pooled, tmod, B, T, c.text_dim, d, s));
+    if (!m->blocks_only) HIP_TRY(launch_text_mod(text, m->wx, m->bx, pooled, tmod, B, T, c.text_dim, d, s, text_len));
     return DITTO_OK;
+}
+
+int ditto_text_precompute(ditto_model_t m, const float* text, int B, int T, void* cond, size_t cond_bytes,
+                          void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+    return text_precompute(m, text, nullptr, B, T, cond, cond_bytes, workspace, workspace_bytes, stream);
+}
+
+int ditto_text_precompute_varlen(ditto_model_t m, const float* text, const int32_t* text_len, int B, int T, void* cond,
+                                 size_t cond_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+    if (!text_len) return fail(DITTO_ERR_ARG, "ditto_text_precompute_varlen: null text_len");
+    return text_precompute(m, text, text_len, B, T, cond, cond_bytes, workspace, workspace_bytes, stream);
 }
 
 // thread-scoped options: the stack of what ditto_call_opts_push found in force (kernels.h t_opts is the top)
@@ -698,9 +720,9 @@ int ditto_forward_opts(ditto_model_t m, const float* x, const void* cond, const 
     return ditto_forward(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream);
 }
 
-int ditto_forward(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
-                  const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
-                  size_t workspace_bytes, ditto_stream_t stream) {
+static int forward_impl(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
+                        const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
+                        size_t workspace_bytes, ditto_stream_t stream, const int32_t* speech_len, const int32_t* text_len) {
     if (!m || !x || !cond || !t || !rope_cos || !rope_sin || !eps_out || !workspace || B <= 0 || N <= 0 || T <= 0)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_forward");
     const ditto_config& c = m->cfg;
@@ -753,7 +775,7 @@ int ditto_forward(ditto_model_t m, const float* x, const void* cond, const int64
                                L * 2 * cfg_dp(c), rope_cos, rope_sin, B, N, T, s, nullptr, nullptr,
                                ((chain_ln1 || chain_ll) && l > 0) || (ln1_in_adaln && l == 0),
                                (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].g1 : nullptr,
-                               (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].be1 : nullptr, hb))
+                               (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].be1 : nullptr, hb, speech_len, text_len))
             return rc;
     {   // eps = proj_in(x_raw) + proj_out(h_L)  (src/model/DiTTO.py:83,93-94), one K = 2d GEMM
         ProfScope ps(m, s, DITTO_KC_GEMM_FINAL);
@@ -770,7 +792,24 @@ int ditto_forward(ditto_model_t m, const float* x, const void* cond, const int64
             HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
         }
     }
+    if (speech_len) HIP_TRY(launch_zero_rows_past_len(eps_out, speech_len, B, N, d, s));   // eps rows >= N_b are exactly 0
     return DITTO_OK;
+}
+
+int ditto_forward(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
+                  const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
+                  size_t workspace_bytes, ditto_stream_t stream) {
+    return forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+int ditto_forward_varlen_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* speech_len,
+                              const int32_t* text_len, int B, int N, int T, const float* rope_cos, const float* rope_sin,
+                              float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                              const ditto_call_opts* opts) {
+    if (!speech_len || !text_len) return fail(DITTO_ERR_ARG, "ditto_forward_varlen_opts: null speech_len / text_len");
+    if (int rc = check_call_opts(opts)) return rc;
+    CallScope scope(opts);
+    return forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream, speech_len, text_len);
 }
 
 
@@ -894,6 +933,50 @@ int ditto_p_sample_seeded(ditto_model_t m, float* x, const void* cond, const int
     if (per % 4) return fail(DITTO_ERR_SHAPE, "elems_per_utt must be a multiple of 4");
     HIP_TRY(launch_p_sample_update_seeded(x, eps, seeds, step, t, betas, alphas, alphas_cumprod, B, per,
                                           (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_p_sample_seeded_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const int64_t* seeds,
+                                      const int32_t* speech_len, const int32_t* text_len, uint32_t step, const float* betas,
+                                      const float* alphas, const float* alphas_cumprod, int B, int N, int T, const float* rope_cos,
+                                      const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                                      const ditto_call_opts* opts) {
+    if (!m || !workspace || !seeds || !betas || !alphas || !alphas_cumprod || !speech_len || !text_len)
+        return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample_seeded_varlen_opts");
+    if (B <= 0 || N <= 0 || T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_p_sample_seeded_varlen_opts: B, N and T must be positive");
+    if (int rc = check_call_opts(opts)) return rc;
+    CallScope scope(opts);
+    const WsPlan w = plan_ws(m->cfg, B, N, T);
+    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    float* eps = (float*)((char*)workspace + w.eps);
+    if (int rc = forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
+        return rc;
+    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+    const size_t per = (size_t)N * m->cfg.hidden_dim;
+    // the noise of element i of an utterance is a function of (seed, step, i): in the padded layout i is the same row-major index as
+    // at the utterance's own length, so a varlen trajectory is comparable to the solo one; rows >= N_b of x then become 0
+    HIP_TRY(launch_p_sample_update_seeded(x, eps, seeds, step, t, betas, alphas, alphas_cumprod, B, per, (hipStream_t)stream));
+    HIP_TRY(launch_zero_rows_past_len(x, speech_len, B, N, m->cfg.hidden_dim, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_p_sample_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise,
+                               const int32_t* speech_len, const int32_t* text_len, const float* betas, const float* alphas,
+                               const float* alphas_cumprod, int B, int N, int T, const float* rope_cos, const float* rope_sin,
+                               void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    if (!m || !workspace || !betas || !alphas || !alphas_cumprod || !speech_len || !text_len)
+        return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample_varlen_opts");
+    if (B <= 0 || N <= 0 || T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_p_sample_varlen_opts: B, N and T must be positive");
+    if (int rc = check_call_opts(opts)) return rc;
+    CallScope scope(opts);
+    const WsPlan w = plan_ws(m->cfg, B, N, T);
+    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    float* eps = (float*)((char*)workspace + w.eps);
+    if (int rc = forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
+        return rc;
+    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+    HIP_TRY(launch_p_sample_update(x, eps, noise, t, betas, alphas, alphas_cumprod, B, (size_t)N * m->cfg.hidden_dim, (hipStream_t)stream));
+    HIP_TRY(launch_zero_rows_past_len(x, speech_len, B, N, m->cfg.hidden_dim, (hipStream_t)stream));
     return DITTO_OK;
 }
 
@@ -1061,6 +1144,43 @@ int ditto_attention_resid_bf16(const void* q, int ldq, const void* k, int ldk, c
     a.q_prescaled = (g_attn_flags & 16) && dh == 64;   // as ditto_attention_bf16
     HIP_TRY(launch_attention(a, (hipStream_t)stream));
     return DITTO_OK;
+}
+
+// variable-length batches: the fused head_dim-64 kernels' VARLEN instantiations (attn64q.h); q pre-scaled, no workspace
+static int attention_varlen(const char* fn, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out,
+                            int ldo, float* resid_out, const float* resid_in, int ldr, int resid_is_bf16, const int32_t* q_len,
+                            const int32_t* kv_len, int B, int H, int Sq, int Skv, int dh, ditto_stream_t stream) {
+    if (!q || !k || !v || !(out || resid_out)) return fail(DITTO_ERR_ARG, "%s: null pointer", fn);
+    if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0) return fail(DITTO_ERR_SHAPE, "%s: B, H, Sq and Skv must be positive", fn);
+    if (dh != 64) return fail(DITTO_ERR_SHAPE, "%s: variable-length attention needs head_dim 64", fn);
+    if ((ldq | ldk | ldv) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh)
+        return fail(DITTO_ERR_SHAPE, "%s: ldq / ldk / ldv must cover H * 64 columns in multiples of 8", fn);
+    if (out && (ldo % 8 || ldo < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldo must cover H * 64 columns in multiples of 8", fn);
+    if (resid_out && (ldr % 8 || ldr < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldr must cover H * 64 columns in multiples of 8", fn);
+    AttnArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out_bf16 = out; a.ldo = out ? ldo : 8;
+    a.resid_f32 = resid_out; a.ldr = ldr; a.resid_in = resid_in; a.resid_bf16 = resid_is_bf16 != 0;
+    a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.dh = dh; a.scale = 1.0f; a.q_prescaled = true;
+    if (!q_len && !kv_len) return fail(DITTO_ERR_ARG, "%s: q_len and kv_len are both NULL (the dense entry serves that)", fn);
+    a.q_len = q_len; a.kv_len = kv_len;
+    HIP_TRY(launch_attention(a, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_attention_varlen_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                const int32_t* q_len, const int32_t* kv_len, int B, int H, int Sq, int Skv, int dh,
+                                ditto_stream_t stream) {
+    if (!out) return fail(DITTO_ERR_ARG, "ditto_attention_varlen_bf16: null pointer");
+    return attention_varlen("ditto_attention_varlen_bf16", q, ldq, k, ldk, v, ldv, out, ldo, nullptr, nullptr, 0, 0, q_len,
+                            kv_len, B, H, Sq, Skv, dh, stream);
+}
+
+int ditto_attention_resid_varlen_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid_in,
+                                      void* resid_out, int ldr, int resid_is_bf16, const int32_t* q_len, const int32_t* kv_len,
+                                      int B, int H, int Sq, int Skv, int dh, ditto_stream_t stream) {
+    if (!resid_out) return fail(DITTO_ERR_ARG, "ditto_attention_resid_varlen_bf16: null pointer");
+    return attention_varlen("ditto_attention_resid_varlen_bf16", q, ldq, k, ldk, v, ldv, nullptr, 0, (float*)resid_out,
+                            (const float*)resid_in, ldr, resid_is_bf16, q_len, kv_len, B, H, Sq, Skv, dh, stream);
 }
 
 int ditto_vq_argmin(const float* latents, const float* codebook, int64_t* idx, int R, int K, int D, float* scratch_k,

@@ -50,7 +50,9 @@ hipError_t launch_time_table(const float* emb, const float* w0, const float* b0,
                              const float* wt, const float* bt, float* ttab, int steps, int td, int d, hipStream_t s);
 // pooled[b, :] = mean_T text[b, :, :]   then   tmod[b, 0:2d] = Wx * silu(pooled[b]) + bx
 hipError_t launch_text_mod(const float* text, const float* wx, const float* bx, float* pooled_scratch, float* tmod,
-                           int B, int T, int dt, int d, hipStream_t s);
+                           int B, int T, int dt, int d, hipStream_t s, const int32_t* text_len = nullptr);
+// variable-length batches: rows r >= len[b] of x [B, N, d] fp32 set to 0 (len device int32 [B], clamped into [1, N])
+hipError_t launch_zero_rows_past_len(float* x, const int32_t* len, int B, int N, int d, hipStream_t s);
 hipError_t launch_apply_rope_f32(const float* pos, const float* x, float* out, int B, int N, int H, int dh,
                                  hipStream_t s);
 hipError_t launch_rope_tables(const float* inv_freq, float* cos_out, float* sin_out, int N, int half, hipStream_t s);
@@ -256,6 +258,10 @@ struct AttnArgs {
     float* lse_out;                  // fused (dh == 64) path: fp32 [B, H, Sq] log2-domain log-sum-exp for the backward
     bool q_prescaled;                // q already multiplied by scale * log2(e) (packed weights, dh == 64): `scale` unused
     bool causal;                     // key j visible to query i only if j <= i + (Skv - Sq); GEMM-composed path only
+    // variable-length batch (fused head_dim-64 inference path with pre-scaled q only): device int32 [B] valid query / key rows per
+    // utterance, nullptr = the whole padded Sq / Skv.  Either set: the VARLEN instantiations of attn64q / attn64p.
+    const int32_t* q_len = nullptr;
+    const int32_t* kv_len = nullptr;
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 size_t attention_workspace_bytes(int B, int H, int Sq, int Skv, int dh);

@@ -566,18 +566,23 @@ hipError_t launch_time_table(const float* emb, const float* w0, const float* b0,
 // Text half of GlobalAdaLN, once per utterance batch (step-invariant):
 //   pooled = mean_T(text)  (no mask, src/components/DiT.py:27);  tmod = Linear(SiLU(pooled)) (:19-22,31)
 // ------------------------------------------------------------------------------------------------
+// VARLEN: the mean over the utterance's own T_b = text_len[b] rows (clamped into [1, T]) at the padded row stride T — the same
+// association as the dense kernel at T = T_b, so a varlen utterance pools exactly as it would alone
+template <bool VARLEN = false>
 __global__ __launch_bounds__(256) void text_pool_kernel(const float* __restrict__ text, float* __restrict__ pooled,
-                                                        int T, int dt) {
+                                                        int T, int dt, const int32_t* __restrict__ text_len = nullptr) {
     __shared__ float red[4][64];
     const int col = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6, b = blockIdx.y;
+    int Tb = T;
+    if constexpr (VARLEN) { const int v = text_len[b]; Tb = v < 1 ? 1 : (v > T ? T : v); }
     float acc = 0.f;
     if (col < dt)
-        for (int r = g; r < T; r += 4) acc += text[((size_t)b * T + r) * dt + col];
+        for (int r = g; r < Tb; r += 4) acc += text[((size_t)b * T + r) * dt + col];
     red[g][threadIdx.x & 63] = acc;
     __syncthreads();
     if (g == 0 && col < dt)
         pooled[(size_t)b * dt + col] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) +
-                                        (red[2][threadIdx.x] + red[3][threadIdx.x])) / (float)T;
+                                        (red[2][threadIdx.x] + red[3][threadIdx.x])) / (float)Tb;
 }
 // one wave per output row j of the [2d, dt] matrix
 __global__ __launch_bounds__(256) void text_mod_kernel(const float* __restrict__ pooled, const float* __restrict__ wx,
@@ -593,8 +598,9 @@ __global__ __launch_bounds__(256) void text_mod_kernel(const float* __restrict__
     if (lane == 0) tmod[(size_t)b * d2 + j] = acc + bx[j];
 }
 hipError_t launch_text_mod(const float* text, const float* wx, const float* bx, float* pooled, float* tmod, int B,
-                           int T, int dt, int d, hipStream_t s) {
-    hipLaunchKernelGGL(text_pool_kernel, dim3((dt + 63) / 64, B), dim3(256), 0, s, text, pooled, T, dt);
+                           int T, int dt, int d, hipStream_t s, const int32_t* text_len) {
+    if (text_len) hipLaunchKernelGGL(text_pool_kernel<true>, dim3((dt + 63) / 64, B), dim3(256), 0, s, text, pooled, T, dt, text_len);
+    else hipLaunchKernelGGL(text_pool_kernel<false>, dim3((dt + 63) / 64, B), dim3(256), 0, s, text, pooled, T, dt, nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(text_mod_kernel, dim3((2 * d + 3) / 4, B), dim3(256), 0, s, pooled, wx, bx, tmod, dt, 2 * d);
@@ -821,6 +827,24 @@ hipError_t launch_fill_i64(int64_t* dst, int n, int64_t value, hipStream_t s) {
 }
 hipError_t launch_add_vec(const float* a, const float* b, float* dst, int n, hipStream_t s) {
     hipLaunchKernelGGL(add_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, b, dst, n);
+    return hipGetLastError();
+}
+
+// variable-length batches: rows r >= len[b] (clamped into [1, N]) of utterance b of x [B, N, d] fp32 become 0 (d % 4 == 0)
+__global__ __launch_bounds__(256) void zero_rows_past_len_kernel(float* __restrict__ x, const int32_t* __restrict__ len, int N, int d) {
+    const int b = blockIdx.y;
+    const int v = len[b], nb = v < 1 ? 1 : (v > N ? N : v);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, n4 = (size_t)N * d / 4, start4 = (size_t)nb * d / 4;
+    if (i < n4 && i >= start4) {
+        f32x4 z;
+        z[0] = z[1] = z[2] = z[3] = 0.f;
+        *reinterpret_cast<f32x4*>(x + (size_t)b * N * d + 4 * i) = z;
+    }
+}
+hipError_t launch_zero_rows_past_len(float* x, const int32_t* len, int B, int N, int d, hipStream_t s) {
+    if (d % 4) return hipErrorInvalidValue;
+    const size_t n4 = (size_t)N * d / 4;
+    hipLaunchKernelGGL(zero_rows_past_len_kernel, dim3((unsigned)((n4 + 255) / 256), B), dim3(256), 0, s, x, len, N, d);
     return hipGetLastError();
 }
 

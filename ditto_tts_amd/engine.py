@@ -11,6 +11,7 @@ from typing import Dict, Mapping, Optional, Tuple
 import torch
 
 from . import hip
+from .varlen import validate_lengths
 from .config import DiTTOConfig
 
 
@@ -26,8 +27,10 @@ class TextCond:
     """Step-invariant conditioning of one utterance batch: cached cross-attention K/V of every layer and the
     text half of the AdaLN modulation (ditto_text_precompute)."""
 
-    def __init__(self, buf: torch.Tensor, B: int, T: int):
-        self.buf, self.B, self.T = buf, B, T
+    def __init__(self, buf: torch.Tensor, B: int, T: int, text_lengths: Optional[torch.Tensor] = None):
+        # text_lengths: device int32 [B] of a variable-length batch (ditto_text_precompute_varlen), carried with the K/V cache so
+        # that a forward cannot pair this conditioning with other lengths; None = every utterance has all T rows
+        self.buf, self.B, self.T, self.text_lengths = buf, B, T, text_lengths
 
 
 class StepGraph:
@@ -134,8 +137,9 @@ class DenoiseEngine:
             raise RuntimeError(f"{name} must be a CUDA (ROCm) tensor: ditto_tts_amd has no CPU path")
         return t.to(dtype=torch.float32).contiguous()
 
-    def prepare_text(self, text_emb: torch.Tensor, N_hint: int = 1) -> TextCond:
-        """text_emb [B, T, text_dim] -> TextCond (K/V cache of all layers + text modulation)."""
+    def prepare_text(self, text_emb: torch.Tensor, N_hint: int = 1, text_lengths=None) -> TextCond:
+        """text_emb [B, T, text_dim] -> TextCond (K/V cache of all layers + text modulation).  `text_lengths` (list / tuple /
+        int tensor [B]): a variable-length batch — utterance b's text is text_emb[b, :text_lengths[b]], the rest padding."""
         text = self._f32(text_emb, "text_emb")
         B, T, dt = text.shape
         if dt != self.cfg.text_dim:
@@ -143,15 +147,40 @@ class DenoiseEngine:
         nb = self.lib.ditto_cond_bytes(C.byref(self._ccfg), B, T)
         buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
         ws = self.workspace(B, max(N_hint, 1), T)
+        if text_lengths is not None:
+            self._require_varlen()
+            tl = validate_lengths(text_lengths, B, T, "text_lengths").to(self.device)
+            hip.check(self.lib.ditto_text_precompute_varlen(self.handle, text.data_ptr(), tl.data_ptr(), B, T, buf.data_ptr(), nb,
+                                                            ws.data_ptr(), ws.numel(), _stream()))
+            return TextCond(buf, B, T, tl)
         hip.check(self.lib.ditto_text_precompute(self.handle, text.data_ptr(), B, T, buf.data_ptr(), nb,
                                                  ws.data_ptr(), ws.numel(), _stream()))
         return TextCond(buf, B, T)
+
+    def _require_varlen(self):
+        if self.cfg.head_dim != 64:
+            raise NotImplementedError(f"variable-length batches need head_dim 64 (the fused attention kernels); this model's is "
+                                      f"{self.cfg.head_dim}")
+        if getattr(self.cfg, "fp8_linear", False):
+            raise NotImplementedError("variable-length batches are not supported with fp8_linear=True")
+
+    def _lengths(self, speech_lengths, cond: TextCond, B: int, N: int):
+        """(speech, text) device int32 [B] of a varlen call, or None for a dense one"""
+        if speech_lengths is None and cond.text_lengths is None:
+            return None
+        self._require_varlen()
+        sl = (validate_lengths(speech_lengths, B, N, "speech_lengths").to(self.device) if speech_lengths is not None
+              else torch.full((B,), N, dtype=torch.int32, device=self.device))
+        tl = cond.text_lengths if cond.text_lengths is not None else torch.full((B,), cond.T, dtype=torch.int32, device=self.device)
+        return sl, tl
 
     def prepare_text_into(self, text_emb: torch.Tensor, N_hint: int, cond: TextCond) -> TextCond:
         """Recompute the conditioning of a new utterance batch into an EXISTING TextCond buffer (same B, T), so
         captured graphs bound to that buffer stay valid."""
         text = self._f32(text_emb, "text_emb")
         B, T, _ = text.shape
+        if cond.text_lengths is not None:
+            raise NotImplementedError("prepare_text_into on a variable-length conditioning: call prepare_text(..., text_lengths=)")
         if (B, T) != (cond.B, cond.T):
             raise ValueError("prepare_text_into needs the same (B, T) as the existing conditioning")
         ws = self.workspace(B, max(N_hint, 1), T)
@@ -175,9 +204,10 @@ class DenoiseEngine:
             hip.check(getattr(self.lib, name)(*args))
 
     def forward(self, x: torch.Tensor, cond: TextCond, t: torch.Tensor, out: Optional[torch.Tensor] = None,
-                opts: Optional[hip.CallOpts] = None):
+                opts: Optional[hip.CallOpts] = None, speech_lengths=None):
         """DiTTO.forward(x, text_emb, t) with text_emb pre-digested into `cond` -> eps fp32 [B,N,d].  `opts`: this call's
-        hip.CallOpts (kernel class pin, residual-stream type ...: include/ditto_hip.h ditto_call_opts)."""
+        hip.CallOpts (kernel class pin, residual-stream type ...: include/ditto_hip.h ditto_call_opts).  `speech_lengths` (or a
+        `cond` with text lengths): a variable-length batch; eps rows past an utterance's length are 0."""
         xf = self._f32(x, "x")
         B, N, d = xf.shape
         if d != self.cfg.hidden_dim or B != cond.B:
@@ -187,6 +217,13 @@ class DenoiseEngine:
             out = torch.empty_like(xf)
         ws = self.workspace(B, N, cond.T)
         c, s = self.rope_tables(N)
+        lens = self._lengths(speech_lengths, cond, B, N)
+        if lens is not None:
+            hip.check(self.lib.ditto_forward_varlen_opts(self.handle, xf.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(),
+                                                         lens[0].data_ptr(), lens[1].data_ptr(), B, N, cond.T, c.data_ptr(),
+                                                         s.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+                                                         None if opts is None else C.byref(opts)))
+            return out
         self._call("ditto_forward", self.handle, xf.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), B, N, cond.T,
                                               c.data_ptr(), s.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                               _stream(), opts=opts)
@@ -194,8 +231,8 @@ class DenoiseEngine:
 
     def p_sample_(self, x: torch.Tensor, cond: TextCond, t: torch.Tensor, noise: Optional[torch.Tensor],
                   betas: torch.Tensor, alphas: torch.Tensor, alphas_cumprod: torch.Tensor,
-                  opts: Optional[hip.CallOpts] = None):
-        """One reverse-diffusion step IN PLACE on the fp32 CUDA state x [B,N,d]."""
+                  opts: Optional[hip.CallOpts] = None, speech_lengths=None):
+        """One reverse-diffusion step IN PLACE on the fp32 CUDA state x [B,N,d] (varlen: rows past a length become 0)."""
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
             raise ValueError("p_sample_ needs a contiguous fp32 CUDA state tensor (it is updated in place)")
         B, N, d = x.shape
@@ -204,6 +241,13 @@ class DenoiseEngine:
         c, s = self.rope_tables(N)
         if noise is not None:
             noise = self._f32(noise, "noise")
+        lens = self._lengths(speech_lengths, cond, B, N)
+        if lens is not None:
+            hip.check(self.lib.ditto_p_sample_varlen_opts(self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), _ptr(noise),
+                                                          lens[0].data_ptr(), lens[1].data_ptr(), betas.data_ptr(), alphas.data_ptr(),
+                                                          alphas_cumprod.data_ptr(), B, N, cond.T, c.data_ptr(), s.data_ptr(),
+                                                          ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+            return x
         self._call("ditto_p_sample", self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), _ptr(noise),
                                                betas.data_ptr(), alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T,
                                                c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), opts=opts)
@@ -222,7 +266,7 @@ class DenoiseEngine:
 
     def p_sample_seeded_(self, x: torch.Tensor, cond: TextCond, t: torch.Tensor, seeds: torch.Tensor, step: int,
                          betas: torch.Tensor, alphas: torch.Tensor, alphas_cumprod: torch.Tensor,
-                         opts: Optional[hip.CallOpts] = None):
+                         opts: Optional[hip.CallOpts] = None, speech_lengths=None):
         """p_sample_ with the step's noise generated inside the update kernel from per-utterance seeds
         (bit-identical to noise_normal_(z, seeds, step) + p_sample_(x, ..., z))."""
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
@@ -231,6 +275,13 @@ class DenoiseEngine:
         tt, sd = self._t64(t, B), self._t64(seeds, B)
         ws = self.workspace(B, N, cond.T)
         c, s = self.rope_tables(N)
+        lens = self._lengths(speech_lengths, cond, B, N)
+        if lens is not None:
+            hip.check(self.lib.ditto_p_sample_seeded_varlen_opts(
+                self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), sd.data_ptr(), lens[0].data_ptr(), lens[1].data_ptr(),
+                int(step) & 0xFFFFFFFF, betas.data_ptr(), alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T, c.data_ptr(),
+                s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+            return x
         self._call("ditto_p_sample_seeded", self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(),
                                                       sd.data_ptr(), int(step) & 0xFFFFFFFF, betas.data_ptr(),
                                                       alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T, c.data_ptr(),

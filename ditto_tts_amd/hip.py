@@ -154,6 +154,15 @@ SYMBOLS = {
     "ditto_attention_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "ditto_attention_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ditto_attention_resid_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    # variable-length batches (per-utterance q / kv lengths, device int32 [B]; q pre-scaled, head_dim 64)
+    "ditto_text_precompute_varlen": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "ditto_forward_varlen_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_p_sample_varlen_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp,
+                                        C.POINTER(CallOpts)]),
+    "ditto_p_sample_seeded_varlen_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp,
+                                               _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_attention_varlen_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_attention_resid_varlen_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ditto_vq_argmin": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ditto_embedding_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "ditto_code_embed_mean": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -247,6 +256,11 @@ def get_option(name: str) -> int:
     v = C.c_int(0)
     check(lib().ditto_get_option(name.encode(), C.byref(v)))
     return int(v.value)
+
+
+def has_varlen() -> bool:
+    """Does the loaded library have the variable-length entry points (detected by symbol, as the call options are)?"""
+    return hasattr(lib(), "ditto_attention_varlen_bf16")
 
 
 def _has_call_opts() -> bool:

@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
+from .varlen import validate_lengths
 from .config import DiTTOConfig
 from .engine import DenoiseEngine, TextCond, _stream
 from .synth import cosine_betas
@@ -319,13 +320,15 @@ class DiTTO(nn.Module):
         (src/utils/Trainer.py:16 trains on one device); this is the hook a multi-GPU Trainer would use."""
         self._grad_sync, self._grad_sync_layers = sync, int(layers_per_piece)
 
-    def text_cond(self, text_emb: torch.Tensor, N_hint: int = 1) -> TextCond:
+    def text_cond(self, text_emb: torch.Tensor, N_hint: int = 1, text_lengths=None) -> TextCond:
         """Step-invariant text work, cached while the caller keeps passing the same text_emb tensor (the
-        sampler does for all its steps, reference src/model/SpeechGenerator.py:161-163)."""
+        sampler does for all its steps, reference src/model/SpeechGenerator.py:161-163) and the same text lengths."""
         eng = self.engine()
-        key = (text_emb.data_ptr(), text_emb._version, tuple(text_emb.shape), text_emb.dtype, text_emb.device)
+        tl = None if text_lengths is None else tuple(validate_lengths(text_lengths, text_emb.shape[0], text_emb.shape[1],
+                                                                      "text_lengths").tolist())
+        key = (text_emb.data_ptr(), text_emb._version, tuple(text_emb.shape), text_emb.dtype, text_emb.device, tl)
         if key != self._cond_key or self._cond is None:
-            self._cond = eng.prepare_text(text_emb, N_hint)
+            self._cond = eng.prepare_text(text_emb, N_hint, text_lengths=None if tl is None else list(tl))
             self._cond_key = key
             # the entry is keyed by ADDRESS: keep the keyed tensor alive for as long as the entry is, or the caching
             # allocator hands the same address (version 0, same shape) to the next utterance's temporary
@@ -343,10 +346,22 @@ class DiTTO(nn.Module):
         self._cond_src = None
 
     # ------------------------------------------------------------------ reference surface
-    def forward(self, x, text_emb, t):
+    def forward(self, x, text_emb, t, *, speech_lengths=None, text_lengths=None):
         """x [B,N,d] noisy latents, text_emb [B,T,text_dim], t [B] long -> predicted noise [B,N,d]
-        (reference src/model/DiTTO.py:66-94)."""
+        (reference src/model/DiTTO.py:66-94).  `speech_lengths` / `text_lengths` (list, tuple or int tensor [B]): a
+        variable-length batch in the padded layout — utterance b is x[b, :speech_lengths[b]] with text_emb[b, :text_lengths[b]];
+        eps rows past its length are 0, and padding contents never reach a valid row (inference only, head_dim 64)."""
         _require_cuda(x, "x")
+        varlen = speech_lengths is not None or text_lengths is not None
+        if varlen:
+            if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad or
+                                            any(p.requires_grad for n, p in self.named_parameters() if not n.startswith("nac."))):
+                raise NotImplementedError("ditto_tts_amd: variable-length batches are inference only (run under torch.no_grad() "
+                                          "or with frozen parameters)")
+            eng = self.engine(x.device)
+            cond = self.text_cond(text_emb.to(x.device), x.shape[1], text_lengths=text_lengths)
+            out = eng.forward(x, cond, t, speech_lengths=speech_lengths)
+            return out if x.dtype == torch.float32 else out.to(x.dtype)
         if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad):
             raise NotImplementedError("ditto_tts_amd: gradients with respect to x / text_emb are not produced (the "
                                       "reference feeds frozen-encoder outputs, src/TrainDiTTO.py:66-73); detach them")

@@ -114,7 +114,8 @@ class SpeechGenerator:
 
     @torch.no_grad()
     def __sample_latents(self, text_emb, audio_emb, text_prompt=None, audio=None, is_slp=False, cond_by_audio=False,
-                         noises=None, keep=None, use_graph=None, seeds=None, batch_class=None):
+                         noises=None, keep=None, use_graph=None, seeds=None, batch_class=None, speech_lengths=None,
+                         text_lengths=None):
         """All reverse diffusion steps (reference :149-164).
 
         `noises` (optional): a sequence / callable giving the z of executed step i, for parity tests;
@@ -138,6 +139,11 @@ class SpeechGenerator:
         m = self.ditto_model
         if seeds is not None and (noises is not None or use_graph):
             raise ValueError("seeds= excludes noises= and use_graph=")
+        varlen = speech_lengths is not None or text_lengths is not None
+        if varlen and use_graph:
+            raise NotImplementedError("variable-length batches are not captured into a step graph (use_graph=False)")
+        if varlen and cond_by_audio:
+            raise NotImplementedError("variable-length batches start from noise (cond_by_audio=False)")
         if seeds is not None and not cond_by_audio:
             x = torch.empty(audio_emb.shape, dtype=torch.float32, device=self.device)
             seeds = seeds.to(self.device).long().contiguous()
@@ -148,8 +154,12 @@ class SpeechGenerator:
             if seeds is not None:
                 seeds = seeds.to(self.device).long().contiguous()
         eng = m.engine(x.device)
-        cond = m.text_cond(text_emb.to(x.device), x.shape[1])
+        cond = m.text_cond(text_emb.to(x.device), x.shape[1], text_lengths=text_lengths)
         B = x.shape[0]
+        if varlen:   # (validated once here; every step passes the same device lengths)
+            from .varlen import validate_lengths
+            speech_lengths = validate_lengths(speech_lengths if speech_lengths is not None else [x.shape[1]] * B, B, x.shape[1],
+                                              "speech_lengths").to(x.device)
         t_tensor = torch.empty(B, device=x.device, dtype=torch.long)
         use_graph = bool(use_graph)
         z = torch.empty_like(x)
@@ -158,9 +168,9 @@ class SpeechGenerator:
         if batch_class is not None:                 # every step of the loop is CALLED with the unsplit batch's kernel class: a
             from .hip import CallOpts               # per-call argument (ditto_call_opts), nothing process-wide changes
             opts = CallOpts(class_rows=int(batch_class) * x.shape[1])
-        return self.__loop(x, cond, t_tensor, z, use_graph, n_loop, seeds, noises, keep, eng, opts)
+        return self.__loop(x, cond, t_tensor, z, use_graph, n_loop, seeds, noises, keep, eng, opts, speech_lengths)
 
-    def __loop(self, x, cond, t_tensor, z, use_graph, n_loop, seeds, noises, keep, eng, opts=None):
+    def __loop(self, x, cond, t_tensor, z, use_graph, n_loop, seeds, noises, keep, eng, opts=None, speech_lengths=None):
         graph = None
         if use_graph:
             t_tensor.fill_(n_loop - 1)
@@ -171,7 +181,8 @@ class SpeechGenerator:
         for i, t_val in enumerate(reversed(range(n_loop))):
             t_tensor.fill_(t_val)
             if seeds is not None:
-                eng.p_sample_seeded_(x, cond, t_tensor, seeds, t_val, self.betas, self.alphas, self.alphas_cumprod, opts=opts)
+                eng.p_sample_seeded_(x, cond, t_tensor, seeds, t_val, self.betas, self.alphas, self.alphas_cumprod, opts=opts,
+                                     speech_lengths=speech_lengths)
                 if keep is not None and i in keep:
                     keep[i] = x.clone()
                 continue
@@ -182,7 +193,8 @@ class SpeechGenerator:
             if graph is not None:
                 graph.replay()
             else:
-                eng.p_sample_(x, cond, t_tensor, z, self.betas, self.alphas, self.alphas_cumprod, opts=opts)
+                eng.p_sample_(x, cond, t_tensor, z, self.betas, self.alphas, self.alphas_cumprod, opts=opts,
+                              speech_lengths=speech_lengths)
             if keep is not None and i in keep:
                 keep[i] = x.clone()
         return x
@@ -190,12 +202,15 @@ class SpeechGenerator:
     # ---------------------------------------------------------------- strided (DDIM) loop + CFG  
     @torch.no_grad()
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
-                               cond_by_audio=False, noises=None):
+                               cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
         DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step
         (ditto_linear_update), with optional classifier-free guidance: the step runs ONE forward on the doubled
         batch [x; x] x [text; null_text] and combines eps_u + w (eps_c - eps_u) (ditto_cfg_combine)."""
         from .around import cfg_combine, linear_update_
+        if speech_lengths is not None or text_lengths is not None:
+            raise NotImplementedError("variable-length batches run the ancestral loop only (sample_latents); the strided / CFG "
+                                      "sampler has no varlen form")
         m = self.ditto_model
         T = self.diffusion_steps
         if not 1 <= n_steps <= T:

@@ -1,0 +1,104 @@
+"""Variable-length batches: per-utterance query / key lengths in the padded layout (include/ditto_hip.h, the *_varlen_* entries).
+
+Utterance b owns rows [0, len[b]) of its padded [Sq] / [Skv] block; the rows past them are padding, never read and never written.
+The library takes the lengths as device int32 [B] and cannot check them without a sync, so they are validated here, on the host,
+before they go to the device.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import hip
+
+
+def validate_lengths(lengths, B: int, maxlen: int, name: str = "lengths") -> torch.Tensor:
+    """`lengths` (list / tuple of ints, or an integer tensor on any device) as a CPU int32 tensor of shape [B], every value in
+    [1, maxlen].  Anything else raises ValueError."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+            raise ValueError(f"{name}: an integer tensor is needed, got {lengths.dtype}")
+        t = lengths.detach().to("cpu", torch.int64)
+    elif isinstance(lengths, (list, tuple)):
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in lengths):
+            raise ValueError(f"{name}: a list / tuple of ints is needed")
+        t = torch.tensor(list(lengths), dtype=torch.int64)
+    else:
+        raise ValueError(f"{name}: a list, tuple or integer tensor is needed, got {type(lengths).__name__}")
+    if t.dim() != 1 or t.shape[0] != B:
+        raise ValueError(f"{name}: shape [{B}] expected, got {list(t.shape)}")
+    if B and (int(t.min()) < 1 or int(t.max()) > maxlen):
+        raise ValueError(f"{name}: every length must lie in [1, {maxlen}], got [{int(t.min())}, {int(t.max())}]")
+    return t.to(torch.int32)
+
+
+def _dev_lengths(lengths, B, maxlen, name, device):
+    if lengths is None:
+        return None
+    return validate_lengths(lengths, B, maxlen, name).to(device)
+
+
+def _check_qkv(q, k, v, H):
+    for n, x in (("q", q), ("k", k), ("v", v)):
+        if x.dtype != torch.bfloat16 or x.dim() != 3 or not x.is_cuda or x.stride(2) != 1 or x.stride(0) != x.shape[1] * x.stride(1):
+            raise ValueError(f"{n}: a bf16 [B, S, H * 64] tensor on the GPU with unit column stride is needed")
+        if x.shape[2] < H * 64:
+            raise ValueError(f"{n}: {x.shape[2]} columns do not hold {H} heads of 64")
+
+
+def _check_batch(q, k, v, H):
+    """q [B, Sq, .], k / v [B, Skv, .]: the kernels address all three with q's B and k's Skv"""
+    if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0] or v.shape[1] != k.shape[1]:
+        raise ValueError(f"q {list(q.shape)}, k {list(k.shape)}, v {list(v.shape)}: k and v need q's batch and one common length")
+    if not (q.device == k.device == v.device):
+        raise ValueError("q, k and v must be on one device")
+
+
+def _check_out(t, name, B, Sq, H, dtypes, device):
+    if (t.dtype not in dtypes or t.device != device or t.dim() != 3 or t.shape[0] != B or t.shape[1] != Sq or t.shape[2] < H * 64
+            or t.stride(2) != 1 or t.stride(0) != Sq * t.stride(1)):
+        raise ValueError(f"{name}: a {' / '.join(str(d) for d in dtypes)} [{B}, {Sq}, >= {H * 64}] tensor with unit column stride on "
+                         f"{device} is needed, got {t.dtype} {list(t.shape)} on {t.device}")
+
+
+def attention(q, k, v, H: int, q_len=None, kv_len=None, out=None):
+    """softmax(q k^T) v per (utterance, head) over each utterance's own rows (q carries scale * log2(e)); q / out [B, Sq, >= H*64],
+    k / v [B, Skv, >= H*64], bf16.  Rows of `out` past q_len are left as they were.  Returns `out`."""
+    _check_qkv(q, k, v, H)
+    _check_batch(q, k, v, H)
+    B, Sq, Skv = q.shape[0], q.shape[1], k.shape[1]
+    if q_len is None and kv_len is None:
+        raise ValueError("q_len and kv_len are both None: the dense attention serves that")
+    if out is not None:
+        _check_out(out, "out", B, Sq, H, (torch.bfloat16,), q.device)
+    ql = _dev_lengths(q_len, B, Sq, "q_len", q.device)
+    kl = _dev_lengths(kv_len, B, Skv, "kv_len", q.device)
+    if out is None:
+        out = torch.zeros(B, Sq, H * 64, dtype=torch.bfloat16, device=q.device)
+    hip.check(hip.lib().ditto_attention_varlen_bf16(
+        q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(1), out.data_ptr(), out.stride(1),
+        ql.data_ptr() if ql is not None else None, kl.data_ptr() if kl is not None else None, B, H, Sq, Skv, 64,
+        torch.cuda.current_stream(q.device).cuda_stream))
+    return out
+
+
+def attention_resid(q, k, v, H: int, resid, q_len=None, kv_len=None, resid_in=None):
+    """The residual form: resid[b, i, h*64 + c] = resid_in[...] + attention, for i < q_len[b] (resid_in None: in place); resid
+    is fp32 or bf16 [B, Sq, >= H*64].  Rows past q_len are left untouched.  Returns `resid`."""
+    _check_qkv(q, k, v, H)
+    _check_batch(q, k, v, H)
+    B, Sq, Skv = q.shape[0], q.shape[1], k.shape[1]
+    if q_len is None and kv_len is None:
+        raise ValueError("q_len and kv_len are both None: the dense attention serves that")
+    src = resid if resid_in is None else resid_in
+    _check_out(resid, "resid", B, Sq, H, (torch.float32, torch.bfloat16), q.device)
+    _check_out(src, "resid_in", B, Sq, H, (resid.dtype,), q.device)
+    if (resid.dtype not in (torch.float32, torch.bfloat16) or src.dtype != resid.dtype or src.stride() != resid.stride()
+            or resid.stride(2) != 1 or resid.stride(0) != Sq * resid.stride(1)):
+        raise ValueError("resid / resid_in: fp32 or bf16 with the same dtype and row stride")
+    ql = _dev_lengths(q_len, B, Sq, "q_len", q.device)
+    kl = _dev_lengths(kv_len, B, Skv, "kv_len", q.device)
+    hip.check(hip.lib().ditto_attention_resid_varlen_bf16(
+        q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(1), src.data_ptr(), resid.data_ptr(),
+        resid.stride(1), int(resid.dtype == torch.bfloat16), ql.data_ptr() if ql is not None else None,
+        kl.data_ptr() if kl is not None else None, B, H, Sq, Skv, 64, torch.cuda.current_stream(q.device).cuda_stream))
+    return resid

@@ -156,6 +156,19 @@ int ditto_forward(ditto_model_t m, const float* x, const void* cond, const int64
 int ditto_forward_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
                        const float* rope_cos, const float* rope_sin, float* eps_out,
                        void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+/* Variable-length batches (padded layout): utterance b is x[b, :speech_len[b]] and text[b, :text_len[b]]; the rows past them are
+ * padding, whose contents (NaN / Inf included) never reach a valid row.  speech_len / text_len: DEVICE int32 [B], non-NULL.
+ * Precondition (not checked: that would need a sync): 1 <= speech_len[b] <= N, 1 <= text_len[b] <= T; the kernels clamp into that
+ * range, so a bad value gives wrong rows but never an out-of-bounds access.  head_dim 64 only (DITTO_ERR_SHAPE otherwise).
+ * ditto_text_precompute_varlen: the text mean-pool of GlobalAdaLN over the utterance's own T_b rows (the same association as
+ * the dense kernel at T = T_b).  ditto_forward_varlen_opts: `cond` from ditto_text_precompute_varlen with the same text_len;
+ * eps rows >= speech_len[b] are written 0 (one extra launch).  Every other launch is row-wise and also computes the padding rows. */
+int ditto_text_precompute_varlen(ditto_model_t m, const float* text, const int32_t* text_len, int B, int T, void* cond,
+                                 size_t cond_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream);
+int ditto_forward_varlen_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* speech_len,
+                              const int32_t* text_len, int B, int N, int T, const float* rope_cos, const float* rope_sin,
+                              float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                              const ditto_call_opts* opts);
 /* Thread-scoped form for every other entry point (ditto_block_forward*, the unit-test kernels, a caller's own helper that
  * makes several calls): `opts` are in force for the calls THIS THREAD makes until the matching pop.  Nests (depth <= 16);
  * fields at -1 inherit the enclosing scope.  ditto_call_opts_pop without a push is an error. */
@@ -243,6 +256,19 @@ int ditto_p_sample_seeded_opts(ditto_model_t m, float* x, const void* cond, cons
                                uint32_t step, const float* betas, const float* alphas, const float* alphas_cumprod, int B,
                                int N, int T, const float* rope_cos, const float* rope_sin, void* workspace,
                                size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+/* ditto_p_sample_opts over a variable-length batch (the sampler's noises= path): rows >= speech_len[b] of x are written 0 */
+int ditto_p_sample_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise,
+                               const int32_t* speech_len, const int32_t* text_len, const float* betas, const float* alphas,
+                               const float* alphas_cumprod, int B, int N, int T, const float* rope_cos, const float* rope_sin,
+                               void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+/* ditto_p_sample_seeded over a variable-length batch (lengths as ditto_forward_varlen_opts): the seeded update keeps the element
+ * index of the padded layout (row-major within the utterance: the index it has at the utterance's own length), and rows
+ * >= speech_len[b] of x are written 0 (one extra launch). */
+int ditto_p_sample_seeded_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const int64_t* seeds,
+                                      const int32_t* speech_len, const int32_t* text_len, uint32_t step, const float* betas,
+                                      const float* alphas, const float* alphas_cumprod, int B, int N, int T, const float* rope_cos,
+                                      const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                                      const ditto_call_opts* opts);
 
 /* DiTTO.q_sample (src/model/DiTTO.py:106-126), bug-for-bug: `buffer` is the module's
  * `alphas_cumprod` buffer, which holds clipped betas.  out may alias x_start. */
@@ -280,6 +306,22 @@ size_t ditto_attention_workspace_bytes(int B, int H, int Sq, int Skv, int dh);
 int ditto_attention_resid_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid_in,
                                void* resid_out, int ldr, int resid_is_bf16, int B, int H, int Sq, int Skv, int dh, float scale,
                                void* workspace, size_t workspace_bytes, ditto_stream_t stream);
+
+/* Variable-length batches (padded layout): utterance b owns query rows [b*Sq, b*Sq + q_len[b]) and key / value rows
+ * [b*Skv, b*Skv + kv_len[b]); the rows past them are padding — never read (NaN / Inf there reach nothing) and never written.
+ * q_len / kv_len: DEVICE int32 [B], either may be NULL (= the whole padded Sq / Skv), not both.  Precondition (the library cannot
+ * read device memory without a sync): 1 <= q_len[b] <= Sq and 1 <= kv_len[b] <= Skv; the kernels clamp into that range, so a bad
+ * value gives wrong rows but never an out-of-bounds access.  head_dim 64 only; q carries scale * log2(e) (the model's packed q:
+ * attn_flags 16 of the dense entries is implied); row strides are multiples of 8 elements.  The dense entries' dispatch is not
+ * used: every varlen launch runs attn64q (attn64p's exact body for an utterance of <= 64 keys; attn_flags 1048576: attn64p alone),
+ * and an utterance's bits depend only on its own rows and lengths. */
+int ditto_attention_varlen_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                const int32_t* q_len, const int32_t* kv_len, int B, int H, int Sq, int Skv, int dh,
+                                ditto_stream_t stream);
+/* the residual form (as ditto_attention_resid_bf16): stream rows past q_len[b] are left untouched */
+int ditto_attention_resid_varlen_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid_in,
+                                      void* resid_out, int ldr, int resid_is_bf16, const int32_t* q_len, const int32_t* kv_len,
+                                      int B, int H, int Sq, int Skv, int dh, ditto_stream_t stream);
 
 /* Full-row GEMM with the residual add and the FOLLOWING LayerNorm fused (N = 768: csrc/gemm_frd.hip, or its 64-row twin
  * csrc/gemm_fr64.hip under "fr_tile" 64 — 64 <= M < 128 always runs the 64-row twin, same fp32 bits;

@@ -8,14 +8,16 @@ of a VGPR and a vector read of it for its own instructions only, not for an asm 
 statement reads, the last MFMA that wrote it is found on every path into the statement (into the loop and round its back edge), and
 the wait states in between are counted: one per instruction, N + 1 per `s_nop N`.  v_mfma_f32_32x32x16_bf16 (8 passes) needs 12.
 The same counter is applied to hipcc's own vector reads of MFMA results: it must find none below 12, or the counting model is wrong.
-    python tools/check_attn_loop.py          (compiles into a private temporary directory; exit code 1 on a finding)"""
+    python tools/check_attn_loop.py          (compiles into a private temporary directory; exit code 1 on a finding)
+    python tools/check_attn_loop.py --varlen (the same checks on attention_varlen.hip: the VARLEN instantiations)"""
 import os, re, subprocess, sys, tempfile
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+src = "attention_varlen.hip" if "--varlen" in sys.argv[1:] else "attention_p.hip"
 tmp = tempfile.TemporaryDirectory()
 out = os.path.join(tmp.name, "check_attn_loop.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", root + "/include", "-I",
                        root + "/ditto_tts_amd/csrc", "-w", "-fno-honor-nans", "-fno-slp-vectorize", "-S", "--cuda-device-only",
-                       root + "/ditto_tts_amd/csrc/attention_p.hip", "-o", out])
+                       root + "/ditto_tts_amd/csrc/" + src, "-o", out])
 s = open(out).read()
 bad = 0
 for name in re.findall(r"^(_ZN\S*attn64[pq]_kernel\S+):", s, re.M):
@@ -27,7 +29,7 @@ for name in re.findall(r"^(_ZN\S*attn64[pq]_kernel\S+):", s, re.M):
         q = "attn64q" in name
         if q and (n not in (4, 28) or not b.count("v_exp") or b.count("v_exp") > 100):      # attn64q: the steady loop's two blocks (28 + 4 MFMAs)
             continue
-        if not q and (n != 16 or "Loop" not in b.split("\n")[0] or "Li0EEEv" not in name):   # attn64p: the 16-MFMA blocks of its tile loops (product instantiations)
+        if not q and (n != 16 or "Loop" not in b.split("\n")[0] or not re.search(r"Li0ELb[01]EEEv", name)):   # attn64p: the 16-MFMA blocks of its tile loops (product instantiations, dense and VARLEN)
             continue
         in_asm, waits = False, 0
         for l in b.split("\n"):
