@@ -72,6 +72,26 @@ def linear_update_(x, eps, noise, a, ce, cz):
     return x
 
 
+def guided_update_(x2, eps2, a, ce, cz, w=None, noise=None, seeds=None, step: int = 0, speech_len=None):
+    """The fused update of a guided strided step in place on x2 (ditto_guided_update): x2 / eps2 fp32 [2B, N, d] with w (fp32 [B]:
+    e = w (eps_c - eps_u) + eps_u), [B, N, d] without; x' = a x + ce e + cz z written to both halves; z from `noise` [B, N, d], from
+    Philox of `seeds` (int64 [B]) at tag `step`, or none.  speech_len: device int32 [B]; rows past it become 0 in both halves."""
+    _need_cuda(x2, "x2")
+    nb, N, d = x2.shape
+    B = nb // 2 if w is not None else nb
+    for name, t, shape in (("x2", x2, x2.shape), ("eps2", eps2, x2.shape), ("noise", noise, (B, N, d))):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == shape):
+            raise ValueError(f"{name}: a contiguous fp32 CUDA tensor of shape {tuple(shape)} is needed")
+    if w is not None and nb % 2:
+        raise ValueError("x2 of a guided update holds [conditional; unconditional]: an even number of utterances")
+    hip.check(hip.lib().ditto_guided_update(x2.data_ptr(), eps2.data_ptr(), None if noise is None else noise.data_ptr(),
+                                            None if seeds is None else seeds.data_ptr(), int(step) & 0xFFFFFFFF,
+                                            None if w is None else w.data_ptr(), a.data_ptr(), ce.data_ptr(), cz.data_ptr(),
+                                            None if speech_len is None else speech_len.data_ptr(), B, N, d, int(w is not None),
+                                            _stream()))
+    return x2
+
+
 def cfg_combine(eps2, w: float):
     """eps2 [2B, ...] = [conditional; unconditional] -> eps_u + w*(eps_c - eps_u), [B, ...]."""
     B2 = eps2.shape[0]

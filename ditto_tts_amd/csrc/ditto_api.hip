@@ -1224,6 +1224,51 @@ int ditto_cfg_combine(const float* eps2, float* out, float w, size_t elems_half,
     return DITTO_OK;
 }
 
+// guided strided step (guided.hip): every argument is checked here, before any launch
+static int check_guided_update(const char* who, const float* x2, const float* eps2, const float* noise, const int64_t* seeds,
+                               const float* w, const float* a, const float* ce, const float* cz, int B, int N, int d, int cfg) {
+    if (!x2 || !eps2) return fail(DITTO_ERR_ARG, "%s: null x2 / eps2", who);
+    if (noise && seeds) return fail(DITTO_ERR_ARG, "%s: noise and seeds are exclusive (a noise buffer, or Philox from seeds)", who);
+    if (cfg && !w) return fail(DITTO_ERR_ARG, "%s: classifier-free guidance needs w (fp32 [B])", who);
+    if (!a || !ce || ((noise || seeds) && !cz)) return fail(DITTO_ERR_ARG, "%s: null a / ce / cz", who);
+    if (B <= 0 || N <= 0 || d <= 0) return fail(DITTO_ERR_SHAPE, "%s: B, N and d must be positive (B %d, N %d, d %d)", who, B, N, d);
+    if (d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
+    if (B > 65535) return fail(DITTO_ERR_SHAPE, "%s: more than 65535 utterances", who);
+    return DITTO_OK;
+}
+
+int ditto_guided_update(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                        const float* a, const float* ce, const float* cz, const int32_t* speech_len, int B, int N, int d, int cfg,
+                        ditto_stream_t stream) {
+    if (int rc = check_guided_update("ditto_guided_update", x2, eps2, noise, seeds, w, a, ce, cz, B, N, d, cfg)) return rc;
+    HIP_TRY(launch_guided_update(x2, eps2, noise, seeds, step, w, a, ce, cz, speech_len, B, N, d, cfg != 0, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* speech_len,
+                           const int32_t* text_len, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                           const float* a, const float* ce, const float* cz, int B, int N, int T, int cfg, const float* rope_cos,
+                           const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                           const ditto_call_opts* opts) {
+    if (!m || !cond || !t || !rope_cos || !rope_sin || !workspace) return fail(DITTO_ERR_ARG, "bad argument to ditto_guided_step_opts");
+    if (!speech_len != !text_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_opts: speech_len and text_len are both given or both NULL");
+    if (T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_guided_step_opts: T must be positive");
+    if (int rc = check_guided_update("ditto_guided_step_opts", x2, x2, noise, seeds, w, a, ce, cz, B, N, m->cfg.hidden_dim, cfg))
+        return rc;
+    if (int rc = check_call_opts(opts)) return rc;
+    CallScope scope(opts);
+    const int nb = cfg ? 2 * B : B;                 // the forward runs over [x; x] x [text; null] under guidance
+    const WsPlan w_ = plan_ws(m->cfg, nb, N, T);
+    if (workspace_bytes < w_.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w_.total);
+    float* eps = (float*)((char*)workspace + w_.eps);
+    if (int rc = forward_impl(m, x2, cond, t, nb, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
+        return rc;
+    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+    HIP_TRY(launch_guided_update(x2, eps, noise, seeds, step, w, a, ce, cz, speech_len, B, N, m->cfg.hidden_dim, cfg != 0,
+                                 (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 int ditto_quantize_rows_fp8(const float* src, int rows, int cols, void* dst_fp8, float* scales, ditto_stream_t stream) {
     if (!src || !dst_fp8 || !scales || rows <= 0 || cols <= 0) return fail(DITTO_ERR_ARG, "bad argument to ditto_quantize_rows_fp8");
     if (cols % 4) return fail(DITTO_ERR_SHAPE, "cols must be a multiple of 4");

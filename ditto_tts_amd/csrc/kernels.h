@@ -239,6 +239,10 @@ hipError_t launch_code_embed_mean(const float* table, const int64_t* codes, floa
 hipError_t launch_linear_update(float* x, const float* eps, const float* z, const float* a, const float* ce,
                                 const float* cz, int B, size_t elems_per_utt, hipStream_t s);
 hipError_t launch_cfg_combine(const float* eps2, float* out, float w, size_t elems_half, hipStream_t s);
+// ---------------- guided.hip ----------------
+hipError_t launch_guided_update(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
+                                const float* w, const float* a, const float* ce, const float* cz, const int32_t* speech_len,
+                                int B, int N, int d, bool cfg, hipStream_t s);
 
 // ---------------- attention.hip ----------------
 struct AttnArgs {

@@ -288,6 +288,59 @@ class DenoiseEngine:
                                                       s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), opts=opts)
         return x
 
+    def guided_lengths(self, speech_lengths, cond: TextCond, B: int, N: int, cfg: bool):
+        """(speech, text) device int32 [2B] (cfg) or [B] of a guided step, or None for a dense one.  `speech_lengths`: the B
+        utterances' (list / tuple / int tensor); under guidance the unconditional half repeats them.  The text lengths are the
+        conditioning's own (prepare_text(..., text_lengths=) over [text; null])."""
+        nb = 2 * B if cfg else B
+        if cond.B != nb:
+            raise ValueError(f"the conditioning holds {cond.B} utterances; a guided step of {B} needs {nb}")
+        if speech_lengths is None and cond.text_lengths is None:
+            return None
+        self._require_varlen()
+        sl = (validate_lengths(speech_lengths, B, N, "speech_lengths") if speech_lengths is not None
+              else torch.full((B,), N, dtype=torch.int32))
+        if cfg:
+            sl = torch.cat([sl, sl])
+        tl = cond.text_lengths if cond.text_lengths is not None else torch.full((nb,), cond.T, dtype=torch.int32, device=self.device)
+        return sl.to(self.device), tl
+
+    def guided_step_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, a: torch.Tensor, ce: torch.Tensor,
+                     cz: torch.Tensor, w: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                     seeds: Optional[torch.Tensor] = None, step: int = 0, lengths=None, speech_lengths=None,
+                     opts: Optional[hip.CallOpts] = None):
+        """One guided strided step IN PLACE on x2 (ditto_guided_step_opts): the forward over x2's 2B (w given: [x; x] x
+        [text; null]) or B utterances, then the fused update x' = a x + ce e + cz z with e = w (eps_c - eps_u) + eps_u (or eps),
+        written to both halves.  a / ce / cz / w: device fp32 [B]; z from `noise` fp32 [B, N, d], from Philox of `seeds` at tag
+        `step`, or none (cz unused).  `lengths`: guided_lengths(...) built once per sampling call (else it is built here from
+        `speech_lengths` and the conditioning).  Rows past an utterance's length become 0 in both halves."""
+        if not (x2.is_cuda and x2.dtype == torch.float32 and x2.is_contiguous()):
+            raise ValueError("guided_step_ needs a contiguous fp32 CUDA state tensor (it is updated in place)")
+        cfg = w is not None
+        nb, N, d = x2.shape
+        if nb != (2 * B if cfg else B):
+            raise ValueError(f"x2 holds {nb} utterances; a guided step of {B} needs {2 * B if cfg else B}")
+        if noise is not None and seeds is not None:
+            raise ValueError("noise and seeds are exclusive")
+        tt = self._t64(t, nb)
+        sd = self._t64(seeds, B) if seeds is not None else None
+        if noise is not None:
+            noise = self._f32(noise, "noise")
+            if noise.shape != (B, N, d):
+                raise ValueError(f"noise must have shape {(B, N, d)}")
+        for name, v in (("a", a), ("ce", ce), ("cz", cz), ("w", w)):
+            if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
+                raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
+        lens = lengths if lengths is not None else self.guided_lengths(speech_lengths, cond, B, N, cfg)
+        ws = self.workspace(nb, N, cond.T)
+        c, s = self.rope_tables(N)
+        hip.check(self.lib.ditto_guided_step_opts(
+            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), None if lens is None else lens[0].data_ptr(),
+            None if lens is None else lens[1].data_ptr(), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, _ptr(w), a.data_ptr(),
+            ce.data_ptr(), cz.data_ptr(), B, N, cond.T, int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+            None if opts is None else C.byref(opts)))
+        return x2
+
     def denoise_steps_(self, x: torch.Tensor, cond: TextCond, t_begin: int, t_end: int, noises: Optional[torch.Tensor],
                        betas: torch.Tensor, alphas: torch.Tensor, alphas_cumprod: torch.Tensor,
                        opts: Optional[hip.CallOpts] = None):

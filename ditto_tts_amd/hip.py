@@ -168,6 +168,10 @@ SYMBOLS = {
     "ditto_code_embed_mean": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ditto_linear_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
     "ditto_cfg_combine": (_i, [_vp, _vp, _f, _sz, _vp]),
+    # guided strided step (fused CFG + DDIM update over a variable-length batch)
+    "ditto_guided_update": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ditto_guided_step_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp,
+                                    _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),
     "ditto_tape_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
     "ditto_train_workspace_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),

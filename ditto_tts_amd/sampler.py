@@ -28,6 +28,52 @@ import torch
 from .modules import DiTTO
 
 
+def strided_schedule(alphas_cumprod: torch.Tensor, n_steps: int, eta: float = 0.0):
+    """The strided (DDIM) schedule of `n_steps` evenly spaced timesteps over the table `alphas_cumprod`: a list of
+    (tau_i, a, ce, sigma), x' = a x + ce eps + sigma z at step i (Song et al. 2021 eq. 12; the last step ends at abar = 1).
+    The coefficients are computed in float64 and returned as Python floats: the expressions of sample_latents_strided."""
+    T = int(alphas_cumprod.shape[0])
+    if not 1 <= n_steps <= T:
+        raise ValueError("n_steps must be in [1, diffusion_steps]")
+    stride = T / n_steps
+    taus = [int(round(T - 1 - i * stride)) for i in range(n_steps)]
+    ac = alphas_cumprod.double().cpu()
+    out = []
+    for i, t_val in enumerate(taus):
+        ab_t = ac[t_val]
+        ab_p = ac[taus[i + 1]] if i + 1 < n_steps else torch.tensor(1.0, dtype=torch.float64)
+        sigma = eta * torch.sqrt((1 - ab_p) / (1 - ab_t)) * torch.sqrt(1 - ab_t / ab_p)
+        a = torch.sqrt(ab_p / ab_t)
+        ce = torch.sqrt(torch.clamp(1 - ab_p - sigma ** 2, min=0.0)) - torch.sqrt(ab_p * (1 - ab_t) / ab_t)
+        out.append((t_val, float(a), float(ce), float(sigma)))
+    return out
+
+
+def guidance_vector(guidance, B: int) -> Optional[torch.Tensor]:
+    """`guidance` (None, a number, or a sequence / tensor of B numbers) as a CPU fp32 tensor [B], or None (no guidance)."""
+    if guidance is None:
+        return None
+    if isinstance(guidance, bool):
+        raise ValueError("guidance: a number or a sequence of numbers is needed, got a bool")
+    if isinstance(guidance, (int, float)):
+        return torch.full((B,), float(guidance), dtype=torch.float32)
+    if isinstance(guidance, torch.Tensor):
+        if guidance.dtype == torch.bool or guidance.is_complex():
+            raise ValueError(f"guidance: a real tensor is needed, got {guidance.dtype}")
+        g = guidance.detach().to("cpu", torch.float32)
+    elif isinstance(guidance, (list, tuple)):
+        if not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in guidance):
+            raise ValueError("guidance: a list / tuple of numbers is needed")
+        g = torch.tensor([float(v) for v in guidance], dtype=torch.float32)
+    else:
+        raise ValueError(f"guidance: None, a number, a sequence or a tensor is needed, got {type(guidance).__name__}")
+    if g.dim() != 1 or g.shape[0] != B:
+        raise ValueError(f"guidance: shape [{B}] expected, got {list(g.shape)}")
+    if not torch.isfinite(g).all():
+        raise ValueError("guidance: every scale must be finite")
+    return g.contiguous()
+
+
 class SpeechGenerator:
     def __init__(self, lambda_factor=0.1, nac_model_path=None, ditto_model_path=None, slp_path=None,
                  sample_rate=24000, device="cuda", *, ditto_model: Optional[DiTTO] = None, config=None,
@@ -209,8 +255,8 @@ class SpeechGenerator:
         batch [x; x] x [text; null_text] and combines eps_u + w (eps_c - eps_u) (ditto_cfg_combine)."""
         from .around import cfg_combine, linear_update_
         if speech_lengths is not None or text_lengths is not None:
-            raise NotImplementedError("variable-length batches run the ancestral loop only (sample_latents); the strided / CFG "
-                                      "sampler has no varlen form")
+            raise NotImplementedError("sample_latents_strided has no varlen form: a variable-length batch runs sample_guided "
+                                      "(guided strided loop) or the ancestral sample_latents")
         m = self.ditto_model
         T = self.diffusion_steps
         if not 1 <= n_steps <= T:
@@ -253,6 +299,90 @@ class SpeechGenerator:
                     z.copy_((noises(i) if callable(noises) else noises[i]).to(x.device))
             linear_update_(x, eps, z if use_noise else None, coef[0], coef[1], coef[2])
         return x
+
+    # ---------------------------------------------------------------- guided strided loop over a variable-length batch
+    @torch.no_grad()
+    def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
+                      null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
+                      cond_by_audio=False, batch_class=None):
+        """The strided (DDIM) loop of sample_latents_strided with what serving needs: per-utterance `speech_lengths` /
+        `text_lengths` (a padded batch; rows past an utterance's length are exactly 0 in the result and padding never reaches a
+        valid row), per-utterance `guidance` (None: no CFG; a number; or [B] numbers), and per-utterance `seeds`.  One library
+        call per step (ditto_guided_step_opts): the forward over [x; x] x [text; null] and one fused update kernel
+        (csrc/guided.hip) that combines the guidance, adds the step's noise, writes both halves of the next doubled input and
+        zeroes the padding.
+
+        `null_text_emb` (required with guidance) broadcasts to text_emb; `null_text_lengths` default to `text_lengths`.
+        x_T: `seeds` -> ditto_noise_normal(seeds, 0xFFFFFFFF) (the x_T of sample_latents(seeds=)); `cond_by_audio` -> audio_emb;
+        else torch.randn_like.  Step i's z (when sigma != 0): Philox of `seeds` at tag tau_i, `noises[i]` (a sequence or
+        callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
+        count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
+        Dense, full-length, uniform guidance with noises= or cond_by_audio: the bits of sample_latents_strided.
+        Returns fp32 [B, N, d]."""
+        if seeds is not None and noises is not None:
+            raise ValueError("seeds= excludes noises=")
+        m = self.ditto_model
+        eng = m.engine(torch.empty(0, device=self.device).device)      # "cuda" -> cuda:0: the engine the other loops use
+        B, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        gv = guidance_vector(guidance, B)
+        cfg = gv is not None
+        if cfg and null_text_emb is None:
+            raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
+        schedule = strided_schedule(self.alphas_cumprod, n_steps, eta)
+        text = text_emb.to(eng.device).float()
+        T = int(text.shape[1])
+        if null_text_lengths is not None and not cfg:
+            raise ValueError("null_text_lengths without guidance")
+        varlen = speech_lengths is not None or text_lengths is not None or null_text_lengths is not None
+        if varlen:
+            eng._require_varlen()
+            from .varlen import validate_lengths
+            sl = validate_lengths(speech_lengths if speech_lengths is not None else [N] * B, B, N, "speech_lengths")
+            tl = validate_lengths(text_lengths if text_lengths is not None else [T] * B, B, T, "text_lengths")
+            if cfg:
+                ntl = validate_lengths(null_text_lengths, B, T, "null_text_lengths") if null_text_lengths is not None else tl
+                tl = torch.cat([tl, ntl])
+        if cfg:
+            text = torch.cat([text, null_text_emb.to(eng.device).float().expand_as(text)], dim=0).contiguous()
+        cond = eng.prepare_text(text, N, text_lengths=tl if varlen else None)
+        nb = 2 * B if cfg else B
+        lens = eng.guided_lengths(sl if varlen else None, cond, B, N, cfg)
+        x2 = torch.empty(nb, N, int(audio_emb.shape[2]), dtype=torch.float32, device=eng.device)
+        x = x2[:B]
+        if seeds is not None:
+            seeds = seeds.to(eng.device).long().contiguous()
+            if seeds.shape != (B,):
+                raise ValueError(f"seeds must have shape [{B}]")
+        if seeds is not None and not cond_by_audio:
+            eng.noise_normal_(x, seeds, 0xFFFFFFFF)         # x_T: the step tag no loop step uses (sample_latents(seeds=))
+        else:
+            x.copy_(torch.randn_like(audio_emb) if not cond_by_audio else audio_emb)
+        if cfg:
+            x2[B:].copy_(x)                                  # after this, every step's update writes both halves itself
+        # every step's coefficients in one upload: coef[i] = (a, ce, sigma) x B
+        coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
+        w = gv.to(eng.device) if cfg else None
+        t_tensor = torch.empty(nb, device=eng.device, dtype=torch.long)
+        z = torch.empty(B, *x2.shape[1:], dtype=torch.float32, device=eng.device) if seeds is None else None
+        opts = None
+        if batch_class is not None:
+            from .hip import CallOpts
+            opts = CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
+        for i, (t_val, _, _, sigma) in enumerate(schedule):
+            t_tensor.fill_(t_val)
+            noise = sd = None
+            if sigma != 0.0:
+                if seeds is not None:
+                    sd = seeds
+                elif noises is None:
+                    z.normal_()
+                    noise = z
+                else:
+                    z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
+                    noise = z
+            eng.guided_step_(x2, cond, t_tensor, B, coef[i, 0], coef[i, 1], coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val,
+                             lengths=lens, opts=opts)
+        return x2[:B].clone() if cfg else x2
 
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):

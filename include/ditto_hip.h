@@ -449,6 +449,29 @@ int ditto_code_embed_mean(const float* table, const int64_t* codes, float* out, 
 int ditto_linear_update(float* x, const float* eps, const float* noise, const float* a, const float* ce,
                         const float* cz, int B, size_t elems_per_utt, ditto_stream_t stream);
 int ditto_cfg_combine(const float* eps2, float* out, float w, size_t elems_half, ditto_stream_t stream);
+/* Guided strided (DDIM) step over a variable-length batch (the paper's serving configuration: 25 steps, guidance 5.0).
+ * ditto_guided_update: one launch for the update of a step.  x2, eps2 fp32 [2B, N, d] when cfg != 0 ([conditional; unconditional]:
+ *   the forward over [text; null]), [B, N, d] when cfg == 0.  For utterance b < B, row r < speech_len[b]:
+ *     e = cfg ? w[b] (c - u) + u : c  (c = eps2[b], u = eps2[B + b]: ditto_cfg_combine's fmaf),
+ *     x' = a[b] x + ce[b] e + cz[b] z  (ditto_linear_update's fmaf order; z = cz = 0 with neither noise nor seeds),
+ *   written to x2[b] and, when cfg != 0, to x2[B + b] (the next step's doubled input needs no copy).  Rows r >= speech_len[b] become 0
+ *   in both halves without x, eps2 or the noise being read there; speech_len NULL = every row valid (device int32 [B], clamped into
+ *   [1, N]).  The step's z: `noise` fp32 [B, N, d], or Philox from `seeds` (device int64 [B]) at tag `step`, the bits of
+ *   ditto_noise_normal(seeds, step) on every valid row; giving both is DITTO_ERR_ARG.  w, a, ce, cz: device fp32 [B] (w only when
+ *   cfg != 0; cz only with noise or seeds).  d % 64 == 0 (DITTO_ERR_SHAPE otherwise).
+ * ditto_guided_step_opts: the forward over the B (cfg == 0) or 2B utterances of x2 with t int64 [2B or B], then
+ *   ditto_guided_update into the same x2: one library call per step.  `cond` holds the 2B (or B) utterances' conditioning.  With
+ *   speech_len and text_len both NULL the forward is ditto_forward_opts'; otherwise both are device int32 [2B or B] (every row of
+ *   x2, as ditto_forward_varlen_opts takes them, and the conditioning from ditto_text_precompute_varlen with that text_len).
+ *   The workspace is ditto_workspace_bytes(cfg, 2B or B, N, T). */
+int ditto_guided_update(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                        const float* a, const float* ce, const float* cz, const int32_t* speech_len, int B, int N, int d, int cfg,
+                        ditto_stream_t stream);
+int ditto_guided_step_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* speech_len,
+                           const int32_t* text_len, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                           const float* a, const float* ce, const float* cz, int B, int N, int T, int cfg, const float* rope_cos,
+                           const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                           const ditto_call_opts* opts);
 
 /* ---- training: the backward of DiTTO.forward, so that the reference's training closure
  * (src/TrainDiTTO.py:55-95: model.train(); loss = mse(model(x_t, text, t), noise); loss.backward()) runs on this
