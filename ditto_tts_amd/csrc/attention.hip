@@ -741,6 +741,10 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
         return hipErrorInvalidValue;
     const bool varlen = a.q_len || a.kv_len;
     if (varlen && (a.dh != DH || a.force_generic || a.causal || train_fwd || !a.q_prescaled)) return hipErrorInvalidValue;
+    const bool packed = a.cu_q || a.cu_kv;   // packed batch: both offset arrays, the same restrictions as varlen
+    if (packed && (!a.cu_q || !a.cu_kv || varlen || a.q_rows <= 0 || a.kv_rows <= 0 || a.dh != DH || a.force_generic || a.causal ||
+                   train_fwd || !a.q_prescaled))
+        return hipErrorInvalidValue;
     if (a.dh == DH && !a.force_generic && !a.causal) {
         if ((a.ldq | a.ldk | a.ldv) % 8) return hipErrorInvalidValue;
         AttnParams p;
@@ -752,6 +756,11 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
         p.lse = a.lse_out; p.drop_thr = dropout_threshold(a.dropout_p);
         p.keep_scale = p.drop_thr ? 1.0f / (1.0f - a.dropout_p) : 1.0f;
         p.seed_lo = (unsigned)(a.seed & 0xFFFFFFFFu); p.seed_hi = (unsigned)(a.seed >> 32); p.layer = a.layer;
+        if (packed) {   // utterances concatenated along the rows (attention_packed.hip)
+            if (a.ldo % 8 || (a.resid_f32 && a.ldr % 8)) return hipErrorInvalidValue;
+            p.cu_q = a.cu_q; p.cu_kv = a.cu_kv; p.q_rows = a.q_rows; p.kv_rows = a.kv_rows;
+            return launch_attn64p_packed(p, a.resid_f32 != nullptr, s, (g_attn_flags & 1048576) != 0);
+        }
         if (varlen) {   // per-utterance lengths: the 64-queries-per-wave family only (attention_p.hip), whatever the class rows
             if (a.ldo % 8 || (a.resid_f32 && a.ldr % 8)) return hipErrorInvalidValue;   // 16-byte row pieces in the epilogue
             p.q_len = a.q_len; p.kv_len = a.kv_len;

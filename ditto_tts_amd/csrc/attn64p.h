@@ -38,6 +38,20 @@
 // that ends iteration t leaves the younger tiles in flight: one barrier per 32 MFMAs per wave.
 #pragma once
 
+// Rows of utterance b (b, p in scope): the padded layout, b * Sq / b * Skv; or, in a translation unit that defines
+// DITTO_ATTN_PACKED 1 before including this file (attention_packed.hip), the packed one: the utterance's first rows q0 / k0 from
+// p.cu_q / p.cu_kv (attn_span), every VARLEN instantiation then packed.  The other translation units compile to what they did.
+#ifndef DITTO_ATTN_PACKED
+#define DITTO_ATTN_PACKED 0
+#endif
+#if DITTO_ATTN_PACKED
+#define ATTN_QROW(r) (q0 + (size_t)(r))
+#define ATTN_KROW(r) (k0 + (size_t)(r))
+#else
+#define ATTN_QROW(r) ((size_t)b * p.Sq + (r))
+#define ATTN_KROW(r) ((size_t)b * p.Skv + (r))
+#endif
+
 // this lane's value and lane i ^ 32's (the other 32 keys of the same query): one v_permlane32_swap (vdst lanes 32..63 <-> src lanes
 // 0..31) on two COPIES of the value.  As an asm statement with its own wait states: a vector write of a permlane operand must be two
 // instructions back, and the builtin handed the same value twice gets ONE register for both operands (which swaps a register's
@@ -72,7 +86,13 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
     const int id = xcd_remap(bid, nwg);
     const int qb = id % p.nqb, bh = id / p.nqb;
     const int h = bh % p.H, b = bh / p.H;
+#if DITTO_ATTN_PACKED
+    static_assert(VARLEN, "a packed utterance is bounded by its own offsets");
+    int sq, skv;
+    const size_t q0 = attn_span(p.cu_q, b, p.Sq, p.q_rows, sq), k0 = attn_span(p.cu_kv, b, p.Skv, p.kv_rows, skv);
+#else
     const int sq = VARLEN ? attn_len(p.q_len, b, p.Sq) : p.Sq, skv = VARLEN ? attn_len(p.kv_len, b, p.Skv) : p.Skv;
+#endif
     if (VARLEN && qb * QWG >= sq) return;   // (workgroup-uniform)
     const int ql = lane & 31, hh = lane >> 5;
     int qrow[2];
@@ -90,7 +110,7 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
     {
 #pragma unroll
         for (int x = 0; x < 2; ++x) {
-            const bf16* qp = p.q + ((size_t)b * p.Sq + qrow[x]) * p.ldq + h * DH + 8 * hh;
+            const bf16* qp = p.q + ATTN_QROW(qrow[x]) * p.ldq + h * DH + 8 * hh;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) qf[x][ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
         }
@@ -100,8 +120,8 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = (wid * 2 + i) * 8 + (lane >> 3), cpos = lane & 7;
-        ksrc[i] = p.k + ((size_t)b * p.Skv + row) * p.ldk + h * DH + (cpos ^ ((row >> 1) & 7)) * 8;
-        vsrc[i] = p.v + ((size_t)b * p.Skv + row) * p.ldv + h * DH + (cpos ^ (((row >> 1) & 1) << 2)) * 8;
+        ksrc[i] = p.k + ATTN_KROW(row) * p.ldk + h * DH + (cpos ^ ((row >> 1) & 7)) * 8;
+        vsrc[i] = p.v + ATTN_KROW(row) * p.ldv + h * DH + (cpos ^ (((row >> 1) & 1) << 2)) * 8;
     }
     const size_t kstep = (size_t)KBLK * p.ldk, vstep = (size_t)KBLK * p.ldv;
     auto dma_kv = [&](int kt, int slot) {   // 4 loads per wave
@@ -113,9 +133,9 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
                 int key = kt * KBLK + row;
                 key = key < skv ? key : skv - 1;
                 const int ck = cpos ^ ((row >> 1) & 7), cv = cpos ^ (((row >> 1) & 1) << 2);
-                glds16(p.k + ((size_t)b * p.Skv + key) * p.ldk + h * DH + ck * 8,
+                glds16(p.k + ATTN_KROW(key) * p.ldk + h * DH + ck * 8,
                        lds_base + (unsigned)(slot * 2 * KV_TILE_BYTES + piece * 1024));
-                glds16(p.v + ((size_t)b * p.Skv + key) * p.ldv + h * DH + cv * 8,
+                glds16(p.v + ATTN_KROW(key) * p.ldv + h * DH + cv * 8,
                        lds_base + (unsigned)(slot * 2 * KV_TILE_BYTES + KV_TILE_BYTES + piece * 1024));
             }
             return;
@@ -335,7 +355,7 @@ DITTO_DEV void attn64p_body(const AttnParams& p, char* smem, int tid, int bid) {
         float s0, s1;
         swap32(lrun[x], s0, s1);
         const float inv = 1.0f / (s0 + s1);
-        const size_t grow = (size_t)b * p.Sq + qrow[x];
+        const size_t grow = ATTN_QROW(qrow[x]);
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll

@@ -88,7 +88,13 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
     const int qb = id % p.nqb, bh = id / p.nqb;
     const int h = bh % p.H, b = bh / p.H;
     static_assert(!VARLEN || RAGGED, "a varlen key sequence may end anywhere");
+#if DITTO_ATTN_PACKED
+    static_assert(VARLEN, "a packed utterance is bounded by its own offsets");
+    int sq, skv;
+    const size_t q0 = attn_span(p.cu_q, b, p.Sq, p.q_rows, sq), k0 = attn_span(p.cu_kv, b, p.Skv, p.kv_rows, skv);
+#else
     const int sq = VARLEN ? attn_len(p.q_len, b, p.Sq) : p.Sq, skv = VARLEN ? attn_len(p.kv_len, b, p.Skv) : p.Skv;
+#endif
     if constexpr (VARLEN) {
         if (qb * QWG >= sq) return;   // (workgroup-uniform: before any load)
         if (skv <= KBLK) {            // one key tile: the exact body (attn64q needs two)
@@ -114,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
     bf16x8 qf[2][4];
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
-        const bf16* qp = p.q + ((size_t)b * p.Sq + qrow[x]) * p.ldq + h * DH + 8 * hh;
+        const bf16* qp = p.q + ATTN_QROW(qrow[x]) * p.ldq + h * DH + 8 * hh;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[x][ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
     }
@@ -122,8 +128,8 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = (wid * 2 + i) * 8 + (lane >> 3), cpos = lane & 7;
-        ksrc[i] = p.k + ((size_t)b * p.Skv + row) * p.ldk + h * DH + (cpos ^ ((row >> 1) & 7)) * 8;
-        vsrc[i] = p.v + ((size_t)b * p.Skv + row) * p.ldv + h * DH + (cpos ^ (((row >> 1) & 1) << 2)) * 8;
+        ksrc[i] = p.k + ATTN_KROW(row) * p.ldk + h * DH + (cpos ^ ((row >> 1) & 7)) * 8;
+        vsrc[i] = p.v + ATTN_KROW(row) * p.ldv + h * DH + (cpos ^ (((row >> 1) & 1) << 2)) * 8;
     }
     const size_t kstep = (size_t)KBLK * p.ldk, vstep = (size_t)KBLK * p.ldv;
     auto dma_kv = [&](int kt, int slot) {   // 4 loads per wave
@@ -136,9 +142,9 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
                 int key = kt * KBLK + row;
                 key = key < skv ? key : skv - 1;
                 const int ck = cpos ^ ((row >> 1) & 7), cv = cpos ^ (((row >> 1) & 1) << 2);
-                glds16(p.k + ((size_t)b * p.Skv + key) * p.ldk + h * DH + ck * 8,
+                glds16(p.k + ATTN_KROW(key) * p.ldk + h * DH + ck * 8,
                        lds_base + (unsigned)(slot * 2 * KV_TILE_BYTES + piece * 1024));
-                glds16(p.v + ((size_t)b * p.Skv + key) * p.ldv + h * DH + cv * 8,
+                glds16(p.v + ATTN_KROW(key) * p.ldv + h * DH + cv * 8,
                        lds_base + (unsigned)(slot * 2 * KV_TILE_BYTES + KV_TILE_BYTES + piece * 1024));
             }
             return;
@@ -292,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
                     const int row = 8 * i + (lane >> 3);
                     int qr = qb * QWG + wid * 64 + row;
                     qr = qr < sq ? qr : sq - 1;
-                    glds16(reinterpret_cast<const bf16*>(p.resid_in) + ((size_t)b * p.Sq + qr) * p.ldr + h * DH + (((lane & 7) ^ (row & 7)) << 3),
+                    glds16(reinterpret_cast<const bf16*>(p.resid_in) + ATTN_QROW(qr) * p.ldr + h * DH + (((lane & 7) ^ (row & 7)) << 3),
                            rdst + (unsigned)(i * 1024));
                 }
             }
@@ -419,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void attn64q_kernel(AttnParams p) {
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
         const float inv = linv[x];
-        const size_t grow = (size_t)b * p.Sq + qrow[x];
+        const size_t grow = ATTN_QROW(qrow[x]);
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll

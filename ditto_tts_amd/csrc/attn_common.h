@@ -26,6 +26,11 @@ struct AttnParams {
     // offsets stay where they were.
     const int32_t* q_len = nullptr;
     const int32_t* kv_len = nullptr;
+    // packed batches (the instantiations of attention_packed.hip only): device int32 [B + 1] row offsets, utterance b owns rows
+    // [cu[b], cu[b+1]) of q / out / resid (q_rows rows in all) and of k / v (kv_rows rows); Sq / Skv bound every length
+    const int32_t* cu_q = nullptr;
+    const int32_t* cu_kv = nullptr;
+    int q_rows = 0, kv_rows = 0;
 };
 
 // an utterance's valid length, clamped into [1, full] (a bad value cannot address out of bounds)
@@ -35,9 +40,20 @@ DITTO_DEV int attn_len(const int32_t* len, int b, int full) {
     return v < 1 ? 1 : (v > full ? full : v);
 }
 
+// a packed utterance's first row (clamped into [0, rows - 1]) and its length (clamped into [1, min(full, rows - first)]): a bad
+// offset cannot address outside the buffer
+DITTO_DEV int attn_span(const int32_t* cu, int b, int full, int rows, int& len) {
+    int lo = cu[b];
+    lo = lo < 0 ? 0 : (lo > rows - 1 ? rows - 1 : lo);
+    const int n = cu[b + 1] - lo, cap = rows - lo < full ? rows - lo : full;
+    len = n < 1 ? 1 : (n > cap ? cap : n);
+    return lo;
+}
+
 hipError_t launch_attention_train64(const AttnParams& p, bool resid, hipStream_t s);   // attention_train.hip
 hipError_t launch_attn64p(const AttnParams& p, bool resid, hipStream_t s, bool ring3 = false, int no_q = 0);   // attention_p.hip: 64 queries per wave (round 6: attn64p, attn64q)
 hipError_t launch_attn64p_varlen(const AttnParams& p, bool resid, hipStream_t s, bool exact_only);   // attention_varlen.hip: p.q_len / p.kv_len
+hipError_t launch_attn64p_packed(const AttnParams& p, bool resid, hipStream_t s, bool exact_only);   // attention_packed.hip: p.cu_q / p.cu_kv
 
 // the self-attention epilogue's stream update  h[row, col .. col+3] = h_in[...] + o  (src/components/DiT.py:139: no out-proj),
 // on an fp32 stream or a bf16 one (wave-uniform branch, outside every loop)

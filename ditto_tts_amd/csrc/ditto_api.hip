@@ -252,13 +252,36 @@ struct ProfScope {
 
 }  // namespace
 
+// A packed batch (ditto_forward_packed_opts): utterance b owns speech rows [cu[b], cu[b+1]) of the S rows and text rows
+// [cu_t[b], cu_t[b+1]) of the S_T rows of the conditioning; `pos` is the per-row RoPE position (launch_packed_row_map).  The forward
+// then runs as ONE sequence of M = S rows (B = 1, N = S, T = S_T in run_block's terms): every launch but the attention and the two
+// per-row reads (AdaLN's utterance, the QKV epilogue's position) is row-wise.
+struct PackedRows {
+    const int32_t* cu; const int32_t* cu_t; const int32_t* utt; const int32_t* pos;
+    int B, max_N, max_T, S, S_T;
+};
+
+// the workspace of a packed forward: plan_ws over the rows rounded up to whole 256-row tiles, then the two int32 row maps; the text
+// precompute's scratch (bf16 text [S_T, dt] | pooled fp32 [B, dt]) at the front
+struct PackedWsPlan { WsPlan w; size_t utt, pos, total; };
+static PackedWsPlan plan_ws_packed(const ditto_config& c, int B, int S, int S_T) {
+    PackedWsPlan p;
+    p.w = plan_ws(c, 1, (S + 255) / 256 * 256, S_T);
+    size_t off = p.w.total;
+    p.utt = off; off += al((size_t)S * 4);
+    p.pos = off; off += al((size_t)S * 4);
+    const size_t tneed = al((size_t)S_T * c.text_dim * 2) + al((size_t)B * c.text_dim * 4);
+    p.total = off > tneed ? off : tneed;
+    return p;
+}
+
 // One DiT block (reference src/components/DiT.py:100-157) on the fp32 residual stream `h`, in place.
 static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* act, char* xcat_or_null,
                      void* attn_ws, size_t attn_ws_bytes, float* splitk_ws, size_t splitk_bytes, const char* kv, int kv_layer, int kv_ld,
                      const float* rope_cos, const float* rope_sin, int B, int N, int T, hipStream_t s,
                      float* tap_self = nullptr, float* tap_cross = nullptr, bool ln1_done = false,
                      const float* next_g1 = nullptr, const float* next_be1 = nullptr, bool hb = false,
-                     const int32_t* speech_len = nullptr, const int32_t* text_len = nullptr) {
+                     const int32_t* speech_len = nullptr, const int32_t* text_len = nullptr, const PackedRows* pk = nullptr) {
     const ditto_config& c = m->cfg;
     const int d = c.hidden_dim, H = c.num_heads, dh = d / H, M = B * N;
     const float scale = 1.0f / sqrtf((float)dh);
@@ -278,7 +301,7 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
     const bool fr_fc2 = !fp8 && lp.W2P && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
     // tiles per utterance: the K-loop rotation period (gemm_fr.hip).  A varlen batch runs unrotated (here and in gemm_lnq's): the
     // rotation is a function of the PADDED N, and an utterance's bits must not depend on the padding
-    const bool varlen = speech_len || text_len;
+    const bool varlen = speech_len || text_len || pk;   // (a packed batch is one too: its tiles straddle utterances)
     const int fr_rot = !varlen && N % 128 == 0 ? N / 128 : 0;
     if (int rc = ditto::check_class_pin(M, d, fp8, !pad)) return rc;
     // hb: `h` holds BF16 rows (the bf16 residual stream; ditto_forward decides, and only where both fused launches run)
@@ -303,6 +326,10 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             g.rope_cos = rope_cos; g.rope_sin = rope_sin; g.rope_rows_per_batch = N; g.rope_cols = 2 * d;
             if (fused_rope && !(g_gemm_flags & 1024)) g.rope_freq_rev = m->invf_rev;   // flag 1024: A/B, table loads
             g.fp8 = fp8; g.wscale = fp8 ? lp.sqkv : nullptr;
+            // packed batch: every row's position inside its utterance from the row map (the table-free angles of the same float
+            // position: the padded layout's bits)
+            const GemmEpilogue qkv_epi = pk ? EPI_QKV_ROPE_PACKED : EPI_QKV_ROPE;
+            if (pk) g.rope_pos = pk->pos;
 #ifdef DITTO_DIAG_QKV_PLAIN   // tools/build_diag.sh: the QKV GEMM with the plain bias epilogue (NO RoPE: wrong results) — what
                               // would the 256 x 192 kernel (whole tile rounds at M = 32768; gemm_tile 192) buy this class?
             HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
@@ -319,12 +346,12 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             if (q_split) {
                 GemmArgs gm = g, gt = g;
                 gm.N = 3 * dp - 256;
-                HIP_TRY(launch_gemm(gm, EPI_QKV_ROPE, s));
+                HIP_TRY(launch_gemm(gm, qkv_epi, s));
                 gt.N = 256; gt.W = (const char*)lp.Wqkv + (size_t)gm.N * d * 2; gt.bias = lp.bqkv + gm.N;
                 gt.out = qkv + (size_t)gm.N * 2; gt.rope_cols = 0; gt.rope_freq_rev = nullptr;
                 HIP_TRY(launch_gemm(gt, EPI_BIAS_BF16, s));
             } else {
-            HIP_TRY(launch_gemm(g, fused_rope ? EPI_QKV_ROPE : EPI_BIAS_BF16, s));
+            HIP_TRY(launch_gemm(g, fused_rope ? qkv_epi : EPI_BIAS_BF16, s));
             if (!fused_rope) HIP_TRY(launch_rope_inplace(qkv, 3 * dp, rope_cos, rope_sin, M, N, 2 * dp, dh, s, 1.0f, dhp));
             }
 #endif
@@ -342,6 +369,7 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             a.ldv = 3 * dp; a.B = B; a.H = H; a.Sq = N; a.Skv = N; a.dh = dhp;
             a.scale = scale; a.workspace = attn_ws; a.workspace_bytes = attn_ws_bytes; a.q_prescaled = (dh == 64);
             a.q_len = speech_len; a.kv_len = speech_len;
+            if (pk) { a.B = pk->B; a.Sq = a.Skv = pk->max_N; a.cu_q = a.cu_kv = pk->cu; a.q_rows = a.kv_rows = pk->S; }
             if (pad) {   // O at the padded stride into `act` (free here), then h[:, hd dh + c] += O[:, hd dhp + c]
                 a.out_bf16 = act; a.ldo = dp;
                 HIP_TRY(launch_attention(a, s));
@@ -377,6 +405,9 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             a.B = B; a.H = H; a.Sq = N; a.Skv = T; a.dh = dhp; a.scale = scale;
             a.workspace = attn_ws; a.workspace_bytes = attn_ws_bytes; a.q_prescaled = (dh == 64);
             if (speech_len || text_len) { a.q_len = speech_len; a.kv_len = text_len; }
+            if (pk) {
+                a.B = pk->B; a.Sq = pk->max_N; a.Skv = pk->max_T; a.cu_q = pk->cu; a.cu_kv = pk->cu_t; a.q_rows = pk->S; a.kv_rows = pk->S_T;
+            }
             HIP_TRY(launch_attention(a, s));
         }
         bool ln3_done = false;
@@ -722,12 +753,14 @@ int ditto_forward_opts(ditto_model_t m, const float* x, const void* cond, const 
 
 static int forward_impl(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
                         const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
-                        size_t workspace_bytes, ditto_stream_t stream, const int32_t* speech_len, const int32_t* text_len) {
+                        size_t workspace_bytes, ditto_stream_t stream, const int32_t* speech_len, const int32_t* text_len,
+                        const PackedRows* pk = nullptr) {
     if (!m || !x || !cond || !t || !rope_cos || !rope_sin || !eps_out || !workspace || B <= 0 || N <= 0 || T <= 0)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_forward");
     const ditto_config& c = m->cfg;
     if (m->blocks_only) return fail(DITTO_ERR_ARG, "ditto_forward on a blocks-only handle");
-    const WsPlan w = plan_ws(c, B, N, T);
+    // (packed: B = 1, N = S, T = S_T — ditto_forward_packed_opts checked the workspace against plan_ws_packed)
+    const WsPlan w = pk ? plan_ws_packed(c, pk->B, pk->S, pk->S_T).w : plan_ws(c, B, N, T);
     if (workspace_bytes < w.total)
         return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
     if ((uintptr_t)workspace % 256) return fail(DITTO_ERR_ARG, "workspace must be 256-byte aligned");
@@ -765,9 +798,16 @@ static int forward_impl(ditto_model_t m, const float* x, const void* cond, const
     const bool ln1_in_adaln = !fp8c && !(g_gemm_flags & 32768);      // gemm_flags bit 15: A/B, the separate launch
     {   // GlobalAdaLN (src/components/DiT.py:25-40) + bf16 copy of the raw input for proj_in
         ProfScope ps(m, s, DITTO_KC_ADALN);
+        if (pk) {   // the row maps first (utterance and RoPE position of every packed row), then the entry with the utterance map
+            HIP_TRY(launch_packed_row_map(pk->cu, pk->B, pk->S, pk->max_N, (int32_t*)pk->utt, (int32_t*)pk->pos, s));
+            HIP_TRY(launch_adaln_packed(x, m->ttab, tmod, t, c.diffusion_steps, pk->utt, h, xcat, 2 * d, M, d, s, hb,
+                                        ln1_in_adaln ? m->layers[0].g1 : nullptr, ln1_in_adaln ? m->layers[0].be1 : nullptr,
+                                        ln1_in_adaln ? u : nullptr));
+        } else {
         HIP_TRY(launch_adaln(x, m->ttab, tmod, t, c.diffusion_steps, h, xcat, 2 * d, B, N, d, s, hb,
                              ln1_in_adaln ? m->layers[0].g1 : nullptr, ln1_in_adaln ? m->layers[0].be1 : nullptr,
                              ln1_in_adaln ? u : nullptr));
+        }
     }
     for (int l = 0; l < L; ++l)
         if (int rc = run_block(m, l, h, u, qkv, act, l == L - 1 ? xcat : nullptr, attn_ws, w.attn_bytes,
@@ -775,7 +815,7 @@ static int forward_impl(ditto_model_t m, const float* x, const void* cond, const
                                L * 2 * cfg_dp(c), rope_cos, rope_sin, B, N, T, s, nullptr, nullptr,
                                ((chain_ln1 || chain_ll) && l > 0) || (ln1_in_adaln && l == 0),
                                (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].g1 : nullptr,
-                               (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].be1 : nullptr, hb, speech_len, text_len))
+                               (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].be1 : nullptr, hb, speech_len, text_len, pk))
             return rc;
     {   // eps = proj_in(x_raw) + proj_out(h_L)  (src/model/DiTTO.py:83,93-94), one K = 2d GEMM
         ProfScope ps(m, s, DITTO_KC_GEMM_FINAL);
@@ -812,6 +852,85 @@ int ditto_forward_varlen_opts(ditto_model_t m, const float* x, const void* cond,
     return forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream, speech_len, text_len);
 }
 
+// ---- packed batches: utterances concatenated along the rows, described by device int32 offsets [B + 1] ----
+size_t ditto_packed_workspace_bytes(const ditto_config* cfg, int B, int S, int S_T) {
+    if (check_cfg(cfg) != DITTO_OK || B <= 0 || S <= 0 || S_T <= 0) return 0;
+    return plan_ws_packed(*cfg, B, S, S_T).total;
+}
+size_t ditto_packed_cond_bytes(const ditto_config* cfg, int B, int S_T) {
+    if (check_cfg(cfg) != DITTO_OK || B <= 0 || S_T <= 0) return 0;
+    const size_t d = cfg->hidden_dim, dp = cfg_dp(*cfg);
+    return al((size_t)S_T * cfg->num_layers * 2 * dp * 2) + al((size_t)B * 2 * d * 4);
+}
+
+// what every packed entry checks on the host (the offsets themselves live on the device: documented, clamped by the kernels)
+static int check_packed(const char* who, int B, int S, int max_N, int S_T, int max_T) {
+    if (B <= 0 || S <= 0 || max_N <= 0 || S_T <= 0 || max_T <= 0)
+        return fail(DITTO_ERR_SHAPE, "%s: B, S, max_N, S_T and max_T must be positive", who);
+    if (max_N > S || max_T > S_T || B > S || B > S_T)
+        return fail(DITTO_ERR_SHAPE, "%s: need max_N <= S, max_T <= S_T and at least one row per utterance (B %d, S %d, S_T %d)", who, B,
+                    S, S_T);
+    if (B > 65535) return fail(DITTO_ERR_SHAPE, "%s: more than 65535 utterances", who);
+    return DITTO_OK;
+}
+static int check_packed_model(const char* who, ditto_model_t m) {
+    const ditto_config& c = m->cfg;
+    if (m->blocks_only) return fail(DITTO_ERR_ARG, "%s on a blocks-only handle", who);
+    if (c.hidden_dim / c.num_heads != 64) return fail(DITTO_ERR_SHAPE, "%s: packed batches need head_dim 64 (this model's is %d)", who,
+                                                      c.hidden_dim / c.num_heads);
+    if (c.flags & DITTO_CFG_FP8_LINEAR) return fail(DITTO_ERR_SHAPE, "%s: packed batches are not supported with fp8 linear layers", who);
+    return DITTO_OK;
+}
+
+int ditto_text_precompute_packed(ditto_model_t m, const float* text, const int32_t* cu_text, int B, int S_T, int max_T, void* cond,
+                                 size_t cond_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+    if (!m || !text || !cu_text || !cond || !workspace) return fail(DITTO_ERR_ARG, "bad argument to ditto_text_precompute_packed");
+    if (int rc = check_packed_model("ditto_text_precompute_packed", m)) return rc;
+    if (int rc = check_packed("ditto_text_precompute_packed", B, S_T, 1, S_T, max_T)) return rc;
+    const ditto_config& c = m->cfg;
+    if (cond_bytes < ditto_packed_cond_bytes(&c, B, S_T)) return fail(DITTO_ERR_SIZE, "cond buffer too small");
+    const size_t need = al((size_t)S_T * c.text_dim * 2) + al((size_t)B * c.text_dim * 4);
+    if (workspace_bytes < need)
+        return fail(DITTO_ERR_SIZE, "workspace too small for text precompute: %zu < %zu", workspace_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    const int d = c.hidden_dim, L = c.num_layers, dp = cfg_dp(c);
+    char* ws = (char*)workspace;
+    void* textbf = ws;
+    float* pooled = (float*)(ws + al((size_t)S_T * c.text_dim * 2));
+    char* kv = (char*)cond;
+    float* tmod = (float*)(kv + al((size_t)S_T * L * 2 * dp * 2));
+    HIP_TRY(launch_cast_bf16(text, textbf, (size_t)S_T * c.text_dim, s));
+    GemmArgs g{};   // the K/V rows of every layer: row-wise, over the packed rows as they are
+    g.A = textbf; g.lda = c.text_dim; g.W = m->Wkv; g.bias = m->bkv; g.out = kv; g.ldo = L * 2 * dp;
+    g.M = S_T; g.N = L * 2 * dp; g.K = d;
+    HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
+    HIP_TRY(launch_text_mod_packed(text, cu_text, S_T, max_T, m->wx, m->bx, pooled, tmod, B, c.text_dim, d, s));
+    return DITTO_OK;
+}
+
+static int forward_packed(const char* who, ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                          const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T, const float* rope_cos,
+                          const float* rope_sin, float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+    if (!m || !x || !cond || !t || !cu_speech || !cu_text || !rope_cos || !rope_sin || !eps_out || !workspace)
+        return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    if (int rc = check_packed_model(who, m)) return rc;
+    if (int rc = check_packed(who, B, S, max_N, S_T, max_T)) return rc;
+    const PackedWsPlan pw = plan_ws_packed(m->cfg, B, S, S_T);
+    if (workspace_bytes < pw.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, pw.total);
+    char* ws = (char*)workspace;
+    const PackedRows pk{cu_speech, cu_text, (const int32_t*)(ws + pw.utt), (const int32_t*)(ws + pw.pos), B, max_N, max_T, S, S_T};
+    return forward_impl(m, x, cond, t, 1, S, S_T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream, nullptr, nullptr, &pk);
+}
+
+int ditto_forward_packed_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                              const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T, const float* rope_cos,
+                              const float* rope_sin, float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                              const ditto_call_opts* opts) {
+    if (int rc = check_call_opts(opts)) return rc;
+    CallScope scope(opts);
+    return forward_packed("ditto_forward_packed_opts", m, x, cond, t, cu_speech, cu_text, B, S, max_N, S_T, max_T, rope_cos, rope_sin,
+                          eps_out, workspace, workspace_bytes, stream);
+}
 
 int ditto_block_forward(ditto_model_t m, int layer, float* h, const void* cond, int cond_layer, int B, int N, int T,
                         const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
@@ -1183,6 +1302,43 @@ int ditto_attention_resid_varlen_bf16(const void* q, int ldq, const void* k, int
                             (const float*)resid_in, ldr, resid_is_bf16, q_len, kv_len, B, H, Sq, Skv, dh, stream);
 }
 
+// packed batches: the packed instantiations of the fused head_dim-64 kernels (attention_packed.hip); q pre-scaled, no workspace
+static int attention_packed(const char* fn, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                            float* resid_out, const float* resid_in, int ldr, int resid_is_bf16, const int32_t* cu_q,
+                            const int32_t* cu_kv, int B, int H, int Sq, int Skv, int max_q, int max_kv, int dh, ditto_stream_t stream) {
+    if (!q || !k || !v || !(out || resid_out) || !cu_q || !cu_kv) return fail(DITTO_ERR_ARG, "%s: null pointer", fn);
+    if (H <= 0) return fail(DITTO_ERR_SHAPE, "%s: H must be positive", fn);
+    if (int rc = check_packed(fn, B, Sq, max_q, Skv, max_kv)) return rc;
+    if (dh != 64) return fail(DITTO_ERR_SHAPE, "%s: packed attention needs head_dim 64", fn);
+    if ((ldq | ldk | ldv) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh)
+        return fail(DITTO_ERR_SHAPE, "%s: ldq / ldk / ldv must cover H * 64 columns in multiples of 8", fn);
+    if (out && (ldo % 8 || ldo < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldo must cover H * 64 columns in multiples of 8", fn);
+    if (resid_out && (ldr % 8 || ldr < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldr must cover H * 64 columns in multiples of 8", fn);
+    AttnArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out_bf16 = out; a.ldo = out ? ldo : 8;
+    a.resid_f32 = resid_out; a.ldr = ldr; a.resid_in = resid_in; a.resid_bf16 = resid_is_bf16 != 0;
+    a.B = B; a.H = H; a.Sq = max_q; a.Skv = max_kv; a.dh = dh; a.scale = 1.0f; a.q_prescaled = true;
+    a.cu_q = cu_q; a.cu_kv = cu_kv; a.q_rows = Sq; a.kv_rows = Skv;
+    HIP_TRY(launch_attention(a, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_attention_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                const int32_t* cu_q, const int32_t* cu_kv, int B, int H, int Sq, int Skv, int max_q, int max_kv, int dh,
+                                ditto_stream_t stream) {
+    if (!out) return fail(DITTO_ERR_ARG, "ditto_attention_packed_bf16: null pointer");
+    return attention_packed("ditto_attention_packed_bf16", q, ldq, k, ldk, v, ldv, out, ldo, nullptr, nullptr, 0, 0, cu_q, cu_kv, B, H,
+                            Sq, Skv, max_q, max_kv, dh, stream);
+}
+
+int ditto_attention_resid_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid_in,
+                                      void* resid_out, int ldr, int resid_is_bf16, const int32_t* cu_q, const int32_t* cu_kv, int B, int H,
+                                      int Sq, int Skv, int max_q, int max_kv, int dh, ditto_stream_t stream) {
+    if (!resid_out) return fail(DITTO_ERR_ARG, "ditto_attention_resid_packed_bf16: null pointer");
+    return attention_packed("ditto_attention_resid_packed_bf16", q, ldq, k, ldk, v, ldv, nullptr, 0, (float*)resid_out,
+                            (const float*)resid_in, ldr, resid_is_bf16, cu_q, cu_kv, B, H, Sq, Skv, max_q, max_kv, dh, stream);
+}
+
 int ditto_vq_argmin(const float* latents, const float* codebook, int64_t* idx, int R, int K, int D, float* scratch_k,
                     ditto_stream_t stream) {
     if (!latents || !codebook || !idx || !scratch_k || R <= 0 || K <= 0 || D <= 0)
@@ -1266,6 +1422,42 @@ int ditto_guided_step_opts(ditto_model_t m, float* x2, const void* cond, const i
     ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
     HIP_TRY(launch_guided_update(x2, eps, noise, seeds, step, w, a, ce, cz, speech_len, B, N, m->cfg.hidden_dim, cfg != 0,
                                  (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                               const float* a, const float* ce, const float* cz, const int32_t* cu, int B, int S, int max_N, int d,
+                               int cfg, ditto_stream_t stream) {
+    if (!cu) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed: null cu");
+    if (int rc = check_guided_update("ditto_guided_update_packed", x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed("ditto_guided_update_packed", B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_guided_update_packed(x2, eps2, noise, seeds, step, w, a, ce, cz, cu, B, S, max_N, d, cfg != 0, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                  const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                                  const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
+                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                  ditto_stream_t stream, const ditto_call_opts* opts) {
+    if (!m) return fail(DITTO_ERR_ARG, "bad argument to ditto_guided_step_packed_opts");
+    if (int rc = check_guided_update("ditto_guided_step_packed_opts", x2, x2, noise, seeds, w, a, ce, cz, B, max_N, m->cfg.hidden_dim, cfg))
+        return rc;
+    if (B > 32767) return fail(DITTO_ERR_SHAPE, "ditto_guided_step_packed_opts: more than 32767 utterances");
+    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "ditto_guided_step_packed_opts: S must lie in [1, 2^30)");
+    if (int rc = check_call_opts(opts)) return rc;
+    CallScope scope(opts);
+    // under guidance the forward runs over the 2B utterances of [x; x] x [text; null]: cu_speech then holds 2B + 1 offsets over 2S rows
+    const int nb = cfg ? 2 * B : B, rows = cfg ? 2 * S : S;
+    const PackedWsPlan pw = plan_ws_packed(m->cfg, nb, rows, S_T > 0 ? S_T : 1);
+    if (workspace_bytes < pw.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, pw.total);
+    float* eps = (float*)((char*)workspace + pw.w.eps);
+    if (int rc = forward_packed("ditto_guided_step_packed_opts", m, x2, cond, t, cu_speech, cu_text, nb, rows, max_N, S_T, max_T, rope_cos,
+                                rope_sin, eps, workspace, workspace_bytes, stream))
+        return rc;
+    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+    HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim, cfg != 0,
+                                        (hipStream_t)stream));
     return DITTO_OK;
 }
 

@@ -307,12 +307,17 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     for (int i = 0; i < 2; ++i) { p.sA[i] = a.sA[i]; p.sW[i] = a.sW[i]; p.sO[i] = a.sO[i]; p.sR[i] = a.sR[i]; }
     p.out_esz = (epi == EPI_BIAS_RES_F32 || epi == EPI_BIAS_F32) ? 4 : 2;
     p.pre = (const bf16*)a.pre_bf16; p.ldpre = a.ldpre; p.colpart = a.colsum_partial;
+    if (epi == EPI_QKV_ROPE_PACKED) p.rope_pos = a.rope_pos;   // (shares pre's slot)
     if (nbatch > 1 && (a.fp8 || p.k_splits > 1 || nbatch > 65535)) return hipErrorInvalidValue;
     g_batch_y = nbatch;
     if (p.k_splits > 1 && (epi != EPI_BIAS_F32 || a.bias || a.fp8)) return hipErrorInvalidValue;
     switch (epi) {
         case EPI_QKV_ROPE:
             if (a.N % 64 || a.rope_cols % 64 || !a.rope_cos || !a.rope_sin || a.rope_rows_per_batch <= 0)
+                return hipErrorInvalidValue;
+            break;
+        case EPI_QKV_ROPE_PACKED:   // the tiled bf16 kernels of the plain QKV launch (gemm.hip 128 x 128, gemm256.hip): no split, no batch
+            if (a.N % 64 || a.rope_cols % 64 || !a.rope_cos || !a.rope_sin || !a.rope_pos || a.fp8 || nbatch > 1 || p.k_splits > 1)
                 return hipErrorInvalidValue;
             break;
         case EPI_GATED:
@@ -346,6 +351,8 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     if (epi == EPI_GATED_FP8) return hipErrorInvalidValue;   // fp8 output only from the fp8 GEMM
     // split-K and batched launches exist on the 128x128 structures only
     int forced = p.k_splits > 1 ? 128 : (nbatch > 1 ? 128 : g_gemm_tile);
+    // the packed QKV epilogue exists on the 128 x 128 and 256 x 256 structures: any other forced tile takes the rule below
+    if (epi == EPI_QKV_ROPE_PACKED && forced != 127 && forced != 128 && forced != 256) forced = 0;
     // the ReLU epilogue is built for the 128x128 and 256x256 structures only
     if (epi == EPI_BIAS_RELU_BF16 && forced != 128 && forced != 127 && forced != 256)
         forced = (long)((a.M + 255) / 256) * ((a.N + 255) / 256) >= 4 * 256 ? 256 : 128;
@@ -353,7 +360,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     // Ping-pong 128x256 tiles (gemm_pp.hip) by GEMM class.  pp_mask bits: 1 narrow bf16 output (cross q-proj), 2 narrow
     // fp32 in-place residual with K <= 1024 (cross out-proj), 4 narrow fp32 output (final projection), 8 narrow residual
     // with long K (fc2), 16 QKV + RoPE, 32 gated MLP.
-    if (forced == 0 && gemm_pp_supports(p, epi) && a.M >= 128) {
+    if (forced == 0 && epi != EPI_QKV_ROPE_PACKED && gemm_pp_supports(p, epi) && a.M >= 128) {
         const bool narrow = a.N <= 1024;
         int cls = 0;
         if (epi == EPI_BIAS_BF16 && narrow) cls = 1;
@@ -395,12 +402,12 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     // the final K = 1536 projection 92.1 vs 97.2 us, the K = 768 d x d GEMMs 69.2 vs 70.1 us (noise): long K only.
     // (K >= 768 since the end of round 1: at M = 16384 the K = 768 d x d GEMMs are exactly one round of 256 such tiles,
     // 32.8 us against 41.2 on the 128x128 kernel; at M = 32768 the two are equal, 69.9 / 71.7.)
-    if (forced == 0 && gemm192_supports(epi) && a.N % 192 == 0 && a.K >= 768) {
+    if (forced == 0 && epi != EPI_QKV_ROPE_PACKED && gemm192_supports(epi) && a.N % 192 == 0 && a.K >= 768) {
         const long t192 = (long)((a.M + 255) / 256) * (a.N / 192);
         const long r192 = (t192 + 255) / 256, r128 = (tp128 + 255) / 256;
         if (t192 >= 256 && r192 * 3 <= r128 * 2) return launch_gemm192(p, epi, s);
     }
-    if (forced == 129 || (forced == 0 && tp128 >= 2 * 256 && a.K >= 1536)) {
+    if (forced == 129 || (forced == 0 && epi != EPI_QKV_ROPE_PACKED && tp128 >= 2 * 256 && a.K >= 1536)) {
         p.tiles_m = (a.M + 255) / 256;
         p.tiles_n = (a.N + 127) / 128;
         return launch_gemm_p128(p, epi, s);
@@ -416,6 +423,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
             case EPI_BIAS_BF16: return launch_deep_t<EPI_BIAS_BF16>(p, s);
             case EPI_BIAS_RES_F32: return launch_deep_t<EPI_BIAS_RES_F32>(p, s);
             case EPI_QKV_ROPE: return launch_deep_t<EPI_QKV_ROPE>(p, s);
+            case EPI_QKV_ROPE_PACKED: return launch_deep_t<EPI_QKV_ROPE_PACKED>(p, s);
             case EPI_GATED: return launch_deep_t<EPI_GATED>(p, s);
             case EPI_BIAS_F32: return launch_deep_t<EPI_BIAS_F32>(p, s);
             case EPI_BIAS_RELU_BF16: return launch_deep_t<EPI_BIAS_RELU_BF16>(p, s);
@@ -427,6 +435,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
         case EPI_BIAS_BF16: return launch_t<EPI_BIAS_BF16>(p, s);
         case EPI_BIAS_RES_F32: return launch_t<EPI_BIAS_RES_F32>(p, s);
         case EPI_QKV_ROPE: return launch_t<EPI_QKV_ROPE>(p, s);
+        case EPI_QKV_ROPE_PACKED: return launch_t<EPI_QKV_ROPE_PACKED>(p, s);
         case EPI_GATED: return launch_t<EPI_GATED>(p, s);
         case EPI_BIAS_F32: return launch_t<EPI_BIAS_F32>(p, s);
         case EPI_BIAS_RELU_BF16: return launch_t<EPI_BIAS_RELU_BF16>(p, s);

@@ -303,7 +303,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
     // drain of the previous tile then overlaps the first phases instead of stalling the whole workgroup.
     // (EPI_GATED_PRE: 8 + 16 stores, counted as 16; EPI_GATED_BWD: 32 loads + 32 stores + 8 partial-sum stores, counted as 32 —
     // fewer than the truth only makes the wait stricter)
-    constexpr int EPI_STORES = (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_RELU_BF16 || EPI == EPI_GATED_PRE) ? 16 : EPI == EPI_QKV_ROPE ? 16
+    constexpr int EPI_STORES = (EPI == EPI_BIAS_BF16 || EPI == EPI_BIAS_RELU_BF16 || EPI == EPI_GATED_PRE) ? 16 : (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_PACKED) ? 16
                                : (EPI == EPI_GATED || EPI == EPI_GATED_FP8) ? 8 : 32;
     bool prev_interior = false;   // previous tile of this workgroup was interior (its store count is exact)
 
@@ -576,7 +576,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
             // (The two waves of a SIMD run their epilogues at the same time and the arbiter serves the OLDER one first — the stamps
             // have wave group 0 through in 5 300 ticks and group 1 in 9 900.  s_setprio swapped between the groups halfway through
             // the row blocks changes nothing: gated GEMM 266.0 vs 266.0 us in the model, profiles/r04_step_ab_epi_prio.txt.)
-            if constexpr (EPI == EPI_QKV_ROPE) {
+            if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_PACKED) {
                 if (cb >= p.rope_cols) {   // a v head: bias only (wave-uniform)
 #pragma unroll
                     for (int m = 0; m < 8; ++m) epilogue_row<EPI_BIAS_BF16, true>(p, r0 + m * 16, cb, acc[m], bias4, fq);
@@ -718,6 +718,7 @@ hipError_t launch_gemm256(const GemmParams& p_in, GemmEpilogue epi, hipStream_t 
         case EPI_BIAS_BF16: return launch256_t<EPI_BIAS_BF16>(p, s);
         case EPI_BIAS_RES_F32: return launch256_t<EPI_BIAS_RES_F32>(p, s);
         case EPI_QKV_ROPE: return launch256_t<EPI_QKV_ROPE>(p, s);
+        case EPI_QKV_ROPE_PACKED: return launch256_t<EPI_QKV_ROPE_PACKED>(p, s);
         case EPI_GATED: return launch256_t<EPI_GATED>(p, s);
         case EPI_GATED_PRE: return launch256_t<EPI_GATED_PRE>(p, s);
         case EPI_GATED_BWD: return launch256_t<EPI_GATED_BWD>(p, s);

@@ -31,7 +31,11 @@ struct GemmParams {
     int batch_inner;                      // gemm128 only: blockIdx.y = zo * batch_inner + zi
     long long sA[2], sW[2], sO[2], sR[2];
     int out_esz;                          // bytes per output element (batch offset of `out`)
-    const bf16* pre; int ldpre;           // EPI_GATED_BWD
+    union {
+        const bf16* pre;                  // EPI_GATED_BWD
+        const int32_t* rope_pos;          // EPI_QKV_ROPE_PACKED: int32 [M] position of each row inside its utterance
+    };                                    // (one slot: the layout, and with it every other instantiation's code, stays as it was)
+    int ldpre;                            // EPI_GATED_BWD
     float* colpart;                       // EPI_GATED_BWD
 };
 
@@ -266,7 +270,7 @@ DITTO_DEV void epilogue_row(const GemmParams& p, int row, int cbase, const f32x4
             store_bf16_pair<FAST>(rowp, cbase, pr[0], pr[1], fq, p.N, p.flags & ~GF_DIAG_LINEAR_STORE, p.ldo2);
             store_bf16_pair<FAST>(rowp, cbase + 32, pr[2], pr[3], fq, p.N, p.flags & ~GF_DIAG_LINEAR_STORE, p.ldo2);
         }
-    } else if constexpr (EPI == EPI_QKV_ROPE) {
+    } else if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_PACKED) {
         float v[4][4];
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
@@ -274,7 +278,8 @@ DITTO_DEV void epilogue_row(const GemmParams& p, int row, int cbase, const f32x4
             for (int e = 0; e < 4; ++e) v[n][e] = acc[n][e] + bias[n][e];
         }
         if (FAST || cbase < p.rope_cols) {  // a q or k head (FAST: the caller runs v columns through EPI_BIAS_BF16) (width 64): half-split RoPE, pair (j, j+32); DiT.py:52-72
-            const int pos = row % p.rope_rpb;
+            // (packed: the row's position inside its utterance; the same float position gives the padded layout's bits)
+            const int pos = EPI == EPI_QKV_ROPE_PACKED ? p.rope_pos[row < p.M ? row : p.M - 1] : row % p.rope_rpb;
             float r[4][4];
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
@@ -466,7 +471,7 @@ DITTO_DEV bool epilogue_fast_ok(const GemmParams& p, int m0, int n0, int BM_, in
     if (m0 + BM_ > p.M || n0 + BN_ > p.N || (p.out2 && EPI != EPI_GATED_PRE) || (p.flags & must_off) || !(p.flags & GF_STORE_NT)) return false;
     if ((p.flags & GF_SLOW_EPILOGUE) || !p.bias) return false;
     if constexpr (EPI == EPI_BIAS_RES_F32) return p.residual != nullptr;
-    if constexpr (EPI == EPI_QKV_ROPE) return p.rope_freq_rev != nullptr;   // table-free angles (the model path)
+    if constexpr (EPI == EPI_QKV_ROPE || EPI == EPI_QKV_ROPE_PACKED) return p.rope_freq_rev != nullptr;   // table-free angles (the model path)
     return true;
 }
 

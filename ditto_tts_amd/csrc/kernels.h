@@ -53,6 +53,17 @@ hipError_t launch_text_mod(const float* text, const float* wx, const float* bx, 
                            int B, int T, int dt, int d, hipStream_t s, const int32_t* text_len = nullptr);
 // variable-length batches: rows r >= len[b] of x [B, N, d] fp32 set to 0 (len device int32 [B], clamped into [1, N])
 hipError_t launch_zero_rows_past_len(float* x, const int32_t* len, int B, int N, int d, hipStream_t s);
+// packed batches (utterance b owns rows [cu[b], cu[b+1]) of a [S, .] buffer, cu device int32 [B + 1]):
+//   row map: utt[r] = the utterance of row r (clamped into [0, B)), pos[r] = r - cu[utt[r]] clamped into [0, max_len)
+hipError_t launch_packed_row_map(const int32_t* cu, int B, int S, int max_len, int32_t* utt, int32_t* pos, hipStream_t s);
+//   text half of GlobalAdaLN: the mean over rows [cu_t[b], cu_t[b+1]) of text [S_T, dt] (the varlen pool's association at
+//   T = T_b), then tmod[b] = Wx silu(pooled[b]) + bx
+hipError_t launch_text_mod_packed(const float* text, const int32_t* cu_t, int S_T, int max_T, const float* wx, const float* bx,
+                                  float* pooled, float* tmod, int B, int dt, int d, hipStream_t s);
+//   AdaLN entry over S packed rows: utterance of row r = utt[r] (launch_packed_row_map), else as launch_adaln
+hipError_t launch_adaln_packed(const float* x, const float* ttab, const float* tmod, const int64_t* t, int steps, const int32_t* utt,
+                               float* h_out, void* raw_bf16, int ldraw, int S, int d, hipStream_t s, bool h_bf16,
+                               const float* g1, const float* be1, void* u1_bf16);
 hipError_t launch_apply_rope_f32(const float* pos, const float* x, float* out, int B, int N, int H, int dh,
                                  hipStream_t s);
 hipError_t launch_rope_tables(const float* inv_freq, float* cos_out, float* sin_out, int N, int half, hipStream_t s);
@@ -190,7 +201,10 @@ enum GemmEpilogue {
     EPI_GATED_BWD = 7,
     // EPI_GATED that ALWAYS writes the pre-activations (out2_bf16 [M, N], packed order) as well: the training forward, as
     // its own instantiation so that it takes the straight-line epilogue the inference kernel has.  256 x 256 kernel only.
-    EPI_GATED_PRE = 8
+    EPI_GATED_PRE = 8,
+    // EPI_QKV_ROPE over a PACKED batch (utterances concatenated along the rows): the RoPE position of row r is rope_pos[r] (the
+    // row's offset inside its utterance, int32 [M]) instead of r % rope_rows_per_batch.  Tiled kernels only (gemm.hip, gemm256.hip).
+    EPI_QKV_ROPE_PACKED = 9
 };
 struct GemmArgs {
     const void* A; int lda;          // bf16 [M, K], row stride lda (elements)
@@ -217,6 +231,7 @@ struct GemmArgs {
     long long sA[2], sW[2], sO[2], sR[2];
     const void* pre_bf16; int ldpre;   // EPI_GATED_BWD: the forward's pre-activations, bf16 [M, ldpre]
     float* colsum_partial;             // EPI_GATED_BWD: fp32 [2 * ceil(M / 256), 2N]
+    const int32_t* rope_pos;           // EPI_QKV_ROPE_PACKED: int32 [M], row r's position inside its utterance
 };
 // may the fc2 dgrad + gated backward of M rows, F = N act columns, run as ONE launch (EPI_GATED_BWD)?
 bool gemm_gated_bwd_fused_ok(int M, int F);
@@ -243,6 +258,11 @@ hipError_t launch_cfg_combine(const float* eps2, float* out, float w, size_t ele
 hipError_t launch_guided_update(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
                                 const float* w, const float* a, const float* ce, const float* cz, const int32_t* speech_len,
                                 int B, int N, int d, bool cfg, hipStream_t s);
+// packed batch: x2, eps2 [S, d] (CFG: [2S, d] = [conditional; unconditional]); utterance b owns rows [cu[b], cu[b+1]) of each half.
+// The same expressions as launch_guided_update; Philox quad index = the utterance-local one, ((row - cu[b]) d + col) / 4.
+hipError_t launch_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
+                                       const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                       int B, int S, int max_N, int d, bool cfg, hipStream_t s);
 
 // ---------------- attention.hip ----------------
 struct AttnArgs {
@@ -266,6 +286,12 @@ struct AttnArgs {
     // utterance, nullptr = the whole padded Sq / Skv.  Either set: the VARLEN instantiations of attn64q / attn64p.
     const int32_t* q_len = nullptr;
     const int32_t* kv_len = nullptr;
+    // packed batch (with cu_q / cu_kv set, q_len / kv_len unused): device int32 [B + 1] row offsets of every utterance in q / out /
+    // resid (q_rows rows) and k / v (kv_rows rows); Sq / Skv are then the longest lengths.  The packed instantiations of
+    // attn64q / attn64p (attention_packed.hip).
+    const int32_t* cu_q = nullptr;
+    const int32_t* cu_kv = nullptr;
+    int q_rows = 0, kv_rows = 0;
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 size_t attention_workspace_bytes(int B, int H, int Sq, int Skv, int dh);

@@ -19,6 +19,8 @@ namespace ditto {
 // MODE 0: affine (gamma/beta may be null) -> bf16.   MODE 1: AdaLN modulation -> fp32 + bf16(raw x).
 // ------------------------------------------------------------------------------------------------
 // MODE 2: as MODE 0 with fp8 e4m3 output (A operand of the fp8 QKV / fc1|gate GEMMs, config C5)
+// MODE 3: as MODE 1 over a packed batch: the utterance of row r is utt[r] (launch_packed_row_map), not r / rows_per_batch; the
+// int32 map rides in the `gamma` slot, which the AdaLN modes do not read (the other modes' signature and code stay as they were)
 template <int CH, int MODE>
 __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                  const float* __restrict__ beta, const float* __restrict__ ttab,
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, co
             }
         }
     } else {
-        const int b_idx = row / rows_per_batch;
+        const int b_idx = MODE == 3 ? reinterpret_cast<const int32_t*>(gamma)[row] : row / rows_per_batch;
         long long ts = t ? t[b_idx] : b_idx;               // t == nullptr: table row = batch index
         ts = ts < 0 ? 0 : (ts >= steps ? steps - 1 : ts);  // nn.Embedding would raise; clamp instead of faulting
         const f32x4* tt = reinterpret_cast<const f32x4*>(ttab + (size_t)ts * 2 * d);
@@ -201,6 +203,13 @@ hipError_t launch_adaln(const float* x, const float* ttab, const float* tmod, co
                         const float* g1, const float* be1, void* u1_bf16) {
     return ln_dispatch<1>(x, nullptr, nullptr, ttab, tmod, t, steps, N, (bf16*)raw_bf16, ldraw, h_out, B * N, d, s, 0,
                           h_bf16 ? 1 : 0, g1, be1, (bf16*)u1_bf16);
+}
+hipError_t launch_adaln_packed(const float* x, const float* ttab, const float* tmod, const int64_t* t, int steps, const int32_t* utt,
+                               float* h_out, void* raw_bf16, int ldraw, int S, int d, hipStream_t s, bool h_bf16,
+                               const float* g1, const float* be1, void* u1_bf16) {
+    if (!utt) return hipErrorInvalidValue;
+    return ln_dispatch<3>(x, reinterpret_cast<const float*>(utt), nullptr, ttab, tmod, t, steps, 1, (bf16*)raw_bf16, ldraw, h_out, S, d,
+                          s, 0, h_bf16 ? 1 : 0, g1, be1, (bf16*)u1_bf16);
 }
 // LayerNorm of a BF16 row stream (the bf16 residual stream): x bf16 [M, d]
 hipError_t launch_layernorm_xbf16(const void* x_bf16, const float* gamma, const float* beta, void* out_bf16, int ldo, int M,
@@ -569,6 +578,65 @@ hipError_t launch_text_mod(const float* text, const float* wx, const float* bx, 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(text_mod_kernel, dim3((2 * d + 3) / 4, B), dim3(256), 0, s, pooled, wx, bx, tmod, dt, 2 * d);
+    return hipGetLastError();
+}
+
+// packed batches: utterance b's first row and length from the offsets cu [B + 1], clamped like attn_span (attn_common.h): the row
+// into [0, rows - 1], the length into [1, min(max_len, rows - first)] — a bad offset cannot address outside the buffer
+DITTO_DEV int packed_span(const int32_t* cu, int b, int max_len, int rows, int& len) {
+    int lo = cu[b];
+    lo = lo < 0 ? 0 : (lo > rows - 1 ? rows - 1 : lo);
+    const int n = cu[b + 1] - lo, cap = rows - lo < max_len ? rows - lo : max_len;
+    len = n < 1 ? 1 : (n > cap ? cap : n);
+    return lo;
+}
+
+// the text pool over rows [cu_t[b], cu_t[b+1]) of text [S_T, dt]: text_pool_kernel<true>'s association at T = T_b
+__global__ __launch_bounds__(256) void text_pool_packed_kernel(const float* __restrict__ text, float* __restrict__ pooled,
+                                                               const int32_t* __restrict__ cu_t, int S_T, int max_T, int dt) {
+    __shared__ float red[4][64];
+    const int col = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6, b = blockIdx.y;
+    int Tb;
+    const int r0 = packed_span(cu_t, b, max_T, S_T, Tb);
+    float acc = 0.f;
+    if (col < dt)
+        for (int r = g; r < Tb; r += 4) acc += text[((size_t)r0 + r) * dt + col];
+    red[g][threadIdx.x & 63] = acc;
+    __syncthreads();
+    if (g == 0 && col < dt)
+        pooled[(size_t)b * dt + col] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) +
+                                        (red[2][threadIdx.x] + red[3][threadIdx.x])) / (float)Tb;
+}
+hipError_t launch_text_mod_packed(const float* text, const int32_t* cu_t, int S_T, int max_T, const float* wx, const float* bx,
+                                  float* pooled, float* tmod, int B, int dt, int d, hipStream_t s) {
+    if (!cu_t || S_T <= 0 || max_T <= 0 || B <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(text_pool_packed_kernel, dim3((dt + 63) / 64, B), dim3(256), 0, s, text, pooled, cu_t, S_T, max_T, dt);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(text_mod_kernel, dim3((2 * d + 3) / 4, B), dim3(256), 0, s, pooled, wx, bx, tmod, dt, 2 * d);
+    return hipGetLastError();
+}
+
+// packed batches: the per-row map of the AdaLN entry and the QKV + RoPE epilogue, once per call.  Row r belongs to the last utterance
+// b with cu[b] <= r (binary search over the B + 1 offsets, clamped into [0, B)); its position r - cu[b] is clamped into [0, max_len).
+// Every row of the map is written whatever the offsets hold.
+__global__ __launch_bounds__(256) void packed_row_map_kernel(const int32_t* __restrict__ cu, int B, int S, int max_len,
+                                                             int32_t* __restrict__ utt, int32_t* __restrict__ pos) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= S) return;
+    int lo = 0, hi = B - 1;   // invariant: the answer lies in [lo, hi]
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cu[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    const int p = r - cu[lo];
+    utt[r] = lo;
+    pos[r] = p < 0 ? 0 : (p >= max_len ? max_len - 1 : p);
+}
+hipError_t launch_packed_row_map(const int32_t* cu, int B, int S, int max_len, int32_t* utt, int32_t* pos, hipStream_t s) {
+    if (!cu || B <= 0 || S <= 0 || max_len <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(packed_row_map_kernel, dim3((S + 255) / 256), dim3(256), 0, s, cu, B, S, max_len, utt, pos);
     return hipGetLastError();
 }
 

@@ -11,7 +11,7 @@ from typing import Dict, Mapping, Optional, Tuple
 import torch
 
 from . import hip
-from .varlen import validate_lengths
+from .varlen import doubled_cu_seqlens, validate_cu_seqlens, validate_lengths
 from .config import DiTTOConfig
 
 
@@ -27,10 +27,14 @@ class TextCond:
     """Step-invariant conditioning of one utterance batch: cached cross-attention K/V of every layer and the
     text half of the AdaLN modulation (ditto_text_precompute)."""
 
-    def __init__(self, buf: torch.Tensor, B: int, T: int, text_lengths: Optional[torch.Tensor] = None):
+    def __init__(self, buf: torch.Tensor, B: int, T: int, text_lengths: Optional[torch.Tensor] = None,
+                 cu_seqlens: Optional[torch.Tensor] = None, max_len: Optional[int] = None):
         # text_lengths: device int32 [B] of a variable-length batch (ditto_text_precompute_varlen), carried with the K/V cache so
         # that a forward cannot pair this conditioning with other lengths; None = every utterance has all T rows
         self.buf, self.B, self.T, self.text_lengths = buf, B, T, text_lengths
+        # cu_seqlens: device int32 [B + 1] of a PACKED conditioning (ditto_text_precompute_packed): T is then the packed text rows
+        # S_T and max_len the longest utterance's; only the *_packed entries take it
+        self.cu_seqlens, self.max_len = cu_seqlens, max_len
 
 
 class StepGraph:
@@ -122,6 +126,15 @@ class DenoiseEngine:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def workspace_packed(self, B: int, S: int, S_T: int) -> torch.Tensor:
+        need = self.lib.ditto_packed_workspace_bytes(C.byref(self._ccfg), B, S, S_T)
+        if need == 0:
+            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
     def rope_tables(self, N: int):
         if N not in self._rope:
             half = self.cfg.head_dim // 2
@@ -163,6 +176,117 @@ class DenoiseEngine:
                                       f"{self.cfg.head_dim}")
         if getattr(self.cfg, "fp8_linear", False):
             raise NotImplementedError("variable-length batches are not supported with fp8_linear=True")
+
+    def _require_packed(self):
+        if self.cfg.head_dim != 64:
+            raise NotImplementedError(f"packed batches need head_dim 64 (the fused attention kernels); this model's is "
+                                      f"{self.cfg.head_dim}")
+        if getattr(self.cfg, "fp8_linear", False):
+            raise NotImplementedError("packed batches are not supported with fp8_linear=True")   # (modules.require_packed: the same rule)
+
+    @staticmethod
+    def _max_len(cu: torch.Tensor) -> int:
+        return int((cu[1:] - cu[:-1]).max())
+
+    def prepare_text_packed(self, text_emb: torch.Tensor, text_cu_seqlens, max_text_seqlen: Optional[int] = None) -> TextCond:
+        """text_emb [S_T, text_dim], utterance b in rows [cu[b], cu[b+1]) -> TextCond of a packed batch
+        (ditto_text_precompute_packed): the K/V rows of every layer over the S_T rows and the per-utterance text modulation."""
+        self._require_packed()
+        text = self._f32(text_emb, "text_emb")
+        if text.dim() != 2 or text.shape[1] != self.cfg.text_dim:
+            raise ValueError(f"text_emb: [S_T, {self.cfg.text_dim}] expected, got {list(text.shape)}")
+        S_T = int(text.shape[0])
+        B = len(text_cu_seqlens) - 1
+        ct = validate_cu_seqlens(text_cu_seqlens, B, S_T, S_T if max_text_seqlen is None else int(max_text_seqlen), "text_cu_seqlens")
+        max_T = self._max_len(ct) if max_text_seqlen is None else int(max_text_seqlen)
+        nb = self.lib.ditto_packed_cond_bytes(C.byref(self._ccfg), B, S_T)
+        if nb == 0:
+            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
+        buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        ws = self.workspace_packed(B, B, S_T)
+        ctd = ct.to(self.device)
+        hip.check(self.lib.ditto_text_precompute_packed(self.handle, text.data_ptr(), ctd.data_ptr(), B, S_T, max_T, buf.data_ptr(), nb,
+                                                        ws.data_ptr(), ws.numel(), _stream()))
+        return TextCond(buf, B, S_T, cu_seqlens=ctd, max_len=max_T)
+
+    def _packed_cond(self, cond: TextCond, B: int):
+        if cond.cu_seqlens is None:
+            raise ValueError("a packed call needs a packed conditioning (prepare_text_packed)")
+        if cond.B != B:
+            raise ValueError(f"the conditioning holds {cond.B} utterances, the call {B}")
+
+    def forward_packed(self, x: torch.Tensor, cond: TextCond, t: torch.Tensor, cu_seqlens, max_seqlen: Optional[int] = None,
+                       out: Optional[torch.Tensor] = None, opts: Optional[hip.CallOpts] = None):
+        """DiTTO.forward over a packed batch (ditto_forward_packed_opts): x [S, d], utterance b in rows [cu[b], cu[b+1]), with the
+        packed conditioning `cond` and t [B] -> eps fp32 [S, d]."""
+        self._require_packed()
+        xf = self._f32(x, "x")
+        if xf.dim() != 2 or xf.shape[1] != self.cfg.hidden_dim:
+            raise ValueError(f"x: [S, {self.cfg.hidden_dim}] expected, got {list(xf.shape)}")
+        S = int(xf.shape[0])
+        B = len(cu_seqlens) - 1
+        self._packed_cond(cond, B)
+        cu = validate_cu_seqlens(cu_seqlens, B, S, S if max_seqlen is None else int(max_seqlen), "cu_seqlens")
+        max_N = self._max_len(cu) if max_seqlen is None else int(max_seqlen)
+        tt = self._t64(t, B)
+        if out is None:
+            out = torch.empty_like(xf)
+        ws = self.workspace_packed(B, S, cond.T)
+        c, s = self.rope_tables(max_N)
+        cud = cu.to(self.device)
+        hip.check(self.lib.ditto_forward_packed_opts(self.handle, xf.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(),
+                                                     cond.cu_seqlens.data_ptr(), B, S, max_N, cond.T, cond.max_len, c.data_ptr(),
+                                                     s.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+                                                     None if opts is None else C.byref(opts)))
+        return out
+
+    def guided_offsets_packed(self, cu_seqlens, S: int, max_seqlen: Optional[int], cfg: bool):
+        """(device int32 offsets of the step's forward — [cu; S + cu[1:]] under guidance —, max_N) of a packed guided step"""
+        self._require_packed()
+        B = len(cu_seqlens) - 1
+        cu = validate_cu_seqlens(cu_seqlens, B, S, S if max_seqlen is None else int(max_seqlen), "cu_seqlens")
+        max_N = self._max_len(cu) if max_seqlen is None else int(max_seqlen)
+        return (doubled_cu_seqlens(cu) if cfg else cu).to(self.device), max_N
+
+    def guided_step_packed_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, a: torch.Tensor, ce: torch.Tensor,
+                            cz: torch.Tensor, w: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                            seeds: Optional[torch.Tensor] = None, step: int = 0, cu_seqlens=None, max_seqlen: Optional[int] = None,
+                            offsets=None, opts: Optional[hip.CallOpts] = None):
+        """guided_step_ over a packed batch, IN PLACE on x2 fp32 [2S, d] ([x; x], w given) or [S, d]
+        (ditto_guided_step_packed_opts).  `offsets`: guided_offsets_packed(...) built once per sampling call (else built here from
+        `cu_seqlens`); `cond`: prepare_text_packed over [text; null] (2B utterances) or text.  noise: packed fp32 [S, d]."""
+        if not (x2.is_cuda and x2.dtype == torch.float32 and x2.is_contiguous() and x2.dim() == 2):
+            raise ValueError("guided_step_packed_ needs a contiguous fp32 CUDA state tensor [rows, d] (it is updated in place)")
+        cfg = w is not None
+        nb = 2 * B if cfg else B
+        rows, d = x2.shape
+        if cfg and rows % 2:
+            raise ValueError("x2 must hold [x; x] under guidance")
+        S = rows // 2 if cfg else rows
+        self._packed_cond(cond, nb)
+        if noise is not None and seeds is not None:
+            raise ValueError("noise and seeds are exclusive")
+        if offsets is None:
+            offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, cfg)
+        cud, max_N = offsets
+        if cud.shape != (nb + 1,):
+            raise ValueError(f"offsets: [{nb + 1}] expected")
+        tt = self._t64(t, nb)
+        sd = self._t64(seeds, B) if seeds is not None else None
+        if noise is not None:
+            noise = self._f32(noise, "noise")
+            if noise.shape != (S, d):
+                raise ValueError(f"noise must have shape {(S, d)}")
+        for name, v in (("a", a), ("ce", ce), ("cz", cz), ("w", w)):
+            if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
+                raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
+        ws = self.workspace_packed(nb, rows, cond.T)
+        c, s = self.rope_tables(max_N)
+        hip.check(self.lib.ditto_guided_step_packed_opts(
+            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(noise),
+            _ptr(sd), int(step) & 0xFFFFFFFF, _ptr(w), a.data_ptr(), ce.data_ptr(), cz.data_ptr(), B, S, max_N, cond.T, cond.max_len,
+            int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+        return x2
 
     def _lengths(self, speech_lengths, cond: TextCond, B: int, N: int):
         """(speech, text) device int32 [B] of a varlen call, or None for a dense one"""

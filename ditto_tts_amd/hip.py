@@ -172,6 +172,17 @@ SYMBOLS = {
     "ditto_guided_update": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ditto_guided_step_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp,
                                     _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    # packed batches (utterances concatenated along the rows, device int32 offsets [B + 1])
+    "ditto_packed_workspace_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
+    "ditto_packed_cond_bytes": (_sz, [C.POINTER(Config), _i, _i]),
+    "ditto_text_precompute_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
+    "ditto_forward_packed_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp,
+                                       C.POINTER(CallOpts)]),
+    "ditto_attention_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ditto_attention_resid_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ditto_guided_update_packed": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_guided_step_packed_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                           _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),
     "ditto_tape_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
     "ditto_train_workspace_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),

@@ -236,6 +236,14 @@ class _BlocksOnlyEngine(DenoiseEngine):
         self._generation += 1
 
 
+def require_packed(cfg):
+    """packed batches run the fused head_dim-64 attention and bf16 linears only (NotImplementedError otherwise)"""
+    if cfg.head_dim != 64:
+        raise NotImplementedError(f"packed batches need head_dim 64 (the fused attention kernels); this model's is {cfg.head_dim}")
+    if getattr(cfg, "fp8_linear", False):
+        raise NotImplementedError("packed batches are not supported with fp8_linear=True")
+
+
 class DiTTO(nn.Module):
     """Full DiT noise predictor — reference src/model/DiTTO.py:7-126.
 
@@ -379,6 +387,24 @@ class DiTTO(nn.Module):
         eng = self.engine(x.device)
         cond = self.text_cond(text_emb.to(x.device), x.shape[1])
         out = eng.forward(x, cond, t)
+        return out if x.dtype == torch.float32 else out.to(x.dtype)
+
+    def forward_packed(self, x, cu_seqlens, text_emb, text_cu_seqlens, t, *, max_seqlen=None, max_text_seqlen=None):
+        """forward over a PACKED batch: x [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb [S_T, text_dim]
+        with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]), t [B] long -> eps [S, d].  Utterance b gets what
+        forward(x[cu[b]:cu[b+1]][None], text_emb[cu_t[b]:cu_t[b+1]][None], t[b:b+1]) gives; no padding is allocated or computed.
+        Offsets: list, tuple or int tensor [B + 1] (validated on the host); max_seqlen / max_text_seqlen bound the lengths (default:
+        the longest).  Inference only, head_dim 64, bf16 linears."""
+        # the refusals first: each is decided by the configuration and the grad mode alone
+        if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad or
+                                        any(p.requires_grad for n, p in self.named_parameters() if not n.startswith("nac."))):
+            raise NotImplementedError("ditto_tts_amd: packed batches are inference only (run under torch.no_grad() or with frozen "
+                                      "parameters)")
+        require_packed(self.cfg)
+        _require_cuda(x, "x")
+        eng = self.engine(x.device)
+        cond = eng.prepare_text_packed(text_emb.to(x.device), text_cu_seqlens, max_text_seqlen)
+        out = eng.forward_packed(x, cond, t, cu_seqlens, max_seqlen)
         return out if x.dtype == torch.float32 else out.to(x.dtype)
 
     def cosine_beta_schedule(self, timesteps, s=0.008):

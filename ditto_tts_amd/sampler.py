@@ -384,6 +384,91 @@ class SpeechGenerator:
                              lengths=lens, opts=opts)
         return x2[:B].clone() if cfg else x2
 
+    @torch.no_grad()
+    def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
+                             null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
+                             batch_class=None):
+        """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
+        [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
+        sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
+        [x; x] (offsets [cu; S + cu[1:]]) x [text; null].
+        `null_text_emb` (required with guidance) is packed like the text — the same rows and offsets — unless `null_text_cu_seqlens`
+        gives its own offsets.  `seeds`: x_T = ditto_noise_normal(seeds, 0xFFFFFFFF) per utterance and Philox z at each step's tag,
+        the bits sample_guided(seeds=) draws for the same utterance.  `noises[i]` (a sequence or callable): packed [S, d].
+        `batch_class`: class_rows = (2 with guidance, else 1) * batch_class * max length, what sample_guided pins for the padded
+        batch of batch_class utterances.  Returns fp32 [S, d]."""
+        if seeds is not None and noises is not None:
+            raise ValueError("seeds= excludes noises=")
+        m = self.ditto_model
+        from .modules import require_packed
+        require_packed(m.cfg)
+        eng = m.engine(torch.empty(0, device=self.device).device)
+        from .varlen import validate_cu_seqlens
+        S, d = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        B = len(cu_seqlens) - 1
+        cu = validate_cu_seqlens(cu_seqlens, B, S, S, "cu_seqlens")
+        N = int((cu[1:] - cu[:-1]).max())
+        gv = guidance_vector(guidance, B)
+        cfg = gv is not None
+        if cfg and null_text_emb is None:
+            raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
+        if null_text_cu_seqlens is not None and not cfg:
+            raise ValueError("null_text_cu_seqlens without guidance")
+        schedule = strided_schedule(self.alphas_cumprod, n_steps, eta)
+        text = text_emb.to(eng.device).float()
+        S_T = int(text.shape[0])
+        ct = validate_cu_seqlens(text_cu_seqlens, B, S_T, S_T, "text_cu_seqlens")
+        if cfg:
+            null = null_text_emb.to(eng.device).float()
+            if null_text_cu_seqlens is None:
+                null, cn = null.expand_as(text), ct
+            else:
+                cn = validate_cu_seqlens(null_text_cu_seqlens, B, int(null.shape[0]), int(null.shape[0]), "null_text_cu_seqlens")
+            text = torch.cat([text, null], dim=0).contiguous()
+            ct = torch.cat([ct, ct[-1] + cn[1:]])
+        cond = eng.prepare_text_packed(text, ct)
+        nb = 2 * B if cfg else B
+        offsets = eng.guided_offsets_packed(cu, S, N, cfg)
+        x2 = torch.empty(2 * S if cfg else S, d, dtype=torch.float32, device=eng.device)
+        x = x2[:S]
+        if seeds is not None:
+            seeds = seeds.to(eng.device).long().contiguous()
+            if seeds.shape != (B,):
+                raise ValueError(f"seeds must have shape [{B}]")
+        if seeds is not None and not cond_by_audio:
+            # x_T: ditto_noise_normal over the padded [B, N, d] (the numbers of sample_guided(seeds=)), packed row by row
+            from .varlen import pack
+            xt = torch.empty(B, N, d, dtype=torch.float32, device=eng.device)
+            eng.noise_normal_(xt, seeds, 0xFFFFFFFF)
+            x.copy_(pack(xt, (cu[1:] - cu[:-1]).tolist())[0])
+        else:
+            x.copy_(torch.randn_like(audio_emb.float()) if not cond_by_audio else audio_emb)
+        if cfg:
+            x2[S:].copy_(x)
+        coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
+        w = gv.to(eng.device) if cfg else None
+        t_tensor = torch.empty(nb, device=eng.device, dtype=torch.long)
+        z = torch.empty(S, d, dtype=torch.float32, device=eng.device) if seeds is None else None
+        opts = None
+        if batch_class is not None:
+            from .hip import CallOpts
+            opts = CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
+        for i, (t_val, _, _, sigma) in enumerate(schedule):
+            t_tensor.fill_(t_val)
+            noise = sd = None
+            if sigma != 0.0:
+                if seeds is not None:
+                    sd = seeds
+                elif noises is None:
+                    z.normal_()
+                    noise = z
+                else:
+                    z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
+                    noise = z
+            eng.guided_step_packed_(x2, cond, t_tensor, B, coef[i, 0], coef[i, 1], coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val,
+                                    offsets=offsets, opts=opts)
+        return x2[:S].clone() if cfg else x2
+
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):
         return self.__p_sample(x, t, text_emb, noise)

@@ -102,3 +102,128 @@ def attention_resid(q, k, v, H: int, resid, q_len=None, kv_len=None, resid_in=No
         resid.stride(1), int(resid.dtype == torch.bfloat16), ql.data_ptr() if ql is not None else None,
         kl.data_ptr() if kl is not None else None, B, H, Sq, Skv, 64, torch.cuda.current_stream(q.device).cuda_stream))
     return resid
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Packed batches (include/ditto_hip.h, the *_packed_* entries): utterances concatenated along the row axis, utterance b owning rows
+# [cu[b], cu[b+1]) — flash-attention's varlen layout.  No padding is allocated, moved or computed.
+
+def validate_cu_seqlens(cu, B: int, total: int, max_len: int, name: str = "cu_seqlens") -> torch.Tensor:
+    """`cu` (list / tuple of ints, or an integer tensor on any device) as a CPU int32 tensor of shape [B + 1]: starting at 0, strictly
+    increasing (no empty utterance), no utterance longer than `max_len`, ending at `total` (the packed rows).  Anything else raises
+    ValueError."""
+    if isinstance(cu, torch.Tensor):
+        if cu.dtype.is_floating_point or cu.dtype.is_complex or cu.dtype == torch.bool:
+            raise ValueError(f"{name}: an integer tensor is needed, got {cu.dtype}")
+        t = cu.detach().to("cpu", torch.int64)
+    elif isinstance(cu, (list, tuple)):
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in cu):
+            raise ValueError(f"{name}: a list / tuple of ints is needed")
+        t = torch.tensor(list(cu), dtype=torch.int64)
+    else:
+        raise ValueError(f"{name}: a list, tuple or integer tensor is needed, got {type(cu).__name__}")
+    if t.dim() != 1 or t.shape[0] != B + 1:
+        raise ValueError(f"{name}: shape [{B + 1}] expected, got {list(t.shape)}")
+    if int(t[0]) != 0:
+        raise ValueError(f"{name}: the offsets must start at 0, got {int(t[0])}")
+    lens = t[1:] - t[:-1]
+    if B and int(lens.min()) < 1:
+        raise ValueError(f"{name}: the offsets must increase strictly (an utterance of {int(lens.min())} rows)")
+    if B and int(lens.max()) > max_len:
+        raise ValueError(f"{name}: an utterance of {int(lens.max())} rows exceeds the maximum length {max_len}")
+    if int(t[-1]) != total:
+        raise ValueError(f"{name}: the last offset {int(t[-1])} differs from the {total} packed rows")
+    if total >= 2 ** 31:
+        raise ValueError(f"{name}: {total} rows exceed int32 offsets")
+    return t.to(torch.int32)
+
+
+def cu_from_lengths(lengths) -> torch.Tensor:
+    """[0, l0, l0 + l1, ...] as a CPU int32 tensor"""
+    lens = torch.as_tensor(lengths, dtype=torch.int64).cpu()
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(lens, 0)]).to(torch.int32)
+
+
+def doubled_cu_seqlens(cu) -> torch.Tensor:
+    """The offsets of [x; x] (classifier-free guidance: the batch followed by itself): [cu; S + cu[1:]]"""
+    c = torch.as_tensor(cu).to(torch.int64)
+    return torch.cat([c, c[-1] + c[1:]]).to(torch.int32)
+
+
+def pack(x: torch.Tensor, lengths):
+    """x [B, N, ...] padded, utterance b valid in x[b, :lengths[b]] -> (packed [S, ...] on x's device, cu int32 [B + 1] on x's
+    device)."""
+    B, N = int(x.shape[0]), int(x.shape[1])
+    lens = validate_lengths(lengths, B, N, "lengths").to(torch.int64)
+    cu = cu_from_lengths(lens)
+    mask = torch.arange(N).unsqueeze(0) < lens.unsqueeze(1)                     # [B, N]
+    packed = x[mask.to(x.device)]
+    return packed.contiguous(), cu.to(x.device)
+
+
+def unpack(packed: torch.Tensor, cu, N: int, fill: float = 0.0) -> torch.Tensor:
+    """packed [S, ...] with offsets cu [B + 1] -> padded [B, N, ...] (rows past an utterance's length hold `fill`)."""
+    c = torch.as_tensor(cu).detach().to("cpu", torch.int64)
+    B = int(c.shape[0]) - 1
+    c = validate_cu_seqlens(c, B, int(packed.shape[0]), N, "cu").to(torch.int64)
+    out = torch.full((B, N, *packed.shape[1:]), fill, dtype=packed.dtype, device=packed.device)
+    lens = c[1:] - c[:-1]
+    mask = torch.arange(N).unsqueeze(0) < lens.unsqueeze(1)
+    out[mask.to(packed.device)] = packed
+    return out
+
+
+def _dev_cu(cu, B, total, max_len, name, device):
+    return validate_cu_seqlens(cu, B, total, max_len, name).to(device)
+
+
+def _check_packed(t, name, H, dtypes=(torch.bfloat16,)):
+    if t.dtype not in dtypes or t.dim() != 2 or not t.is_cuda or t.stride(1) != 1 or t.shape[1] < H * 64:
+        raise ValueError(f"{name}: a {' / '.join(str(d) for d in dtypes)} [rows, >= {H * 64}] tensor on the GPU with unit column stride "
+                         f"is needed, got {t.dtype} {list(t.shape)}")
+
+
+def attention_packed(q, k, v, H: int, cu_q, cu_kv, max_q=None, max_kv=None, out=None):
+    """softmax(q k^T) v per (utterance, head) of a packed batch (q carries scale * log2(e)): q / out [Sq, >= H*64] with utterance
+    b in rows [cu_q[b], cu_q[b+1]), k / v [Skv, >= H*64] with rows [cu_kv[b], cu_kv[b+1]); bf16.  Returns `out`."""
+    for n, x in (("q", q), ("k", k), ("v", v)):
+        _check_packed(x, n, H)
+    if v.shape[0] != k.shape[0] or not (q.device == k.device == v.device):
+        raise ValueError("k and v need one row count, q / k / v one device")
+    Sq, Skv = int(q.shape[0]), int(k.shape[0])
+    B = len(cu_q) - 1
+    max_q = Sq if max_q is None else int(max_q)
+    max_kv = Skv if max_kv is None else int(max_kv)
+    cq = _dev_cu(cu_q, B, Sq, max_q, "cu_q", q.device)
+    ck = _dev_cu(cu_kv, B, Skv, max_kv, "cu_kv", q.device)
+    if out is None:
+        out = torch.zeros(Sq, H * 64, dtype=torch.bfloat16, device=q.device)
+    _check_packed(out, "out", H)
+    if out.shape[0] != Sq:
+        raise ValueError(f"out: {Sq} rows expected")
+    hip.check(hip.lib().ditto_attention_packed_bf16(
+        q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), out.data_ptr(), out.stride(0),
+        cq.data_ptr(), ck.data_ptr(), B, H, Sq, Skv, max_q, max_kv, 64, torch.cuda.current_stream(q.device).cuda_stream))
+    return out
+
+
+def attention_resid_packed(q, k, v, H: int, resid, cu_q, cu_kv, max_q=None, max_kv=None, resid_in=None):
+    """The residual form of attention_packed: resid[i, h*64 + c] = resid_in[...] + attention (resid_in None: in place); resid fp32 or
+    bf16 [Sq, >= H*64].  Returns `resid`."""
+    for n, x in (("q", q), ("k", k), ("v", v)):
+        _check_packed(x, n, H)
+    src = resid if resid_in is None else resid_in
+    _check_packed(resid, "resid", H, (torch.float32, torch.bfloat16))
+    if src.dtype != resid.dtype or src.stride() != resid.stride() or src.shape != resid.shape or resid.shape[0] != q.shape[0]:
+        raise ValueError("resid / resid_in: one dtype, shape and row stride, q's rows")
+    Sq, Skv = int(q.shape[0]), int(k.shape[0])
+    B = len(cu_q) - 1
+    max_q = Sq if max_q is None else int(max_q)
+    max_kv = Skv if max_kv is None else int(max_kv)
+    cq = _dev_cu(cu_q, B, Sq, max_q, "cu_q", q.device)
+    ck = _dev_cu(cu_kv, B, Skv, max_kv, "cu_kv", q.device)
+    hip.check(hip.lib().ditto_attention_resid_packed_bf16(
+        q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), src.data_ptr(), resid.data_ptr(),
+        resid.stride(0), int(resid.dtype == torch.bfloat16), cq.data_ptr(), ck.data_ptr(), B, H, Sq, Skv, max_q, max_kv, 64,
+        torch.cuda.current_stream(q.device).cuda_stream))
+    return resid

@@ -473,6 +473,53 @@ int ditto_guided_step_opts(ditto_model_t m, float* x2, const void* cond, const i
                            const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
                            const ditto_call_opts* opts);
 
+/* ---- Packed batches (flash-attention's varlen layout): utterances concatenated along the rows, no padding.  Utterance b owns speech
+ * rows [cu_speech[b], cu_speech[b+1]) of x / eps [S, d] and text rows [cu_text[b], cu_text[b+1]) of text [S_T, text_dim]; RoPE
+ * positions and the text mean-pool are local to the utterance, so utterance b is x[cu[b]:cu[b+1]] with text[cu_t[b]:cu_t[b+1]].
+ * cu_speech / cu_text: DEVICE int32 [B + 1].  Precondition (not checked: that would need a sync): they start at 0, increase strictly,
+ * end at S / S_T, and no utterance is longer than max_N / max_T.  The kernels clamp every offset and length into the buffers, so a bad
+ * value gives wrong rows but never an out-of-bounds access.  head_dim 64 and bf16 linear layers only (DITTO_ERR_SHAPE otherwise).
+ * Every launch but the attention, the AdaLN entry and the QKV + RoPE epilogue is row-wise and runs over the S rows as they are; the
+ * full-row GEMMs run unrotated (as varlen).  Under the same kernel class (ditto_call_opts.class_rows) an utterance gets the bits of
+ * the padded varlen path (ditto_forward_varlen_opts) — it serves the same reference calls, DiTTO.forward and sample_guided.
+ * ditto_packed_workspace_bytes / ditto_packed_cond_bytes: the sizes for B utterances of S speech and S_T text rows (0 on a bad
+ *   argument).  ditto_text_precompute_packed: text fp32 [S_T, text_dim] -> cond (K/V rows [S_T, ...] | tmod [B, 2d]).
+ * ditto_forward_packed_opts: DiTTO.forward -> eps_out fp32 [S, d]; rope_cos / rope_sin: ditto_rope_tables(max_N) (used only under
+ *   the A/B table flag of the QKV epilogue). */
+size_t ditto_packed_workspace_bytes(const ditto_config* cfg, int B, int S, int S_T);
+size_t ditto_packed_cond_bytes(const ditto_config* cfg, int B, int S_T);
+int ditto_text_precompute_packed(ditto_model_t m, const float* text, const int32_t* cu_text, int B, int S_T, int max_T, void* cond,
+                                 size_t cond_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream);
+int ditto_forward_packed_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                              const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T, const float* rope_cos,
+                              const float* rope_sin, float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                              const ditto_call_opts* opts);
+/* Unit entries of the packed attention (as ditto_attention_varlen_bf16 / ditto_attention_resid_varlen_bf16): q / out / resid rows
+ * [cu_q[b], cu_q[b+1]) of Sq, k / v rows [cu_kv[b], cu_kv[b+1]) of Skv; max_q / max_kv bound the lengths.  Rows outside an
+ * utterance's own range (other utterances' included) are never read or written.  An utterance gets the arithmetic of the padded
+ * varlen kernel: the same bits. */
+int ditto_attention_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                const int32_t* cu_q, const int32_t* cu_kv, int B, int H, int Sq, int Skv, int max_q, int max_kv, int dh,
+                                ditto_stream_t stream);
+int ditto_attention_resid_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid_in,
+                                      void* resid_out, int ldr, int resid_is_bf16, const int32_t* cu_q, const int32_t* cu_kv, int B, int H,
+                                      int Sq, int Skv, int max_q, int max_kv, int dh, ditto_stream_t stream);
+/* ditto_guided_update over a packed batch (sample_guided): x2, eps2 fp32 [S, d], or [2S, d] when cfg != 0 (rows [0, S)
+ *   conditional, [S, 2S) unconditional), utterance b < B owning rows [cu[b], cu[b+1]) of each half (cu: device int32 [B + 1]).  The
+ *   same expressions; the Philox quad index is utterance-local, ((row - cu[b]) d + col) / 4, so the step's z is
+ *   ditto_noise_normal(seeds, step)'s; `noise` is packed fp32 [S, d].  No padding, nothing zeroed.
+ * ditto_guided_step_packed_opts: the forward over x2's 2B (cfg) or B packed utterances, then that update: cu_speech device int32
+ *   [2B + 1] over the 2S rows of [x; x] (= [cu; S + cu[1:]]) or [B + 1]; cu_text the conditioning's (ditto_text_precompute_packed
+ *   over [text; null]); t int64 [2B or B].  Workspace: ditto_packed_workspace_bytes(cfg, 2B or B, 2S or S, S_T). */
+int ditto_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                               const float* a, const float* ce, const float* cz, const int32_t* cu, int B, int S, int max_N, int d,
+                               int cfg, ditto_stream_t stream);
+int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                  const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                                  const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
+                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                  ditto_stream_t stream, const ditto_call_opts* opts);
+
 /* ---- training: the backward of DiTTO.forward, so that the reference's training closure
  * (src/TrainDiTTO.py:55-95: model.train(); loss = mse(model(x_t, text, t), noise); loss.backward()) runs on this
  * library.  Gradients are fp32, in the reference's parameter layout (one pointer per state_dict key, as

@@ -9,10 +9,12 @@ statement reads, the last MFMA that wrote it is found on every path into the sta
 the wait states in between are counted: one per instruction, N + 1 per `s_nop N`.  v_mfma_f32_32x32x16_bf16 (8 passes) needs 12.
 The same counter is applied to hipcc's own vector reads of MFMA results: it must find none below 12, or the counting model is wrong.
     python tools/check_attn_loop.py          (compiles into a private temporary directory; exit code 1 on a finding)
-    python tools/check_attn_loop.py --varlen (the same checks on attention_varlen.hip: the VARLEN instantiations)"""
+    python tools/check_attn_loop.py --varlen (the same checks on attention_varlen.hip: the VARLEN instantiations)
+    python tools/check_attn_loop.py --packed (the same checks on attention_packed.hip: the packed instantiations)"""
 import os, re, subprocess, sys, tempfile
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = "attention_varlen.hip" if "--varlen" in sys.argv[1:] else "attention_p.hip"
+src = ("attention_varlen.hip" if "--varlen" in sys.argv[1:] else
+       "attention_packed.hip" if "--packed" in sys.argv[1:] else "attention_p.hip")
 tmp = tempfile.TemporaryDirectory()
 out = os.path.join(tmp.name, "check_attn_loop.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", root + "/include", "-I",
