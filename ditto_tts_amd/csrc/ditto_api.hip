@@ -74,9 +74,9 @@ ArenaPlan plan_arena(const ditto_config& c) {
     return p;
 }
 
-// ditto_text_precompute scratch (front of the same workspace): bf16(text) | pooled fp32
-static inline size_t text_scratch_bytes(const ditto_config& c, int B, int T) {
-    return al((size_t)B * T * c.text_dim * 2) + al((size_t)B * c.text_dim * 4);
+// ditto_text_precompute scratch (front of the same workspace) over `rows` text rows of B utterances: bf16(text) | pooled fp32
+static inline size_t text_scratch_bytes(const ditto_config& c, int B, size_t rows) {
+    return al(rows * c.text_dim * 2) + al((size_t)B * c.text_dim * 4);
 }
 
 // Small batches leave the long-K GEMMs of the step on a few dozen workgroups, each walking all of K alone (B = 1:
@@ -152,7 +152,7 @@ WsPlan plan_ws(const ditto_config& c, int B, int N, int T) {
     // split-K partials of fc2 / the final projection at small batch: sized for the most splits the option allows
     w.splitk_bytes = (long)((M + 127) / 128) * ((d + 127) / 128) <= 256 ? 8 * M * d * 4 : 0;
     w.splitk = take(w.splitk_bytes);
-    const size_t tneed = text_scratch_bytes(c, B, T);
+    const size_t tneed = text_scratch_bytes(c, B, (size_t)B * T);
     w.total = off > tneed ? off : tneed;
     return w;
 }
@@ -270,7 +270,7 @@ static PackedWsPlan plan_ws_packed(const ditto_config& c, int B, int S, int S_T)
     size_t off = p.w.total;
     p.utt = off; off += al((size_t)S * 4);
     p.pos = off; off += al((size_t)S * 4);
-    const size_t tneed = al((size_t)S_T * c.text_dim * 2) + al((size_t)B * c.text_dim * 4);
+    const size_t tneed = text_scratch_bytes(c, B, (size_t)S_T);
     p.total = off > tneed ? off : tneed;
     return p;
 }
@@ -683,40 +683,51 @@ int ditto_rope_tables(ditto_model_t m, int N, float* cos_out, float* sin_out, di
     return DITTO_OK;
 }
 
-static int text_precompute(ditto_model_t m, const float* text, const int32_t* text_len, int B, int T, void* cond, size_t cond_bytes,
-                           void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
-    if (!m || !text || !cond || !workspace || B <= 0 || T <= 0)
-        return fail(DITTO_ERR_ARG, "bad argument to ditto_text_precompute");
+// the text precompute of a padded (rows = B * T, text_len optional) or packed (cu_text given: rows = S_T, T = max_T) conditioning,
+// after the entry's own checks: bf16(text) | pooled fp32 at the front of the workspace, the K/V rows of every layer (row-wise over
+// the `rows` text rows), then the per-utterance text modulation
+static int text_precompute(ditto_model_t m, const float* text, const int32_t* text_len, const int32_t* cu_text, int B, int T,
+                           size_t rows, void* cond, size_t cond_bytes, size_t cond_need, void* workspace, size_t workspace_bytes,
+                           ditto_stream_t stream) {
     const ditto_config& c = m->cfg;
-    if (cond_bytes < ditto_cond_bytes(&c, B, T)) return fail(DITTO_ERR_SIZE, "cond buffer too small");
-    const size_t need = text_scratch_bytes(c, B, T);
+    if (cond_bytes < cond_need) return fail(DITTO_ERR_SIZE, "cond buffer too small");
+    const size_t need = text_scratch_bytes(c, B, rows);
     if (workspace_bytes < need) return fail(DITTO_ERR_SIZE, "workspace too small for text precompute: %zu < %zu",
                                             workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     const int d = c.hidden_dim, L = c.num_layers, dp = cfg_dp(c);
     char* ws = (char*)workspace;
     void* textbf = ws;
-    float* pooled = (float*)(ws + al((size_t)B * T * c.text_dim * 2));
+    float* pooled = (float*)(ws + al(rows * c.text_dim * 2));
     char* kv = (char*)cond;
-    float* tmod = (float*)(kv + al((size_t)B * T * L * 2 * dp * 2));
-    HIP_TRY(launch_cast_bf16(text, textbf, (size_t)B * T * c.text_dim, s));
+    float* tmod = (float*)(kv + al(rows * L * 2 * dp * 2));
+    HIP_TRY(launch_cast_bf16(text, textbf, rows * c.text_dim, s));
     GemmArgs g{};
     g.A = textbf; g.lda = c.text_dim; g.W = m->Wkv; g.bias = m->bkv; g.out = kv; g.ldo = L * 2 * dp;
-    g.M = B * T; g.N = L * 2 * dp; g.K = d;
+    g.M = (int)rows; g.N = L * 2 * dp; g.K = d;
     HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
-    if (!m->blocks_only) HIP_TRY(launch_text_mod(text, m->wx, m->bx, pooled, tmod, B, T, c.text_dim, d, s, text_len));
+    if (cu_text) HIP_TRY(launch_text_mod_packed(text, cu_text, (int)rows, T, m->wx, m->bx, pooled, tmod, B, c.text_dim, d, s));
+    else if (!m->blocks_only) HIP_TRY(launch_text_mod(text, m->wx, m->bx, pooled, tmod, B, T, c.text_dim, d, s, text_len));
     return DITTO_OK;
+}
+
+static int text_precompute_padded(ditto_model_t m, const float* text, const int32_t* text_len, int B, int T, void* cond,
+                                  size_t cond_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+    if (!m || !text || !cond || !workspace || B <= 0 || T <= 0)
+        return fail(DITTO_ERR_ARG, "bad argument to ditto_text_precompute");
+    return text_precompute(m, text, text_len, nullptr, B, T, (size_t)B * T, cond, cond_bytes, ditto_cond_bytes(&m->cfg, B, T), workspace,
+                           workspace_bytes, stream);
 }
 
 int ditto_text_precompute(ditto_model_t m, const float* text, int B, int T, void* cond, size_t cond_bytes,
                           void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
-    return text_precompute(m, text, nullptr, B, T, cond, cond_bytes, workspace, workspace_bytes, stream);
+    return text_precompute_padded(m, text, nullptr, B, T, cond, cond_bytes, workspace, workspace_bytes, stream);
 }
 
 int ditto_text_precompute_varlen(ditto_model_t m, const float* text, const int32_t* text_len, int B, int T, void* cond,
                                  size_t cond_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
     if (!text_len) return fail(DITTO_ERR_ARG, "ditto_text_precompute_varlen: null text_len");
-    return text_precompute(m, text, text_len, B, T, cond, cond_bytes, workspace, workspace_bytes, stream);
+    return text_precompute_padded(m, text, text_len, B, T, cond, cond_bytes, workspace, workspace_bytes, stream);
 }
 
 // thread-scoped options: the stack of what ditto_call_opts_push found in force (kernels.h t_opts is the top)
@@ -887,25 +898,8 @@ int ditto_text_precompute_packed(ditto_model_t m, const float* text, const int32
     if (!m || !text || !cu_text || !cond || !workspace) return fail(DITTO_ERR_ARG, "bad argument to ditto_text_precompute_packed");
     if (int rc = check_packed_model("ditto_text_precompute_packed", m)) return rc;
     if (int rc = check_packed("ditto_text_precompute_packed", B, S_T, 1, S_T, max_T)) return rc;
-    const ditto_config& c = m->cfg;
-    if (cond_bytes < ditto_packed_cond_bytes(&c, B, S_T)) return fail(DITTO_ERR_SIZE, "cond buffer too small");
-    const size_t need = al((size_t)S_T * c.text_dim * 2) + al((size_t)B * c.text_dim * 4);
-    if (workspace_bytes < need)
-        return fail(DITTO_ERR_SIZE, "workspace too small for text precompute: %zu < %zu", workspace_bytes, need);
-    hipStream_t s = (hipStream_t)stream;
-    const int d = c.hidden_dim, L = c.num_layers, dp = cfg_dp(c);
-    char* ws = (char*)workspace;
-    void* textbf = ws;
-    float* pooled = (float*)(ws + al((size_t)S_T * c.text_dim * 2));
-    char* kv = (char*)cond;
-    float* tmod = (float*)(kv + al((size_t)S_T * L * 2 * dp * 2));
-    HIP_TRY(launch_cast_bf16(text, textbf, (size_t)S_T * c.text_dim, s));
-    GemmArgs g{};   // the K/V rows of every layer: row-wise, over the packed rows as they are
-    g.A = textbf; g.lda = c.text_dim; g.W = m->Wkv; g.bias = m->bkv; g.out = kv; g.ldo = L * 2 * dp;
-    g.M = S_T; g.N = L * 2 * dp; g.K = d;
-    HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
-    HIP_TRY(launch_text_mod_packed(text, cu_text, S_T, max_T, m->wx, m->bx, pooled, tmod, B, c.text_dim, d, s));
-    return DITTO_OK;
+    return text_precompute(m, text, nullptr, cu_text, B, max_T, (size_t)S_T, cond, cond_bytes, ditto_packed_cond_bytes(&m->cfg, B, S_T),
+                           workspace, workspace_bytes, stream);
 }
 
 static int forward_packed(const char* who, ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1003,19 +997,34 @@ int ditto_p_sample_update(float* x, const float* eps, const float* noise, const 
     return DITTO_OK;
 }
 
+// one reverse-diffusion step after the entry's own checks: the forward into the workspace's eps slot, then the update with z from
+// `noise` or, with seeds, from Philox of (seed, step); varlen (speech_len given): rows past each length of x then become 0.  The
+// noise of element i of an utterance is a function of (seed, step, i): in the padded layout i is the same row-major index as at the
+// utterance's own length, so a varlen trajectory is comparable to the solo one.
+static int p_sample_step(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise, const int64_t* seeds,
+                         uint32_t step, const int32_t* speech_len, const int32_t* text_len, const float* betas, const float* alphas,
+                         const float* alphas_cumprod, int B, int N, int T, const float* rope_cos, const float* rope_sin, void* workspace,
+                         size_t workspace_bytes, ditto_stream_t stream) {
+    const WsPlan w = plan_ws(m->cfg, B, N, T);
+    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    float* eps = (float*)((char*)workspace + w.eps);
+    if (int rc = forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
+        return rc;
+    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+    const size_t per = (size_t)N * m->cfg.hidden_dim;   // a multiple of 64 (check_cfg): what the update kernels' float4 rows need
+    if (seeds) HIP_TRY(launch_p_sample_update_seeded(x, eps, seeds, step, t, betas, alphas, alphas_cumprod, B, per, (hipStream_t)stream));
+    else if (int rc = ditto_p_sample_update(x, eps, noise, t, betas, alphas, alphas_cumprod, B, per, stream)) return rc;
+    if (speech_len) HIP_TRY(launch_zero_rows_past_len(x, speech_len, B, N, m->cfg.hidden_dim, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 int ditto_p_sample(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise,
                    const float* betas, const float* alphas, const float* alphas_cumprod, int B, int N, int T,
                    const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                    ditto_stream_t stream) {
     if (!m || !workspace) return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample");
-    const WsPlan w = plan_ws(m->cfg, B, N, T);
-    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
-    float* eps = (float*)((char*)workspace + w.eps);
-    if (int rc = ditto_forward(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream))
-        return rc;
-    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-    return ditto_p_sample_update(x, eps, noise, t, betas, alphas, alphas_cumprod, B,
-                                 (size_t)N * m->cfg.hidden_dim, stream);
+    return p_sample_step(m, x, cond, t, noise, nullptr, 0, nullptr, nullptr, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin,
+                         workspace, workspace_bytes, stream);
 }
 
 int ditto_p_sample_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise,
@@ -1042,17 +1051,8 @@ int ditto_p_sample_seeded(ditto_model_t m, float* x, const void* cond, const int
                           size_t workspace_bytes, ditto_stream_t stream) {
     if (!m || !workspace || !seeds || !betas || !alphas || !alphas_cumprod)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample_seeded");
-    const WsPlan w = plan_ws(m->cfg, B, N, T);
-    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
-    float* eps = (float*)((char*)workspace + w.eps);
-    if (int rc = ditto_forward(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream))
-        return rc;
-    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-    const size_t per = (size_t)N * m->cfg.hidden_dim;
-    if (per % 4) return fail(DITTO_ERR_SHAPE, "elems_per_utt must be a multiple of 4");
-    HIP_TRY(launch_p_sample_update_seeded(x, eps, seeds, step, t, betas, alphas, alphas_cumprod, B, per,
-                                          (hipStream_t)stream));
-    return DITTO_OK;
+    return p_sample_step(m, x, cond, t, nullptr, seeds, step, nullptr, nullptr, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin,
+                         workspace, workspace_bytes, stream);
 }
 
 int ditto_p_sample_seeded_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const int64_t* seeds,
@@ -1065,18 +1065,8 @@ int ditto_p_sample_seeded_varlen_opts(ditto_model_t m, float* x, const void* con
     if (B <= 0 || N <= 0 || T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_p_sample_seeded_varlen_opts: B, N and T must be positive");
     if (int rc = check_call_opts(opts)) return rc;
     CallScope scope(opts);
-    const WsPlan w = plan_ws(m->cfg, B, N, T);
-    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
-    float* eps = (float*)((char*)workspace + w.eps);
-    if (int rc = forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
-        return rc;
-    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-    const size_t per = (size_t)N * m->cfg.hidden_dim;
-    // the noise of element i of an utterance is a function of (seed, step, i): in the padded layout i is the same row-major index as
-    // at the utterance's own length, so a varlen trajectory is comparable to the solo one; rows >= N_b of x then become 0
-    HIP_TRY(launch_p_sample_update_seeded(x, eps, seeds, step, t, betas, alphas, alphas_cumprod, B, per, (hipStream_t)stream));
-    HIP_TRY(launch_zero_rows_past_len(x, speech_len, B, N, m->cfg.hidden_dim, (hipStream_t)stream));
-    return DITTO_OK;
+    return p_sample_step(m, x, cond, t, nullptr, seeds, step, speech_len, text_len, betas, alphas, alphas_cumprod, B, N, T, rope_cos,
+                         rope_sin, workspace, workspace_bytes, stream);
 }
 
 int ditto_p_sample_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise,
@@ -1088,15 +1078,8 @@ int ditto_p_sample_varlen_opts(ditto_model_t m, float* x, const void* cond, cons
     if (B <= 0 || N <= 0 || T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_p_sample_varlen_opts: B, N and T must be positive");
     if (int rc = check_call_opts(opts)) return rc;
     CallScope scope(opts);
-    const WsPlan w = plan_ws(m->cfg, B, N, T);
-    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
-    float* eps = (float*)((char*)workspace + w.eps);
-    if (int rc = forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
-        return rc;
-    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-    HIP_TRY(launch_p_sample_update(x, eps, noise, t, betas, alphas, alphas_cumprod, B, (size_t)N * m->cfg.hidden_dim, (hipStream_t)stream));
-    HIP_TRY(launch_zero_rows_past_len(x, speech_len, B, N, m->cfg.hidden_dim, (hipStream_t)stream));
-    return DITTO_OK;
+    return p_sample_step(m, x, cond, t, noise, nullptr, 0, speech_len, text_len, betas, alphas, alphas_cumprod, B, N, T, rope_cos,
+                         rope_sin, workspace, workspace_bytes, stream);
 }
 
 int ditto_p_sample_seeded_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const int64_t* seeds,
@@ -1265,21 +1248,32 @@ int ditto_attention_resid_bf16(const void* q, int ldq, const void* k, int ldk, c
     return DITTO_OK;
 }
 
-// variable-length batches: the fused head_dim-64 kernels' VARLEN instantiations (attn64q.h); q pre-scaled, no workspace
+// the operands of the fused head_dim-64 entries (varlen and packed, `layout`): head_dim 64, every leading dimension covering H * 64
+// columns in multiples of 8; then the fields of `a` they share (q pre-scaled, no workspace)
+static int attn64_args(const char* fn, const char* layout, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
+                       void* out, int ldo, float* resid_out, const float* resid_in, int ldr, int resid_is_bf16, int B, int H, int dh,
+                       AttnArgs& a) {
+    if (dh != 64) return fail(DITTO_ERR_SHAPE, "%s: %s attention needs head_dim 64", fn, layout);
+    if ((ldq | ldk | ldv) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh)
+        return fail(DITTO_ERR_SHAPE, "%s: ldq / ldk / ldv must cover H * 64 columns in multiples of 8", fn);
+    if (out && (ldo % 8 || ldo < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldo must cover H * 64 columns in multiples of 8", fn);
+    if (resid_out && (ldr % 8 || ldr < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldr must cover H * 64 columns in multiples of 8", fn);
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out_bf16 = out; a.ldo = out ? ldo : 8;
+    a.resid_f32 = resid_out; a.ldr = ldr; a.resid_in = resid_in; a.resid_bf16 = resid_is_bf16 != 0;
+    a.B = B; a.H = H; a.dh = dh; a.scale = 1.0f; a.q_prescaled = true;
+    return DITTO_OK;
+}
+
+// variable-length batches: the fused head_dim-64 kernels' VARLEN instantiations (attn64q.h)
 static int attention_varlen(const char* fn, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out,
                             int ldo, float* resid_out, const float* resid_in, int ldr, int resid_is_bf16, const int32_t* q_len,
                             const int32_t* kv_len, int B, int H, int Sq, int Skv, int dh, ditto_stream_t stream) {
     if (!q || !k || !v || !(out || resid_out)) return fail(DITTO_ERR_ARG, "%s: null pointer", fn);
     if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0) return fail(DITTO_ERR_SHAPE, "%s: B, H, Sq and Skv must be positive", fn);
-    if (dh != 64) return fail(DITTO_ERR_SHAPE, "%s: variable-length attention needs head_dim 64", fn);
-    if ((ldq | ldk | ldv) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh)
-        return fail(DITTO_ERR_SHAPE, "%s: ldq / ldk / ldv must cover H * 64 columns in multiples of 8", fn);
-    if (out && (ldo % 8 || ldo < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldo must cover H * 64 columns in multiples of 8", fn);
-    if (resid_out && (ldr % 8 || ldr < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldr must cover H * 64 columns in multiples of 8", fn);
     AttnArgs a{};
-    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out_bf16 = out; a.ldo = out ? ldo : 8;
-    a.resid_f32 = resid_out; a.ldr = ldr; a.resid_in = resid_in; a.resid_bf16 = resid_is_bf16 != 0;
-    a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.dh = dh; a.scale = 1.0f; a.q_prescaled = true;
+    if (int rc = attn64_args(fn, "variable-length", q, ldq, k, ldk, v, ldv, out, ldo, resid_out, resid_in, ldr, resid_is_bf16, B, H, dh, a))
+        return rc;
+    a.Sq = Sq; a.Skv = Skv;
     if (!q_len && !kv_len) return fail(DITTO_ERR_ARG, "%s: q_len and kv_len are both NULL (the dense entry serves that)", fn);
     a.q_len = q_len; a.kv_len = kv_len;
     HIP_TRY(launch_attention(a, (hipStream_t)stream));
@@ -1302,22 +1296,17 @@ int ditto_attention_resid_varlen_bf16(const void* q, int ldq, const void* k, int
                             (const float*)resid_in, ldr, resid_is_bf16, q_len, kv_len, B, H, Sq, Skv, dh, stream);
 }
 
-// packed batches: the packed instantiations of the fused head_dim-64 kernels (attention_packed.hip); q pre-scaled, no workspace
+// packed batches: the packed instantiations of the fused head_dim-64 kernels (attention_packed.hip)
 static int attention_packed(const char* fn, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
                             float* resid_out, const float* resid_in, int ldr, int resid_is_bf16, const int32_t* cu_q,
                             const int32_t* cu_kv, int B, int H, int Sq, int Skv, int max_q, int max_kv, int dh, ditto_stream_t stream) {
     if (!q || !k || !v || !(out || resid_out) || !cu_q || !cu_kv) return fail(DITTO_ERR_ARG, "%s: null pointer", fn);
     if (H <= 0) return fail(DITTO_ERR_SHAPE, "%s: H must be positive", fn);
     if (int rc = check_packed(fn, B, Sq, max_q, Skv, max_kv)) return rc;
-    if (dh != 64) return fail(DITTO_ERR_SHAPE, "%s: packed attention needs head_dim 64", fn);
-    if ((ldq | ldk | ldv) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh)
-        return fail(DITTO_ERR_SHAPE, "%s: ldq / ldk / ldv must cover H * 64 columns in multiples of 8", fn);
-    if (out && (ldo % 8 || ldo < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldo must cover H * 64 columns in multiples of 8", fn);
-    if (resid_out && (ldr % 8 || ldr < H * dh)) return fail(DITTO_ERR_SHAPE, "%s: ldr must cover H * 64 columns in multiples of 8", fn);
     AttnArgs a{};
-    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out_bf16 = out; a.ldo = out ? ldo : 8;
-    a.resid_f32 = resid_out; a.ldr = ldr; a.resid_in = resid_in; a.resid_bf16 = resid_is_bf16 != 0;
-    a.B = B; a.H = H; a.Sq = max_q; a.Skv = max_kv; a.dh = dh; a.scale = 1.0f; a.q_prescaled = true;
+    if (int rc = attn64_args(fn, "packed", q, ldq, k, ldk, v, ldv, out, ldo, resid_out, resid_in, ldr, resid_is_bf16, B, H, dh, a))
+        return rc;
+    a.Sq = max_q; a.Skv = max_kv;
     a.cu_q = cu_q; a.cu_kv = cu_kv; a.q_rows = Sq; a.kv_rows = Skv;
     HIP_TRY(launch_attention(a, (hipStream_t)stream));
     return DITTO_OK;

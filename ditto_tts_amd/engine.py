@@ -23,6 +23,15 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def require_fused_attention(cfg: DiTTOConfig, what: str):
+    """variable-length and packed batches (`what`) run the fused head_dim-64 attention and bf16 linears only
+    (NotImplementedError otherwise)"""
+    if cfg.head_dim != 64:
+        raise NotImplementedError(f"{what} need head_dim 64 (the fused attention kernels); this model's is {cfg.head_dim}")
+    if getattr(cfg, "fp8_linear", False):
+        raise NotImplementedError(f"{what} are not supported with fp8_linear=True")
+
+
 class TextCond:
     """Step-invariant conditioning of one utterance batch: cached cross-attention K/V of every layer and the
     text half of the AdaLN modulation (ditto_text_precompute)."""
@@ -117,8 +126,8 @@ class DenoiseEngine:
             pass
 
     # ------------------------------------------------------------------ buffers
-    def workspace(self, B: int, N: int, T: int) -> torch.Tensor:
-        need = self.lib.ditto_workspace_bytes(C.byref(self._ccfg), B, N, T)
+    def _grow_ws(self, need: int) -> torch.Tensor:
+        """the one workspace, grown to `need` bytes (0: the library refused the shape)"""
         if need == 0:
             raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
         if self._ws is None or self._ws.numel() < need:
@@ -126,14 +135,11 @@ class DenoiseEngine:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def workspace(self, B: int, N: int, T: int) -> torch.Tensor:
+        return self._grow_ws(self.lib.ditto_workspace_bytes(C.byref(self._ccfg), B, N, T))
+
     def workspace_packed(self, B: int, S: int, S_T: int) -> torch.Tensor:
-        need = self.lib.ditto_packed_workspace_bytes(C.byref(self._ccfg), B, S, S_T)
-        if need == 0:
-            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grow_ws(self.lib.ditto_packed_workspace_bytes(C.byref(self._ccfg), B, S, S_T))
 
     def rope_tables(self, N: int):
         if N not in self._rope:
@@ -161,7 +167,7 @@ class DenoiseEngine:
         buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
         ws = self.workspace(B, max(N_hint, 1), T)
         if text_lengths is not None:
-            self._require_varlen()
+            require_fused_attention(self.cfg, "variable-length batches")
             tl = validate_lengths(text_lengths, B, T, "text_lengths").to(self.device)
             hip.check(self.lib.ditto_text_precompute_varlen(self.handle, text.data_ptr(), tl.data_ptr(), B, T, buf.data_ptr(), nb,
                                                             ws.data_ptr(), ws.numel(), _stream()))
@@ -170,35 +176,22 @@ class DenoiseEngine:
                                                  ws.data_ptr(), ws.numel(), _stream()))
         return TextCond(buf, B, T)
 
-    def _require_varlen(self):
-        if self.cfg.head_dim != 64:
-            raise NotImplementedError(f"variable-length batches need head_dim 64 (the fused attention kernels); this model's is "
-                                      f"{self.cfg.head_dim}")
-        if getattr(self.cfg, "fp8_linear", False):
-            raise NotImplementedError("variable-length batches are not supported with fp8_linear=True")
-
-    def _require_packed(self):
-        if self.cfg.head_dim != 64:
-            raise NotImplementedError(f"packed batches need head_dim 64 (the fused attention kernels); this model's is "
-                                      f"{self.cfg.head_dim}")
-        if getattr(self.cfg, "fp8_linear", False):
-            raise NotImplementedError("packed batches are not supported with fp8_linear=True")   # (modules.require_packed: the same rule)
-
     @staticmethod
-    def _max_len(cu: torch.Tensor) -> int:
-        return int((cu[1:] - cu[:-1]).max())
+    def _cu(cu_seqlens, B: int, rows: int, max_len: Optional[int], name: str):
+        """(validated CPU int32 offsets [B + 1] over `rows` rows, the longest utterance: `max_len`, else the offsets' own)"""
+        cu = validate_cu_seqlens(cu_seqlens, B, rows, rows if max_len is None else int(max_len), name)
+        return cu, int((cu[1:] - cu[:-1]).max()) if max_len is None else int(max_len)
 
     def prepare_text_packed(self, text_emb: torch.Tensor, text_cu_seqlens, max_text_seqlen: Optional[int] = None) -> TextCond:
         """text_emb [S_T, text_dim], utterance b in rows [cu[b], cu[b+1]) -> TextCond of a packed batch
         (ditto_text_precompute_packed): the K/V rows of every layer over the S_T rows and the per-utterance text modulation."""
-        self._require_packed()
+        require_fused_attention(self.cfg, "packed batches")
         text = self._f32(text_emb, "text_emb")
         if text.dim() != 2 or text.shape[1] != self.cfg.text_dim:
             raise ValueError(f"text_emb: [S_T, {self.cfg.text_dim}] expected, got {list(text.shape)}")
         S_T = int(text.shape[0])
         B = len(text_cu_seqlens) - 1
-        ct = validate_cu_seqlens(text_cu_seqlens, B, S_T, S_T if max_text_seqlen is None else int(max_text_seqlen), "text_cu_seqlens")
-        max_T = self._max_len(ct) if max_text_seqlen is None else int(max_text_seqlen)
+        ct, max_T = self._cu(text_cu_seqlens, B, S_T, max_text_seqlen, "text_cu_seqlens")
         nb = self.lib.ditto_packed_cond_bytes(C.byref(self._ccfg), B, S_T)
         if nb == 0:
             raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
@@ -219,15 +212,14 @@ class DenoiseEngine:
                        out: Optional[torch.Tensor] = None, opts: Optional[hip.CallOpts] = None):
         """DiTTO.forward over a packed batch (ditto_forward_packed_opts): x [S, d], utterance b in rows [cu[b], cu[b+1]), with the
         packed conditioning `cond` and t [B] -> eps fp32 [S, d]."""
-        self._require_packed()
+        require_fused_attention(self.cfg, "packed batches")
         xf = self._f32(x, "x")
         if xf.dim() != 2 or xf.shape[1] != self.cfg.hidden_dim:
             raise ValueError(f"x: [S, {self.cfg.hidden_dim}] expected, got {list(xf.shape)}")
         S = int(xf.shape[0])
         B = len(cu_seqlens) - 1
         self._packed_cond(cond, B)
-        cu = validate_cu_seqlens(cu_seqlens, B, S, S if max_seqlen is None else int(max_seqlen), "cu_seqlens")
-        max_N = self._max_len(cu) if max_seqlen is None else int(max_seqlen)
+        cu, max_N = self._cu(cu_seqlens, B, S, max_seqlen, "cu_seqlens")
         tt = self._t64(t, B)
         if out is None:
             out = torch.empty_like(xf)
@@ -242,10 +234,8 @@ class DenoiseEngine:
 
     def guided_offsets_packed(self, cu_seqlens, S: int, max_seqlen: Optional[int], cfg: bool):
         """(device int32 offsets of the step's forward — [cu; S + cu[1:]] under guidance —, max_N) of a packed guided step"""
-        self._require_packed()
-        B = len(cu_seqlens) - 1
-        cu = validate_cu_seqlens(cu_seqlens, B, S, S if max_seqlen is None else int(max_seqlen), "cu_seqlens")
-        max_N = self._max_len(cu) if max_seqlen is None else int(max_seqlen)
+        require_fused_attention(self.cfg, "packed batches")
+        cu, max_N = self._cu(cu_seqlens, len(cu_seqlens) - 1, S, max_seqlen, "cu_seqlens")
         return (doubled_cu_seqlens(cu) if cfg else cu).to(self.device), max_N
 
     def guided_step_packed_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, a: torch.Tensor, ce: torch.Tensor,
@@ -255,31 +245,20 @@ class DenoiseEngine:
         """guided_step_ over a packed batch, IN PLACE on x2 fp32 [2S, d] ([x; x], w given) or [S, d]
         (ditto_guided_step_packed_opts).  `offsets`: guided_offsets_packed(...) built once per sampling call (else built here from
         `cu_seqlens`); `cond`: prepare_text_packed over [text; null] (2B utterances) or text.  noise: packed fp32 [S, d]."""
-        if not (x2.is_cuda and x2.dtype == torch.float32 and x2.is_contiguous() and x2.dim() == 2):
-            raise ValueError("guided_step_packed_ needs a contiguous fp32 CUDA state tensor [rows, d] (it is updated in place)")
+        sd, noise = self._guided_args("guided_step_packed_", x2, 2, B, a, ce, cz, w, noise, seeds)
         cfg = w is not None
         nb = 2 * B if cfg else B
-        rows, d = x2.shape
+        rows = x2.shape[0]
         if cfg and rows % 2:
             raise ValueError("x2 must hold [x; x] under guidance")
         S = rows // 2 if cfg else rows
         self._packed_cond(cond, nb)
-        if noise is not None and seeds is not None:
-            raise ValueError("noise and seeds are exclusive")
         if offsets is None:
             offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, cfg)
         cud, max_N = offsets
         if cud.shape != (nb + 1,):
             raise ValueError(f"offsets: [{nb + 1}] expected")
         tt = self._t64(t, nb)
-        sd = self._t64(seeds, B) if seeds is not None else None
-        if noise is not None:
-            noise = self._f32(noise, "noise")
-            if noise.shape != (S, d):
-                raise ValueError(f"noise must have shape {(S, d)}")
-        for name, v in (("a", a), ("ce", ce), ("cz", cz), ("w", w)):
-            if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
-                raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
         ws = self.workspace_packed(nb, rows, cond.T)
         c, s = self.rope_tables(max_N)
         hip.check(self.lib.ditto_guided_step_packed_opts(
@@ -288,15 +267,18 @@ class DenoiseEngine:
             int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
         return x2
 
-    def _lengths(self, speech_lengths, cond: TextCond, B: int, N: int):
-        """(speech, text) device int32 [B] of a varlen call, or None for a dense one"""
+    def _lengths(self, speech_lengths, cond: TextCond, B: int, N: int, halves: int = 1):
+        """(speech, text) device int32 [halves * B] of a varlen call, or None for a dense one.  `speech_lengths`: the B
+        utterances' (list / tuple / int tensor), repeated by each half of a guided [x; x] (halves 2); the text lengths are the
+        conditioning's own."""
         if speech_lengths is None and cond.text_lengths is None:
             return None
-        self._require_varlen()
-        sl = (validate_lengths(speech_lengths, B, N, "speech_lengths").to(self.device) if speech_lengths is not None
-              else torch.full((B,), N, dtype=torch.int32, device=self.device))
-        tl = cond.text_lengths if cond.text_lengths is not None else torch.full((B,), cond.T, dtype=torch.int32, device=self.device)
-        return sl, tl
+        require_fused_attention(self.cfg, "variable-length batches")
+        sl = (validate_lengths(speech_lengths, B, N, "speech_lengths") if speech_lengths is not None
+              else torch.full((B,), N, dtype=torch.int32))
+        tl = (cond.text_lengths if cond.text_lengths is not None
+              else torch.full((halves * B,), cond.T, dtype=torch.int32, device=self.device))
+        return sl.repeat(halves).to(self.device), tl
 
     def prepare_text_into(self, text_emb: torch.Tensor, N_hint: int, cond: TextCond) -> TextCond:
         """Recompute the conditioning of a new utterance batch into an EXISTING TextCond buffer (same B, T), so
@@ -316,6 +298,15 @@ class DenoiseEngine:
         if t.shape != (B,):
             raise ValueError(f"t must have shape [{B}]")
         return t.to(device=self.device, dtype=torch.int64).contiguous()
+
+    def _call_varlen(self, name, lens, head, tail, opts):
+        """`name` of a dense batch (lens None: through _call), else `name`_varlen_opts with the (speech, text) length pointers
+        between the arguments `head` and `tail`"""
+        if lens is None:
+            self._call(name, *head, *tail, opts=opts)
+        else:
+            hip.check(getattr(self.lib, name + "_varlen_opts")(*head, lens[0].data_ptr(), lens[1].data_ptr(), *tail,
+                                                               None if opts is None else C.byref(opts)))
 
     def _call(self, name, *args, opts=None):
         """`name`_opts(*args, opts) — the entry point with this call's ditto_call_opts (None = NULL: every field inherits the
@@ -341,16 +332,9 @@ class DenoiseEngine:
             out = torch.empty_like(xf)
         ws = self.workspace(B, N, cond.T)
         c, s = self.rope_tables(N)
-        lens = self._lengths(speech_lengths, cond, B, N)
-        if lens is not None:
-            hip.check(self.lib.ditto_forward_varlen_opts(self.handle, xf.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(),
-                                                         lens[0].data_ptr(), lens[1].data_ptr(), B, N, cond.T, c.data_ptr(),
-                                                         s.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
-                                                         None if opts is None else C.byref(opts)))
-            return out
-        self._call("ditto_forward", self.handle, xf.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), B, N, cond.T,
-                                              c.data_ptr(), s.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              _stream(), opts=opts)
+        self._call_varlen("ditto_forward", self._lengths(speech_lengths, cond, B, N),
+                          (self.handle, xf.data_ptr(), cond.buf.data_ptr(), tt.data_ptr()),
+                          (B, N, cond.T, c.data_ptr(), s.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), opts)
         return out
 
     def p_sample_(self, x: torch.Tensor, cond: TextCond, t: torch.Tensor, noise: Optional[torch.Tensor],
@@ -365,16 +349,10 @@ class DenoiseEngine:
         c, s = self.rope_tables(N)
         if noise is not None:
             noise = self._f32(noise, "noise")
-        lens = self._lengths(speech_lengths, cond, B, N)
-        if lens is not None:
-            hip.check(self.lib.ditto_p_sample_varlen_opts(self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), _ptr(noise),
-                                                          lens[0].data_ptr(), lens[1].data_ptr(), betas.data_ptr(), alphas.data_ptr(),
-                                                          alphas_cumprod.data_ptr(), B, N, cond.T, c.data_ptr(), s.data_ptr(),
-                                                          ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
-            return x
-        self._call("ditto_p_sample", self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), _ptr(noise),
-                                               betas.data_ptr(), alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T,
-                                               c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), opts=opts)
+        self._call_varlen("ditto_p_sample", self._lengths(speech_lengths, cond, B, N),
+                          (self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), _ptr(noise)),
+                          (betas.data_ptr(), alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T, c.data_ptr(), s.data_ptr(),
+                           ws.data_ptr(), ws.numel(), _stream()), opts)
         return x
 
     def noise_normal_(self, out: torch.Tensor, seeds: torch.Tensor, step: int):
@@ -399,17 +377,10 @@ class DenoiseEngine:
         tt, sd = self._t64(t, B), self._t64(seeds, B)
         ws = self.workspace(B, N, cond.T)
         c, s = self.rope_tables(N)
-        lens = self._lengths(speech_lengths, cond, B, N)
-        if lens is not None:
-            hip.check(self.lib.ditto_p_sample_seeded_varlen_opts(
-                self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), sd.data_ptr(), lens[0].data_ptr(), lens[1].data_ptr(),
-                int(step) & 0xFFFFFFFF, betas.data_ptr(), alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T, c.data_ptr(),
-                s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
-            return x
-        self._call("ditto_p_sample_seeded", self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(),
-                                                      sd.data_ptr(), int(step) & 0xFFFFFFFF, betas.data_ptr(),
-                                                      alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T, c.data_ptr(),
-                                                      s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), opts=opts)
+        self._call_varlen("ditto_p_sample_seeded", self._lengths(speech_lengths, cond, B, N),
+                          (self.handle, x.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), sd.data_ptr()),
+                          (int(step) & 0xFFFFFFFF, betas.data_ptr(), alphas.data_ptr(), alphas_cumprod.data_ptr(), B, N, cond.T,
+                           c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), opts)
         return x
 
     def guided_lengths(self, speech_lengths, cond: TextCond, B: int, N: int, cfg: bool):
@@ -419,15 +390,24 @@ class DenoiseEngine:
         nb = 2 * B if cfg else B
         if cond.B != nb:
             raise ValueError(f"the conditioning holds {cond.B} utterances; a guided step of {B} needs {nb}")
-        if speech_lengths is None and cond.text_lengths is None:
-            return None
-        self._require_varlen()
-        sl = (validate_lengths(speech_lengths, B, N, "speech_lengths") if speech_lengths is not None
-              else torch.full((B,), N, dtype=torch.int32))
-        if cfg:
-            sl = torch.cat([sl, sl])
-        tl = cond.text_lengths if cond.text_lengths is not None else torch.full((nb,), cond.T, dtype=torch.int32, device=self.device)
-        return sl.to(self.device), tl
+        return self._lengths(speech_lengths, cond, B, N, 2 if cfg else 1)
+
+    def _guided_args(self, who, x2, dim, B, a, ce, cz, w, noise, seeds):
+        """The checks of both guided steps: the state x2 ([x; x] under guidance: w given), noise / seeds, the fp32 [B]
+        coefficients.  Returns (seeds as int64 [B], noise as fp32 of x2's first half), each None when not given."""
+        if not (x2.is_cuda and x2.dtype == torch.float32 and x2.is_contiguous() and x2.dim() == dim):
+            raise ValueError(f"{who} needs a contiguous fp32 CUDA state tensor of {dim} dimensions (it is updated in place)")
+        if noise is not None and seeds is not None:
+            raise ValueError("noise and seeds are exclusive")
+        if noise is not None:
+            noise = self._f32(noise, "noise")
+            half = (x2.shape[0] // 2 if w is not None else x2.shape[0], *x2.shape[1:])
+            if noise.shape != half:
+                raise ValueError(f"noise must have shape {half}")
+        for name, v in (("a", a), ("ce", ce), ("cz", cz), ("w", w)):
+            if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
+                raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
+        return (self._t64(seeds, B) if seeds is not None else None), noise
 
     def guided_step_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, a: torch.Tensor, ce: torch.Tensor,
                      cz: torch.Tensor, w: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
@@ -438,23 +418,12 @@ class DenoiseEngine:
         written to both halves.  a / ce / cz / w: device fp32 [B]; z from `noise` fp32 [B, N, d], from Philox of `seeds` at tag
         `step`, or none (cz unused).  `lengths`: guided_lengths(...) built once per sampling call (else it is built here from
         `speech_lengths` and the conditioning).  Rows past an utterance's length become 0 in both halves."""
-        if not (x2.is_cuda and x2.dtype == torch.float32 and x2.is_contiguous()):
-            raise ValueError("guided_step_ needs a contiguous fp32 CUDA state tensor (it is updated in place)")
+        sd, noise = self._guided_args("guided_step_", x2, 3, B, a, ce, cz, w, noise, seeds)
         cfg = w is not None
         nb, N, d = x2.shape
         if nb != (2 * B if cfg else B):
             raise ValueError(f"x2 holds {nb} utterances; a guided step of {B} needs {2 * B if cfg else B}")
-        if noise is not None and seeds is not None:
-            raise ValueError("noise and seeds are exclusive")
         tt = self._t64(t, nb)
-        sd = self._t64(seeds, B) if seeds is not None else None
-        if noise is not None:
-            noise = self._f32(noise, "noise")
-            if noise.shape != (B, N, d):
-                raise ValueError(f"noise must have shape {(B, N, d)}")
-        for name, v in (("a", a), ("ce", ce), ("cz", cz), ("w", w)):
-            if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
-                raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
         lens = lengths if lengths is not None else self.guided_lengths(speech_lengths, cond, B, N, cfg)
         ws = self.workspace(nb, N, cond.T)
         c, s = self.rope_tables(N)

@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import hip
 from .varlen import validate_lengths
 from .config import DiTTOConfig
-from .engine import DenoiseEngine, TextCond, _stream
+from .engine import DenoiseEngine, TextCond, _stream, require_fused_attention
 from .synth import cosine_betas
 
 
@@ -236,14 +236,6 @@ class _BlocksOnlyEngine(DenoiseEngine):
         self._generation += 1
 
 
-def require_packed(cfg):
-    """packed batches run the fused head_dim-64 attention and bf16 linears only (NotImplementedError otherwise)"""
-    if cfg.head_dim != 64:
-        raise NotImplementedError(f"packed batches need head_dim 64 (the fused attention kernels); this model's is {cfg.head_dim}")
-    if getattr(cfg, "fp8_linear", False):
-        raise NotImplementedError("packed batches are not supported with fp8_linear=True")
-
-
 class DiTTO(nn.Module):
     """Full DiT noise predictor — reference src/model/DiTTO.py:7-126.
 
@@ -353,6 +345,12 @@ class DiTTO(nn.Module):
         self._cond = None
         self._cond_src = None
 
+    def _inference_only(self, what: str, x, text_emb):
+        if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad or
+                                        any(p.requires_grad for n, p in self.named_parameters() if not n.startswith("nac."))):
+            raise NotImplementedError(f"ditto_tts_amd: {what} are inference only (run under torch.no_grad() or with frozen "
+                                      "parameters)")
+
     # ------------------------------------------------------------------ reference surface
     def forward(self, x, text_emb, t, *, speech_lengths=None, text_lengths=None):
         """x [B,N,d] noisy latents, text_emb [B,T,text_dim], t [B] long -> predicted noise [B,N,d]
@@ -362,10 +360,7 @@ class DiTTO(nn.Module):
         _require_cuda(x, "x")
         varlen = speech_lengths is not None or text_lengths is not None
         if varlen:
-            if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad or
-                                            any(p.requires_grad for n, p in self.named_parameters() if not n.startswith("nac."))):
-                raise NotImplementedError("ditto_tts_amd: variable-length batches are inference only (run under torch.no_grad() "
-                                          "or with frozen parameters)")
+            self._inference_only("variable-length batches", x, text_emb)
             eng = self.engine(x.device)
             cond = self.text_cond(text_emb.to(x.device), x.shape[1], text_lengths=text_lengths)
             out = eng.forward(x, cond, t, speech_lengths=speech_lengths)
@@ -396,11 +391,8 @@ class DiTTO(nn.Module):
         Offsets: list, tuple or int tensor [B + 1] (validated on the host); max_seqlen / max_text_seqlen bound the lengths (default:
         the longest).  Inference only, head_dim 64, bf16 linears."""
         # the refusals first: each is decided by the configuration and the grad mode alone
-        if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad or
-                                        any(p.requires_grad for n, p in self.named_parameters() if not n.startswith("nac."))):
-            raise NotImplementedError("ditto_tts_amd: packed batches are inference only (run under torch.no_grad() or with frozen "
-                                      "parameters)")
-        require_packed(self.cfg)
+        self._inference_only("packed batches", x, text_emb)
+        require_fused_attention(self.cfg, "packed batches")
         _require_cuda(x, "x")
         eng = self.engine(x.device)
         cond = eng.prepare_text_packed(text_emb.to(x.device), text_cu_seqlens, max_text_seqlen)

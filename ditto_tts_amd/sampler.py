@@ -21,17 +21,19 @@ RNG: `torch.randn_like` on the state's device, in the reference's call order (on
 """
 from __future__ import annotations
 
+import functools
 from typing import Callable, Optional
 
 import torch
 
+from .engine import require_fused_attention
 from .modules import DiTTO
 
 
 def strided_schedule(alphas_cumprod: torch.Tensor, n_steps: int, eta: float = 0.0):
     """The strided (DDIM) schedule of `n_steps` evenly spaced timesteps over the table `alphas_cumprod`: a list of
     (tau_i, a, ce, sigma), x' = a x + ce eps + sigma z at step i (Song et al. 2021 eq. 12; the last step ends at abar = 1).
-    The coefficients are computed in float64 and returned as Python floats: the expressions of sample_latents_strided."""
+    The coefficients are computed in float64 and returned as Python floats."""
     T = int(alphas_cumprod.shape[0])
     if not 1 <= n_steps <= T:
         raise ValueError("n_steps must be in [1, diffusion_steps]")
@@ -250,57 +252,62 @@ class SpeechGenerator:
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
                                cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
-        DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step
-        (ditto_linear_update), with optional classifier-free guidance: the step runs ONE forward on the doubled
-        batch [x; x] x [text; null_text] and combines eps_u + w (eps_c - eps_u) (ditto_cfg_combine)."""
-        from .around import cfg_combine, linear_update_
+        DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step, with optional
+        classifier-free guidance: the step runs ONE forward on the doubled batch [x; x] x [text; null_text] and combines
+        eps_u + w (eps_c - eps_u).  sample_guided with one uniform `cfg_scale` over a dense batch: one library call per step."""
         if speech_lengths is not None or text_lengths is not None:
             raise NotImplementedError("sample_latents_strided has no varlen form: a variable-length batch runs sample_guided "
                                       "(guided strided loop) or the ancestral sample_latents")
-        m = self.ditto_model
-        T = self.diffusion_steps
-        if not 1 <= n_steps <= T:
-            raise ValueError("n_steps must be in [1, diffusion_steps]")
-        x = (torch.randn_like(audio_emb) if not cond_by_audio else audio_emb.clone()).to(self.device).float().contiguous()
-        B = x.shape[0]
-        eng = m.engine(x.device)
-        text = text_emb.to(x.device).float()
-        if cfg_scale is not None:
-            if null_text_emb is None:
-                raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
-            text = torch.cat([text, null_text_emb.to(x.device).float().expand_as(text)], dim=0).contiguous()
-        cond = eng.prepare_text(text, x.shape[1])
-        stride = T / n_steps
-        taus = [int(round(T - 1 - i * stride)) for i in range(n_steps)]
-        ac = self.alphas_cumprod.double().cpu()
-        nb = 2 * B if cfg_scale is not None else B
-        t_tensor = torch.empty(nb, device=x.device, dtype=torch.long)
-        coef = torch.empty(3, B, device=x.device, dtype=torch.float32)
-        z = torch.empty_like(x)
-        x2 = torch.empty(nb, *x.shape[1:], device=x.device) if cfg_scale is not None else None
-        for i, t_val in enumerate(taus):
-            ab_t = ac[t_val]
-            ab_p = ac[taus[i + 1]] if i + 1 < n_steps else torch.tensor(1.0, dtype=torch.float64)
-            sigma = eta * torch.sqrt((1 - ab_p) / (1 - ab_t)) * torch.sqrt(1 - ab_t / ab_p)
-            a = torch.sqrt(ab_p / ab_t)
-            ce = torch.sqrt(torch.clamp(1 - ab_p - sigma ** 2, min=0.0)) - torch.sqrt(ab_p * (1 - ab_t) / ab_t)
-            coef[0].fill_(float(a)); coef[1].fill_(float(ce)); coef[2].fill_(float(sigma))
-            t_tensor.fill_(t_val)
-            if cfg_scale is not None:
-                x2[:B].copy_(x); x2[B:].copy_(x)
-                eps = cfg_combine(eng.forward(x2, cond, t_tensor), cfg_scale)
-            else:
-                eps = eng.forward(x, cond, t_tensor)
-            use_noise = float(sigma) != 0.0
-            if use_noise:
-                if noises is None:
-                    z.normal_()
-                else:
-                    z.copy_((noises(i) if callable(noises) else noises[i]).to(x.device))
-            linear_update_(x, eps, z if use_noise else None, coef[0], coef[1], coef[2])
-        return x
+        return self.sample_guided(text_emb, audio_emb, n_steps=n_steps, eta=eta,
+                                  guidance=None if cfg_scale is None else float(cfg_scale), null_text_emb=null_text_emb,
+                                  noises=noises, cond_by_audio=cond_by_audio)
 
     # ---------------------------------------------------------------- guided strided loop over a variable-length batch
+    def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin):
+        """The strided loop of sample_guided and sample_guided_packed.  `begin(eng, cfg, seeds)` is the layout's own prologue: it
+        builds the conditioning and the state x2 (rows [x_T; room for the unconditional half] under guidance, else x_T) and returns
+        (x2, max length, step) with `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)` the layout's library call bound to
+        x2, its conditioning and its lengths or offsets."""
+        if seeds is not None and noises is not None:
+            raise ValueError("seeds= excludes noises=")
+        gv = guidance_vector(guidance, B)
+        cfg = gv is not None
+        if cfg and null_text_emb is None:
+            raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
+        schedule = strided_schedule(self.alphas_cumprod, n_steps, eta)
+        eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)   # "cuda" -> cuda:0: the engine the other loops use
+        if seeds is not None:
+            seeds = seeds.to(eng.device).long().contiguous()
+            if seeds.shape != (B,):
+                raise ValueError(f"seeds must have shape [{B}]")
+        x2, N, step = begin(eng, cfg, seeds)
+        rows = x2.shape[0] // 2 if cfg else x2.shape[0]
+        if cfg:
+            x2[rows:].copy_(x2[:rows])                       # after this, every step's update writes both halves itself
+        # every step's coefficients in one upload: coef[i] = (a, ce, sigma) x B
+        coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
+        w = gv.to(eng.device) if cfg else None
+        t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
+        z = torch.empty_like(x2[:rows]) if seeds is None else None
+        opts = None
+        if batch_class is not None:
+            from .hip import CallOpts
+            opts = CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
+        for i, (t_val, _, _, sigma) in enumerate(schedule):
+            t_tensor.fill_(t_val)
+            noise = sd = None
+            if sigma != 0.0:
+                if seeds is not None:
+                    sd = seeds
+                elif noises is None:
+                    z.normal_()
+                    noise = z
+                else:
+                    z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
+                    noise = z
+            step(t=t_tensor, a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val, opts=opts)
+        return x2[:rows].clone() if cfg else x2
+
     @torch.no_grad()
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
                       null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
@@ -317,72 +324,35 @@ class SpeechGenerator:
         else torch.randn_like.  Step i's z (when sigma != 0): Philox of `seeds` at tag tau_i, `noises[i]` (a sequence or
         callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
         count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
-        Dense, full-length, uniform guidance with noises= or cond_by_audio: the bits of sample_latents_strided.
         Returns fp32 [B, N, d]."""
-        if seeds is not None and noises is not None:
-            raise ValueError("seeds= excludes noises=")
-        m = self.ditto_model
-        eng = m.engine(torch.empty(0, device=self.device).device)      # "cuda" -> cuda:0: the engine the other loops use
         B, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
-        gv = guidance_vector(guidance, B)
-        cfg = gv is not None
-        if cfg and null_text_emb is None:
-            raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
-        schedule = strided_schedule(self.alphas_cumprod, n_steps, eta)
-        text = text_emb.to(eng.device).float()
-        T = int(text.shape[1])
-        if null_text_lengths is not None and not cfg:
-            raise ValueError("null_text_lengths without guidance")
-        varlen = speech_lengths is not None or text_lengths is not None or null_text_lengths is not None
-        if varlen:
-            eng._require_varlen()
-            from .varlen import validate_lengths
-            sl = validate_lengths(speech_lengths if speech_lengths is not None else [N] * B, B, N, "speech_lengths")
-            tl = validate_lengths(text_lengths if text_lengths is not None else [T] * B, B, T, "text_lengths")
+
+        def begin(eng, cfg, seeds):
+            text = text_emb.to(eng.device).float()
+            T = int(text.shape[1])
+            if null_text_lengths is not None and not cfg:
+                raise ValueError("null_text_lengths without guidance")
+            varlen = speech_lengths is not None or text_lengths is not None or null_text_lengths is not None
+            if varlen:
+                require_fused_attention(eng.cfg, "variable-length batches")
+                from .varlen import validate_lengths
+                sl = validate_lengths(speech_lengths if speech_lengths is not None else [N] * B, B, N, "speech_lengths")
+                tl = validate_lengths(text_lengths if text_lengths is not None else [T] * B, B, T, "text_lengths")
+                if cfg:
+                    ntl = validate_lengths(null_text_lengths, B, T, "null_text_lengths") if null_text_lengths is not None else tl
+                    tl = torch.cat([tl, ntl])
             if cfg:
-                ntl = validate_lengths(null_text_lengths, B, T, "null_text_lengths") if null_text_lengths is not None else tl
-                tl = torch.cat([tl, ntl])
-        if cfg:
-            text = torch.cat([text, null_text_emb.to(eng.device).float().expand_as(text)], dim=0).contiguous()
-        cond = eng.prepare_text(text, N, text_lengths=tl if varlen else None)
-        nb = 2 * B if cfg else B
-        lens = eng.guided_lengths(sl if varlen else None, cond, B, N, cfg)
-        x2 = torch.empty(nb, N, int(audio_emb.shape[2]), dtype=torch.float32, device=eng.device)
-        x = x2[:B]
-        if seeds is not None:
-            seeds = seeds.to(eng.device).long().contiguous()
-            if seeds.shape != (B,):
-                raise ValueError(f"seeds must have shape [{B}]")
-        if seeds is not None and not cond_by_audio:
-            eng.noise_normal_(x, seeds, 0xFFFFFFFF)         # x_T: the step tag no loop step uses (sample_latents(seeds=))
-        else:
-            x.copy_(torch.randn_like(audio_emb) if not cond_by_audio else audio_emb)
-        if cfg:
-            x2[B:].copy_(x)                                  # after this, every step's update writes both halves itself
-        # every step's coefficients in one upload: coef[i] = (a, ce, sigma) x B
-        coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
-        w = gv.to(eng.device) if cfg else None
-        t_tensor = torch.empty(nb, device=eng.device, dtype=torch.long)
-        z = torch.empty(B, *x2.shape[1:], dtype=torch.float32, device=eng.device) if seeds is None else None
-        opts = None
-        if batch_class is not None:
-            from .hip import CallOpts
-            opts = CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
-        for i, (t_val, _, _, sigma) in enumerate(schedule):
-            t_tensor.fill_(t_val)
-            noise = sd = None
-            if sigma != 0.0:
-                if seeds is not None:
-                    sd = seeds
-                elif noises is None:
-                    z.normal_()
-                    noise = z
-                else:
-                    z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
-                    noise = z
-            eng.guided_step_(x2, cond, t_tensor, B, coef[i, 0], coef[i, 1], coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val,
-                             lengths=lens, opts=opts)
-        return x2[:B].clone() if cfg else x2
+                text = torch.cat([text, null_text_emb.to(eng.device).float().expand_as(text)], dim=0).contiguous()
+            cond = eng.prepare_text(text, N, text_lengths=tl if varlen else None)
+            lens = eng.guided_lengths(sl if varlen else None, cond, B, N, cfg)
+            x2 = torch.empty(2 * B if cfg else B, N, int(audio_emb.shape[2]), dtype=torch.float32, device=eng.device)
+            if seeds is not None and not cond_by_audio:
+                eng.noise_normal_(x2[:B], seeds, 0xFFFFFFFF)   # x_T: the step tag no loop step uses (sample_latents(seeds=))
+            else:
+                x2[:B].copy_(torch.randn_like(audio_emb) if not cond_by_audio else audio_emb)
+            return x2, N, functools.partial(eng.guided_step_, x2, cond, B=B, lengths=lens)
+
+        return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin)
 
     @torch.no_grad()
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
@@ -397,77 +367,40 @@ class SpeechGenerator:
         the bits sample_guided(seeds=) draws for the same utterance.  `noises[i]` (a sequence or callable): packed [S, d].
         `batch_class`: class_rows = (2 with guidance, else 1) * batch_class * max length, what sample_guided pins for the padded
         batch of batch_class utterances.  Returns fp32 [S, d]."""
-        if seeds is not None and noises is not None:
-            raise ValueError("seeds= excludes noises=")
-        m = self.ditto_model
-        from .modules import require_packed
-        require_packed(m.cfg)
-        eng = m.engine(torch.empty(0, device=self.device).device)
-        from .varlen import validate_cu_seqlens
+        require_fused_attention(self.ditto_model.cfg, "packed batches")
+        from .varlen import pack, validate_cu_seqlens
         S, d = int(audio_emb.shape[0]), int(audio_emb.shape[1])
         B = len(cu_seqlens) - 1
         cu = validate_cu_seqlens(cu_seqlens, B, S, S, "cu_seqlens")
         N = int((cu[1:] - cu[:-1]).max())
-        gv = guidance_vector(guidance, B)
-        cfg = gv is not None
-        if cfg and null_text_emb is None:
-            raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
-        if null_text_cu_seqlens is not None and not cfg:
-            raise ValueError("null_text_cu_seqlens without guidance")
-        schedule = strided_schedule(self.alphas_cumprod, n_steps, eta)
-        text = text_emb.to(eng.device).float()
-        S_T = int(text.shape[0])
-        ct = validate_cu_seqlens(text_cu_seqlens, B, S_T, S_T, "text_cu_seqlens")
-        if cfg:
-            null = null_text_emb.to(eng.device).float()
-            if null_text_cu_seqlens is None:
-                null, cn = null.expand_as(text), ct
-            else:
-                cn = validate_cu_seqlens(null_text_cu_seqlens, B, int(null.shape[0]), int(null.shape[0]), "null_text_cu_seqlens")
-            text = torch.cat([text, null], dim=0).contiguous()
-            ct = torch.cat([ct, ct[-1] + cn[1:]])
-        cond = eng.prepare_text_packed(text, ct)
-        nb = 2 * B if cfg else B
-        offsets = eng.guided_offsets_packed(cu, S, N, cfg)
-        x2 = torch.empty(2 * S if cfg else S, d, dtype=torch.float32, device=eng.device)
-        x = x2[:S]
-        if seeds is not None:
-            seeds = seeds.to(eng.device).long().contiguous()
-            if seeds.shape != (B,):
-                raise ValueError(f"seeds must have shape [{B}]")
-        if seeds is not None and not cond_by_audio:
-            # x_T: ditto_noise_normal over the padded [B, N, d] (the numbers of sample_guided(seeds=)), packed row by row
-            from .varlen import pack
-            xt = torch.empty(B, N, d, dtype=torch.float32, device=eng.device)
-            eng.noise_normal_(xt, seeds, 0xFFFFFFFF)
-            x.copy_(pack(xt, (cu[1:] - cu[:-1]).tolist())[0])
-        else:
-            x.copy_(torch.randn_like(audio_emb.float()) if not cond_by_audio else audio_emb)
-        if cfg:
-            x2[S:].copy_(x)
-        coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
-        w = gv.to(eng.device) if cfg else None
-        t_tensor = torch.empty(nb, device=eng.device, dtype=torch.long)
-        z = torch.empty(S, d, dtype=torch.float32, device=eng.device) if seeds is None else None
-        opts = None
-        if batch_class is not None:
-            from .hip import CallOpts
-            opts = CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
-        for i, (t_val, _, _, sigma) in enumerate(schedule):
-            t_tensor.fill_(t_val)
-            noise = sd = None
-            if sigma != 0.0:
-                if seeds is not None:
-                    sd = seeds
-                elif noises is None:
-                    z.normal_()
-                    noise = z
+
+        def begin(eng, cfg, seeds):
+            if null_text_cu_seqlens is not None and not cfg:
+                raise ValueError("null_text_cu_seqlens without guidance")
+            text = text_emb.to(eng.device).float()
+            S_T = int(text.shape[0])
+            ct = validate_cu_seqlens(text_cu_seqlens, B, S_T, S_T, "text_cu_seqlens")
+            if cfg:
+                null = null_text_emb.to(eng.device).float()
+                if null_text_cu_seqlens is None:
+                    null, cn = null.expand_as(text), ct
                 else:
-                    z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
-                    noise = z
-            eng.guided_step_packed_(x2, cond, t_tensor, B, coef[i, 0], coef[i, 1], coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val,
-                                    offsets=offsets, opts=opts)
-        return x2[:S].clone() if cfg else x2
+                    cn = validate_cu_seqlens(null_text_cu_seqlens, B, int(null.shape[0]), int(null.shape[0]), "null_text_cu_seqlens")
+                text = torch.cat([text, null], dim=0).contiguous()
+                ct = torch.cat([ct, ct[-1] + cn[1:]])
+            cond = eng.prepare_text_packed(text, ct)
+            offsets = eng.guided_offsets_packed(cu, S, N, cfg)
+            x2 = torch.empty(2 * S if cfg else S, d, dtype=torch.float32, device=eng.device)
+            if seeds is not None and not cond_by_audio:
+                # x_T: ditto_noise_normal over the padded [B, N, d] (the numbers of sample_guided(seeds=)), packed row by row
+                xt = torch.empty(B, N, d, dtype=torch.float32, device=eng.device)
+                eng.noise_normal_(xt, seeds, 0xFFFFFFFF)
+                x2[:S].copy_(pack(xt, (cu[1:] - cu[:-1]).tolist())[0])
+            else:
+                x2[:S].copy_(torch.randn_like(audio_emb.float()) if not cond_by_audio else audio_emb)
+            return x2, N, functools.partial(eng.guided_step_packed_, x2, cond, B=B, offsets=offsets)
+
+        return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin)
 
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):

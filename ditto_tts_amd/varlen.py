@@ -60,48 +60,44 @@ def _check_out(t, name, B, Sq, H, dtypes, device):
                          f"{device} is needed, got {t.dtype} {list(t.shape)} on {t.device}")
 
 
-def attention(q, k, v, H: int, q_len=None, kv_len=None, out=None):
-    """softmax(q k^T) v per (utterance, head) over each utterance's own rows (q carries scale * log2(e)); q / out [B, Sq, >= H*64],
-    k / v [B, Skv, >= H*64], bf16.  Rows of `out` past q_len are left as they were.  Returns `out`."""
+def _attention(q, k, v, H, q_len, kv_len, out=None, resid=None, resid_in=None):
+    """attention (resid None: into `out`, allocated when None) and attention_resid (into `resid`): one entry each"""
     _check_qkv(q, k, v, H)
     _check_batch(q, k, v, H)
     B, Sq, Skv = q.shape[0], q.shape[1], k.shape[1]
     if q_len is None and kv_len is None:
         raise ValueError("q_len and kv_len are both None: the dense attention serves that")
-    if out is not None:
+    if resid is None:
+        if out is None:
+            out = torch.zeros(B, Sq, H * 64, dtype=torch.bfloat16, device=q.device)
         _check_out(out, "out", B, Sq, H, (torch.bfloat16,), q.device)
+        entry, outs = hip.lib().ditto_attention_varlen_bf16, (out.data_ptr(), out.stride(1))
+    else:
+        src = resid if resid_in is None else resid_in
+        _check_out(resid, "resid", B, Sq, H, (torch.float32, torch.bfloat16), q.device)
+        _check_out(src, "resid_in", B, Sq, H, (resid.dtype,), q.device)
+        if src.stride() != resid.stride():
+            raise ValueError("resid / resid_in: fp32 or bf16 with the same dtype and row stride")
+        entry = hip.lib().ditto_attention_resid_varlen_bf16
+        outs = (src.data_ptr(), resid.data_ptr(), resid.stride(1), int(resid.dtype == torch.bfloat16))
     ql = _dev_lengths(q_len, B, Sq, "q_len", q.device)
     kl = _dev_lengths(kv_len, B, Skv, "kv_len", q.device)
-    if out is None:
-        out = torch.zeros(B, Sq, H * 64, dtype=torch.bfloat16, device=q.device)
-    hip.check(hip.lib().ditto_attention_varlen_bf16(
-        q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(1), out.data_ptr(), out.stride(1),
-        ql.data_ptr() if ql is not None else None, kl.data_ptr() if kl is not None else None, B, H, Sq, Skv, 64,
-        torch.cuda.current_stream(q.device).cuda_stream))
-    return out
+    hip.check(entry(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(1), *outs,
+                    ql.data_ptr() if ql is not None else None, kl.data_ptr() if kl is not None else None, B, H, Sq, Skv, 64,
+                    torch.cuda.current_stream(q.device).cuda_stream))
+    return out if resid is None else resid
+
+
+def attention(q, k, v, H: int, q_len=None, kv_len=None, out=None):
+    """softmax(q k^T) v per (utterance, head) over each utterance's own rows (q carries scale * log2(e)); q / out [B, Sq, >= H*64],
+    k / v [B, Skv, >= H*64], bf16.  Rows of `out` past q_len are left as they were.  Returns `out`."""
+    return _attention(q, k, v, H, q_len, kv_len, out=out)
 
 
 def attention_resid(q, k, v, H: int, resid, q_len=None, kv_len=None, resid_in=None):
     """The residual form: resid[b, i, h*64 + c] = resid_in[...] + attention, for i < q_len[b] (resid_in None: in place); resid
     is fp32 or bf16 [B, Sq, >= H*64].  Rows past q_len are left untouched.  Returns `resid`."""
-    _check_qkv(q, k, v, H)
-    _check_batch(q, k, v, H)
-    B, Sq, Skv = q.shape[0], q.shape[1], k.shape[1]
-    if q_len is None and kv_len is None:
-        raise ValueError("q_len and kv_len are both None: the dense attention serves that")
-    src = resid if resid_in is None else resid_in
-    _check_out(resid, "resid", B, Sq, H, (torch.float32, torch.bfloat16), q.device)
-    _check_out(src, "resid_in", B, Sq, H, (resid.dtype,), q.device)
-    if (resid.dtype not in (torch.float32, torch.bfloat16) or src.dtype != resid.dtype or src.stride() != resid.stride()
-            or resid.stride(2) != 1 or resid.stride(0) != Sq * resid.stride(1)):
-        raise ValueError("resid / resid_in: fp32 or bf16 with the same dtype and row stride")
-    ql = _dev_lengths(q_len, B, Sq, "q_len", q.device)
-    kl = _dev_lengths(kv_len, B, Skv, "kv_len", q.device)
-    hip.check(hip.lib().ditto_attention_resid_varlen_bf16(
-        q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(), v.stride(1), src.data_ptr(), resid.data_ptr(),
-        resid.stride(1), int(resid.dtype == torch.bfloat16), ql.data_ptr() if ql is not None else None,
-        kl.data_ptr() if kl is not None else None, B, H, Sq, Skv, 64, torch.cuda.current_stream(q.device).cuda_stream))
-    return resid
+    return _attention(q, k, v, H, q_len, kv_len, resid=resid, resid_in=resid_in)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -183,47 +179,44 @@ def _check_packed(t, name, H, dtypes=(torch.bfloat16,)):
                          f"is needed, got {t.dtype} {list(t.shape)}")
 
 
-def attention_packed(q, k, v, H: int, cu_q, cu_kv, max_q=None, max_kv=None, out=None):
-    """softmax(q k^T) v per (utterance, head) of a packed batch (q carries scale * log2(e)): q / out [Sq, >= H*64] with utterance
-    b in rows [cu_q[b], cu_q[b+1]), k / v [Skv, >= H*64] with rows [cu_kv[b], cu_kv[b+1]); bf16.  Returns `out`."""
+def _attention_packed(q, k, v, H, cu_q, cu_kv, max_q, max_kv, out=None, resid=None, resid_in=None):
+    """attention_packed (resid None: into `out`, allocated when None) and attention_resid_packed (into `resid`): one entry each"""
     for n, x in (("q", q), ("k", k), ("v", v)):
         _check_packed(x, n, H)
     if v.shape[0] != k.shape[0] or not (q.device == k.device == v.device):
         raise ValueError("k and v need one row count, q / k / v one device")
     Sq, Skv = int(q.shape[0]), int(k.shape[0])
+    if resid is None:
+        if out is None:
+            out = torch.zeros(Sq, H * 64, dtype=torch.bfloat16, device=q.device)
+        _check_packed(out, "out", H)
+        if out.shape[0] != Sq:
+            raise ValueError(f"out: {Sq} rows expected")
+        entry, outs = hip.lib().ditto_attention_packed_bf16, (out.data_ptr(), out.stride(0))
+    else:
+        src = resid if resid_in is None else resid_in
+        _check_packed(resid, "resid", H, (torch.float32, torch.bfloat16))
+        if src.dtype != resid.dtype or src.stride() != resid.stride() or src.shape != resid.shape or resid.shape[0] != Sq:
+            raise ValueError("resid / resid_in: one dtype, shape and row stride, q's rows")
+        entry = hip.lib().ditto_attention_resid_packed_bf16
+        outs = (src.data_ptr(), resid.data_ptr(), resid.stride(0), int(resid.dtype == torch.bfloat16))
     B = len(cu_q) - 1
     max_q = Sq if max_q is None else int(max_q)
     max_kv = Skv if max_kv is None else int(max_kv)
     cq = _dev_cu(cu_q, B, Sq, max_q, "cu_q", q.device)
     ck = _dev_cu(cu_kv, B, Skv, max_kv, "cu_kv", q.device)
-    if out is None:
-        out = torch.zeros(Sq, H * 64, dtype=torch.bfloat16, device=q.device)
-    _check_packed(out, "out", H)
-    if out.shape[0] != Sq:
-        raise ValueError(f"out: {Sq} rows expected")
-    hip.check(hip.lib().ditto_attention_packed_bf16(
-        q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), out.data_ptr(), out.stride(0),
-        cq.data_ptr(), ck.data_ptr(), B, H, Sq, Skv, max_q, max_kv, 64, torch.cuda.current_stream(q.device).cuda_stream))
-    return out
+    hip.check(entry(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), *outs, cq.data_ptr(), ck.data_ptr(),
+                    B, H, Sq, Skv, max_q, max_kv, 64, torch.cuda.current_stream(q.device).cuda_stream))
+    return out if resid is None else resid
+
+
+def attention_packed(q, k, v, H: int, cu_q, cu_kv, max_q=None, max_kv=None, out=None):
+    """softmax(q k^T) v per (utterance, head) of a packed batch (q carries scale * log2(e)): q / out [Sq, >= H*64] with utterance
+    b in rows [cu_q[b], cu_q[b+1]), k / v [Skv, >= H*64] with rows [cu_kv[b], cu_kv[b+1]); bf16.  Returns `out`."""
+    return _attention_packed(q, k, v, H, cu_q, cu_kv, max_q, max_kv, out=out)
 
 
 def attention_resid_packed(q, k, v, H: int, resid, cu_q, cu_kv, max_q=None, max_kv=None, resid_in=None):
     """The residual form of attention_packed: resid[i, h*64 + c] = resid_in[...] + attention (resid_in None: in place); resid fp32 or
     bf16 [Sq, >= H*64].  Returns `resid`."""
-    for n, x in (("q", q), ("k", k), ("v", v)):
-        _check_packed(x, n, H)
-    src = resid if resid_in is None else resid_in
-    _check_packed(resid, "resid", H, (torch.float32, torch.bfloat16))
-    if src.dtype != resid.dtype or src.stride() != resid.stride() or src.shape != resid.shape or resid.shape[0] != q.shape[0]:
-        raise ValueError("resid / resid_in: one dtype, shape and row stride, q's rows")
-    Sq, Skv = int(q.shape[0]), int(k.shape[0])
-    B = len(cu_q) - 1
-    max_q = Sq if max_q is None else int(max_q)
-    max_kv = Skv if max_kv is None else int(max_kv)
-    cq = _dev_cu(cu_q, B, Sq, max_q, "cu_q", q.device)
-    ck = _dev_cu(cu_kv, B, Skv, max_kv, "cu_kv", q.device)
-    hip.check(hip.lib().ditto_attention_resid_packed_bf16(
-        q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), src.data_ptr(), resid.data_ptr(),
-        resid.stride(0), int(resid.dtype == torch.bfloat16), cq.data_ptr(), ck.data_ptr(), B, H, Sq, Skv, max_q, max_kv, 64,
-        torch.cuda.current_stream(q.device).cuda_stream))
-    return resid
+    return _attention_packed(q, k, v, H, cu_q, cu_kv, max_q, max_kv, resid=resid, resid_in=resid_in)

@@ -1,5 +1,6 @@
 """SpeechGenerator.sample_guided: the guided strided (DDIM) loop over a variable-length batch.
-(a) dense, full lengths, uniform guidance, noises= and cond_by_audio: the bits of sample_latents_strided;
+(a) dense, full lengths, uniform guidance, noises= and cond_by_audio: the bits of the unfused strided chain (forward,
+    cfg_combine, linear_update) and of sample_latents_strided;
 (b) mixed speech / text / null-text lengths, per-utterance guidance, seeds: each utterance against the fp32 oracle's strided loop on
     its own rows;
 (c) padded output rows exactly 0, and NaN in padded rows of the text, the null text and audio_emb changing no bit;
@@ -11,7 +12,8 @@ import torch
 from ditto_tts_amd import hip
 from ditto_tts_amd.config import DiTTOConfig
 from ditto_tts_amd.modules import DiTTO
-from ditto_tts_amd.sampler import SpeechGenerator
+from ditto_tts_amd.around import cfg_combine, linear_update_
+from ditto_tts_amd.sampler import SpeechGenerator, strided_schedule
 from ditto_tts_amd.synth import hash_normal, synthetic_inputs, synthetic_state_dict
 from gpu_util import rel_l2
 from oracle import ditto_oracle as O
@@ -46,11 +48,28 @@ def test_dense_is_bitwise_sample_latents_strided(cfg_scale, eta):
     null = torch.zeros(1, T, 256, device=DEV)
     xinit = hash_normal((B, N, 256), "xT", 55).to(DEV)
     noises = [hash_normal((B, N, 256), f"z{i}", 77) for i in range(S)]
-    want = sg.sample_latents_strided(text, xinit, n_steps=S, eta=eta, cfg_scale=cfg_scale, null_text_emb=null, cond_by_audio=True,
-                                     noises=noises)
+    # the unfused chain per step: forward over [x; x] x [text; null], ditto_cfg_combine, ditto_linear_update
+    eng = m.engine()
+    x = xinit.clone()
+    cond_text = text if cfg_scale is None else torch.cat([text, null.expand_as(text)]).contiguous()
+    cond = eng.prepare_text(cond_text, N)
+    t = torch.empty(cond_text.shape[0], dtype=torch.long, device=DEV)
+    coef = torch.empty(3, B, device=DEV)
+    z = torch.empty_like(x)
+    for i, (t_val, a, ce, sigma) in enumerate(strided_schedule(sg.alphas_cumprod, S, eta)):
+        coef[0].fill_(a); coef[1].fill_(ce); coef[2].fill_(sigma)
+        t.fill_(t_val)
+        eps = eng.forward(x, cond, t) if cfg_scale is None else cfg_combine(eng.forward(torch.cat([x, x]), cond, t), cfg_scale)
+        if sigma != 0.0:
+            z.copy_(noises[i].to(DEV))
+        linear_update_(x, eps, z if sigma != 0.0 else None, coef[0], coef[1], coef[2])
+    want = x
     got = sg.sample_guided(text, xinit, n_steps=S, eta=eta, guidance=cfg_scale, null_text_emb=null, cond_by_audio=True, noises=noises)
     assert got.shape == want.shape and got.dtype == torch.float32
     assert torch.equal(got, want)
+    # sample_latents_strided is this loop with one uniform scale
+    assert torch.equal(sg.sample_latents_strided(text, xinit, n_steps=S, eta=eta, cfg_scale=cfg_scale, null_text_emb=null,
+                                                 cond_by_audio=True, noises=noises), want)
     # guidance as a [B] sequence of one value: the same bits
     if cfg_scale is not None:
         got_v = sg.sample_guided(text, xinit, n_steps=S, eta=eta, guidance=[cfg_scale] * B, null_text_emb=null, cond_by_audio=True,

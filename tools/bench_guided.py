@@ -4,8 +4,9 @@ lengths of tools/bench_varlen.py (random.Random(2026): N_b in [256, 1024], T_b i
 ms per denoise step of
   (a) sample_guided on the varlen batch;
   (b) sample_guided dense at the padded lengths;
-  (c) sample_latents_strided with the same settings (dense, torch's generator: the loop this one replaces);
   (d) one sample_guided call per utterance at its own (N_b, T_b).
+(Row (c), sample_latents_strided, was the unfused loop sample_guided replaced; it now runs sample_guided itself and differs from (b)
+only in the noise source, so it is no longer timed.)
 And the update alone at B = 32, N = 1024: the fused ditto_guided_update (Philox noise, CFG) against the old chain (2 copies into
 the doubled batch + cfg_combine + normal_ + linear_update), in us and GB/s on algorithmic bytes.
 Prints one JSON line (and writes it to --out).  Timed with HIP events."""
@@ -66,14 +67,12 @@ def main():
         res["a_guided_varlen_ms_per_step"] = timed(lambda: sg.sample_guided(text, x, speech_lengths=SL, text_lengths=TL, seeds=seeds,
                                                                             **kw), args.reps, args.warmup) / S
         res["b_guided_dense_ms_per_step"] = timed(lambda: sg.sample_guided(text, x, seeds=seeds, **kw), args.reps, args.warmup) / S
-        res["c_strided_dense_ms_per_step"] = timed(lambda: sg.sample_latents_strided(text, x, n_steps=S, eta=1.0, cfg_scale=G,
-                                                                                     null_text_emb=null), args.reps, args.warmup) / S
         solo = [(text[b:b + 1, :TL[b]].contiguous(), x[b:b + 1, :SL[b]].contiguous(), seeds[b:b + 1]) for b in range(B)]
         kw1 = dict(n_steps=S, eta=1.0, guidance=G)
         res["d_guided_per_utterance_ms_per_step"] = timed(
             lambda: [sg.sample_guided(t_, x_, seeds=s_, null_text_emb=null[:, :t_.shape[1]], **kw1) for t_, x_, s_ in solo],
             args.reps, args.warmup) / S
-        for k in ("a_guided_varlen", "b_guided_dense", "c_strided_dense", "d_guided_per_utterance"):
+        for k in ("a_guided_varlen", "b_guided_dense", "d_guided_per_utterance"):
             res[k + "_utt_steps_per_s"] = B * 1000.0 / res[k + "_ms_per_step"]
 
         # the update alone (every row valid, then the varlen lengths)
