@@ -1424,16 +1424,17 @@ int ditto_guided_update_packed(float* x2, const float* eps2, const float* noise,
     return DITTO_OK;
 }
 
-int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
-                                  const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
-                                  const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
-                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
-                                  ditto_stream_t stream, const ditto_call_opts* opts) {
-    if (!m) return fail(DITTO_ERR_ARG, "bad argument to ditto_guided_step_packed_opts");
-    if (int rc = check_guided_update("ditto_guided_step_packed_opts", x2, x2, noise, seeds, w, a, ce, cz, B, max_N, m->cfg.hidden_dim, cfg))
-        return rc;
-    if (B > 32767) return fail(DITTO_ERR_SHAPE, "ditto_guided_step_packed_opts: more than 32767 utterances");
-    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "ditto_guided_step_packed_opts: S must lie in [1, 2^30)");
+// the packed guided step with one scalar step tag (tags NULL) or one tag per utterance (guided_tags.hip)
+static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                              const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const uint32_t* tags,
+                              bool per_utt, const float* w, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
+                              int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
+                              size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    if (int rc = check_guided_update(who, x2, x2, noise, seeds, w, a, ce, cz, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
+    if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
+    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
+    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
     if (int rc = check_call_opts(opts)) return rc;
     CallScope scope(opts);
     // under guidance the forward runs over the 2B utterances of [x; x] x [text; null]: cu_speech then holds 2B + 1 offsets over 2S rows
@@ -1441,12 +1442,79 @@ int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, 
     const PackedWsPlan pw = plan_ws_packed(m->cfg, nb, rows, S_T > 0 ? S_T : 1);
     if (workspace_bytes < pw.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, pw.total);
     float* eps = (float*)((char*)workspace + pw.w.eps);
-    if (int rc = forward_packed("ditto_guided_step_packed_opts", m, x2, cond, t, cu_speech, cu_text, nb, rows, max_N, S_T, max_T, rope_cos,
-                                rope_sin, eps, workspace, workspace_bytes, stream))
+    if (int rc = forward_packed(who, m, x2, cond, t, cu_speech, cu_text, nb, rows, max_N, S_T, max_T, rope_cos, rope_sin, eps, workspace,
+                                workspace_bytes, stream))
         return rc;
     ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-    HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim, cfg != 0,
-                                        (hipStream_t)stream));
+    if (per_utt)
+        HIP_TRY(launch_guided_update_packed_tags(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim,
+                                                 cfg != 0, (hipStream_t)stream));
+    else
+        HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim, cfg != 0,
+                                            (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                  const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
+                                  const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
+                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                  ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_packed("ditto_guided_step_packed_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false, w, a,
+                              ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
+}
+
+// ---- continuous batching: per-utterance step tags (guided_tags.hip) and the device regroup (regroup_packed.hip) ----
+int ditto_guided_update_packed_tags(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                    const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu, int B, int S,
+                                    int max_N, int d, int cfg, ditto_stream_t stream) {
+    if (!cu) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_tags: null cu");
+    if (seeds && !tags) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_tags: seeds need tags (uint32 [B])");
+    if (int rc = check_guided_update("ditto_guided_update_packed_tags", x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed("ditto_guided_update_packed_tags", B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_guided_update_packed_tags(x2, eps2, noise, seeds, tags, w, a, ce, cz, cu, B, S, max_N, d, cfg != 0,
+                                             (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_packed_tags_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                       const int32_t* cu_text, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                       const float* w, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
+                                       int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
+                                       size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_packed("ditto_guided_step_packed_tags_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true, w, a,
+                              ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
+}
+
+int ditto_regroup_packed(const ditto_regroup_seg* table, int n_seg, const void* const* src, const size_t* src_bytes, void* const* dst,
+                         const size_t* dst_bytes, int n_bufs, const int64_t* seeds, int n_seeds, size_t max_bytes,
+                         ditto_stream_t stream) {
+    if (!table || !src || !src_bytes || !dst || !dst_bytes) return fail(DITTO_ERR_ARG, "ditto_regroup_packed: null pointer");
+    if (n_seg <= 0 || n_seg > 65535) return fail(DITTO_ERR_SHAPE, "ditto_regroup_packed: n_seg must lie in [1, 65535]");
+    if (n_bufs <= 0 || n_bufs > DITTO_REGROUP_BUFS)
+        return fail(DITTO_ERR_SHAPE, "ditto_regroup_packed: n_bufs must lie in [1, %d]", DITTO_REGROUP_BUFS);
+    if (n_seeds < 0 || (n_seeds > 0 && !seeds)) return fail(DITTO_ERR_ARG, "ditto_regroup_packed: n_seeds without seeds");
+    if ((uintptr_t)table % 16) return fail(DITTO_ERR_ARG, "ditto_regroup_packed: the table must be 16-byte aligned");
+    RegroupBufs bufs{};
+    for (int k = 0; k < n_bufs; ++k) {
+        if (((uintptr_t)src[k] | (uintptr_t)dst[k]) % 16)
+            return fail(DITTO_ERR_ARG, "ditto_regroup_packed: buffer %d is not 16-byte aligned", k);
+        if ((src_bytes[k] >> 36) || (dst_bytes[k] >> 36)) return fail(DITTO_ERR_SIZE, "ditto_regroup_packed: buffer %d exceeds 2^36 bytes", k);
+        bufs.src[k] = (const char*)src[k];
+        bufs.dst[k] = (char*)dst[k];
+        bufs.src_n[k] = src[k] ? (unsigned)(src_bytes[k] / 16) : 0u;
+        bufs.dst_n[k] = dst[k] ? (unsigned)(dst_bytes[k] / 16) : 0u;
+    }
+    HIP_TRY(launch_regroup_packed(table, n_seg, bufs, n_seeds > 0 ? seeds : nullptr, n_seeds, max_bytes / 16, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_regroup_cond_layout(const ditto_config* cfg, int S_T, size_t* kv_row_bytes, size_t* tmod_offset) {
+    if (!kv_row_bytes || !tmod_offset) return fail(DITTO_ERR_ARG, "ditto_regroup_cond_layout: null pointer");
+    if (int rc = check_cfg(cfg)) return rc;
+    if (S_T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_regroup_cond_layout: S_T must be positive");
+    *kv_row_bytes = (size_t)cfg->num_layers * 2 * cfg_dp(*cfg) * 2;
+    *tmod_offset = al((size_t)S_T * *kv_row_bytes);
     return DITTO_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct ditto_regroup_seg;   // include/ditto_hip.h
+
 namespace ditto {
 
 // ---------------- rowwise.hip : HBM-bound row / elementwise kernels ----------------
@@ -263,6 +265,23 @@ hipError_t launch_guided_update(float* x2, const float* eps2, const float* noise
 hipError_t launch_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
                                        const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                        int B, int S, int max_N, int d, bool cfg, hipStream_t s);
+// ---------------- guided_tags.hip ----------------
+// launch_guided_update_packed with the Philox step tag of utterance b read from tags[b] (device uint32 [B]); an utterance with
+// cz[b] == 0 gets the no-noise instantiation's value
+hipError_t launch_guided_update_packed_tags(float* x2, const float* eps2, const float* noise, const int64_t* seeds,
+                                            const unsigned* tags, const float* w, const float* a, const float* ce, const float* cz,
+                                            const int32_t* cu, int B, int S, int max_N, int d, bool cfg, hipStream_t s);
+// ---------------- regroup_packed.hip ----------------
+// the buffers a regroup's segments name by index, sizes in 16-byte units (a null pointer: no such buffer)
+#define DITTO_REGROUP_BUFS 6
+struct RegroupBufs {
+    const char* src[DITTO_REGROUP_BUFS];
+    char* dst[DITTO_REGROUP_BUFS];
+    unsigned src_n[DITTO_REGROUP_BUFS], dst_n[DITTO_REGROUP_BUFS];
+};
+// one workgroup column per segment of the DEVICE table; max_units: the longest segment (sizes the grid only)
+hipError_t launch_regroup_packed(const ::ditto_regroup_seg* table, int n_seg, const RegroupBufs& bufs, const int64_t* seeds,
+                                 int n_seeds, size_t max_units, hipStream_t s);
 
 // ---------------- attention.hip ----------------
 struct AttnArgs {

@@ -202,6 +202,28 @@ class DenoiseEngine:
                                                         ws.data_ptr(), ws.numel(), _stream()))
         return TextCond(buf, B, S_T, cu_seqlens=ctd, max_len=max_T)
 
+    def prepare_text_packed_into(self, text: torch.Tensor, text_cu_seqlens, buf: torch.Tensor, at: int = 0) -> int:
+        """prepare_text_packed's library call with the image (K/V rows | tmod) written into the uint8 device buffer `buf` at byte
+        `at` (a multiple of 256) instead of a fresh buffer: the same arithmetic, so the same bits.  `text`: fp32 CUDA [S_T,
+        text_dim], contiguous.  Returns the bytes of the image (ditto_packed_cond_bytes)."""
+        require_fused_attention(self.cfg, "packed batches")
+        if not (text.is_cuda and text.dtype == torch.float32 and text.is_contiguous() and text.dim() == 2
+                and text.shape[1] == self.cfg.text_dim):
+            raise ValueError(f"text: a contiguous fp32 CUDA tensor [S_T, {self.cfg.text_dim}] is needed")
+        S_T = int(text.shape[0])
+        B = len(text_cu_seqlens) - 1
+        ct, max_T = self._cu(text_cu_seqlens, B, S_T, None, "text_cu_seqlens")
+        nb = self.lib.ditto_packed_cond_bytes(C.byref(self._ccfg), B, S_T)
+        if nb == 0:
+            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
+        if at % 256 or buf.dtype != torch.uint8 or at + nb > buf.numel():
+            raise ValueError("the conditioning image does not fit the buffer at that offset")
+        ws = self.workspace_packed(B, B, S_T)
+        ctd = ct.to(self.device)
+        hip.check(self.lib.ditto_text_precompute_packed(self.handle, text.data_ptr(), ctd.data_ptr(), B, S_T, max_T,
+                                                        buf.data_ptr() + at, nb, ws.data_ptr(), ws.numel(), _stream()))
+        return int(nb)
+
     def _packed_cond(self, cond: TextCond, B: int):
         if cond.cu_seqlens is None:
             raise ValueError("a packed call needs a packed conditioning (prepare_text_packed)")

@@ -111,6 +111,10 @@ class CallOpts(C.Structure):
         return f"CallOpts(class_rows={self.class_rows}, residual_bf16={self.residual_bf16}, fr_mask={self.fr_mask}, lnq={self.lnq})"
 
 
+REGROUP_BUFS = 6
+REGROUP_SEG_WORDS = 8      # ditto_regroup_seg as int32 / uint32 words: kind, source, dest, aux, src_off, dst_off, n, dup_off (16-byte units)
+REGROUP_COPY, REGROUP_DRAW = 0, 1
+
 # ditto_layer_grads / ditto_grads have the layout of the weight structs (one pointer per state_dict key)
 LayerGrads, Grads = LayerWeights, Weights
 
@@ -183,6 +187,12 @@ SYMBOLS = {
     "ditto_guided_update_packed": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ditto_guided_step_packed_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                            _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    # continuous batching: per-utterance Philox step tags (device uint32 [B]) and the device regroup of a packed batch
+    "ditto_guided_update_packed_tags": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_guided_step_packed_tags_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                                _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),
+    "ditto_regroup_cond_layout": (_i, [C.POINTER(Config), _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),
     "ditto_tape_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
     "ditto_train_workspace_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),

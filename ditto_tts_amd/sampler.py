@@ -402,6 +402,20 @@ class SpeechGenerator:
 
         return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin)
 
+    def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None):
+        """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an
+        utterance, step() admits what fits, runs one guided strided step over everything in flight — each utterance at its own
+        index of its own strided_schedule — and returns the finished ones.  `max_rows` / `max_utterances` / `max_text_rows`: the
+        speech rows, utterances and conditioning rows (text, plus null text under guidance) in flight at once; every buffer is
+        sized from them here.  `class_rows`: hip.CallOpts(class_rows=) of every step (else the thread's hip.batch_class scope)."""
+        from .serving import DeviceBatch, GuidedStream
+        require_fused_attention(self.ditto_model.cfg, "request streams (packed batches)")
+        eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
+        batch = DeviceBatch(eng, max_rows=max_rows, max_utterances=max_utterances, max_text_rows=max_text_rows, guided=guided,
+                            class_rows=class_rows)
+        return GuidedStream(batch, self.alphas_cumprod, max_rows=max_rows, max_utterances=max_utterances,
+                            max_text_rows=max_text_rows, guided=guided, text_dim=eng.cfg.text_dim, hidden_dim=eng.cfg.hidden_dim)
+
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):
         return self.__p_sample(x, t, text_emb, noise)

@@ -1,0 +1,446 @@
+"""Continuous batching for guided strided sampling: utterances join and leave a packed batch between steps.
+
+`sample_guided_packed` serves a closed batch: every utterance starts at step 0, runs the same `n_steps` and `eta`, and the call
+returns when the last one is done.  A `GuidedStream` holds a queue of requests and a packed batch in flight; each `step()` admits
+what fits (strictly FIFO), runs ONE library call over everything in flight — every utterance at its own index of its own
+`strided_schedule` — and hands back the utterances that have run all their steps.  Under a pinned kernel class an utterance's bits
+depend on its own rows and lengths only, so it comes out exactly as `sample_guided_packed` samples it alone.
+
+Two layers:
+  * `GuidedStream`: the scheduler.  Host arithmetic only (queue, capacities, schedules, offsets); it drives a batch object through
+    three calls (`regroup`, `step`, `retire`) and never touches the device itself.
+  * `DeviceBatch`: the packed batch on one GPU.  State, conditioning, offsets and the per-step arguments live in buffers sized once
+    from the capacities; membership changes run in ONE launch of ditto_regroup_packed driven by a segment table, the step is
+    ditto_guided_step_packed_tags_opts.  Nothing synchronises the device; steady-state steps allocate nothing.
+They serve the reference's sampling loop (reference src/model/SpeechGenerator.py:130-164) to a request stream.
+"""
+from __future__ import annotations
+
+import collections
+import ctypes as C
+import math
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import hip
+
+
+class StreamHandle:
+    """What `submit` returns and `step` hands back with the result."""
+    __slots__ = ("id",)
+
+    def __init__(self, id_: int):
+        self.id = id_
+
+    def __repr__(self):
+        return f"StreamHandle({self.id})"
+
+
+class Request:
+    """One utterance of a stream: what was submitted, and where it stands (index `i` of its schedule; its slot `b`, speech row
+    `row` and conditioning rows `trow` / `nrow` in the batch's CURRENT buffers once admitted)."""
+    __slots__ = ("handle", "text", "null", "T", "T_null", "n_frames", "seed", "w", "n_steps", "eta", "x_T", "schedule", "i", "b",
+                 "row", "trow", "nrow")
+
+    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule):
+        self.handle, self.text, self.null = handle, text, null
+        self.T, self.T_null = int(text.shape[0]), 0 if null is None else int(null.shape[0])
+        self.n_frames, self.seed, self.w, self.n_steps, self.eta, self.x_T = n_frames, seed, w, n_steps, eta, x_T
+        self.schedule, self.i = schedule, 0
+        self.b = self.row = self.trow = self.nrow = None
+
+    @property
+    def text_rows(self) -> int:
+        return self.T + self.T_null
+
+
+class Plan:
+    """A membership change: `members` (Requests in their new order: the survivors in their old order, then the newcomers in
+    admission order), which of them are `newcomers`, and the new layout — `cu` speech offsets [B + 1], `cu_text` / `cu_null` text
+    offsets [B + 1] (cu_null None without guidance)."""
+    __slots__ = ("members", "newcomers", "cu", "cu_text", "cu_null")
+
+    def __init__(self, members, newcomers, guided):
+        self.members, self.newcomers = list(members), list(newcomers)
+        self.cu, self.cu_text = _cumulate(r.n_frames for r in members), _cumulate(r.T for r in members)
+        self.cu_null = _cumulate(r.T_null for r in members) if guided else None
+
+
+class StepArgs:
+    """One step over the batch in flight: per-utterance lists in slot order."""
+    __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles")
+
+
+def _cumulate(lengths) -> List[int]:
+    out = [0]
+    for n in lengths:
+        out.append(out[-1] + int(n))
+    return out
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+class GuidedStream:
+    """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None)
+    h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None)
+    done = stream.step()          # [(handle, latents fp32 [N_b, d] on the GPU), ...]
+    stream.pending, stream.active, stream.drain()
+
+    Capacities: `max_rows` speech rows, `max_utterances` utterances and `max_text_rows` rows of the conditioning (text rows, plus
+    the null-text rows under guidance) in flight at once.  `guided=True`: every request carries `guidance` and `null_text_emb`;
+    `guided=False`: none does (a mix would waste the unconditional half of the doubled batch).
+    x_T of a request: `x_T` when given, else Philox of its `seed` at tag 0xFFFFFFFF — ditto_noise_normal's numbers, what
+    sample_guided_packed(seeds=) starts from.  Every step's z is Philox of the seed at the step's tag.  `seed=None` draws one from
+    torch's default CPU generator at submit."""
+
+    def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
+                 text_dim: int, hidden_dim: int):
+        for name, v in (("max_rows", max_rows), ("max_utterances", max_utterances), ("max_text_rows", max_text_rows)):
+            if not _is_int(v) or v < 1:
+                raise ValueError(f"{name}: a positive int is needed, got {v!r}")
+        self.batch, self.guided = batch, bool(guided)
+        self.max_rows, self.max_utterances, self.max_text_rows = max_rows, max_utterances, max_text_rows
+        self.text_dim, self.hidden_dim = int(text_dim), int(hidden_dim)
+        self._acp = alphas_cumprod.detach().double().cpu()
+        self._schedules = {}                       # (n_steps, eta) -> strided_schedule
+        self._queue: collections.deque = collections.deque()
+        self._active: List[Request] = []
+        self._dirty = False                        # utterances left since the last regroup: the buffers have holes
+        self._next_id = 0
+
+    # ------------------------------------------------------------------ the public surface
+    @property
+    def pending(self) -> int:
+        """requests submitted and not yet admitted"""
+        return len(self._queue)
+
+    @property
+    def active(self) -> int:
+        """utterances in flight"""
+        return len(self._active)
+
+    def _schedule(self, n_steps: int, eta: float):
+        key = (n_steps, eta)
+        if key not in self._schedules:
+            from .sampler import strided_schedule
+            self._schedules[key] = strided_schedule(self._acp, n_steps, eta)
+        return self._schedules[key]
+
+    def _text(self, t, name):
+        if not isinstance(t, torch.Tensor) or not t.dtype.is_floating_point:
+            raise ValueError(f"{name}: a floating-point tensor [rows, {self.text_dim}] is needed")
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != self.text_dim:
+            raise ValueError(f"{name}: shape [rows >= 1, {self.text_dim}] expected, got {list(t.shape)}")
+        return t.detach()
+
+    def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None) -> StreamHandle:
+        """Queue one utterance.  Everything is validated here, on the host: a bad request raises ValueError and leaves the stream as
+        it was; so does one that could never fit the capacities."""
+        text = self._text(text_emb, "text_emb")
+        if not _is_int(n_frames) or n_frames < 1:
+            raise ValueError(f"n_frames: a positive int is needed, got {n_frames!r}")
+        if not _is_int(n_steps):
+            raise ValueError(f"n_steps: an int is needed, got {n_steps!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not math.isfinite(eta) or eta < 0:
+            raise ValueError(f"eta: a finite number >= 0 is needed, got {eta!r}")
+        schedule = self._schedule(n_steps, float(eta))             # (ValueError unless 1 <= n_steps <= diffusion_steps)
+        if self.guided:
+            if guidance is None or null_text_emb is None:
+                raise ValueError("this stream is guided: every request needs guidance= and null_text_emb=")
+            if isinstance(guidance, bool) or not isinstance(guidance, (int, float)) or not math.isfinite(guidance):
+                raise ValueError(f"guidance: a finite number is needed, got {guidance!r}")
+            null = self._text(null_text_emb, "null_text_emb")
+        else:
+            if guidance is not None or null_text_emb is not None:
+                raise ValueError("this stream is unguided: a request with guidance= or null_text_emb= belongs in a guided stream")
+            null = None
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)))
+        elif not _is_int(seed) or not -2 ** 63 <= seed < 2 ** 63:
+            raise ValueError(f"seed: an int64 is needed, got {seed!r}")
+        if x_T is not None:
+            if not isinstance(x_T, torch.Tensor) or not x_T.dtype.is_floating_point or tuple(x_T.shape) != (n_frames, self.hidden_dim):
+                raise ValueError(f"x_T: a floating-point tensor [{n_frames}, {self.hidden_dim}] is needed")
+            x_T = x_T.detach()
+        req = Request(StreamHandle(self._next_id), text, null, n_frames, seed, None if guidance is None else float(guidance), n_steps,
+                      float(eta), x_T, schedule)
+        if req.n_frames > self.max_rows:
+            raise ValueError(f"a request of {req.n_frames} frames can never fit max_rows = {self.max_rows}")
+        if req.text_rows > self.max_text_rows:
+            raise ValueError(f"a request of {req.text_rows} conditioning rows can never fit max_text_rows = {self.max_text_rows}")
+        self._next_id += 1
+        self._queue.append(req)
+        return req.handle
+
+    def _fits(self, req: Request, members: List[Request]) -> bool:
+        return (len(members) + 1 <= self.max_utterances
+                and sum(r.n_frames for r in members) + req.n_frames <= self.max_rows
+                and sum(r.text_rows for r in members) + req.text_rows <= self.max_text_rows)
+
+    def step(self):
+        """Admit (FIFO, stopping at the first request that does not fit: nothing is overtaken), regroup if the membership changed,
+        run one step over everything in flight, retire the utterances that have run their own n_steps.  Returns the retired
+        [(handle, latents fp32 [N_b, d] on the GPU), ...] in slot order; [] when nothing is in flight."""
+        members, newcomers = list(self._active), []
+        while self._queue and self._fits(self._queue[0], members):
+            req = self._queue.popleft()
+            members.append(req)
+            newcomers.append(req)
+        if not members:
+            return []
+        args = self._step_args(members)
+        if newcomers or self._dirty:
+            self.batch.regroup(Plan(members, newcomers, self.guided), args)
+            self._dirty = False
+        self._active = members
+        self.batch.step(args)
+        done = []
+        for r in members:
+            r.i += 1
+            if r.i == r.n_steps:
+                done.append(r)
+        if not done:
+            return []
+        outs = self.batch.retire(done)
+        self._active = [r for r in members if r.i < r.n_steps]
+        self._dirty = True
+        return [(r.handle, o) for r, o in zip(done, outs)]
+
+    def drain(self):
+        """step() until nothing is pending or in flight; every result, in the order it came back."""
+        out = []
+        while self._queue or self._active:
+            out.extend(self.step())
+        return out
+
+    def _step_args(self, members: List[Request]) -> StepArgs:
+        s = StepArgs()
+        s.B, s.S = len(members), sum(r.n_frames for r in members)
+        s.max_N = max(r.n_frames for r in members)
+        s.S_T = sum(r.text_rows for r in members)
+        s.max_T = max(max(r.T, r.T_null) for r in members)
+        rows = [r.schedule[r.i] for r in members]                   # (tau, a, ce, sigma) of each utterance's own step
+        s.t = [int(q[0]) for q in rows]
+        s.a, s.ce, s.cz = [q[1] for q in rows], [q[2] for q in rows], [q[3] for q in rows]
+        s.tags = [int(q[0]) & 0xFFFFFFFF for q in rows]             # the step's Philox tag: its timestep, as in the closed loops
+        s.w = [r.w for r in members] if self.guided else None
+        s.seeds = [r.seed for r in members]
+        s.handles = [r.handle for r in members]
+        return s
+
+
+def _pad(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+class _Upload:
+    """One device buffer fed from a ring of pinned host buffers by asynchronous copies.  A slot is rewritten only after the copy that
+    last read it has finished (its event — `slots` sends old; the wait is on that one copy, not on the device)."""
+
+    def __init__(self, nbytes: int, device, slots: int = 8):
+        self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self._host = [torch.zeros(nbytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+        self._np = [h.numpy() for h in self._host]
+        self._events = [None] * slots
+        self._k = 0
+
+    def send(self, data: np.ndarray):
+        k, n = self._k, int(data.nbytes)
+        self._k = (k + 1) % len(self._host)
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        self._np[k][:n] = data.view(np.uint8).reshape(-1)
+        self.dev[:n].copy_(self._host[k][:n], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev.device))
+        self._events[k] = ev
+
+
+# the buffers a regroup's segments name (ditto_regroup_packed): sources and destinations
+_SRC_X, _SRC_XT, _SRC_COND, _SRC_NEW_COND, _SRC_TABLE = range(5)
+_DST_X, _DST_OUT, _DST_COND, _DST_OFFSETS = range(4)
+
+
+class DeviceBatch:
+    """The packed batch of a GuidedStream on one GPU.  Buffers (sized once from the capacities): two state buffers [2 max_rows, d]
+    ([max_rows, d] unguided) and two conditioning images (a regroup reads one and writes the other), a staging image for the
+    newcomers' conditioning and one for callers' x_T, the device offsets, the per-step argument block and the segment table."""
+
+    def __init__(self, engine, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool, class_rows=None):
+        from .engine import require_fused_attention
+        require_fused_attention(engine.cfg, "request streams (packed batches)")
+        self.eng, self.lib, self.guided = engine, engine.lib, bool(guided)
+        self.halves = 2 if guided else 1
+        self.maxB, self.maxS, self.maxT = int(max_utterances), int(max_rows), int(max_text_rows)
+        self.opts = None if class_rows is None else hip.CallOpts(class_rows=int(class_rows))
+        dev, d = engine.device, engine.cfg.hidden_dim
+        self.d = d
+        row, off = C.c_size_t(0), C.c_size_t(0)
+        hip.check(self.lib.ditto_regroup_cond_layout(C.byref(engine._ccfg), self.maxT, C.byref(row), C.byref(off)))
+        self.kv_row = int(row.value)                                       # bytes of one K/V row of the conditioning image
+        self.tmod_row = 2 * d * 4
+        nbB = self.halves * self.maxB
+        cond_bytes = int(self.lib.ditto_packed_cond_bytes(C.byref(engine._ccfg), nbB, self.maxT))
+        with torch.cuda.device(dev):
+            self.x = [torch.zeros(self.halves * self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)]
+            self.cond = [torch.zeros(cond_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+            # every newcomer's own image [K/V rows | tmod], 256-byte aligned, one behind the other
+            self.new_cond = torch.zeros(self.maxT * self.kv_row + self.maxB * (_pad(self.halves * self.tmod_row, 256) + 256),
+                                        dtype=torch.uint8, device=dev)
+            self.x_T = torch.zeros(self.maxS, d, dtype=torch.float32, device=dev)
+            self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
+            self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
+            # the step block: t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w fp32 [maxB] | tags uint32 [maxB]
+            self.o_t, self.o_seeds = 0, _pad(nbB * 8, 16)
+            self.o_f = self.o_seeds + _pad(self.maxB * 8, 16)
+            self.f_stride = _pad(self.maxB * 4, 16)
+            self.block = _Upload(self.o_f + 5 * self.f_stride, dev)
+            self.max_seg = 8 * self.maxB + 8
+            self.table = _Upload(self.max_seg * 4 * hip.REGROUP_SEG_WORDS + 2 * self.cu_pad * 4, dev)
+            engine.workspace_packed(nbB, self.halves * self.maxS, self.maxT)
+            self.rope = engine.rope_tables(self.maxS)                      # rows [0, max_N) of it are ditto_rope_tables(max_N)
+        self.cur = 0                 # which of x / cond holds the batch in flight
+        self.B = self.S = self.T_text = 0
+        self._tmod_off = 0           # of the current conditioning image
+        self._block_sent = False     # the step block of the coming step went up with its regroup
+
+    # ------------------------------------------------------------------ uploads
+    def _send_block(self, a: StepArgs):
+        B, nb = a.B, self.halves * a.B
+        buf = np.zeros(self.o_f + 5 * self.f_stride, dtype=np.uint8)
+        buf[self.o_t:self.o_t + nb * 8].view(np.int64)[:] = a.t * self.halves
+        buf[self.o_seeds:self.o_seeds + B * 8].view(np.int64)[:] = a.seeds
+        for k, v in enumerate((a.a, a.ce, a.cz, a.w if a.w is not None else [0.0] * B)):
+            o = self.o_f + k * self.f_stride
+            buf[o:o + B * 4].view(np.float32)[:] = v
+        o = self.o_f + 4 * self.f_stride
+        buf[o:o + B * 4].view(np.uint32)[:] = a.tags
+        self.block.send(buf)
+
+    def _block_ptr(self, off: int) -> int:
+        return self.block.dev.data_ptr() + off
+
+    def _tmod_offset(self, S_T: int) -> int:
+        row, off = C.c_size_t(0), C.c_size_t(0)
+        hip.check(self.lib.ditto_regroup_cond_layout(C.byref(self.eng._ccfg), S_T, C.byref(row), C.byref(off)))
+        return int(off.value)
+
+    def _run_table(self, segs: List[List[int]], tail: Optional[np.ndarray], out: Optional[torch.Tensor]):
+        """upload the segments (+ `tail`: int32 words appended for the offsets segment) and run ditto_regroup_packed"""
+        if len(segs) > self.max_seg:
+            raise RuntimeError("regroup: more segments than the table holds")
+        tab = np.asarray(segs, dtype=np.int64).astype(np.uint32).view(np.uint8).reshape(-1)
+        data = tab if tail is None else np.concatenate([tab, tail.view(np.uint8).reshape(-1)])
+        self.table.send(data)
+        nxt = 1 - self.cur
+        src = [self.x[self.cur], self.x_T, self.cond[self.cur], self.new_cond, self.table.dev]
+        dst = [self.x[nxt], out, self.cond[nxt], self.offsets]
+        n = hip.REGROUP_BUFS
+        sp, sb, dp, db = (C.c_void_p * n)(), (C.c_size_t * n)(), (C.c_void_p * n)(), (C.c_size_t * n)()
+        for k, t in enumerate(src):
+            sp[k], sb[k] = t.data_ptr(), t.numel() * t.element_size()
+        for k, t in enumerate(dst):
+            if t is not None:
+                dp[k], db[k] = t.data_ptr(), t.numel() * t.element_size()
+        hip.check(self.lib.ditto_regroup_packed(self.table.dev.data_ptr(), len(segs), sp, sb, dp, db, n, self._block_ptr(self.o_seeds),
+                                                self.maxB, 16 * max(s[6] for s in segs), _stream()))
+
+    # ------------------------------------------------------------------ what the scheduler calls
+    def _condition(self, r: Request, at: int) -> int:
+        """the conditioning of newcomer `r`, computed exactly as a solo sample_guided_packed computes it — one
+        ditto_text_precompute_packed over that utterance's [text; null] — into the staging image at byte `at`; returns its size"""
+        dev = self.eng.device
+        text = r.text.to(dev, torch.float32)
+        ct = [0, r.T]
+        if self.guided:
+            text = torch.cat([text, r.null.to(dev, torch.float32)], dim=0)
+            ct.append(r.T + r.T_null)
+        nb = self.eng.prepare_text_packed_into(text.contiguous(), ct, self.new_cond, at)
+        return nb
+
+    def regroup(self, plan: Plan, args: StepArgs):
+        """Build the next batch in the other pair of buffers: survivors' rows from the current ones, newcomers' x_T (drawn from the
+        seed, or the caller's) and freshly computed conditioning, the new offsets.  One launch."""
+        self._send_block(args)                                     # first: "draw x_T" reads the newcomers' seeds from it
+        d4, kv16, tm16 = self.d // 4, self.kv_row // 16, self.tmod_row // 16
+        B, S, Tt = len(plan.members), plan.cu[-1], plan.cu_text[-1]
+        S_T = Tt + (plan.cu_null[-1] if self.guided else 0)
+        tmod_new = self._tmod_offset(S_T)
+        at, xt_row = 0, 0
+        new_at = {}
+        for r in plan.newcomers:
+            new_at[r.handle.id] = at
+            at += self._condition(r, at)
+        segs = []
+        for j, r in enumerate(plan.members):
+            new = r.handle.id in new_at
+            n_x = r.n_frames * d4
+            dup = S * d4 if self.guided else 0
+            if not new:
+                segs.append([hip.REGROUP_COPY, _SRC_X, _DST_X, 0, r.row * d4, plan.cu[j] * d4, n_x, dup])
+            elif r.x_T is not None:
+                self.x_T[xt_row:xt_row + r.n_frames].copy_(r.x_T, non_blocking=True)
+                segs.append([hip.REGROUP_COPY, _SRC_XT, _DST_X, 0, xt_row * d4, plan.cu[j] * d4, n_x, dup])
+                xt_row += r.n_frames
+            else:
+                segs.append([hip.REGROUP_DRAW, 0, _DST_X, j, 0, plan.cu[j] * d4, n_x, dup])
+            # conditioning: K/V rows and the tmod row of the text, then of the null text ([text_0 .. ; null_0 ..] under CFG)
+            if new:
+                base, own_tmod = new_at[r.handle.id], new_at[r.handle.id] + self._tmod_offset(r.text_rows)
+                source, kv_t, kv_n = _SRC_NEW_COND, base // 16, base // 16 + r.T * kv16
+                tm_t, tm_n = own_tmod // 16, own_tmod // 16 + tm16
+            else:
+                source, kv_t, kv_n = _SRC_COND, r.trow * kv16, r.nrow * kv16 if self.guided else 0
+                tm_t, tm_n = self._tmod_off // 16 + r.b * tm16, self._tmod_off // 16 + (self.B + r.b) * tm16
+            segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, kv_t, plan.cu_text[j] * kv16, r.T * kv16, 0])
+            segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, tm_t, tmod_new // 16 + j * tm16, tm16, 0])
+            if self.guided:
+                segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, kv_n, (Tt + plan.cu_null[j]) * kv16, r.T_null * kv16, 0])
+                segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, tm_n, tmod_new // 16 + (B + j) * tm16, tm16, 0])
+        # the offsets ride behind the segments in the same upload and are copied from there: [cu; S + cu[1:]] (cu unguided) | cu_text
+        tail = np.zeros(2 * self.cu_pad, dtype=np.int32)
+        cu2 = plan.cu + [S + c for c in plan.cu[1:]] if self.guided else plan.cu
+        ct2 = plan.cu_text + [Tt + c for c in plan.cu_null[1:]] if self.guided else plan.cu_text
+        tail[:len(cu2)] = cu2
+        tail[self.cu_pad:self.cu_pad + len(ct2)] = ct2
+        segs.append([hip.REGROUP_COPY, _SRC_TABLE, _DST_OFFSETS, 0, (len(segs) + 1) * 2, 0, 2 * self.cu_pad // 4, 0])
+        self._run_table(segs, tail, None)
+        self.cur = 1 - self.cur
+        self.B, self.S, self.T_text, self._tmod_off = B, S, Tt, tmod_new
+        for j, r in enumerate(plan.members):
+            r.b, r.row, r.trow = j, plan.cu[j], plan.cu_text[j]
+            r.nrow = Tt + plan.cu_null[j] if self.guided else None
+        self._block_sent = True
+
+    def step(self, a: StepArgs):
+        """ditto_guided_step_packed_tags_opts over the batch in flight, in place on the current state"""
+        if not self._block_sent:
+            self._send_block(a)
+        self._block_sent = False
+        eng, f = self.eng, self.o_f
+        nb, rows = self.halves * a.B, self.halves * a.S
+        ws = eng.workspace_packed(nb, rows, a.S_T)
+        hip.check(self.lib.ditto_guided_step_packed_tags_opts(
+            eng.handle, self.x[self.cur].data_ptr(), self.cond[self.cur].data_ptr(), self._block_ptr(self.o_t), self.offsets.data_ptr(),
+            self.offsets.data_ptr() + 4 * self.cu_pad, None, self._block_ptr(self.o_seeds), self._block_ptr(f + 4 * self.f_stride),
+            self._block_ptr(f + 3 * self.f_stride) if self.guided else None, self._block_ptr(f), self._block_ptr(f + self.f_stride),
+            self._block_ptr(f + 2 * self.f_stride), a.B, a.S, a.max_N, a.S_T, a.max_T, int(self.guided), self.rope[0].data_ptr(),
+            self.rope[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if self.opts is None else C.byref(self.opts)))
+
+    def retire(self, done: List[Request]) -> List[torch.Tensor]:
+        """the packed rows of the utterances that leave, copied out of the state in one launch; the batch keeps its layout (with
+        holes) until the next regroup"""
+        cu = _cumulate(r.n_frames for r in done)
+        out = torch.empty(cu[-1], self.d, dtype=torch.float32, device=self.eng.device)
+        d4 = self.d // 4
+        segs = [[hip.REGROUP_COPY, _SRC_X, _DST_OUT, 0, r.row * d4, cu[k] * d4, r.n_frames * d4, 0] for k, r in enumerate(done)]
+        self._run_table(segs, None, out)
+        return [out[cu[k]:cu[k + 1]] for k in range(len(done))]
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream

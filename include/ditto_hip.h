@@ -520,6 +520,51 @@ int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, 
                                   const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                                   ditto_stream_t stream, const ditto_call_opts* opts);
 
+/* ---- Continuous batching over packed batches: utterances join and leave between steps, each at its own index of its own strided
+ * schedule.  The reference's loop (src/model/SpeechGenerator.py:130-164: __p_sample and __sample_latents) serves one closed batch in
+ * which every utterance starts at step 0 and runs the same steps; these entries serve the same per-utterance arithmetic to a batch
+ * whose membership changes.
+ * ditto_guided_update_packed_tags / ditto_guided_step_packed_tags_opts: ditto_guided_update_packed / ditto_guided_step_packed_opts
+ *   with the Philox step tag of utterance b read from tags[b] (device uint32 [B]; may be NULL without seeds) instead of one scalar:
+ *   utterance b gets the bits the scalar-tag entry gives it at step = tags[b].  An utterance with cz[b] == 0 (a sigma = 0 step of
+ *   its schedule) gets the value of the entry called without noise (up to the sign of a zero).  Every other argument as there. */
+int ditto_guided_update_packed_tags(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                    const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu, int B, int S,
+                                    int max_N, int d, int cfg, ditto_stream_t stream);
+int ditto_guided_step_packed_tags_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                       const int32_t* cu_text, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                       const float* w, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
+                                       int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
+                                       size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+/* ditto_regroup_packed: build the next packed batch from the current one plus the newcomers, in ONE launch driven by a DEVICE table
+ *   of n_seg segments.  A segment moves `n` 16-byte units (every row of the state, the K/V cache and tmod is a whole number of them)
+ *   to unit dst_off of destination buffer `dest` and, when dup_off != 0, also to dst_off + dup_off (a speech segment under CFG: the
+ *   unconditional half).  kind 0: the units come from unit src_off of source buffer `source` — a survivor's rows of the current
+ *   state or conditioning, a newcomer's freshly computed conditioning, a caller's x_T, or offsets the caller appended to the
+ *   uploaded table itself (cu, doubled cu, cu_text; name the table's buffer as a source).  kind 1: "draw x_T" — unit i of the
+ *   segment is Philox of seeds[aux] at tag 0xFFFFFFFF, quad index i: with one segment per utterance, the numbers
+ *   ditto_noise_normal(seeds, 0xFFFFFFFF) writes for it.  A destination may be an output buffer receiving the rows of utterances that
+ *   leave.  src / dst: HOST arrays of n_bufs (<= 6) device pointers (16-byte aligned; NULL = absent) and their sizes in bytes
+ *   (< 2^36).  Every index, offset and length of the table is clamped into those sizes on the device: a bad table gives wrong rows,
+ *   never an access outside the buffers.  Segments must not overlap a destination range another segment reads or writes.
+ *   max_bytes: the longest segment (sizes the grid only).  Nothing synchronises.
+ * ditto_regroup_cond_layout: the packed conditioning image of S_T text rows (ditto_packed_cond_bytes): bytes of one K/V row and the
+ *   byte offset of tmod fp32 [B, 2d] behind the S_T K/V rows. */
+typedef struct ditto_regroup_seg {
+    int32_t kind;      /* 0: copy, 1: draw x_T */
+    int32_t source;    /* kind 0: index into src */
+    int32_t dest;      /* index into dst */
+    int32_t aux;       /* kind 1: index into seeds */
+    uint32_t src_off;  /* 16-byte units */
+    uint32_t dst_off;
+    uint32_t n;
+    uint32_t dup_off;
+} ditto_regroup_seg;
+int ditto_regroup_packed(const ditto_regroup_seg* table, int n_seg, const void* const* src, const size_t* src_bytes, void* const* dst,
+                         const size_t* dst_bytes, int n_bufs, const int64_t* seeds, int n_seeds, size_t max_bytes,
+                         ditto_stream_t stream);
+int ditto_regroup_cond_layout(const ditto_config* cfg, int S_T, size_t* kv_row_bytes, size_t* tmod_offset);
+
 /* ---- training: the backward of DiTTO.forward, so that the reference's training closure
  * (src/TrainDiTTO.py:55-95: model.train(); loss = mse(model(x_t, text, t), noise); loss.backward()) runs on this
  * library.  Gradients are fp32, in the reference's parameter layout (one pointer per state_dict key, as
