@@ -27,6 +27,7 @@
 using namespace ditto;
 
 namespace ditto {
+extern thread_local int t_gemm_structure;   // gemm.hip: the tile structure this thread's last launch_gemm took (ditto_gemm_epilogue_bf16)
 
 thread_local char g_err[512] = "";
 
@@ -1156,6 +1157,66 @@ int ditto_gemm_bf16(const void* A, int lda, const void* W, const float* bias, co
         default: return fail(DITTO_ERR_ARG, "epilogue must be 0, 1, 3, 4 or 6");
     }
     HIP_TRY(launch_gemm(g, e, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_gemm_epilogue_bf16(const ditto_gemm_epilogue_args* a, int epilogue, int* structure_out, ditto_stream_t stream) {
+    const char* who = "ditto_gemm_epilogue_bf16";
+    if (structure_out) *structure_out = 0;
+    if (!a || !a->A || !a->W || !a->out) return fail(DITTO_ERR_ARG, "null pointer to %s", who);
+    if (epilogue == 5) return fail(DITTO_ERR_ARG, "%s: epilogue 5 (fp8 output) belongs to ditto_gemm_fp8", who);
+    if (epilogue < 0 || epilogue > 9) return fail(DITTO_ERR_ARG, "%s: epilogue must be 0 .. 9 (not 5)", who);
+    const int M = a->M, N = a->N, K = a->K;
+    if (M <= 0 || N <= 0 || K <= 0) return fail(DITTO_ERR_SHAPE, "%s: M, N and K must be positive", who);
+    if (K % 64 || N % 16) return fail(DITTO_ERR_SHAPE, "%s: need K %% 64 == 0 and N %% 16 == 0", who);
+    if (a->lda % 8 || a->lda < K || a->ldw % 8 || (a->ldw && a->ldw < K))
+        return fail(DITTO_ERR_SHAPE, "%s: lda / ldw must cover K columns in multiples of 8 (ldw 0 = K)", who);
+    if (a->w_rows < 0 || a->w_rows > N) return fail(DITTO_ERR_SHAPE, "%s: w_rows must be in [0, N] (0 = N)", who);
+    const GemmEpilogue e = (GemmEpilogue)epilogue;
+    const bool f32_out = e == EPI_BIAS_RES_F32 || e == EPI_BIAS_F32;
+    const int out_cols = (e == EPI_GATED || e == EPI_GATED_PRE) ? N / 2 : (e == EPI_GATED_BWD ? 2 * N : N);
+    if (a->ldo < out_cols || a->ldo % (f32_out ? 4 : 8))   // rows are written in 16-byte pieces
+        return fail(DITTO_ERR_SHAPE, "%s: ldo must cover %d columns in multiples of %d", who, out_cols, f32_out ? 4 : 8);
+    switch (e) {
+        case EPI_BIAS_RES_F32:
+            if (a->residual && (a->ldr < N || a->ldr % 4)) return fail(DITTO_ERR_SHAPE, "%s: ldr must cover N columns in multiples of 4", who);
+            if (a->out2_bf16 && (a->ldo2 < N || a->ldo2 % 4)) return fail(DITTO_ERR_SHAPE, "%s: ldo2 must cover N columns in multiples of 4", who);
+            break;
+        case EPI_QKV_ROPE:
+        case EPI_QKV_ROPE_PACKED:
+            if (!a->rope_cos || !a->rope_sin) return fail(DITTO_ERR_ARG, "%s: the RoPE epilogues need rope_cos and rope_sin (read unless rope_freq_rev is given)", who);
+            if (e == EPI_QKV_ROPE_PACKED && !a->rope_pos) return fail(DITTO_ERR_ARG, "%s: epilogue 9 needs rope_pos", who);
+            if (N % 64 || a->rope_cols % 64 || a->rope_cols < 0 || a->rope_cols > N)
+                return fail(DITTO_ERR_SHAPE, "%s: the RoPE epilogues need N %% 64 == 0 and 0 <= rope_cols <= N in multiples of 64", who);
+            if (e == EPI_QKV_ROPE && a->rope_rows_per_batch <= 0) return fail(DITTO_ERR_SHAPE, "%s: epilogue 2 needs rope_rows_per_batch > 0", who);
+            break;
+        case EPI_GATED:
+            if (!a->bias) return fail(DITTO_ERR_ARG, "%s: the gated epilogue needs a bias", who);
+            if (N % 32) return fail(DITTO_ERR_SHAPE, "%s: the gated epilogue needs N %% 32 == 0", who);
+            break;
+        case EPI_GATED_PRE:
+            if (!a->bias || !a->out2_bf16) return fail(DITTO_ERR_ARG, "%s: epilogue 8 needs a bias and out2_bf16", who);
+            if (N % 256) return fail(DITTO_ERR_SHAPE, "%s: epilogue 8 runs on 256 x 256 tiles only: N %% 256 == 0", who);
+            if (a->ldo2 < N || a->ldo2 % 8) return fail(DITTO_ERR_SHAPE, "%s: ldo2 must cover N columns in multiples of 8", who);
+            break;
+        case EPI_GATED_BWD:
+            if (a->bias || !a->pre_bf16 || !a->colsum_partial) return fail(DITTO_ERR_ARG, "%s: epilogue 7 takes no bias and needs pre_bf16 and colsum_partial", who);
+            if (N % 256 || !gemm_gated_bwd_fused_ok(M, N))
+                return fail(DITTO_ERR_SHAPE, "%s: epilogue 7 needs N %% 256 == 0, N >= 2048, at least 144 tiles of 256 x 256 and gemm_tile 0 or 256", who);
+            if (a->ldpre < 2 * N || a->ldpre % 8) return fail(DITTO_ERR_SHAPE, "%s: ldpre must cover 2 N columns in multiples of 8", who);
+            break;
+        default: break;
+    }
+    GemmArgs g{};
+    g.A = a->A; g.lda = a->lda; g.W = a->W; g.ldw = a->ldw; g.w_rows = a->w_rows; g.bias = a->bias;
+    g.residual = a->residual; g.ldr = a->ldr; g.out = a->out; g.ldo = a->ldo; g.out2_bf16 = a->out2_bf16; g.ldo2 = a->ldo2;
+    g.rope_cos = a->rope_cos; g.rope_sin = a->rope_sin; g.rope_rows_per_batch = a->rope_rows_per_batch; g.rope_cols = a->rope_cols;
+    g.rope_freq_rev = a->rope_freq_rev; g.rope_pos = a->rope_pos;
+    g.pre_bf16 = a->pre_bf16; g.ldpre = a->ldpre; g.colsum_partial = a->colsum_partial;
+    g.M = M; g.N = N; g.K = K;
+    const hipError_t err = launch_gemm(g, e, (hipStream_t)stream);
+    if (structure_out) *structure_out = t_gemm_structure;
+    HIP_TRY(err);
     return DITTO_OK;
 }
 

@@ -49,6 +49,9 @@ int g_fr_class_rows = 0;   // kernels.h fr_pays: rows of the unsplit batch whose
 thread_local CallOpts t_opts = {-1, -1, -1, -1};   // kernels.h: the calling thread's per-call options (-1 = the process default)
 int g_pp_mask = [] { const char* e = getenv("DITTO_PP_MASK"); return e ? atoi(e) : -1; }();   // -1 = built-in rule
 int g_gemm_tile = [] { const char* e = getenv("DITTO_GEMM"); return e ? atoi(e) : 0; }();
+// the tile structure the calling thread's last launch_gemm took, as the value "gemm_tile" would force (127 / 128 / 129 / 131 / 192 /
+// 256; 0 = refused before any launch): read by the unit-test entry ditto_gemm_epilogue_bf16, nothing else
+thread_local int t_gemm_structure = 0;
 
 namespace {
 
@@ -287,6 +290,7 @@ bool gemm_gated_bwd_fused_ok(int M, int F) {
 }
 
 hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
+    t_gemm_structure = 0;
     if (a.M <= 0 || a.N <= 0 || a.K <= 0) return hipErrorInvalidValue;
     if (a.fp8) {
         if (a.K % 128 || a.N % 16 || a.lda % 16 || a.ldw % 16) return hipErrorInvalidValue;
@@ -337,6 +341,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     if (epi == EPI_GATED_PRE || epi == EPI_GATED_BWD) {
         p.tiles_m = (a.M + 255) / 256;
         p.tiles_n = a.N / 256;
+        t_gemm_structure = 256;
         return launch_gemm256(p, epi, s);
     }
     // Structure choice (measured in-model on MI355X, tools/step_ab.py, one device): the persistent 256x256
@@ -346,6 +351,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     if (a.fp8) {
         p.tiles_m = (a.M + 255) / 256;
         p.tiles_n = (a.N + 255) / 256;
+        t_gemm_structure = 256;
         return launch_gemm256_fp8(p, epi, s);
     }
     if (epi == EPI_GATED_FP8) return hipErrorInvalidValue;   // fp8 output only from the fp8 GEMM
@@ -356,7 +362,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     // the ReLU epilogue is built for the 128x128 and 256x256 structures only
     if (epi == EPI_BIAS_RELU_BF16 && forced != 128 && forced != 127 && forced != 256)
         forced = (long)((a.M + 255) / 256) * ((a.N + 255) / 256) >= 4 * 256 ? 256 : 128;
-    if (forced == 131 && gemm_pp_supports(p, epi)) return launch_gemm_pp(p, epi, s);
+    if (forced == 131 && gemm_pp_supports(p, epi)) { t_gemm_structure = 131; return launch_gemm_pp(p, epi, s); }
     // Ping-pong 128x256 tiles (gemm_pp.hip) by GEMM class.  pp_mask bits: 1 narrow bf16 output (cross q-proj), 2 narrow
     // fp32 in-place residual with K <= 1024 (cross out-proj), 4 narrow fp32 output (final projection), 8 narrow residual
     // with long K (fc2), 16 QKV + RoPE, 32 gated MLP.
@@ -373,9 +379,9 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
         // cross out-proj 94.5 -> 89.7 us; q-proj 46.9 -> 52.6, final 91 -> 108, fc2 186 -> 217 (worse; in isolation,
         // with every operand resident in the Infinity Cache, the out-proj showed 96 -> 68 us: bench GEMMs in the model).
         const int mask = g_pp_mask >= 0 ? g_pp_mask : (tpp >= 512 ? 2 : 0);
-        if (cls & mask) return launch_gemm_pp(p, epi, s);
+        if (cls & mask) { t_gemm_structure = 131; return launch_gemm_pp(p, epi, s); }
     }
-    if (forced == 192 && gemm192_supports(epi)) return launch_gemm192(p, epi, s);
+    if (forced == 192 && gemm192_supports(epi)) { t_gemm_structure = 192; return launch_gemm192(p, epi, s); }
     const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
     // Wide outputs (N >= 2048: QKV, fc1|gate) take the 256x256 structure from 144 tiles on — re-measured at the end of
     // round 1 (tools/step_ab.py --batch 4 / 8 / 16, per launch): QKV 35.2 -> 31.0 us at B = 4 (144 tiles), 87.1 -> 79.1 at
@@ -390,6 +396,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     if (forced == 256 || (forced == 0 && (t256 >= 4 * 256 || wide256 || rounds256))) {
         p.tiles_m = (a.M + 255) / 256;
         p.tiles_n = (a.N + 255) / 256;
+        t_gemm_structure = 256;
         return launch_gemm256(p, epi, s);
     }
     // 256x128 ring kernel (gemm_p128.hip): N = d GEMMs, exactly 3 tiles per CU at M = 32768, N = 768.  Measured
@@ -405,11 +412,12 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     if (forced == 0 && epi != EPI_QKV_ROPE_PACKED && gemm192_supports(epi) && a.N % 192 == 0 && a.K >= 768) {
         const long t192 = (long)((a.M + 255) / 256) * (a.N / 192);
         const long r192 = (t192 + 255) / 256, r128 = (tp128 + 255) / 256;
-        if (t192 >= 256 && r192 * 3 <= r128 * 2) return launch_gemm192(p, epi, s);
+        if (t192 >= 256 && r192 * 3 <= r128 * 2) { t_gemm_structure = 192; return launch_gemm192(p, epi, s); }
     }
     if (forced == 129 || (forced == 0 && epi != EPI_QKV_ROPE_PACKED && tp128 >= 2 * 256 && a.K >= 1536)) {
         p.tiles_m = (a.M + 255) / 256;
         p.tiles_n = (a.N + 127) / 128;
+        t_gemm_structure = 129;
         return launch_gemm_p128(p, epi, s);
     }
     p.tiles_m = (a.M + BM - 1) / BM;
@@ -419,6 +427,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
     // small grid (one workgroup per CU at most): the deep-prefetch variant; forced with gemm_tile = 127
     const long wgs = (long)p.tiles_m * p.tiles_n * (p.k_splits > 1 ? p.k_splits : 1);
     if (forced == 127 || (forced == 0 && wgs <= 256 && a.K >= 4 * BK)) {
+        t_gemm_structure = 127;
         switch (epi) {
             case EPI_BIAS_BF16: return launch_deep_t<EPI_BIAS_BF16>(p, s);
             case EPI_BIAS_RES_F32: return launch_deep_t<EPI_BIAS_RES_F32>(p, s);
@@ -431,6 +440,7 @@ hipError_t launch_gemm(const GemmArgs& a, GemmEpilogue epi, hipStream_t s) {
         }
         return hipErrorInvalidValue;
     }
+    t_gemm_structure = 128;
     switch (epi) {
         case EPI_BIAS_BF16: return launch_t<EPI_BIAS_BF16>(p, s);
         case EPI_BIAS_RES_F32: return launch_t<EPI_BIAS_RES_F32>(p, s);

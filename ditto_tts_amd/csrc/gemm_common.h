@@ -287,8 +287,9 @@ DITTO_DEV void epilogue_row(const GemmParams& p, int row, int cbase, const f32x4
                 if (p.rope_freq_rev) {
                     // cos / sin of pos * inv_freq[j] right here: v_fract + v_sin + v_cos on the angle in revolutions
                     // (the table loads were 8 dependent row-indexed f32x4 loads per row block in a serial epilogue: 27 us of
-                    // the 129 us QKV GEMM, measured with the no-epilogue diagnostic).  fp32 fract at <= 4096 positions keeps
-                    // 14 fraction bits: 2e-4 rad, 20x below the bf16 rounding of q and k.
+                    // the 129 us QKV GEMM, measured with the no-epilogue diagnostic).  fp32 at <= 4096 positions: the product keeps
+                    // 14 fraction bits (half an ulp: 2e-4 rad) and the rounding of the fp32 frequency itself, times the position,
+                    // adds as much: 3.8e-4 rad at position 4095, 10x below the bf16 rounding of q and k (tests/gemm_epi_ref.py).
                     const f32x4 fr = *reinterpret_cast<const f32x4*>(p.rope_freq_rev + n * 16 + c4);
                     const float posf = (float)pos;
 #pragma unroll

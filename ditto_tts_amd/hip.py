@@ -111,6 +111,16 @@ class CallOpts(C.Structure):
         return f"CallOpts(class_rows={self.class_rows}, residual_bf16={self.residual_bf16}, fr_mask={self.fr_mask}, lnq={self.lnq})"
 
 
+class GemmEpilogueArgs(C.Structure):
+    """ditto_gemm_epilogue_args: the fields of one bf16 GEMM launch (ditto_gemm_epilogue_bf16, unit tests)."""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int), ("W", C.c_void_p), ("ldw", C.c_int), ("w_rows", C.c_int),
+                ("bias", C.c_void_p), ("residual", C.c_void_p), ("ldr", C.c_int), ("out", C.c_void_p), ("ldo", C.c_int),
+                ("out2_bf16", C.c_void_p), ("ldo2", C.c_int), ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p),
+                ("rope_rows_per_batch", C.c_int), ("rope_cols", C.c_int), ("rope_freq_rev", C.c_void_p),
+                ("rope_pos", C.c_void_p), ("pre_bf16", C.c_void_p), ("ldpre", C.c_int), ("colsum_partial", C.c_void_p),
+                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int)]
+
+
 REGROUP_BUFS = 6
 REGROUP_SEG_WORDS = 8      # ditto_regroup_seg as int32 / uint32 words: kind, source, dest, aux, src_off, dst_off, n, dup_off (16-byte units)
 REGROUP_COPY, REGROUP_DRAW = 0, 1
@@ -153,6 +163,7 @@ SYMBOLS = {
     "ditto_q_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
     "ditto_layernorm_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "ditto_gemm_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_gemm_epilogue_bf16": (_i, [C.POINTER(GemmEpilogueArgs), _i, C.POINTER(C.c_int), _vp]),
     "ditto_gemm_ln_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ditto_gemm_tn_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "ditto_attention_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),

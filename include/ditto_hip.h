@@ -290,6 +290,38 @@ int ditto_layernorm_bf16(const float* x, const float* gamma, const float* beta, 
 int ditto_gemm_bf16(const void* A, int lda, const void* W, const float* bias, const float* residual,
                     void* out, int ldo, int M, int N, int K, int epilogue, ditto_stream_t stream);
 
+/* Every bf16 GEMM epilogue with every stride (tests/test_gpu_gemm_epilogues.py): the fields of a bf16 launch as the library's own
+ * callers fill them.  epilogue (csrc/kernels.h GemmEpilogue): 0, 1, 3, 4, 6 as ditto_gemm_bf16;
+ *   2 = QKV + RoPE: out bf16 [M, ldo]; columns < rope_cols get the half-split rotation (pairs (j, j + 32) of each 64-wide head,
+ *       src/components/DiT.py:52-72) at position row % rope_rows_per_batch; angles from rope_freq_rev (fp32 [32] = inv_freq / (2 pi))
+ *       if given, else from the tables rope_cos / rope_sin (fp32 [positions, 32]; both are required either way);
+ *   9 = the same over a packed batch: the position of row r is rope_pos[r] (int32 [M]);
+ *   8 = epilogue 3 that also writes the pre-activations acc + bias to out2_bf16 [M, ldo2] (packed column order), N % 256 == 0;
+ *   7 = the gated MLP's backward on the fc2 dgrad: acc = dact [M, N]; pre_bf16 [M, ldpre] = the forward's pre-activations;
+ *       out bf16 [M, 2 N] = [da | dg] in the packed order; colsum_partial fp32 [2 * ceil(M / 256), 2 N] = the column sums of the
+ *       rounded output, one row per 128 rows.  No bias.  Only where the library itself fuses it (N % 256 == 0, N >= 2048, >= 144
+ *       tiles of 256 x 256, "gemm_tile" 0 or 256): DITTO_ERR_SHAPE otherwise.
+ *   5 (fp8 output) is ditto_gemm_fp8's: DITTO_ERR_ARG here.
+ * ldw 0 = K; w_rows 0 = N (W rows >= w_rows are not read; the output columns they would give are unspecified); rows of `out`
+ * start at multiples of 16 bytes.  Which tile structure runs is decided as for ditto_gemm_bf16 ("gemm_tile", "gemm_flags",
+ * "pp_nb"); *structure_out (may be NULL) receives the one that ran, as the value "gemm_tile" would force (127 = the 128 x 128
+ * kernel's deep-prefetch form), 0 if nothing was launched. */
+typedef struct ditto_gemm_epilogue_args {
+    const void* A; int lda;
+    const void* W; int ldw; int w_rows;
+    const float* bias;
+    const float* residual; int ldr;
+    void* out; int ldo;
+    void* out2_bf16; int ldo2;
+    const float* rope_cos; const float* rope_sin; int rope_rows_per_batch; int rope_cols;
+    const float* rope_freq_rev;
+    const int32_t* rope_pos;
+    const void* pre_bf16; int ldpre;
+    float* colsum_partial;
+    int M, N, K;
+} ditto_gemm_epilogue_args;
+int ditto_gemm_epilogue_bf16(const ditto_gemm_epilogue_args* args, int epilogue, int* structure_out, ditto_stream_t stream);
+
 /* softmax(q k^T * scale) v per (batch, head), no mask (src/components/DiT.py:131-134;
  * torch functional.py MHA math).  q/k/v/out bf16, element strides given per row; head h occupies
  * columns [h*dh, (h+1)*dh) of each row; rows of batch b start at b*Sq (q,out) / b*Skv (k,v). */

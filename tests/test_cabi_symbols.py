@@ -81,6 +81,7 @@ def test_null_arguments_are_refused_not_crashed():
     assert lib.ditto_p_sample_update(None, None, None, None, None, None, None, 1, 4, None) == hip.ERR_ARG
     with pytest.raises(hip.DittoHipError):
         hip.check(lib.ditto_gemm_bf16(None, 0, None, None, None, None, 0, 1, 1, 1, 0, None))
+    assert lib.ditto_gemm_epilogue_bf16(None, 0, None, None) == hip.ERR_ARG
 
 
 def test_config_rejects_what_the_reference_cannot_run():
