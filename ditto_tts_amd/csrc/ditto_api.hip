@@ -21,7 +21,7 @@
 #include <new>
 #include <vector>
 
-#include "model.h"
+#include "batch_layout.h"
 #include "gemm_common.h"
 
 using namespace ditto;
@@ -153,9 +153,27 @@ WsPlan plan_ws(const ditto_config& c, int B, int N, int T) {
     // split-K partials of fc2 / the final projection at small batch: sized for the most splits the option allows
     w.splitk_bytes = (long)((M + 127) / 128) * ((d + 127) / 128) <= 256 ? 8 * M * d * 4 : 0;
     w.splitk = take(w.splitk_bytes);
+    w.utt = w.pos = 0;
     const size_t tneed = text_scratch_bytes(c, B, (size_t)B * T);
     w.total = off > tneed ? off : tneed;
     return w;
+}
+
+// the workspace of a packed forward: plan_ws over the rows rounded up to whole 256-row tiles, then the two int32 row maps; the text
+// precompute's scratch (bf16 text [S_T, dt] | pooled fp32 [B, dt]) at the front
+static WsPlan plan_ws_packed(const ditto_config& c, int B, int S, int S_T) {
+    WsPlan w = plan_ws(c, 1, (S + 255) / 256 * 256, S_T);
+    size_t off = w.total;
+    w.utt = off; off += al((size_t)S * 4);
+    w.pos = off; off += al((size_t)S * 4);
+    const size_t tneed = text_scratch_bytes(c, B, (size_t)S_T);
+    w.total = off > tneed ? off : tneed;
+    return w;
+}
+
+// (a step entry sizes its workspace before the forward has validated Mt)
+WsPlan BatchLayout::plan(const ditto_config& c) const {
+    return kind == PACKED ? plan_ws_packed(c, B, M, Mt > 0 ? Mt : 1) : plan_ws(c, B, N, T);
 }
 
 int check_cfg(const ditto_config* c) {
@@ -253,38 +271,40 @@ struct ProfScope {
 
 }  // namespace
 
-// A packed batch (ditto_forward_packed_opts): utterance b owns speech rows [cu[b], cu[b+1]) of the S rows and text rows
-// [cu_t[b], cu_t[b+1]) of the S_T rows of the conditioning; `pos` is the per-row RoPE position (launch_packed_row_map).  The forward
-// then runs as ONE sequence of M = S rows (B = 1, N = S, T = S_T in run_block's terms): every launch but the attention and the two
-// per-row reads (AdaLN's utterance, the QKV epilogue's position) is row-wise.
-struct PackedRows {
-    const int32_t* cu; const int32_t* cu_t; const int32_t* utt; const int32_t* pos;
-    int B, max_N, max_T, S, S_T;
+// the workspace of one call, sliced by its plan (`h` is the caller's own buffer in ditto_block_forward); utt / pos: the row maps of a
+// packed batch (launch_packed_row_map writes them at the head of every packed forward), null otherwise
+struct Ws { float* h; void* u; char* qkv; void* act; char* xcat; float* eps; void* attn; size_t attn_bytes; float* splitk; size_t splitk_bytes; int32_t *utt, *pos; };
+static Ws slice_ws(const WsPlan& w, void* workspace) {
+    char* ws = (char*)workspace;
+    return {(float*)(ws + w.h), ws + w.u, ws + w.qkv, ws + w.act, ws + w.xcat, (float*)(ws + w.eps), ws + w.attn, w.attn_bytes,
+            (float*)(ws + w.splitk), w.splitk_bytes, w.pos ? (int32_t*)(ws + w.utt) : nullptr, w.pos ? (int32_t*)(ws + w.pos) : nullptr};
+}
+
+struct Rope { const float *cos, *sin; };   // the [N, head_dim / 2] tables of ditto_rope_tables
+struct Buf { void* p; size_t bytes; };     // a caller-owned workspace
+// what one block inherits from / hands to its neighbours in ditto_forward's chain (a lone ditto_block_forward: the defaults)
+struct BlockChain {
+    bool ln1_done = false;                                   // this block's norm1 output is already in u
+    const float *next_g1 = nullptr, *next_be1 = nullptr;     // fc2's launch also writes the NEXT block's norm1 into u
+    bool hb = false;                                         // h holds BF16 rows (the bf16 residual stream)
+    float *tap_self = nullptr, *tap_cross = nullptr;         // fp32 copies of h after the self- / cross-attention segment
+    char* xcat = nullptr;                                    // last block: fc2 also writes bf16(h_L) into xcat's second half
 };
 
-// the workspace of a packed forward: plan_ws over the rows rounded up to whole 256-row tiles, then the two int32 row maps; the text
-// precompute's scratch (bf16 text [S_T, dt] | pooled fp32 [B, dt]) at the front
-struct PackedWsPlan { WsPlan w; size_t utt, pos, total; };
-static PackedWsPlan plan_ws_packed(const ditto_config& c, int B, int S, int S_T) {
-    PackedWsPlan p;
-    p.w = plan_ws(c, 1, (S + 255) / 256 * 256, S_T);
-    size_t off = p.w.total;
-    p.utt = off; off += al((size_t)S * 4);
-    p.pos = off; off += al((size_t)S * 4);
-    const size_t tneed = text_scratch_bytes(c, B, (size_t)S_T);
-    p.total = off > tneed ? off : tneed;
-    return p;
+// an _opts entry: the call's options validated, then in force on this thread for the length of f()
+template <class F> static int with_opts(const ditto_call_opts* opts, F&& f) {
+    if (int rc = check_call_opts(opts)) return rc;
+    CallScope scope(opts);
+    return f();
 }
 
 // One DiT block (reference src/components/DiT.py:100-157) on the fp32 residual stream `h`, in place.
-static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* act, char* xcat_or_null,
-                     void* attn_ws, size_t attn_ws_bytes, float* splitk_ws, size_t splitk_bytes, const char* kv, int kv_layer, int kv_ld,
-                     const float* rope_cos, const float* rope_sin, int B, int N, int T, hipStream_t s,
-                     float* tap_self = nullptr, float* tap_cross = nullptr, bool ln1_done = false,
-                     const float* next_g1 = nullptr, const float* next_be1 = nullptr, bool hb = false,
-                     const int32_t* speech_len = nullptr, const int32_t* text_len = nullptr, const PackedRows* pk = nullptr) {
+static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv_layer, Rope rope, const BatchLayout& lay,
+                     const BlockChain& ch, hipStream_t s) {
+    float* const h = ws.h; void* const u = ws.u; char* const qkv = ws.qkv; void* const act = ws.act;
+    const bool hb = ch.hb;
     const ditto_config& c = m->cfg;
-    const int d = c.hidden_dim, H = c.num_heads, dh = d / H, M = B * N;
+    const int d = c.hidden_dim, H = c.num_heads, dh = d / H, M = lay.M, kv_ld = c.num_layers * 2 * cfg_dp(c);
     const float scale = 1.0f / sqrtf((float)dh);
     const bool fused_rope = (dh == 64);
     // padded heads (head_dim % 64 != 0): q / k / v and the attention outputs are dp = H * dhp wide, heads at a stride of dhp
@@ -295,25 +315,25 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
     const bool fp8 = (c.flags & DITTO_CFG_FP8_LINEAR) != 0;   // u / act hold fp8 bytes for the fp8 GEMMs
     const LayerPack& lp = m->layers[l];
     // full-row GEMM with the residual add and the FOLLOWING LayerNorm fused (gemm_fr.hip): bit 0 = cross out-proj + norm3,
-    // bit 1 = fc2 + the next block's norm1 (ln1_done tells that block its norm1 output is already in u)
+    // bit 1 = fc2 + the next block's norm1 (ch.ln1_done tells that block its norm1 output is already in u)
     // (the stage-major weight copies exist exactly where a kernel exists: d = 768 bf16, d = 1024 — there the out-projection
     // also in the fp8 configuration, with the LayerNorm output written as fp8)
     const bool fr_out = lp.WcoP && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
     const bool fr_fc2 = !fp8 && lp.W2P && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
     // tiles per utterance: the K-loop rotation period (gemm_fr.hip).  A varlen batch runs unrotated (here and in gemm_lnq's): the
     // rotation is a function of the PADDED N, and an utterance's bits must not depend on the padding
-    const bool varlen = speech_len || text_len || pk;   // (a packed batch is one too: its tiles straddle utterances)
-    const int fr_rot = !varlen && N % 128 == 0 ? N / 128 : 0;
+    const bool varlen = lay.varlen();
+    const int fr_rot = lay.rot_period(128);
     if (int rc = ditto::check_class_pin(M, d, fp8, !pad)) return rc;
     // hb: `h` holds BF16 rows (the bf16 residual stream; ditto_forward decides, and only where both fused launches run)
-    if (hb && (!fr_out || !fr_fc2 || dh != 64 || tap_self || tap_cross)) return fail(DITTO_ERR_ARG, "internal: bf16 stream outside its class");
+    if (hb && (!fr_out || !fr_fc2 || dh != 64 || ch.tap_self || ch.tap_cross)) return fail(DITTO_ERR_ARG, "internal: bf16 stream outside its class");
     // variable-length batches: the attention kernels bound every utterance by its own lengths (attention_varlen.hip); every other
     // launch is row-wise and computes the padding rows too (their results never reach a valid row)
     if (varlen && (dh != 64 || pad)) {
         return fail(DITTO_ERR_SHAPE, "variable-length batches need head_dim 64 (this model's is %d)", dh);
     }
         // ---- self-attention (src/components/DiT.py:103-139) ----
-        if (!ln1_done) {
+        if (!ch.ln1_done) {
             ProfScope ps(m, s, DITTO_KC_LAYERNORM);
             if (fp8) HIP_TRY(launch_layernorm_fp8(h, lp.g1, lp.be1, u, d, M, d, s));
             else if (hb) HIP_TRY(launch_layernorm_xbf16(h, lp.g1, lp.be1, u, d, M, d, s));
@@ -324,13 +344,13 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             GemmArgs g{};
             g.A = u; g.lda = d; g.W = lp.Wqkv; g.bias = lp.bqkv; g.out = qkv; g.ldo = 3 * dp;
             g.M = M; g.N = 3 * dp; g.K = d;
-            g.rope_cos = rope_cos; g.rope_sin = rope_sin; g.rope_rows_per_batch = N; g.rope_cols = 2 * d;
+            g.rope_cos = rope.cos; g.rope_sin = rope.sin; g.rope_rows_per_batch = lay.rope_rows_per_batch(); g.rope_cols = 2 * d;
             if (fused_rope && !(g_gemm_flags & 1024)) g.rope_freq_rev = m->invf_rev;   // flag 1024: A/B, table loads
             g.fp8 = fp8; g.wscale = fp8 ? lp.sqkv : nullptr;
             // packed batch: every row's position inside its utterance from the row map (the table-free angles of the same float
             // position: the padded layout's bits)
-            const GemmEpilogue qkv_epi = pk ? EPI_QKV_ROPE_PACKED : EPI_QKV_ROPE;
-            if (pk) g.rope_pos = pk->pos;
+            const GemmEpilogue qkv_epi = lay.kind == BatchLayout::PACKED ? EPI_QKV_ROPE_PACKED : EPI_QKV_ROPE;
+            g.rope_pos = ws.pos;
 #ifdef DITTO_DIAG_QKV_PLAIN   // tools/build_diag.sh: the QKV GEMM with the plain bias epilogue (NO RoPE: wrong results) — what
                               // would the 256 x 192 kernel (whole tile rounds at M = 32768; gemm_tile 192) buy this class?
             HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
@@ -353,7 +373,7 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
                 HIP_TRY(launch_gemm(gt, EPI_BIAS_BF16, s));
             } else {
             HIP_TRY(launch_gemm(g, fused_rope ? qkv_epi : EPI_BIAS_BF16, s));
-            if (!fused_rope) HIP_TRY(launch_rope_inplace(qkv, 3 * dp, rope_cos, rope_sin, M, N, 2 * dp, dh, s, 1.0f, dhp));
+            if (!fused_rope) HIP_TRY(launch_rope_inplace(qkv, 3 * dp, rope.cos, rope.sin, M, lay.rope_rows_per_batch(), 2 * dp, dh, s, 1.0f, dhp));
             }
 #endif
         }
@@ -367,10 +387,9 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             ProfScope ps(m, s, DITTO_KC_ATTN_SELF);
             AttnArgs a{};
             a.q = qkv; a.ldq = 3 * dp; a.k = qkv + (size_t)dp * 2; a.ldk = 3 * dp; a.v = qkv + (size_t)2 * dp * 2;
-            a.ldv = 3 * dp; a.B = B; a.H = H; a.Sq = N; a.Skv = N; a.dh = dhp;
-            a.scale = scale; a.workspace = attn_ws; a.workspace_bytes = attn_ws_bytes; a.q_prescaled = (dh == 64);
-            a.q_len = speech_len; a.kv_len = speech_len;
-            if (pk) { a.B = pk->B; a.Sq = a.Skv = pk->max_N; a.cu_q = a.cu_kv = pk->cu; a.q_rows = a.kv_rows = pk->S; }
+            a.ldv = 3 * dp; a.H = H; a.dh = dhp;
+            a.scale = scale; a.workspace = ws.attn; a.workspace_bytes = ws.attn_bytes; a.q_prescaled = (dh == 64);
+            lay.fill_attn(a, false);
             if (pad) {   // O at the padded stride into `act` (free here), then h[:, hd dh + c] += O[:, hd dhp + c]
                 a.out_bf16 = act; a.ldo = dp;
                 HIP_TRY(launch_attention(a, s));
@@ -380,13 +399,13 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
                 HIP_TRY(launch_attention(a, s));
             }
         }
-        if (tap_self) HIP_TRY(hipMemcpyAsync(tap_self, h, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+        if (ch.tap_self) HIP_TRY(hipMemcpyAsync(ch.tap_self, h, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
         // ---- cross-attention (src/components/DiT.py:141-148), K/V from the per-utterance cache ----
         if (lnq) {
             ProfScope ps(m, s, DITTO_KC_GEMM_QPROJ);
             const int shape = d == 768 ? opt_lnq() : 32;
             HIP_TRY(launch_gemm_lnq(h, d, hb, lp.g2, lp.be2, shape == 16 ? lp.WcqP32 : lp.WcqP, lp.bcq, qkv, d, M, d, shape,
-                                    !varlen && N % 64 == 0 ? N / 64 : 0, s));
+                                    lay.rot_period(64), s));
         } else {
             {
                 ProfScope ps(m, s, DITTO_KC_LAYERNORM);
@@ -403,12 +422,9 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             AttnArgs a{};
             a.q = qkv; a.ldq = dp; a.k = kv + (size_t)kv_layer * 2 * dp * 2; a.ldk = kv_ld;
             a.v = kv + ((size_t)kv_layer * 2 * dp + dp) * 2; a.ldv = kv_ld; a.out_bf16 = u; a.ldo = dp;
-            a.B = B; a.H = H; a.Sq = N; a.Skv = T; a.dh = dhp; a.scale = scale;
-            a.workspace = attn_ws; a.workspace_bytes = attn_ws_bytes; a.q_prescaled = (dh == 64);
-            if (speech_len || text_len) { a.q_len = speech_len; a.kv_len = text_len; }
-            if (pk) {
-                a.B = pk->B; a.Sq = pk->max_N; a.Skv = pk->max_T; a.cu_q = pk->cu; a.cu_kv = pk->cu_t; a.q_rows = pk->S; a.kv_rows = pk->S_T;
-            }
+            a.H = H; a.dh = dhp; a.scale = scale;
+            a.workspace = ws.attn; a.workspace_bytes = ws.attn_bytes; a.q_prescaled = (dh == 64);
+            lay.fill_attn(a, true);
             HIP_TRY(launch_attention(a, s));
         }
         bool ln3_done = false;
@@ -426,17 +442,17 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             g.A = u; g.lda = dp; g.W = lp.Wco; g.bias = lp.bco; g.residual = h; g.ldr = d; g.out = h; g.ldo = d;
             g.M = M; g.N = d; g.K = dp;
             const int nso = fp8 ? 1 : small_batch_k_splits_outproj(M, dp);
-            if (nso > 1 && splitk_ws && splitk_bytes >= (size_t)nso * M * d * 4) {
+            if (nso > 1 && ws.splitk && ws.splitk_bytes >= (size_t)nso * M * d * 4) {
                 // low-latency class: K-splits + a finish that adds bias + residual AND writes norm3 (into qkv: u is the A operand)
-                g.bias = nullptr; g.residual = nullptr; g.out = splitk_ws; g.k_splits = nso; g.split_stride = (size_t)M * d;
+                g.bias = nullptr; g.residual = nullptr; g.out = ws.splitk; g.k_splits = nso; g.split_stride = (size_t)M * d;
                 HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
-                HIP_TRY(launch_splitk_finish(splitk_ws, nso, (size_t)M * d, lp.bco, h, h, nullptr, 0, M, d, s, lp.g3, lp.be3, qkv, d));
+                HIP_TRY(launch_splitk_finish(ws.splitk, nso, (size_t)M * d, lp.bco, h, h, nullptr, 0, M, d, s, lp.g3, lp.be3, qkv, d));
                 ln3_done = true;
             } else {
                 HIP_TRY(launch_gemm(g, EPI_BIAS_RES_F32, s));
             }
         }
-        if (tap_cross) HIP_TRY(hipMemcpyAsync(tap_cross, h, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+        if (ch.tap_cross) HIP_TRY(hipMemcpyAsync(ch.tap_cross, h, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
         // ---- gated MLP (src/components/DiT.py:150-155) ----
         const void* u3 = (fr_out || ln3_done) ? (const void*)qkv : (const void*)u;   // where norm3's output is
         if (!fr_out && !ln3_done) {
@@ -457,25 +473,25 @@ static int run_block(ditto_model* m, int l, float* h, void* u, char* qkv, void* 
             GemmParams gp{};
             gp.A = (const bf16*)act; gp.lda = 4 * d; gp.W = (const bf16*)lp.W2P; gp.ldw = 4 * d; gp.w_rows = d; gp.bias = lp.b2;
             gp.residual = h; gp.ldr = d; gp.out = h; gp.ldo = d; gp.M = M; gp.N = d; gp.K = 4 * d;
-            if (xcat_or_null && hb) { gp.out = xcat_or_null + (size_t)d * 2; gp.ldo = 2 * d; }   // bf16 h_L IS proj_out's operand
-            else if (xcat_or_null) { gp.out2 = (bf16*)(xcat_or_null + (size_t)d * 2); gp.ldo2 = 2 * d; }
-            HIP_TRY(launch_gemm_fr(gp, next_g1, next_be1, next_g1 ? u : nullptr, d, fr_rot, s, false, hb));
+            if (ch.xcat && hb) { gp.out = ch.xcat + (size_t)d * 2; gp.ldo = 2 * d; }   // bf16 h_L IS proj_out's operand
+            else if (ch.xcat) { gp.out2 = (bf16*)(ch.xcat + (size_t)d * 2); gp.ldo2 = 2 * d; }
+            HIP_TRY(launch_gemm_fr(gp, ch.next_g1, ch.next_be1, ch.next_g1 ? u : nullptr, d, fr_rot, s, false, hb));
         } else {
             ProfScope ps(m, s, DITTO_KC_GEMM_FC2);
             GemmArgs g{};
             g.A = act; g.lda = 4 * d; g.W = lp.W2; g.bias = lp.b2; g.residual = h; g.ldr = d; g.out = h; g.ldo = d;
             g.M = M; g.N = d; g.K = 4 * d; g.fp8 = fp8; g.wscale = fp8 ? lp.s2 : nullptr;
-            void* out2 = xcat_or_null ? xcat_or_null + (size_t)d * 2 : nullptr;   // bf16(h_L) for proj_out
+            void* out2 = ch.xcat ? ch.xcat + (size_t)d * 2 : nullptr;   // bf16(h_L) for proj_out
             const int ns = fp8 ? 1 : small_batch_k_splits(M, d, 4 * d);
-            if (ns > 1 && splitk_ws && splitk_bytes >= (size_t)ns * M * d * 4) {
-                g.bias = nullptr; g.residual = nullptr; g.out = splitk_ws; g.k_splits = ns;
+            if (ns > 1 && ws.splitk && ws.splitk_bytes >= (size_t)ns * M * d * 4) {
+                g.bias = nullptr; g.residual = nullptr; g.out = ws.splitk; g.k_splits = ns;
                 g.split_stride = (size_t)M * d;
                 HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
-                // (next_g1 set: the finish also writes the NEXT block's norm1 into u — ditto_forward decided it, chain_ll)
-                HIP_TRY(launch_splitk_finish(splitk_ws, ns, (size_t)M * d, lp.b2, h, h, out2, 2 * d, M, d, s, next_g1, next_be1,
-                                             next_g1 ? u : nullptr, d));
+                // (ch.next_g1 set: the finish also writes the NEXT block's norm1 into u — ditto_forward decided it, chain_ll)
+                HIP_TRY(launch_splitk_finish(ws.splitk, ns, (size_t)M * d, lp.b2, h, h, out2, 2 * d, M, d, s, ch.next_g1, ch.next_be1,
+                                             ch.next_g1 ? u : nullptr, d));
             } else {
-                if (next_g1) return fail(DITTO_ERR_ARG, "internal: norm1 chaining without a kernel that writes it");
+                if (ch.next_g1) return fail(DITTO_ERR_ARG, "internal: norm1 chaining without a kernel that writes it");
                 if (out2) { g.out2_bf16 = out2; g.ldo2 = 2 * d; }
                 HIP_TRY(launch_gemm(g, EPI_BIAS_RES_F32, s));
             }
@@ -755,126 +771,6 @@ int ditto_call_opts_current(ditto_call_opts* out) {
     return DITTO_OK;
 }
 
-int ditto_forward_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
-                       const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
-                       size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return ditto_forward(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream);
-}
-
-static int forward_impl(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
-                        const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
-                        size_t workspace_bytes, ditto_stream_t stream, const int32_t* speech_len, const int32_t* text_len,
-                        const PackedRows* pk = nullptr) {
-    if (!m || !x || !cond || !t || !rope_cos || !rope_sin || !eps_out || !workspace || B <= 0 || N <= 0 || T <= 0)
-        return fail(DITTO_ERR_ARG, "bad argument to ditto_forward");
-    const ditto_config& c = m->cfg;
-    if (m->blocks_only) return fail(DITTO_ERR_ARG, "ditto_forward on a blocks-only handle");
-    // (packed: B = 1, N = S, T = S_T — ditto_forward_packed_opts checked the workspace against plan_ws_packed)
-    const WsPlan w = pk ? plan_ws_packed(c, pk->B, pk->S, pk->S_T).w : plan_ws(c, B, N, T);
-    if (workspace_bytes < w.total)
-        return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
-    if ((uintptr_t)workspace % 256) return fail(DITTO_ERR_ARG, "workspace must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const int d = c.hidden_dim, L = c.num_layers, M = B * N;
-    char* ws = (char*)workspace;
-    float* h = (float*)(ws + w.h);
-    void* u = ws + w.u;
-    char* qkv = ws + w.qkv;
-    void* act = ws + w.act;
-    char* xcat = ws + w.xcat;
-    void* attn_ws = ws + w.attn;
-    const char* kv = (const char*)cond;
-    const float* tmod = (const float*)(kv + al((size_t)B * T * L * 2 * cfg_dp(c) * 2));
-
-    // fc2 on the full-row kernel also emits the NEXT block's norm1 (fr_mask bit 1): that block then skips its LayerNorm
-    const bool fp8c = (c.flags & DITTO_CFG_FP8_LINEAR) != 0;
-    const bool chain_ln1 = (opt_fr_mask() & 2) && !fp8c && m->layers[0].W2P && fr_fc2_ok(M, d);
-    // bf16 residual stream ("residual_bf16"): only where EVERY consumer of h has the bf16 form — d = 768, head_dim 64, both fused
-    // launches of a block on gemm_frd.hip (the full-row class); any other launch keeps the fp32 stream
-    const bool hb_class = opt_resid_bf16() && !fp8c && d == 768 && d / c.num_heads == 64 && chain_ln1 && (opt_fr_mask() & 1) &&
-                          m->layers[0].WcoP && fr_outproj_ok(M, d) &&
-                          (g_fr_tile == 130 || (g_fr_tile == 0 && fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M) == 130));
-    // (only gemm_frd.hip has the bf16 form: a launch of fewer than 128 rows under a PINNED class would run the 64-row kernel)
-    if (hb_class && M < 128)
-        return fail(DITTO_ERR_SHAPE, "kernel class pinned to a batch of %d rows (bf16 residual stream on the 128-row full-row kernel), "
-                                     "but this launch has %d rows: it cannot take that class.  Give every shard at least 128 rows, or "
-                                     "ditto_set_option(\"residual_bf16\", 0).", opt_class_rows(), M);
-    const bool hb = hb_class;
-    // low-latency class: fc2 runs split over K and its finish launch also writes the next block's norm1 (the same bits as the
-    // LayerNorm launch it replaces); decided exactly as run_block will decide the split
-    const int ns_fc2 = fp8c ? 1 : small_batch_k_splits(M, d, 4 * d);
-    const bool chain_ll = !chain_ln1 && (g_ll_mask & 1) && ns_fc2 > 1 && w.splitk_bytes >= (size_t)ns_fc2 * M * d * 4;
-    // block 0's norm1 rides in the GlobalAdaLN kernel (same statistics order as the LayerNorm kernel: the same bits)
-    const bool ln1_in_adaln = !fp8c && !(g_gemm_flags & 32768);      // gemm_flags bit 15: A/B, the separate launch
-    {   // GlobalAdaLN (src/components/DiT.py:25-40) + bf16 copy of the raw input for proj_in
-        ProfScope ps(m, s, DITTO_KC_ADALN);
-        if (pk) {   // the row maps first (utterance and RoPE position of every packed row), then the entry with the utterance map
-            HIP_TRY(launch_packed_row_map(pk->cu, pk->B, pk->S, pk->max_N, (int32_t*)pk->utt, (int32_t*)pk->pos, s));
-            HIP_TRY(launch_adaln_packed(x, m->ttab, tmod, t, c.diffusion_steps, pk->utt, h, xcat, 2 * d, M, d, s, hb,
-                                        ln1_in_adaln ? m->layers[0].g1 : nullptr, ln1_in_adaln ? m->layers[0].be1 : nullptr,
-                                        ln1_in_adaln ? u : nullptr));
-        } else {
-        HIP_TRY(launch_adaln(x, m->ttab, tmod, t, c.diffusion_steps, h, xcat, 2 * d, B, N, d, s, hb,
-                             ln1_in_adaln ? m->layers[0].g1 : nullptr, ln1_in_adaln ? m->layers[0].be1 : nullptr,
-                             ln1_in_adaln ? u : nullptr));
-        }
-    }
-    for (int l = 0; l < L; ++l)
-        if (int rc = run_block(m, l, h, u, qkv, act, l == L - 1 ? xcat : nullptr, attn_ws, w.attn_bytes,
-                               (float*)(ws + w.splitk), w.splitk_bytes, kv, l,
-                               L * 2 * cfg_dp(c), rope_cos, rope_sin, B, N, T, s, nullptr, nullptr,
-                               ((chain_ln1 || chain_ll) && l > 0) || (ln1_in_adaln && l == 0),
-                               (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].g1 : nullptr,
-                               (chain_ln1 || chain_ll) && l + 1 < L ? m->layers[l + 1].be1 : nullptr, hb, speech_len, text_len, pk))
-            return rc;
-    {   // eps = proj_in(x_raw) + proj_out(h_L)  (src/model/DiTTO.py:83,93-94), one K = 2d GEMM
-        ProfScope ps(m, s, DITTO_KC_GEMM_FINAL);
-        GemmArgs g{};
-        g.A = xcat; g.lda = 2 * d; g.W = m->Wfin; g.bias = m->bfin; g.out = eps_out; g.ldo = d; g.M = M; g.N = d;
-        g.K = 2 * d;
-        const int ns = small_batch_k_splits(M, d, 2 * d);
-        if (ns > 1 && w.splitk_bytes >= (size_t)ns * M * d * 4) {
-            float* part = (float*)(ws + w.splitk);
-            g.bias = nullptr; g.out = part; g.k_splits = ns; g.split_stride = (size_t)M * d;
-            HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
-            HIP_TRY(launch_splitk_finish(part, ns, (size_t)M * d, m->bfin, nullptr, eps_out, nullptr, 0, M, d, s));
-        } else {
-            HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
-        }
-    }
-    if (speech_len) HIP_TRY(launch_zero_rows_past_len(eps_out, speech_len, B, N, d, s));   // eps rows >= N_b are exactly 0
-    return DITTO_OK;
-}
-
-int ditto_forward(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
-                  const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
-                  size_t workspace_bytes, ditto_stream_t stream) {
-    return forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream, nullptr, nullptr);
-}
-
-int ditto_forward_varlen_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* speech_len,
-                              const int32_t* text_len, int B, int N, int T, const float* rope_cos, const float* rope_sin,
-                              float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
-                              const ditto_call_opts* opts) {
-    if (!speech_len || !text_len) return fail(DITTO_ERR_ARG, "ditto_forward_varlen_opts: null speech_len / text_len");
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream, speech_len, text_len);
-}
-
-// ---- packed batches: utterances concatenated along the rows, described by device int32 offsets [B + 1] ----
-size_t ditto_packed_workspace_bytes(const ditto_config* cfg, int B, int S, int S_T) {
-    if (check_cfg(cfg) != DITTO_OK || B <= 0 || S <= 0 || S_T <= 0) return 0;
-    return plan_ws_packed(*cfg, B, S, S_T).total;
-}
-size_t ditto_packed_cond_bytes(const ditto_config* cfg, int B, int S_T) {
-    if (check_cfg(cfg) != DITTO_OK || B <= 0 || S_T <= 0) return 0;
-    const size_t d = cfg->hidden_dim, dp = cfg_dp(*cfg);
-    return al((size_t)S_T * cfg->num_layers * 2 * dp * 2) + al((size_t)B * 2 * d * 4);
-}
-
 // what every packed entry checks on the host (the offsets themselves live on the device: documented, clamped by the kernels)
 static int check_packed(const char* who, int B, int S, int max_N, int S_T, int max_T) {
     if (B <= 0 || S <= 0 || max_N <= 0 || S_T <= 0 || max_T <= 0)
@@ -894,6 +790,121 @@ static int check_packed_model(const char* who, ditto_model_t m) {
     return DITTO_OK;
 }
 
+// One DiTTO.forward over a batch in any layout: eps_out fp32 [lay.M, d].  `who` names the entry in the argument errors.
+static int forward_impl(const char* who, ditto_model_t m, const float* x, const void* cond, const int64_t* t, Rope rope, float* eps_out,
+                        Buf wsb, ditto_stream_t stream, const BatchLayout& lay) {
+    const bool packed = lay.kind == BatchLayout::PACKED;
+    if (!m || !x || !cond || !t || !rope.cos || !rope.sin || !eps_out || !wsb.p ||
+        (packed ? !lay.cu || !lay.cu_t : lay.B <= 0 || lay.N <= 0 || lay.T <= 0))
+        return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    const ditto_config& c = m->cfg;
+    if (packed) {
+        if (int rc = check_packed_model(who, m)) return rc;
+        if (int rc = check_packed(who, lay.B, lay.M, lay.N, lay.Mt, lay.T)) return rc;
+    } else if (m->blocks_only) {
+        return fail(DITTO_ERR_ARG, "%s on a blocks-only handle", who);
+    }
+    const WsPlan w = lay.plan(c);
+    if (wsb.bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", wsb.bytes, w.total);
+    if ((uintptr_t)wsb.p % 256) return fail(DITTO_ERR_ARG, "workspace must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int d = c.hidden_dim, L = c.num_layers, M = lay.M;
+    const Ws ws = slice_ws(w, wsb.p);
+    const char* kv = (const char*)cond;
+    const float* tmod = (const float*)(kv + lay.tmod_offset(c));
+    // fc2 on the full-row kernel also emits the NEXT block's norm1 (fr_mask bit 1): that block then skips its LayerNorm
+    const bool fp8c = (c.flags & DITTO_CFG_FP8_LINEAR) != 0;
+    const bool chain_ln1 = (opt_fr_mask() & 2) && !fp8c && m->layers[0].W2P && fr_fc2_ok(M, d);
+    // bf16 residual stream ("residual_bf16"): only where EVERY consumer of h has the bf16 form — d = 768, head_dim 64, both fused
+    // launches of a block on gemm_frd.hip (the full-row class); any other launch keeps the fp32 stream
+    const bool hb_class = opt_resid_bf16() && !fp8c && d == 768 && d / c.num_heads == 64 && chain_ln1 && (opt_fr_mask() & 1) &&
+                          m->layers[0].WcoP && fr_outproj_ok(M, d) &&
+                          (g_fr_tile == 130 || (g_fr_tile == 0 && fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M) == 130));
+    // (only gemm_frd.hip has the bf16 form: a launch of fewer than 128 rows under a PINNED class would run the 64-row kernel)
+    if (hb_class && M < 128)
+        return fail(DITTO_ERR_SHAPE, "kernel class pinned to a batch of %d rows (bf16 residual stream on the 128-row full-row kernel), "
+                                     "but this launch has %d rows: it cannot take that class.  Give every shard at least 128 rows, or "
+                                     "ditto_set_option(\"residual_bf16\", 0).", opt_class_rows(), M);
+    const bool hb = hb_class;
+    // low-latency class: fc2 runs split over K and its finish launch also writes the next block's norm1 (the same bits as the
+    // LayerNorm launch it replaces); decided exactly as run_block will decide the split
+    const int ns_fc2 = fp8c ? 1 : small_batch_k_splits(M, d, 4 * d);
+    const bool chain_ll = !chain_ln1 && (g_ll_mask & 1) && ns_fc2 > 1 && ws.splitk_bytes >= (size_t)ns_fc2 * M * d * 4;
+    // block 0's norm1 rides in the GlobalAdaLN kernel (same statistics order as the LayerNorm kernel: the same bits)
+    const bool ln1_in_adaln = !fp8c && !(g_gemm_flags & 32768);      // gemm_flags bit 15: A/B, the separate launch
+    {   // GlobalAdaLN (src/components/DiT.py:25-40) + bf16 copy of the raw input for proj_in
+        ProfScope ps(m, s, DITTO_KC_ADALN);
+        const float *g1 = ln1_in_adaln ? m->layers[0].g1 : nullptr, *be1 = ln1_in_adaln ? m->layers[0].be1 : nullptr;
+        void* u1 = ln1_in_adaln ? ws.u : nullptr;
+        if (packed) {   // the row maps first (utterance and RoPE position of every packed row), then the entry with the utterance map
+            HIP_TRY(launch_packed_row_map(lay.cu, lay.B, M, lay.N, ws.utt, ws.pos, s));
+            HIP_TRY(launch_adaln_packed(x, m->ttab, tmod, t, c.diffusion_steps, ws.utt, ws.h, ws.xcat, 2 * d, M, d, s, hb, g1, be1, u1));
+        } else {
+            HIP_TRY(launch_adaln(x, m->ttab, tmod, t, c.diffusion_steps, ws.h, ws.xcat, 2 * d, lay.B, lay.N, d, s, hb, g1, be1, u1));
+        }
+    }
+    const bool chain = chain_ln1 || chain_ll;
+    for (int l = 0; l < L; ++l) {
+        BlockChain ch;
+        ch.ln1_done = l > 0 ? chain : ln1_in_adaln;
+        if (chain && l + 1 < L) { ch.next_g1 = m->layers[l + 1].g1; ch.next_be1 = m->layers[l + 1].be1; }
+        ch.hb = hb; ch.xcat = l == L - 1 ? ws.xcat : nullptr;
+        if (int rc = run_block(m, l, ws, kv, l, rope, lay, ch, s)) return rc;
+    }
+    {   // eps = proj_in(x_raw) + proj_out(h_L)  (src/model/DiTTO.py:83,93-94), one K = 2d GEMM
+        ProfScope ps(m, s, DITTO_KC_GEMM_FINAL);
+        GemmArgs g{};
+        g.A = ws.xcat; g.lda = 2 * d; g.W = m->Wfin; g.bias = m->bfin; g.out = eps_out; g.ldo = d; g.M = M; g.N = d;
+        g.K = 2 * d;
+        const int ns = small_batch_k_splits(M, d, 2 * d);
+        if (ns > 1 && ws.splitk_bytes >= (size_t)ns * M * d * 4) {
+            float* part = ws.splitk;
+            g.bias = nullptr; g.out = part; g.k_splits = ns; g.split_stride = (size_t)M * d;
+            HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
+            HIP_TRY(launch_splitk_finish(part, ns, (size_t)M * d, m->bfin, nullptr, eps_out, nullptr, 0, M, d, s));
+        } else {
+            HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
+        }
+    }
+    if (lay.speech_len) HIP_TRY(launch_zero_rows_past_len(eps_out, lay.speech_len, lay.B, lay.N, d, s));   // eps rows >= N_b are exactly 0
+    return DITTO_OK;
+}
+
+int ditto_forward(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
+                  const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
+                  size_t workspace_bytes, ditto_stream_t stream) {
+    return forward_impl("ditto_forward", m, x, cond, t, {rope_cos, rope_sin}, eps_out, {workspace, workspace_bytes}, stream,
+                        BatchLayout::dense(B, N, T));
+}
+
+int ditto_forward_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, int B, int N, int T,
+                       const float* rope_cos, const float* rope_sin, float* eps_out, void* workspace,
+                       size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    return with_opts(opts, [&] { return ditto_forward(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream); });
+}
+
+int ditto_forward_varlen_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* speech_len,
+                              const int32_t* text_len, int B, int N, int T, const float* rope_cos, const float* rope_sin,
+                              float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                              const ditto_call_opts* opts) {
+    if (!speech_len || !text_len) return fail(DITTO_ERR_ARG, "ditto_forward_varlen_opts: null speech_len / text_len");
+    return with_opts(opts, [&] {
+        return forward_impl("ditto_forward", m, x, cond, t, {rope_cos, rope_sin}, eps_out, {workspace, workspace_bytes}, stream,
+                            BatchLayout::padded(B, N, T, speech_len, text_len));
+    });
+}
+
+// ---- packed batches: utterances concatenated along the rows, described by device int32 offsets [B + 1] ----
+size_t ditto_packed_workspace_bytes(const ditto_config* cfg, int B, int S, int S_T) {
+    if (check_cfg(cfg) != DITTO_OK || B <= 0 || S <= 0 || S_T <= 0) return 0;
+    return plan_ws_packed(*cfg, B, S, S_T).total;
+}
+size_t ditto_packed_cond_bytes(const ditto_config* cfg, int B, int S_T) {
+    if (check_cfg(cfg) != DITTO_OK || B <= 0 || S_T <= 0) return 0;
+    const size_t d = cfg->hidden_dim, dp = cfg_dp(*cfg);
+    return al((size_t)S_T * cfg->num_layers * 2 * dp * 2) + al((size_t)B * 2 * d * 4);
+}
+
 int ditto_text_precompute_packed(ditto_model_t m, const float* text, const int32_t* cu_text, int B, int S_T, int max_T, void* cond,
                                  size_t cond_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
     if (!m || !text || !cu_text || !cond || !workspace) return fail(DITTO_ERR_ARG, "bad argument to ditto_text_precompute_packed");
@@ -903,28 +914,14 @@ int ditto_text_precompute_packed(ditto_model_t m, const float* text, const int32
                            workspace, workspace_bytes, stream);
 }
 
-static int forward_packed(const char* who, ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* cu_speech,
-                          const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T, const float* rope_cos,
-                          const float* rope_sin, float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
-    if (!m || !x || !cond || !t || !cu_speech || !cu_text || !rope_cos || !rope_sin || !eps_out || !workspace)
-        return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (int rc = check_packed_model(who, m)) return rc;
-    if (int rc = check_packed(who, B, S, max_N, S_T, max_T)) return rc;
-    const PackedWsPlan pw = plan_ws_packed(m->cfg, B, S, S_T);
-    if (workspace_bytes < pw.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, pw.total);
-    char* ws = (char*)workspace;
-    const PackedRows pk{cu_speech, cu_text, (const int32_t*)(ws + pw.utt), (const int32_t*)(ws + pw.pos), B, max_N, max_T, S, S_T};
-    return forward_impl(m, x, cond, t, 1, S, S_T, rope_cos, rope_sin, eps_out, workspace, workspace_bytes, stream, nullptr, nullptr, &pk);
-}
-
 int ditto_forward_packed_opts(ditto_model_t m, const float* x, const void* cond, const int64_t* t, const int32_t* cu_speech,
                               const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T, const float* rope_cos,
                               const float* rope_sin, float* eps_out, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
                               const ditto_call_opts* opts) {
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return forward_packed("ditto_forward_packed_opts", m, x, cond, t, cu_speech, cu_text, B, S, max_N, S_T, max_T, rope_cos, rope_sin,
-                          eps_out, workspace, workspace_bytes, stream);
+    return with_opts(opts, [&] {
+        return forward_impl("ditto_forward_packed_opts", m, x, cond, t, {rope_cos, rope_sin}, eps_out, {workspace, workspace_bytes}, stream,
+                            BatchLayout::packed(B, S, max_N, S_T, max_T, cu_speech, cu_text));
+    });
 }
 
 int ditto_block_forward(ditto_model_t m, int layer, float* h, const void* cond, int cond_layer, int B, int N, int T,
@@ -944,12 +941,10 @@ int ditto_block_forward_taps(ditto_model_t m, int layer, float* h, const void* c
         return fail(DITTO_ERR_ARG, "layer index out of range");
     const WsPlan w = plan_ws(c, B, N, T);
     if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
-    char* ws = (char*)workspace;
-    return run_block(m, layer, h, ws + w.u, ws + w.qkv, ws + w.act, nullptr, ws + w.attn, w.attn_bytes,
-                     (float*)(ws + w.splitk), w.splitk_bytes, (const char*)cond, cond_layer, c.num_layers * 2 * cfg_dp(c), rope_cos, rope_sin, B, N, T,
-                     (hipStream_t)stream, tap_self, tap_cross);
+    Ws ws = slice_ws(w, workspace); ws.h = h;
+    BlockChain ch; ch.tap_self = tap_self; ch.tap_cross = tap_cross;
+    return run_block(m, layer, ws, (const char*)cond, cond_layer, {rope_cos, rope_sin}, BatchLayout::dense(B, N, T), ch, (hipStream_t)stream);
 }
-
 
 size_t ditto_global_adaln_scratch_bytes(int B, int d, int time_dim, int text_dim) {
     return al((size_t)B * time_dim * 4) + al((size_t)B * text_dim * 4) + 2 * al((size_t)B * 2 * d * 4);
@@ -998,24 +993,31 @@ int ditto_p_sample_update(float* x, const float* eps, const float* noise, const 
     return DITTO_OK;
 }
 
-// one reverse-diffusion step after the entry's own checks: the forward into the workspace's eps slot, then the update with z from
-// `noise` or, with seeds, from Philox of (seed, step); varlen (speech_len given): rows past each length of x then become 0.  The
-// noise of element i of an utterance is a function of (seed, step, i): in the padded layout i is the same row-major index as at the
-// utterance's own length, so a varlen trajectory is comparable to the solo one.
+// what every step entry does after its own checks: the workspace against the layout's plan, then the forward into the plan's eps
+// slot (returned in *eps); the entry's own update launch follows
+static int step_forward(const char* who, ditto_model_t m, const float* x, const void* cond, const int64_t* t, Rope rope, Buf wsb,
+                        ditto_stream_t stream, const BatchLayout& lay, float** eps) {
+    const WsPlan w = lay.plan(m->cfg);
+    if (wsb.bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", wsb.bytes, w.total);
+    *eps = (float*)((char*)wsb.p + w.eps);
+    return forward_impl(who, m, x, cond, t, rope, *eps, wsb, stream, lay);
+}
+
+// one reverse-diffusion step after the entry's own checks: the forward, then the update with z from `noise` or, with seeds, from
+// Philox of (seed, step); varlen (lay.speech_len given): rows past each length of x then become 0.  The noise of element i of an
+// utterance is a function of (seed, step, i): in the padded layout i is the same row-major index as at the utterance's own length, so
+// a varlen trajectory is comparable to the solo one.
 static int p_sample_step(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise, const int64_t* seeds,
-                         uint32_t step, const int32_t* speech_len, const int32_t* text_len, const float* betas, const float* alphas,
-                         const float* alphas_cumprod, int B, int N, int T, const float* rope_cos, const float* rope_sin, void* workspace,
-                         size_t workspace_bytes, ditto_stream_t stream) {
-    const WsPlan w = plan_ws(m->cfg, B, N, T);
-    if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
-    float* eps = (float*)((char*)workspace + w.eps);
-    if (int rc = forward_impl(m, x, cond, t, B, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
-        return rc;
+                         uint32_t step, const float* betas, const float* alphas, const float* alphas_cumprod, Rope rope, Buf wsb,
+                         ditto_stream_t stream, const BatchLayout& lay) {
+    float* eps;
+    if (int rc = step_forward("ditto_forward", m, x, cond, t, rope, wsb, stream, lay, &eps)) return rc;
     ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+    const int B = lay.B, N = lay.N;
     const size_t per = (size_t)N * m->cfg.hidden_dim;   // a multiple of 64 (check_cfg): what the update kernels' float4 rows need
     if (seeds) HIP_TRY(launch_p_sample_update_seeded(x, eps, seeds, step, t, betas, alphas, alphas_cumprod, B, per, (hipStream_t)stream));
     else if (int rc = ditto_p_sample_update(x, eps, noise, t, betas, alphas, alphas_cumprod, B, per, stream)) return rc;
-    if (speech_len) HIP_TRY(launch_zero_rows_past_len(x, speech_len, B, N, m->cfg.hidden_dim, (hipStream_t)stream));
+    if (lay.speech_len) HIP_TRY(launch_zero_rows_past_len(x, lay.speech_len, B, N, m->cfg.hidden_dim, (hipStream_t)stream));
     return DITTO_OK;
 }
 
@@ -1024,18 +1026,16 @@ int ditto_p_sample(ditto_model_t m, float* x, const void* cond, const int64_t* t
                    const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                    ditto_stream_t stream) {
     if (!m || !workspace) return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample");
-    return p_sample_step(m, x, cond, t, noise, nullptr, 0, nullptr, nullptr, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin,
-                         workspace, workspace_bytes, stream);
+    return p_sample_step(m, x, cond, t, noise, nullptr, 0, betas, alphas, alphas_cumprod, {rope_cos, rope_sin}, {workspace, workspace_bytes},
+                         stream, BatchLayout::dense(B, N, T));
 }
 
 int ditto_p_sample_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise,
                         const float* betas, const float* alphas, const float* alphas_cumprod, int B, int N, int T,
                         const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                         ditto_stream_t stream, const ditto_call_opts* opts) {
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return ditto_p_sample(m, x, cond, t, noise, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin, workspace,
-                          workspace_bytes, stream);
+    return with_opts(opts, [&] { return ditto_p_sample(m, x, cond, t, noise, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin, workspace,
+                                                       workspace_bytes, stream); });
 }
 
 int ditto_noise_normal(float* out, const int64_t* seeds, uint32_t step, int B, size_t elems_per_utt,
@@ -1052,8 +1052,8 @@ int ditto_p_sample_seeded(ditto_model_t m, float* x, const void* cond, const int
                           size_t workspace_bytes, ditto_stream_t stream) {
     if (!m || !workspace || !seeds || !betas || !alphas || !alphas_cumprod)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample_seeded");
-    return p_sample_step(m, x, cond, t, nullptr, seeds, step, nullptr, nullptr, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin,
-                         workspace, workspace_bytes, stream);
+    return p_sample_step(m, x, cond, t, nullptr, seeds, step, betas, alphas, alphas_cumprod, {rope_cos, rope_sin}, {workspace, workspace_bytes},
+                         stream, BatchLayout::dense(B, N, T));
 }
 
 int ditto_p_sample_seeded_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const int64_t* seeds,
@@ -1064,10 +1064,10 @@ int ditto_p_sample_seeded_varlen_opts(ditto_model_t m, float* x, const void* con
     if (!m || !workspace || !seeds || !betas || !alphas || !alphas_cumprod || !speech_len || !text_len)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample_seeded_varlen_opts");
     if (B <= 0 || N <= 0 || T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_p_sample_seeded_varlen_opts: B, N and T must be positive");
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return p_sample_step(m, x, cond, t, nullptr, seeds, step, speech_len, text_len, betas, alphas, alphas_cumprod, B, N, T, rope_cos,
-                         rope_sin, workspace, workspace_bytes, stream);
+    return with_opts(opts, [&] {
+        return p_sample_step(m, x, cond, t, nullptr, seeds, step, betas, alphas, alphas_cumprod, {rope_cos, rope_sin},
+                             {workspace, workspace_bytes}, stream, BatchLayout::padded(B, N, T, speech_len, text_len));
+    });
 }
 
 int ditto_p_sample_varlen_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const float* noise,
@@ -1077,30 +1077,26 @@ int ditto_p_sample_varlen_opts(ditto_model_t m, float* x, const void* cond, cons
     if (!m || !workspace || !betas || !alphas || !alphas_cumprod || !speech_len || !text_len)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_p_sample_varlen_opts");
     if (B <= 0 || N <= 0 || T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_p_sample_varlen_opts: B, N and T must be positive");
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return p_sample_step(m, x, cond, t, noise, nullptr, 0, speech_len, text_len, betas, alphas, alphas_cumprod, B, N, T, rope_cos,
-                         rope_sin, workspace, workspace_bytes, stream);
+    return with_opts(opts, [&] {
+        return p_sample_step(m, x, cond, t, noise, nullptr, 0, betas, alphas, alphas_cumprod, {rope_cos, rope_sin},
+                             {workspace, workspace_bytes}, stream, BatchLayout::padded(B, N, T, speech_len, text_len));
+    });
 }
 
 int ditto_p_sample_seeded_opts(ditto_model_t m, float* x, const void* cond, const int64_t* t, const int64_t* seeds,
                                uint32_t step, const float* betas, const float* alphas, const float* alphas_cumprod, int B,
                                int N, int T, const float* rope_cos, const float* rope_sin, void* workspace,
                                size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return ditto_p_sample_seeded(m, x, cond, t, seeds, step, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin, workspace,
-                                 workspace_bytes, stream);
+    return with_opts(opts, [&] { return ditto_p_sample_seeded(m, x, cond, t, seeds, step, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin,
+                                                              workspace, workspace_bytes, stream); });
 }
 
 int ditto_denoise_steps_opts(ditto_model_t m, float* x, const void* cond, int t_begin, int t_end, const float* noise,
                              const float* betas, const float* alphas, const float* alphas_cumprod, int B, int N, int T,
                              const float* rope_cos, const float* rope_sin, int64_t* t_scratch, void* workspace,
                              size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    return ditto_denoise_steps(m, x, cond, t_begin, t_end, noise, betas, alphas, alphas_cumprod, B, N, T, rope_cos, rope_sin,
-                               t_scratch, workspace, workspace_bytes, stream);
+    return with_opts(opts, [&] { return ditto_denoise_steps(m, x, cond, t_begin, t_end, noise, betas, alphas, alphas_cumprod, B, N, T, rope_cos,
+                                                            rope_sin, t_scratch, workspace, workspace_bytes, stream); });
 }
 
 int ditto_denoise_steps(ditto_model_t m, float* x, const void* cond, int t_begin, int t_end, const float* noise,
@@ -1461,18 +1457,17 @@ int ditto_guided_step_opts(ditto_model_t m, float* x2, const void* cond, const i
     if (T <= 0) return fail(DITTO_ERR_SHAPE, "ditto_guided_step_opts: T must be positive");
     if (int rc = check_guided_update("ditto_guided_step_opts", x2, x2, noise, seeds, w, a, ce, cz, B, N, m->cfg.hidden_dim, cfg))
         return rc;
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    const int nb = cfg ? 2 * B : B;                 // the forward runs over [x; x] x [text; null] under guidance
-    const WsPlan w_ = plan_ws(m->cfg, nb, N, T);
-    if (workspace_bytes < w_.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w_.total);
-    float* eps = (float*)((char*)workspace + w_.eps);
-    if (int rc = forward_impl(m, x2, cond, t, nb, N, T, rope_cos, rope_sin, eps, workspace, workspace_bytes, stream, speech_len, text_len))
-        return rc;
-    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-    HIP_TRY(launch_guided_update(x2, eps, noise, seeds, step, w, a, ce, cz, speech_len, B, N, m->cfg.hidden_dim, cfg != 0,
-                                 (hipStream_t)stream));
-    return DITTO_OK;
+    return with_opts(opts, [&]() -> int {
+        const int nb = cfg ? 2 * B : B;                 // the forward runs over [x; x] x [text; null] under guidance
+        float* eps;
+        if (int rc = step_forward("ditto_forward", m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
+                                  BatchLayout::padded(nb, N, T, speech_len, text_len), &eps))
+            return rc;
+        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        HIP_TRY(launch_guided_update(x2, eps, noise, seeds, step, w, a, ce, cz, speech_len, B, N, m->cfg.hidden_dim, cfg != 0,
+                                     (hipStream_t)stream));
+        return DITTO_OK;
+    });
 }
 
 int ditto_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
@@ -1496,24 +1491,22 @@ static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const
     if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
     if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
     if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    // under guidance the forward runs over the 2B utterances of [x; x] x [text; null]: cu_speech then holds 2B + 1 offsets over 2S rows
-    const int nb = cfg ? 2 * B : B, rows = cfg ? 2 * S : S;
-    const PackedWsPlan pw = plan_ws_packed(m->cfg, nb, rows, S_T > 0 ? S_T : 1);
-    if (workspace_bytes < pw.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, pw.total);
-    float* eps = (float*)((char*)workspace + pw.w.eps);
-    if (int rc = forward_packed(who, m, x2, cond, t, cu_speech, cu_text, nb, rows, max_N, S_T, max_T, rope_cos, rope_sin, eps, workspace,
-                                workspace_bytes, stream))
-        return rc;
-    ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-    if (per_utt)
-        HIP_TRY(launch_guided_update_packed_tags(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim,
-                                                 cfg != 0, (hipStream_t)stream));
-    else
-        HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim, cfg != 0,
-                                            (hipStream_t)stream));
-    return DITTO_OK;
+    return with_opts(opts, [&]() -> int {
+        // under guidance the forward runs over the 2B utterances of [x; x] x [text; null]: cu_speech then holds 2B + 1 offsets over 2S rows
+        const int nb = cfg ? 2 * B : B, rows = cfg ? 2 * S : S;
+        float* eps;
+        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
+                                  BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
+            return rc;
+        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        if (per_utt)
+            HIP_TRY(launch_guided_update_packed_tags(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim,
+                                                     cfg != 0, (hipStream_t)stream));
+        else
+            HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim,
+                                                cfg != 0, (hipStream_t)stream));
+        return DITTO_OK;
+    });
 }
 
 int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1776,22 +1769,22 @@ int ditto_full_row_plan(const ditto_config* cfg, int B, int N, int* outproj, int
 
 int ditto_full_row_plan_opts(const ditto_config* cfg, int B, int N, const ditto_call_opts* opts, int* outproj, int* fc2,
                              int* stream_bf16) {
-    if (int rc = check_call_opts(opts)) return rc;
-    CallScope scope(opts);
-    if (int rc = check_cfg(cfg)) return rc;
-    if (!outproj || !fc2 || B <= 0 || N <= 0) return fail(DITTO_ERR_ARG, "bad argument to ditto_full_row_plan");
-    if ((long long)B * N > 0x7fffffffLL) return fail(DITTO_ERR_SHAPE, "B * N exceeds 2^31 - 1 rows");
-    const int d = cfg->hidden_dim, M = B * N;
-    const bool fp8c = (cfg->flags & DITTO_CFG_FP8_LINEAR) != 0;          // plan_arena packs the stage-major copies for these:
-    if (int rc = check_class_pin(M, d, fp8c, !cfg_padded(*cfg))) return rc;   // what the forward itself would answer
-    const bool padc = cfg_padded(*cfg);                                   // padded heads: the tiled path only
-    const bool have_o = !padc && ((d == 768 && !fp8c) || d == 1024), have_2 = !padc && (d == 768 || d == 1024) && !fp8c;
-    *outproj = have_o && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
-    *fc2 = have_2 && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
-    if (stream_bf16)   // ditto_forward's hb_class
-        *stream_bf16 = opt_resid_bf16() && !fp8c && d == 768 && d / cfg->num_heads == 64 && *outproj && *fc2 && M >= 128 &&
-                       (g_fr_tile == 130 || (g_fr_tile == 0 && fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M) == 130));
-    return DITTO_OK;
+    return with_opts(opts, [&]() -> int {
+        if (int rc = check_cfg(cfg)) return rc;
+        if (!outproj || !fc2 || B <= 0 || N <= 0) return fail(DITTO_ERR_ARG, "bad argument to ditto_full_row_plan");
+        if ((long long)B * N > 0x7fffffffLL) return fail(DITTO_ERR_SHAPE, "B * N exceeds 2^31 - 1 rows");
+        const int d = cfg->hidden_dim, M = B * N;
+        const bool fp8c = (cfg->flags & DITTO_CFG_FP8_LINEAR) != 0;          // plan_arena packs the stage-major copies for these:
+        if (int rc = check_class_pin(M, d, fp8c, !cfg_padded(*cfg))) return rc;   // what the forward itself would answer
+        const bool padc = cfg_padded(*cfg);                                   // padded heads: the tiled path only
+        const bool have_o = !padc && ((d == 768 && !fp8c) || d == 1024), have_2 = !padc && (d == 768 || d == 1024) && !fp8c;
+        *outproj = have_o && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
+        *fc2 = have_2 && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
+        if (stream_bf16)   // ditto_forward's hb_class
+            *stream_bf16 = opt_resid_bf16() && !fp8c && d == 768 && d / cfg->num_heads == 64 && *outproj && *fc2 && M >= 128 &&
+                           (g_fr_tile == 130 || (g_fr_tile == 0 && fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M) == 130));
+        return DITTO_OK;
+    });
 }
 
 int ditto_profile_enable(ditto_model_t m, int enable) {

@@ -1,0 +1,73 @@
+// guided_update.h — the one source of the fused guided (DDIM) update of guided.hip, guided_packed.hip and guided_tags.hip.
+//   e' = CFG ? fmaf(w[b], c - u, u) : c               c, u = the conditional / unconditional half of eps2 (cfg_combine_kernel's expression)
+//   x' = fmaf(a[b], x, fmaf(ce[b], e', cz[b] * z))    (linear_update_kernel's; z = cz = 0 without noise)
+// written to the conditional and, under CFG, the unconditional half of x2.  NOISE: 0 none, 1 a buffer laid out like x, 2 Philox of
+// (seeds[b], step, quad index inside the utterance) — ditto_noise_normal's bits (philox.h).  HBM-bound: per element CFG 4 reads (x,
+// c, u, buffer noise) + 2 writes, without CFG 3 + 1; 16-byte lane accesses, grid (chunks, B); d % 64 == 0: no quad straddles a row.
+#pragma once
+#include <type_traits>
+#include "common.h"
+#include "philox.h"
+
+namespace ditto {
+
+// what utterance b multiplies with (s_loads: b = blockIdx.y is uniform over the workgroup)
+struct GuidedCoef { float a, ce, cz, w; unsigned long long seed; };
+template <int NOISE, bool CFG>
+__device__ __forceinline__ GuidedCoef guided_coef(const float* a, const float* ce, const float* cz, const float* w,
+                                                  const int64_t* seeds, int b) {
+    return {a[b], ce[b], NOISE ? cz[b] : 0.f, CFG ? w[b] : 0.f, NOISE == 2 ? (unsigned long long)seeds[b] : 0ull};
+}
+
+// utterance b's rows [cu[b], cu[b+1]) of a packed [S, d] buffer, clamped like attn_span (never outside the S rows, at least one row)
+struct GuidedSpan { size_t base4, n4; };
+__device__ __forceinline__ GuidedSpan guided_span(const int32_t* cu, int b, int S, int d) {
+    int r0 = cu[b];
+    r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
+    const int n = cu[b + 1] - r0, nb = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);
+    return {(size_t)r0 * d / 4, (size_t)nb * d / 4};
+}
+
+// quads [i0, n4) of one utterance at a grid stride: xc / ec (xu / eu) = its first quad in the conditional (unconditional) half, nz in
+// the noise buffer.  PADDED: quads from valid4 on are written as 0 and read nothing.  draw: whether a Philox utterance draws at all.
+// i0 and stride come from the __global__ function: read here, blockDim / gridDim compile to a vector load of the implicit arguments.
+template <int NOISE, bool CFG, bool PADDED>
+__device__ __forceinline__ void guided_rows(f32x4* xc, f32x4* xu, const f32x4* ec, const f32x4* eu, const f32x4* nz,
+                                            const GuidedCoef& k, unsigned step, bool draw, size_t n4, size_t valid4, size_t i0,
+                                            size_t stride) {
+    for (size_t i = i0; i < n4; i += stride) {
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (!PADDED || i < valid4) {
+            const f32x4 xv = xc[i];
+            const f32x4 c = ec[i];
+            f32x4 u = c;
+            if (CFG) u = eu[i];
+            f32x4 zv = {0.f, 0.f, 0.f, 0.f};
+            if (NOISE == 1) zv = nz[i];
+            if (NOISE == 2 && draw) zv = normal4(k.seed, step, i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float ev = CFG ? fmaf(k.w, c[e] - u[e], u[e]) : c[e];
+                o[e] = fmaf(k.a, xv[e], fmaf(k.ce, ev, k.cz * zv[e]));
+            }
+        }
+        xc[i] = o;
+        if (CFG) xu[i] = o;
+    }
+}
+
+// 256-thread workgroups over the quads of the longest utterance (at most 1024: the kernels stride), one grid column per utterance
+inline dim3 guided_grid(int max_rows, int d, int B) {
+    const size_t n4 = (size_t)max_rows * d / 4;
+    size_t gx = (n4 + 255) / 256;
+    if (gx > 1024) gx = 1024;
+    return dim3((unsigned)gx, B);
+}
+
+// f(noise mode, CFG) with both as compile-time constants: the six instantiations of a kernel
+template <class F> inline hipError_t guided_dispatch(const float* noise, const int64_t* seeds, bool cfg, F&& f) {
+    auto g = [&](auto nz) { return cfg ? f(nz, std::true_type{}) : f(nz, std::false_type{}); };
+    return seeds ? g(std::integral_constant<int, 2>{}) : noise ? g(std::integral_constant<int, 1>{}) : g(std::integral_constant<int, 0>{});
+}
+
+}  // namespace ditto

@@ -50,7 +50,7 @@ inline int cfg_dhp(const ditto_config& c) { const int dh = c.hidden_dim / c.num_
 inline int cfg_dp(const ditto_config& c) { return c.num_heads * cfg_dhp(c); }
 inline bool cfg_padded(const ditto_config& c) { return cfg_dp(c) != c.hidden_dim; }
 
-struct WsPlan { size_t h, u, qkv, act, xcat, eps, attn, attn_bytes, splitk, splitk_bytes, total; };
+struct WsPlan { size_t h, u, qkv, act, xcat, eps, attn, attn_bytes, splitk, splitk_bytes, utt, pos, total; };   // utt, pos: a packed batch's int32 row maps (0: none)
 // K-splits of a long-K, few-tile GEMM [M, N] x K at small batch (1 = none): ditto_api.hip
 int small_batch_k_splits(int M, int N, int K);
 int small_batch_k_splits_outproj(int M, int K);
@@ -66,7 +66,8 @@ int check_class_pin(int M, int d, bool fp8, bool has_fr);   // ditto_api.hip: a 
 int check_call_opts(const ditto_call_opts* o);
 struct CallScope {
     CallOpts saved;
-    explicit CallScope(const ditto_call_opts* o) : saved(t_opts) { apply(o); }
+    // (out of line: one copy for every _opts entry, and the weak symbol the library has exported since ABI 9 stays)
+    __attribute__((noinline)) explicit CallScope(const ditto_call_opts* o) : saved(t_opts) { apply(o); }
     ~CallScope() { t_opts = saved; }
     CallScope(const CallScope&) = delete;
     CallScope& operator=(const CallScope&) = delete;
