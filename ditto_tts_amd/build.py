@@ -24,7 +24,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EXTRA = {"attention.hip": ["-fno-honor-nans"], "attention_p.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
          "attention_varlen.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
          "attention_packed.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
-         "attention_bwd.hip": ["-fno-slp-vectorize"], "attention_train.hip": ["-fno-honor-nans", "-fno-slp-vectorize"]}
+         "attention_bwd.hip": ["-fno-slp-vectorize"], "attention_train.hip": ["-fno-honor-nans", "-fno-slp-vectorize"],
+         "attention_bwd_packed.hip": ["-fno-slp-vectorize"],
+         "attention_train_packed.hip": ["-fno-honor-nans", "-fno-slp-vectorize"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC,
          "-Wall", "-Wno-unused-function"]
 

@@ -742,8 +742,9 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     const bool varlen = a.q_len || a.kv_len;
     if (varlen && (a.dh != DH || a.force_generic || a.causal || train_fwd || !a.q_prescaled)) return hipErrorInvalidValue;
     const bool packed = a.cu_q || a.cu_kv;   // packed batch: both offset arrays, the same restrictions as varlen
+    // (the training forward over a packed batch takes q UNSCALED, as the dense one: attention_train_packed.hip)
     if (packed && (!a.cu_q || !a.cu_kv || varlen || a.q_rows <= 0 || a.kv_rows <= 0 || a.dh != DH || a.force_generic || a.causal ||
-                   train_fwd || !a.q_prescaled))
+                   (train_fwd ? a.q_prescaled || (g_attn_flags & 8192) != 0 : !a.q_prescaled)))
         return hipErrorInvalidValue;
     if (a.dh == DH && !a.force_generic && !a.causal) {
         if ((a.ldq | a.ldk | a.ldv) % 8) return hipErrorInvalidValue;
@@ -759,6 +760,7 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
         if (packed) {   // utterances concatenated along the rows (attention_packed.hip)
             if (a.ldo % 8 || (a.resid_f32 && a.ldr % 8)) return hipErrorInvalidValue;
             p.cu_q = a.cu_q; p.cu_kv = a.cu_kv; p.q_rows = a.q_rows; p.kv_rows = a.kv_rows;
+            if (train_fwd) return launch_attention_train64_packed(p, a.resid_f32 != nullptr, s);
             return launch_attn64p_packed(p, a.resid_f32 != nullptr, s, (g_attn_flags & 1048576) != 0);
         }
         if (varlen) {   // per-utterance lengths: the 64-queries-per-wave family only (attention_p.hip), whatever the class rows
@@ -961,11 +963,18 @@ size_t attention_train_workspace_bytes(int B, int H, int Sq, int Skv, int dh) {
     return g > dl ? g : dl;
 }
 
-bool attention_bwd_fuses_rope(const AttnBwdArgs& a) { return a.dh == DH && a.lse && a.rope_cos && a.rope_sin && a.Sq == a.Skv; }
+bool attention_bwd_fuses_rope(const AttnBwdArgs& a) {
+    return a.dh == DH && a.lse && a.rope_cos && a.rope_sin && a.Sq == a.Skv && a.cu_q == a.cu_kv;
+}
 
 hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) {
     if (a.B <= 0 || a.H <= 0 || a.Sq <= 0 || a.Skv <= 0 || a.dh % 64) return hipErrorInvalidValue;
     if ((a.rope_cos || a.rope_sin) && !attention_bwd_fuses_rope(a)) return hipErrorInvalidValue;   // the caller asks first
+    if (a.cu_q || a.cu_kv) {   // packed batch: the fused kernels' packed instantiations only (attention_bwd_packed.hip)
+        if (a.dh != DH || !a.lse || !a.workspace || a.workspace_bytes < attention_bwd_stats_bytes_packed(a.B, a.H, a.q_rows))
+            return hipErrorInvalidValue;
+        return launch_attention_bwd64_packed(a, (float*)a.workspace, s);
+    }
     if (a.dh == DH && a.lse) {   // fused: the two kernels; the {L, delta = rowsum(dO * O)} records live in the workspace
         if (!a.workspace || a.workspace_bytes < attention_bwd_stats_bytes(a.B, a.H, a.Sq)) return hipErrorInvalidValue;
         return launch_attention_bwd64(a, (float*)a.workspace, s);

@@ -4,6 +4,25 @@
 // Include inside `namespace ditto { namespace {` after attn_common.h.
 #pragma once
 
+#ifndef DITTO_ATTN_V2_PACKED   // 1 (attention_train_packed.hip): a packed batch — an utterance's first rows and lengths from p.cu_q / p.cu_kv
+#define DITTO_ATTN_V2_PACKED 0
+#endif
+// an utterance's extents, first query / key row and first log-sum-exp slot: the kernel's locals (packed) or, for the dense and padded
+// instantiations, the very expressions they have always been compiled from (their ISA does not move).  The dense forms are
+// UNPARENTHESISED products on purpose (the old parse, so the old ISA): use them only as the left operand of + inside parentheses
+#if DITTO_ATTN_V2_PACKED
+#define A2_SQ sq
+#define A2_SKV skv
+#define A2_Q0 q0
+#define A2_K0 k0
+#define A2_LSE0 lse0
+#else
+#define A2_SQ p.Sq
+#define A2_SKV p.Skv
+#define A2_Q0 (size_t)b * p.Sq
+#define A2_K0 (size_t)b * p.Skv
+#define A2_LSE0 (size_t)bh * p.Sq
+#endif
 constexpr int DH = ATT_DH, QBLK = 128, KBLK = ATT_KBLK;
 constexpr int KV_TILE_BYTES = ATT_KV_TILE_BYTES;  // 8 KiB
 constexpr float RESCALE_THR_LOG2 = ATT_RESCALE_THR_LOG2;   // attn_common.h
@@ -58,13 +77,20 @@ __global__ __launch_bounds__(256, WPS) void attn64v2_kernel(AttnParams p) {
     const int qb = id % p.nqb, bh = id / p.nqb;
     const int h = bh % p.H, b = bh / p.H;
     const int ql = lane & 31, hh = lane >> 5;
+#if DITTO_ATTN_V2_PACKED
+    // the utterance's own extents and first rows (clamped: attn_span); a workgroup past its last query leaves at once (before any barrier)
+    int sq, skv;
+    const size_t q0 = attn_span(p.cu_q, b, p.Sq, p.q_rows, sq), k0 = attn_span(p.cu_kv, b, p.Skv, p.kv_rows, skv);
+    if (qb * QBLK >= sq) return;
+    const size_t lse0 = (size_t)h * p.q_rows + q0;   // lse [H, q_rows]
+#endif
     int qrow = qb * QBLK + wid * 32 + ql;
-    const bool qvalid = qrow < p.Sq;
-    qrow = qvalid ? qrow : p.Sq - 1;
+    const bool qvalid = qrow < A2_SQ;
+    qrow = qvalid ? qrow : A2_SQ - 1;
 
     bf16x8 qf[4];
     {
-        const bf16* qp = p.q + ((size_t)b * p.Sq + qrow) * p.ldq + h * DH + 8 * hh;
+        const bf16* qp = p.q + (A2_Q0 + qrow) * p.ldq + h * DH + 8 * hh;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
         if constexpr (TRAIN) {
@@ -76,16 +102,16 @@ __global__ __launch_bounds__(256, WPS) void attn64v2_kernel(AttnParams p) {
     }
     DropStream dstream{};
     if constexpr (DROP) dstream = drop_stream(p.seed_lo, p.seed_hi, p.layer, bh);
-    const int nkt = (p.Skv + KBLK - 1) / KBLK;
-    const bool ragged = (p.Skv & (KBLK - 1)) != 0;
+    const int nkt = (A2_SKV + KBLK - 1) / KBLK;
+    const bool ragged = (A2_SKV & (KBLK - 1)) != 0;
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
     // this lane's two (row, chunk) DMA sources of tile 0; tile kt is + kt * 64 rows
     const bf16 *ksrc[2], *vsrc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = (wid * 2 + i) * 8 + (lane >> 3), cpos = lane & 7;
-        ksrc[i] = p.k + ((size_t)b * p.Skv + row) * p.ldk + h * DH + (cpos ^ ((row >> 1) & 7)) * 8;
-        vsrc[i] = p.v + ((size_t)b * p.Skv + row) * p.ldv + h * DH + (cpos ^ (((row >> 1) & 1) << 2)) * 8;
+        ksrc[i] = p.k + (A2_K0 + row) * p.ldk + h * DH + (cpos ^ ((row >> 1) & 7)) * 8;
+        vsrc[i] = p.v + (A2_K0 + row) * p.ldv + h * DH + (cpos ^ (((row >> 1) & 1) << 2)) * 8;
     }
     const size_t kstep = (size_t)KBLK * p.ldk, vstep = (size_t)KBLK * p.ldv;
     auto dma_kv = [&](int kt, int buf) {
@@ -95,11 +121,11 @@ __global__ __launch_bounds__(256, WPS) void attn64v2_kernel(AttnParams p) {
                 const int piece = wid * 2 + i;
                 const int row = piece * 8 + (lane >> 3), cpos = lane & 7;
                 int key = kt * KBLK + row;
-                key = key < p.Skv ? key : p.Skv - 1;
+                key = key < A2_SKV ? key : A2_SKV - 1;
                 const int ck = cpos ^ ((row >> 1) & 7), cv = cpos ^ (((row >> 1) & 1) << 2);
-                glds16(p.k + ((size_t)b * p.Skv + key) * p.ldk + h * DH + ck * 8,
+                glds16(p.k + (A2_K0 + key) * p.ldk + h * DH + ck * 8,
                        lds_base + (unsigned)(buf * 2 * KV_TILE_BYTES + piece * 1024));
-                glds16(p.v + ((size_t)b * p.Skv + key) * p.ldv + h * DH + cv * 8,
+                glds16(p.v + (A2_K0 + key) * p.ldv + h * DH + cv * 8,
                        lds_base + (unsigned)(buf * 2 * KV_TILE_BYTES + KV_TILE_BYTES + piece * 1024));
             }
             return;
@@ -178,7 +204,7 @@ __global__ __launch_bounds__(256, WPS) void attn64v2_kernel(AttnParams p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kbase_idx + kb2 * 32 + (r & 3) + 8 * (r >> 2);
-                    if (key >= p.Skv) st[kb2][r] = -1e30f;
+                    if (key >= A2_SKV) st[kb2][r] = -1e30f;
                 }
         }
         bf16x8 vf[8];
@@ -292,9 +318,9 @@ __global__ __launch_bounds__(256, WPS) void attn64v2_kernel(AttnParams p) {
     const float inv = 1.0f / lsum[0];
     if (!qvalid) return;
     if constexpr (TRAIN) {   // log2-domain log-sum-exp of the scaled scores: running maximum (= -cneg) + log2(row sum)
-        if (p.lse && hh == 0) p.lse[(size_t)bh * p.Sq + qrow] = __builtin_amdgcn_logf(lsum[0]) - cneg[0];
+        if (p.lse && hh == 0) p.lse[A2_LSE0 + qrow] = __builtin_amdgcn_logf(lsum[0]) - cneg[0];
     }
-    const size_t grow = (size_t)b * p.Sq + qrow;
+    const size_t grow = A2_Q0 + qrow;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -321,3 +347,8 @@ __global__ __launch_bounds__(256, WPS) void attn64v2_kernel(AttnParams p) {
             }
         }
 }
+#undef A2_SQ
+#undef A2_SKV
+#undef A2_Q0
+#undef A2_K0
+#undef A2_LSE0

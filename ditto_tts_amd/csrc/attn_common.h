@@ -40,17 +40,10 @@ DITTO_DEV int attn_len(const int32_t* len, int b, int full) {
     return v < 1 ? 1 : (v > full ? full : v);
 }
 
-// a packed utterance's first row (clamped into [0, rows - 1]) and its length (clamped into [1, min(full, rows - first)]): a bad
-// offset cannot address outside the buffer
-DITTO_DEV int attn_span(const int32_t* cu, int b, int full, int rows, int& len) {
-    int lo = cu[b];
-    lo = lo < 0 ? 0 : (lo > rows - 1 ? rows - 1 : lo);
-    const int n = cu[b + 1] - lo, cap = rows - lo < full ? rows - lo : full;
-    len = n < 1 ? 1 : (n > cap ? cap : n);
-    return lo;
-}
+// (attn_span, the packed utterance's clamped first row and length: gemm_common.h — shared with the backward kernels)
 
 hipError_t launch_attention_train64(const AttnParams& p, bool resid, hipStream_t s);   // attention_train.hip
+hipError_t launch_attention_train64_packed(const AttnParams& p, bool resid, hipStream_t s);   // attention_train_packed.hip: p.cu_q / p.cu_kv, lse [H, q_rows]
 hipError_t launch_attn64p(const AttnParams& p, bool resid, hipStream_t s, bool ring3 = false, int no_q = 0);   // attention_p.hip: 64 queries per wave (round 6: attn64p, attn64q)
 hipError_t launch_attn64p_varlen(const AttnParams& p, bool resid, hipStream_t s, bool exact_only);   // attention_varlen.hip: p.q_len / p.kv_len
 hipError_t launch_attn64p_packed(const AttnParams& p, bool resid, hipStream_t s, bool exact_only);   // attention_packed.hip: p.cu_q / p.cu_kv

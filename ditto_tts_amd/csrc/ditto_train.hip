@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "batch_layout.h"
 #include "gemm_common.h"
 #include "model.h"
 
@@ -25,13 +26,16 @@ inline size_t pad64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 struct TapePlan {
     size_t kv, tmod, text, pooled, xcat, hs, hs_stride;
-    struct L { size_t u1, u2, u3, qkv, qc, oc, pre, act, lse_s, lse_c; };
+    struct L { size_t u1, u2, u3, qkv, qc, oc, pre, act, lse_s, lse_c, os; };
     std::vector<L> layers;
     size_t total;
 };
-TapePlan plan_tape(const ditto_config& c, int B, int N, int T) {
+// The tape of a step over M speech and Mt text rows in all (dense: B * N, B * T; packed: S, S_T — every slot is per row, the two
+// log-sum-exp arrays hold H floats per speech row in either layout).  keep_o: a slot for the self-attention's O as bf16 [M, d] (the
+// packed backward reads O itself; the dense one takes h_after - h_before on the fp32 stream and needs no slot)
+TapePlan plan_tape(const ditto_config& c, int B, size_t M, size_t Mt, bool keep_o = false) {
     TapePlan p;
-    const size_t d = c.hidden_dim, L = c.num_layers, M = (size_t)B * N, Mt = (size_t)B * T;
+    const size_t d = c.hidden_dim, L = c.num_layers;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
     p.kv = take(Mt * L * 2 * d * 2); p.tmod = take((size_t)B * 2 * d * 4); p.text = take(Mt * c.text_dim * 2);
@@ -42,7 +46,8 @@ TapePlan plan_tape(const ditto_config& c, int B, int N, int T) {
     for (auto& q : p.layers) {
         q.u1 = take(M * d * 2); q.u2 = take(M * d * 2); q.u3 = take(M * d * 2); q.qkv = take(M * 3 * d * 2);
         q.qc = take(M * d * 2); q.oc = take(M * d * 2); q.pre = take(M * 8 * d * 2); q.act = take(M * 4 * d * 2);
-        q.lse_s = take((size_t)B * c.num_heads * N * 4); q.lse_c = take((size_t)B * c.num_heads * N * 4);
+        q.lse_s = take((size_t)c.num_heads * M * 4); q.lse_c = take((size_t)c.num_heads * M * 4);
+        q.os = keep_o ? take(M * d * 2) : 0;
     }
     p.total = off;
     return p;
@@ -72,7 +77,7 @@ TrainArenaPlan plan_train_arena(const ditto_config& c) {
 }
 
 struct TrainWsPlan {
-    size_t dh, du, dyb, big1, big2, dkv, zero, wtmp, vtmp, red, dmod, small, wpart, attn, attn_bytes, total;
+    size_t dh, du, dyb, big1, big2, dkv, zero, wtmp, vtmp, red, dmod, small, wpart, attn, attn_bytes, utt, pos, total;   // utt, pos: a packed batch's int32 row maps
 };
 // split-K factor of a wgrad GEMM with `tiles` 128x128 output tiles and `kt` K-tiles of 64.  Cost model, in units of
 // one K-tile of one resident workgroup (~1 us; 2 workgroups per CU = 512 slots): rounds(S) * ceil(kt / S) for the
@@ -119,9 +124,10 @@ inline int wgrad_splits_wide(long tiles, long kt) {
     return (int)best;
 }
 constexpr size_t WPART_BYTES = (size_t)(2048 + 320) * 128 * 128 * 4;   // S * tiles: up to ~4 rounds of 512 workgroups
-TrainWsPlan plan_train_ws(const ditto_config& c, int B, int N, int T) {
+// (N, T: rows per utterance, or the longest utterance's of a packed batch of M / Mt rows in all)
+TrainWsPlan plan_train_ws(const ditto_config& c, int B, int N, int T, size_t M, size_t Mt, bool packed) {
     TrainWsPlan w;
-    const size_t d = c.hidden_dim, M = (size_t)B * N, Mt = (size_t)B * T, dh = d / c.num_heads;
+    const size_t d = c.hidden_dim, dh = d / c.num_heads;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
     w.dh = take(M * d * 4); w.du = take(M * d * 4); w.dyb = take(M * d * 2);
@@ -129,7 +135,8 @@ TrainWsPlan plan_train_ws(const ditto_config& c, int B, int N, int T) {
     w.zero = take(256);
     w.wtmp = take(8 * d * d * 4); w.vtmp = take(8 * d * 4);
     size_t red = (size_t)256 * 8 * d * 4;   // colsum: <= 256 row chunks x <= 8d columns
-    const size_t r2 = ln_bwd_scratch_bytes((int)M, 1, (int)d), r3 = ln_bwd_scratch_bytes(N, B, (int)d);
+    const size_t r2 = ln_bwd_scratch_bytes((int)M, 1, (int)d);
+    const size_t r3 = packed ? adaln_bwd_packed_scratch_bytes(N, B, (int)d) : ln_bwd_scratch_bytes(N, B, (int)d);
     red = red > r2 ? red : r2; red = red > r3 ? red : r3;
     const size_t r4 = (size_t)2 * ((M + 255) / 256) * 8 * d * 4;   // fused fc2 dgrad + gated backward: one partial row per 128-row half tile
     red = red > r4 ? red : r4;
@@ -137,10 +144,16 @@ TrainWsPlan plan_train_ws(const ditto_config& c, int B, int N, int T) {
     w.dmod = take((size_t)B * 2 * d * 4);
     w.small = take(6 * al((size_t)B * c.time_dim * 4));
     w.wpart = take(WPART_BYTES);
-    const size_t a1 = attention_train_workspace_bytes(B, c.num_heads, N, N, (int)dh);
-    const size_t a2 = attention_train_workspace_bytes(B, c.num_heads, N, T, (int)dh);
-    w.attn_bytes = a1 > a2 ? a1 : a2;
+    if (packed) {   // head_dim 64 only: the fused backward's {L, delta} records are all the attention needs
+        w.attn_bytes = attention_bwd_stats_bytes_packed(B, c.num_heads, (int)M);
+    } else {
+        const size_t a1 = attention_train_workspace_bytes(B, c.num_heads, N, N, (int)dh);
+        const size_t a2 = attention_train_workspace_bytes(B, c.num_heads, N, T, (int)dh);
+        w.attn_bytes = a1 > a2 ? a1 : a2;
+    }
     w.attn = take(w.attn_bytes);
+    w.utt = w.pos = 0;
+    if (packed) { w.utt = take(M * 4); w.pos = take(M * 4); }
     w.total = off;
     return w;
 }
@@ -152,6 +165,26 @@ int check_train(const ditto_model* m) {
     if (cfg_padded(m->cfg))
         return fail(DITTO_ERR_SHAPE, "training needs head_dim %% 64 == 0 (head_dim %d runs forward-only, on padded heads)",
                     m->cfg.hidden_dim / m->cfg.num_heads);
+    return DITTO_OK;
+}
+TapePlan plan_tape(const ditto_config& c, const BatchLayout& lay) {
+    return plan_tape(c, lay.B, (size_t)lay.M, (size_t)lay.Mt, lay.kind == BatchLayout::PACKED);
+}
+TrainWsPlan plan_train_ws(const ditto_config& c, const BatchLayout& lay) {
+    return plan_train_ws(c, lay.B, lay.N, lay.T, (size_t)lay.M, (size_t)lay.Mt, lay.kind == BatchLayout::PACKED);
+}
+// what the packed training entries check on the host (the offsets live on the device: validated by the caller, clamped by every
+// kernel that turns one into an address)
+int check_train_packed(const char* who, const ditto_model* m, int B, int S, int max_N, int S_T, int max_T) {
+    const ditto_config& c = m->cfg;
+    if (c.hidden_dim / c.num_heads != 64)
+        return fail(DITTO_ERR_SHAPE, "%s: packed batches need head_dim 64 (this model's is %d)", who, c.hidden_dim / c.num_heads);
+    if (B <= 0 || S <= 0 || max_N <= 0 || S_T <= 0 || max_T <= 0)
+        return fail(DITTO_ERR_SHAPE, "%s: B, S, max_N, S_T and max_T must be positive", who);
+    if (max_N > S || max_T > S_T || B > S || B > S_T)
+        return fail(DITTO_ERR_SHAPE, "%s: need max_N <= S, max_T <= S_T and at least one row per utterance (B %d, S %d, S_T %d)", who, B,
+                    S, S_T);
+    if (B > 65535) return fail(DITTO_ERR_SHAPE, "%s: more than 65535 utterances", who);
     return DITTO_OK;
 }
 
@@ -170,11 +203,21 @@ size_t ditto_train_arena_bytes(const ditto_config* cfg) {
 }
 size_t ditto_tape_bytes(const ditto_config* cfg, int B, int N, int T) {
     if (check_cfg(cfg) != DITTO_OK || cfg_padded(*cfg) || B <= 0 || N <= 0 || T <= 0) return 0;
-    return plan_tape(*cfg, B, N, T).total;
+    return plan_tape(*cfg, BatchLayout::dense(B, N, T)).total;
 }
 size_t ditto_train_workspace_bytes(const ditto_config* cfg, int B, int N, int T) {
     if (check_cfg(cfg) != DITTO_OK || cfg_padded(*cfg) || B <= 0 || N <= 0 || T <= 0) return 0;
-    return plan_train_ws(*cfg, B, N, T).total;
+    return plan_train_ws(*cfg, BatchLayout::dense(B, N, T)).total;
+}
+size_t ditto_tape_bytes_packed(const ditto_config* cfg, int B, int S, int S_T) {
+    if (check_cfg(cfg) != DITTO_OK || cfg_padded(*cfg) || cfg->hidden_dim / cfg->num_heads != 64 || B <= 0 || S < B || S_T < B) return 0;
+    return plan_tape(*cfg, B, (size_t)S, (size_t)S_T, true).total;
+}
+size_t ditto_train_workspace_bytes_packed(const ditto_config* cfg, int B, int S, int max_N, int S_T, int max_T) {
+    if (check_cfg(cfg) != DITTO_OK || cfg_padded(*cfg) || cfg->hidden_dim / cfg->num_heads != 64 || B <= 0 || S < B || S_T < B ||
+        max_N <= 0 || max_T <= 0 || max_N > S || max_T > S_T)
+        return 0;
+    return plan_train_ws(*cfg, B, max_N, max_T, (size_t)S, (size_t)S_T, true).total;
 }
 
 int ditto_train_attach(ditto_model_t m, const ditto_weights* w, void* train_arena, size_t train_arena_bytes,
@@ -242,25 +285,31 @@ int ditto_train_forward(ditto_model_t m, const float* x, const float* text, cons
                                     workspace_bytes, stream, nullptr);
 }
 
-int ditto_train_forward_opts(ditto_model_t m, const float* x, const float* text, const int64_t* t, int B, int N, int T,
-                             const float* rope_cos, const float* rope_sin, float dropout_p, uint64_t seed, float* eps_out,
-                             void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
-                             const ditto_call_opts* opts) {
+// One training forward over a batch in the dense or the packed layout (one body: the dense step's launches are what they were)
+static int train_forward_impl(const char* who, ditto_model_t m, const float* x, const float* text, const int64_t* t,
+                              const BatchLayout& lay, const float* rope_cos, const float* rope_sin, float dropout_p, uint64_t seed,
+                              float* eps_out, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
+                              ditto_stream_t stream, const ditto_call_opts* opts) {
     if (int rc = check_call_opts(opts)) return rc;
     CallScope scope(opts);
     if (int rc = check_train(m)) return rc;
-    if (!x || !text || !t || !rope_cos || !rope_sin || !eps_out || !tape || !workspace || B <= 0 || N <= 0 || T <= 0)
-        return fail(DITTO_ERR_ARG, "bad argument to ditto_train_forward");
+    const bool packed = lay.kind == BatchLayout::PACKED;
+    const int B = lay.B, N = lay.N, T = lay.T;
+    if (!x || !text || !t || !rope_cos || !rope_sin || !eps_out || !tape || !workspace || B <= 0 || N <= 0 || T <= 0 ||
+        (packed && (!lay.cu || !lay.cu_t)))
+        return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    if (packed)
+        if (int rc = check_train_packed(who, m, B, lay.M, N, lay.Mt, T)) return rc;
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(DITTO_ERR_ARG, "dropout_p must be in [0, 1)");
     if (m->layersT.empty()) return fail(DITTO_ERR_ARG, "ditto_train_attach was not called on this handle");
     const ditto_config& c = m->cfg;
-    const TapePlan tp = plan_tape(c, B, N, T);
-    const TrainWsPlan wp = plan_train_ws(c, B, N, T);
+    const TapePlan tp = plan_tape(c, lay);
+    const TrainWsPlan wp = plan_train_ws(c, lay);
     if (tape_bytes < tp.total) return fail(DITTO_ERR_SIZE, "tape too small: %zu < %zu", tape_bytes, tp.total);
     if (workspace_bytes < wp.total) return fail(DITTO_ERR_SIZE, "train workspace too small: %zu < %zu", workspace_bytes, wp.total);
     if ((uintptr_t)tape % 256 || (uintptr_t)workspace % 256) return fail(DITTO_ERR_ARG, "tape / workspace must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const int d = c.hidden_dim, L = c.num_layers, H = c.num_heads, dh = d / H, M = B * N, Mt = B * T;
+    const int d = c.hidden_dim, L = c.num_layers, H = c.num_heads, dh = d / H, M = lay.M, Mt = lay.Mt;
     const float scale = 1.0f / sqrtf((float)dh);
     const bool fused_rope = (dh == 64);
     char* tb = (char*)tape;
@@ -281,13 +330,20 @@ int ditto_train_forward_opts(ditto_model_t m, const float* x, const float* text,
         g.M = Mt; g.N = L * 2 * d; g.K = d;
         HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
     }
-    HIP_TRY(launch_text_mod(text, m->wx, m->bx, pooled, tmod, B, T, c.text_dim, d, s));
+    if (packed) HIP_TRY(launch_text_mod_packed(text, lay.cu_t, Mt, T, m->wx, m->bx, pooled, tmod, B, c.text_dim, d, s));
+    else HIP_TRY(launch_text_mod(text, m->wx, m->bx, pooled, tmod, B, T, c.text_dim, d, s));
     const bool hb = train_stream_bf16(m, M);
+    int32_t *utt = packed ? (int32_t*)(ws + wp.utt) : nullptr, *pos = packed ? (int32_t*)(ws + wp.pos) : nullptr;
     {   // a tape whose forward fails half-way must not look written: drop any older record of this address now, record at the end
         std::lock_guard<std::mutex> lk(m->tape_mu);
         m->tapes.erase(tape);
     }
-    if (hb)   // bf16 h0 + block 0's norm1 from the same kernel, as the inference forward
+    if (packed) {   // the row maps (utterance and RoPE position of every packed row), then the entry with the utterance map
+        HIP_TRY(launch_packed_row_map(lay.cu, B, M, N, utt, pos, s));
+        HIP_TRY(launch_adaln_packed(x, m->ttab, tmod, t, c.diffusion_steps, utt, hs(0), xcat, 2 * d, M, d, s, hb,
+                                    hb ? m->layers[0].g1 : nullptr, hb ? m->layers[0].be1 : nullptr,
+                                    hb ? tb + tp.layers[0].u1 : nullptr));
+    } else if (hb)   // bf16 h0 + block 0's norm1 from the same kernel, as the inference forward
         HIP_TRY(launch_adaln(x, m->ttab, tmod, t, c.diffusion_steps, hs(0), xcat, 2 * d, B, N, d, s, true, m->layers[0].g1,
                              m->layers[0].be1, tb + tp.layers[0].u1));
     else
@@ -299,7 +355,7 @@ int ditto_train_forward_opts(ditto_model_t m, const float* x, const float* text,
     const bool fr_have = d == 768 && m->layers[0].WcoP != nullptr && m->layers[0].W2P != nullptr;
     const bool fr_out = fr_have && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
     const bool fr_fc2 = fr_have && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
-    const int fr_rot = N % 128 == 0 ? N / 128 : 0;
+    const int fr_rot = lay.rot_period(128);
     for (int l = 0; l < L; ++l) {
         const LayerPack& lp = m->layers[l];
         const LayerPackT& lt = m->layersT[l];
@@ -312,17 +368,19 @@ int ditto_train_forward_opts(ditto_model_t m, const float* x, const float* text,
             GemmArgs g{};
             g.A = tb + q.u1; g.lda = d; g.W = lt.Wqkv_u; g.bias = lt.bqkv_u; g.out = qkv; g.ldo = 3 * d;
             g.M = M; g.N = 3 * d; g.K = d;
-            g.rope_cos = rope_cos; g.rope_sin = rope_sin; g.rope_rows_per_batch = N; g.rope_cols = 2 * d;
-            HIP_TRY(launch_gemm(g, fused_rope ? EPI_QKV_ROPE : EPI_BIAS_BF16, s));
+            g.rope_cos = rope_cos; g.rope_sin = rope_sin; g.rope_rows_per_batch = lay.rope_rows_per_batch(); g.rope_cols = 2 * d;
+            g.rope_pos = pos;   // packed: the row's position inside its utterance (the tables' row)
+            HIP_TRY(launch_gemm(g, !fused_rope ? EPI_BIAS_BF16 : packed ? EPI_QKV_ROPE_PACKED : EPI_QKV_ROPE, s));
             if (!fused_rope) HIP_TRY(launch_rope_inplace(qkv, 3 * d, rope_cos, rope_sin, M, N, 2 * d, dh, s));
         }
         {
             AttnArgs a{};
             a.q = qkv; a.ldq = 3 * d; a.k = qkv + (size_t)d * 2; a.ldk = 3 * d; a.v = qkv + (size_t)2 * d * 2;
-            a.ldv = 3 * d; a.resid_f32 = h1; a.resid_in = h0; a.ldr = d; a.B = B; a.H = H; a.Sq = N; a.Skv = N;
+            a.ldv = 3 * d; a.resid_f32 = h1; a.resid_in = h0; a.ldr = d; a.H = H; lay.fill_attn(a, false);
             a.dh = dh; a.scale = scale; a.workspace = attn_ws; a.workspace_bytes = wp.attn_bytes;
             if (dh == 64) a.lse_out = (float*)(tb + q.lse_s);
             if (hb) { a.resid_bf16 = true; a.out_bf16 = (char*)h1 + (size_t)M * d * 2; a.ldo = d; }   // + O for the backward
+            else if (packed) { a.out_bf16 = tb + q.os; a.ldo = d; }   // the packed backward reads O itself on either stream
             HIP_TRY(launch_attention(a, s));
         }
         // ---- cross-attention (dropout on the probabilities in train mode) ----
@@ -338,7 +396,7 @@ int ditto_train_forward_opts(ditto_model_t m, const float* x, const float* text,
             AttnArgs a{};
             a.q = tb + q.qc; a.ldq = d; a.k = kv + (size_t)l * 2 * d * 2; a.ldk = L * 2 * d;
             a.v = kv + ((size_t)l * 2 * d + d) * 2; a.ldv = L * 2 * d; a.out_bf16 = tb + q.oc; a.ldo = d;
-            a.B = B; a.H = H; a.Sq = N; a.Skv = T; a.dh = dh; a.scale = scale;
+            a.H = H; lay.fill_attn(a, true); a.dh = dh; a.scale = scale;
             a.workspace = attn_ws; a.workspace_bytes = wp.attn_bytes;
             a.dropout_p = dropout_p; a.seed = seed; a.layer = l;
             if (dh == 64) a.lse_out = (float*)(tb + q.lse_c);
@@ -394,13 +452,31 @@ int ditto_train_forward_opts(ditto_model_t m, const float* x, const float* text,
         g.K = 2 * d;
         HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
     }
-    {   // every launch of the forward is enqueued: the tape is this handle's.  The map is bounded: a caller that allocates
-        // a fresh tape per step would otherwise grow it for ever, and a tape is gigabytes — nobody holds 64 live ones
+    {   // every launch of the forward is enqueued: the tape is this handle's.  A record leaves the map when a forward
+        // rewrites its tape or ditto_train_tape_forget is called, never wholesale: a pending backward always finds its own
+        // (a record is a few words; a caller that allocates a fresh tape per step and never tells grows the map by that much)
         std::lock_guard<std::mutex> lk(m->tape_mu);
-        if (m->tapes.size() >= 64) m->tapes.clear();
-        m->tapes[tape] = ditto_model::TapeRec{B, N, T, hb};
+        m->tapes[tape] = ditto_model::TapeRec{B, N, T, hb, M, Mt, packed};
     }
     return DITTO_OK;
+}
+
+int ditto_train_forward_opts(ditto_model_t m, const float* x, const float* text, const int64_t* t, int B, int N, int T,
+                             const float* rope_cos, const float* rope_sin, float dropout_p, uint64_t seed, float* eps_out,
+                             void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                             const ditto_call_opts* opts) {
+    return train_forward_impl("ditto_train_forward", m, x, text, t, BatchLayout::dense(B, N, T), rope_cos, rope_sin, dropout_p, seed,
+                              eps_out, tape, tape_bytes, workspace, workspace_bytes, stream, opts);
+}
+
+int ditto_train_forward_packed_opts(ditto_model_t m, const float* x, const float* text, const int64_t* t, const int32_t* cu_speech,
+                                    const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T, const float* rope_cos,
+                                    const float* rope_sin, float dropout_p, uint64_t seed, float* eps_out, void* tape,
+                                    size_t tape_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                                    const ditto_call_opts* opts) {
+    return train_forward_impl("ditto_train_forward_packed_opts", m, x, text, t,
+                              BatchLayout::packed(B, S, max_N, S_T, max_T, cu_speech, cu_text), rope_cos, rope_sin, dropout_p, seed,
+                              eps_out, tape, tape_bytes, workspace, workspace_bytes, stream, opts);
 }
 
 int ditto_train_backward(ditto_model_t m, const ditto_weights* w, const float* grad_eps, const float* x,
@@ -420,27 +496,32 @@ int ditto_train_backward_opts(ditto_model_t m, const ditto_weights* w, const flo
                                        workspace, workspace_bytes, stream, opts, m->cfg.num_layers - 1, 0);
 }
 
-int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const float* grad_eps, const float* x,
-                                const int64_t* t, int B, int N, int T, const float* rope_cos, const float* rope_sin,
-                                float dropout_p, uint64_t seed, const void* tape, size_t tape_bytes, const ditto_grads* grads,
-                                void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
-                                int layer_from, int layer_to) {
+// The layers layer_from .. layer_to of the backward over a batch in the dense or the packed layout (one body, as the forward)
+static int train_backward_impl(const char* who, ditto_model_t m, const ditto_weights* w, const float* grad_eps, const float* x,
+                               const int64_t* t, const BatchLayout& lay, const float* rope_cos, const float* rope_sin,
+                               float dropout_p, uint64_t seed, const void* tape, size_t tape_bytes, const ditto_grads* grads,
+                               void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
+                               int layer_from, int layer_to) {
     if (int rc = check_call_opts(opts)) return rc;
     CallScope scope(opts);
     if (int rc = check_train(m)) return rc;
     if (layer_from >= m->cfg.num_layers || layer_to < 0 || layer_from < layer_to)
-        return fail(DITTO_ERR_ARG, "ditto_train_backward_layers: need num_layers > layer_from >= layer_to >= 0");
+        return fail(DITTO_ERR_ARG, "%s: need num_layers > layer_from >= layer_to >= 0", who);
+    const bool packed = lay.kind == BatchLayout::PACKED;
+    const int B = lay.B, N = lay.N, T = lay.T;
     if (!w || !grad_eps || !x || !t || !rope_cos || !rope_sin || !tape || !grads || !grads->layers || !workspace ||
-        B <= 0 || N <= 0 || T <= 0)
-        return fail(DITTO_ERR_ARG, "bad argument to ditto_train_backward");
+        B <= 0 || N <= 0 || T <= 0 || (packed && (!lay.cu || !lay.cu_t)))
+        return fail(DITTO_ERR_ARG, "bad argument to %s", packed ? who : "ditto_train_backward");
+    if (packed)
+        if (int rc = check_train_packed(who, m, B, lay.M, N, lay.Mt, T)) return rc;
     if (m->layersT.empty() || !m->WoutT) return fail(DITTO_ERR_ARG, "ditto_train_attach was not called on this handle");
     const ditto_config& c = m->cfg;
-    const TapePlan tp = plan_tape(c, B, N, T);
-    const TrainWsPlan wp = plan_train_ws(c, B, N, T);
+    const TapePlan tp = plan_tape(c, lay);
+    const TrainWsPlan wp = plan_train_ws(c, lay);
     if (tape_bytes < tp.total) return fail(DITTO_ERR_SIZE, "tape too small: %zu < %zu", tape_bytes, tp.total);
     if (workspace_bytes < wp.total) return fail(DITTO_ERR_SIZE, "train workspace too small: %zu < %zu", workspace_bytes, wp.total);
     hipStream_t s = (hipStream_t)stream;
-    const int d = c.hidden_dim, L = c.num_layers, H = c.num_heads, dhd = d / H, M = B * N, Mt = B * T, td = c.time_dim;
+    const int d = c.hidden_dim, L = c.num_layers, H = c.num_heads, dhd = d / H, M = lay.M, Mt = lay.Mt, td = c.time_dim;
     const float scale = 1.0f / sqrtf((float)dhd);
     const bool lt0_has_fr = m->layersT[0].W1gTP != nullptr;
     const char* tb = (const char*)tape;
@@ -504,6 +585,9 @@ int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const f
         if (it->second.B != B || it->second.N != N || it->second.T != T)
             return fail(DITTO_ERR_SHAPE, "ditto_train_backward: the tape was written for (B, N, T) = (%d, %d, %d), not (%d, %d, %d)",
                         it->second.B, it->second.N, it->second.T, B, N, T);
+        if (it->second.packed != packed || it->second.M != M || it->second.Mt != Mt)
+            return fail(DITTO_ERR_SHAPE, "%s: the tape was written for a %s batch of %d speech and %d text rows, not a %s one of %d and %d",
+                        who, it->second.packed ? "packed" : "dense", it->second.M, it->second.Mt, packed ? "packed" : "dense", M, Mt);
         hb = it->second.hb;
     }
     const bool du_bf16 = !(g_train_flags & 8);
@@ -514,7 +598,7 @@ int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const f
         gp.out = out; gp.ldo = d; gp.M = M; gp.N = d; gp.K = n_out;
         // bf16 output exists on gemm_frd.hip (kernels.h fr_launch_kernel == 130: every row count the full-row dgrads run at)
         const bool hb = du_bf16 && fr_launch_kernel(M, n_out) == 130;
-        HIP_TRY(launch_gemm_fr(gp, nullptr, nullptr, nullptr, d, N % 128 == 0 ? N / 128 : 0, s, false, hb));
+        HIP_TRY(launch_gemm_fr(gp, nullptr, nullptr, nullptr, d, lay.rot_period(128), s, false, hb));
         du_is_bf16 = hb;
         return DITTO_OK;
     };
@@ -580,6 +664,7 @@ int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const f
             a.v = kv + ((size_t)l * 2 * d + d) * 2; a.ldv = L * 2 * d; a.dout = big2; a.lddo = d;
             a.dq = big1; a.lddq = d; a.dk = dkv; a.lddk = 2 * d; a.dv = dkv + (size_t)d * 2; a.lddv = 2 * d;
             a.B = B; a.H = H; a.Sq = N; a.Skv = T; a.dh = dhd; a.scale = scale;
+            if (packed) { a.cu_q = lay.cu; a.cu_kv = lay.cu_t; a.q_rows = M; a.kv_rows = Mt; }
             a.dropout_p = dropout_p; a.seed = seed; a.layer = l; a.workspace = attn_ws; a.workspace_bytes = wp.attn_bytes;
             if (dhd == 64) { a.lse = (const float*)(tb + q.lse_c); a.o_bf16 = tb + q.oc; a.ldo = d; }
             HIP_TRY(launch_attention_bwd(a, s));
@@ -601,11 +686,14 @@ int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const f
             a.dq = big1; a.lddq = 3 * d; a.dk = big1 + (size_t)d * 2; a.lddk = 3 * d; a.dv = big1 + (size_t)2 * d * 2;
             a.lddv = 3 * d; a.B = B; a.H = H; a.Sq = N; a.Skv = N; a.dh = dhd; a.scale = scale;
             a.workspace = attn_ws; a.workspace_bytes = wp.attn_bytes;
-            if (dhd == 64 && hb) { a.lse = (const float*)(tb + q.lse_s); a.o_bf16 = (const char*)h1 + (size_t)M * d * 2; a.ldo = d; }
+            if (packed) { a.cu_q = a.cu_kv = lay.cu; a.q_rows = a.kv_rows = M; }
+            if (packed && !hb) { a.lse = (const float*)(tb + q.lse_s); a.o_bf16 = tb + q.os; a.ldo = d; }   // O from its own slot
+            else if (dhd == 64 && hb) { a.lse = (const float*)(tb + q.lse_s); a.o_bf16 = (const char*)h1 + (size_t)M * d * 2; a.ldo = d; }
             else if (dhd == 64) { a.lse = (const float*)(tb + q.lse_s); a.h_after = h1; a.h_before = h0; a.ldh = d; }
             // the rotation's backward: in the dq / dk epilogues where the kernel can (head_dim 64), else one pass in place
             a.rope_cos = rope_cos; a.rope_sin = rope_sin;
-            const bool fused_rope_bwd = (g_train_flags & 1) == 0 && attention_bwd_fuses_rope(a);
+            // (a packed batch has the fused form only: the in-place pass takes a row's position as row % N)
+            const bool fused_rope_bwd = ((g_train_flags & 1) == 0 || packed) && attention_bwd_fuses_rope(a);
             if (!fused_rope_bwd) a.rope_cos = a.rope_sin = nullptr;
             HIP_TRY(launch_attention_bwd(a, s));
             if (!fused_rope_bwd) HIP_TRY(launch_rope_inplace(big1, 3 * d, rope_cos, rope_sin, M, N, 2 * d, dhd, s, -1.0f));
@@ -620,7 +708,8 @@ int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const f
     if (layer_to > 0) return DITTO_OK;   // the tail belongs to the call that ends at layer 0
     // ---- GlobalAdaLN (src/components/DiT.py:25-40): h0 = xhat (1 + s_t + s_x) + (b_t + b_x) ----
     // dmod[b] = [sum_n dh xhat | sum_n dh]: the gradient of BOTH branches' (scale, shift) vectors
-    HIP_TRY(launch_ln_bwd(dh, x, nullptr, nullptr, dmod, red, N, B, d, s));
+    if (packed) HIP_TRY(launch_adaln_bwd_packed(dh, x, lay.cu, B, M, N, d, dmod, red, s));   // per utterance: rows [cu[b], cu[b+1])
+    else HIP_TRY(launch_ln_bwd(dh, x, nullptr, nullptr, dmod, red, N, B, d, s));
     const float* pooled = (const float*)(tb + tp.pooled);
     HIP_TRY(launch_small_linear_bwd_w(dmod, pooled, grads->ada_text_mlp_weight, grads->ada_text_mlp_bias, B,
                                       c.text_dim, 2 * d, true, s));
@@ -642,6 +731,32 @@ int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const f
         HIP_TRY(launch_embedding_scatter_add(de0, t, grads->t_embedding_weight, B, c.diffusion_steps, td, s));
     }
 #undef TRY_RC
+    return DITTO_OK;
+}
+
+int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const float* grad_eps, const float* x,
+                                const int64_t* t, int B, int N, int T, const float* rope_cos, const float* rope_sin,
+                                float dropout_p, uint64_t seed, const void* tape, size_t tape_bytes, const ditto_grads* grads,
+                                void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
+                                int layer_from, int layer_to) {
+    return train_backward_impl("ditto_train_backward_layers", m, w, grad_eps, x, t, BatchLayout::dense(B, N, T), rope_cos, rope_sin,
+                               dropout_p, seed, tape, tape_bytes, grads, workspace, workspace_bytes, stream, opts, layer_from, layer_to);
+}
+
+int ditto_train_backward_packed_layers(ditto_model_t m, const ditto_weights* w, const float* grad_eps, const float* x, const int64_t* t,
+                                       const int32_t* cu_speech, const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T,
+                                       const float* rope_cos, const float* rope_sin, float dropout_p, uint64_t seed, const void* tape,
+                                       size_t tape_bytes, const ditto_grads* grads, void* workspace, size_t workspace_bytes,
+                                       ditto_stream_t stream, const ditto_call_opts* opts, int layer_from, int layer_to) {
+    return train_backward_impl("ditto_train_backward_packed_layers", m, w, grad_eps, x, t,
+                               BatchLayout::packed(B, S, max_N, S_T, max_T, cu_speech, cu_text), rope_cos, rope_sin, dropout_p, seed,
+                               tape, tape_bytes, grads, workspace, workspace_bytes, stream, opts, layer_from, layer_to);
+}
+
+int ditto_train_tape_forget(ditto_model_t m, const void* tape) {
+    if (!m || !tape) return fail(DITTO_ERR_ARG, "null argument to ditto_train_tape_forget");
+    std::lock_guard<std::mutex> lk(m->tape_mu);
+    m->tapes.erase(tape);
     return DITTO_OK;
 }
 
@@ -702,6 +817,63 @@ int ditto_attention_dropout_bf16(const void* q, int ldq, const void* k, int ldk,
     a.dropout_p = dropout_p; a.seed = seed; a.layer = layer; a.force_generic = lse_out == nullptr;
     a.lse_out = lse_out;
     HIP_TRY(launch_attention(a, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+
+size_t ditto_attention_bwd_packed_workspace_bytes(int B, int H, int Sq) {
+    if (B <= 0 || H <= 0 || Sq <= 0) return 0;
+    return attention_bwd_stats_bytes_packed(B, H, Sq);
+}
+static int check_attn_packed(const char* who, int B, int H, int Sq, int Skv, int max_q, int max_kv, int dh) {
+    if (dh != 64) return fail(DITTO_ERR_SHAPE, "%s: packed batches need head_dim 64", who);
+    if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || max_q <= 0 || max_kv <= 0)
+        return fail(DITTO_ERR_SHAPE, "%s: B, H, Sq, Skv, max_q and max_kv must be positive", who);
+    if (max_q > Sq || max_kv > Skv || B > Sq || B > Skv || B > 65535)
+        return fail(DITTO_ERR_SHAPE, "%s: need max_q <= Sq, max_kv <= Skv and at least one row per utterance (at most 65535 of them)", who);
+    return DITTO_OK;
+}
+int ditto_attention_train_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                      float* lse_out, const int32_t* cu_q, const int32_t* cu_kv, int B, int H, int Sq, int Skv,
+                                      int max_q, int max_kv, int dh, float scale, float dropout_p, uint64_t seed, int layer,
+                                      ditto_stream_t stream) {
+    if (!q || !k || !v || !out || !lse_out || !cu_q || !cu_kv) return fail(DITTO_ERR_ARG, "null pointer to ditto_attention_train_packed_bf16");
+    if (int rc = check_attn_packed("ditto_attention_train_packed_bf16", B, H, Sq, Skv, max_q, max_kv, dh)) return rc;
+    if ((ldq | ldk | ldv | ldo) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh || ldo < H * dh)
+        return fail(DITTO_ERR_SHAPE, "ditto_attention_train_packed_bf16: row strides must be multiples of 8 covering H * 64 columns");
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(DITTO_ERR_ARG, "dropout_p must be in [0, 1)");
+    AttnArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out_bf16 = out; a.ldo = ldo;
+    a.B = B; a.H = H; a.Sq = max_q; a.Skv = max_kv; a.dh = dh; a.scale = scale;
+    a.cu_q = cu_q; a.cu_kv = cu_kv; a.q_rows = Sq; a.kv_rows = Skv;
+    a.dropout_p = dropout_p; a.seed = seed; a.layer = layer; a.lse_out = lse_out;
+    HIP_TRY(launch_attention(a, (hipStream_t)stream));
+    return DITTO_OK;
+}
+int ditto_attention_bwd_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int lddo,
+                                    const void* out, int ldo, const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv,
+                                    int lddv, const int32_t* cu_q, const int32_t* cu_kv, int B, int H, int Sq, int Skv, int max_q,
+                                    int max_kv, int dh, float scale, float dropout_p, uint64_t seed, int layer, const float* rope_cos,
+                                    const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
+    if (!q || !k || !v || !dout || !out || !lse || !dq || !dk || !dv || !cu_q || !cu_kv || !workspace)
+        return fail(DITTO_ERR_ARG, "null pointer to ditto_attention_bwd_packed_bf16");
+    if (int rc = check_attn_packed("ditto_attention_bwd_packed_bf16", B, H, Sq, Skv, max_q, max_kv, dh)) return rc;
+    if ((ldq | ldk | ldv | lddo | ldo | lddq | lddk | lddv) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh || lddo < H * dh ||
+        ldo < H * dh || lddq < H * dh || lddk < H * dh || lddv < H * dh)
+        return fail(DITTO_ERR_SHAPE, "ditto_attention_bwd_packed_bf16: row strides must be multiples of 8 covering H * 64 columns");
+    if ((rope_cos == nullptr) != (rope_sin == nullptr) || (rope_cos && (cu_q != cu_kv || Sq != Skv || max_q != max_kv)))
+        return fail(DITTO_ERR_ARG, "ditto_attention_bwd_packed_bf16: the fused RoPE backward needs both tables and self-attention (cu_q == cu_kv)");
+    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(DITTO_ERR_ARG, "dropout_p must be in [0, 1)");
+    if (workspace_bytes < attention_bwd_stats_bytes_packed(B, H, Sq)) return fail(DITTO_ERR_SIZE, "attention backward workspace too small");
+    AttnBwdArgs a{};
+    a.lse = lse; a.o_bf16 = out; a.ldo = ldo;
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.dout = dout; a.lddo = lddo;
+    a.dq = dq; a.lddq = lddq; a.dk = dk; a.lddk = lddk; a.dv = dv; a.lddv = lddv;
+    a.B = B; a.H = H; a.Sq = max_q; a.Skv = max_kv; a.dh = dh; a.scale = scale;
+    a.cu_q = cu_q; a.cu_kv = cu_kv; a.q_rows = Sq; a.kv_rows = Skv;
+    a.dropout_p = dropout_p; a.seed = seed; a.layer = layer; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.rope_cos = rope_cos; a.rope_sin = rope_sin;
+    HIP_TRY(launch_attention_bwd(a, (hipStream_t)stream));
     return DITTO_OK;
 }
 

@@ -517,6 +517,16 @@ inline bool fr_fc2_ok(int M, int d) {
                gemm_fr64_supports(M, d, 4 * d, (size_t)4 * d, (size_t)4 * d);
     return fr_pays(M) && gemm_fr_supports(M, d, 4 * d, (size_t)4 * d, (size_t)4 * d);
 }
+// a packed utterance's first row (clamped into [0, rows - 1]) and its length (clamped into [1, min(full, rows - first)]): a bad
+// offset cannot address outside the buffer
+DITTO_DEV int attn_span(const int32_t* cu, int b, int full, int rows, int& len) {
+    int lo = cu[b];
+    lo = lo < 0 ? 0 : (lo > rows - 1 ? rows - 1 : lo);
+    const int n = cu[b + 1] - lo, cap = rows - lo < full ? rows - lo : full;
+    len = n < 1 ? 1 : (n > cap ? cap : n);
+    return lo;
+}
+
 // gemm_pp.hip
 bool gemm_pp_supports(const GemmParams& p, GemmEpilogue epi);
 hipError_t launch_gemm_pp(const GemmParams& p, GemmEpilogue epi, hipStream_t s);

@@ -342,12 +342,21 @@ struct AttnBwdArgs {
     // fused path: the INVERSE half-split RoPE of dq and dk (the backward of the rotation the QKV GEMM's epilogue applied) in
     // the kernels' epilogues, on the fp32 accumulators; tables [Sq, dh / 2] (self-attention: Skv == Sq).  null: no rotation.
     const float* rope_cos; const float* rope_sin;
+    // packed batch (fused path only; attention_bwd_packed.hip): device int32 [B + 1] row offsets of every utterance in q / dout / O /
+    // dq (q_rows rows) and k / v / dk / dv (kv_rows rows); Sq / Skv are then the longest lengths, lse is [H, q_rows], O is o_bf16,
+    // the RoPE tables are indexed by the row's position inside its utterance
+    const int32_t* cu_q = nullptr;
+    const int32_t* cu_kv = nullptr;
+    int q_rows = 0, kv_rows = 0;
 };
 hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s);
 // true when launch_attention_bwd(a) applies a.rope_cos / a.rope_sin itself (the fused dh == 64 path)
 bool attention_bwd_fuses_rope(const AttnBwdArgs& a);
 size_t attention_bwd_stats_bytes(int B, int H, int Sq);   // scratch for the per-tile {L, delta} records of the fused backward
 hipError_t launch_attention_bwd64(const AttnBwdArgs& a, float* stats, hipStream_t s);
+// packed batch: S / 64 + B + 1 records per head (utterance b's from record (cu_q[b] >> 6) + b on)
+size_t attention_bwd_stats_bytes_packed(int B, int H, int q_rows);
+hipError_t launch_attention_bwd64_packed(const AttnBwdArgs& a, float* stats, hipStream_t s);   // attention_bwd_packed.hip
 size_t attention_train_workspace_bytes(int B, int H, int Sq, int Skv, int dh);   // forward + backward scratch
 
 // ---------------- gemm_tn.hip : out fp32 [Mo, No] = X[K, Mo]^T Y[K, No], both operands K-major (wgrad) ----------------
@@ -367,6 +376,11 @@ hipError_t launch_ln_bwd_stream(const void* dy, bool dy_bf16, const void* x, boo
                                 hipStream_t s);
 hipError_t launch_ln_bwd(const float* dy, const float* x, const float* gamma, float* dx_accum, float* dgb_out,
                          float* scratch, int rows_per_group, int groups, int d, hipStream_t s);
+// train_packed.hip: the GlobalAdaLN reductions of a packed batch: dmod fp32 [B, 2d] = [sum dy * xhat | sum dy] over utterance b's rows
+// [cu[b], cu[b+1]) of dy, x fp32 [S, d]; partials never straddle an utterance and are summed in order (no atomics)
+size_t adaln_bwd_packed_scratch_bytes(int max_len, int B, int d);
+hipError_t launch_adaln_bwd_packed(const float* dy, const float* x, const int32_t* cu, int B, int S, int max_len, int d, float* dmod,
+                                   float* scratch, hipStream_t s);
 hipError_t launch_gated_bwd(const void* dact, const void* pre, void* dpre, int M, int F, hipStream_t s,
                             float* colsum_out = nullptr, float* scratch = nullptr);
 hipError_t launch_unpack_rows(const float* src, float* dst, int rows, int cols, int blk, int mult, int row_off,

@@ -96,7 +96,7 @@ struct ditto_model {
     const void* WoutT = nullptr;
     // what ditto_train_forward DECIDED for the tape it wrote (keyed by the tape's address): the backward reads the tape as it was
     // written, whatever the options say by then (a bf16 tape read as fp32 is garbage gradients without an error)
-    struct TapeRec { int B, N, T; bool hb; };
+    struct TapeRec { int B, N, T; bool hb; int M, Mt; bool packed; };   // M, Mt: speech / text rows in all (packed: S, S_T)
     std::mutex tape_mu;
     std::unordered_map<const void*, TapeRec> tapes;
     // profiling

@@ -573,6 +573,133 @@ class DenoiseEngine:
     def release_tape(self, tape, B, N, T):
         self._tapes.setdefault((B, N, T), []).append(tape)
 
+    # ---- packed variable-length batches: x [S, d], text [S_T, text_dim], utterance b in rows [cu[b], cu[b+1]) of each.  S and S_T differ
+    # every step, so tapes and the workspace are pooled by CAPACITY (bytes), not by shape: after the largest batch has been seen a step
+    # takes a tape that is large enough and allocates no device memory
+    def _take_tape_packed(self, need: int):
+        """the smallest free tape of at least `need` bytes; when none fits, the largest free one is dropped for a new one (the loop of
+        one forward, one backward converges on ONE tape of the largest size; several forwards outstanding at growing sizes keep
+        allocating until each has its own)"""
+        pool = self._tapes.setdefault("packed", [])
+        fit = [i for i, tp in enumerate(pool) if tp.numel() >= need]
+        if fit:
+            return pool.pop(min(fit, key=lambda i: pool[i].numel()))
+        if pool:   # every free tape is too small: the largest one makes room for its replacement
+            big = pool.pop(max(range(len(pool)), key=lambda i: pool[i].numel()))
+            hip.check(self.lib.ditto_train_tape_forget(self.handle, big.data_ptr()))
+            del big
+        return torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def release_tape_packed(self, tape):
+        """the tape's backward is done (or will never run): its record leaves the handle, the buffer returns to the pool"""
+        hip.check(self.lib.ditto_train_tape_forget(self.handle, tape.data_ptr()))
+        self._tapes.setdefault("packed", []).append(tape)
+
+    def _train_workspace_packed(self, B, S, max_N, S_T, max_T):
+        need = self.lib.ditto_train_workspace_bytes_packed(C.byref(self._ccfg), B, S, max_N, S_T, max_T)
+        if need == 0:
+            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
+        if self._train_ws is None or self._train_ws.numel() < need:
+            self._train_ws = None
+            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._train_ws
+
+    def _rope_tables_cap(self, N: int):
+        """RoPE tables of at least N rows (row i = position i, whatever the table's length): grown, never shrunk"""
+        cur = getattr(self, "_rope_cap", None)
+        if cur is None or cur[0].shape[0] < N or cur[2] != self._generation:
+            c, s = self.rope_tables(N)
+            self._rope_cap = (c, s, self._generation)
+        return self._rope_cap[0], self._rope_cap[1]
+
+    def train_forward_packed(self, x, cu_seqlens, text_emb, text_cu_seqlens, t, dropout_p: float, seed: int,
+                             max_seqlen: Optional[int] = None, max_text_seqlen: Optional[int] = None,
+                             opts: Optional[hip.CallOpts] = None):
+        """The training forward over a packed batch (ditto_train_forward_packed_opts): returns (eps fp32 [S, d], state) where
+        `state` carries what train_backward_packed needs (tape, inputs, offsets).  Utterance b's rows of eps are what train_forward
+        gives for it alone."""
+        require_fused_attention(self.cfg, "packed batches")
+        if not getattr(self, "_train_attached", False):
+            raise RuntimeError("train_attach() has not been called for the current weights")
+        xf, text = self._f32(x, "x"), self._f32(text_emb, "text_emb")
+        if xf.dim() != 2 or xf.shape[1] != self.cfg.hidden_dim:
+            raise ValueError(f"x: [S, {self.cfg.hidden_dim}] expected, got {list(xf.shape)}")
+        if text.dim() != 2 or text.shape[1] != self.cfg.text_dim:
+            raise ValueError(f"text_emb: [S_T, {self.cfg.text_dim}] expected, got {list(text.shape)}")
+        S, S_T = int(xf.shape[0]), int(text.shape[0])
+        B = len(cu_seqlens) - 1
+        if len(text_cu_seqlens) - 1 != B:
+            raise ValueError("cu_seqlens and text_cu_seqlens describe different numbers of utterances")
+        cu, max_N = self._cu(cu_seqlens, B, S, max_seqlen, "cu_seqlens")
+        ct, max_T = self._cu(text_cu_seqlens, B, S_T, max_text_seqlen, "text_cu_seqlens")
+        tt = self._t64(t, B)
+        need = self.lib.ditto_tape_bytes_packed(C.byref(self._ccfg), B, S, S_T)
+        if need == 0:
+            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
+        ws = self._train_workspace_packed(B, S, max_N, S_T, max_T)
+        tape = self._take_tape_packed(need)
+        c, s = self._rope_tables_cap(max_N)
+        cud, ctd = cu.to(self.device), ct.to(self.device)
+        out = torch.empty_like(xf)
+        try:
+            hip.check(self.lib.ditto_train_forward_packed_opts(
+                self.handle, xf.data_ptr(), text.data_ptr(), tt.data_ptr(), cud.data_ptr(), ctd.data_ptr(), B, S, max_N, S_T, max_T,
+                c.data_ptr(), s.data_ptr(), float(dropout_p), int(seed), out.data_ptr(), tape.data_ptr(), tape.numel(), ws.data_ptr(),
+                ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+        except BaseException:
+            self.release_tape_packed(tape)
+            raise
+        state = dict(tape=tape, xf=xf, tt=tt, cu=cud, cu_t=ctd, B=B, S=S, S_T=S_T, max_N=max_N, max_T=max_T, rope=(c, s),
+                     dropout_p=float(dropout_p), seed=int(seed))
+        return out, state
+
+    def train_backward_packed(self, state: Mapping[str, torch.Tensor], grad_eps, st, opts: Optional[hip.CallOpts] = None,
+                              piece_cb=None, layers_per_piece: int = 1) -> Dict[str, torch.Tensor]:
+        """Backward of train_forward_packed (`st`: its second result): fp32 gradients keyed by the reference state_dict names.
+        `piece_cb`: as train_backward — pieces of `layers_per_piece` layers, top first (ditto_train_backward_packed_layers),
+        bit-identical to the single call."""
+        g = self._f32(grad_eps, "grad_output")
+        if tuple(g.shape) != (st["S"], self.cfg.hidden_dim):
+            raise ValueError(f"grad_output: [{st['S']}, {self.cfg.hidden_dim}] expected, got {list(g.shape)}")
+        w, keep = self._weights_struct(state)
+        keys = [f"blocks.{l}.{k}" for l in range(self.cfg.num_layers) for k in hip.LAYER_KEY.values()] + \
+               [k for f, k in hip.GLOBAL_KEY.items() if f != "rotary_inv_freq"]
+        grads = {k: torch.empty(state[k].shape, dtype=torch.float32, device=self.device) for k in keys}
+        L = self.cfg.num_layers
+        layers = (hip.LayerGrads * L)()
+        for l in range(L):
+            for f, k in hip.LAYER_KEY.items():
+                setattr(layers[l], f, grads[f"blocks.{l}.{k}"].data_ptr())
+        gs = hip.Grads()
+        for f, k in hip.GLOBAL_KEY.items():
+            if f != "rotary_inv_freq":
+                setattr(gs, f, grads[k].data_ptr())
+        gs.layers = layers
+        ws = self._train_workspace_packed(st["B"], st["S"], st["max_N"], st["S_T"], st["max_T"])
+        c, s = st["rope"]
+        tape = st["tape"]
+        args = (self.handle, C.byref(w), g.data_ptr(), st["xf"].data_ptr(), st["tt"].data_ptr(), st["cu"].data_ptr(),
+                st["cu_t"].data_ptr(), st["B"], st["S"], st["max_N"], st["S_T"], st["max_T"], c.data_ptr(), s.data_ptr(),
+                st["dropout_p"], st["seed"], tape.data_ptr(), tape.numel(), C.byref(gs), ws.data_ptr(), ws.numel(), _stream(),
+                None if opts is None else C.byref(opts))
+        if piece_cb is None:
+            hip.check(self.lib.ditto_train_backward_packed_layers(*args, L - 1, 0))
+            return grads
+        head = ("proj_in.weight", "proj_in.bias", "proj_out.weight", "proj_out.bias")     # written by the piece that starts at the top
+        tail = [k for f, k in hip.GLOBAL_KEY.items() if f != "rotary_inv_freq" and k not in head]   # ... that ends at layer 0
+        step = max(int(layers_per_piece), 1)
+        hi = L - 1
+        while hi >= 0:
+            lo = max(hi - step + 1, 0)
+            hip.check(self.lib.ditto_train_backward_packed_layers(*args, hi, lo))
+            piece = [grads[k] for k in head] if hi == L - 1 else []
+            piece += [grads[f"blocks.{l}.{k}"] for l in range(hi, lo - 1, -1) for k in hip.LAYER_KEY.values()]
+            if lo == 0:
+                piece += [grads[k] for k in tail]
+            piece_cb(piece)
+            hi = lo - 1
+        return grads
+
     def train_forward(self, x, text_emb, t, dropout_p: float, seed: int, opts: Optional[hip.CallOpts] = None):
         """DiTTO.forward in train mode: returns (eps fp32 [B,N,d], tape).  The library records against the tape how it wrote it
         (bf16 or fp32 stream rows): train_backward reads it that way whatever the options are by then."""

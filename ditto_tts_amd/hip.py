@@ -217,6 +217,19 @@ SYMBOLS = {
                                        C.POINTER(Grads), _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_train_backward_layers": (_i, [_vp, C.POINTER(Weights), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _sz,
                                          C.POINTER(Grads), _vp, _sz, _vp, C.POINTER(CallOpts), _i, _i]),
+    # training on packed variable-length batches
+    "ditto_tape_bytes_packed": (_sz, [C.POINTER(Config), _i, _i, _i]),
+    "ditto_train_workspace_bytes_packed": (_sz, [C.POINTER(Config), _i, _i, _i, _i, _i]),
+    "ditto_train_forward_packed_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _vp, _sz, _vp,
+                                             _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_train_backward_packed_layers": (_i, [_vp, C.POINTER(Weights), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f,
+                                                _u64, _vp, _sz, C.POINTER(Grads), _vp, _sz, _vp, C.POINTER(CallOpts), _i, _i]),
+    "ditto_train_tape_forget": (_i, [_vp, _vp]),
+    "ditto_attention_bwd_packed_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ditto_attention_train_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f,
+                                               _u64, _i, _vp]),
+    "ditto_attention_bwd_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp,
+                                             _i, _i, _i, _i, _i, _i, _i, _f, _f, _u64, _i, _vp, _vp, _vp, _sz, _vp]),
     "ditto_layernorm_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "ditto_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "ditto_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .varlen import validate_lengths
+from .varlen import validate_cu_seqlens, validate_lengths
 from .config import DiTTOConfig
 from .engine import DenoiseEngine, TextCond, _stream, require_fused_attention
 from .synth import cosine_betas
@@ -84,6 +84,45 @@ class _DiTTOTrainFn(torch.autograd.Function):
         eng.release_tape(ctx.tape, B, N, ctx.T)
         ctx.tape = None
         return (None, None, None, None, None, None, None) + tuple(grads.get(k) for k in ctx.keys)
+
+
+class _DiTTOTrainPackedFn(torch.autograd.Function):
+    """DiTTO.train_forward_packed with a tape (ditto_train_forward_packed_opts) and its backward
+    (ditto_train_backward_packed_layers); built like _DiTTOTrainFn."""
+
+    @staticmethod
+    def forward(ctx, model, x, cu_seqlens, text_emb, text_cu_seqlens, t, max_seqlen, max_text_seqlen, dropout_p, seed, keys, *params):
+        eng = model.engine(x.device, train=True)
+        # the options in force at the call site travel to the backward thread in ctx (see _DiTTOTrainFn)
+        ctx.opts = hip.current_opts() if hip._has_call_opts() else None
+        out, st = eng.train_forward_packed(x, cu_seqlens, text_emb.to(x.device), text_cu_seqlens, t, dropout_p, seed,
+                                           max_seqlen=max_seqlen, max_text_seqlen=max_text_seqlen, opts=ctx.opts)
+        ctx.model, ctx.eng, ctx.st, ctx.keys = model, eng, st, keys
+        ctx.sig = model._watch.sig
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        model, eng = ctx.model, ctx.eng
+        if model._watch.sig != ctx.sig or model._watch.changed(model._path_tensors()):
+            raise RuntimeError("DiTTO parameters changed between forward and backward")
+        if ctx.st is None:
+            raise RuntimeError("backward through the same DiTTO.train_forward_packed twice (the activation tape was released)")
+        sd = {k: v for k, v in model.state_dict(keep_vars=True).items() if not k.startswith("nac.")}
+        sync = getattr(model, "_grad_sync", None)
+        try:
+            grads = eng.train_backward_packed(sd, grad_out, ctx.st, opts=ctx.opts,
+                                              piece_cb=sync.reduce if sync is not None else None,
+                                              layers_per_piece=getattr(model, "_grad_sync_layers", 1))
+        except BaseException:
+            if sync is not None:
+                sync.abort()
+            raise
+        if sync is not None:
+            sync.finish()
+        eng.release_tape_packed(ctx.st["tape"])
+        ctx.st = None
+        return (None,) * 11 + tuple(grads.get(k) for k in ctx.keys)
 
 
 class _ParamWatch:
@@ -398,6 +437,65 @@ class DiTTO(nn.Module):
         cond = eng.prepare_text_packed(text_emb.to(x.device), text_cu_seqlens, max_text_seqlen)
         out = eng.forward_packed(x, cond, t, cu_seqlens, max_seqlen)
         return out if x.dtype == torch.float32 else out.to(x.dtype)
+
+    def train_forward_packed(self, x, cu_seqlens, text_emb, text_cu_seqlens, t, *, max_seqlen=None, max_text_seqlen=None):
+        """The TRAINABLE forward over a packed batch (arguments and validation of forward_packed): eps [S, d] attached to autograd.
+        Utterance b's rows are what forward(x[cu[b]:cu[b+1]][None], text_emb[cu_t[b]:cu_t[b+1]][None], t[b:b+1]) gives under
+        autograd for it alone — attention over its own keys, the AdaLN text pool over its own text rows, RoPE from its own first row,
+        cross-attention dropout (train mode) from the counter hash at utterance-local indices — and backward() leaves in every live
+        parameter's .grad the gradient of the caller's loss over the S rows (no padding row exists: F.mse_loss(eps, noise_packed)
+        is the mean over real elements).  No gradient for x / text_emb or `.attn.out_proj.*`, as forward.  head_dim 64, bf16
+        linears."""
+        require_fused_attention(self.cfg, "packed batches")
+        if self.cfg.fp8_linear:
+            raise NotImplementedError("ditto_tts_amd: training with fp8_linear=True is not supported")
+        if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad):
+            raise NotImplementedError("ditto_tts_amd: gradients with respect to x / text_emb are not produced (the "
+                                      "reference feeds frozen-encoder outputs, src/TrainDiTTO.py:66-73); detach them")
+        if x.dim() != 2 or text_emb.dim() != 2:
+            raise ValueError("train_forward_packed: x [S, d] and text_emb [S_T, text_dim] expected")
+        B = len(cu_seqlens) - 1
+        # validated here, before any launch (the engine validates again on its own entry)
+        validate_cu_seqlens(cu_seqlens, B, int(x.shape[0]), int(x.shape[0]) if max_seqlen is None else int(max_seqlen), "cu_seqlens")
+        validate_cu_seqlens(text_cu_seqlens, B, int(text_emb.shape[0]),
+                            int(text_emb.shape[0]) if max_text_seqlen is None else int(max_text_seqlen), "text_cu_seqlens")
+        if x.shape[1] != self.cfg.hidden_dim or text_emb.shape[1] != self.cfg.text_dim or tuple(t.shape) != (B,):
+            raise ValueError(f"train_forward_packed: x [S, {self.cfg.hidden_dim}], text_emb [S_T, {self.cfg.text_dim}] and t [{B}] expected")
+        _require_cuda(x, "x")      # the arguments are sound: now the device (there is no CPU path)
+        named = [(n, p) for n, p in self.named_parameters() if not n.startswith("nac.") and ".attn.out_proj." not in n]
+        p_drop = float(self.blocks[0].cross_attn.dropout) if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0 else 0
+        keys = tuple(n for n, _ in named)
+        out = _DiTTOTrainPackedFn.apply(self, x, cu_seqlens, text_emb, text_cu_seqlens, t, max_seqlen, max_text_seqlen, p_drop, seed,
+                                        keys, *[p for _, p in named])
+        return out if x.dtype == torch.float32 else out.to(x.dtype)
+
+    def train_forward(self, x, text_emb, t, *, speech_lengths, text_lengths):
+        """The trainable forward for a batch in the reference's padded collate (src/utils/MLS.py:136-151): x [B, N, d], text_emb
+        [B, T, text_dim], utterance b valid on its first speech_lengths[b] / text_lengths[b] rows.  The valid rows are gathered into
+        the packed layout, train_forward_packed runs on them, and eps [B, N, d] is scattered into zeros: padded eps rows are exactly
+        0, padding contents (NaN included) reach nothing, and gradient arriving on padded rows is dropped."""
+        require_fused_attention(self.cfg, "variable-length batches")
+        if self.cfg.fp8_linear:
+            raise NotImplementedError("ditto_tts_amd: training with fp8_linear=True is not supported")
+        if x.dim() != 3 or text_emb.dim() != 3 or text_emb.shape[0] != x.shape[0]:
+            raise ValueError("train_forward: x [B, N, d] and text_emb [B, T, text_dim] expected")
+        B, N, d = x.shape
+        T = text_emb.shape[1]
+        sl = validate_lengths(speech_lengths, B, N, "speech_lengths")
+        tl = validate_lengths(text_lengths, B, T, "text_lengths")
+        _require_cuda(x, "x")
+        cu = [0] + torch.cumsum(sl.long(), 0).tolist()
+        cu_t = [0] + torch.cumsum(tl.long(), 0).tolist()
+        dev = x.device
+        sld, tld = sl.to(dev).long(), tl.to(dev).long()
+        rows = torch.nonzero((torch.arange(N, device=dev)[None, :] < sld[:, None]).reshape(-1)).reshape(-1)
+        trows = torch.nonzero((torch.arange(T, device=dev)[None, :] < tld[:, None]).reshape(-1)).reshape(-1)
+        xp = x.reshape(B * N, d).index_select(0, rows)
+        tp = text_emb.to(dev).reshape(B * T, text_emb.shape[2]).index_select(0, trows)
+        eps_p = self.train_forward_packed(xp, cu, tp, cu_t, t, max_seqlen=int(sl.max()), max_text_seqlen=int(tl.max()))
+        out = torch.zeros(B * N, d, dtype=eps_p.dtype, device=dev).index_copy(0, rows, eps_p)
+        return out.reshape(B, N, d)
 
     def cosine_beta_schedule(self, timesteps, s=0.008):
         """Reference src/model/DiTTO.py:96-104 (a dozen-element host-side table, torch ops as in the reference)."""

@@ -671,6 +671,49 @@ int ditto_train_backward_layers(ditto_model_t m, const ditto_weights* w, const f
                                 float dropout_p, uint64_t seed, const void* tape, size_t tape_bytes, const ditto_grads* grads,
                                 void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
                                 int layer_from, int layer_to);
+/* ---- training on PACKED variable-length batches.  The reference pads a training batch (src/utils/MLS.py:136-151) and lets every
+ * utterance attend to its neighbours' padding and pool it into the AdaLN text vector (src/components/DiT.py:25-40, 131-148: no
+ * key-padding mask); here utterance b owns speech rows [cu_speech[b], cu_speech[b+1]) of x / eps [S, d] and text rows
+ * [cu_text[b], cu_text[b+1]) of text [S_T, text_dim] (device int32 [B + 1] each, validated by the caller, clamped by every kernel that
+ * turns one into an address), and its rows of eps are what ditto_train_forward gives for it alone: attention over its own keys, the
+ * text pool over its own text rows, RoPE positions from its own first row (rope tables: at least max_N rows), dropout mask = the
+ * hash on stream b * H + h at the utterance-local (query, key) indices.  Gradients: of the caller's scalar loss over the S rows =
+ * the sum of the per-utterance gradients (src/TrainDiTTO.py:55-95 one utterance at a time), no atomics.  head_dim 64, bf16 linears.
+ * The tape and the workspace are per ROW: a buffer sized for (B, S, S_T) serves any batch that needs no more bytes. */
+size_t ditto_tape_bytes_packed(const ditto_config* cfg, int B, int S, int S_T);
+size_t ditto_train_workspace_bytes_packed(const ditto_config* cfg, int B, int S, int max_N, int S_T, int max_T);
+int ditto_train_forward_packed_opts(ditto_model_t m, const float* x, const float* text, const int64_t* t, const int32_t* cu_speech,
+                                    const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T, const float* rope_cos,
+                                    const float* rope_sin, float dropout_p, uint64_t seed, float* eps_out, void* tape,
+                                    size_t tape_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                                    const ditto_call_opts* opts);
+/* layers layer_from .. layer_to as ditto_train_backward_layers (src/TrainDiTTO.py:82-88 loss.backward()); the whole backward is the
+ * call (num_layers - 1, 0) */
+int ditto_train_backward_packed_layers(ditto_model_t m, const ditto_weights* w, const float* grad_eps, const float* x, const int64_t* t,
+                                       const int32_t* cu_speech, const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T,
+                                       const float* rope_cos, const float* rope_sin, float dropout_p, uint64_t seed, const void* tape,
+                                       size_t tape_bytes, const ditto_grads* grads, void* workspace, size_t workspace_bytes,
+                                       ditto_stream_t stream, const ditto_call_opts* opts, int layer_from, int layer_to);
+/* The handle keeps one small record per tape a forward wrote (how it was written), until a forward rewrites that tape or the caller
+ * says the tape's backward is done / the buffer is gone (src/TrainDiTTO.py:82-95: one backward per forward).  Records never leave
+ * wholesale: a backward that is still pending always finds its own. */
+int ditto_train_tape_forget(ditto_model_t m, const void* tape);
+/* the packed forms of ditto_attention_dropout_bf16 / ditto_attention_bwd_bf16 (nn.MultiheadAttention in train mode,
+ * src/components/DiT.py:131-148, per utterance): q / out / dout / dq [Sq, ld], k / v / dk / dv [Skv, ld], utterance b's rows from
+ * cu_q / cu_kv (device int32 [B + 1]), max_q / max_kv the longest lengths, lse fp32 [H, Sq] (log2 domain), q UNSCALED.  Rows outside
+ * every utterance's range are neither read nor written.  rope_cos / rope_sin (both or neither; self-attention, cu_q == cu_kv): the
+ * inverse half-split rotation of dq / dk (src/components/DiT.py:126-129) at the row's position inside its utterance, tables
+ * fp32 [>= max_q, 32].  workspace >= ditto_attention_bwd_packed_workspace_bytes(B, H, Sq). */
+size_t ditto_attention_bwd_packed_workspace_bytes(int B, int H, int Sq);
+int ditto_attention_train_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                      float* lse_out, const int32_t* cu_q, const int32_t* cu_kv, int B, int H, int Sq, int Skv,
+                                      int max_q, int max_kv, int dh, float scale, float dropout_p, uint64_t seed, int layer,
+                                      ditto_stream_t stream);
+int ditto_attention_bwd_packed_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int lddo,
+                                    const void* out, int ldo, const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv,
+                                    int lddv, const int32_t* cu_q, const int32_t* cu_kv, int B, int H, int Sq, int Skv, int max_q,
+                                    int max_kv, int dh, float scale, float dropout_p, uint64_t seed, int layer, const float* rope_cos,
+                                    const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream);
 /* building blocks of the backward, exported for unit parity tests:
  * ditto_layernorm_bwd: dx_accum fp32 [M,d] += LN'(dy); dgamma_dbeta fp32 [groups, 2d] (rows_per_group * groups = M;
  *   gamma may be NULL = ones; dx_accum or dgamma_dbeta may be NULL); scratch >= ditto_layernorm_bwd_scratch_bytes.
