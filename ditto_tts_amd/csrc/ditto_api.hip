@@ -1266,7 +1266,8 @@ int ditto_gemm_ln_bf16(const void* A, int lda, const void* W, const float* bias,
     p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = K; p.w_rows = N; p.bias = bias;
     p.residual = residual; p.ldr = ldo; p.out = out; p.ldo = ldo; p.M = M; p.N = N; p.K = K;
     if (g_fr_u_fp8 && (N != 1024 || !gamma)) return fail(DITTO_ERR_SHAPE, "fr_u_fp8 (test hook) needs N == 1024 and a LayerNorm output");
-    HIP_TRY(launch_gemm_fr(p, gamma, beta, u_bf16, ldu, g_fr_rot > 1 ? g_fr_rot : 0, (hipStream_t)stream, g_fr_u_fp8 != 0));
+    if (g_fr_hb && (N != 768 || g_fr_u_fp8)) return fail(DITTO_ERR_SHAPE, "fr_hb (test hook) needs N == 768 and a bf16 LayerNorm output");
+    HIP_TRY(launch_gemm_fr(p, gamma, beta, u_bf16, ldu, g_fr_rot > 1 ? g_fr_rot : 0, (hipStream_t)stream, g_fr_u_fp8 != 0, g_fr_hb != 0));
     return DITTO_OK;
 }
 
@@ -1615,7 +1616,7 @@ static int* option_slot(const char* name) {
     static const struct { const char* n; int* p; } tab[] = {
         {"gemm_tile", &g_gemm_tile}, {"attn_flags", &g_attn_flags}, {"gemm_flags", &g_gemm_flags}, {"gemm_group", &g_gemm_group},
         {"pp_mask", &g_pp_mask}, {"fr_mask", &g_fr_mask}, {"fr_class_rows", &g_fr_class_rows}, {"fr_dgrad", &g_fr_dgrad},
-        {"train_flags", &g_train_flags}, {"fr_u_fp8", &g_fr_u_fp8}, {"fr_tile", &g_fr_tile}, {"fr64_maxk", &g_fr64_maxk},
+        {"train_flags", &g_train_flags}, {"fr_u_fp8", &g_fr_u_fp8}, {"fr_hb", &g_fr_hb}, {"fr_tile", &g_fr_tile}, {"fr64_maxk", &g_fr64_maxk},
         {"fr_stagger", &g_fr_stagger}, {"fr_rot", &g_fr_rot}, {"pp_nb", &g_pp_nb}, {"pp_stagger", &g_pp_stagger},
         {"splitk_wgs", &g_splitk_wgs}, {"residual_bf16", &g_resid_bf16}, {"lnq", &g_lnq}, {"lnq_ring", &g_lnq_ring}, {"lnq_waves", &g_lnq_waves}, {"qkv_split", &g_qkv_split}, {"ll_mask", &g_ll_mask}, {"lnq_min_rows", &g_lnq_min_rows}, {"attn64p_min_wgs", &g_attn64p_min_wgs}, {"attn64p_min_wgs_plain", &g_attn64p_min_wgs_plain}};
     for (auto& e : tab) if (!strcmp(name, e.n)) return e.p;
@@ -1683,6 +1684,10 @@ int ditto_set_option(const char* name, int value) {
     }
     if (!strcmp(name, "fr_u_fp8")) {   // test hook: ditto_gemm_ln_bf16 writes u as fp8 e4m3 bytes ([M, ldu] bytes; N = 1024)
         g_fr_u_fp8 = value != 0;
+        return DITTO_OK;
+    }
+    if (!strcmp(name, "fr_hb")) {   // test hook: ditto_gemm_ln_bf16's residual and out are bf16 [M, ldo] (the bf16 residual stream's kernel form; N = 768)
+        g_fr_hb = value != 0;
         return DITTO_OK;
     }
     if (!strcmp(name, "fr_tile")) {

@@ -24,8 +24,14 @@
 //   K order   as gemm_fr.hip (rotation per 128-row tile included): h is bit-identical to gemm_fr.hip's.  The LayerNorm
 //             statistics are summed per quarter row ((q0 + q1) + (q2 + q3)), so u may differ from gemm_fr.hip's in the last
 //             bf16 bit of a few elements.
-//   LDS       A 2 x 16 KiB + bias row 3 KiB in the loop; the epilogue stages every output row through a wave-private
-//             32 KiB (whole-line stores) + gamma | beta + row statistics: 138 KiB.
+//   residual  bf16 stream (the model path): the tile's 192 KiB reach the accumulators THROUGH THE LDS — every wave fetches its own
+//             384 bytes of each row by LDS-DMA in whole 128-byte lines (48 pieces of 1 KiB per wave, two 32-row units in flight)
+//             and reads them back in the accumulator layout (96 ds_read_b64 per lane).  In-model the launch went 66.5 -> 62.0 us
+//             (K = 768) and 137.6 -> 132.7 us (K = 3072); with no residual read at all it would be 55.8 / 121.4
+//             (profiles/r13_frd_res_ceiling.txt).  The fp32 stream keeps its loads in the accumulator layout.
+//   LDS       A 2 x 16 KiB + bias row 3 KiB in the loop, the residual staging (4 waves x 2 x 12 KiB) behind them in the prologue;
+//             the epilogue stages every output row through a wave-private 32 KiB (whole-line stores) + gamma | beta + row
+//             statistics: 138 KiB.
 #include <type_traits>
 
 #include "gemm_common.h"
@@ -43,6 +49,12 @@ constexpr int D_GB = D_STAGE;                       // ... gamma | beta rows (6 
 constexpr int D_RED = D_GB + 2 * DN * 4;            // ... row sums [4 quarters][128 rows] fp32 (2 KiB)
 constexpr int D_LDS = D_RED + 4 * DM * 4;           // 138 KiB
 constexpr int DNA = 4;                              // column blocks (of 6) whose accumulators live in AGPRs
+// prologue, bf16 stream: the residual tile comes through the LDS in whole 128-byte lines.  Per wave two buffers of one UNIT =
+// 32 rows (one mb block) x this wave's 384 bytes of the row, as three [32 rows][128 B] images (16-byte chunk c of row r at
+// c ^ ((r >> 1) & 7), the A slabs' swizzle, applied on the DMA's source address); idle in the main loop, under the epilogue's staging
+constexpr int D_RSTG = D_BIAS + DN * 4;
+constexpr int D_RUNIT = 32 * 384;                   // 12 KiB = 12 LDS-DMA pieces of 8 rows x 128 B
+static_assert(D_RSTG % 128 == 0 && D_RUNIT % 128 == 0 && D_RSTG + 4 * 2 * D_RUNIT <= D_LDS, "residual staging fits under the epilogue's");
 
 #ifdef DITTO_DIAG_FR_NOSTORE
 #define FD_DIAG_M (p.M - (1 << 30))
@@ -92,6 +104,11 @@ DITTO_DEV void frd_dma(unsigned voff, const char* base, unsigned dst) {
 #endif
 }
 
+// one piece of the residual tile (the same instruction as frd_dma, without the A stream's A/B switches)
+DITTO_DEV void frd_res_dma(unsigned voff, const char* base, unsigned dst) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
+}
+
 // Vector-memory operations a wave has issued AFTER the load of W fragment (s, nb) when MFMA (s, nb) is about to issue, i.e.
 // what may stay in flight at that wait.  Issue order of a stage at slab position j: W0 W1 W2 W3 W4 [A] W5 [A]  (the two A
 // pieces only at j < 2 and while a next slab exists), W = the fragments of stage s + 2 while that stage exists.
@@ -130,20 +147,13 @@ DITTO_DEV unsigned long long frd_now() {
 #endif
 
 // accumulator-init group gi of 24 -> its (nb, mb) block (see the kernel's prologue)
-constexpr int frd_group_nb(int gi) {
-#if defined(FRD_PAIRED) && FRD_PAIRED
-    return 2 * (gi >> 3) + (gi & 1);
+constexpr int frd_group_nb(int gi) { return gi >> 2; }
+constexpr int frd_group_mb(int gi) { return gi & 3; }
+#ifdef DITTO_DIAG_FRD_NORES   // stamps only: the accumulators start from the bias alone (valid numbers, WRONG results) — what do the residual loads cost?
+constexpr bool FRD_NORES = true;
 #else
-    return gi >> 2;
+constexpr bool FRD_NORES = false;
 #endif
-}
-constexpr int frd_group_mb(int gi) {
-#if defined(FRD_PAIRED) && FRD_PAIRED
-    return (gi >> 1) & 3;
-#else
-    return gi & 3;
-#endif
-}
 
 template <bool LN, bool RES, bool HB = false>
 __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
@@ -224,55 +234,103 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
     const int a_row = r32 * 128;                                      // + mb * 4096
     const int a_x = (hh ^ ((r32 >> 1) & 7)) << 4;                     // ^ (j << 5)
 
-    // ---- accumulators START as bias + residual (the epilogue only READS them): 96 hand-written global_load_dwordx4 per lane
-    //      in the accumulator layout, four 32 x 32 blocks (16 loads) in flight ----
+    // ---- accumulators START as bias + residual (the epilogue only READS them) ----
     const float* lbias = reinterpret_cast<const float*>(smem + D_BIAS);
     const float* lgamma = reinterpret_cast<const float*>(smem + D_GB);     // these two: valid in the epilogue only
     const float* lbeta = lgamma + DN;
     f32x16 acca[DNA][4], accv[6 - DNA][4];
-    {
+    using res_t = typename std::conditional<HB, u32x2, f32x4>::type;   // four columns of one row: bf16 x 4 or fp32 x 4
+    // block (nb, mb) = bias + the residual values t (four columns per g), into its home file
+    auto init_block = [&](auto NB, auto MB, const res_t (&t)[4]) {
+        constexpr int nb = decltype(NB)::value, mb = decltype(MB)::value;
+        f32x16 v;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(lbias + wid * 192 + nb * 32 + 8 * g + 4 * hh);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float r;
+                if constexpr (HB) r = __builtin_bit_cast(float, (e & 1) ? (t[g][e >> 1] & 0xFFFF0000u) : (t[g][e >> 1] << 16));
+                else r = t[g][e];
+                v[4 * g + e] = r + b4[e];
+            }
+        }
+        if constexpr (nb < DNA) { acca[nb < DNA ? nb : 0][mb] = v; FD_PIN_A(acca[nb < DNA ? nb : 0][mb]); }
+        else { accv[nb < DNA ? 0 : nb - DNA][mb] = v; FD_PIN_V(accv[nb < DNA ? 0 : nb - DNA][mb]); }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    if constexpr (RES && HB && !FRD_NORES) {
+        // The bf16 stream (the model path).  In the accumulator layout a wave instruction would touch 32 rows for 16 bytes each:
+        // 12 288 sixteen-byte requests per tile (measured at 2.9 TB/s, 14-16 % over-fetch).  Instead every wave stages ITS 384
+        // bytes of each row through the LDS by LDS-DMA — three whole 128-byte lines per row, eight lines per instruction — one
+        // unit of 32 rows at a time into two buffers, and reads it back in the accumulator layout with ds_read_b64 (chunk
+        // (nb & 1) * 4 + g of image nb >> 1; the swizzle leaves the 32 rows of a read on 16 different chunk slots).  Wave-private:
+        // no barrier, the wave's own counted vmcnt orders its reads behind its DMA.  Unit mb + 2 is issued into the buffer of
+        // unit mb once that one has been read, so two units (24 KiB per wave) are in flight while one is converted.
+        // Everything is retired by the vmcnt(0) below: the main loop's counts (frd_vm) see A and W only, as before.
+        const unsigned rs_wave = lds_base + (unsigned)(D_RSTG + wid * 2 * D_RUNIT);
+        const char* rs_rd = smem + D_RSTG + wid * 2 * D_RUNIT;
+        const unsigned rd_off = (unsigned)(r32 * 128 + (((r32 >> 1) & 7) << 4) + hh * 8);     // ^ (chunk << 4)
+        const unsigned rs_col = (unsigned)(wid * 384);
+        auto issue_unit = [&](auto MB) {
+            constexpr int mb = decltype(MB)::value;
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb) {                                  // piece = 8 rows x 128 B: lane -> (row, position)
+                const int row = rb * 8 + (lane >> 3);
+                int gr = m0 + mb * 32 + row;
+                gr = gr < p.M ? gr : p.M - 1;
+                const unsigned voff = (unsigned)gr * (unsigned)p.ldr * 2u + rs_col + (unsigned)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    frd_res_dma(voff + (unsigned)(j * 128), reinterpret_cast<const char*>(p.residual),
+                                rs_wave + (unsigned)((mb & 1) * D_RUNIT + (j * 4 + rb) * 1024));
+            }
+        };
+        auto read_block = [&](auto NB, auto MB, res_t (&t)[4]) {
+            constexpr int nb = decltype(NB)::value, mb = decltype(MB)::value;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                t[g] = *reinterpret_cast<const u32x2*>(rs_rd + (mb & 1) * D_RUNIT + (nb >> 1) * 4096 + (rd_off ^ (unsigned)(((nb & 1) * 4 + g) << 4)));
+        };
+        // YOUNGER: the DMA pieces issued after this unit's (12 per unit still in flight behind it).  The reads of block nb + 1
+        // are issued before block nb is converted.
+        auto read_unit = [&](auto MB, auto YOUNGER) {
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(YOUNGER)::value) : "memory");
+            if constexpr (decltype(MB)::value == 0) FD_BAR();   // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
+            res_t ta[4], tb[4];
+            read_block(DC<0>{}, MB, ta);
+            read_block(DC<1>{}, MB, tb); init_block(DC<0>{}, MB, ta);
+            read_block(DC<2>{}, MB, ta); init_block(DC<1>{}, MB, tb);
+            read_block(DC<3>{}, MB, tb); init_block(DC<2>{}, MB, ta);
+            read_block(DC<4>{}, MB, ta); init_block(DC<3>{}, MB, tb);
+            read_block(DC<5>{}, MB, tb); init_block(DC<4>{}, MB, ta);
+            init_block(DC<5>{}, MB, tb);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the buffer is read: the next unit's DMA may overwrite it
+        };
+        issue_unit(DC<0>{}); issue_unit(DC<1>{});
+        read_unit(DC<0>{}, DC<12>{}); issue_unit(DC<2>{});
+        read_unit(DC<1>{}, DC<12>{}); issue_unit(DC<3>{});
+        read_unit(DC<2>{}, DC<12>{});
+        read_unit(DC<3>{}, DC<0>{});
+    } else {
+        // fp32 stream: 96 hand-written global_load_dwordx4 per lane in the accumulator layout, four 32 x 32 blocks (16 loads) in
+        // flight.  (Round 5 A/B of a deeper window on the bf16 form of these loads, profiles/r05_frd_window_ab.txt: inside the
+        // noise — the phase was bound by its 16-byte requests, not by the window.)
         const char* rp[4] = {nullptr, nullptr, nullptr, nullptr};
-        if constexpr (RES) {
+        if constexpr (RES && !HB) {
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
                 int gr = m0 + mb * 32 + r32;
                 gr = gr < p.M ? gr : p.M - 1;
-                if constexpr (HB) rp[mb] = reinterpret_cast<const char*>(reinterpret_cast<const bf16*>(p.residual) + (size_t)gr * p.ldr + wid * 192 + 4 * hh);
-                else rp[mb] = reinterpret_cast<const char*>(p.residual + (size_t)gr * p.ldr + wid * 192 + 4 * hh);
+                rp[mb] = reinterpret_cast<const char*>(p.residual + (size_t)gr * p.ldr + wid * 192 + 4 * hh);
             }
         }
-#ifndef FRD_WD
-#define FRD_WD 4
-#endif
-#ifndef FRD_PAIRED
-#define FRD_PAIRED 0
-#endif
-        // window depth (groups of four loads in flight per wave); 24 groups = (nb, mb) blocks.  Order: mb fastest (FRD_PAIRED 0),
-        // or the two column blocks that share a row's 128-byte line back to back (bf16 stream: 2 x 64 B; FRD_PAIRED 1).
-        // Round 5 A/B (-DFRD_WD=8|12 -DFRD_PAIRED=1, profiles/r05_frd_window_ab.txt): out-proj 65.6 -> 64.2 .. 65.4 us, fc2 137.5 ->
-        // 136.2 .. 137.0: inside the noise — the 17 us of this phase are not a too-small load window; defaults kept.
-        constexpr int WD = HB ? FRD_WD : 4, NG = 24;                 // (the fp32 form: 16-byte loads, twice the window registers)
-        static_assert(WD == 4 || WD == 8 || WD == 12, "window depth");
-        using res_t = typename std::conditional<HB, u32x2, f32x4>::type;   // four columns of one row: bf16 x 4 or fp32 x 4
+        constexpr int WD = 4, NG = 24;                               // window depth (groups of four loads in flight per wave); 24 groups = (nb, mb) blocks, mb fastest
+        constexpr bool LOADS = RES && !HB && !FRD_NORES;
         res_t T[WD][4];
         auto issue_group = [&](auto GI, res_t (&t)[4]) {
             constexpr int nb = frd_group_nb(decltype(GI)::value), mb = frd_group_mb(decltype(GI)::value);
-#ifdef DITTO_DIAG_FRD_NORES   // stamps only: the accumulators start from the bias alone (valid numbers, WRONG results) — what do the residual loads cost?
-            if constexpr (true) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) t[i] = res_t{};
-            } else
-#endif
-            if constexpr (RES && HB) {
-                const char* ptr = rp[mb];
-                asm volatile("global_load_dwordx2 %0, %4, off offset:%5\n\t"
-                             "global_load_dwordx2 %1, %4, off offset:%6\n\t"
-                             "global_load_dwordx2 %2, %4, off offset:%7\n\t"
-                             "global_load_dwordx2 %3, %4, off offset:%8"
-                             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
-                             : "v"(ptr), "n"(nb * 64), "n"(nb * 64 + 16), "n"(nb * 64 + 32), "n"(nb * 64 + 48)
-                             : "memory");
-            } else if constexpr (RES) {
+            if constexpr (LOADS) {
                 const char* ptr = rp[mb];
                 asm volatile("global_load_dwordx4 %0, %4, off offset:%5\n\t"
                              "global_load_dwordx4 %1, %4, off offset:%6\n\t"
@@ -289,31 +347,13 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
         auto finish_group = [&](auto GI, res_t (&t)[4]) {
             constexpr int gi = decltype(GI)::value, nb = frd_group_nb(gi), mb = frd_group_mb(gi);
             constexpr int younger = NG - 1 - gi < WD - 1 ? NG - 1 - gi : WD - 1;
-#ifndef DITTO_DIAG_FRD_NORES
-            if constexpr (RES)
+            if constexpr (LOADS)
                 asm volatile("s_waitcnt vmcnt(%4)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) : "n"(4 * younger) : "memory");
-#else
-            if constexpr (gi == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             if constexpr (gi == 0) {
-                if constexpr (!RES) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if constexpr (!LOADS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 FD_BAR();      // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
             }
-            f32x16 v;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 b4 = *reinterpret_cast<const f32x4*>(lbias + wid * 192 + nb * 32 + 8 * g + 4 * hh);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float r;
-                    if constexpr (HB) r = __builtin_bit_cast(float, (e & 1) ? (t[g][e >> 1] & 0xFFFF0000u) : (t[g][e >> 1] << 16));
-                    else r = t[g][e];
-                    v[4 * g + e] = r + b4[e];
-                }
-            }
-            if constexpr (nb < DNA) { acca[nb < DNA ? nb : 0][mb] = v; FD_PIN_A(acca[nb < DNA ? nb : 0][mb]); }
-            else { accv[nb < DNA ? 0 : nb - DNA][mb] = v; FD_PIN_V(accv[nb < DNA ? 0 : nb - DNA][mb]); }
-            __builtin_amdgcn_sched_barrier(0);
+            init_block(DC<nb>{}, DC<mb>{}, t);
         };
         auto init_step = [&](auto GI) {
             constexpr int gi = decltype(GI)::value;
@@ -321,8 +361,6 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
             if constexpr (gi + WD < NG) issue_group(DC<gi + WD>{}, T[gi % WD]);
         };
         issue_group(DC<0>{}, T[0]); issue_group(DC<1>{}, T[1]); issue_group(DC<2>{}, T[2]); issue_group(DC<3>{}, T[3]);
-        if constexpr (WD > 4) { issue_group(DC<4>{}, T[4 % WD]); issue_group(DC<5>{}, T[5 % WD]); issue_group(DC<6>{}, T[6 % WD]); issue_group(DC<7>{}, T[7 % WD]); }
-        if constexpr (WD > 8) { issue_group(DC<8>{}, T[8 % WD]); issue_group(DC<9>{}, T[9 % WD]); issue_group(DC<10>{}, T[10 % WD]); issue_group(DC<11>{}, T[11 % WD]); }
         init_step(DC<0>{}); init_step(DC<1>{}); init_step(DC<2>{}); init_step(DC<3>{}); init_step(DC<4>{}); init_step(DC<5>{});
         init_step(DC<6>{}); init_step(DC<7>{}); init_step(DC<8>{}); init_step(DC<9>{}); init_step(DC<10>{}); init_step(DC<11>{});
         init_step(DC<12>{}); init_step(DC<13>{}); init_step(DC<14>{}); init_step(DC<15>{}); init_step(DC<16>{}); init_step(DC<17>{});
@@ -595,6 +633,9 @@ hipError_t launch_gemm_frd(const FrParams& fp_in, hipStream_t s) {
     fp.g.tiles_m = (fp.g.M + DM - 1) / DM;
     fp.g.tiles_n = 1;
     const bool ln = fp.gamma && fp.u, res = fp.g.residual != nullptr;
+    // the bf16 residual tile is fetched by 16-byte LDS-DMA pieces at 32-bit byte offsets from the residual pointer
+    if (fp.hb && res && (fp.g.ldr % 8 || (uintptr_t)fp.g.residual % 16 || (size_t)fp.g.M * (size_t)fp.g.ldr * 2 >= (1ull << 32)))
+        return hipErrorInvalidValue;
     if (fp.hb) {   // bf16 residual stream (the model path's two launches: always with a residual), or — no residual, no LayerNorm —
                    // a plain product with a bf16 result (the training backward's long-K dgrads)
         if (fp.g.out2 || (!res && ln)) return hipErrorInvalidValue;

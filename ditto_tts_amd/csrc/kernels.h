@@ -164,6 +164,7 @@ extern int g_fr_rot;     // gemm.hip: full-row kernel's K-loop rotation: 0 off, 
 // g_fr_tile (declared above): gemm.hip: full-row kernel's tile: 0 = rule, 64 = gemm_fr64.hip for every launch with K <= g_fr64_maxk, 128 = gemm_fr.hip
 // g_fr64_maxk (declared below): gemm.hip: longest K that takes the 64-row kernel when fr_tile = 64
 extern int g_fr_u_fp8;   // gemm.hip: test hook (ditto_set_option("fr_u_fp8")): ditto_gemm_ln_bf16 writes the LayerNorm output as fp8
+extern int g_fr_hb;     // gemm.hip: test hook (ditto_set_option("fr_hb")): ditto_gemm_ln_bf16 reads the residual and writes h as bf16 (gemm_frd.hip's bf16 stream form)
 extern int g_fr_stagger; // gemm.hip: gemm_fr64's start delay of the second workgroup of a CU (10 ns ticks)
 extern int g_fr64_maxk;
 // The kernel a full-row LAUNCH of M rows and depth K runs on: 130 = gemm_frd.hip (W straight into registers: the N = 768

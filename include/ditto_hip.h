@@ -407,6 +407,8 @@ int ditto_gemm_tn_bf16(const void* X, int ldx, const void* Y, int ldy, float* ou
  * kernel, 10 ns ticks.  (N = 1024 always runs csrc/gemm_fr64.hip.)
  * "fr_u_fp8": TEST HOOK: ditto_gemm_ln_bf16 at N = 1024 writes u as fp8 e4m3 bytes ([M, ldu] bytes), the form the fp8 linear
  * path's model forward uses for norm3.
+ * "fr_hb": TEST HOOK: ditto_gemm_ln_bf16 at N = 768 takes `residual` and `out` as bf16 [M, ldo] (ldo % 8 == 0, 16-byte aligned):
+ * the 128-row kernel's bf16 residual stream form, which the model path runs (launches the 64-row kernel would take are an error).
  * "fr_dgrad": training backward, the long-K dgrads (N = d = 768) on the same kernel: bit 0 = fc1|gate (K = 8d), bit 1 = QKV.
  * "train_flags": training-step A/B switches: bit 0 = the backward of the self-attention rotation (RoPE) as its own pass over
  * dq | dk instead of inside the attention backward's dq / dk epilogues (head_dim 64; other head dims always take the pass);
