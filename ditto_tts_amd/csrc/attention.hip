@@ -54,9 +54,6 @@ namespace {
 
 #include "attn64v2.h"   // constants + attn64v2_kernel
 
-template <int V>
-struct IC1 { static constexpr int value = V; };
-
 // __launch_bounds__(256, 2): 2 waves per SIMD => a 256-register budget, so the MFMA accumulators (S^T, O^T: 64
 // registers) stay in VGPRs.  With the default budget hipcc parks them in AGPRs and moves all 64 through
 // v_accvgpr_read/write around every softmax (127 extra VALU per tile, as much as the softmax itself).
@@ -550,7 +547,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn64v3_kernel(AttnParams p) {
     };
 
     // ---- prologue: tiles 0, 1 in flight; scores of tile 0; its maximum becomes the running maximum ----
-    using T = IC1<1>; using F = IC1<0>;
+    using T = IntC<1>; using F = IntC<0>;
     dma_next(); dma_next();
     wait_tile(0);
     dma_next();                                                     // tile 2

@@ -39,6 +39,15 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 constexpr int WAVE = 64;
 
+// An integer as a TYPE: what a generic lambda takes where it needs a compile-time constant (decltype(X)::value), e.g. an
+// instruction immediate or an index into register arrays that must never become a run-time index.
+template <int V>
+struct IntC { static constexpr int value = V; };
+
+// Workgroup barrier WITHOUT the s_waitcnt vmcnt(0) lgkmcnt(0) that __syncthreads() puts in front of it: the hand-scheduled
+// kernels count their own waits and keep loads in flight across it.
+#define DITTO_BAR() asm volatile("s_barrier" ::: "memory")
+
 // Wave-wide sum / maximum, the total in every lane.  Round 5: on the cross-lane paths of the VECTOR pipe (DPP quad permutes and row
 // mirrors, two row broadcasts, one v_readlane) instead of six ds_bpermute round trips through the LDS: the fused norm2 + q-projection
 // kernel normalises its 64 rows at ONE wave per SIMD, where each of its 32 reductions per wave was a chain of six ~120-cycle LDS

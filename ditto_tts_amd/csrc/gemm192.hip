@@ -25,11 +25,6 @@ constexpr int B_BYTES = 192 * 64 * 2;            // 24 KiB
 constexpr int KT192 = 2 * H_BYTES + B_BYTES;     // 56 KiB
 constexpr int LDS192 = 2 * KT192;                // 112 KiB
 
-template <int V>
-struct IC192 { static constexpr int value = V; };
-
-#define DITTO_BAR() asm volatile("s_barrier" ::: "memory")
-
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm192_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(512, 2) void gemm192_kernel(GemmParams p) {
             stage_a(1, 1, to);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             DITTO_BAR();
-            mma(IC192<0>{});
+            mma(IntC<0>{});
             DITTO_BAR();
 
             read_A(0, 1);
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(512, 2) void gemm192_kernel(GemmParams p) {
             wait_dma(te + 2 < nkt);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             DITTO_BAR();
-            mma(IC192<1>{});
+            mma(IntC<1>{});
             DITTO_BAR();
 
             read_B(1);
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(512, 2) void gemm192_kernel(GemmParams p) {
             stage_a(0, 1, te + 2);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             DITTO_BAR();
-            if (odd_valid) mma(IC192<0>{});
+            if (odd_valid) mma(IntC<0>{});
             DITTO_BAR();
 
             read_A(1, 1);
@@ -187,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void gemm192_kernel(GemmParams p) {
             wait_dma(to + 2 < nkt);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             DITTO_BAR();
-            if (odd_valid) mma(IC192<1>{});
+            if (odd_valid) mma(IntC<1>{});
             DITTO_BAR();
         }
         if (wm == 0) DITTO_BAR();  // balance the stagger barrier

@@ -45,11 +45,6 @@ constexpr int KT_BYTES = 4 * HALF_BYTES;  // 64 KiB: A_lo | A_hi | B_lo | B_hi
 constexpr int LDS256 = 2 * KT_BYTES;      // 128 KiB
 constexpr int LDS256_ALLOC = LDS256 + 4 * 1024;   // + two (bias row, fp8 weight-scale row) pairs of 256 fp32, double-buffered by tile
 
-template <int V>
-struct IC { static constexpr int value = V; };
-
-#define DITTO_BAR() asm volatile("s_barrier" ::: "memory")
-
 #ifdef DITTO_DIAG_G256_STAMP   // tools/build_diag.sh: where does a tile spend its cycles?  (s_memtime stamps; timing build only)
 constexpr int G256_STAMP_WAVES = 4096;
 __device__ unsigned long long g_g256_stamps[G256_STAMP_WAVES * 8];   // per wave: tile start | main loop | end barrier + prologue | epilogue | tiles | 1
@@ -195,12 +190,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
         n0 = tn * 256;
         if constexpr (FLAT) set_bases(m0, n0, 0);
         stage_bias(n0);
-        stage(0, IC<2>{}, 0);
-        stage(0, IC<3>{}, 0);
-        stage(0, IC<0>{}, 0);
-        stage(0, IC<1>{}, 0);
-        stage(1, IC<2>{}, 1);
-        stage(1, IC<3>{}, 1);
+        stage(0, IntC<2>{}, 0);
+        stage(0, IntC<3>{}, 0);
+        stage(0, IntC<0>{}, 0);
+        stage(0, IntC<1>{}, 0);
+        stage(1, IntC<2>{}, 1);
+        stage(1, IntC<3>{}, 1);
     };
 
     // ---- fragment addressing ----
@@ -388,11 +383,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
             for (int it = 0; it < niter; ++it) {
                 const int te = 2 * it, to = te + 1;
                 const bool odd_valid = to < nkt;
-                read_B(0, IC<0>{});
-                read_B(0, IC<1>{});
-                read_A(0, IC<0>{});
-                stage(1, IC<0>{}, to);
-                stage(1, IC<1>{}, to);
+                read_B(0, IntC<0>{});
+                read_B(0, IntC<1>{});
+                read_A(0, IntC<0>{});
+                stage(1, IntC<0>{}, to);
+                stage(1, IntC<1>{}, to);
                 if constexpr (FLAT) {
                     if (it == niter - 1 && next < ntiles) {   // wave-uniform, once per tile: from here on the stage calls feed the NEXT tile
                         m0 = __builtin_amdgcn_readfirstlane(nm0v);
@@ -403,42 +398,42 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 DITTO_BAR();
-                mma(IC<0>{}, IC<0>{});
-                mma(IC<0>{}, IC<1>{});
+                mma(IntC<0>{}, IntC<0>{});
+                mma(IntC<0>{}, IntC<1>{});
                 DITTO_BAR();
 
-                read_A(0, IC<1>{});
-                stage(0, IC<2>{}, te + 2);
-                stage(0, IC<3>{}, te + 2);
+                read_A(0, IntC<1>{});
+                stage(0, IntC<2>{}, te + 2);
+                stage(0, IntC<3>{}, te + 2);
                 wait_dma(te + 2 < (FLAT ? klim : nkt));
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 DITTO_BAR();
-                mma(IC<1>{}, IC<1>{});
-                mma(IC<1>{}, IC<0>{});
+                mma(IntC<1>{}, IntC<1>{});
+                mma(IntC<1>{}, IntC<0>{});
                 DITTO_BAR();
 
-                read_B(1, IC<0>{});
-                read_B(1, IC<1>{});
-                read_A(1, IC<0>{});
-                stage(0, IC<0>{}, te + 2);
-                stage(0, IC<1>{}, te + 2);
+                read_B(1, IntC<0>{});
+                read_B(1, IntC<1>{});
+                read_A(1, IntC<0>{});
+                stage(0, IntC<0>{}, te + 2);
+                stage(0, IntC<1>{}, te + 2);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 DITTO_BAR();
                 if (odd_valid) {
-                    mma(IC<0>{}, IC<0>{});
-                    mma(IC<0>{}, IC<1>{});
+                    mma(IntC<0>{}, IntC<0>{});
+                    mma(IntC<0>{}, IntC<1>{});
                 }
                 DITTO_BAR();
 
-                read_A(1, IC<1>{});
-                stage(1, IC<2>{}, to + 2);
-                stage(1, IC<3>{}, to + 2);
+                read_A(1, IntC<1>{});
+                stage(1, IntC<2>{}, to + 2);
+                stage(1, IntC<3>{}, to + 2);
                 wait_dma(to + 2 < (FLAT ? klim : nkt));
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 DITTO_BAR();
                 if (odd_valid) {
-                    mma(IC<1>{}, IC<1>{});
-                    mma(IC<1>{}, IC<0>{});
+                    mma(IntC<1>{}, IntC<1>{});
+                    mma(IntC<1>{}, IntC<0>{});
                 }
                 DITTO_BAR();
             }
@@ -447,55 +442,55 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
                 const int te = 2 * it, to = te + 1;
                 const bool odd_valid = to < nkt;
                 // ---------------- K-tile te from buffer 0 ----------------
-                read_B(0, IC<0>{});
-                read_A(0, IC<0>{});
-                stage(1, IC<0>{}, to);                    // P1: o.A_lo   (buffer 1's A halves were last read in P7)
+                read_B(0, IntC<0>{});
+                read_A(0, IntC<0>{});
+                stage(1, IntC<0>{}, to);                    // P1: o.A_lo   (buffer 1's A halves were last read in P7)
                 DITTO_BAR();
-                mma(IC<0>{}, IC<0>{});
-                DITTO_BAR();
-
-                read_B(0, IC<1>{});
-                stage(1, IC<1>{}, to);                    // P2: o.A_hi
-                DITTO_BAR();
-                mma(IC<0>{}, IC<1>{});
+                mma(IntC<0>{}, IntC<0>{});
                 DITTO_BAR();
 
-                read_A(0, IC<1>{});                       // P3: no DMA
+                read_B(0, IntC<1>{});
+                stage(1, IntC<1>{}, to);                    // P2: o.A_hi
                 DITTO_BAR();
-                mma(IC<1>{}, IC<1>{});
+                mma(IntC<0>{}, IntC<1>{});
                 DITTO_BAR();
 
-                stage(0, IC<2>{}, te + 2);                // P4: e.B_lo + e.B_hi (buffer 0's B halves were last read in P2)
-                stage(0, IC<3>{}, te + 2);
+                read_A(0, IntC<1>{});                       // P3: no DMA
+                DITTO_BAR();
+                mma(IntC<1>{}, IntC<1>{});
+                DITTO_BAR();
+
+                stage(0, IntC<2>{}, te + 2);                // P4: e.B_lo + e.B_hi (buffer 0's B halves were last read in P2)
+                stage(0, IntC<3>{}, te + 2);
                 wait_dma(te + 2 < nkt);                   // buffer 1 (tile to: issued P8, P1, P2) has landed
                 DITTO_BAR();
-                mma(IC<1>{}, IC<0>{});
+                mma(IntC<1>{}, IntC<0>{});
                 DITTO_BAR();
 
                 // ---------------- K-tile to from buffer 1 ----------------
-                read_B(1, IC<0>{});
-                read_A(1, IC<0>{});
-                stage(0, IC<0>{}, te + 2);                // P5: e.A_lo   (buffer 0's A halves were last read in P3)
+                read_B(1, IntC<0>{});
+                read_A(1, IntC<0>{});
+                stage(0, IntC<0>{}, te + 2);                // P5: e.A_lo   (buffer 0's A halves were last read in P3)
                 DITTO_BAR();
-                if (odd_valid) mma(IC<0>{}, IC<0>{});
-                DITTO_BAR();
-
-                read_B(1, IC<1>{});
-                stage(0, IC<1>{}, te + 2);                // P6: e.A_hi
-                DITTO_BAR();
-                if (odd_valid) mma(IC<0>{}, IC<1>{});
+                if (odd_valid) mma(IntC<0>{}, IntC<0>{});
                 DITTO_BAR();
 
-                read_A(1, IC<1>{});                       // P7: no DMA
+                read_B(1, IntC<1>{});
+                stage(0, IntC<1>{}, te + 2);                // P6: e.A_hi
                 DITTO_BAR();
-                if (odd_valid) mma(IC<1>{}, IC<1>{});
+                if (odd_valid) mma(IntC<0>{}, IntC<1>{});
                 DITTO_BAR();
 
-                stage(1, IC<2>{}, to + 2);                // P8: o.B_lo + o.B_hi of the next odd tile
-                stage(1, IC<3>{}, to + 2);
+                read_A(1, IntC<1>{});                       // P7: no DMA
+                DITTO_BAR();
+                if (odd_valid) mma(IntC<1>{}, IntC<1>{});
+                DITTO_BAR();
+
+                stage(1, IntC<2>{}, to + 2);                // P8: o.B_lo + o.B_hi of the next odd tile
+                stage(1, IntC<3>{}, to + 2);
                 wait_dma(to + 2 < nkt);                   // buffer 0 (tile te+2: issued P4, P5, P6) has landed
                 DITTO_BAR();
-                if (odd_valid) mma(IC<1>{}, IC<0>{});
+                if (odd_valid) mma(IntC<1>{}, IntC<0>{});
                 DITTO_BAR();
             }
         }
@@ -592,8 +587,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
                                   // if the epilogue segment does not grow, the matrix pipe is free under it and the restructure
                                   // could hide one K-tile of twelve; if it grows by what the MFMAs take, there is nothing to win.
                 if constexpr (!FP8) {
-                    read_B(0, IC<0>{});
-                    read_B(0, IC<1>{});
+                    read_B(0, IntC<0>{});
+                    read_B(0, IntC<1>{});
                     f32x4 dacc[2][4];
 #pragma unroll
                     for (int i = 0; i < 2; ++i)

@@ -484,7 +484,8 @@ hipError_t launch_gemm_p128(const GemmParams& p, GemmEpilogue epi, hipStream_t s
 // gemm192.hip
 bool gemm192_supports(GemmEpilogue epi);
 hipError_t launch_gemm192(const GemmParams& p, GemmEpilogue epi, hipStream_t s);
-// gemm_fr.hip / gemm_fr64.hip: full-row N = 768 GEMM, fp32 residual in place, fused LayerNorm -> u bf16 (gamma/u null: none)
+// The full-row GEMMs (N = d = 768 or 1024): residual in place, fused LayerNorm -> u (gamma / u null: none).  gemm_fr.hip
+// dispatches to gemm_frd.hip and gemm_fr64.hip; what those two and gemm_lnq.hip share is in fr_common.h.
 struct FrParams {
     GemmParams g;
     const float* gamma; const float* beta;   // LayerNorm affine of the fused norm (null: no LayerNorm output)
@@ -498,15 +499,15 @@ bool gemm_fr_supports(int M, int N, int K, size_t lda, size_t ldw);
 hipError_t launch_gemm_fr(const GemmParams& p, const float* gamma, const float* beta, void* u_bf16, int ldu, int rot_period,
                           hipStream_t s, bool u_fp8 = false, bool hb = false);   // u_fp8 (N = 1024 only): u is fp8 e4m3 bytes;
                                                                                  // hb: bf16 residual / out (gemm_frd only: else an error)
-// The two full-row launches of a DiT block over M rows of width d, each judged on the operand strides IT runs with (the
-// kernel builds 32-bit byte offsets from M * lda: fc2 reads A at lda = 4d).  One predicate for the inference forward, the
-// LayerNorm chaining decision and the training forward, so that the three cannot disagree.
-// gemm_fr64.hip: the same contract and the SAME BITS on 64-row tiles, two workgroups per CU (called by launch_gemm_fr)
+// gemm_fr64.hip: the same contract and the SAME h BITS on 64-row tiles, two workgroups per CU (called by launch_gemm_fr)
 hipError_t launch_gemm_fr64(const FrParams& fp, hipStream_t s);
 // gemm_frd.hip: the same contract at N = 768 with W fetched straight from L2 into registers (128-row tiles, wave-private W)
 hipError_t launch_gemm_frd(const FrParams& fp, hipStream_t s);
 bool gemm_fr64_supports(int M, int N, int K, size_t lda, size_t ldw);   // N = 768 or 1024
-// d = 768: gemm_fr.hip (or its bit-identical 64-row twin); d = 1024: gemm_fr64.hip only.
+// The two full-row launches of a DiT block over M rows of width d, each judged on the operand strides IT runs with (the
+// kernel builds 32-bit byte offsets from M * lda: fc2 reads A at lda = 4d).  One predicate for the inference forward, the
+// LayerNorm chaining decision and the training forward, so that the three cannot disagree.
+// d = 768: launch_gemm_fr's choice of gemm_frd.hip or gemm_fr64.hip; d = 1024: gemm_fr64.hip only.
 inline bool fr_outproj_ok(int M, int d) {
     if (d == 1024) return fr_pays_64(M) && gemm_fr64_supports(M, d, d, (size_t)d, (size_t)d);
     return fr_pays(M) && gemm_fr_supports(M, d, d, (size_t)d, (size_t)d);

@@ -1,10 +1,11 @@
 // gemm_fr64.hip — the full-row N = 768 GEMM with fused residual + LayerNorm (gemm_fr.hip) on 64-ROW tiles, TWO independent
-// workgroups per CU (gfx950).  Same contract, same weight layout, and the SAME BITS as gemm_fr.hip.
+// workgroups per CU (gfx950).  Same contract, same weight layout, and the SAME BITS as gemm_fr128.
 //
 //     h[M, 768] (fp32, in place) = residual + A[M, K] * W[768, K]^T + bias            (reference DiT.py:148, :155)
 //     u[M, 768] (bf16)           = LayerNorm(h) * gamma + beta   (eps 1e-5)           (reference DiT.py:152, :105)
 //
-// Why: gemm_fr.hip owns 128 rows per workgroup with one wave per SIMD, one workgroup per CU and (at M = 32768) one tile per
+// (gemm_fr128 = the 128-row kernel of rounds 2-5 with the weights through an LDS ring, deleted in round 6; gemm_frd.hip took its
+// place and keeps its h bits.)  Why: gemm_fr128 owned 128 rows per workgroup with one wave per SIMD, one workgroup per CU and (at M = 32768) one tile per
 // workgroup, so its phases — 100 MB of residual read, the MFMA loop, LayerNorm, 150 MB of stores — run one after the other,
 // chip-wide in lockstep: at K = 768 the MFMA loop is 27 % of the launch.  A 64 x 768 tile needs 192 accumulators per lane,
 // so two 4-wave workgroups fit a CU (256 registers and 80 KiB of LDS each) and the matrix pipe, the vector memory path and
@@ -15,8 +16,8 @@
 //
 //   tile      64 rows x 768 columns; 256 threads = 4 waves side by side in N: wave wn owns all 64 rows x columns
 //             [192 wn, +192) = 2 x 6 blocks of v_mfma_f32_32x32x16_bf16 = 192 accumulators, pinned by asm MFMAs: column
-//             blocks 0..NA-1 in AGPRs, the rest in VGPRs (hipcc cannot be trusted with them as values, gemm_fr.hip).
-//   operands  W stage-major packed Wp[K/16][768][16] (the gemm_fr.hip layout).  A wave DMAs exactly the 6 KiB of a K = 16
+//             blocks 0..NA-1 in AGPRs, the rest in VGPRs (hipcc cannot be trusted with them as values, fr_common.h).
+//   operands  W stage-major packed Wp[K/16][768][16] (the gemm_fr128 layout).  A wave DMAs exactly the 6 KiB of a K = 16
 //             stage that IT multiplies (its own 192 weight rows = 6 pieces of 1 KiB): the W ring is WAVE-PRIVATE, no
 //             barrier guards it, and piece nb of stage s+3 is issued into the bytes of piece nb of stage s right behind the
 //             MFMAs that consumed that fragment (three slots give 2-2.5 stages of look-ahead).  A (row-major, the
@@ -32,17 +33,17 @@
 //             nb = 3   : counted vmcnt (this wave's stage s+1 has landed) ; j = 1: s_barrier (everyone's piece of the next
 //                        slab has landed, everyone is done reading this one) + this wave's piece of the slab after next ;
 //                        A fragments of stage s+1 ; then as nb = 0..2, W fragments now from stage s+1
-//   bits      the K loop starts where gemm_fr.hip's does for the 128-row tile these rows belong to (rot_period), the
+//   bits      the K loop starts where gemm_fr128's does for the 128-row tile these rows belong to (rot_period), the
 //             accumulators start as residual + bias, and the LayerNorm statistics are summed in the same association
 //             (per lane ONE chain over a half row — the odd wave of a pair continues the even wave's partial —, + lane ^ 32,
 //             half 0 + half 1): h and u are bit-identical to
-//             gemm_fr.hip's (tests/test_gpu_kernels.py), so the choice between the two kernels is not a numerics class.
+//             gemm_fr128's (tests/test_gpu_kernels.py), so the choice between the two kernels is not a numerics class.
 //
 // d = 1024 (BASELINE config C5): the same kernel with NBW = 8 column blocks per wave — a 64 x 1024 tile, 256 accumulators per
 // lane (all in AGPRs), ONE workgroup per CU with the whole register file, a W ring of FOUR 32-KiB stages (136 KiB of LDS),
 // DMA four stages ahead.  M = 16 x 1024 rows make exactly one tile per CU.  There is no 128-row kernel at this width, so
 // nothing pins its bits; U8 = the LayerNorm output as fp8 e4m3 (saturating) for the fp8 linear path's next GEMM.
-#include "gemm_common.h"
+#include "fr_common.h"
 
 namespace ditto {
 
@@ -73,34 +74,6 @@ template <int NBW> struct FH {
     static_assert(RED + 3 * 2 * HM * 4 <= WRING, "epilogue overlays fit the idle W ring");
 };
 
-#ifdef DITTO_DIAG_FR_NOSTORE
-#define FH_DIAG_M (p.M - (1 << 30))
-#else
-#define FH_DIAG_M p.M
-#endif
-#define FH_BAR() asm volatile("s_barrier" ::: "memory")
-#define FH_PIN_A(x) asm volatile("" : "+a"(x))
-#define FH_PIN_V(x) asm volatile("" : "+v"(x))
-
-template <int V>
-struct HC { static constexpr int value = V; };
-
-DITTO_DEV void hmfma_a(f32x16& c, const bf16x8& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
-}
-DITTO_DEV void hmfma_v(f32x16& c, const bf16x8& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(a));
-}
-// The LAST MFMA of an accumulator chain carries its own wait states: an 8-pass MFMA's result may be read by anything but
-// the next MFMA of its chain only 11 cycles after issue, hipcc pads nothing behind an asm producer, and it DID place the
-// spill of a just-written block between two MFMA statements (ahead of a separate s_nop statement: wrong lanes in u).
-DITTO_DEV void hmfma_a_last(f32x16& c, const bf16x8& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\ts_nop 15" : "+a"(c) : "v"(w), "v"(a));
-}
-DITTO_DEV void hmfma_v_last(f32x16& c, const bf16x8& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\ts_nop 15" : "+v"(c) : "v"(w), "v"(a));
-}
-
 template <int NBW, bool LN, bool RES, bool U8>
 __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams fp) {
     constexpr int HN = FH<NBW>::HN, HNS = FH<NBW>::HNS, H_W_BYTES = FH<NBW>::W_BYTES, H_WRING = FH<NBW>::WRING;
@@ -114,10 +87,9 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
     const int nkt = p.K / HK;                                        // a multiple of 4 (K % 64 == 0)
     const int nslab = nkt >> 1;                                      // 32-k slabs
     // XCD-contiguous tiles (workgroups go to the XCDs round-robin): the 64 workgroups of an XCD hold neighbouring rows
-    const int ntile = gridDim.x;
-    const int tile = (ntile & 7) == 0 ? (int)(blockIdx.x & 7) * (ntile >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int tile = fr_xcd_tile();
     const int m0 = tile * HM;
-    // K-loop rotation exactly as gemm_fr.hip applies it to the 128-row tile these 64 rows belong to (same sums, same bits)
+    // K-loop rotation exactly as gemm_fr128 applies it to the 128-row tile these 64 rows belong to (same sums, same bits)
     const int nslab64 = nkt >> 2;
     const int s0 = fp.rot_period > 0 ? ((((tile >> 1) % fp.rot_period) & 7) * nslab64) >> 3 : 0;   // in 64-k units
     const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
@@ -151,7 +123,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
     unsigned a_buf = lds_base + H_ARING + (unsigned)(wid * 1024); // ... and of this wave's piece in the buffer the next slab goes to
     auto dma = [&](unsigned voff, const char* base, unsigned dst) {
 #ifndef DITTO_DIAG_FR_NODMA
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
+        fr_dma(voff, base, dst);
 #endif
     };
     auto issue_w_piece = [&](auto I) {
@@ -170,21 +142,16 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
         vak += a_left == 0 ? 64u - (unsigned)nslab * 64u : 64u;
     };
     auto issue_w_stage = [&]() {
-        issue_w_piece(HC<0>{}); issue_w_piece(HC<1>{}); issue_w_piece(HC<2>{});
-        issue_w_piece(HC<3>{}); issue_w_piece(HC<4>{}); issue_w_piece(HC<5>{});
-        if constexpr (NBW == 8) { issue_w_piece(HC<6>{}); issue_w_piece(HC<7>{}); }
+        issue_w_piece(IntC<0>{}); issue_w_piece(IntC<1>{}); issue_w_piece(IntC<2>{});
+        issue_w_piece(IntC<3>{}); issue_w_piece(IntC<4>{}); issue_w_piece(IntC<5>{});
+        if constexpr (NBW == 8) { issue_w_piece(IntC<6>{}); issue_w_piece(IntC<7>{}); }
         advance_w();
     };
 
     // bias row -> the last ring slot (N fp32 = 3 / 4 pieces of 1 KiB): the oldest loads of the kernel
     if (wid == 0) {
-        if (p.bias) {
-#pragma unroll
-            for (int i = 0; i < NBP; ++i) glds16(p.bias + i * 256 + lane * 4, lds_base + (unsigned)(H_BIAS + i * 1024));
-        } else {
-#pragma unroll
-            for (int i = 0; i < NBP; ++i) *reinterpret_cast<f32x4*>(smem + H_BIAS + i * 1024 + lane * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        if (p.bias) fr_stage_row<NBP>(p.bias, lds_base, H_BIAS, lane);
+        else fr_zero_row<NBP>(smem, H_BIAS, lane);
     }
     // ---- fragment addressing: lane reads row (lane & 31) of a 32-row block, 16-B half (lane >> 5) ----
     const int r32 = lane & 31, hh = lane >> 5;
@@ -198,7 +165,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
     issue_w_stage(); issue_w_stage();
     if constexpr (HNS == 4) issue_w_stage();
 
-    // ---- the accumulators START as bias + residual (gemm_fr.hip: the epilogue then only READS them).  48 hand-written
+    // ---- the accumulators START as bias + residual (the epilogue then only READS them).  48 hand-written
     //      global_load_dwordx4 per lane in the accumulator layout, a window of two (N = 768) or four (N = 1024) 32 x 32 blocks in flight. ----
     const float* lbias = reinterpret_cast<const float*>(smem + H_BIAS);
     const float* lgamma = reinterpret_cast<const float*>(smem + H_GB);     // these two: valid in the epilogue only
@@ -219,14 +186,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
         auto issue_group = [&](auto GI, f32x4 (&t)[4]) {             // the 4 loads of block (nb, mb) = (GI / 2, GI % 2)
             constexpr int nb = decltype(GI)::value >> 1, mb = decltype(GI)::value & 1;
             if constexpr (RES) {
-                const float* ptr = rp[mb];
-                asm volatile("global_load_dwordx4 %0, %4, off offset:%5\n\t"
-                             "global_load_dwordx4 %1, %4, off offset:%6\n\t"
-                             "global_load_dwordx4 %2, %4, off offset:%7\n\t"
-                             "global_load_dwordx4 %3, %4, off offset:%8"
-                             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
-                             : "v"(ptr), "n"(nb * 128), "n"(nb * 128 + 32), "n"(nb * 128 + 64), "n"(nb * 128 + 96)
-                             : "memory");
+                fr_res_load<nb>(t, rp[mb]);
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) t[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -236,38 +196,32 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
             constexpr int gi = decltype(GI)::value, nb = gi >> 1, mb = gi & 1;
             constexpr int younger = NG - 1 - gi < WD - 1 ? NG - 1 - gi : WD - 1;   // groups issued after this one and still in flight
             if constexpr (RES)
-                asm volatile("s_waitcnt vmcnt(%4)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) : "n"(4 * younger) : "memory");
+                fr_res_wait<4 * younger>(t);
             if constexpr (gi == 0) {
                 if constexpr (!RES) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                FH_BAR();      // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
+                DITTO_BAR();      // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
             }
-            f32x16 v;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 b4 = *reinterpret_cast<const f32x4*>(lbias + wid * WCOLS + nb * 32 + 8 * g + 4 * hh);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[4 * g + e] = t[g][e] + b4[e];
-            }
-            if constexpr (nb < HNA) { acca[nb < HNA ? nb : 0][mb] = v; FH_PIN_A(acca[nb < HNA ? nb : 0][mb]); }
-            else { accv[nb < HNA ? 0 : nb - HNA][mb] = v; FH_PIN_V(accv[nb < HNA ? 0 : nb - HNA][mb]); }
+            const f32x16 v = fr_acc_init(t, lbias + wid * WCOLS + nb * 32 + 4 * hh);
+            if constexpr (nb < HNA) { acca[nb < HNA ? nb : 0][mb] = v; fr_pin(InAgpr{}, acca[nb < HNA ? nb : 0][mb]); }
+            else { accv[nb < HNA ? 0 : nb - HNA][mb] = v; fr_pin(InVgpr{}, accv[nb < HNA ? 0 : nb - HNA][mb]); }
             __builtin_amdgcn_sched_barrier(0);
         };
         auto init_step = [&](auto GI) {
             constexpr int gi = decltype(GI)::value;
             finish_group(GI, T[gi % WD]);
-            if constexpr (gi + WD < NG) issue_group(HC<gi + WD>{}, T[gi % WD]);
+            if constexpr (gi + WD < NG) issue_group(IntC<gi + WD>{}, T[gi % WD]);
         };
-        issue_group(HC<0>{}, T[0]); issue_group(HC<1>{}, T[1]);
-        if constexpr (WD == 4) { issue_group(HC<2>{}, T[2]); issue_group(HC<3>{}, T[3]); }
-        init_step(HC<0>{}); init_step(HC<1>{}); init_step(HC<2>{}); init_step(HC<3>{}); init_step(HC<4>{}); init_step(HC<5>{});
-        init_step(HC<6>{}); init_step(HC<7>{}); init_step(HC<8>{}); init_step(HC<9>{}); init_step(HC<10>{}); init_step(HC<11>{});
-        if constexpr (NBW == 8) { init_step(HC<12>{}); init_step(HC<13>{}); init_step(HC<14>{}); init_step(HC<15>{}); }
+        issue_group(IntC<0>{}, T[0]); issue_group(IntC<1>{}, T[1]);
+        if constexpr (WD == 4) { issue_group(IntC<2>{}, T[2]); issue_group(IntC<3>{}, T[3]); }
+        init_step(IntC<0>{}); init_step(IntC<1>{}); init_step(IntC<2>{}); init_step(IntC<3>{}); init_step(IntC<4>{}); init_step(IntC<5>{});
+        init_step(IntC<6>{}); init_step(IntC<7>{}); init_step(IntC<8>{}); init_step(IntC<9>{}); init_step(IntC<10>{}); init_step(IntC<11>{});
+        if constexpr (NBW == 8) { init_step(IntC<12>{}); init_step(IntC<13>{}); init_step(IntC<14>{}); init_step(IntC<15>{}); }
     }
 
     // slabs 0, 1 and W stages 0, 1 have landed for this wave (older than the residual loads); for everyone, and everyone is
     // done with the bias row in slot 2:
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    FH_BAR();
+    DITTO_BAR();
     issue_w_stage();             // the W stage whose slot held the bias row (nkt >= 4)
     unsigned c_off = 0;          // W ring byte offset of the stage being multiplied
     unsigned a_cur = H_ARING;    // byte offset of the A slab being multiplied
@@ -297,7 +251,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(vm) : "memory");
                 if constexpr (j == 1) {
 #ifndef DITTO_DIAG_FR_NOBAR
-                    FH_BAR();
+                    DITTO_BAR();
 #endif
                     if constexpr (do_a) { issue_a_piece(); advance_a(); }
                 }
@@ -311,23 +265,23 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb) {
                 if constexpr (has_next) {
-                    if (nb < HNA) hmfma_a(acca[nb < HNA ? nb : 0][mb], wf[G & 3], ACUR[mb]);
-                    else hmfma_v(accv[nb < HNA ? 0 : nb - HNA][mb], wf[G & 3], ACUR[mb]);
-                } else {   // LAST stage: the final writes of the block's accumulators
-                    if (nb < HNA) hmfma_a_last(acca[nb < HNA ? nb : 0][mb], wf[G & 3], ACUR[mb]);
-                    else hmfma_v_last(accv[nb < HNA ? 0 : nb - HNA][mb], wf[G & 3], ACUR[mb]);
+                    if (nb < HNA) fr_mfma(InAgpr{}, acca[nb < HNA ? nb : 0][mb], wf[G & 3], ACUR[mb]);
+                    else fr_mfma(InVgpr{}, accv[nb < HNA ? 0 : nb - HNA][mb], wf[G & 3], ACUR[mb]);
+                } else {   // LAST stage: the final writes of the block's accumulators, with their wait states (fr_mfma_last)
+                    if (nb < HNA) fr_mfma_last(InAgpr{}, acca[nb < HNA ? nb : 0][mb], wf[G & 3], ACUR[mb]);
+                    else fr_mfma_last(InVgpr{}, accv[nb < HNA ? 0 : nb - HNA][mb], wf[G & 3], ACUR[mb]);
                 }
             }
             if constexpr (do_w) {
-                if (nb == 0) issue_w_piece(HC<0>{});
-                if (nb == 1) issue_w_piece(HC<1>{});
-                if (nb == 2) issue_w_piece(HC<2>{});
-                if (nb == 3) issue_w_piece(HC<3>{});
-                if (nb == 4) issue_w_piece(HC<4>{});
-                if (nb == 5) issue_w_piece(HC<5>{});
+                if (nb == 0) issue_w_piece(IntC<0>{});
+                if (nb == 1) issue_w_piece(IntC<1>{});
+                if (nb == 2) issue_w_piece(IntC<2>{});
+                if (nb == 3) issue_w_piece(IntC<3>{});
+                if (nb == 4) issue_w_piece(IntC<4>{});
+                if (nb == 5) issue_w_piece(IntC<5>{});
                 if constexpr (NBW == 8) {
-                    if (nb == 6) issue_w_piece(HC<6>{});
-                    if (nb == 7) issue_w_piece(HC<7>{});
+                    if (nb == 6) issue_w_piece(IntC<6>{});
+                    if (nb == 7) issue_w_piece(IntC<7>{});
                 }
             }
         }
@@ -338,17 +292,17 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
     // all slabs but the last two: full issue (the waits leave 10 / 9 loads in flight); then the last four stages, in which
     // the issue stops
     for (int sl = 0; sl + 2 < nslab; ++sl) {
-        stage(HC<0>{}, HC<1>{}, HC<1>{}, HC<1>{}, HC<FH<NBW>::VM0>{}, a0, a1);
-        stage(HC<1>{}, HC<1>{}, HC<1>{}, HC<1>{}, HC<FH<NBW>::VM1>{}, a1, a0);
+        stage(IntC<0>{}, IntC<1>{}, IntC<1>{}, IntC<1>{}, IntC<FH<NBW>::VM0>{}, a0, a1);
+        stage(IntC<1>{}, IntC<1>{}, IntC<1>{}, IntC<1>{}, IntC<FH<NBW>::VM1>{}, a1, a0);
     }
-    stage(HC<0>{}, HC<FH<NBW>::T4_ISSUES_W>{}, HC<0>{}, HC<1>{}, HC<FH<NBW>::VMT4>{}, a0, a1);   // stage nkt-4 (3-slot ring: issues W stage nkt-1)
-    stage(HC<1>{}, HC<0>{}, HC<0>{}, HC<1>{}, HC<FH<NBW>::VMT3>{}, a1, a0);                       // stage nkt-3
-    stage(HC<0>{}, HC<0>{}, HC<0>{}, HC<1>{}, HC<0>{}, a0, a1);    // stage nkt-2
-    stage(HC<1>{}, HC<0>{}, HC<0>{}, HC<0>{}, HC<0>{}, a1, a0);    // stage nkt-1
+    stage(IntC<0>{}, IntC<FH<NBW>::T4_ISSUES_W>{}, IntC<0>{}, IntC<1>{}, IntC<FH<NBW>::VMT4>{}, a0, a1);   // stage nkt-4 (3-slot ring: issues W stage nkt-1)
+    stage(IntC<1>{}, IntC<0>{}, IntC<0>{}, IntC<1>{}, IntC<FH<NBW>::VMT3>{}, a1, a0);                       // stage nkt-3
+    stage(IntC<0>{}, IntC<0>{}, IntC<0>{}, IntC<1>{}, IntC<0>{}, a0, a1);    // stage nkt-2
+    stage(IntC<1>{}, IntC<0>{}, IntC<0>{}, IntC<0>{}, IntC<0>{}, a1, a0);    // stage nkt-1
 
     // ---------------- epilogue: the accumulators hold h = residual + bias + A W^T; they are only READ from here on ----------------
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    FH_BAR();                                                       // every wave is out of the main loop: ring and A buffers idle
+    DITTO_BAR();                                                       // every wave is out of the main loop: ring and A buffers idle
     float mean[2] = {0.f, 0.f}, rstd[2] = {1.f, 1.f};
     if constexpr (LN) {
         // gamma and beta rows -> the idle ring (3 pieces of 1 KiB each), landed by the first exchange below
@@ -357,11 +311,11 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
 #pragma unroll
             for (int i = 0; i < NBP; ++i) glds16(src + i * 256 + lane * 4, lds_base + (unsigned)(H_GB + wid * HN * 4 + i * 1024));
         }
-        // Row statistics in gemm_fr.hip's association, bit for bit: there ONE lane sums the 12 column blocks of a half row in
+        // Row statistics in gemm_fr128's association, bit for bit: there ONE lane sums the 12 column blocks of a half row in
         // one sequential chain; here a half row is split over waves 2 p (blocks 0..5) and 2 p + 1 (blocks 6..11), so the odd
         // wave CONTINUES the even wave's per-lane partial (handed over through LDS: 512 B per pair), then lane + lane ^ 32,
         // then half 0 + half 1.  Two barriers per pass; the odd waves idle for ~100 VALU instructions per pass.
-        // The fused forms are written out: gemm_fr.hip's compiler-contracted ones are v - sum / 768 as ONE fma in the variance
+        // The fused forms are written out: gemm_fr128's compiler-contracted ones are v - sum / 768 as ONE fma in the variance
         // pass, the rounded mean in the output pass, fma(sum, 1 / 768, eps) under the rsqrt (contraction depends on basic-block
         // structure, which differs here).
         float rsum[2] = {0.f, 0.f};
@@ -372,15 +326,10 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
             for (int nb = 0; nb < NBW; ++nb)
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb) {
-                    // re-pin the block in its home file: the copy below is then a NEW value that cannot be hoisted above this
-                    // statement (un-pinned, hipcc read four AGPR blocks into VGPRs at once right behind the barrier)
-                    if (nb < HNA) FH_PIN_A(acca[nb < HNA ? nb : 0][mb]); else FH_PIN_V(accv[nb < HNA ? 0 : nb - HNA][mb]);
+                    // re-pin the block in its home file: the copy below is then a NEW value that cannot be hoisted above this (fr_common.h fr_pin)
+                    if (nb < HNA) fr_pin(InAgpr{}, acca[nb < HNA ? nb : 0][mb]); else fr_pin(InVgpr{}, accv[nb < HNA ? 0 : nb - HNA][mb]);
                     const f32x16 v = nb < HNA ? acca[nb < HNA ? nb : 0][mb] : accv[nb < HNA ? 0 : nb - HNA][mb];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        if constexpr (decltype(PASS)::value == 0) c2[mb] += v[e];
-                        else { const float dl = fmaf(rsum[mb], -(1.0f / HN), v[e]); c2[mb] = fmaf(dl, dl, c2[mb]); }
-                    }
+                    fr_row_acc<decltype(PASS)::value, HN>(c2[mb], v, rsum[mb]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
         };
@@ -406,7 +355,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
             }
             __syncthreads();
         };
-        row_reduce(HC<0>{});
+        row_reduce(IntC<0>{});
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
             const int r = mb * 32 + r32;
@@ -415,14 +364,14 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
             asm volatile("" : "+v"(mean[mb]));                        // the ROUNDED mean, never re-fused into a consumer
         }
         __syncthreads();                                              // everyone has read the sums before the next pass overwrites them
-        row_reduce(HC<1>{});
+        row_reduce(IntC<1>{});
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
             const int r = mb * 32 + r32;
             rstd[mb] = rsqrtf(fmaf(red[r] + red[HM + r], 1.0f / HN, 1e-5f));
         }
     }
-    // stores (gemm_fr.hip): every output row leaves through a wave-private LDS stage so that the stores are whole 128-B
+    // stores: every output row leaves through a wave-private LDS stage so that the stores are whole 128-B
     // lines: h fp32 (nt), u = LN(h) bf16, optional bf16 copy of h.
     const int cl = wid * WCOLS + 4 * hh;                             // this lane's column origin; + nb * 32 + 8 g
     const float* gl = lgamma + cl;
@@ -440,7 +389,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
     for (int nb = 0; nb < NBW; ++nb) {
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-            if (nb < HNA) FH_PIN_A(acca[nb < HNA ? nb : 0][mb]); else FH_PIN_V(accv[nb < HNA ? 0 : nb - HNA][mb]);
+            if (nb < HNA) fr_pin(InAgpr{}, acca[nb < HNA ? nb : 0][mb]); else fr_pin(InVgpr{}, accv[nb < HNA ? 0 : nb - HNA][mb]);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -455,7 +404,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
                 const f32x16& v = nb < HNA ? acca[nb < HNA ? nb : 0][mb] : accv[nb < HNA ? 0 : nb - HNA][mb];
                 const f32x4 v4 = {v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
                 const int row = mb * 32 + r32;
-                *reinterpret_cast<f32x4*>(hst + row * 128 + (((2 * g + hh) ^ (row & 7)) << 4)) = v4;
+                fr_stage_f32(hst, row, g, hh, v4);
                 f32x4 y = v4;                                        // bf16 side: LayerNorm output, or the plain copy
                 if constexpr (LN) y = (v4 - mean[mb]) * rstd[mb] * g4 + b4;
                 if constexpr (U8) {
@@ -463,9 +412,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
                     *reinterpret_cast<unsigned*>(ust + row * 128 + ((((nb & 3) * 2 + (g >> 1)) ^ (row & 7)) << 4) + (g & 1) * 8 + hh * 4) =
                         pack_fp8x4(y[0], y[1], y[2], y[3]);
                 } else {
-                    u32x2 st;
-                    st[0] = pack_bf16x2(y[0], y[1]); st[1] = pack_bf16x2(y[2], y[3]);
-                    *reinterpret_cast<u32x2*>(ust + row * 128 + ((((nb & 1) * 4 + g) ^ (row & 7)) << 4) + hh * 8) = st;
+                    fr_stage_bf16(ust, row, nb, g, hh, y);
                 }
             }
         }
@@ -476,7 +423,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
             for (int i = 4 * half; i < 4 * half + 4; ++i) {
                 const int row = srow + 8 * i;
                 const u32x4 hv = *reinterpret_cast<const u32x4*>(hst + row * 128 + ((sq ^ (row & 7)) << 4));
-                if (grow0 + 8 * i < FH_DIAG_M) store16<true, true>(hrow + (size_t)(8 * i) * p.ldo + nb * 32, hv, 0);   // nt (a run-time plain / nt switch here cost the K = 768 launch 5 us: the branch splits the store block; the A/B itself: no gain from plain stores)
+                if (grow0 + 8 * i < fr_store_m(p)) store16<true, true>(hrow + (size_t)(8 * i) * p.ldo + nb * 32, hv, 0);   // nt (a run-time plain / nt switch here cost the K = 768 launch 5 us: the branch splits the store block; the A/B itself: no gain from plain stores)
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -487,7 +434,7 @@ __global__ __launch_bounds__(256, FH<NBW>::WPE) void gemm_fr64_kernel(FrParams f
                 for (int i = 4 * half; i < 4 * half + 4; ++i) {
                     const int row = srow + 8 * i;
                     const u32x4 uv = *reinterpret_cast<const u32x4*>(ust + row * 128 + ((sq ^ (row & 7)) << 4));
-                    if (grow0 + 8 * i < FH_DIAG_M) {
+                    if (grow0 + 8 * i < fr_store_m(p)) {
                         if constexpr (U8) *reinterpret_cast<u32x4*>(u8row + (size_t)(8 * i) * fp.ldu + (nb - 3) * 32) = uv;
                         else if (LN) *reinterpret_cast<u32x4*>(urow + (size_t)(8 * i) * fp.ldu + (nb - 1) * 32) = uv;
                         else if (orow) *reinterpret_cast<u32x4*>(orow + (size_t)(8 * i) * p.ldo2 + (nb - 1) * 32) = uv;

@@ -4,7 +4,8 @@
 //     h[M, 768] (fp32, in place) = residual + A[M, K] * W[768, K]^T + bias            (reference DiT.py:148, :155)
 //     u[M, 768] (bf16)           = LayerNorm(h) * gamma + beta   (eps 1e-5)           (reference DiT.py:152, :105)
 //
-// Why: gemm_fr.hip's main loop runs at 0.55 us per K = 16 stage where its 24 MFMAs need 0.40: the 24 KiB of W per stage go
+// (gemm_fr128 = the 128-row kernel of rounds 2-5 with the weights through an LDS ring, deleted in round 6; it lived in gemm_fr.hip, now the
+// dispatcher.)  Why: gemm_fr128's main loop ran at 0.55 us per K = 16 stage where its 24 MFMAs need 0.40: the 24 KiB of W per stage go
 // L2 -> LDS by LDS-DMA (the path sustains ~52 GB/s per CU next to MFMAs and fragment reads) and come back out through 12
 // ds_read_b128 per wave and stage behind a barrier per stage.  The weights are packed stage-major, Wp[K/16][768][16], so the
 // 1 KiB of a (stage, 32-column block) piece is contiguous and lane (r32, hh) of a v_mfma_f32_32x32x16_bf16 operand wants
@@ -18,11 +19,11 @@
 //             loaded into the registers of fragment nb of stage s right behind the four MFMAs that consumed it.  Every
 //             fragment is waited for separately with a counted vmcnt (11 younger loads + the A pieces issued since: a
 //             compile-time constant per (slab position, nb)), so each load has its full two stages to land.
-//   A         shared by the four waves, through the LDS as in gemm_fr.hip: slabs of 64 k (128 rows x 128 B = 16 pieces of
+//   A         shared by the four waves, through the LDS as in gemm_fr128: slabs of 64 k (128 rows x 128 B = 16 pieces of
 //             1 KiB, 4 per wave, chunk c of row r at c ^ ((r >> 1) & 7)), double-buffered, ONE barrier per slab; 4
-//             ds_read_b128 per wave and stage (gemm_fr.hip: 14).
-//   K order   as gemm_fr.hip (rotation per 128-row tile included): h is bit-identical to gemm_fr.hip's.  The LayerNorm
-//             statistics are summed per quarter row ((q0 + q1) + (q2 + q3)), so u may differ from gemm_fr.hip's in the last
+//             ds_read_b128 per wave and stage (gemm_fr128: 14).
+//   K order   as gemm_fr128 (rotation per 128-row tile included): h is bit-identical to gemm_fr128's.  The LayerNorm
+//             statistics are summed per quarter row ((q0 + q1) + (q2 + q3)), so u may differ from gemm_fr128's in the last
 //             bf16 bit of a few elements.
 //   residual  bf16 stream (the model path): the tile's 192 KiB reach the accumulators THROUGH THE LDS — every wave fetches its own
 //             384 bytes of each row by LDS-DMA in whole 128-byte lines (48 pieces of 1 KiB per wave, two 32-row units in flight)
@@ -34,7 +35,7 @@
 //             statistics: 138 KiB.
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "fr_common.h"
 
 namespace ditto {
 
@@ -56,57 +57,21 @@ constexpr int D_RSTG = D_BIAS + DN * 4;
 constexpr int D_RUNIT = 32 * 384;                   // 12 KiB = 12 LDS-DMA pieces of 8 rows x 128 B
 static_assert(D_RSTG % 128 == 0 && D_RUNIT % 128 == 0 && D_RSTG + 4 * 2 * D_RUNIT <= D_LDS, "residual staging fits under the epilogue's");
 
-#ifdef DITTO_DIAG_FR_NOSTORE
-#define FD_DIAG_M (p.M - (1 << 30))
-#else
-#define FD_DIAG_M p.M
-#endif
-#define FD_BAR() asm volatile("s_barrier" ::: "memory")
-#define FD_PIN_A(x) asm volatile("" : "+a"(x))
-#define FD_PIN_V(x) asm volatile("" : "+v"(x))
-
-template <int V>
-struct DC { static constexpr int value = V; };
-
-DITTO_DEV void dmfma_a(f32x16& c, const f32x4& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
-}
-DITTO_DEV void dmfma_v(f32x16& c, const f32x4& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(a));
-}
-// last MFMA of a chain: its wait states inside the statement (hazard argument: gemm_fr.hip)
-DITTO_DEV void dmfma_a_last(f32x16& c, const f32x4& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\ts_nop 15" : "+a"(c) : "v"(w), "v"(a));
-}
-DITTO_DEV void dmfma_v_last(f32x16& c, const f32x4& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\ts_nop 15" : "+v"(c) : "v"(w), "v"(a));
-}
-
-// asm with operands lives in free functions: inside a generic lambda clang rejects asm operands that name captured locals
 template <int IMM>
 DITTO_DEV void frd_wload(f32x4& dst, unsigned voff, const char* base) {
 #ifndef DITTO_DIAG_FRD_NOW      // tools/build_diag.sh: the main loop without its W stream (timing only, wrong results)
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
+    fr_wload<IMM>(dst, voff, base);
 #else
     asm volatile("" : "+v"(dst) : "v"(voff), "s"(base));
 #endif
 }
-template <int VM>
-DITTO_DEV void frd_wait(f32x4& frag) {   // counted wait that ties the fragment's registers: no use moves above it
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(frag) : "n"(VM) : "memory");
-}
-DITTO_DEV void frd_dma(unsigned voff, const char* base, unsigned dst) {
+DITTO_DEV void frd_dma(unsigned voff, const char* base, unsigned dst) {   // fr_dma with the A stream's A/B switches
 #ifndef DITTO_DIAG_FR_NODMA
 #ifndef DITTO_FRD_A_POLICY     // A/B builds: cache policy of the A slab stream (tools/build_diag.sh -DDITTO_FRD_A_POLICY='"nt"')
 #define DITTO_FRD_A_POLICY ""
 #endif
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 " DITTO_FRD_A_POLICY ::"v"(voff), "s"(base), "s"(dst) : "memory");
 #endif
-}
-
-// one piece of the residual tile (the same instruction as frd_dma, without the A stream's A/B switches)
-DITTO_DEV void frd_res_dma(unsigned voff, const char* base, unsigned dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(dst) : "memory");
 }
 
 // Vector-memory operations a wave has issued AFTER the load of W fragment (s, nb) when MFMA (s, nb) is about to issue, i.e.
@@ -164,9 +129,8 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);       // = the wave's column quarter
     const int nkt = p.K / DK;                                        // a multiple of 4 (K % 64 == 0)
     const int nslab = nkt >> 2;
-    // XCD-contiguous tiles and the K-loop rotation: exactly gemm_fr.hip's (same sums in the same order)
-    const int ntile = gridDim.x;
-    const int tile = (ntile & 7) == 0 ? (int)(blockIdx.x & 7) * (ntile >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    // XCD-contiguous tiles and the K-loop rotation: the same for every N = 768 kernel (same sums in the same order)
+    const int tile = fr_xcd_tile();
     const int m0 = tile * DM;
     const int s0 = fp.rot_period > 0 ? (((tile % fp.rot_period) & 7) * nslab) >> 3 : 0;
     const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)smem;
@@ -210,7 +174,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
         if constexpr (nb < 4) frd_wload<nb * 1024>(dst, vw0, (const char*)p.W);
         else frd_wload<(nb - 4) * 1024>(dst, vw0 + 4096u, (const char*)p.W);
     };
-    auto wait_frag = [&](auto VM, f32x4& frag) { frd_wait<decltype(VM)::value>(frag); };
+    auto wait_frag = [&](auto VM, f32x4& frag) { fr_wait<decltype(VM)::value>(frag); };
     auto advance_w = [&]() {
         --w_left;
         vw0 += w_left == 0 ? (unsigned)D_W_BYTES - (unsigned)nkt * D_W_BYTES : (unsigned)D_W_BYTES;
@@ -218,16 +182,11 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
 
     // bias row -> LDS (3 pieces of 1 KiB): the oldest loads of the kernel
     if (wid == 0) {
-        if (p.bias) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) glds16(p.bias + i * 256 + lane * 4, lds_base + (unsigned)(D_BIAS + i * 1024));
-        } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) *reinterpret_cast<f32x4*>(smem + D_BIAS + i * 1024 + lane * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        if (p.bias) fr_stage_row<3>(p.bias, lds_base, D_BIAS, lane);
+        else fr_zero_row<3>(smem, D_BIAS, lane);
     }
     // A slab 0 (in flight while the accumulators are initialised)
-    issue_a_piece(DC<0>{}); issue_a_piece(DC<1>{}); issue_a_piece(DC<2>{}); issue_a_piece(DC<3>{});
+    issue_a_piece(IntC<0>{}); issue_a_piece(IntC<1>{}); issue_a_piece(IntC<2>{}); issue_a_piece(IntC<3>{});
     advance_a();
 
     // A fragment addressing: row (32 mb + r32) x 128 B; stage j of the slab = 16-B chunks 2 j + hh
@@ -243,20 +202,9 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
     // block (nb, mb) = bias + the residual values t (four columns per g), into its home file
     auto init_block = [&](auto NB, auto MB, const res_t (&t)[4]) {
         constexpr int nb = decltype(NB)::value, mb = decltype(MB)::value;
-        f32x16 v;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(lbias + wid * 192 + nb * 32 + 8 * g + 4 * hh);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float r;
-                if constexpr (HB) r = __builtin_bit_cast(float, (e & 1) ? (t[g][e >> 1] & 0xFFFF0000u) : (t[g][e >> 1] << 16));
-                else r = t[g][e];
-                v[4 * g + e] = r + b4[e];
-            }
-        }
-        if constexpr (nb < DNA) { acca[nb < DNA ? nb : 0][mb] = v; FD_PIN_A(acca[nb < DNA ? nb : 0][mb]); }
-        else { accv[nb < DNA ? 0 : nb - DNA][mb] = v; FD_PIN_V(accv[nb < DNA ? 0 : nb - DNA][mb]); }
+        const f32x16 v = fr_acc_init(t, lbias + wid * 192 + nb * 32 + 4 * hh);
+        if constexpr (nb < DNA) { acca[nb < DNA ? nb : 0][mb] = v; fr_pin(InAgpr{}, acca[nb < DNA ? nb : 0][mb]); }
+        else { accv[nb < DNA ? 0 : nb - DNA][mb] = v; fr_pin(InVgpr{}, accv[nb < DNA ? 0 : nb - DNA][mb]); }
         __builtin_amdgcn_sched_barrier(0);
     };
     if constexpr (RES && HB && !FRD_NORES) {
@@ -282,7 +230,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
                 const unsigned voff = (unsigned)gr * (unsigned)p.ldr * 2u + rs_col + (unsigned)(((lane & 7) ^ ((row >> 1) & 7)) << 4);
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
-                    frd_res_dma(voff + (unsigned)(j * 128), reinterpret_cast<const char*>(p.residual),
+                    fr_dma(voff + (unsigned)(j * 128), reinterpret_cast<const char*>(p.residual),
                                 rs_wave + (unsigned)((mb & 1) * D_RUNIT + (j * 4 + rb) * 1024));
             }
         };
@@ -296,22 +244,22 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
         // are issued before block nb is converted.
         auto read_unit = [&](auto MB, auto YOUNGER) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(YOUNGER)::value) : "memory");
-            if constexpr (decltype(MB)::value == 0) FD_BAR();   // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
+            if constexpr (decltype(MB)::value == 0) DITTO_BAR();   // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
             res_t ta[4], tb[4];
-            read_block(DC<0>{}, MB, ta);
-            read_block(DC<1>{}, MB, tb); init_block(DC<0>{}, MB, ta);
-            read_block(DC<2>{}, MB, ta); init_block(DC<1>{}, MB, tb);
-            read_block(DC<3>{}, MB, tb); init_block(DC<2>{}, MB, ta);
-            read_block(DC<4>{}, MB, ta); init_block(DC<3>{}, MB, tb);
-            read_block(DC<5>{}, MB, tb); init_block(DC<4>{}, MB, ta);
-            init_block(DC<5>{}, MB, tb);
+            read_block(IntC<0>{}, MB, ta);
+            read_block(IntC<1>{}, MB, tb); init_block(IntC<0>{}, MB, ta);
+            read_block(IntC<2>{}, MB, ta); init_block(IntC<1>{}, MB, tb);
+            read_block(IntC<3>{}, MB, tb); init_block(IntC<2>{}, MB, ta);
+            read_block(IntC<4>{}, MB, ta); init_block(IntC<3>{}, MB, tb);
+            read_block(IntC<5>{}, MB, tb); init_block(IntC<4>{}, MB, ta);
+            init_block(IntC<5>{}, MB, tb);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the buffer is read: the next unit's DMA may overwrite it
         };
-        issue_unit(DC<0>{}); issue_unit(DC<1>{});
-        read_unit(DC<0>{}, DC<12>{}); issue_unit(DC<2>{});
-        read_unit(DC<1>{}, DC<12>{}); issue_unit(DC<3>{});
-        read_unit(DC<2>{}, DC<12>{});
-        read_unit(DC<3>{}, DC<0>{});
+        issue_unit(IntC<0>{}); issue_unit(IntC<1>{});
+        read_unit(IntC<0>{}, IntC<12>{}); issue_unit(IntC<2>{});
+        read_unit(IntC<1>{}, IntC<12>{}); issue_unit(IntC<3>{});
+        read_unit(IntC<2>{}, IntC<12>{});
+        read_unit(IntC<3>{}, IntC<0>{});
     } else {
         // fp32 stream: 96 hand-written global_load_dwordx4 per lane in the accumulator layout, four 32 x 32 blocks (16 loads) in
         // flight.  (Round 5 A/B of a deeper window on the bf16 form of these loads, profiles/r05_frd_window_ab.txt: inside the
@@ -331,14 +279,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
         auto issue_group = [&](auto GI, res_t (&t)[4]) {
             constexpr int nb = frd_group_nb(decltype(GI)::value), mb = frd_group_mb(decltype(GI)::value);
             if constexpr (LOADS) {
-                const char* ptr = rp[mb];
-                asm volatile("global_load_dwordx4 %0, %4, off offset:%5\n\t"
-                             "global_load_dwordx4 %1, %4, off offset:%6\n\t"
-                             "global_load_dwordx4 %2, %4, off offset:%7\n\t"
-                             "global_load_dwordx4 %3, %4, off offset:%8"
-                             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
-                             : "v"(ptr), "n"(nb * 128), "n"(nb * 128 + 32), "n"(nb * 128 + 64), "n"(nb * 128 + 96)
-                             : "memory");
+                fr_res_load<nb>(t, rp[mb]);
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) t[i] = res_t{};
@@ -348,35 +289,35 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
             constexpr int gi = decltype(GI)::value, nb = frd_group_nb(gi), mb = frd_group_mb(gi);
             constexpr int younger = NG - 1 - gi < WD - 1 ? NG - 1 - gi : WD - 1;
             if constexpr (LOADS)
-                asm volatile("s_waitcnt vmcnt(%4)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) : "n"(4 * younger) : "memory");
+                fr_res_wait<4 * younger>(t);
             if constexpr (gi == 0) {
                 if constexpr (!LOADS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                FD_BAR();      // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
+                DITTO_BAR();      // every wave is past a wait that covers wave 0's bias row (the oldest load): visible to all
             }
-            init_block(DC<nb>{}, DC<mb>{}, t);
+            init_block(IntC<nb>{}, IntC<mb>{}, t);
         };
         auto init_step = [&](auto GI) {
             constexpr int gi = decltype(GI)::value;
             finish_group(GI, T[gi % WD]);
-            if constexpr (gi + WD < NG) issue_group(DC<gi + WD>{}, T[gi % WD]);
+            if constexpr (gi + WD < NG) issue_group(IntC<gi + WD>{}, T[gi % WD]);
         };
-        issue_group(DC<0>{}, T[0]); issue_group(DC<1>{}, T[1]); issue_group(DC<2>{}, T[2]); issue_group(DC<3>{}, T[3]);
-        init_step(DC<0>{}); init_step(DC<1>{}); init_step(DC<2>{}); init_step(DC<3>{}); init_step(DC<4>{}); init_step(DC<5>{});
-        init_step(DC<6>{}); init_step(DC<7>{}); init_step(DC<8>{}); init_step(DC<9>{}); init_step(DC<10>{}); init_step(DC<11>{});
-        init_step(DC<12>{}); init_step(DC<13>{}); init_step(DC<14>{}); init_step(DC<15>{}); init_step(DC<16>{}); init_step(DC<17>{});
-        init_step(DC<18>{}); init_step(DC<19>{}); init_step(DC<20>{}); init_step(DC<21>{}); init_step(DC<22>{}); init_step(DC<23>{});
+        issue_group(IntC<0>{}, T[0]); issue_group(IntC<1>{}, T[1]); issue_group(IntC<2>{}, T[2]); issue_group(IntC<3>{}, T[3]);
+        init_step(IntC<0>{}); init_step(IntC<1>{}); init_step(IntC<2>{}); init_step(IntC<3>{}); init_step(IntC<4>{}); init_step(IntC<5>{});
+        init_step(IntC<6>{}); init_step(IntC<7>{}); init_step(IntC<8>{}); init_step(IntC<9>{}); init_step(IntC<10>{}); init_step(IntC<11>{});
+        init_step(IntC<12>{}); init_step(IntC<13>{}); init_step(IntC<14>{}); init_step(IntC<15>{}); init_step(IntC<16>{}); init_step(IntC<17>{});
+        init_step(IntC<18>{}); init_step(IntC<19>{}); init_step(IntC<20>{}); init_step(IntC<21>{}); init_step(IntC<22>{}); init_step(IntC<23>{});
     }
 
     // A slab 0 has landed for this wave (older than the residual loads); for everyone:
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    FD_BAR();
+    DITTO_BAR();
     FRD_STAMP(1);
     // W stages 0 and 1 -> the register ring (twelve loads, nothing else behind them: the wait counts of frd_vm start here)
-    issue_w(DC<0>{}, wr[0][0]); issue_w(DC<1>{}, wr[0][1]); issue_w(DC<2>{}, wr[0][2]);
-    issue_w(DC<3>{}, wr[0][3]); issue_w(DC<4>{}, wr[0][4]); issue_w(DC<5>{}, wr[0][5]);
+    issue_w(IntC<0>{}, wr[0][0]); issue_w(IntC<1>{}, wr[0][1]); issue_w(IntC<2>{}, wr[0][2]);
+    issue_w(IntC<3>{}, wr[0][3]); issue_w(IntC<4>{}, wr[0][4]); issue_w(IntC<5>{}, wr[0][5]);
     advance_w();
-    issue_w(DC<0>{}, wr[1][0]); issue_w(DC<1>{}, wr[1][1]); issue_w(DC<2>{}, wr[1][2]);
-    issue_w(DC<3>{}, wr[1][3]); issue_w(DC<4>{}, wr[1][4]); issue_w(DC<5>{}, wr[1][5]);
+    issue_w(IntC<0>{}, wr[1][0]); issue_w(IntC<1>{}, wr[1][1]); issue_w(IntC<2>{}, wr[1][2]);
+    issue_w(IntC<3>{}, wr[1][3]); issue_w(IntC<4>{}, wr[1][4]); issue_w(IntC<5>{}, wr[1][5]);
     advance_w();
     unsigned a_cur = 0;          // byte offset of the A slab being multiplied
     bf16x8 a0[4], a1[4];
@@ -399,7 +340,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
                     // behind the barrier, which also certifies that every wave is done reading the slab the NEXT issue overwrites
                     asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
 #ifndef DITTO_DIAG_FR_NOBAR
-                    FD_BAR();
+                    DITTO_BAR();
 #endif
                 }
 #pragma unroll
@@ -407,33 +348,33 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
                     ANXT[mb] = *reinterpret_cast<const bf16x8*>(smem + a_nxt + a_row + mb * 4096 + (a_x ^ (((j + 1) & 3) << 5)));
             }
             // fragment (s, nb) has landed: everything but the frd_vm(j, nb) operations issued after it
-            if (nb == 0) wait_frag(DC<frd_vm(j, 0, last)>{}, wr[slot][0]);
-            if (nb == 1) wait_frag(DC<frd_vm(j, 1, last)>{}, wr[slot][1]);
-            if (nb == 2) wait_frag(DC<frd_vm(j, 2, last)>{}, wr[slot][2]);
-            if (nb == 3) wait_frag(DC<frd_vm(j, 3, last)>{}, wr[slot][3]);
-            if (nb == 4) wait_frag(DC<frd_vm(j, 4, last)>{}, wr[slot][4]);
-            if (nb == 5) wait_frag(DC<frd_vm(j, 5, last)>{}, wr[slot][5]);
+            if (nb == 0) wait_frag(IntC<frd_vm(j, 0, last)>{}, wr[slot][0]);
+            if (nb == 1) wait_frag(IntC<frd_vm(j, 1, last)>{}, wr[slot][1]);
+            if (nb == 2) wait_frag(IntC<frd_vm(j, 2, last)>{}, wr[slot][2]);
+            if (nb == 3) wait_frag(IntC<frd_vm(j, 3, last)>{}, wr[slot][3]);
+            if (nb == 4) wait_frag(IntC<frd_vm(j, 4, last)>{}, wr[slot][4]);
+            if (nb == 5) wait_frag(IntC<frd_vm(j, 5, last)>{}, wr[slot][5]);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
                 if constexpr (has_next) {
-                    if (nb < DNA) dmfma_a(acca[nb < DNA ? nb : 0][mb], wr[slot][nb], ACUR[mb]);
-                    else dmfma_v(accv[nb < DNA ? 0 : nb - DNA][mb], wr[slot][nb], ACUR[mb]);
+                    if (nb < DNA) fr_mfma(InAgpr{}, acca[nb < DNA ? nb : 0][mb], wr[slot][nb], ACUR[mb]);
+                    else fr_mfma(InVgpr{}, accv[nb < DNA ? 0 : nb - DNA][mb], wr[slot][nb], ACUR[mb]);
                 } else {
-                    if (nb < DNA) dmfma_a_last(acca[nb < DNA ? nb : 0][mb], wr[slot][nb], ACUR[mb]);
-                    else dmfma_v_last(accv[nb < DNA ? 0 : nb - DNA][mb], wr[slot][nb], ACUR[mb]);
+                    if (nb < DNA) fr_mfma_last(InAgpr{}, acca[nb < DNA ? nb : 0][mb], wr[slot][nb], ACUR[mb]);
+                    else fr_mfma_last(InVgpr{}, accv[nb < DNA ? 0 : nb - DNA][mb], wr[slot][nb], ACUR[mb]);
                 }
             }
             if constexpr (do_w) {   // fragment nb of stage s + 2 into the registers just consumed
-                if (nb == 0) issue_w(DC<0>{}, wr[slot][0]);
-                if (nb == 1) issue_w(DC<1>{}, wr[slot][1]);
-                if (nb == 2) issue_w(DC<2>{}, wr[slot][2]);
-                if (nb == 3) issue_w(DC<3>{}, wr[slot][3]);
-                if (nb == 4) issue_w(DC<4>{}, wr[slot][4]);
-                if (nb == 5) issue_w(DC<5>{}, wr[slot][5]);
+                if (nb == 0) issue_w(IntC<0>{}, wr[slot][0]);
+                if (nb == 1) issue_w(IntC<1>{}, wr[slot][1]);
+                if (nb == 2) issue_w(IntC<2>{}, wr[slot][2]);
+                if (nb == 3) issue_w(IntC<3>{}, wr[slot][3]);
+                if (nb == 4) issue_w(IntC<4>{}, wr[slot][4]);
+                if (nb == 5) issue_w(IntC<5>{}, wr[slot][5]);
             }
             if constexpr (do_a) {   // half of the next slab's four pieces, behind W4 and W5
-                if (nb == 4) issue_a_piece(DC<2 * j>{});
-                if (nb == 5) issue_a_piece(DC<2 * j + 1>{});
+                if (nb == 4) issue_a_piece(IntC<2 * j>{});
+                if (nb == 5) issue_a_piece(IntC<2 * j + 1>{});
             }
         }
         if constexpr (do_w) advance_w();
@@ -441,19 +382,19 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
         if constexpr (j == 3) a_cur = a_nxt;
     };
     for (int sl = 0; sl + 1 < nslab; ++sl) {
-        stage(DC<0>{}, DC<0>{}, a0, a1);
-        stage(DC<1>{}, DC<0>{}, a1, a0);
-        stage(DC<2>{}, DC<0>{}, a0, a1);
-        stage(DC<3>{}, DC<0>{}, a1, a0);
+        stage(IntC<0>{}, IntC<0>{}, a0, a1);
+        stage(IntC<1>{}, IntC<0>{}, a1, a0);
+        stage(IntC<2>{}, IntC<0>{}, a0, a1);
+        stage(IntC<3>{}, IntC<0>{}, a1, a0);
     }
-    stage(DC<0>{}, DC<1>{}, a0, a1);
-    stage(DC<1>{}, DC<1>{}, a1, a0);
-    stage(DC<2>{}, DC<1>{}, a0, a1);
-    stage(DC<3>{}, DC<1>{}, a1, a0);
+    stage(IntC<0>{}, IntC<1>{}, a0, a1);
+    stage(IntC<1>{}, IntC<1>{}, a1, a0);
+    stage(IntC<2>{}, IntC<1>{}, a0, a1);
+    stage(IntC<3>{}, IntC<1>{}, a1, a0);
 
     // ---------------- epilogue: the accumulators hold h = residual + bias + A W^T; they are only READ from here on ----------------
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    FD_BAR();                                                       // every wave is out of the main loop: the A slabs are idle
+    DITTO_BAR();                                                       // every wave is out of the main loop: the A slabs are idle
     FRD_STAMP(2);
     float mean[4] = {0.f, 0.f, 0.f, 0.f}, rstd[4] = {1.f, 1.f, 1.f, 1.f};
     if constexpr (LN) {
@@ -471,14 +412,10 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
             for (int nb = 0; nb < 6; ++nb)
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) {
-                    // re-pin the block in its home file: the copy below is then a NEW value that cannot be hoisted above this
-                    if (nb < DNA) FD_PIN_A(acca[nb < DNA ? nb : 0][mb]); else FD_PIN_V(accv[nb < DNA ? 0 : nb - DNA][mb]);
+                    // re-pin the block in its home file: the copy below is then a NEW value that cannot be hoisted above this (fr_common.h fr_pin)
+                    if (nb < DNA) fr_pin(InAgpr{}, acca[nb < DNA ? nb : 0][mb]); else fr_pin(InVgpr{}, accv[nb < DNA ? 0 : nb - DNA][mb]);
                     const f32x16 v = nb < DNA ? acca[nb < DNA ? nb : 0][mb] : accv[nb < DNA ? 0 : nb - DNA][mb];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        if constexpr (decltype(PASS)::value == 0) c4[mb] += v[e];
-                        else { const float dl = fmaf(rsum[mb], -(1.0f / DN), v[e]); c4[mb] = fmaf(dl, dl, c4[mb]); }
-                    }
+                    fr_row_acc<decltype(PASS)::value, DN>(c4[mb], v, rsum[mb]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
@@ -489,7 +426,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
             }
         };
         float c4[4] = {0.f, 0.f, 0.f, 0.f};
-        row_pass(DC<0>{}, c4);
+        row_pass(IntC<0>{}, c4);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // gamma / beta have landed
         __syncthreads();
 #pragma unroll
@@ -501,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
         }
         __syncthreads();                                              // everyone has read the sums before the next pass overwrites them
         float q4[4] = {0.f, 0.f, 0.f, 0.f};
-        row_pass(DC<1>{}, q4);
+        row_pass(IntC<1>{}, q4);
         __syncthreads();
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) {
@@ -510,7 +447,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
         }
     }
     FRD_STAMP(3);
-    // stores (gemm_fr.hip): every output row leaves through a wave-private LDS stage so that the stores are whole 128-B lines:
+    // stores: every output row leaves through a wave-private LDS stage so that the stores are whole 128-B lines:
     // h fp32 (nt), u = LN(h) bf16, optional bf16 copy of h.
     const int cl = wid * 192 + 4 * hh;                             // this lane's column origin; + nb * 32 + 8 g
     const float* gl = lgamma + cl;
@@ -527,7 +464,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
     for (int nb = 0; nb < 6; ++nb) {
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) {
-            if (nb < DNA) FD_PIN_A(acca[nb < DNA ? nb : 0][mb]); else FD_PIN_V(accv[nb < DNA ? 0 : nb - DNA][mb]);
+            if (nb < DNA) fr_pin(InAgpr{}, acca[nb < DNA ? nb : 0][mb]); else fr_pin(InVgpr{}, accv[nb < DNA ? 0 : nb - DNA][mb]);
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -547,14 +484,12 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
                     sh[0] = pack_bf16x2(v4[0], v4[1]); sh[1] = pack_bf16x2(v4[2], v4[3]);
                     *reinterpret_cast<u32x2*>(hst + row * 128 + ((((nb & 1) * 4 + g) ^ (row & 7)) << 4) + hh * 8) = sh;
                 } else {
-                    *reinterpret_cast<f32x4*>(hst + row * 128 + (((2 * g + hh) ^ (row & 7)) << 4)) = v4;
+                    fr_stage_f32(hst, row, g, hh, v4);
                 }
                 if constexpr (LN || !HB) {
                     f32x4 y = v4;                                    // bf16 side: LayerNorm output, or the plain copy
                     if constexpr (LN) y = (v4 - mean[mb]) * rstd[mb] * g4 + b4;
-                    u32x2 st;
-                    st[0] = pack_bf16x2(y[0], y[1]); st[1] = pack_bf16x2(y[2], y[3]);
-                    *reinterpret_cast<u32x2*>(ust + row * 128 + ((((nb & 1) * 4 + g) ^ (row & 7)) << 4) + hh * 8) = st;
+                    fr_stage_bf16(ust, row, nb, g, hh, y);
                 }
             }
         }
@@ -566,7 +501,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
                 for (int i = 4 * q; i < 4 * q + 4; ++i) {
                     const int row = srow + 8 * i;
                     const u32x4 hv = *reinterpret_cast<const u32x4*>(hst + row * 128 + ((sq ^ (row & 7)) << 4));
-                    if (grow0 + 8 * i < FD_DIAG_M) store16<true, true>(hrow + (size_t)(8 * i) * p.ldo + nb * 32, hv, 0);
+                    if (grow0 + 8 * i < fr_store_m(p)) store16<true, true>(hrow + (size_t)(8 * i) * p.ldo + nb * 32, hv, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -577,7 +512,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
                 for (int i = 4 * q; i < 4 * q + 4; ++i) {
                     const int row = srow + 8 * i;
                     const u32x4 hv = *reinterpret_cast<const u32x4*>(hst + row * 128 + ((sq ^ (row & 7)) << 4));
-                    if (grow0 + 8 * i < FD_DIAG_M) *reinterpret_cast<u32x4*>(hbrow + (size_t)(8 * i) * p.ldo + (nb - 1) * 32) = hv;
+                    if (grow0 + 8 * i < fr_store_m(p)) *reinterpret_cast<u32x4*>(hbrow + (size_t)(8 * i) * p.ldo + (nb - 1) * 32) = hv;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -589,7 +524,7 @@ __global__ __launch_bounds__(256, 1) void gemm_frd_kernel(FrParams fp) {
                 for (int i = 4 * q; i < 4 * q + 4; ++i) {
                     const int row = srow + 8 * i;
                     const u32x4 uv = *reinterpret_cast<const u32x4*>(ust + row * 128 + ((sq ^ (row & 7)) << 4));
-                    if (grow0 + 8 * i < FD_DIAG_M) {
+                    if (grow0 + 8 * i < fr_store_m(p)) {
                         if (LN) *reinterpret_cast<u32x4*>(urow + (size_t)(8 * i) * fp.ldu + (nb - 1) * 32) = uv;
                         else if (orow) *reinterpret_cast<u32x4*>(orow + (size_t)(8 * i) * p.ldo2 + (nb - 1) * 32) = uv;
                     }

@@ -27,7 +27,7 @@
 //             normalised row is the LayerNorm kernel's bit for bit.  h is fp32 or bf16 (the bf16 residual stream).
 #include <type_traits>
 
-#include "gemm_common.h"
+#include "fr_common.h"
 
 namespace ditto {
 
@@ -43,9 +43,6 @@ struct QW {
     static constexpr int LDS = A + D * 4;          // 99 / 132 KiB
     static constexpr int CH = D / 256;             // f32x4 per lane of a row (one wave per row)
 };
-
-template <int V>
-struct QC { static constexpr int value = V; };
 
 #ifdef DITTO_DIAG_LNQ_STAMP   // tools/build_diag_one.sh ... gemm_lnq.hip -DDITTO_DIAG_LNQ_STAMP: s_memtime stamps around the kernel's phases
 __device__ unsigned long long g_lnq_stamps[2048 * 4 * 8];
@@ -75,16 +72,12 @@ struct Geo<16, D, NW> {
     using acc_t = f32x4;
 };
 
-DITTO_DEV void q_mfma(f32x16& c, const f32x4& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
-}
+// the accumulators are all in AGPRs.  32x32x16: fr_common.h; its 16x16x32 twin (4 passes: fewer wait states behind the last one):
+DITTO_DEV void q_mfma(f32x16& c, const f32x4& w, const bf16x8& a) { fr_mfma(InAgpr{}, c, w, a); }
 DITTO_DEV void q_mfma(f32x4& c, const f32x4& w, const bf16x8& a) {
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
 }
-// last MFMA of a chain: its wait states inside the statement (hipcc knows nothing about an asm producer: gemm_fr.hip)
-DITTO_DEV void q_mfma_last(f32x16& c, const f32x4& w, const bf16x8& a) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0\n\ts_nop 15" : "+a"(c) : "v"(w), "v"(a));
-}
+DITTO_DEV void q_mfma_last(f32x16& c, const f32x4& w, const bf16x8& a) { fr_mfma_last(InAgpr{}, c, w, a); }
 DITTO_DEV void q_mfma_last(f32x4& c, const f32x4& w, const bf16x8& a) {
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0\n\ts_nop 9" : "+a"(c) : "v"(w), "v"(a));
 }
@@ -95,11 +88,7 @@ DITTO_DEV void q_wload(f32x4& dst, unsigned voff, const char* base) {
                             // no NaN garbage speeds the rest of the step up).  TIMING ONLY: LayerNorm, LDS reads, MFMAs, epilogue alone
     if constexpr (!PROLOGUE) { asm volatile("" : "+v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory"); return; }
 #endif
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(base), "n"(IMM) : "memory");
-}
-template <int VM>
-DITTO_DEV void q_wait(f32x4& frag) {   // counted wait that ties the fragment's registers: no use moves above it
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(frag) : "n"(VM) : "memory");
+    fr_wload<IMM>(dst, voff, base);
 }
 
 // Loads a wave has issued AFTER the load of W fragment (s, nb) when MFMA (s, nb) is about to issue (issue order: the ring
@@ -150,8 +139,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_lnq_kernel(LnqParams p) 
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     LNQ_STAMP(0);
     // XCD-contiguous tiles (blocks b and b + 8 share an XCD: neighbouring tiles, i.e. neighbouring K-loop phases, on one L2)
-    const int ntile = gridDim.x;
-    const int tile = (ntile & 7) == 0 ? (int)(blockIdx.x & 7) * (ntile >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int tile = fr_xcd_tile();
     const int m0 = tile * QM;
     // K-loop rotation by whole periods: the workgroups of an XCD do not all ask their L2 for the same weight lines at once.
     // A function of the tile's place INSIDE its utterance, so an utterance's bits do not depend on its place in the batch.
@@ -160,13 +148,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_lnq_kernel(LnqParams p) 
 
     // bias row -> LDS (3 pieces of 1 KiB), wave 3; landed and visible behind the barrier that ends the LayerNorm
     if (wid == 3) {
-        if (p.bias) {
-#pragma unroll
-            for (int i = 0; i < CH; ++i) glds16(p.bias + i * 256 + lane * 4, lds_base + (unsigned)(Q_BIAS + i * 1024));
-        } else {
-#pragma unroll
-            for (int i = 0; i < CH; ++i) *reinterpret_cast<f32x4*>(smem + Q_BIAS + i * 1024 + lane * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        if (p.bias) fr_stage_row<CH>(p.bias, lds_base, Q_BIAS, lane);
+        else fr_zero_row<CH>(smem, Q_BIAS, lane);
     }
 
     // ---- W: straight into registers.  (The ring's first loads go out AFTER the LayerNorm: an asm load issued between a
@@ -191,12 +174,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_lnq_kernel(LnqParams p) 
         q_wload<(nb & 3) * 1024, true>(dst, vw + (unsigned)((nb >> 2) * 4096), wbase);
     };
     auto issue_stage = [&](f32x4 (&slot)[NBW]) {
-        issue_wp(QC<0>{}, slot[0]); issue_wp(QC<1>{}, slot[1]); issue_wp(QC<2>{}, slot[2]);
-        if constexpr (NBW > 3) issue_wp(QC<3>{}, slot[3]);
-        if constexpr (NBW > 4) { issue_wp(QC<4>{}, slot[4]); issue_wp(QC<5>{}, slot[5]); }
-        if constexpr (NBW > 6) { issue_wp(QC<6>{}, slot[6]); issue_wp(QC<7>{}, slot[7]); }
+        issue_wp(IntC<0>{}, slot[0]); issue_wp(IntC<1>{}, slot[1]); issue_wp(IntC<2>{}, slot[2]);
+        if constexpr (NBW > 3) issue_wp(IntC<3>{}, slot[3]);
+        if constexpr (NBW > 4) { issue_wp(IntC<4>{}, slot[4]); issue_wp(IntC<5>{}, slot[5]); }
+        if constexpr (NBW > 6) { issue_wp(IntC<6>{}, slot[6]); issue_wp(IntC<7>{}, slot[7]); }
         if constexpr (NBW > 8) {
-            issue_wp(QC<8>{}, slot[8]); issue_wp(QC<9>{}, slot[9]); issue_wp(QC<10>{}, slot[10]); issue_wp(QC<11>{}, slot[11]);
+            issue_wp(IntC<8>{}, slot[8]); issue_wp(IntC<9>{}, slot[9]); issue_wp(IntC<10>{}, slot[10]); issue_wp(IntC<11>{}, slot[11]);
         }
         advance_w();
     };
@@ -277,7 +260,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_lnq_kernel(LnqParams p) 
         for (int mb = 0; mb < MBW; ++mb) {
 #pragma unroll
             for (int e = 0; e < (int)(sizeof(acc_t) / 4); ++e) acc[nb][mb][e] = 0.f;
-            asm volatile("" : "+a"(acc[nb][mb]));
+            fr_pin(InAgpr{}, acc[nb][mb]);
         }
     
 #ifdef DITTO_DIAG_LNQ_STAMP
@@ -318,7 +301,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_lnq_kernel(LnqParams p) 
         constexpr bool last = remc == 0, do_w = remc >= R;
         auto block = [&](auto NB) {
             constexpr int nb = decltype(NB)::value;
-            q_wait<lnq_vm(NBW, R, nb, remc)>(slot[nb]);
+            fr_wait<lnq_vm(NBW, R, nb, remc)>(slot[nb]);
 #pragma unroll
             for (int mb = 0; mb < MBW; ++mb) {
                 if constexpr (last) q_mfma_last(acc[nb][mb], slot[nb], ACUR[mb]);
@@ -327,39 +310,39 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_lnq_kernel(LnqParams p) 
             if constexpr (do_w) issue_w(NB, slot[nb]);
             if constexpr (nb == 0 && !last) read_a(ANXT, span_next, aoff[(j + 1) % PER]);
         };
-        block(QC<0>{}); block(QC<1>{}); block(QC<2>{});
-        if constexpr (NBW > 3) block(QC<3>{});
-        if constexpr (NBW > 4) { block(QC<4>{}); block(QC<5>{}); }
-        if constexpr (NBW > 6) { block(QC<6>{}); block(QC<7>{}); }
-        if constexpr (NBW > 8) { block(QC<8>{}); block(QC<9>{}); block(QC<10>{}); block(QC<11>{}); }
+        block(IntC<0>{}); block(IntC<1>{}); block(IntC<2>{});
+        if constexpr (NBW > 3) block(IntC<3>{});
+        if constexpr (NBW > 4) { block(IntC<4>{}); block(IntC<5>{}); }
+        if constexpr (NBW > 6) { block(IntC<6>{}); block(IntC<7>{}); }
+        if constexpr (NBW > 8) { block(IntC<8>{}); block(IntC<9>{}); block(IntC<10>{}); block(IntC<11>{}); }
         if constexpr (do_w) advance_w();
     };
     // a period = PER stages = one 256-B span of A (16 chunks); a stage reads the NEXT stage's fragments, which sit in the next
     // period's span when j = PER - 1.  Stage j of a period uses ring slot j % R.
     auto period = [&](auto LASTP, int span, int span_after) {
         constexpr bool lastp = decltype(LASTP)::value != 0;
-#define LNQ_REM(j) QC<(lastp ? ((PER - 1 - (j)) < R ? (PER - 1 - (j)) : R) : R)>{}
-        stage(QC<0>{}, LNQ_REM(0), span, wr[0 % R], a0, a1);
-        stage(QC<1>{}, LNQ_REM(1), span, wr[1 % R], a1, a0);
-        stage(QC<2>{}, LNQ_REM(2), span, wr[2 % R], a0, a1);
+#define LNQ_REM(j) IntC<(lastp ? ((PER - 1 - (j)) < R ? (PER - 1 - (j)) : R) : R)>{}
+        stage(IntC<0>{}, LNQ_REM(0), span, wr[0 % R], a0, a1);
+        stage(IntC<1>{}, LNQ_REM(1), span, wr[1 % R], a1, a0);
+        stage(IntC<2>{}, LNQ_REM(2), span, wr[2 % R], a0, a1);
         if constexpr (PER == 4) {
-            stage(QC<3>{}, LNQ_REM(3), span_after, wr[3 % R], a1, a0);
+            stage(IntC<3>{}, LNQ_REM(3), span_after, wr[3 % R], a1, a0);
         } else {
-            stage(QC<3>{}, LNQ_REM(3), span, wr[3 % R], a1, a0);
-            stage(QC<4>{}, LNQ_REM(4), span, wr[4 % R], a0, a1);
-            stage(QC<5>{}, LNQ_REM(5), span, wr[5 % R], a1, a0);
-            stage(QC<6>{}, LNQ_REM(6), span, wr[6 % R], a0, a1);
-            stage(QC<7>{}, LNQ_REM(7), span_after, wr[7 % R], a1, a0);
+            stage(IntC<3>{}, LNQ_REM(3), span, wr[3 % R], a1, a0);
+            stage(IntC<4>{}, LNQ_REM(4), span, wr[4 % R], a0, a1);
+            stage(IntC<5>{}, LNQ_REM(5), span, wr[5 % R], a1, a0);
+            stage(IntC<6>{}, LNQ_REM(6), span, wr[6 % R], a0, a1);
+            stage(IntC<7>{}, LNQ_REM(7), span_after, wr[7 % R], a1, a0);
         }
 #undef LNQ_REM
     };
     int pcur = p0;
     for (int pi = 0; pi + 1 < NPER; ++pi) {
         const int pnext = pcur + 1 == NPER ? 0 : pcur + 1;
-        period(QC<0>{}, pcur * 256, pnext * 256);
+        period(IntC<0>{}, pcur * 256, pnext * 256);
         pcur = pnext;
     }
-    period(QC<1>{}, pcur * 256, 0);
+    period(IntC<1>{}, pcur * 256, 0);
     LNQ_STAMP(2);
 
     // ---------------- epilogue: q = acc + bias -> bf16, staged through the A region (every wave is done reading it) ----------------
@@ -371,7 +354,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_lnq_kernel(LnqParams p) 
     for (int nb = 0; nb < NBW; ++nb) {
 #pragma unroll
         for (int mb = 0; mb < MBW; ++mb) {
-            asm volatile("" : "+a"(acc[nb][mb]));                         // re-pin: the copy below is a NEW value, never hoisted
+            fr_pin(InAgpr{}, acc[nb][mb]);                         // re-pin: the copy below is a NEW value, never hoisted
             const acc_t v = acc[nb][mb];
             if constexpr (SHAPE == 32) {
                 const int row = mb * 32 + (lane & 31);

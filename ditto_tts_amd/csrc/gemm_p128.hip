@@ -25,11 +25,6 @@ constexpr int HB = 128 * 64 * 2;   // half-tile bytes: 16 KiB
 constexpr int KTB = 3 * HB;        // A_lo | A_hi | B = 48 KiB
 constexpr int LDS_P128 = 3 * KTB;  // 144 KiB
 
-template <int V>
-struct ICp { static constexpr int value = V; };
-
-#define DITTO_BAR() asm volatile("s_barrier" ::: "memory")
-
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_p128_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -66,17 +61,17 @@ __global__ __launch_bounds__(512, 2) void gemm_p128_kernel(GemmParams p) {
         }
     };
     auto stage_tile = [&](auto BUF, int kt) {   // all three halves of K-tile kt into ring slot BUF
-        stage(BUF, ICp<0>{}, kt);
-        stage(BUF, ICp<1>{}, kt);
-        stage(BUF, ICp<2>{}, kt);
+        stage(BUF, IntC<0>{}, kt);
+        stage(BUF, IntC<1>{}, kt);
+        stage(BUF, IntC<2>{}, kt);
     };
     auto prologue = [&](int tile) {
         int tm, tn;
         tile_to_mn(xcd_remap(tile, ntiles), p.tiles_m, p.tiles_n, p.group_n, tm, tn);
         m0 = tm * 256;
         n0 = tn * 128;
-        stage_tile(ICp<0>{}, 0);
-        stage_tile(ICp<1>{}, 1);
+        stage_tile(IntC<0>{}, 0);
+        stage_tile(IntC<1>{}, 1);
     };
 
     const int frow = lane & 15, fq = lane >> 4, fswz = frow >> 1;
@@ -154,26 +149,26 @@ __global__ __launch_bounds__(512, 2) void gemm_p128_kernel(GemmParams p) {
         // first read of every K-tile (seen in the .s; the kernel then ran at a third of the MFMA rate).
         auto ktile = [&](int kt, auto BUF, auto BUF2) {
             // P1
-            read_B(BUF, ICp<0>{});
+            read_B(BUF, IntC<0>{});
             read_A(BUF);
-            stage(BUF2, ICp<0>{}, kt + 2);
-            stage(BUF2, ICp<1>{}, kt + 2);
+            stage(BUF2, IntC<0>{}, kt + 2);
+            stage(BUF2, IntC<1>{}, kt + 2);
             DITTO_BAR();
-            mma(ICp<0>{});
+            mma(IntC<0>{});
             DITTO_BAR();
             // P2
-            read_B(BUF, ICp<1>{});
-            stage(BUF2, ICp<2>{}, kt + 2);
+            read_B(BUF, IntC<1>{});
+            stage(BUF2, IntC<2>{}, kt + 2);
             if (kt + 2 < nkt) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // K-tile kt+1 has landed
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             DITTO_BAR();
-            mma(ICp<1>{});
+            mma(IntC<1>{});
             DITTO_BAR();
         };
         for (int kt = 0; kt < nkt; kt += 3) {
-            ktile(kt, ICp<0>{}, ICp<2>{});
-            if (kt + 1 < nkt) ktile(kt + 1, ICp<1>{}, ICp<0>{});
-            if (kt + 2 < nkt) ktile(kt + 2, ICp<2>{}, ICp<1>{});
+            ktile(kt, IntC<0>{}, IntC<2>{});
+            if (kt + 1 < nkt) ktile(kt + 1, IntC<1>{}, IntC<0>{});
+            if (kt + 2 < nkt) ktile(kt + 2, IntC<2>{}, IntC<1>{});
         }
         if (wid < 4) DITTO_BAR();    // balance the stagger barrier: every LDS read of this tile has retired
 

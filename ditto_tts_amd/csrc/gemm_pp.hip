@@ -47,8 +47,6 @@ template <int NB> struct PP {
     static constexpr int PER_WAVE = PIECES / 4;               // 6 / 5
 };
 
-#define PP_BAR() asm volatile("s_barrier" ::: "memory")
-
 template <int EPI, int NB>
 __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(GemmParams p) {
     constexpr int PN = PP<NB>::PN, P_STAGE = PP<NB>::STAGE, P_LDS = PP<NB>::LDS, NPW = PP<NB>::PER_WAVE;
@@ -149,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(GemmParams p) {
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-            PP_BAR();
+            DITTO_BAR();
             const char* cur = smem + c_slot;
             bf16x8 af[8], wf[NB];
 #pragma unroll
