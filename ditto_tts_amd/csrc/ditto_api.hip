@@ -1486,8 +1486,10 @@ static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const
                               const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const uint32_t* tags,
                               bool per_utt, const float* w, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
                               int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
-                              size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+                              size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
+                              const int32_t* prompt_len = nullptr, bool prompted = false) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    if (prompted && !prompt_len) return fail(DITTO_ERR_ARG, "%s: null prompt_len (int32 [B])", who);
     if (int rc = check_guided_update(who, x2, x2, noise, seeds, w, a, ce, cz, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
     if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
     if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
@@ -1500,7 +1502,10 @@ static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const
                                   BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
             return rc;
         ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-        if (per_utt)
+        if (prompted)
+            HIP_TRY(launch_guided_update_prompt(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, B, S, max_N,
+                                                m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
+        else if (per_utt)
             HIP_TRY(launch_guided_update_packed_tags(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim,
                                                      cfg != 0, (hipStream_t)stream));
         else
@@ -1539,6 +1544,87 @@ int ditto_guided_step_packed_tags_opts(ditto_model_t m, float* x2, const void* c
                                        size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
     return guided_step_packed("ditto_guided_step_packed_tags_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true, w, a,
                               ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
+}
+
+// ---- speech prompts: the packed update and step that leave each utterance's first prompt_len[b] rows alone (guided_prompt.hip) ----
+static int guided_update_prompt(const char* who, float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
+                                const uint32_t* tags, bool per_utt, const float* w, const float* a, const float* ce, const float* cz,
+                                const int32_t* cu, const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg,
+                                ditto_stream_t stream) {
+    if (!cu || !prompt_len) return fail(DITTO_ERR_ARG, "%s: null cu / prompt_len", who);
+    if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
+    if (int rc = check_guided_update(who, x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_guided_update_prompt(x2, eps2, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu, prompt_len, B, S, max_N, d, cfg != 0,
+                                        (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_update_packed_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
+                                      const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                      const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
+    return guided_update_prompt("ditto_guided_update_packed_prompt", x2, eps2, noise, seeds, step, nullptr, false, w, a, ce, cz, cu,
+                                prompt_len, B, S, max_N, d, cfg, stream);
+}
+
+int ditto_guided_update_packed_tags_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                           const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                           const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
+    return guided_update_prompt("ditto_guided_update_packed_tags_prompt", x2, eps2, noise, seeds, 0, tags, true, w, a, ce, cz, cu,
+                                prompt_len, B, S, max_N, d, cfg, stream);
+}
+
+int ditto_guided_step_packed_prompt_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                         const int32_t* cu_text, const int32_t* prompt_len, const float* noise, const int64_t* seeds,
+                                         uint32_t step, const float* w, const float* a, const float* ce, const float* cz, int B, int S,
+                                         int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
+                                         void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_packed("ditto_guided_step_packed_prompt_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false,
+                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
+                              prompt_len, true);
+}
+
+int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                              const int32_t* cu_text, const int32_t* prompt_len, const float* noise, const int64_t* seeds,
+                                              const uint32_t* tags, const float* w, const float* a, const float* ce, const float* cz,
+                                              int B, int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos,
+                                              const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                                              const ditto_call_opts* opts) {
+    return guided_step_packed("ditto_guided_step_packed_tags_prompt_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true,
+                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
+                              prompt_len, true);
+}
+
+// ---- span-masked training over a packed batch with prompts (span_train.hip) ----
+static int check_span(const char* who, const void* in, const float* noise, const int64_t* seeds, const int32_t* cu,
+                      const int32_t* prompt_len, const void* out, int B, int S, int max_N, int d) {
+    if (!in || !out || !cu || !prompt_len) return fail(DITTO_ERR_ARG, "%s: null pointer", who);
+    if (!noise == !seeds) return fail(DITTO_ERR_ARG, "%s: exactly one of noise (a packed buffer) and seeds (Philox) is needed", who);
+    if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
+    return check_packed(who, B, S, max_N, S, max_N);
+}
+
+int ditto_span_noise_packed(const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca, const float* cs,
+                            const int32_t* cu, const int32_t* prompt_len, float* x_in, int B, int S, int max_N, int d,
+                            ditto_stream_t stream) {
+    if (!ca || !cs) return fail(DITTO_ERR_ARG, "ditto_span_noise_packed: null ca / cs");
+    if (int rc = check_span("ditto_span_noise_packed", x0, noise, seeds, cu, prompt_len, x_in, B, S, max_N, d)) return rc;
+    HIP_TRY(launch_span_noise_packed(x0, noise, seeds, tag, ca, cs, cu, prompt_len, x_in, B, S, max_N, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
+                          const int32_t* prompt_len, size_t n_elems, float* grad_eps, float* loss, void* workspace,
+                          size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream) {
+    if (!loss || !workspace) return fail(DITTO_ERR_ARG, "ditto_span_mse_packed: null loss / workspace");
+    if (int rc = check_span("ditto_span_mse_packed", eps, noise, seeds, cu, prompt_len, grad_eps, B, S, max_N, d)) return rc;
+    if (n_elems == 0 || n_elems > (size_t)S * d) return fail(DITTO_ERR_SHAPE, "ditto_span_mse_packed: n_elems must lie in [1, S d]");
+    if ((uintptr_t)workspace % 4 || workspace_bytes < span_mse_partials(B, max_N, d) * sizeof(float))
+        return fail(DITTO_ERR_SIZE, "ditto_span_mse_packed: the workspace needs %zu bytes (B x min(1024, ceil(max_N d / 1024)) floats)",
+                    span_mse_partials(B, max_N, d) * sizeof(float));
+    HIP_TRY(launch_span_mse_packed(eps, noise, seeds, tag, cu, prompt_len, (double)n_elems, grad_eps, loss, (float*)workspace, B, S, max_N,
+                                   d, (hipStream_t)stream));
+    return DITTO_OK;
 }
 
 int ditto_regroup_packed(const ditto_regroup_seg* table, int n_seg, const void* const* src, const size_t* src_bytes, void* const* dst,

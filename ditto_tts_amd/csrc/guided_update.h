@@ -28,6 +28,18 @@ __device__ __forceinline__ GuidedSpan guided_span(const int32_t* cu, int b, int 
     return {(size_t)r0 * d / 4, (size_t)nb * d / 4};
 }
 
+// guided_span plus a speech prompt: the first prompt_len[b] rows of the utterance are clean latents.  p4 = the quad where the generated
+// rows begin, P_b clamped into [0, n_b - 1]: a bad prompt length gives wrong rows, never an access outside the utterance's own
+struct PromptSpan { size_t base4, n4, p4; };
+__device__ __forceinline__ PromptSpan prompt_span(const int32_t* cu, const int32_t* prompt_len, int b, int S, int d) {
+    int r0 = cu[b];
+    r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
+    const int n = cu[b + 1] - r0, nb = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);
+    int p = prompt_len[b];
+    p = p < 0 ? 0 : (p > nb - 1 ? nb - 1 : p);
+    return {(size_t)r0 * d / 4, (size_t)nb * d / 4, (size_t)p * d / 4};
+}
+
 // quads [i0, n4) of one utterance at a grid stride: xc / ec (xu / eu) = its first quad in the conditional (unconditional) half, nz in
 // the noise buffer.  PADDED: quads from valid4 on are written as 0 and read nothing.  draw: whether a Philox utterance draws at all.
 // i0 and stride come from the __global__ function: read here, blockDim / gridDim compile to a vector load of the implicit arguments.

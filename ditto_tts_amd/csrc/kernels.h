@@ -272,6 +272,23 @@ hipError_t launch_guided_update_packed(float* x2, const float* eps2, const float
 hipError_t launch_guided_update_packed_tags(float* x2, const float* eps2, const float* noise, const int64_t* seeds,
                                             const unsigned* tags, const float* w, const float* a, const float* ce, const float* cz,
                                             const int32_t* cu, int B, int S, int max_N, int d, bool cfg, hipStream_t s);
+// ---------------- guided_prompt.hip ----------------
+// launch_guided_update_packed (per_utt false) / launch_guided_update_packed_tags (per_utt true) over the rows behind each utterance's
+// speech prompt: prompt_len device int32 [B], clamped into [0, n_b - 1]; the prompt rows of x2 and eps2 are neither read nor written
+hipError_t launch_guided_update_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
+                                       const unsigned* tags, bool per_utt, const float* w, const float* a, const float* ce,
+                                       const float* cz, const int32_t* cu, const int32_t* prompt_len, int B, int S, int max_N, int d,
+                                       bool cfg, hipStream_t s);
+// ---------------- span_train.hip ----------------
+// span-masked training over a packed batch with prompts: the noising that keeps the prompt rows, the MSE over the generated rows
+// (n_elems of them) with its gradient; `partial`: span_mse_partials(B, max_N, d) floats
+size_t span_mse_partials(int B, int max_N, int d);
+hipError_t launch_span_noise_packed(const float* x0, const float* noise, const int64_t* seeds, unsigned tag, const float* ca,
+                                    const float* cs, const int32_t* cu, const int32_t* prompt_len, float* x_in, int B, int S, int max_N,
+                                    int d, hipStream_t s);
+hipError_t launch_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
+                                  const int32_t* prompt_len, double n_elems, float* grad, float* loss, float* partial, int B, int S,
+                                  int max_N, int d, hipStream_t s);
 // ---------------- regroup_packed.hip ----------------
 // the buffers a regroup's segments name by index, sizes in 16-byte units (a null pointer: no such buffer)
 #define DITTO_REGROUP_BUFS 6

@@ -86,7 +86,8 @@ def sample_sharded(sample_fn: Callable[[torch.Tensor, torch.Tensor, int], torch.
                    text_full: Optional[torch.Tensor], xT_full: Optional[torch.Tensor], text_tail, x_tail,
                    device, root: int = 0, group=None, phases: Optional[dict] = None,
                    sync: Optional[Callable[[], None]] = None, pin_class: bool = True,
-                   text_dtype: torch.dtype = torch.float32, speech_lengths=None, text_lengths=None) -> Optional[torch.Tensor]:
+                   text_dtype: torch.dtype = torch.float32, speech_lengths=None, text_lengths=None,
+                   prompt_lengths=None) -> Optional[torch.Tensor]:
     """Scatter (text_emb, x_T) from root, run `sample_fn(text_shard, xT_shard, first_global_index)` on every
     rank (the whole denoise loop — no communication inside), gather the final latents on root.
 
@@ -110,6 +111,9 @@ def sample_sharded(sample_fn: Callable[[torch.Tensor, torch.Tensor, int], torch.
     if speech_lengths is not None or text_lengths is not None:
         raise NotImplementedError("sample_sharded: variable-length batches are not sharded (run SpeechGenerator.sample_latents with "
                                   "speech_lengths= / text_lengths= per rank)")
+    if prompt_lengths is not None:
+        raise NotImplementedError("sample_sharded: speech prompts are not sharded (run SpeechGenerator.sample_guided_packed with "
+                                  "prompt_lengths= per rank)")
     import time
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     tick = (lambda: (sync() if sync else None, time.perf_counter())[1]) if phases is not None else (lambda: 0.0)

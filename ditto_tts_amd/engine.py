@@ -263,10 +263,12 @@ class DenoiseEngine:
     def guided_step_packed_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, a: torch.Tensor, ce: torch.Tensor,
                             cz: torch.Tensor, w: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             seeds: Optional[torch.Tensor] = None, step: int = 0, cu_seqlens=None, max_seqlen: Optional[int] = None,
-                            offsets=None, opts: Optional[hip.CallOpts] = None):
+                            offsets=None, opts: Optional[hip.CallOpts] = None, prompt_len: Optional[torch.Tensor] = None):
         """guided_step_ over a packed batch, IN PLACE on x2 fp32 [2S, d] ([x; x], w given) or [S, d]
         (ditto_guided_step_packed_opts).  `offsets`: guided_offsets_packed(...) built once per sampling call (else built here from
-        `cu_seqlens`); `cond`: prepare_text_packed over [text; null] (2B utterances) or text.  noise: packed fp32 [S, d]."""
+        `cu_seqlens`); `cond`: prepare_text_packed over [text; null] (2B utterances) or text.  noise: packed fp32 [S, d].
+        `prompt_len` (device int32 [B], validated by the caller: varlen.validate_prompt_lengths): the first prompt_len[b] rows of
+        utterance b are a speech prompt the update leaves alone (ditto_guided_step_packed_prompt_opts)."""
         sd, noise = self._guided_args("guided_step_packed_", x2, 2, B, a, ce, cz, w, noise, seeds)
         cfg = w is not None
         nb = 2 * B if cfg else B
@@ -283,11 +285,62 @@ class DenoiseEngine:
         tt = self._t64(t, nb)
         ws = self.workspace_packed(nb, rows, cond.T)
         c, s = self.rope_tables(max_N)
-        hip.check(self.lib.ditto_guided_step_packed_opts(
-            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(noise),
+        if prompt_len is not None:
+            if not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous() and prompt_len.shape == (B,)):
+                raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+            entry, head = self.lib.ditto_guided_step_packed_prompt_opts, (prompt_len.data_ptr(),)
+        else:
+            entry, head = self.lib.ditto_guided_step_packed_opts, ()
+        hip.check(entry(
+            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), *head, _ptr(noise),
             _ptr(sd), int(step) & 0xFFFFFFFF, _ptr(w), a.data_ptr(), ce.data_ptr(), cz.data_ptr(), B, S, max_N, cond.T, cond.max_len,
             int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
         return x2
+
+    # ------------------------------------------------------------------ span-masked training (csrc/span_train.hip)
+    def _span_args(self, who, buf, cu_seqlens, prompt_lengths, seeds, noise):
+        """the checks of span_noise_packed / span_mse_packed: (device offsets, device prompt lengths, B, max_N, generated rows,
+        seeds int64 [B] or None, noise fp32 [S, d] or None)"""
+        from .varlen import validate_prompt_lengths
+        if not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and buf.dim() == 2 and buf.shape[1] % 64 == 0):
+            raise ValueError(f"{who} needs a contiguous fp32 CUDA tensor [S, d] with d % 64 == 0")
+        if (seeds is None) == (noise is None):
+            raise ValueError(f"{who}: exactly one of seeds= and noise= is needed")
+        S = int(buf.shape[0])
+        B = len(cu_seqlens) - 1
+        cu, max_N = self._cu(cu_seqlens, B, S, None, "cu_seqlens")
+        pl = validate_prompt_lengths(prompt_lengths, cu)
+        if noise is not None:
+            noise = self._f32(noise, "noise")
+            if noise.shape != buf.shape:
+                raise ValueError(f"noise must have shape {list(buf.shape)}")
+        sd = self._t64(seeds, B) if seeds is not None else None
+        return cu.to(self.device), pl.to(self.device), B, max_N, S - int(pl.sum()), sd, noise
+
+    def span_noise_packed(self, x0: torch.Tensor, cu_seqlens, prompt_lengths, ca: torch.Tensor, cs: torch.Tensor, seeds=None,
+                          tag: int = 0, noise=None) -> torch.Tensor:
+        """x_in fp32 [S, d]: x0 on each utterance's prompt rows, ca[b] x0 + cs[b] z on its generated rows (ditto_span_noise_packed)"""
+        cud, pld, B, max_N, _, sd, noise = self._span_args("span_noise_packed", x0, cu_seqlens, prompt_lengths, seeds, noise)
+        for name, v in (("ca", ca), ("cs", cs)):
+            if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
+                raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
+        out = torch.empty_like(x0)
+        hip.check(self.lib.ditto_span_noise_packed(x0.data_ptr(), _ptr(noise), _ptr(sd), int(tag) & 0xFFFFFFFF, ca.data_ptr(),
+                                                   cs.data_ptr(), cud.data_ptr(), pld.data_ptr(), out.data_ptr(), B, x0.shape[0], max_N,
+                                                   x0.shape[1], _stream()))
+        return out
+
+    def span_mse_packed(self, eps: torch.Tensor, cu_seqlens, prompt_lengths, seeds=None, tag: int = 0, noise=None):
+        """(loss fp32 [], grad_eps fp32 [S, d]) of the MSE over the generated rows (ditto_span_mse_packed)"""
+        cud, pld, B, max_N, gen_rows, sd, noise = self._span_args("span_mse_packed", eps, cu_seqlens, prompt_lengths, seeds, noise)
+        S, d = int(eps.shape[0]), int(eps.shape[1])
+        grad = torch.empty_like(eps)
+        loss = torch.empty((), dtype=torch.float32, device=eps.device)
+        part = torch.empty(B * min(1024, (max_N * d // 4 + 255) // 256), dtype=torch.float32, device=eps.device)
+        hip.check(self.lib.ditto_span_mse_packed(eps.data_ptr(), _ptr(noise), _ptr(sd), int(tag) & 0xFFFFFFFF, cud.data_ptr(),
+                                                 pld.data_ptr(), gen_rows * d, grad.data_ptr(), loss.data_ptr(), part.data_ptr(),
+                                                 part.numel() * 4, B, S, max_N, d, _stream()))
+        return loss, grad
 
     def _lengths(self, speech_lengths, cond: TextCond, B: int, N: int, halves: int = 1):
         """(speech, text) device int32 [halves * B] of a varlen call, or None for a dense one.  `speech_lengths`: the B

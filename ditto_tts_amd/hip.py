@@ -202,6 +202,15 @@ SYMBOLS = {
     "ditto_guided_update_packed_tags": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ditto_guided_step_packed_tags_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                                 _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    # speech prompts: the packed update / step that leave each utterance's first prompt_len[b] rows alone; span-masked training
+    "ditto_guided_update_packed_prompt": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_guided_update_packed_tags_prompt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_guided_step_packed_prompt_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i,
+                                                  _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_guided_step_packed_tags_prompt_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
+                                                       _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_span_noise_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ditto_span_mse_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),
     "ditto_regroup_cond_layout": (_i, [C.POINTER(Config), _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),

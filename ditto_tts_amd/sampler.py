@@ -250,11 +250,13 @@ class SpeechGenerator:
     # ---------------------------------------------------------------- strided (DDIM) loop + CFG  
     @torch.no_grad()
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
-                               cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None):
+                               cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None, prompt_lengths=None):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
         DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step, with optional
         classifier-free guidance: the step runs ONE forward on the doubled batch [x; x] x [text; null_text] and combines
         eps_u + w (eps_c - eps_u).  sample_guided with one uniform `cfg_scale` over a dense batch: one library call per step."""
+        if prompt_lengths is not None:
+            raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         if speech_lengths is not None or text_lengths is not None:
             raise NotImplementedError("sample_latents_strided has no varlen form: a variable-length batch runs sample_guided "
                                       "(guided strided loop) or the ancestral sample_latents")
@@ -311,7 +313,7 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
                       null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
-                      cond_by_audio=False, batch_class=None):
+                      cond_by_audio=False, batch_class=None, prompt_lengths=None):
         """The strided (DDIM) loop of sample_latents_strided with what serving needs: per-utterance `speech_lengths` /
         `text_lengths` (a padded batch; rows past an utterance's length are exactly 0 in the result and padding never reaches a
         valid row), per-utterance `guidance` (None: no CFG; a number; or [B] numbers), and per-utterance `seeds`.  One library
@@ -324,7 +326,10 @@ class SpeechGenerator:
         else torch.randn_like.  Step i's z (when sigma != 0): Philox of `seeds` at tag tau_i, `noises[i]` (a sequence or
         callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
         count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
-        Returns fp32 [B, N, d]."""
+        The padded layout has no speech prompts (`prompt_lengths` raises NotImplementedError): pack the batch and call
+        sample_guided_packed.  Returns fp32 [B, N, d]."""
+        if prompt_lengths is not None:
+            raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         B, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
 
         def begin(eng, cfg, seeds):
@@ -357,7 +362,7 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
-                             batch_class=None):
+                             batch_class=None, prompt_lengths=None):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -366,13 +371,20 @@ class SpeechGenerator:
         gives its own offsets.  `seeds`: x_T = ditto_noise_normal(seeds, 0xFFFFFFFF) per utterance and Philox z at each step's tag,
         the bits sample_guided(seeds=) draws for the same utterance.  `noises[i]` (a sequence or callable): packed [S, d].
         `batch_class`: class_rows = (2 with guidance, else 1) * batch_class * max length, what sample_guided pins for the padded
-        batch of batch_class utterances.  Returns fp32 [S, d]."""
+        batch of batch_class utterances.
+        `prompt_lengths` (list / tuple / int tensor [B], 0 <= P_b < N_b): a SPEECH PROMPT per utterance — the first P_b rows of
+        utterance b in `audio_emb` are the target speaker's clean latents; they stand in front of the frames to generate at every
+        step (the forward attends to them like to any rows) and come back bit-equal.  The other G_b = N_b - P_b rows start from x_T —
+        with `seeds`, ditto_noise_normal(seed_b, 0xFFFFFFFF) over G_b rows, what an unprompted utterance of G_b frames starts from —
+        and every step is one ditto_guided_step_packed_prompt_opts call whose update skips the prompt rows.  A model uses a prompt
+        only if it was trained with one (DiTTO.span_noise_packed / span_loss_packed).  Returns fp32 [S, d]."""
         require_fused_attention(self.ditto_model.cfg, "packed batches")
-        from .varlen import pack, validate_cu_seqlens
+        from .varlen import pack, validate_cu_seqlens, validate_prompt_lengths
         S, d = int(audio_emb.shape[0]), int(audio_emb.shape[1])
         B = len(cu_seqlens) - 1
         cu = validate_cu_seqlens(cu_seqlens, B, S, S, "cu_seqlens")
         N = int((cu[1:] - cu[:-1]).max())
+        pl = None if prompt_lengths is None else validate_prompt_lengths(prompt_lengths, cu)
 
         def begin(eng, cfg, seeds):
             if null_text_cu_seqlens is not None and not cfg:
@@ -391,6 +403,19 @@ class SpeechGenerator:
             cond = eng.prepare_text_packed(text, ct)
             offsets = eng.guided_offsets_packed(cu, S, N, cfg)
             x2 = torch.empty(2 * S if cfg else S, d, dtype=torch.float32, device=eng.device)
+            if pl is not None:
+                x2[:S].copy_(audio_emb)                          # the prompts (and, with cond_by_audio, the start of the rest)
+                if not cond_by_audio:
+                    gl = (cu[1:] - cu[:-1] - pl).tolist()        # generated rows per utterance, and where they sit in the batch
+                    at = torch.cat([torch.arange(int(cu[b]) + int(pl[b]), int(cu[b + 1])) for b in range(B)]).to(eng.device)
+                    if seeds is not None:                        # x_T of an unprompted utterance of G_b rows with that seed
+                        xt = torch.empty(B, max(gl), d, dtype=torch.float32, device=eng.device)
+                        eng.noise_normal_(xt, seeds, 0xFFFFFFFF)
+                        xt = pack(xt, gl)[0]
+                    else:
+                        xt = torch.randn(len(at), d, dtype=torch.float32, device=eng.device)
+                    x2[:S].index_copy_(0, at, xt)
+                return x2, N, functools.partial(eng.guided_step_packed_, x2, cond, B=B, offsets=offsets, prompt_len=pl.to(eng.device))
             if seeds is not None and not cond_by_audio:
                 # x_T: ditto_noise_normal over the padded [B, N, d] (the numbers of sample_guided(seeds=)), packed row by row
                 xt = torch.empty(B, N, d, dtype=torch.float32, device=eng.device)

@@ -40,12 +40,14 @@ class StreamHandle:
 
 class Request:
     """One utterance of a stream: what was submitted, and where it stands (index `i` of its schedule; its slot `b`, speech row
-    `row` and conditioning rows `trow` / `nrow` in the batch's CURRENT buffers once admitted)."""
+    `row` and conditioning rows `trow` / `nrow` in the batch's CURRENT buffers once admitted).  `prompt` ([P, d] or None): the
+    speech prompt that stands in front of the `n_frames` generated rows; the utterance occupies `rows` = P + n_frames rows."""
     __slots__ = ("handle", "text", "null", "T", "T_null", "n_frames", "seed", "w", "n_steps", "eta", "x_T", "schedule", "i", "b",
-                 "row", "trow", "nrow")
+                 "row", "trow", "nrow", "prompt", "P")
 
-    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule):
+    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None):
         self.handle, self.text, self.null = handle, text, null
+        self.prompt, self.P = prompt, 0 if prompt is None else int(prompt.shape[0])
         self.T, self.T_null = int(text.shape[0]), 0 if null is None else int(null.shape[0])
         self.n_frames, self.seed, self.w, self.n_steps, self.eta, self.x_T = n_frames, seed, w, n_steps, eta, x_T
         self.schedule, self.i = schedule, 0
@@ -54,6 +56,10 @@ class Request:
     @property
     def text_rows(self) -> int:
         return self.T + self.T_null
+
+    @property
+    def rows(self) -> int:
+        return self.P + self.n_frames
 
 
 class Plan:
@@ -64,13 +70,13 @@ class Plan:
 
     def __init__(self, members, newcomers, guided):
         self.members, self.newcomers = list(members), list(newcomers)
-        self.cu, self.cu_text = _cumulate(r.n_frames for r in members), _cumulate(r.T for r in members)
+        self.cu, self.cu_text = _cumulate(r.rows for r in members), _cumulate(r.T for r in members)
         self.cu_null = _cumulate(r.T_null for r in members) if guided else None
 
 
 class StepArgs:
     """One step over the batch in flight: per-utterance lists in slot order."""
-    __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles")
+    __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt")
 
 
 def _cumulate(lengths) -> List[int]:
@@ -86,8 +92,9 @@ def _is_int(v) -> bool:
 
 class GuidedStream:
     """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None)
-    h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None)
-    done = stream.step()          # [(handle, latents fp32 [N_b, d] on the GPU), ...]
+    h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None,
+                      prompt=None)
+    done = stream.step()          # [(handle, latents fp32 [n_frames, d] on the GPU), ...]
     stream.pending, stream.active, stream.drain()
 
     Capacities: `max_rows` speech rows, `max_utterances` utterances and `max_text_rows` rows of the conditioning (text rows, plus
@@ -95,7 +102,10 @@ class GuidedStream:
     `guided=False`: none does (a mix would waste the unconditional half of the doubled batch).
     x_T of a request: `x_T` when given, else Philox of its `seed` at tag 0xFFFFFFFF — ditto_noise_normal's numbers, what
     sample_guided_packed(seeds=) starts from.  Every step's z is Philox of the seed at the step's tag.  `seed=None` draws one from
-    torch's default CPU generator at submit."""
+    torch's default CPU generator at submit.
+    `prompt` (floating [P, d], P >= 1): a speech prompt — the target speaker's clean latents, kept in front of the `n_frames`
+    generated rows at every step (sample_guided_packed(prompt_lengths=)).  The request then occupies P + n_frames of `max_rows`;
+    `x_T` stays [n_frames, d] and so does the result."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
                  text_dim: int, hidden_dim: int):
@@ -137,7 +147,8 @@ class GuidedStream:
             raise ValueError(f"{name}: shape [rows >= 1, {self.text_dim}] expected, got {list(t.shape)}")
         return t.detach()
 
-    def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None) -> StreamHandle:
+    def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None,
+               prompt=None) -> StreamHandle:
         """Queue one utterance.  Everything is validated here, on the host: a bad request raises ValueError and leaves the stream as
         it was; so does one that could never fit the capacities."""
         text = self._text(text_emb, "text_emb")
@@ -166,10 +177,16 @@ class GuidedStream:
             if not isinstance(x_T, torch.Tensor) or not x_T.dtype.is_floating_point or tuple(x_T.shape) != (n_frames, self.hidden_dim):
                 raise ValueError(f"x_T: a floating-point tensor [{n_frames}, {self.hidden_dim}] is needed")
             x_T = x_T.detach()
+        if prompt is not None:
+            if (not isinstance(prompt, torch.Tensor) or not prompt.dtype.is_floating_point or prompt.dim() != 2 or prompt.shape[0] < 1
+                    or prompt.shape[1] != self.hidden_dim):
+                raise ValueError(f"prompt: a floating-point tensor [P >= 1, {self.hidden_dim}] is needed")
+            prompt = prompt.detach()
         req = Request(StreamHandle(self._next_id), text, null, n_frames, seed, None if guidance is None else float(guidance), n_steps,
-                      float(eta), x_T, schedule)
-        if req.n_frames > self.max_rows:
-            raise ValueError(f"a request of {req.n_frames} frames can never fit max_rows = {self.max_rows}")
+                      float(eta), x_T, schedule, prompt)
+        if req.rows > self.max_rows:
+            raise ValueError(f"a request of {req.rows} rows ({req.P} prompt + {req.n_frames} frames) can never fit max_rows = "
+                             f"{self.max_rows}")
         if req.text_rows > self.max_text_rows:
             raise ValueError(f"a request of {req.text_rows} conditioning rows can never fit max_text_rows = {self.max_text_rows}")
         self._next_id += 1
@@ -178,7 +195,7 @@ class GuidedStream:
 
     def _fits(self, req: Request, members: List[Request]) -> bool:
         return (len(members) + 1 <= self.max_utterances
-                and sum(r.n_frames for r in members) + req.n_frames <= self.max_rows
+                and sum(r.rows for r in members) + req.rows <= self.max_rows
                 and sum(r.text_rows for r in members) + req.text_rows <= self.max_text_rows)
 
     def step(self):
@@ -219,8 +236,8 @@ class GuidedStream:
 
     def _step_args(self, members: List[Request]) -> StepArgs:
         s = StepArgs()
-        s.B, s.S = len(members), sum(r.n_frames for r in members)
-        s.max_N = max(r.n_frames for r in members)
+        s.B, s.S = len(members), sum(r.rows for r in members)
+        s.max_N = max(r.rows for r in members)
         s.S_T = sum(r.text_rows for r in members)
         s.max_T = max(max(r.T, r.T_null) for r in members)
         rows = [r.schedule[r.i] for r in members]                   # (tau, a, ce, sigma) of each utterance's own step
@@ -230,6 +247,7 @@ class GuidedStream:
         s.w = [r.w for r in members] if self.guided else None
         s.seeds = [r.seed for r in members]
         s.handles = [r.handle for r in members]
+        s.prompt = [r.P for r in members]
         return s
 
 
@@ -265,6 +283,34 @@ _SRC_X, _SRC_XT, _SRC_COND, _SRC_NEW_COND, _SRC_TABLE = range(5)
 _DST_X, _DST_OUT, _DST_COND, _DST_OFFSETS = range(4)
 
 
+def speech_segments(r: Request, new: bool, j: int, dst_row: int, xt_row: int, d4: int, dup: int) -> List[List[int]]:
+    """The segments that put utterance `r` (slot j) at row `dst_row` of the next state, in 16-byte units (d4 per row).  A survivor
+    moves as one range, prompt included.  A newcomer: its prompt, staged at row `xt_row` of the x_T buffer, is copied in front;
+    behind it its own x_T (staged after the prompt) is copied, or drawn from its seed — the draw counts its units from 0, so the
+    generated rows get ditto_noise_normal's numbers for an utterance of n_frames rows.  `dup`: the unconditional half's offset."""
+    if not new:
+        return [[hip.REGROUP_COPY, _SRC_X, _DST_X, 0, r.row * d4, dst_row * d4, r.rows * d4, dup]]
+    segs = []
+    if r.P:
+        segs.append([hip.REGROUP_COPY, _SRC_XT, _DST_X, 0, xt_row * d4, dst_row * d4, r.P * d4, dup])
+    if r.x_T is not None:
+        segs.append([hip.REGROUP_COPY, _SRC_XT, _DST_X, 0, (xt_row + r.P) * d4, (dst_row + r.P) * d4, r.n_frames * d4, dup])
+    else:
+        segs.append([hip.REGROUP_DRAW, 0, _DST_X, j, 0, (dst_row + r.P) * d4, r.n_frames * d4, dup])
+    return segs
+
+
+def staged_rows(r: Request) -> int:
+    """rows of the x_T staging buffer a newcomer takes: its prompt, then its own x_T"""
+    return r.P + (r.n_frames if r.x_T is not None else 0)
+
+
+def retire_segments(done: List[Request], d4: int) -> List[List[int]]:
+    """the generated rows of the utterances that leave (their prompts stay behind), one behind the other in the output"""
+    cu = _cumulate(r.n_frames for r in done)
+    return [[hip.REGROUP_COPY, _SRC_X, _DST_OUT, 0, (r.row + r.P) * d4, cu[k] * d4, r.n_frames * d4, 0] for k, r in enumerate(done)]
+
+
 class DeviceBatch:
     """The packed batch of a GuidedStream on one GPU.  Buffers (sized once from the capacities): two state buffers [2 max_rows, d]
     ([max_rows, d] unguided) and two conditioning images (a regroup reads one and writes the other), a staging image for the
@@ -294,11 +340,12 @@ class DeviceBatch:
             self.x_T = torch.zeros(self.maxS, d, dtype=torch.float32, device=dev)
             self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
             self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
-            # the step block: t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w fp32 [maxB] | tags uint32 [maxB]
+            # the step block: t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w fp32 [maxB] | tags uint32 [maxB] |
+            # prompt_len int32 [maxB]
             self.o_t, self.o_seeds = 0, _pad(nbB * 8, 16)
             self.o_f = self.o_seeds + _pad(self.maxB * 8, 16)
             self.f_stride = _pad(self.maxB * 4, 16)
-            self.block = _Upload(self.o_f + 5 * self.f_stride, dev)
+            self.block = _Upload(self.o_f + 6 * self.f_stride, dev)
             self.max_seg = 8 * self.maxB + 8
             self.table = _Upload(self.max_seg * 4 * hip.REGROUP_SEG_WORDS + 2 * self.cu_pad * 4, dev)
             engine.workspace_packed(nbB, self.halves * self.maxS, self.maxT)
@@ -311,7 +358,7 @@ class DeviceBatch:
     # ------------------------------------------------------------------ uploads
     def _send_block(self, a: StepArgs):
         B, nb = a.B, self.halves * a.B
-        buf = np.zeros(self.o_f + 5 * self.f_stride, dtype=np.uint8)
+        buf = np.zeros(self.o_f + 6 * self.f_stride, dtype=np.uint8)
         buf[self.o_t:self.o_t + nb * 8].view(np.int64)[:] = a.t * self.halves
         buf[self.o_seeds:self.o_seeds + B * 8].view(np.int64)[:] = a.seeds
         for k, v in enumerate((a.a, a.ce, a.cz, a.w if a.w is not None else [0.0] * B)):
@@ -319,6 +366,8 @@ class DeviceBatch:
             buf[o:o + B * 4].view(np.float32)[:] = v
         o = self.o_f + 4 * self.f_stride
         buf[o:o + B * 4].view(np.uint32)[:] = a.tags
+        o = self.o_f + 5 * self.f_stride
+        buf[o:o + B * 4].view(np.int32)[:] = a.prompt
         self.block.send(buf)
 
     def _block_ptr(self, off: int) -> int:
@@ -378,16 +427,13 @@ class DeviceBatch:
         segs = []
         for j, r in enumerate(plan.members):
             new = r.handle.id in new_at
-            n_x = r.n_frames * d4
-            dup = S * d4 if self.guided else 0
-            if not new:
-                segs.append([hip.REGROUP_COPY, _SRC_X, _DST_X, 0, r.row * d4, plan.cu[j] * d4, n_x, dup])
-            elif r.x_T is not None:
-                self.x_T[xt_row:xt_row + r.n_frames].copy_(r.x_T, non_blocking=True)
-                segs.append([hip.REGROUP_COPY, _SRC_XT, _DST_X, 0, xt_row * d4, plan.cu[j] * d4, n_x, dup])
-                xt_row += r.n_frames
-            else:
-                segs.append([hip.REGROUP_DRAW, 0, _DST_X, j, 0, plan.cu[j] * d4, n_x, dup])
+            if new and r.P:
+                self.x_T[xt_row:xt_row + r.P].copy_(r.prompt, non_blocking=True)
+            if new and r.x_T is not None:
+                self.x_T[xt_row + r.P:xt_row + r.P + r.n_frames].copy_(r.x_T, non_blocking=True)
+            segs.extend(speech_segments(r, new, j, plan.cu[j], xt_row, d4, S * d4 if self.guided else 0))
+            if new:
+                xt_row += staged_rows(r)
             # conditioning: K/V rows and the tmod row of the text, then of the null text ([text_0 .. ; null_0 ..] under CFG)
             if new:
                 base, own_tmod = new_at[r.handle.id], new_at[r.handle.id] + self._tmod_offset(r.text_rows)
@@ -417,28 +463,31 @@ class DeviceBatch:
         self._block_sent = True
 
     def step(self, a: StepArgs):
-        """ditto_guided_step_packed_tags_opts over the batch in flight, in place on the current state"""
+        """ditto_guided_step_packed_tags_opts over the batch in flight, in place on the current state (with a prompted utterance
+        in flight: ditto_guided_step_packed_tags_prompt_opts, the prompt lengths riding in the step block)"""
         if not self._block_sent:
             self._send_block(a)
         self._block_sent = False
         eng, f = self.eng, self.o_f
         nb, rows = self.halves * a.B, self.halves * a.S
         ws = eng.workspace_packed(nb, rows, a.S_T)
-        hip.check(self.lib.ditto_guided_step_packed_tags_opts(
+        if any(a.prompt):
+            entry, head = self.lib.ditto_guided_step_packed_tags_prompt_opts, (self._block_ptr(f + 5 * self.f_stride),)
+        else:
+            entry, head = self.lib.ditto_guided_step_packed_tags_opts, ()
+        hip.check(entry(
             eng.handle, self.x[self.cur].data_ptr(), self.cond[self.cur].data_ptr(), self._block_ptr(self.o_t), self.offsets.data_ptr(),
-            self.offsets.data_ptr() + 4 * self.cu_pad, None, self._block_ptr(self.o_seeds), self._block_ptr(f + 4 * self.f_stride),
+            self.offsets.data_ptr() + 4 * self.cu_pad, *head, None, self._block_ptr(self.o_seeds), self._block_ptr(f + 4 * self.f_stride),
             self._block_ptr(f + 3 * self.f_stride) if self.guided else None, self._block_ptr(f), self._block_ptr(f + self.f_stride),
             self._block_ptr(f + 2 * self.f_stride), a.B, a.S, a.max_N, a.S_T, a.max_T, int(self.guided), self.rope[0].data_ptr(),
             self.rope[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if self.opts is None else C.byref(self.opts)))
 
     def retire(self, done: List[Request]) -> List[torch.Tensor]:
-        """the packed rows of the utterances that leave, copied out of the state in one launch; the batch keeps its layout (with
+        """the generated rows of the utterances that leave, copied out of the state in one launch; the batch keeps its layout (with
         holes) until the next regroup"""
         cu = _cumulate(r.n_frames for r in done)
         out = torch.empty(cu[-1], self.d, dtype=torch.float32, device=self.eng.device)
-        d4 = self.d // 4
-        segs = [[hip.REGROUP_COPY, _SRC_X, _DST_OUT, 0, r.row * d4, cu[k] * d4, r.n_frames * d4, 0] for k, r in enumerate(done)]
-        self._run_table(segs, None, out)
+        self._run_table(retire_segments(done, self.d // 4), None, out)
         return [out[cu[k]:cu[k + 1]] for k in range(len(done))]
 
 

@@ -31,6 +31,32 @@ def validate_lengths(lengths, B: int, maxlen: int, name: str = "lengths") -> tor
     return t.to(torch.int32)
 
 
+def validate_prompt_lengths(prompt_lengths, cu, name: str = "prompt_lengths") -> torch.Tensor:
+    """Speech-prompt lengths of a packed batch: `prompt_lengths` (list / tuple of ints, or an integer tensor) as a CPU int32 tensor
+    [B] with 0 <= P_b < N_b (N_b from the validated offsets `cu` [B + 1]: at least one row of every utterance is generated).
+    Anything else raises ValueError naming the utterance."""
+    B = len(cu) - 1
+    if isinstance(prompt_lengths, torch.Tensor):
+        if prompt_lengths.dtype.is_floating_point or prompt_lengths.dtype.is_complex or prompt_lengths.dtype == torch.bool:
+            raise ValueError(f"{name}: an integer tensor is needed, got {prompt_lengths.dtype}")
+        t = prompt_lengths.detach().to("cpu", torch.int64)
+    elif isinstance(prompt_lengths, (list, tuple)):
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in prompt_lengths):
+            raise ValueError(f"{name}: a list / tuple of ints is needed")
+        t = torch.tensor(list(prompt_lengths), dtype=torch.int64)
+    else:
+        raise ValueError(f"{name}: a list, tuple or integer tensor is needed, got {type(prompt_lengths).__name__}")
+    if t.dim() != 1 or t.shape[0] != B:
+        raise ValueError(f"{name}: shape [{B}] expected, got {list(t.shape)}")
+    n = torch.as_tensor(cu).detach().to("cpu", torch.int64)
+    n = n[1:] - n[:-1]
+    bad = torch.nonzero((t < 0) | (t >= n)).reshape(-1)
+    if bad.numel():
+        b = int(bad[0])
+        raise ValueError(f"{name}: utterance {b} has {int(n[b])} rows, its prompt must hold 0 .. {int(n[b]) - 1} of them, got {int(t[b])}")
+    return t.to(torch.int32)
+
+
 def _dev_lengths(lengths, B, maxlen, name, device):
     if lengths is None:
         return None

@@ -570,6 +570,49 @@ int ditto_guided_step_packed_tags_opts(ditto_model_t m, float* x2, const void* c
                                        const float* w, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
                                        int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                                        size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+/* ---- Speech prompts (zero-shot voice cloning): the first prompt_len[b] rows of utterance b are the target speaker's clean latents,
+ * placed in front of the frames to generate.  The forward sees them like any other rows; the update leaves them alone.  The reference
+ * has no prompting: like the strided loop and the guidance, this is pinned by its own formulas.
+ * ditto_guided_update_packed_prompt / ditto_guided_update_packed_tags_prompt: ditto_guided_update_packed / _tags over rows
+ *   [cu[b] + P_b, cu[b+1]) only, P_b = prompt_len[b] (device int32 [B], shared by both halves under cfg) clamped into [0, n_b - 1] on
+ *   the device: a bad value gives wrong rows, never an access outside the buffers.  The prompt rows of x2 (both halves) and of eps2
+ *   are neither read nor written.  The Philox quad index is local to the generated rows, ((row - cu[b] - P_b) d + col) / 4: a
+ *   prompted utterance draws what an unprompted one of n_b - P_b rows draws, and prompt_len all 0 is the unprompted entry bit for
+ *   bit.  `noise` stays packed [S, d] like x (its prompt rows are not read).
+ * ditto_guided_step_packed_prompt_opts / ditto_guided_step_packed_tags_prompt_opts: the step entries with that update; the forward
+ *   is unchanged. */
+int ditto_guided_update_packed_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
+                                      const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                      const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream);
+int ditto_guided_update_packed_tags_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                           const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                           const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream);
+int ditto_guided_step_packed_prompt_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                         const int32_t* cu_text, const int32_t* prompt_len, const float* noise, const int64_t* seeds,
+                                         uint32_t step, const float* w, const float* a, const float* ce, const float* cz, int B, int S,
+                                         int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
+                                         void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                              const int32_t* cu_text, const int32_t* prompt_len, const float* noise, const int64_t* seeds,
+                                              const uint32_t* tags, const float* w, const float* a, const float* ce, const float* cz,
+                                              int B, int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos,
+                                              const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
+                                              const ditto_call_opts* opts);
+/* Span-masked training over a packed batch with prompts (cu, prompt_len and their clamp as above; every buffer fp32 [S, d]).  z is
+ *   either `noise`, a packed buffer whose prompt rows are not read, or Philox of (seeds[b], tag) at the generated-local quad index:
+ *   exactly one of the two is given.
+ * ditto_span_noise_packed: x_in = x0 on the prompt rows (a bit copy), fmaf(ca[b], x0, cs[b] z) on the generated rows; ca, cs device
+ *   fp32 [B].
+ * ditto_span_mse_packed: loss[0] = (1 / n_elems) sum over the generated rows of (eps - z)^2; grad_eps = (2 / n_elems) (eps - z) there
+ *   and exactly 0 on the prompt rows, where eps is not read.  n_elems = d x the number of generated rows.  With seeds the noise is
+ *   regenerated and never exists in memory.  No atomics: per-workgroup partial sums go to `workspace` (B x min(1024, ceil(max_N d /
+ *   1024)) floats) and a second launch adds them in index order, so a repeated call gives the same bits. */
+int ditto_span_noise_packed(const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca, const float* cs,
+                            const int32_t* cu, const int32_t* prompt_len, float* x_in, int B, int S, int max_N, int d,
+                            ditto_stream_t stream);
+int ditto_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
+                          const int32_t* prompt_len, size_t n_elems, float* grad_eps, float* loss, void* workspace,
+                          size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream);
 /* ditto_regroup_packed: build the next packed batch from the current one plus the newcomers, in ONE launch driven by a DEVICE table
  *   of n_seg segments.  A segment moves `n` 16-byte units (every row of the state, the K/V cache and tmod is a whole number of them)
  *   to unit dst_off of destination buffer `dest` and, when dup_off != 0, also to dst_off + dup_off (a speech segment under CFG: the
