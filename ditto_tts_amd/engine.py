@@ -85,25 +85,39 @@ class DenoiseEngine:
         self._pack(state)
 
     # ------------------------------------------------------------------ weights
-    def _pack(self, state: Mapping[str, torch.Tensor]):
-        keep = []  # fp32 device staging copies must outlive the (stream-ordered) pack kernels
+    def _struct(self, state: Mapping[str, torch.Tensor], ptr=None, globals_: bool = True, skip=()):
+        """One ditto_weights (ditto_grads has the same layout) over `state`: field f <- ptr(f's state_dict key), for every layer
+        and, with `globals_`, for the model-level fields but `skip`.  `ptr` None: the address of the key's tensor as fp32 on this
+        device — no copy when it already is fp32, contiguous and here (an nn.Parameter itself), else a staging copy that the
+        keepalive holds.  Returns (struct, keepalive)."""
+        keep = []
 
-        def dev(key):
+        def staged(key):
             if key not in state:
                 raise KeyError(f"state_dict is missing '{key}'")
             t = state[key].detach().to(device=self.device, dtype=torch.float32).contiguous()
             keep.append(t)
             return t.data_ptr()
 
+        ptr = ptr or staged
         L = self.cfg.num_layers
         layers = (hip.LayerWeights * L)()
         for l in range(L):
             for f, k in hip.LAYER_KEY.items():
-                setattr(layers[l], f, dev(f"blocks.{l}.{k}"))
+                setattr(layers[l], f, ptr(f"blocks.{l}.{k}"))
         w = hip.Weights()
-        for f, k in hip.GLOBAL_KEY.items():
-            setattr(w, f, dev(k))
+        if globals_:
+            for f, k in hip.GLOBAL_KEY.items():
+                if f not in skip:
+                    setattr(w, f, ptr(k))
         w.layers = layers
+        keep.append(layers)
+        return w, keep
+
+    _pack_globals = True    # False: an engine over DiT blocks only (ditto_model_create with NULL model-level weights)
+
+    def _pack(self, state: Mapping[str, torch.Tensor]):
+        w, keep = self._struct(state, globals_=self._pack_globals)  # staging copies must outlive the (stream-ordered) pack kernels
         with torch.cuda.device(self.device):
             if self.handle:
                 hip.check(self.lib.ditto_model_destroy(self.handle))
@@ -126,14 +140,15 @@ class DenoiseEngine:
             pass
 
     # ------------------------------------------------------------------ buffers
-    def _grow_ws(self, need: int) -> torch.Tensor:
-        """the one workspace, grown to `need` bytes (0: the library refused the shape)"""
+    def _grow_ws(self, need: int, attr: str = "_ws") -> torch.Tensor:
+        """the grow-only buffer `attr` (the one workspace; "_train_ws": the training step's), grown to `need` bytes (0: the
+        library refused the shape)"""
         if need == 0:
             raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        if getattr(self, attr, None) is None or getattr(self, attr).numel() < need:
+            setattr(self, attr, None)       # the old buffer goes before the new one comes
+            setattr(self, attr, torch.empty(need, dtype=torch.uint8, device=self.device))
+        return getattr(self, attr)
 
     def workspace(self, B: int, N: int, T: int) -> torch.Tensor:
         return self._grow_ws(self.lib.ditto_workspace_bytes(C.byref(self._ccfg), B, N, T))
@@ -575,28 +590,6 @@ class DenoiseEngine:
         return h
 
     # ------------------------------------------------------------------ training
-    def _weights_struct(self, state: Mapping[str, torch.Tensor]):
-        """ditto_weights over the CURRENT fp32 CUDA tensors of `state` (no copies when they already are fp32,
-        contiguous and on this device: the nn.Parameters themselves).  Returns (struct, keepalive)."""
-        keep = []
-
-        def dev(key):
-            t = state[key].detach().to(device=self.device, dtype=torch.float32).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        L = self.cfg.num_layers
-        layers = (hip.LayerWeights * L)()
-        for l in range(L):
-            for f, k in hip.LAYER_KEY.items():
-                setattr(layers[l], f, dev(f"blocks.{l}.{k}"))
-        w = hip.Weights()
-        for f, k in hip.GLOBAL_KEY.items():
-            setattr(w, f, dev(k))
-        w.layers = layers
-        keep.append(layers)
-        return w, keep
-
     def train_attach(self, state: Mapping[str, torch.Tensor]):
         """Pack the transposed weight copies the dgrad GEMMs read (after every weight change)."""
         nb = self.lib.ditto_train_arena_bytes(C.byref(self._ccfg))
@@ -604,20 +597,17 @@ class DenoiseEngine:
             self._train_arena = torch.empty(nb, dtype=torch.uint8, device=self.device)
             self._tapes = {}
             self._train_ws = None
-        w, keep = self._weights_struct(state)
+        w, keep = self._struct(state)
         hip.check(self.lib.ditto_train_attach(self.handle, C.byref(w), self._train_arena.data_ptr(), nb, _stream()))
         torch.cuda.current_stream().synchronize()
         self._train_attached = True
 
-    def _train_workspace(self, B, N, T):
-        need = self.lib.ditto_train_workspace_bytes(C.byref(self._ccfg), B, N, T)
-        if need == 0:
-            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
-        if self._train_ws is None or self._train_ws.numel() < need:
-            self._train_ws = None
-            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._train_ws
+    def _require_attached(self):
+        if not getattr(self, "_train_attached", False):
+            raise RuntimeError("train_attach() has not been called for the current weights")
 
+    # the two tape pools differ on purpose (tests assert both): a padded tape is pooled by its shape (B, N, T) and keeps its record in
+    # the handle when released; a packed tape is pooled by capacity and its record is forgotten on release
     def _take_tape(self, B, N, T):
         need = self.lib.ditto_tape_bytes(C.byref(self._ccfg), B, N, T)
         pool = self._tapes.setdefault((B, N, T), [])
@@ -648,15 +638,6 @@ class DenoiseEngine:
         hip.check(self.lib.ditto_train_tape_forget(self.handle, tape.data_ptr()))
         self._tapes.setdefault("packed", []).append(tape)
 
-    def _train_workspace_packed(self, B, S, max_N, S_T, max_T):
-        need = self.lib.ditto_train_workspace_bytes_packed(C.byref(self._ccfg), B, S, max_N, S_T, max_T)
-        if need == 0:
-            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
-        if self._train_ws is None or self._train_ws.numel() < need:
-            self._train_ws = None
-            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._train_ws
-
     def _rope_tables_cap(self, N: int):
         """RoPE tables of at least N rows (row i = position i, whatever the table's length): grown, never shrunk"""
         cur = getattr(self, "_rope_cap", None)
@@ -672,8 +653,7 @@ class DenoiseEngine:
         `state` carries what train_backward_packed needs (tape, inputs, offsets).  Utterance b's rows of eps are what train_forward
         gives for it alone."""
         require_fused_attention(self.cfg, "packed batches")
-        if not getattr(self, "_train_attached", False):
-            raise RuntimeError("train_attach() has not been called for the current weights")
+        self._require_attached()
         xf, text = self._f32(x, "x"), self._f32(text_emb, "text_emb")
         if xf.dim() != 2 or xf.shape[1] != self.cfg.hidden_dim:
             raise ValueError(f"x: [S, {self.cfg.hidden_dim}] expected, got {list(xf.shape)}")
@@ -689,7 +669,7 @@ class DenoiseEngine:
         need = self.lib.ditto_tape_bytes_packed(C.byref(self._ccfg), B, S, S_T)
         if need == 0:
             raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
-        ws = self._train_workspace_packed(B, S, max_N, S_T, max_T)
+        ws = self._grow_ws(self.lib.ditto_train_workspace_bytes_packed(C.byref(self._ccfg), B, S, max_N, S_T, max_T), "_train_ws")
         tape = self._take_tape_packed(need)
         c, s = self._rope_tables_cap(max_N)
         cud, ctd = cu.to(self.device), ct.to(self.device)
@@ -714,50 +694,20 @@ class DenoiseEngine:
         g = self._f32(grad_eps, "grad_output")
         if tuple(g.shape) != (st["S"], self.cfg.hidden_dim):
             raise ValueError(f"grad_output: [{st['S']}, {self.cfg.hidden_dim}] expected, got {list(g.shape)}")
-        w, keep = self._weights_struct(state)
-        keys = [f"blocks.{l}.{k}" for l in range(self.cfg.num_layers) for k in hip.LAYER_KEY.values()] + \
-               [k for f, k in hip.GLOBAL_KEY.items() if f != "rotary_inv_freq"]
-        grads = {k: torch.empty(state[k].shape, dtype=torch.float32, device=self.device) for k in keys}
-        L = self.cfg.num_layers
-        layers = (hip.LayerGrads * L)()
-        for l in range(L):
-            for f, k in hip.LAYER_KEY.items():
-                setattr(layers[l], f, grads[f"blocks.{l}.{k}"].data_ptr())
-        gs = hip.Grads()
-        for f, k in hip.GLOBAL_KEY.items():
-            if f != "rotary_inv_freq":
-                setattr(gs, f, grads[k].data_ptr())
-        gs.layers = layers
-        ws = self._train_workspace_packed(st["B"], st["S"], st["max_N"], st["S_T"], st["max_T"])
+        ws = self._grow_ws(self.lib.ditto_train_workspace_bytes_packed(C.byref(self._ccfg), st["B"], st["S"], st["max_N"], st["S_T"],
+                                                                       st["max_T"]), "_train_ws")
         c, s = st["rope"]
         tape = st["tape"]
-        args = (self.handle, C.byref(w), g.data_ptr(), st["xf"].data_ptr(), st["tt"].data_ptr(), st["cu"].data_ptr(),
-                st["cu_t"].data_ptr(), st["B"], st["S"], st["max_N"], st["S_T"], st["max_T"], c.data_ptr(), s.data_ptr(),
-                st["dropout_p"], st["seed"], tape.data_ptr(), tape.numel(), C.byref(gs), ws.data_ptr(), ws.numel(), _stream(),
-                None if opts is None else C.byref(opts))
-        if piece_cb is None:
-            hip.check(self.lib.ditto_train_backward_packed_layers(*args, L - 1, 0))
-            return grads
-        head = ("proj_in.weight", "proj_in.bias", "proj_out.weight", "proj_out.bias")     # written by the piece that starts at the top
-        tail = [k for f, k in hip.GLOBAL_KEY.items() if f != "rotary_inv_freq" and k not in head]   # ... that ends at layer 0
-        step = max(int(layers_per_piece), 1)
-        hi = L - 1
-        while hi >= 0:
-            lo = max(hi - step + 1, 0)
-            hip.check(self.lib.ditto_train_backward_packed_layers(*args, hi, lo))
-            piece = [grads[k] for k in head] if hi == L - 1 else []
-            piece += [grads[f"blocks.{l}.{k}"] for l in range(hi, lo - 1, -1) for k in hip.LAYER_KEY.values()]
-            if lo == 0:
-                piece += [grads[k] for k in tail]
-            piece_cb(piece)
-            hi = lo - 1
-        return grads
+        return self._train_backward(
+            state, None, "ditto_train_backward_packed_layers", g,
+            (st["xf"].data_ptr(), st["tt"].data_ptr(), st["cu"].data_ptr(), st["cu_t"].data_ptr(), st["B"], st["S"], st["max_N"],
+             st["S_T"], st["max_T"], c.data_ptr(), s.data_ptr(), st["dropout_p"], st["seed"], tape.data_ptr(), tape.numel()),
+            ws, opts, piece_cb, layers_per_piece)
 
     def train_forward(self, x, text_emb, t, dropout_p: float, seed: int, opts: Optional[hip.CallOpts] = None):
         """DiTTO.forward in train mode: returns (eps fp32 [B,N,d], tape).  The library records against the tape how it wrote it
         (bf16 or fp32 stream rows): train_backward reads it that way whatever the options are by then."""
-        if not getattr(self, "_train_attached", False):
-            raise RuntimeError("train_attach() has not been called for the current weights")
+        self._require_attached()
         xf, text = self._f32(x, "x"), self._f32(text_emb, "text_emb")
         B, N, d = xf.shape
         T = text.shape[1]
@@ -765,7 +715,7 @@ class DenoiseEngine:
             raise ValueError("x / text_emb shapes do not match the model")
         tt = self._t64(t, B)
         tape = self._take_tape(B, N, T)
-        ws = self._train_workspace(B, N, T)
+        ws = self._grow_ws(self.lib.ditto_train_workspace_bytes(C.byref(self._ccfg), B, N, T), "_train_ws")
         c, s = self.rope_tables(N)
         out = torch.empty_like(xf)
         self._call("ditto_train_forward", self.handle, xf.data_ptr(), text.data_ptr(), tt.data_ptr(), B, N, T,
@@ -784,42 +734,47 @@ class DenoiseEngine:
         the layers below are still being computed."""
         B, N, d = xf.shape
         g = self._f32(grad_eps, "grad_output")
-        w, keep = self._weights_struct(state)
-        keys = [f"blocks.{l}.{k}" for l in range(self.cfg.num_layers) for k in hip.LAYER_KEY.values()] + \
-               [k for f, k in hip.GLOBAL_KEY.items() if f != "rotary_inv_freq"]
+        if g.shape != xf.shape:
+            raise ValueError(f"grad_output: {list(xf.shape)} expected, got {list(g.shape)}")
+        ws = self._grow_ws(self.lib.ditto_train_workspace_bytes(C.byref(self._ccfg), B, N, T), "_train_ws")
+        c, s = self.rope_tables(N)
+        return self._train_backward(
+            state, "ditto_train_backward", "ditto_train_backward_layers", g,
+            (xf.data_ptr(), tt.data_ptr(), B, N, T, c.data_ptr(), s.data_ptr(), float(dropout_p), int(seed), tape.data_ptr(),
+             tape.numel()), ws, opts, piece_cb, layers_per_piece)
+
+    def _train_backward(self, state, plain, layers, g, mid, ws, opts, piece_cb, layers_per_piece):
+        """The backward of either layout.  `plain`: the name of the whole backward's entry (through _call; None: the layers entry
+        over every layer), `layers`: the name of the entry that takes a layer range, `mid`: the layout's own arguments, between
+        grad_output and the gradient struct."""
+        L = self.cfg.num_layers
+        w, keep = self._struct(state)
+        no_grad = ("rotary_inv_freq",)
+        keys = [f"blocks.{l}.{k}" for l in range(L) for k in hip.LAYER_KEY.values()] + \
+               [k for f, k in hip.GLOBAL_KEY.items() if f not in no_grad]
         # one tensor of its own per parameter (the allocator aligns to 512 B): autograd's AccumulateGrad takes such a
         # gradient over as .grad without a copy; views of one flat buffer cost a copy kernel per parameter per step
         grads = {k: torch.empty(state[k].shape, dtype=torch.float32, device=self.device) for k in keys}
-        L = self.cfg.num_layers
-        layers = (hip.LayerGrads * L)()
-        for l in range(L):
-            for f, k in hip.LAYER_KEY.items():
-                setattr(layers[l], f, grads[f"blocks.{l}.{k}"].data_ptr())
-        gs = hip.Grads()
-        for f, k in hip.GLOBAL_KEY.items():
-            if f != "rotary_inv_freq":
-                setattr(gs, f, grads[k].data_ptr())
-        gs.layers = layers
-        ws = self._train_workspace(B, N, T)
-        c, s = self.rope_tables(N)
-        args = (self.handle, C.byref(w), g.data_ptr(), xf.data_ptr(), tt.data_ptr(), B, N, T, c.data_ptr(), s.data_ptr(),
-                float(dropout_p), int(seed), tape.data_ptr(), tape.numel(), C.byref(gs), ws.data_ptr(), ws.numel(), _stream())
-        if piece_cb is None:
-            self._call("ditto_train_backward", *args, opts=opts)
-            return grads
-        if not hip._has_call_opts():
-            # a frozen pre-ABI-9 library (DITTO_HIP_LIB) has no ditto_train_backward_layers: one call, then every tensor as one piece
-            # (the caller's exchange then simply runs after the backward instead of under it)
-            self._call("ditto_train_backward", *args, opts=opts)
-            piece_cb(list(grads.values()))
+        gs, gkeep = self._struct(grads, lambda k: grads[k].data_ptr(), skip=no_grad)
+        args = (self.handle, C.byref(w), g.data_ptr(), *mid, C.byref(gs), ws.data_ptr(), ws.numel(), _stream())
+        o = None if opts is None else C.byref(opts)
+        if piece_cb is None or not hip._has_call_opts():
+            if plain is not None:
+                self._call(plain, *args, opts=opts)
+            else:
+                hip.check(getattr(self.lib, layers)(*args, o, L - 1, 0))
+            if piece_cb is not None:
+                # a frozen pre-ABI-9 library (DITTO_HIP_LIB) has no entry that takes a layer range: one call, then every tensor as
+                # one piece (the caller's exchange then simply runs after the backward instead of under it)
+                piece_cb(list(grads.values()))
             return grads
         head = ("proj_in.weight", "proj_in.bias", "proj_out.weight", "proj_out.bias")     # written by the piece that starts at the top
-        tail = [k for f, k in hip.GLOBAL_KEY.items() if f != "rotary_inv_freq" and k not in head]   # ... that ends at layer 0
+        tail = [k for k in keys[L * len(hip.LAYER_KEY):] if k not in head]                # ... that ends at layer 0
         step = max(int(layers_per_piece), 1)
         hi = L - 1
         while hi >= 0:
             lo = max(hi - step + 1, 0)
-            hip.check(self.lib.ditto_train_backward_layers(*args, None if opts is None else C.byref(opts), hi, lo))
+            hip.check(getattr(self.lib, layers)(*args, o, hi, lo))
             piece = [grads[k] for k in head] if hi == L - 1 else []
             piece += [grads[f"blocks.{l}.{k}"] for l in range(hi, lo - 1, -1) for k in hip.LAYER_KEY.values()]
             if lo == 0:

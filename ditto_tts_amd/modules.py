@@ -20,7 +20,6 @@ and `text_emb` (frozen-encoder outputs in the reference) — asking for those ra
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
@@ -47,82 +46,40 @@ def _refuse_autograd(module: nn.Module):
 
 
 class _DiTTOTrainFn(torch.autograd.Function):
-    """DiTTO.forward with a tape (ditto_train_forward) and its backward (ditto_train_backward)."""
+    """The trainable forward of either layout with its tape, and its backward.  `run(opts)` runs the layout's engine forward and
+    returns (eps, backward, release): backward(state, grad_output, piece_cb=, layers_per_piece=) is the engine's backward over
+    what that forward left (tape, inputs, options), release() hands the tape back.  `who`: the DiTTO method the caller used."""
 
     @staticmethod
-    def forward(ctx, model, x, text_emb, t, dropout_p, seed, keys, *params):
-        eng = model.engine(x.device, train=True)
+    def forward(ctx, model, who, run, keys, *params):
         # the options in force where forward() is CALLED (a hip.batch_class / hip.call_opts scope of this thread) are this
-        # step's options: autograd runs backward() on its own worker thread, where no such scope exists, so they travel in ctx
-        ctx.opts = hip.current_opts() if hip._has_call_opts() else None
-        out, tape, xf, tt = eng.train_forward(x, text_emb.to(x.device), t, dropout_p, seed, opts=ctx.opts)
-        ctx.model, ctx.eng, ctx.tape, ctx.xf, ctx.tt = model, eng, tape, xf, tt
-        ctx.T, ctx.dropout_p, ctx.seed, ctx.keys = text_emb.shape[1], dropout_p, seed, keys
+        # step's options: autograd runs backward() on its own worker thread, where no such scope exists, so they travel with `run`
+        out, ctx.run_backward, ctx.release_tape = run(hip.current_opts() if hip._has_call_opts() else None)
+        ctx.model, ctx.who, ctx.keys = model, who, keys
         ctx.sig = model._watch.sig
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        model, eng = ctx.model, ctx.eng
+        model = ctx.model
         if model._watch.sig != ctx.sig or model._watch.changed(model._path_tensors()):
             raise RuntimeError("DiTTO parameters changed between forward and backward")
-        if ctx.tape is None:
-            raise RuntimeError("backward through the same DiTTO.forward twice (the activation tape was released)")
+        if ctx.release_tape is None:
+            raise RuntimeError(f"backward through the same {ctx.who} twice (the activation tape was released)")
         sd = {k: v for k, v in model.state_dict(keep_vars=True).items() if not k.startswith("nac.")}
         sync = getattr(model, "_grad_sync", None)      # dist.GradSync: the gradient exchange overlapped with this backward
         try:
-            grads = eng.train_backward(sd, grad_out, ctx.xf, ctx.tt, ctx.T, ctx.tape, ctx.dropout_p, ctx.seed, opts=ctx.opts,
-                                       piece_cb=sync.reduce if sync is not None else None,
-                                       layers_per_piece=getattr(model, "_grad_sync_layers", 1))
+            grads = ctx.run_backward(sd, grad_out, piece_cb=sync.reduce if sync is not None else None,
+                                  layers_per_piece=getattr(model, "_grad_sync_layers", 1))
         except BaseException:
             if sync is not None:
                 sync.abort()                           # no stale tensors in the next step's buckets (ADVICE r5)
             raise
         if sync is not None:
             sync.finish()                              # the compute stream waits for the exchange: the gradients returned are the means
-        B, N, _ = ctx.xf.shape
-        eng.release_tape(ctx.tape, B, N, ctx.T)
-        ctx.tape = None
-        return (None, None, None, None, None, None, None) + tuple(grads.get(k) for k in ctx.keys)
-
-
-class _DiTTOTrainPackedFn(torch.autograd.Function):
-    """DiTTO.train_forward_packed with a tape (ditto_train_forward_packed_opts) and its backward
-    (ditto_train_backward_packed_layers); built like _DiTTOTrainFn."""
-
-    @staticmethod
-    def forward(ctx, model, x, cu_seqlens, text_emb, text_cu_seqlens, t, max_seqlen, max_text_seqlen, dropout_p, seed, keys, *params):
-        eng = model.engine(x.device, train=True)
-        # the options in force at the call site travel to the backward thread in ctx (see _DiTTOTrainFn)
-        ctx.opts = hip.current_opts() if hip._has_call_opts() else None
-        out, st = eng.train_forward_packed(x, cu_seqlens, text_emb.to(x.device), text_cu_seqlens, t, dropout_p, seed,
-                                           max_seqlen=max_seqlen, max_text_seqlen=max_text_seqlen, opts=ctx.opts)
-        ctx.model, ctx.eng, ctx.st, ctx.keys = model, eng, st, keys
-        ctx.sig = model._watch.sig
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        model, eng = ctx.model, ctx.eng
-        if model._watch.sig != ctx.sig or model._watch.changed(model._path_tensors()):
-            raise RuntimeError("DiTTO parameters changed between forward and backward")
-        if ctx.st is None:
-            raise RuntimeError("backward through the same DiTTO.train_forward_packed twice (the activation tape was released)")
-        sd = {k: v for k, v in model.state_dict(keep_vars=True).items() if not k.startswith("nac.")}
-        sync = getattr(model, "_grad_sync", None)
-        try:
-            grads = eng.train_backward_packed(sd, grad_out, ctx.st, opts=ctx.opts,
-                                              piece_cb=sync.reduce if sync is not None else None,
-                                              layers_per_piece=getattr(model, "_grad_sync_layers", 1))
-        except BaseException:
-            if sync is not None:
-                sync.abort()
-            raise
-        if sync is not None:
-            sync.finish()
-        eng.release_tape_packed(ctx.st["tape"])
-        ctx.st = None
-        return (None,) * 11 + tuple(grads.get(k) for k in ctx.keys)
+        ctx.release_tape()
+        ctx.run_backward = ctx.release_tape = None
+        return (None,) * (len(ctx.needs_input_grad) - len(ctx.keys)) + tuple(grads.get(k) for k in ctx.keys)
 
 
 class _ParamWatch:
@@ -248,31 +205,7 @@ class DiT(nn.Module):
 
 class _BlocksOnlyEngine(DenoiseEngine):
     """An engine over DiT blocks only (no model-level weights): ditto_model_create with NULL globals."""
-
-    def _pack(self, state):
-        keep = []
-
-        def dev(key):
-            t = state[key].detach().to(device=self.device, dtype=torch.float32).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-
-        L = self.cfg.num_layers
-        layers = (hip.LayerWeights * L)()
-        for l in range(L):
-            for f, k in hip.LAYER_KEY.items():
-                setattr(layers[l], f, dev(f"blocks.{l}.{k}"))
-        w = hip.Weights()
-        w.layers = layers
-        with torch.cuda.device(self.device):
-            if self.handle:
-                hip.check(self.lib.ditto_model_destroy(self.handle))
-                self.handle = C.c_void_p()
-            hip.check(self.lib.ditto_model_create(C.byref(self._ccfg), C.byref(w), self.arena.data_ptr(),
-                                                  self.arena.numel(), _stream(), C.byref(self.handle)))
-            torch.cuda.current_stream().synchronize()
-        self._rope.clear()
-        self._generation += 1
+    _pack_globals = False
 
 
 class _SpanLossFn(torch.autograd.Function):
@@ -407,6 +340,30 @@ class DiTTO(nn.Module):
             raise NotImplementedError(f"ditto_tts_amd: {what} are inference only (run under torch.no_grad() or with frozen "
                                       "parameters)")
 
+    def _refuse_fp8_training(self):
+        if self.cfg.fp8_linear:
+            raise NotImplementedError("ditto_tts_amd: training with fp8_linear=True is not supported")
+
+    @staticmethod
+    def _refuse_input_grads(x, text_emb):
+        if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad):
+            raise NotImplementedError("ditto_tts_amd: gradients with respect to x / text_emb are not produced (the "
+                                      "reference feeds frozen-encoder outputs, src/TrainDiTTO.py:66-73); detach them")
+
+    def _live_params(self):
+        return [(n, p) for n, p in self.named_parameters() if not n.startswith("nac.") and ".attn.out_proj." not in n]
+
+    def _train(self, x, named, who, step):
+        """The trainable forward of either layout under autograd (`named`: _live_params(); `who`: the calling method, for
+        messages).  step(eng, p_drop, seed, opts) runs the engine's training forward and returns what _DiTTOTrainFn's `run` does."""
+        # cross-attention dropout is active in train mode only (nn.MultiheadAttention(dropout=0.1),
+        # reference src/components/DiT.py:90-91); its mask seed comes from torch's CPU generator
+        p_drop = float(self.blocks[0].cross_attn.dropout) if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0 else 0
+        out = _DiTTOTrainFn.apply(self, who, lambda opts: step(self.engine(x.device, train=True), p_drop, seed, opts),
+                                  tuple(n for n, _ in named), *[p for _, p in named])
+        return out if x.dtype == torch.float32 else out.to(x.dtype)
+
     # ------------------------------------------------------------------ reference surface
     def forward(self, x, text_emb, t, *, speech_lengths=None, text_lengths=None):
         """x [B,N,d] noisy latents, text_emb [B,T,text_dim], t [B] long -> predicted noise [B,N,d]
@@ -421,20 +378,17 @@ class DiTTO(nn.Module):
             cond = self.text_cond(text_emb.to(x.device), x.shape[1], text_lengths=text_lengths)
             out = eng.forward(x, cond, t, speech_lengths=speech_lengths)
             return out if x.dtype == torch.float32 else out.to(x.dtype)
-        if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad):
-            raise NotImplementedError("ditto_tts_amd: gradients with respect to x / text_emb are not produced (the "
-                                      "reference feeds frozen-encoder outputs, src/TrainDiTTO.py:66-73); detach them")
-        named = [(n, p) for n, p in self.named_parameters() if not n.startswith("nac.") and ".attn.out_proj." not in n]
+        self._refuse_input_grads(x, text_emb)
+        named = self._live_params()
         if torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
-            if self.cfg.fp8_linear:
-                raise NotImplementedError("ditto_tts_amd: training with fp8_linear=True is not supported")
-            # cross-attention dropout is active in train mode only (nn.MultiheadAttention(dropout=0.1),
-            # reference src/components/DiT.py:90-91); its mask seed comes from torch's CPU generator
-            p_drop = float(self.blocks[0].cross_attn.dropout) if self.training else 0.0
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0 else 0
-            keys = tuple(n for n, _ in named)
-            out = _DiTTOTrainFn.apply(self, x, text_emb, t, p_drop, seed, keys, *[p for _, p in named])
-            return out if x.dtype == torch.float32 else out.to(x.dtype)
+            self._refuse_fp8_training()
+
+            def step(eng, p_drop, seed, opts):
+                out, tape, xf, tt = eng.train_forward(x, text_emb.to(x.device), t, p_drop, seed, opts=opts)
+                B, N, T = xf.shape[0], xf.shape[1], text_emb.shape[1]
+                return (out, lambda sd, g, **pieces: eng.train_backward(sd, g, xf, tt, T, tape, p_drop, seed, opts=opts, **pieces),
+                        lambda: eng.release_tape(tape, B, N, T))
+            return self._train(x, named, "DiTTO.forward", step)
         eng = self.engine(x.device)
         cond = self.text_cond(text_emb.to(x.device), x.shape[1])
         out = eng.forward(x, cond, t)
@@ -464,11 +418,8 @@ class DiTTO(nn.Module):
         is the mean over real elements).  No gradient for x / text_emb or `.attn.out_proj.*`, as forward.  head_dim 64, bf16
         linears."""
         require_fused_attention(self.cfg, "packed batches")
-        if self.cfg.fp8_linear:
-            raise NotImplementedError("ditto_tts_amd: training with fp8_linear=True is not supported")
-        if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad):
-            raise NotImplementedError("ditto_tts_amd: gradients with respect to x / text_emb are not produced (the "
-                                      "reference feeds frozen-encoder outputs, src/TrainDiTTO.py:66-73); detach them")
+        self._refuse_fp8_training()
+        self._refuse_input_grads(x, text_emb)
         if x.dim() != 2 or text_emb.dim() != 2:
             raise ValueError("train_forward_packed: x [S, d] and text_emb [S_T, text_dim] expected")
         B = len(cu_seqlens) - 1
@@ -479,13 +430,13 @@ class DiTTO(nn.Module):
         if x.shape[1] != self.cfg.hidden_dim or text_emb.shape[1] != self.cfg.text_dim or tuple(t.shape) != (B,):
             raise ValueError(f"train_forward_packed: x [S, {self.cfg.hidden_dim}], text_emb [S_T, {self.cfg.text_dim}] and t [{B}] expected")
         _require_cuda(x, "x")      # the arguments are sound: now the device (there is no CPU path)
-        named = [(n, p) for n, p in self.named_parameters() if not n.startswith("nac.") and ".attn.out_proj." not in n]
-        p_drop = float(self.blocks[0].cross_attn.dropout) if self.training else 0.0
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0 else 0
-        keys = tuple(n for n, _ in named)
-        out = _DiTTOTrainPackedFn.apply(self, x, cu_seqlens, text_emb, text_cu_seqlens, t, max_seqlen, max_text_seqlen, p_drop, seed,
-                                        keys, *[p for _, p in named])
-        return out if x.dtype == torch.float32 else out.to(x.dtype)
+
+        def step(eng, p_drop, seed, opts):
+            out, st = eng.train_forward_packed(x, cu_seqlens, text_emb.to(x.device), text_cu_seqlens, t, p_drop, seed,
+                                               max_seqlen=max_seqlen, max_text_seqlen=max_text_seqlen, opts=opts)
+            return (out, lambda sd, g, **pieces: eng.train_backward_packed(sd, g, st, opts=opts, **pieces),
+                    lambda: eng.release_tape_packed(st["tape"]))
+        return self._train(x, self._live_params(), "DiTTO.train_forward_packed", step)
 
     def train_forward(self, x, text_emb, t, *, speech_lengths, text_lengths):
         """The trainable forward for a batch in the reference's padded collate (src/utils/MLS.py:136-151): x [B, N, d], text_emb
@@ -494,8 +445,7 @@ class DiTTO(nn.Module):
         0, padding contents (NaN included) reach nothing, and gradient arriving on padded rows is dropped.  Speech prompts
         (span_noise_packed / span_loss_packed) exist in the packed layout only: pack the batch first."""
         require_fused_attention(self.cfg, "variable-length batches")
-        if self.cfg.fp8_linear:
-            raise NotImplementedError("ditto_tts_amd: training with fp8_linear=True is not supported")
+        self._refuse_fp8_training()
         if x.dim() != 3 or text_emb.dim() != 3 or text_emb.shape[0] != x.shape[0]:
             raise ValueError("train_forward: x [B, N, d] and text_emb [B, T, text_dim] expected")
         B, N, d = x.shape

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .engine import _stream
 
 
 class StreamHandle:
@@ -489,7 +490,3 @@ class DeviceBatch:
         out = torch.empty(cu[-1], self.d, dtype=torch.float32, device=self.eng.device)
         self._run_table(retire_segments(done, self.d // 4), None, out)
         return [out[cu[k]:cu[k + 1]] for k in range(len(done))]
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream

@@ -19,11 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import hip
+from .engine import _stream
 from .modules import _ParamWatch
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 class SlpEngine:

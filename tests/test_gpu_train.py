@@ -593,3 +593,58 @@ def test_backward_in_layer_pieces_is_bitwise_the_single_call(per_piece):
     assert seen[0][0] == pieces["proj_in.weight"].data_ptr() and seen[-1][-1] == pieces["ada_ln.text_mlp.1.bias"].data_ptr()
     for k, g in whole.items():
         assert torch.equal(pieces[k], g), k
+
+
+class _RecSync:
+    """a GradSync stand-in that records what the backward hands it"""
+
+    def __init__(self):
+        self.pieces, self.aborts, self.finishes = [], 0, 0
+
+    def reduce(self, piece):
+        self.pieces.append([z.data_ptr() for z in piece])
+
+    def abort(self):
+        self.aborts += 1
+
+    def finish(self):
+        self.finishes += 1
+
+
+def test_dense_autograd_in_pieces_through_set_grad_sync_is_bitwise_the_single_call():
+    """DiTTO.forward under autograd with a recording sync (set_grad_sync: one piece per layer) against the same step without one:
+    the same bits name by name, three pieces, every gradient in exactly one piece, finish() once and no abort()"""
+    cfg = DiTTOConfig(256, 3, 4, 64, 256, 20)
+    B, N, T = 2, 96, 40
+    x, text, t = (z.to(DEV) for z in synthetic_inputs(cfg, B, N, T, seed=41))
+    target = hash_normal((B, N, 256), "noise", 42).to(DEV)
+    res = []
+    for sync in (None, _RecSync()):
+        m = _build(cfg, 19).train()
+        m.set_grad_sync(sync, 1)
+        torch.manual_seed(9)
+        F.mse_loss(m(x, text, t), target).backward()
+        res.append({n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None})
+    assert res[0].keys() == res[1].keys() and len(res[0]) > 40
+    for n in res[0]:
+        assert torch.equal(res[0][n], res[1][n]), n
+    flat = [p for piece in sync.pieces for p in piece]
+    assert len(sync.pieces) == 3 and len(flat) == len(set(flat)) == len(res[1])
+    assert (sync.finishes, sync.aborts) == (1, 0)
+
+
+@pytest.mark.parametrize("blocks_only", [False, True])
+def test_pack_names_the_missing_key(blocks_only):
+    """a state dict without one of the keys the pack reads: KeyError that names it, from the full engine and the blocks-only one
+    (which reads no model-level key at all)"""
+    from ditto_tts_amd.engine import DenoiseEngine
+    from ditto_tts_amd.modules import _BlocksOnlyEngine
+    cfg = DiTTOConfig(256, 1, 4, 64, 256, 20)
+    sd = synthetic_state_dict(cfg, 3)
+    if blocks_only:
+        sd = {k: v for k, v in sd.items() if k.startswith("blocks.")}
+        _BlocksOnlyEngine(cfg, sd, DEV)                                   # complete without any model-level key
+    missing = ["blocks.0.norm2.bias"] if blocks_only else ["blocks.0.norm2.bias", "proj_out.bias"]
+    for key in missing:
+        with pytest.raises(KeyError, match=f"state_dict is missing '{key}'"):
+            (_BlocksOnlyEngine if blocks_only else DenoiseEngine)(cfg, {k: v for k, v in sd.items() if k != key}, DEV)

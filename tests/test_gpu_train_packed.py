@@ -401,3 +401,61 @@ def test_tape_records_survive_more_than_64_distinct_tapes():
         assert m.proj_out.weight.grad is not None and torch.isfinite(m.proj_out.weight.grad).all()
     for st in keep:
         eng.release_tape_packed(st["tape"])
+
+
+class _RecSync:
+    def __init__(self):
+        self.pieces, self.aborts, self.finishes = 0, 0, 0
+
+    def reduce(self, piece):
+        self.pieces += 1
+
+    def abort(self):
+        self.aborts += 1
+
+    def finish(self):
+        self.finishes += 1
+
+
+@pytest.mark.parametrize("layout", ["padded", "packed"])
+def test_autograd_refusals_of_both_layouts(layout):
+    """The refusals of the training backward, for DiTTO.forward (B = 2, N = 96, T = 40) and DiTTO.train_forward_packed (the same
+    rows as lengths [96, 96] / [40, 40]): a second backward through the same output names the method the caller used; a parameter
+    changed in place between forward and backward is refused; when the engine's backward raises, the sync's abort() runs once and
+    finish() never.
+    The engine's backward raises on a grad_output of the wrong shape — a host-side check, nothing is launched.  A loss cannot hand
+    one over through backward(): autograd compares every gradient a node returns with the shape of the tensor it belongs to and
+    raises itself before this backward runs.  So the node of the output is applied to the wrong-shaped gradient directly
+    (out.grad_fn.apply is what autograd calls with the gradient it has accepted)."""
+    cfg = DiTTOConfig(256, 3, 4, 64, 256, 20)
+    B, N, T, d = 2, 96, 40, 256
+    x, text, t, target = (z.to(DEV) for z in _inputs(cfg, [N] * B, [T] * B, 81))
+    m = _build(cfg, 5).train()
+    if layout == "padded":
+        x, text, target = x.view(B, N, d), text.view(B, T, d), target.view(B, N, d)
+        who, forward = r"DiTTO\.forward", lambda: m(x, text, t)
+    else:
+        who, forward = r"DiTTO\.train_forward_packed", lambda: m.train_forward_packed(x, _cu([N] * B), text, _cu([T] * B), t)
+    sync = _RecSync()
+    m.set_grad_sync(sync, 1)
+    out = forward()
+    F.mse_loss(out, target).backward()
+    assert (sync.pieces, sync.aborts, sync.finishes) == (3, 0, 1)
+    with pytest.raises(RuntimeError, match=f"backward through the same {who} twice"):
+        F.mse_loss(out, target).backward()
+    assert (sync.pieces, sync.aborts, sync.finishes) == (3, 0, 1)            # refused before the engine ran
+    # the engine's backward raises: abort() once, no finish(), no piece
+    out = forward()
+    with pytest.raises(ValueError, match="grad_output"):
+        out.grad_fn.apply(torch.ones_like(out)[..., :N // 2, :].contiguous())
+    assert (sync.pieces, sync.aborts, sync.finishes) == (3, 1, 1)
+    # ... and the same forward's backward still runs afterwards with a sound gradient (its tape was not released)
+    F.mse_loss(out, target).backward()
+    assert (sync.pieces, sync.aborts, sync.finishes) == (6, 1, 2)
+    # a parameter modified in place between forward and backward
+    out = forward()
+    with torch.no_grad():
+        m.proj_in.bias.add_(1.0)
+    with pytest.raises(RuntimeError, match="parameters changed between forward and backward"):
+        F.mse_loss(out, target).backward()
+    assert (sync.pieces, sync.aborts, sync.finishes) == (6, 1, 2)
