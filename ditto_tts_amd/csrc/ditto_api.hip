@@ -1595,6 +1595,51 @@ int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const 
                               prompt_len, true);
 }
 
+// ---- the second-order multistep solver over packed batches (guided_multistep.hip) ----
+static int check_multistep(const char* who, const float* x2, const float* eps2, const float* q, const ditto_multistep_coef* step,
+                           const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, int B, int max_N, int d, int cfg) {
+    if (!x2 || !eps2 || !q || !cu) return fail(DITTO_ERR_ARG, "%s: null x2 / eps2 / q / cu", who);
+    if (!step == !coefs) return fail(DITTO_ERR_ARG, "%s: exactly one of step (host) and coefs (device [B]) is needed", who);
+    if (step && cfg && !w) return fail(DITTO_ERR_ARG, "%s: classifier-free guidance needs w (fp32 [B])", who);
+    if ((uintptr_t)coefs % 16) return fail(DITTO_ERR_ARG, "%s: coefs must be 16-byte aligned", who);
+    if (B <= 0 || max_N <= 0 || d <= 0) return fail(DITTO_ERR_SHAPE, "%s: B, max_N and d must be positive (B %d, max_N %d, d %d)", who, B, max_N, d);
+    if (d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
+    if (B > 65535) return fail(DITTO_ERR_SHAPE, "%s: more than 65535 utterances", who);
+    return DITTO_OK;
+}
+
+int ditto_multistep_update_packed(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
+                                  const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, const int32_t* prompt_len,
+                                  int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
+    if (int rc = check_multistep("ditto_multistep_update_packed", x2, eps2, q, step, coefs, w, cu, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed("ditto_multistep_update_packed", B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_multistep_update_packed(x2, eps2, q, step, coefs, w, cu, prompt_len, B, S, max_N, d, cfg != 0, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                            const int32_t* cu_text, const int32_t* prompt_len, float* q,
+                                            const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, const float* w, int B,
+                                            int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
+                                            void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    const char* who = "ditto_guided_step_packed_multistep_opts";
+    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    if (int rc = check_multistep(who, x2, x2, q, step, coefs, w, cu_speech, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
+    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
+    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
+    return with_opts(opts, [&]() -> int {
+        const int nb = cfg ? 2 * B : B, rows = cfg ? 2 * S : S;          // the forward of guided_step_packed: [x; x] x [text; null]
+        float* eps;
+        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
+                                  BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
+            return rc;
+        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        HIP_TRY(launch_multistep_update_packed(x2, eps, q, step, coefs, w, cu_speech, prompt_len, B, S, max_N, m->cfg.hidden_dim, cfg != 0,
+                                               (hipStream_t)stream));
+        return DITTO_OK;
+    });
+}
+
 // ---- span-masked training over a packed batch with prompts (span_train.hip) ----
 static int check_span(const char* who, const void* in, const float* noise, const int64_t* seeds, const int32_t* cu,
                       const int32_t* prompt_len, const void* out, int B, int S, int max_N, int d) {

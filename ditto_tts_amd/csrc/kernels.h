@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 struct ditto_regroup_seg;   // include/ditto_hip.h
+struct ditto_multistep_coef;
 
 namespace ditto {
 
@@ -279,6 +280,12 @@ hipError_t launch_guided_update_prompt(float* x2, const float* eps2, const float
                                        const unsigned* tags, bool per_utt, const float* w, const float* a, const float* ce,
                                        const float* cz, const int32_t* cu, const int32_t* prompt_len, int B, int S, int max_N, int d,
                                        bool cfg, hipStream_t s);
+// ---------------- guided_multistep.hip ----------------
+// the DPM-Solver++(2M) update over a packed batch: `step` (host: one step for every utterance, guidance scale w[b]) or `coefs`
+// (device [B]: utterance b's own step and scale); q fp32 [S, d] holds the previous step's x0 prediction; prompt_len may be null
+hipError_t launch_multistep_update_packed(float* x2, const float* eps2, float* q, const ::ditto_multistep_coef* step,
+                                          const ::ditto_multistep_coef* coefs, const float* w, const int32_t* cu,
+                                          const int32_t* prompt_len, int B, int S, int max_N, int d, bool cfg, hipStream_t s);
 // ---------------- span_train.hip ----------------
 // span-masked training over a packed batch with prompts: the noising that keeps the prompt rows, the MSE over the generated rows
 // (n_elems of them) with its gradient; `partial`: span_mse_partials(B, max_N, d) floats

@@ -312,6 +312,41 @@ class DenoiseEngine:
             int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
         return x2
 
+    def guided_step_packed_multistep_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
+                                      coef: hip.MultistepCoef, w: Optional[torch.Tensor] = None, cu_seqlens=None,
+                                      max_seqlen: Optional[int] = None, offsets=None, opts: Optional[hip.CallOpts] = None,
+                                      prompt_len: Optional[torch.Tensor] = None):
+        """guided_step_packed_ with the update of the second-order multistep solver (ditto_guided_step_packed_multistep_opts), IN
+        PLACE on x2 and on the history `q` fp32 [S, d]: the previous step's x0 prediction, read only when coef.use_prev and
+        rewritten by every step.  `coef`: the step every utterance stands at (sampler.multistep_schedule; its w is ignored, the
+        guidance scales are `w` fp32 [B]).  x2, cond, t, offsets, opts, prompt_len: as guided_step_packed_."""
+        self._guided_args("guided_step_packed_multistep_", x2, 2, B, None, None, None, w, None, None)
+        cfg = w is not None
+        nb = 2 * B if cfg else B
+        rows = x2.shape[0]
+        if cfg and rows % 2:
+            raise ValueError("x2 must hold [x; x] under guidance")
+        S = rows // 2 if cfg else rows
+        if not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.shape == (S, x2.shape[1])):
+            raise ValueError(f"q must be a contiguous fp32 CUDA tensor of shape [{S}, {x2.shape[1]}]")
+        self._packed_cond(cond, nb)
+        if offsets is None:
+            offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, cfg)
+        cud, max_N = offsets
+        if cud.shape != (nb + 1,):
+            raise ValueError(f"offsets: [{nb + 1}] expected")
+        if prompt_len is not None and not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous()
+                                           and prompt_len.shape == (B,)):
+            raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        tt = self._t64(t, nb)
+        ws = self.workspace_packed(nb, rows, cond.T)
+        c, s = self.rope_tables(max_N)
+        hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
+            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
+            q.data_ptr(), C.byref(coef), None, _ptr(w), B, S, max_N, cond.T, cond.max_len, int(cfg), c.data_ptr(), s.data_ptr(),
+            ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+        return x2
+
     # ------------------------------------------------------------------ span-masked training (csrc/span_train.hip)
     def _span_args(self, who, buf, cu_seqlens, prompt_lengths, seeds, noise):
         """the checks of span_noise_packed / span_mse_packed: (device offsets, device prompt lengths, B, max_N, generated rows,

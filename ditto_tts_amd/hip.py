@@ -121,6 +121,12 @@ class GemmEpilogueArgs(C.Structure):
                 ("M", C.c_int), ("N", C.c_int), ("K", C.c_int)]
 
 
+class MultistepCoef(C.Structure):
+    """ditto_multistep_coef: one utterance's step of the second-order multistep solver (sampler.multistep_schedule), 32 bytes."""
+    _fields_ = [("a", C.c_float), ("kx", C.c_float), ("ke", C.c_float), ("b", C.c_float), ("g", C.c_float), ("w", C.c_float),
+                ("use_prev", C.c_int32), ("reserved", C.c_int32)]
+
+
 REGROUP_BUFS = 6
 REGROUP_SEG_WORDS = 8      # ditto_regroup_seg as int32 / uint32 words: kind, source, dest, aux, src_off, dst_off, n, dup_off (16-byte units)
 REGROUP_COPY, REGROUP_DRAW = 0, 1
@@ -209,6 +215,10 @@ SYMBOLS = {
                                                   _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_guided_step_packed_tags_prompt_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
                                                        _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    # the second-order multistep solver: a step shared by the batch (host struct) or one per utterance (device [B])
+    "ditto_multistep_update_packed": (_i, [_vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_guided_step_packed_multistep_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _i, _i,
+                                                     _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_span_noise_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ditto_span_mse_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),

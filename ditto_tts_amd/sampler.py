@@ -22,6 +22,7 @@ RNG: `torch.randn_like` on the state's device, in the reference's call order (on
 from __future__ import annotations
 
 import functools
+import math
 from typing import Callable, Optional
 
 import torch
@@ -51,6 +52,42 @@ def strided_schedule(alphas_cumprod: torch.Tensor, n_steps: int, eta: float = 0.
     return out
 
 
+SOLVERS = ("ddim", "dpmpp2m")
+
+
+def multistep_schedule(alphas_cumprod: torch.Tensor, n_steps: int):
+    """The second-order multistep data-prediction solver, DPM-Solver++(2M) (Lu et al. 2022), over the timesteps of
+    `strided_schedule`: a list of (tau_i, a, kx, ke, b, g, use_prev).  Step i predicts x0 = kx x + ke eps (kx = 1 / alpha_i, ke =
+    -sigma_i / alpha_i) and moves to x' = a x + b x0 + g q with q the x0 of step i - 1; g = 0 where use_prev is False (step 0 and the
+    last step, which ends at abar = 1 and is first order: x' = x0).  With lambda = log(alpha / sigma), h_i = lambda_{i+1} - lambda_i
+    and r_i = h_{i-1} / h_i: a = sigma_{i+1} / sigma_i and x' = a x - alpha_{i+1} expm1(-h_i) D, D = (1 + 1 / (2 r_i)) x0 - (1 / (2
+    r_i)) q.  Deterministic: one forward per step, no noise.  Computed in float64, returned as Python floats."""
+    T = int(alphas_cumprod.shape[0])
+    if not 1 <= n_steps <= T:
+        raise ValueError("n_steps must be in [1, diffusion_steps]")
+    stride = T / n_steps
+    taus = [int(round(T - 1 - i * stride)) for i in range(n_steps)]
+    ac = alphas_cumprod.double().cpu()
+    alpha = [math.sqrt(float(ac[t])) for t in taus]
+    sigma = [math.sqrt(1.0 - float(ac[t])) for t in taus]
+    lam = [math.log(al / sg) for al, sg in zip(alpha, sigma)]
+    out = []
+    for i, t_val in enumerate(taus):
+        kx, ke = 1.0 / alpha[i], -sigma[i] / alpha[i]
+        if i == n_steps - 1:                                   # sigma_next = 0: the lower-order final step lands on x0
+            out.append((t_val, 0.0, kx, ke, 1.0, 0.0, False))
+            continue
+        h = lam[i + 1] - lam[i]
+        c = -alpha[i + 1] * math.expm1(-h)
+        if i == 0:
+            b, g = c, 0.0
+        else:
+            r = (lam[i] - lam[i - 1]) / h
+            b, g = c * (1.0 + 0.5 / r), -c * 0.5 / r
+        out.append((t_val, sigma[i + 1] / sigma[i], kx, ke, b, g, i > 0))
+    return out
+
+
 def guidance_vector(guidance, B: int) -> Optional[torch.Tensor]:
     """`guidance` (None, a number, or a sequence / tensor of B numbers) as a CPU fp32 tensor [B], or None (no guidance)."""
     if guidance is None:
@@ -74,6 +111,15 @@ def guidance_vector(guidance, B: int) -> Optional[torch.Tensor]:
     if not torch.isfinite(g).all():
         raise ValueError("guidance: every scale must be finite")
     return g.contiguous()
+
+
+def _padded_solver(solver):
+    """the padded layouts run the strided (DDIM) solver only"""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
+    if solver != "ddim":
+        raise NotImplementedError(f"solver={solver!r} is served over packed batches: pack the batch and call "
+                                  "sample_guided_packed(solver=)")
 
 
 class SpeechGenerator:
@@ -250,11 +296,13 @@ class SpeechGenerator:
     # ---------------------------------------------------------------- strided (DDIM) loop + CFG  
     @torch.no_grad()
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
-                               cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None, prompt_lengths=None):
+                               cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None, prompt_lengths=None,
+                               solver="ddim"):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
         DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step, with optional
         classifier-free guidance: the step runs ONE forward on the doubled batch [x; x] x [text; null_text] and combines
         eps_u + w (eps_c - eps_u).  sample_guided with one uniform `cfg_scale` over a dense batch: one library call per step."""
+        _padded_solver(solver)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         if speech_lengths is not None or text_lengths is not None:
@@ -310,10 +358,38 @@ class SpeechGenerator:
             step(t=t_tensor, a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val, opts=opts)
         return x2[:rows].clone() if cfg else x2
 
+    def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin):
+        """_guided_loop for solver="dpmpp2m": the same prologue (`begin`, whose step is engine.guided_step_packed_multistep_ bound to
+        x2, its conditioning and offsets), then one library call per step of multistep_schedule over x2 and the history q — one
+        buffer [S, d] per call, written by step 0 before any step reads it.  Each step's coefficients travel as a host struct."""
+        from .hip import CallOpts, MultistepCoef
+        gv = guidance_vector(guidance, B)
+        cfg = gv is not None
+        if cfg and null_text_emb is None:
+            raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
+        schedule = multistep_schedule(self.alphas_cumprod, n_steps)
+        eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
+        if seeds is not None:
+            seeds = seeds.to(eng.device).long().contiguous()
+            if seeds.shape != (B,):
+                raise ValueError(f"seeds must have shape [{B}]")
+        x2, N, step = begin(eng, cfg, seeds)
+        rows = x2.shape[0] // 2 if cfg else x2.shape[0]
+        if cfg:
+            x2[rows:].copy_(x2[:rows])
+        q = torch.empty_like(x2[:rows])
+        w = gv.to(eng.device) if cfg else None
+        t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
+        opts = None if batch_class is None else CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
+        for t_val, a, kx, ke, b, g, use_prev in schedule:
+            t_tensor.fill_(t_val)
+            step(t=t_tensor, q=q, coef=MultistepCoef(a, kx, ke, b, g, 0.0, int(use_prev), 0), w=w, opts=opts)
+        return x2[:rows].clone() if cfg else x2
+
     @torch.no_grad()
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
                       null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
-                      cond_by_audio=False, batch_class=None, prompt_lengths=None):
+                      cond_by_audio=False, batch_class=None, prompt_lengths=None, solver="ddim"):
         """The strided (DDIM) loop of sample_latents_strided with what serving needs: per-utterance `speech_lengths` /
         `text_lengths` (a padded batch; rows past an utterance's length are exactly 0 in the result and padding never reaches a
         valid row), per-utterance `guidance` (None: no CFG; a number; or [B] numbers), and per-utterance `seeds`.  One library
@@ -327,7 +403,8 @@ class SpeechGenerator:
         callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
         count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
         The padded layout has no speech prompts (`prompt_lengths` raises NotImplementedError): pack the batch and call
-        sample_guided_packed.  Returns fp32 [B, N, d]."""
+        sample_guided_packed; so does solver="dpmpp2m".  Returns fp32 [B, N, d]."""
+        _padded_solver(solver)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         B, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
@@ -362,7 +439,7 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
-                             batch_class=None, prompt_lengths=None):
+                             batch_class=None, prompt_lengths=None, solver="ddim"):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -377,7 +454,16 @@ class SpeechGenerator:
         step (the forward attends to them like to any rows) and come back bit-equal.  The other G_b = N_b - P_b rows start from x_T —
         with `seeds`, ditto_noise_normal(seed_b, 0xFFFFFFFF) over G_b rows, what an unprompted utterance of G_b frames starts from —
         and every step is one ditto_guided_step_packed_prompt_opts call whose update skips the prompt rows.  A model uses a prompt
-        only if it was trained with one (DiTTO.span_noise_packed / span_loss_packed).  Returns fp32 [S, d]."""
+        only if it was trained with one (DiTTO.span_noise_packed / span_loss_packed).
+        `solver`: "ddim" (the strided update above) or "dpmpp2m" — the second-order multistep solver of multistep_schedule over the
+        same timesteps: one ditto_guided_step_packed_multistep_opts call per step, the same forward, and an update that keeps the
+        previous step's x0 prediction in a history buffer [S, d].  It is deterministic: `eta` != 0 and `noises` raise ValueError,
+        `seeds` give x_T only; every other argument works as above.  Returns fp32 [S, d]."""
+        if solver not in SOLVERS:
+            raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
+        multistep = solver == "dpmpp2m"
+        if multistep and (eta != 0 or noises is not None):
+            raise ValueError('solver="dpmpp2m" is deterministic: eta must be 0 and noises= cannot be given')
         require_fused_attention(self.ditto_model.cfg, "packed batches")
         from .varlen import pack, validate_cu_seqlens, validate_prompt_lengths
         S, d = int(audio_emb.shape[0]), int(audio_emb.shape[1])
@@ -387,6 +473,7 @@ class SpeechGenerator:
         pl = None if prompt_lengths is None else validate_prompt_lengths(prompt_lengths, cu)
 
         def begin(eng, cfg, seeds):
+            entry = eng.guided_step_packed_multistep_ if multistep else eng.guided_step_packed_
             if null_text_cu_seqlens is not None and not cfg:
                 raise ValueError("null_text_cu_seqlens without guidance")
             text = text_emb.to(eng.device).float()
@@ -415,7 +502,7 @@ class SpeechGenerator:
                     else:
                         xt = torch.randn(len(at), d, dtype=torch.float32, device=eng.device)
                     x2[:S].index_copy_(0, at, xt)
-                return x2, N, functools.partial(eng.guided_step_packed_, x2, cond, B=B, offsets=offsets, prompt_len=pl.to(eng.device))
+                return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets, prompt_len=pl.to(eng.device))
             if seeds is not None and not cond_by_audio:
                 # x_T: ditto_noise_normal over the padded [B, N, d] (the numbers of sample_guided(seeds=)), packed row by row
                 xt = torch.empty(B, N, d, dtype=torch.float32, device=eng.device)
@@ -423,23 +510,30 @@ class SpeechGenerator:
                 x2[:S].copy_(pack(xt, (cu[1:] - cu[:-1]).tolist())[0])
             else:
                 x2[:S].copy_(torch.randn_like(audio_emb.float()) if not cond_by_audio else audio_emb)
-            return x2, N, functools.partial(eng.guided_step_packed_, x2, cond, B=B, offsets=offsets)
+            return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets)
 
+        if multistep:
+            return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin)
         return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin)
 
-    def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None):
+    def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim"):
         """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an
         utterance, step() admits what fits, runs one guided strided step over everything in flight — each utterance at its own
         index of its own strided_schedule — and returns the finished ones.  `max_rows` / `max_utterances` / `max_text_rows`: the
         speech rows, utterances and conditioning rows (text, plus null text under guidance) in flight at once; every buffer is
-        sized from them here.  `class_rows`: hip.CallOpts(class_rows=) of every step (else the thread's hip.batch_class scope)."""
+        sized from them here.  `class_rows`: hip.CallOpts(class_rows=) of every step (else the thread's hip.batch_class scope).
+        `solver`: "ddim", or "dpmpp2m" — every request of the stream then runs multistep_schedule (sample_guided_packed(solver=));
+        one solver per stream."""
+        if solver not in SOLVERS:
+            raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         from .serving import DeviceBatch, GuidedStream
         require_fused_attention(self.ditto_model.cfg, "request streams (packed batches)")
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
         batch = DeviceBatch(eng, max_rows=max_rows, max_utterances=max_utterances, max_text_rows=max_text_rows, guided=guided,
-                            class_rows=class_rows)
+                            class_rows=class_rows, solver=solver)
         return GuidedStream(batch, self.alphas_cumprod, max_rows=max_rows, max_utterances=max_utterances,
-                            max_text_rows=max_text_rows, guided=guided, text_dim=eng.cfg.text_dim, hidden_dim=eng.cfg.hidden_dim)
+                            max_text_rows=max_text_rows, guided=guided, text_dim=eng.cfg.text_dim, hidden_dim=eng.cfg.hidden_dim,
+                            solver=solver)
 
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):

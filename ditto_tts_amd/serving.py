@@ -76,8 +76,9 @@ class Plan:
 
 
 class StepArgs:
-    """One step over the batch in flight: per-utterance lists in slot order."""
-    __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt")
+    """One step over the batch in flight: per-utterance lists in slot order.  `coef` (solver "dpmpp2m" only, else None): each
+    utterance's (a, kx, ke, b, g, use_prev) of its own multistep_schedule; a, ce, cz and tags are then None."""
+    __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt", "coef")
 
 
 def _cumulate(lengths) -> List[int]:
@@ -106,10 +107,16 @@ class GuidedStream:
     torch's default CPU generator at submit.
     `prompt` (floating [P, d], P >= 1): a speech prompt — the target speaker's clean latents, kept in front of the `n_frames`
     generated rows at every step (sample_guided_packed(prompt_lengths=)).  The request then occupies P + n_frames of `max_rows`;
-    `x_T` stays [n_frames, d] and so does the result."""
+    `x_T` stays [n_frames, d] and so does the result.
+    `solver` (one per stream): "ddim" — each request at its own index of its own strided_schedule — or "dpmpp2m": of its own
+    multistep_schedule (sample_guided_packed(solver="dpmpp2m")); requests then need eta = 0 and their seeds give x_T only."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
-                 text_dim: int, hidden_dim: int):
+                 text_dim: int, hidden_dim: int, solver: str = "ddim"):
+        from .sampler import SOLVERS
+        if solver not in SOLVERS:
+            raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
+        self.solver = solver
         for name, v in (("max_rows", max_rows), ("max_utterances", max_utterances), ("max_text_rows", max_text_rows)):
             if not _is_int(v) or v < 1:
                 raise ValueError(f"{name}: a positive int is needed, got {v!r}")
@@ -137,8 +144,9 @@ class GuidedStream:
     def _schedule(self, n_steps: int, eta: float):
         key = (n_steps, eta)
         if key not in self._schedules:
-            from .sampler import strided_schedule
-            self._schedules[key] = strided_schedule(self._acp, n_steps, eta)
+            from .sampler import multistep_schedule, strided_schedule
+            self._schedules[key] = (strided_schedule(self._acp, n_steps, eta) if self.solver == "ddim" else
+                                    multistep_schedule(self._acp, n_steps))
         return self._schedules[key]
 
     def _text(self, t, name):
@@ -159,6 +167,8 @@ class GuidedStream:
             raise ValueError(f"n_steps: an int is needed, got {n_steps!r}")
         if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not math.isfinite(eta) or eta < 0:
             raise ValueError(f"eta: a finite number >= 0 is needed, got {eta!r}")
+        if self.solver != "ddim" and eta != 0:
+            raise ValueError(f"this stream's solver ({self.solver}) is deterministic: eta must be 0, got {eta!r}")
         schedule = self._schedule(n_steps, float(eta))             # (ValueError unless 1 <= n_steps <= diffusion_steps)
         if self.guided:
             if guidance is None or null_text_emb is None:
@@ -243,8 +253,13 @@ class GuidedStream:
         s.max_T = max(max(r.T, r.T_null) for r in members)
         rows = [r.schedule[r.i] for r in members]                   # (tau, a, ce, sigma) of each utterance's own step
         s.t = [int(q[0]) for q in rows]
-        s.a, s.ce, s.cz = [q[1] for q in rows], [q[2] for q in rows], [q[3] for q in rows]
-        s.tags = [int(q[0]) & 0xFFFFFFFF for q in rows]             # the step's Philox tag: its timestep, as in the closed loops
+        if self.solver == "ddim":
+            s.a, s.ce, s.cz = [q[1] for q in rows], [q[2] for q in rows], [q[3] for q in rows]
+            s.tags = [int(q[0]) & 0xFFFFFFFF for q in rows]         # the step's Philox tag: its timestep, as in the closed loops
+            s.coef = None
+        else:                                                       # (tau, a, kx, ke, b, g, use_prev): use_prev is False at r.i == 0
+            s.a = s.ce = s.cz = s.tags = None
+            s.coef = [tuple(q[1:]) for q in rows]
         s.w = [r.w for r in members] if self.guided else None
         s.seeds = [r.seed for r in members]
         s.handles = [r.handle for r in members]
@@ -280,8 +295,8 @@ class _Upload:
 
 
 # the buffers a regroup's segments name (ditto_regroup_packed): sources and destinations
-_SRC_X, _SRC_XT, _SRC_COND, _SRC_NEW_COND, _SRC_TABLE = range(5)
-_DST_X, _DST_OUT, _DST_COND, _DST_OFFSETS = range(4)
+_SRC_X, _SRC_XT, _SRC_COND, _SRC_NEW_COND, _SRC_TABLE, _SRC_Q = range(6)
+_DST_X, _DST_OUT, _DST_COND, _DST_OFFSETS, _DST_Q = range(5)
 
 
 def speech_segments(r: Request, new: bool, j: int, dst_row: int, xt_row: int, d4: int, dup: int) -> List[List[int]]:
@@ -301,6 +316,12 @@ def speech_segments(r: Request, new: bool, j: int, dst_row: int, xt_row: int, d4
     return segs
 
 
+def history_segment(r: Request, dst_row: int, d4: int) -> List[int]:
+    """The segment that carries a survivor's multistep history — the x0 prediction of its last step, on its generated rows — from
+    the current history buffer to row `dst_row` of the next one.  A newcomer has none: its first step does not read the history."""
+    return [hip.REGROUP_COPY, _SRC_Q, _DST_Q, 0, (r.row + r.P) * d4, (dst_row + r.P) * d4, r.n_frames * d4, 0]
+
+
 def staged_rows(r: Request) -> int:
     """rows of the x_T staging buffer a newcomer takes: its prompt, then its own x_T"""
     return r.P + (r.n_frames if r.x_T is not None else 0)
@@ -315,11 +336,15 @@ def retire_segments(done: List[Request], d4: int) -> List[List[int]]:
 class DeviceBatch:
     """The packed batch of a GuidedStream on one GPU.  Buffers (sized once from the capacities): two state buffers [2 max_rows, d]
     ([max_rows, d] unguided) and two conditioning images (a regroup reads one and writes the other), a staging image for the
-    newcomers' conditioning and one for callers' x_T, the device offsets, the per-step argument block and the segment table."""
+    newcomers' conditioning and one for callers' x_T, the device offsets, the per-step argument block and the segment table.
+    `solver` "dpmpp2m": two history buffers [max_rows, d] beside the state (double-buffered like it: a regroup moves the
+    survivors' rows of both in its one launch), and the step block carries one ditto_multistep_coef per utterance."""
 
-    def __init__(self, engine, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool, class_rows=None):
+    def __init__(self, engine, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool, class_rows=None,
+                 solver: str = "ddim"):
         from .engine import require_fused_attention
         require_fused_attention(engine.cfg, "request streams (packed batches)")
+        self.multistep = solver != "ddim"
         self.eng, self.lib, self.guided = engine, engine.lib, bool(guided)
         self.halves = 2 if guided else 1
         self.maxB, self.maxS, self.maxT = int(max_utterances), int(max_rows), int(max_text_rows)
@@ -334,6 +359,7 @@ class DeviceBatch:
         cond_bytes = int(self.lib.ditto_packed_cond_bytes(C.byref(engine._ccfg), nbB, self.maxT))
         with torch.cuda.device(dev):
             self.x = [torch.zeros(self.halves * self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)]
+            self.q = [torch.zeros(self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)] if self.multistep else None
             self.cond = [torch.zeros(cond_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
             # every newcomer's own image [K/V rows | tmod], 256-byte aligned, one behind the other
             self.new_cond = torch.zeros(self.maxT * self.kv_row + self.maxB * (_pad(self.halves * self.tmod_row, 256) + 256),
@@ -342,11 +368,13 @@ class DeviceBatch:
             self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
             self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
             # the step block: t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w fp32 [maxB] | tags uint32 [maxB] |
-            # prompt_len int32 [maxB]
+            # prompt_len int32 [maxB] | (multistep) ditto_multistep_coef [maxB]
             self.o_t, self.o_seeds = 0, _pad(nbB * 8, 16)
             self.o_f = self.o_seeds + _pad(self.maxB * 8, 16)
             self.f_stride = _pad(self.maxB * 4, 16)
-            self.block = _Upload(self.o_f + 6 * self.f_stride, dev)
+            self.o_coef = self.o_f + 6 * self.f_stride
+            self.block_bytes = self.o_coef + (C.sizeof(hip.MultistepCoef) * self.maxB if self.multistep else 0)
+            self.block = _Upload(self.block_bytes, dev)
             self.max_seg = 8 * self.maxB + 8
             self.table = _Upload(self.max_seg * 4 * hip.REGROUP_SEG_WORDS + 2 * self.cu_pad * 4, dev)
             engine.workspace_packed(nbB, self.halves * self.maxS, self.maxT)
@@ -359,14 +387,20 @@ class DeviceBatch:
     # ------------------------------------------------------------------ uploads
     def _send_block(self, a: StepArgs):
         B, nb = a.B, self.halves * a.B
-        buf = np.zeros(self.o_f + 6 * self.f_stride, dtype=np.uint8)
+        buf = np.zeros(self.block_bytes, dtype=np.uint8)
         buf[self.o_t:self.o_t + nb * 8].view(np.int64)[:] = a.t * self.halves
         buf[self.o_seeds:self.o_seeds + B * 8].view(np.int64)[:] = a.seeds
-        for k, v in enumerate((a.a, a.ce, a.cz, a.w if a.w is not None else [0.0] * B)):
-            o = self.o_f + k * self.f_stride
-            buf[o:o + B * 4].view(np.float32)[:] = v
-        o = self.o_f + 4 * self.f_stride
-        buf[o:o + B * 4].view(np.uint32)[:] = a.tags
+        if self.multistep:             # ditto_multistep_coef: a, kx, ke, b, g, w fp32 | use_prev int32 | reserved
+            co = buf[self.o_coef:self.o_coef + 32 * B].view(np.float32).reshape(B, 8)
+            co[:, :5] = [c[:5] for c in a.coef]
+            co[:, 5] = a.w if a.w is not None else 0.0
+            co.view(np.int32)[:, 6] = [int(c[5]) for c in a.coef]
+        else:
+            for k, v in enumerate((a.a, a.ce, a.cz, a.w if a.w is not None else [0.0] * B)):
+                o = self.o_f + k * self.f_stride
+                buf[o:o + B * 4].view(np.float32)[:] = v
+            o = self.o_f + 4 * self.f_stride
+            buf[o:o + B * 4].view(np.uint32)[:] = a.tags
         o = self.o_f + 5 * self.f_stride
         buf[o:o + B * 4].view(np.int32)[:] = a.prompt
         self.block.send(buf)
@@ -389,6 +423,9 @@ class DeviceBatch:
         nxt = 1 - self.cur
         src = [self.x[self.cur], self.x_T, self.cond[self.cur], self.new_cond, self.table.dev]
         dst = [self.x[nxt], out, self.cond[nxt], self.offsets]
+        if self.multistep:             # the history moves with the state: _SRC_Q, _DST_Q
+            src.append(self.q[self.cur])
+            dst.append(self.q[nxt])
         n = hip.REGROUP_BUFS
         sp, sb, dp, db = (C.c_void_p * n)(), (C.c_size_t * n)(), (C.c_void_p * n)(), (C.c_size_t * n)()
         for k, t in enumerate(src):
@@ -435,6 +472,8 @@ class DeviceBatch:
             segs.extend(speech_segments(r, new, j, plan.cu[j], xt_row, d4, S * d4 if self.guided else 0))
             if new:
                 xt_row += staged_rows(r)
+            elif self.multistep:
+                segs.append(history_segment(r, plan.cu[j], d4))
             # conditioning: K/V rows and the tmod row of the text, then of the null text ([text_0 .. ; null_0 ..] under CFG)
             if new:
                 base, own_tmod = new_at[r.handle.id], new_at[r.handle.id] + self._tmod_offset(r.text_rows)
@@ -465,13 +504,22 @@ class DeviceBatch:
 
     def step(self, a: StepArgs):
         """ditto_guided_step_packed_tags_opts over the batch in flight, in place on the current state (with a prompted utterance
-        in flight: ditto_guided_step_packed_tags_prompt_opts, the prompt lengths riding in the step block)"""
+        in flight: ditto_guided_step_packed_tags_prompt_opts, the prompt lengths riding in the step block).  Solver "dpmpp2m":
+        ditto_guided_step_packed_multistep_opts on the current state and history, each utterance at its block entry."""
         if not self._block_sent:
             self._send_block(a)
         self._block_sent = False
         eng, f = self.eng, self.o_f
         nb, rows = self.halves * a.B, self.halves * a.S
         ws = eng.workspace_packed(nb, rows, a.S_T)
+        if self.multistep:
+            hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
+                eng.handle, self.x[self.cur].data_ptr(), self.cond[self.cur].data_ptr(), self._block_ptr(self.o_t),
+                self.offsets.data_ptr(), self.offsets.data_ptr() + 4 * self.cu_pad,
+                self._block_ptr(f + 5 * self.f_stride) if any(a.prompt) else None, self.q[self.cur].data_ptr(), None,
+                self._block_ptr(self.o_coef), None, a.B, a.S, a.max_N, a.S_T, a.max_T, int(self.guided), self.rope[0].data_ptr(),
+                self.rope[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if self.opts is None else C.byref(self.opts)))
+            return
         if any(a.prompt):
             entry, head = self.lib.ditto_guided_step_packed_tags_prompt_opts, (self._block_ptr(f + 5 * self.f_stride),)
         else:

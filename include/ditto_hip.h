@@ -598,6 +598,34 @@ int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const 
                                               int B, int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos,
                                               const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
                                               const ditto_call_opts* opts);
+/* ---- Second-order multistep solver, DPM-Solver++(2M) (Lu et al. 2022), over packed batches: one forward per step like the strided
+ * (DDIM) step, with the previous step's x0 prediction kept per generated row in `q` fp32 [S, d] (one half only).  Deterministic: no
+ * noise.  The reference has neither solver: like the strided loop this is pinned by its own formulas (sampler.multistep_schedule).
+ * ditto_multistep_coef: one utterance's step — per element
+ *     e  = cfg ? w (c - u) + u : c          (ditto_guided_update's fmaf)
+ *     x0 = fmaf(kx, x, ke e)                (kx = 1 / alpha, ke = -sigma / alpha)
+ *     x' = fmaf(a, x, fmaf(b, x0, use_prev ? g q : 0)),   q = x0
+ *   x' goes to both halves of x2 under cfg.  With use_prev == 0, q is written and NOT read (an utterance's first step meets an
+ *   uninitialised history).
+ * ditto_multistep_update_packed: the update alone.  Exactly one of `step` (a HOST pointer: the step every utterance stands at; its w
+ *   is ignored and w[b], device fp32 [B], is the guidance scale under cfg) and `coefs` (DEVICE [B], 16-byte aligned: utterance b at
+ *   coefs[b], guidance scale included; w is ignored) is given.  x2, eps2, cu, B, S, max_N, d, cfg: as ditto_guided_update_packed.
+ *   prompt_len: NULL, or device int32 [B] clamped as in ditto_guided_update_packed_prompt — the prompt rows of x2, eps2 and q are
+ *   neither read nor written.
+ * ditto_guided_step_packed_multistep_opts: ditto_guided_step_packed_prompt_opts with that update (the forward is unchanged). */
+typedef struct ditto_multistep_coef {
+    float a, kx, ke, b, g, w;
+    int32_t use_prev;
+    int32_t reserved;  /* 0 */
+} ditto_multistep_coef;
+int ditto_multistep_update_packed(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
+                                  const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, const int32_t* prompt_len,
+                                  int B, int S, int max_N, int d, int cfg, ditto_stream_t stream);
+int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                            const int32_t* cu_text, const int32_t* prompt_len, float* q,
+                                            const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, const float* w, int B,
+                                            int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
+                                            void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
 /* Span-masked training over a packed batch with prompts (cu, prompt_len and their clamp as above; every buffer fp32 [S, d]).  z is
  *   either `noise`, a packed buffer whose prompt rows are not read, or Philox of (seeds[b], tag) at the generated-local quad index:
  *   exactly one of the two is given.
