@@ -1640,6 +1640,56 @@ int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const vo
     });
 }
 
+// ---- guidance in a limited interval: a step in which G of the B utterances are guided (guided_mixed.hip) ----
+static int check_mixed(const char* who, const float* x2, const float* eps2, const float* noise, const int64_t* seeds,
+                       const uint32_t* tags, const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                       const int32_t* partner, int B, int G, int S, int S_G, int max_N, int d) {
+    if (!cu || !partner) return fail(DITTO_ERR_ARG, "%s: null cu / partner", who);
+    if (seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
+    if (int rc = check_guided_update(who, x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, 1)) return rc;
+    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
+    if (G < 0 || G > B || S_G < 0 || S_G > S || (G > 0) != (S_G > 0) || G > S_G)
+        return fail(DITTO_ERR_SHAPE, "%s: need 0 <= G <= B, G <= S_G <= S, and S_G == 0 exactly when G == 0 (B %d, G %d, S %d, S_G %d)",
+                    who, B, G, S, S_G);
+    return DITTO_OK;
+}
+
+int ditto_guided_update_packed_mixed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                     const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                     const int32_t* partner, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,
+                                     ditto_stream_t stream) {
+    if (int rc = check_mixed("ditto_guided_update_packed_mixed", x2, eps2, noise, seeds, tags, w, a, ce, cz, cu, partner, B, G, S, S_G,
+                             max_N, d))
+        return rc;
+    HIP_TRY(launch_guided_update_mixed(x2, eps2, noise, seeds, tags, w, a, ce, cz, cu, partner, prompt_len, B, G, S, S_G, max_N, d,
+                                       (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_packed_mixed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                        const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
+                                        const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce,
+                                        const float* cz, int B, int G, int S, int S_G, int max_N, int S_T, int max_T,
+                                        const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                        ditto_stream_t stream, const ditto_call_opts* opts) {
+    const char* who = "ditto_guided_step_packed_mixed_opts";
+    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    if (int rc = check_mixed(who, x2, x2, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, B, G, S, S_G, max_N, m->cfg.hidden_dim))
+        return rc;
+    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
+    if (S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
+    return with_opts(opts, [&]() -> int {
+        float* eps;                                                   // the forward over [x; the guided ones' copies] x [text; their null]
+        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
+                                  BatchLayout::packed(B + G, S + S_G, max_N, S_T, max_T, cu_speech, cu_text), &eps))
+            return rc;
+        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        HIP_TRY(launch_guided_update_mixed(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, prompt_len, B, G, S, S_G, max_N,
+                                           m->cfg.hidden_dim, (hipStream_t)stream));
+        return DITTO_OK;
+    });
+}
+
 // ---- span-masked training over a packed batch with prompts (span_train.hip) ----
 static int check_span(const char* who, const void* in, const float* noise, const int64_t* seeds, const int32_t* cu,
                       const int32_t* prompt_len, const void* out, int B, int S, int max_N, int d) {

@@ -286,6 +286,14 @@ hipError_t launch_guided_update_prompt(float* x2, const float* eps2, const float
 hipError_t launch_multistep_update_packed(float* x2, const float* eps2, float* q, const ::ditto_multistep_coef* step,
                                           const ::ditto_multistep_coef* coefs, const float* w, const int32_t* cu,
                                           const int32_t* prompt_len, int B, int S, int max_N, int d, bool cfg, hipStream_t s);
+// ---------------- guided_mixed.hip ----------------
+// the per-utterance-tag update of a batch in which G of the B utterances are guided at this step: x2, eps2 [S + S_G, d], the guided
+// ones' unconditional copies compacted in rows [S, S + S_G); cu device int32 [B + G + 1] = [cu; S + cu_G[1:]]; partner device int32
+// [B]: b's copy in [0, G), or -1 (e = c, nothing behind row S touched); prompt_len may be null
+hipError_t launch_guided_update_mixed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const unsigned* tags,
+                                      const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                      const int32_t* partner, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,
+                                      hipStream_t s);
 // ---------------- span_train.hip ----------------
 // span-masked training over a packed batch with prompts: the noising that keeps the prompt rows, the MSE over the generated rows
 // (n_elems of them) with its gradient; `partial`: span_mse_partials(B, max_N, d) floats

@@ -219,6 +219,9 @@ SYMBOLS = {
     "ditto_multistep_update_packed": (_i, [_vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ditto_guided_step_packed_multistep_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _i, _i,
                                                      _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    # guidance in a limited interval: a step in which G of the B utterances are guided (partner device int32 [B])
+    "ditto_guided_update_packed_mixed": (_i, [_vp] * 12 + [_i] * 6 + [_vp]),
+    "ditto_guided_step_packed_mixed_opts": (_i, [_vp] * 15 + [_i] * 7 + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_span_noise_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ditto_span_mse_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),

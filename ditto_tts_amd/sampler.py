@@ -88,6 +88,30 @@ def multistep_schedule(alphas_cumprod: torch.Tensor, n_steps: int):
     return out
 
 
+def validate_guidance_interval(interval, diffusion_steps: int):
+    """`guidance_interval` — None, or a pair (t_lo, t_hi) of integer diffusion timesteps with 0 <= t_lo <= t_hi <= diffusion_steps - 1
+    — as None or a tuple of two ints."""
+    if interval is None:
+        return None
+    ok = isinstance(interval, (tuple, list)) and len(interval) == 2 and all(
+        isinstance(v, int) and not isinstance(v, bool) for v in interval)
+    if not ok:
+        raise ValueError(f"guidance_interval: None or a pair (t_lo, t_hi) of ints is needed, got {interval!r}")
+    lo, hi = interval
+    if lo > hi or lo < 0 or hi > diffusion_steps - 1:
+        raise ValueError(f"guidance_interval: 0 <= t_lo <= t_hi <= {diffusion_steps - 1} is needed, got {interval!r}")
+    return lo, hi
+
+
+def guided_steps(schedule, interval):
+    """Which steps of a strided_schedule / multistep_schedule apply classifier-free guidance under `guidance_interval` (guidance in
+    a limited interval, Kynkaanniemi et al. 2024): step i, at timestep tau_i, if and only if t_lo <= tau_i <= t_hi; every step
+    without an interval.  The other steps use the conditional prediction alone and cost the unguided step."""
+    if interval is None:
+        return [True] * len(schedule)
+    return [interval[0] <= row[0] <= interval[1] for row in schedule]
+
+
 def guidance_vector(guidance, B: int) -> Optional[torch.Tensor]:
     """`guidance` (None, a number, or a sequence / tensor of B numbers) as a CPU fp32 tensor [B], or None (no guidance)."""
     if guidance is None:
@@ -313,18 +337,25 @@ class SpeechGenerator:
                                   noises=noises, cond_by_audio=cond_by_audio)
 
     # ---------------------------------------------------------------- guided strided loop over a variable-length batch
-    def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin):
+    def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval=None,
+                     begin_plain=None):
         """The strided loop of sample_guided and sample_guided_packed.  `begin(eng, cfg, seeds)` is the layout's own prologue: it
         builds the conditioning and the state x2 (rows [x_T; room for the unconditional half] under guidance, else x_T) and returns
         (x2, max length, step) with `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)` the layout's library call bound to
-        x2, its conditioning and its lengths or offsets."""
+        x2, its conditioning and its lengths or offsets.
+        `interval` (a guidance interval, packed batches): step i is guided where guided_steps says so; the others run
+        `begin_plain(eng, x2)`'s step — the layout's non-CFG call on the conditional half of x2, built only when a step needs it.
+        The unconditional half is filled from the conditional one before the first guided step, and again before the first one
+        behind unguided steps; in between every guided update writes both halves itself.  With no guided step at all the call is
+        the one without guidance."""
         if seeds is not None and noises is not None:
             raise ValueError("seeds= excludes noises=")
         gv = guidance_vector(guidance, B)
-        cfg = gv is not None
-        if cfg and null_text_emb is None:
+        if gv is not None and null_text_emb is None:
             raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
         schedule = strided_schedule(self.alphas_cumprod, n_steps, eta)
+        guided = guided_steps(schedule, interval)
+        cfg = gv is not None and any(guided)
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)   # "cuda" -> cuda:0: the engine the other loops use
         if seeds is not None:
             seeds = seeds.to(eng.device).long().contiguous()
@@ -332,17 +363,18 @@ class SpeechGenerator:
                 raise ValueError(f"seeds must have shape [{B}]")
         x2, N, step = begin(eng, cfg, seeds)
         rows = x2.shape[0] // 2 if cfg else x2.shape[0]
-        if cfg:
-            x2[rows:].copy_(x2[:rows])                       # after this, every step's update writes both halves itself
+        plain = begin_plain(eng, x2) if cfg and not all(guided) else None
+        stale = cfg                                          # the unconditional half is behind the conditional one
         # every step's coefficients in one upload: coef[i] = (a, ce, sigma) x B
         coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
         w = gv.to(eng.device) if cfg else None
         t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
         z = torch.empty_like(x2[:rows]) if seeds is None else None
-        opts = None
+        opts = plain_opts = None
         if batch_class is not None:
             from .hip import CallOpts
             opts = CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
+            plain_opts = CallOpts(class_rows=int(batch_class) * N)             # what the call without guidance pins
         for i, (t_val, _, _, sigma) in enumerate(schedule):
             t_tensor.fill_(t_val)
             noise = sd = None
@@ -355,19 +387,28 @@ class SpeechGenerator:
                 else:
                     z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
                     noise = z
+            if cfg and not guided[i]:                        # outside the interval: the non-CFG step on the conditional half
+                plain(t=t_tensor[:B], a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=None, noise=noise, seeds=sd, step=t_val,
+                      opts=plain_opts)
+                stale = True
+                continue
+            if stale:                                        # [x; x], once; then every guided update writes both halves itself
+                x2[rows:].copy_(x2[:rows])
+                stale = False
             step(t=t_tensor, a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val, opts=opts)
         return x2[:rows].clone() if cfg else x2
 
-    def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin):
+    def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval=None, begin_plain=None):
         """_guided_loop for solver="dpmpp2m": the same prologue (`begin`, whose step is engine.guided_step_packed_multistep_ bound to
         x2, its conditioning and offsets), then one library call per step of multistep_schedule over x2 and the history q — one
         buffer [S, d] per call, written by step 0 before any step reads it.  Each step's coefficients travel as a host struct."""
         from .hip import CallOpts, MultistepCoef
         gv = guidance_vector(guidance, B)
-        cfg = gv is not None
-        if cfg and null_text_emb is None:
+        if gv is not None and null_text_emb is None:
             raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
         schedule = multistep_schedule(self.alphas_cumprod, n_steps)
+        guided = guided_steps(schedule, interval)           # (interval, begin_plain: as in _guided_loop)
+        cfg = gv is not None and any(guided)
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
         if seeds is not None:
             seeds = seeds.to(eng.device).long().contiguous()
@@ -375,15 +416,24 @@ class SpeechGenerator:
                 raise ValueError(f"seeds must have shape [{B}]")
         x2, N, step = begin(eng, cfg, seeds)
         rows = x2.shape[0] // 2 if cfg else x2.shape[0]
-        if cfg:
-            x2[rows:].copy_(x2[:rows])
+        plain = begin_plain(eng, x2) if cfg and not all(guided) else None
+        stale = cfg
         q = torch.empty_like(x2[:rows])
         w = gv.to(eng.device) if cfg else None
         t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
         opts = None if batch_class is None else CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
-        for t_val, a, kx, ke, b, g, use_prev in schedule:
+        plain_opts = None if batch_class is None else CallOpts(class_rows=int(batch_class) * N)
+        for i, (t_val, a, kx, ke, b, g, use_prev) in enumerate(schedule):
             t_tensor.fill_(t_val)
-            step(t=t_tensor, q=q, coef=MultistepCoef(a, kx, ke, b, g, 0.0, int(use_prev), 0), w=w, opts=opts)
+            coef = MultistepCoef(a, kx, ke, b, g, 0.0, int(use_prev), 0)
+            if cfg and not guided[i]:  # the history q is the x0 of whichever step wrote it, conditional or guided: no special case
+                plain(t=t_tensor[:B], q=q, coef=coef, w=None, opts=plain_opts)
+                stale = True
+                continue
+            if stale:
+                x2[rows:].copy_(x2[:rows])
+                stale = False
+            step(t=t_tensor, q=q, coef=coef, w=w, opts=opts)
         return x2[:rows].clone() if cfg else x2
 
     @torch.no_grad()
@@ -439,7 +489,7 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
-                             batch_class=None, prompt_lengths=None, solver="ddim"):
+                             batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -458,9 +508,17 @@ class SpeechGenerator:
         `solver`: "ddim" (the strided update above) or "dpmpp2m" — the second-order multistep solver of multistep_schedule over the
         same timesteps: one ditto_guided_step_packed_multistep_opts call per step, the same forward, and an update that keeps the
         previous step's x0 prediction in a history buffer [S, d].  It is deterministic: `eta` != 0 and `noises` raise ValueError,
-        `seeds` give x_T only; every other argument works as above.  Returns fp32 [S, d]."""
+        `seeds` give x_T only; every other argument works as above.
+        `guidance_interval` (None, or a pair (t_lo, t_hi) of integer diffusion timesteps in [0, diffusion_steps - 1]): guidance in a
+        limited interval (Kynkaanniemi et al. 2024) — step i is guided if and only if t_lo <= tau_i <= t_hi (guided_steps); the
+        other steps use the conditional prediction alone, run the forward over the B conditional utterances only and cost the
+        unguided step.  One interval per call, either solver; it needs `guidance` and `null_text_emb`.  Seeds, tags and noise are
+        those of the call without it.  Returns fp32 [S, d]."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
+        interval = None if guidance_interval is None else validate_guidance_interval(guidance_interval, self.diffusion_steps)
+        if interval is not None and (guidance is None or null_text_emb is None):
+            raise ValueError("guidance_interval needs guidance= and null_text_emb=")
         multistep = solver == "dpmpp2m"
         if multistep and (eta != 0 or noises is not None):
             raise ValueError('solver="dpmpp2m" is deterministic: eta must be 0 and noises= cannot be given')
@@ -472,9 +530,21 @@ class SpeechGenerator:
         N = int((cu[1:] - cu[:-1]).max())
         pl = None if prompt_lengths is None else validate_prompt_lengths(prompt_lengths, cu)
 
+        def entry_of(eng):
+            return eng.guided_step_packed_multistep_ if multistep else eng.guided_step_packed_
+
+        def begin_plain(eng, x2):
+            """the step outside a guidance interval: the non-CFG entry on the conditional half of x2, with a conditioning image of
+            the texts alone — what the call without guidance runs"""
+            text = text_emb.to(eng.device).float().contiguous()
+            ct = validate_cu_seqlens(text_cu_seqlens, B, int(text.shape[0]), int(text.shape[0]), "text_cu_seqlens")
+            kw = {} if pl is None else dict(prompt_len=pl.to(eng.device))
+            return functools.partial(entry_of(eng), x2[:S], eng.prepare_text_packed(text, ct), B=B,
+                                     offsets=eng.guided_offsets_packed(cu, S, N, False), **kw)
+
         def begin(eng, cfg, seeds):
-            entry = eng.guided_step_packed_multistep_ if multistep else eng.guided_step_packed_
-            if null_text_cu_seqlens is not None and not cfg:
+            entry = entry_of(eng)
+            if null_text_cu_seqlens is not None and guidance is None:
                 raise ValueError("null_text_cu_seqlens without guidance")
             text = text_emb.to(eng.device).float()
             S_T = int(text.shape[0])
@@ -513,8 +583,8 @@ class SpeechGenerator:
             return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets)
 
         if multistep:
-            return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin)
-        return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin)
+            return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval, begin_plain)
+        return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval, begin_plain)
 
     def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim"):
         """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an

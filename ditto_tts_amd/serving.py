@@ -12,6 +12,10 @@ Two layers:
   * `DeviceBatch`: the packed batch on one GPU.  State, conditioning, offsets and the per-step arguments live in buffers sized once
     from the capacities; membership changes run in ONE launch of ditto_regroup_packed driven by a segment table, the step is
     ditto_guided_step_packed_tags_opts.  Nothing synchronises the device; steady-state steps allocate nothing.
+Guidance intervals (submit(guidance_interval=)): a request is guided only at the steps whose timestep lies in its interval, so a
+step's guided set G may be a part of the batch.  The unconditional copies of G are compacted behind the S speech rows, a change of G
+is a regroup like any membership change, and the step is ditto_guided_step_packed_mixed_opts (G everyone / nobody: the entries above
+with cfg 1 / 0).
 They serve the reference's sampling loop (reference src/model/SpeechGenerator.py:130-164) to a request stream.
 """
 from __future__ import annotations
@@ -44,10 +48,13 @@ class Request:
     `row` and conditioning rows `trow` / `nrow` in the batch's CURRENT buffers once admitted).  `prompt` ([P, d] or None): the
     speech prompt that stands in front of the `n_frames` generated rows; the utterance occupies `rows` = P + n_frames rows."""
     __slots__ = ("handle", "text", "null", "T", "T_null", "n_frames", "seed", "w", "n_steps", "eta", "x_T", "schedule", "i", "b",
-                 "row", "trow", "nrow", "prompt", "P")
+                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm")
 
-    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None):
+    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None, interval=None):
         self.handle, self.text, self.null = handle, text, null
+        # `interval`: None, or (t_lo, t_hi) — guided only at the steps whose timestep lies in it.  `in_g`: whether the batch's current
+        # layout holds its unconditional copy (None before its first regroup); `ntm`: the tmod row of its null text there
+        self.interval, self.in_g, self.ntm = interval, None, None
         self.prompt, self.P = prompt, 0 if prompt is None else int(prompt.shape[0])
         self.T, self.T_null = int(text.shape[0]), 0 if null is None else int(null.shape[0])
         self.n_frames, self.seed, self.w, self.n_steps, self.eta, self.x_T = n_frames, seed, w, n_steps, eta, x_T
@@ -58,6 +65,10 @@ class Request:
     def text_rows(self) -> int:
         return self.T + self.T_null
 
+    def guided_now(self) -> bool:
+        """whether the step it stands at applies the guidance: always without an interval, else t_lo <= tau <= t_hi"""
+        return self.interval is None or self.interval[0] <= self.schedule[self.i][0] <= self.interval[1]
+
     @property
     def rows(self) -> int:
         return self.P + self.n_frames
@@ -66,25 +77,57 @@ class Request:
 class Plan:
     """A membership change: `members` (Requests in their new order: the survivors in their old order, then the newcomers in
     admission order), which of them are `newcomers`, and the new layout — `cu` speech offsets [B + 1], `cu_text` / `cu_null` text
-    offsets [B + 1] (cu_null None without guidance)."""
-    __slots__ = ("members", "newcomers", "cu", "cu_text", "cu_null")
+    offsets [B + 1] (cu_null None without guidance).
+    Under guidance `in_g` [B] says which members are guided at the coming step (the set G; default: everyone).  Their unconditional
+    copies are compacted behind the S rows in batch order: `partner` [B] (the copy's index in [0, |G|), or -1), `cu_g` [|G| + 1] the
+    copies' offsets, `offsets` = [cu; S + cu_g[1:]] and `text_offsets` = [cu_text; T + cu_null_g[1:]] what the step's forward
+    reads.  The null conditioning of a member outside G is parked behind G's: `null_row` / `null_tm` [B] are each member's null K/V
+    row (counted from the T text rows) and tmod row (counted from the B text ones) — G's first, in order, then the parked ones."""
+    __slots__ = ("members", "newcomers", "cu", "cu_text", "cu_null", "in_g", "partner", "cu_g", "offsets", "text_offsets", "null_row",
+                 "null_tm")
 
-    def __init__(self, members, newcomers, guided):
+    def __init__(self, members, newcomers, guided, in_g=None):
         self.members, self.newcomers = list(members), list(newcomers)
         self.cu, self.cu_text = _cumulate(r.rows for r in members), _cumulate(r.T for r in members)
         self.cu_null = _cumulate(r.T_null for r in members) if guided else None
+        self.in_g = self.partner = self.cu_g = self.null_row = self.null_tm = None
+        self.offsets, self.text_offsets = self.cu, self.cu_text
+        if guided:
+            self.in_g = [True] * len(self.members) if in_g is None else [bool(f) for f in in_g]
+            self.partner = partner_table(self.in_g)
+            order = [j for j, f in enumerate(self.in_g) if f] + [j for j, f in enumerate(self.in_g) if not f]
+            G = sum(self.in_g)
+            self.cu_g = _cumulate(self.members[j].rows for j in order[:G])
+            at = _cumulate(self.members[j].T_null for j in order)
+            self.null_row, self.null_tm = [0] * len(order), [0] * len(order)
+            for k, j in enumerate(order):
+                self.null_row[j], self.null_tm[j] = at[k], k
+            self.offsets = self.cu + [self.cu[-1] + c for c in self.cu_g[1:]]
+            self.text_offsets = self.cu_text + [self.cu_text[-1] + c for c in at[1:G + 1]]
 
 
 class StepArgs:
     """One step over the batch in flight: per-utterance lists in slot order.  `coef` (solver "dpmpp2m" only, else None): each
-    utterance's (a, kx, ke, b, g, use_prev) of its own multistep_schedule; a, ce, cz and tags are then None."""
-    __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt", "coef")
+    utterance's (a, kx, ke, b, g, use_prev) of its own multistep_schedule; a, ce, cz and tags are then None.  Under guidance
+    `in_g` [B] says who is guided at this step (each request's guided_now(), asked once), `partner` [B] is its partner_table,
+    `G` the number of guided utterances and `S_G` their rows (None, None, 0, 0 unguided)."""
+    __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt", "coef", "in_g",
+                 "partner", "G", "S_G")
 
 
 def _cumulate(lengths) -> List[int]:
     out = [0]
     for n in lengths:
         out.append(out[-1] + int(n))
+    return out
+
+
+def partner_table(in_g) -> List[int]:
+    """partner[b]: the index of utterance b's unconditional copy among the guided ones, in batch order, or -1"""
+    out, g = [], 0
+    for f in in_g:
+        out.append(g if f else -1)
+        g += bool(f)
     return out
 
 
@@ -95,7 +138,7 @@ def _is_int(v) -> bool:
 class GuidedStream:
     """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None)
     h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None,
-                      prompt=None)
+                      prompt=None, guidance_interval=None)
     done = stream.step()          # [(handle, latents fp32 [n_frames, d] on the GPU), ...]
     stream.pending, stream.active, stream.drain()
 
@@ -109,7 +152,10 @@ class GuidedStream:
     generated rows at every step (sample_guided_packed(prompt_lengths=)).  The request then occupies P + n_frames of `max_rows`;
     `x_T` stays [n_frames, d] and so does the result.
     `solver` (one per stream): "ddim" — each request at its own index of its own strided_schedule — or "dpmpp2m": of its own
-    multistep_schedule (sample_guided_packed(solver="dpmpp2m")); requests then need eta = 0 and their seeds give x_T only."""
+    multistep_schedule (sample_guided_packed(solver="dpmpp2m")); requests then need eta = 0 and their seeds give x_T only.
+    `guidance_interval` (a guided "ddim" stream; None or (t_lo, t_hi)): the request is guided only at the steps of its schedule
+    whose timestep lies in the interval (sample_guided_packed(guidance_interval=)); at the others it takes no part in the
+    unconditional forward.  It counts against the capacities like any guided request, at every step."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
                  text_dim: int, hidden_dim: int, solver: str = "ddim"):
@@ -157,7 +203,7 @@ class GuidedStream:
         return t.detach()
 
     def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None,
-               prompt=None) -> StreamHandle:
+               prompt=None, guidance_interval=None) -> StreamHandle:
         """Queue one utterance.  Everything is validated here, on the host: a bad request raises ValueError and leaves the stream as
         it was; so does one that could never fit the capacities."""
         text = self._text(text_emb, "text_emb")
@@ -180,6 +226,14 @@ class GuidedStream:
             if guidance is not None or null_text_emb is not None:
                 raise ValueError("this stream is unguided: a request with guidance= or null_text_emb= belongs in a guided stream")
             null = None
+        interval = None
+        if guidance_interval is not None:
+            if not self.guided:
+                raise ValueError("this stream is unguided: guidance_interval= belongs in a guided stream")
+            if self.solver != "ddim":
+                raise NotImplementedError(f"guidance_interval= is served by \"ddim\" streams; this stream's solver is {self.solver}")
+            from .sampler import validate_guidance_interval
+            interval = validate_guidance_interval(guidance_interval, int(self._acp.shape[0]))
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)))
         elif not _is_int(seed) or not -2 ** 63 <= seed < 2 ** 63:
@@ -194,7 +248,7 @@ class GuidedStream:
                 raise ValueError(f"prompt: a floating-point tensor [P >= 1, {self.hidden_dim}] is needed")
             prompt = prompt.detach()
         req = Request(StreamHandle(self._next_id), text, null, n_frames, seed, None if guidance is None else float(guidance), n_steps,
-                      float(eta), x_T, schedule, prompt)
+                      float(eta), x_T, schedule, prompt, interval)
         if req.rows > self.max_rows:
             raise ValueError(f"a request of {req.rows} rows ({req.P} prompt + {req.n_frames} frames) can never fit max_rows = "
                              f"{self.max_rows}")
@@ -221,8 +275,12 @@ class GuidedStream:
         if not members:
             return []
         args = self._step_args(members)
-        if newcomers or self._dirty:
-            self.batch.regroup(Plan(members, newcomers, self.guided), args)
+        in_g = args.in_g
+        # a change of the guided set is a membership change of the unconditional region: the same one regroup serves it
+        if newcomers or self._dirty or any(r.in_g != f for r, f in zip(members, in_g or ())):
+            self.batch.regroup(Plan(members, newcomers, self.guided, in_g), args)
+            for r, f in zip(members, in_g or ()):
+                r.in_g = f
             self._dirty = False
         self._active = members
         self.batch.step(args)
@@ -261,6 +319,10 @@ class GuidedStream:
             s.a = s.ce = s.cz = s.tags = None
             s.coef = [tuple(q[1:]) for q in rows]
         s.w = [r.w for r in members] if self.guided else None
+        s.in_g = [r.guided_now() for r in members] if self.guided else None
+        s.partner = partner_table(s.in_g) if self.guided else None
+        s.G = sum(s.in_g) if self.guided else 0
+        s.S_G = sum(r.rows for r, f in zip(members, s.in_g) if f) if self.guided else 0
         s.seeds = [r.seed for r in members]
         s.handles = [r.handle for r in members]
         s.prompt = [r.P for r in members]
@@ -333,6 +395,46 @@ def retire_segments(done: List[Request], d4: int) -> List[List[int]]:
     return [[hip.REGROUP_COPY, _SRC_X, _DST_OUT, 0, (r.row + r.P) * d4, cu[k] * d4, r.n_frames * d4, 0] for k, r in enumerate(done)]
 
 
+def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int, tmod_new16: int, new_image: dict, multistep: bool,
+                  cu_pad: int):
+    """(segments, offsets tail) of the ONE launch that builds `plan`'s batch: host arithmetic only.  Units of 16 bytes: d4 per speech
+    row, kv16 per K/V row, tm16 per tmod row; tmod_old16 / tmod_new16: where tmod starts in the current / next conditioning image;
+    new_image[id] = (first unit of a newcomer's own image [text K/V | null K/V | tmod text, null] in the staging buffer, first unit
+    of its tmod).
+    Speech: every member's rows go to [cu[j], cu[j+1]) and, for a member of the guided set G, also to its unconditional copy at row
+    S + cu_g[partner[j]] through the segment's dup_off — a member entering G gets its copy from its conditional rows (the two are
+    equal after any update), one leaving G just has none.  Conditioning: text K/V and tmod in batch order; null K/V and tmod at
+    plan.null_row / plan.null_tm — G's rows compacted behind the texts where the forward reads them, the others parked behind G's.
+    The offsets [offsets | text_offsets] ride behind the segments in the same upload."""
+    guided = plan.in_g is not None
+    B, S, Tt = len(plan.members), plan.cu[-1], plan.cu_text[-1]
+    segs, xt_row = [], 0
+    for j, r in enumerate(plan.members):
+        new = r.handle.id in new_image
+        dup = (S + plan.cu_g[plan.partner[j]] - plan.cu[j]) * d4 if guided and plan.in_g[j] else 0
+        segs.extend(speech_segments(r, new, j, plan.cu[j], xt_row, d4, dup))
+        if new:
+            xt_row += staged_rows(r)
+        elif multistep:
+            segs.append(history_segment(r, plan.cu[j], d4))
+        if new:
+            base, own_tmod = new_image[r.handle.id]
+            source, kv_t, kv_n, tm_t, tm_n = _SRC_NEW_COND, base, base + r.T * kv16, own_tmod, own_tmod + tm16
+        else:
+            source, kv_t, kv_n = _SRC_COND, r.trow * kv16, r.nrow * kv16 if guided else 0
+            tm_t, tm_n = tmod_old16 + r.b * tm16, tmod_old16 + (r.ntm if guided else 0) * tm16
+        segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, kv_t, plan.cu_text[j] * kv16, r.T * kv16, 0])
+        segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, tm_t, tmod_new16 + j * tm16, tm16, 0])
+        if guided:
+            segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, kv_n, (Tt + plan.null_row[j]) * kv16, r.T_null * kv16, 0])
+            segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, tm_n, tmod_new16 + (B + plan.null_tm[j]) * tm16, tm16, 0])
+    tail = np.zeros(2 * cu_pad, dtype=np.int32)
+    tail[:len(plan.offsets)] = plan.offsets
+    tail[cu_pad:cu_pad + len(plan.text_offsets)] = plan.text_offsets
+    segs.append([hip.REGROUP_COPY, _SRC_TABLE, _DST_OFFSETS, 0, (len(segs) + 1) * 2, 0, 2 * cu_pad // 4, 0])
+    return segs, tail
+
+
 class DeviceBatch:
     """The packed batch of a GuidedStream on one GPU.  Buffers (sized once from the capacities): two state buffers [2 max_rows, d]
     ([max_rows, d] unguided) and two conditioning images (a regroup reads one and writes the other), a staging image for the
@@ -368,11 +470,12 @@ class DeviceBatch:
             self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
             self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
             # the step block: t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w fp32 [maxB] | tags uint32 [maxB] |
-            # prompt_len int32 [maxB] | (multistep) ditto_multistep_coef [maxB]
+            # prompt_len int32 [maxB] | partner int32 [maxB] | (multistep) ditto_multistep_coef [maxB]
             self.o_t, self.o_seeds = 0, _pad(nbB * 8, 16)
             self.o_f = self.o_seeds + _pad(self.maxB * 8, 16)
             self.f_stride = _pad(self.maxB * 4, 16)
-            self.o_coef = self.o_f + 6 * self.f_stride
+            (self.o_a, self.o_ce, self.o_cz, self.o_w, self.o_tags, self.o_prompt, self.o_partner,
+             self.o_coef) = (self.o_f + k * self.f_stride for k in range(8))
             self.block_bytes = self.o_coef + (C.sizeof(hip.MultistepCoef) * self.maxB if self.multistep else 0)
             self.block = _Upload(self.block_bytes, dev)
             self.max_seg = 8 * self.maxB + 8
@@ -386,9 +489,11 @@ class DeviceBatch:
 
     # ------------------------------------------------------------------ uploads
     def _send_block(self, a: StepArgs):
-        B, nb = a.B, self.halves * a.B
+        B = a.B
         buf = np.zeros(self.block_bytes, dtype=np.uint8)
-        buf[self.o_t:self.o_t + nb * 8].view(np.int64)[:] = a.t * self.halves
+        # t of the forward's utterances: the B in flight, then (under guidance) the guided ones' unconditional copies
+        tt = a.t + [a.t[j] for j, p in enumerate(a.partner) if p >= 0] if self.guided else a.t
+        buf[self.o_t:self.o_t + len(tt) * 8].view(np.int64)[:] = tt
         buf[self.o_seeds:self.o_seeds + B * 8].view(np.int64)[:] = a.seeds
         if self.multistep:             # ditto_multistep_coef: a, kx, ke, b, g, w fp32 | use_prev int32 | reserved
             co = buf[self.o_coef:self.o_coef + 32 * B].view(np.float32).reshape(B, 8)
@@ -396,13 +501,12 @@ class DeviceBatch:
             co[:, 5] = a.w if a.w is not None else 0.0
             co.view(np.int32)[:, 6] = [int(c[5]) for c in a.coef]
         else:
-            for k, v in enumerate((a.a, a.ce, a.cz, a.w if a.w is not None else [0.0] * B)):
-                o = self.o_f + k * self.f_stride
+            for o, v in ((self.o_a, a.a), (self.o_ce, a.ce), (self.o_cz, a.cz), (self.o_w, a.w if a.w is not None else [0.0] * B)):
                 buf[o:o + B * 4].view(np.float32)[:] = v
-            o = self.o_f + 4 * self.f_stride
-            buf[o:o + B * 4].view(np.uint32)[:] = a.tags
-        o = self.o_f + 5 * self.f_stride
-        buf[o:o + B * 4].view(np.int32)[:] = a.prompt
+            buf[self.o_tags:self.o_tags + B * 4].view(np.uint32)[:] = a.tags
+        buf[self.o_prompt:self.o_prompt + B * 4].view(np.int32)[:] = a.prompt
+        if self.guided:
+            buf[self.o_partner:self.o_partner + B * 4].view(np.int32)[:] = a.partner
         self.block.send(buf)
 
     def _block_ptr(self, off: int) -> int:
@@ -458,78 +562,63 @@ class DeviceBatch:
         S_T = Tt + (plan.cu_null[-1] if self.guided else 0)
         tmod_new = self._tmod_offset(S_T)
         at, xt_row = 0, 0
-        new_at = {}
+        new_image = {}
         for r in plan.newcomers:
-            new_at[r.handle.id] = at
+            new_image[r.handle.id] = (at // 16, (at + self._tmod_offset(r.text_rows)) // 16)
             at += self._condition(r, at)
-        segs = []
-        for j, r in enumerate(plan.members):
-            new = r.handle.id in new_at
-            if new and r.P:
+        for r in plan.members:             # the newcomers' prompts and own x_T, staged in the order speech_segments reads them
+            if r.handle.id not in new_image:
+                continue
+            if r.P:
                 self.x_T[xt_row:xt_row + r.P].copy_(r.prompt, non_blocking=True)
-            if new and r.x_T is not None:
+            if r.x_T is not None:
                 self.x_T[xt_row + r.P:xt_row + r.P + r.n_frames].copy_(r.x_T, non_blocking=True)
-            segs.extend(speech_segments(r, new, j, plan.cu[j], xt_row, d4, S * d4 if self.guided else 0))
-            if new:
-                xt_row += staged_rows(r)
-            elif self.multistep:
-                segs.append(history_segment(r, plan.cu[j], d4))
-            # conditioning: K/V rows and the tmod row of the text, then of the null text ([text_0 .. ; null_0 ..] under CFG)
-            if new:
-                base, own_tmod = new_at[r.handle.id], new_at[r.handle.id] + self._tmod_offset(r.text_rows)
-                source, kv_t, kv_n = _SRC_NEW_COND, base // 16, base // 16 + r.T * kv16
-                tm_t, tm_n = own_tmod // 16, own_tmod // 16 + tm16
-            else:
-                source, kv_t, kv_n = _SRC_COND, r.trow * kv16, r.nrow * kv16 if self.guided else 0
-                tm_t, tm_n = self._tmod_off // 16 + r.b * tm16, self._tmod_off // 16 + (self.B + r.b) * tm16
-            segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, kv_t, plan.cu_text[j] * kv16, r.T * kv16, 0])
-            segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, tm_t, tmod_new // 16 + j * tm16, tm16, 0])
-            if self.guided:
-                segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, kv_n, (Tt + plan.cu_null[j]) * kv16, r.T_null * kv16, 0])
-                segs.append([hip.REGROUP_COPY, source, _DST_COND, 0, tm_n, tmod_new // 16 + (B + j) * tm16, tm16, 0])
-        # the offsets ride behind the segments in the same upload and are copied from there: [cu; S + cu[1:]] (cu unguided) | cu_text
-        tail = np.zeros(2 * self.cu_pad, dtype=np.int32)
-        cu2 = plan.cu + [S + c for c in plan.cu[1:]] if self.guided else plan.cu
-        ct2 = plan.cu_text + [Tt + c for c in plan.cu_null[1:]] if self.guided else plan.cu_text
-        tail[:len(cu2)] = cu2
-        tail[self.cu_pad:self.cu_pad + len(ct2)] = ct2
-        segs.append([hip.REGROUP_COPY, _SRC_TABLE, _DST_OFFSETS, 0, (len(segs) + 1) * 2, 0, 2 * self.cu_pad // 4, 0])
+            xt_row += staged_rows(r)
+        segs, tail = regroup_table(plan, d4=d4, kv16=kv16, tm16=tm16, tmod_old16=self._tmod_off // 16, tmod_new16=tmod_new // 16,
+                                   new_image=new_image, multistep=self.multistep, cu_pad=self.cu_pad)
         self._run_table(segs, tail, None)
         self.cur = 1 - self.cur
         self.B, self.S, self.T_text, self._tmod_off = B, S, Tt, tmod_new
         for j, r in enumerate(plan.members):
             r.b, r.row, r.trow = j, plan.cu[j], plan.cu_text[j]
-            r.nrow = Tt + plan.cu_null[j] if self.guided else None
+            r.nrow = Tt + plan.null_row[j] if self.guided else None
+            r.ntm = B + plan.null_tm[j] if self.guided else None
         self._block_sent = True
 
     def step(self, a: StepArgs):
-        """ditto_guided_step_packed_tags_opts over the batch in flight, in place on the current state (with a prompted utterance
-        in flight: ditto_guided_step_packed_tags_prompt_opts, the prompt lengths riding in the step block).  Solver "dpmpp2m":
-        ditto_guided_step_packed_multistep_opts on the current state and history, each utterance at its block entry."""
+        """One library call over the batch in flight, in place on the current state; every per-utterance argument comes from the
+        step block.
+          * solver "dpmpp2m": ditto_guided_step_packed_multistep_opts on the state and the history, each utterance at its own
+            coefficient entry;
+          * some utterances guided, some not (guidance intervals): ditto_guided_step_packed_mixed_opts over the B utterances and
+            the G copies, with the partner table;
+          * else ditto_guided_step_packed_tags_opts (a prompted utterance in flight: ..._tags_prompt_opts) — with cfg 1 over
+            [x; x] when everyone is guided, with cfg 0 over the conditional rows when nobody is (or the stream is unguided)."""
         if not self._block_sent:
             self._send_block(a)
         self._block_sent = False
-        eng, f = self.eng, self.o_f
-        nb, rows = self.halves * a.B, self.halves * a.S
-        ws = eng.workspace_packed(nb, rows, a.S_T)
+        eng, at = self.eng, self._block_ptr
+        cfg = self.guided and a.G > 0
+        ws = eng.workspace_packed(a.B + a.G, a.S + a.S_G, a.S_T)         # the forward: the B utterances and the G copies
+        # the arguments every entry shares: in front (model, state, conditioning, t, speech and text offsets) and behind
+        head = (eng.handle, self.x[self.cur].data_ptr(), self.cond[self.cur].data_ptr(), at(self.o_t), self.offsets.data_ptr(),
+                self.offsets.data_ptr() + 4 * self.cu_pad)
+        tail = (self.rope[0].data_ptr(), self.rope[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+                None if self.opts is None else C.byref(self.opts))
+        prompt = at(self.o_prompt) if any(a.prompt) else None
+        noise = (None, at(self.o_seeds), at(self.o_tags))                 # no buffer: Philox of the seeds at each utterance's tag
+        coef = (at(self.o_a), at(self.o_ce), at(self.o_cz))
         if self.multistep:
             hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
-                eng.handle, self.x[self.cur].data_ptr(), self.cond[self.cur].data_ptr(), self._block_ptr(self.o_t),
-                self.offsets.data_ptr(), self.offsets.data_ptr() + 4 * self.cu_pad,
-                self._block_ptr(f + 5 * self.f_stride) if any(a.prompt) else None, self.q[self.cur].data_ptr(), None,
-                self._block_ptr(self.o_coef), None, a.B, a.S, a.max_N, a.S_T, a.max_T, int(self.guided), self.rope[0].data_ptr(),
-                self.rope[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if self.opts is None else C.byref(self.opts)))
-            return
-        if any(a.prompt):
-            entry, head = self.lib.ditto_guided_step_packed_tags_prompt_opts, (self._block_ptr(f + 5 * self.f_stride),)
+                *head, prompt, self.q[self.cur].data_ptr(), None, at(self.o_coef), None, a.B, a.S, a.max_N, a.S_T, a.max_T,
+                int(self.guided), *tail))
+        elif 0 < a.G < a.B:
+            hip.check(self.lib.ditto_guided_step_packed_mixed_opts(
+                *head, at(self.o_partner), prompt, *noise, at(self.o_w), *coef, a.B, a.G, a.S, a.S_G, a.max_N, a.S_T, a.max_T, *tail))
         else:
-            entry, head = self.lib.ditto_guided_step_packed_tags_opts, ()
-        hip.check(entry(
-            eng.handle, self.x[self.cur].data_ptr(), self.cond[self.cur].data_ptr(), self._block_ptr(self.o_t), self.offsets.data_ptr(),
-            self.offsets.data_ptr() + 4 * self.cu_pad, *head, None, self._block_ptr(self.o_seeds), self._block_ptr(f + 4 * self.f_stride),
-            self._block_ptr(f + 3 * self.f_stride) if self.guided else None, self._block_ptr(f), self._block_ptr(f + self.f_stride),
-            self._block_ptr(f + 2 * self.f_stride), a.B, a.S, a.max_N, a.S_T, a.max_T, int(self.guided), self.rope[0].data_ptr(),
-            self.rope[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if self.opts is None else C.byref(self.opts)))
+            entry = self.lib.ditto_guided_step_packed_tags_opts if prompt is None else self.lib.ditto_guided_step_packed_tags_prompt_opts
+            hip.check(entry(*head, *(() if prompt is None else (prompt,)), *noise, at(self.o_w) if cfg else None, *coef, a.B, a.S,
+                            a.max_N, a.S_T, a.max_T, int(cfg), *tail))
 
     def retire(self, done: List[Request]) -> List[torch.Tensor]:
         """the generated rows of the utterances that leave, copied out of the state in one launch; the batch keeps its layout (with

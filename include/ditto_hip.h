@@ -626,6 +626,31 @@ int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const vo
                                             const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, const float* w, int B,
                                             int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
                                             void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+/* ---- Guidance in a limited interval (Kynkaanniemi et al. 2024) over a request stream: classifier-free guidance is applied on a range
+ * of noise levels only, so a step of the stream holds guided and unguided utterances side by side and only the guided ones need the
+ * unconditional forward.  The reference has no guided sampler: like the strided loop this is pinned by its own formulas.
+ * Layout of a step with G of the B utterances guided: x2, eps2 fp32 [S + S_G, d] — every utterance in rows [0, S), the guided ones'
+ *   unconditional copies compacted behind them in rows [S, S + S_G) in batch order; cu device int32 [B + G + 1] = [cu; S + cu_G[1:]]
+ *   (copy g owns rows [cu[B + g], cu[B + g + 1])); partner device int32 [B]: the copy of utterance b in [0, G), or -1.
+ * ditto_guided_update_packed_mixed: ditto_guided_update_packed_tags_prompt per utterance — with a partner its cfg != 0 arithmetic
+ *   (eps_u read at the copy's rows, x' written to b's rows and to the copy's), without one its cfg == 0 arithmetic (nothing behind
+ *   row S is read or written).  w, a, ce, cz, tags, seeds: [B]; noise packed fp32 [S, d]; prompt_len NULL or device int32 [B].
+ *   partner[b] is clamped into [-1, G - 1]; the copy's span has b's own length n_b and its first row is clamped into
+ *   [S, S + S_G - n_b] (n_b > S_G: no copy, b is updated without guidance): a bad table gives wrong rows — a copy's span may run
+ *   into the next copy's — never an access outside the buffers.  G == 0 needs S_G == 0 and the reverse.
+ * ditto_guided_step_packed_mixed_opts: one packed forward over the B + G utterances of x2 — cond is ditto_text_precompute_packed
+ *   over [text_0 .. text_{B-1}; null_g ..] with cu_text [B + G + 1], t int64 [B + G] with a copy's t its partner's — then that
+ *   update.  Workspace: ditto_packed_workspace_bytes(cfg, B + G, S + S_G, S_T). */
+int ditto_guided_update_packed_mixed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                     const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                     const int32_t* partner, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,
+                                     ditto_stream_t stream);
+int ditto_guided_step_packed_mixed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                        const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
+                                        const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce,
+                                        const float* cz, int B, int G, int S, int S_G, int max_N, int S_T, int max_T,
+                                        const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                        ditto_stream_t stream, const ditto_call_opts* opts);
 /* Span-masked training over a packed batch with prompts (cu, prompt_len and their clamp as above; every buffer fp32 [S, d]).  z is
  *   either `noise`, a packed buffer whose prompt rows are not read, or Philox of (seeds[b], tag) at the generated-local quad index:
  *   exactly one of the two is given.
