@@ -1220,6 +1220,10 @@ int ditto_gemm_tn_bf16(const void* X, int ldx, const void* Y, int ldy, float* ou
                        int k_splits, int tile, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
     if (!X || !Y || !out || !workspace || Mo < 8 || No < 8 || K <= 0 || (Mo | No | ldx | ldy) % 8 || ldo < No)
         return fail(DITTO_ERR_ARG, "bad argument to ditto_gemm_tn_bf16");
+    if (ldx < Mo || ldy < No) return fail(DITTO_ERR_ARG, "ditto_gemm_tn_bf16: ldx must cover Mo columns and ldy No columns");
+    // the LDS-DMA moves 16 B per lane (ld % 8 keeps every row aligned once the base is); the split-K reduce stores f32x4
+    if (((uintptr_t)X | (uintptr_t)Y) % 16) return fail(DITTO_ERR_ARG, "ditto_gemm_tn_bf16: X and Y must be 16-byte aligned");
+    if (k_splits > 1 && (uintptr_t)out % 16) return fail(DITTO_ERR_ARG, "ditto_gemm_tn_bf16: split-K needs a 16-byte aligned out");
     if (tile != 128 && tile != 256) return fail(DITTO_ERR_ARG, "tile must be 128 or 256");
     if ((uintptr_t)workspace % 256) return fail(DITTO_ERR_ARG, "workspace must be 256-byte aligned");
     const int S = k_splits > 1 ? k_splits : 1;

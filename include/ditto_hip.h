@@ -382,7 +382,9 @@ int ditto_gemm_lnq_bf16(const void* h, int ldh, int h_is_bf16, const float* gamm
  * nn.Linear (what autograd computes for reference src/TrainDiTTO.py:90).  tile = 128 (128x128, two workgroups per CU) or
  * 256 (256x256, one per CU); k_splits > 1: the contraction is split, fp32 partial tiles are summed in slice order
  * (deterministic).  workspace: 256 + k_splits * Mo * No * 4 bytes (256 alone when k_splits <= 1), 256-byte aligned.
- * Mo, No, ldx, ldy multiples of 8. */
+ * Mo, No, ldx, ldy multiples of 8.  DITTO_ERR_ARG for what the kernels cannot serve: ldx < Mo; ldy < No; X or Y not
+ * 16-byte aligned (the tiles are staged 16 B per lane); out not 16-byte aligned when k_splits > 1 (the reduce stores 16 B
+ * per lane); also ldo < No, and ldo != No when k_splits > 1.  DITTO_ERR_SIZE for a workspace that is too small. */
 int ditto_gemm_tn_bf16(const void* X, int ldx, const void* Y, int ldy, float* out, int ldo, int Mo, int No, int K,
                        int k_splits, int tile, void* workspace, size_t workspace_bytes, ditto_stream_t stream);
 
