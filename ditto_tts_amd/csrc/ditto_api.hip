@@ -1485,16 +1485,65 @@ int ditto_guided_update_packed(float* x2, const float* eps2, const float* noise,
     return DITTO_OK;
 }
 
+// ---- guidance rescale (guided_rescale.hip): the scratch [coef_out | scale | partials], each part 256-byte aligned ----
+struct RescaleReq { const float* phi; void* scratch; size_t scratch_bytes; };
+static size_t rescale_head_bytes(int B) { return al((size_t)B * sizeof(ditto_multistep_coef)) + al((size_t)B * sizeof(float)); }
+static size_t rescale_bytes(int B, int max_N, int d) {
+    return rescale_head_bytes(B) + al((size_t)B * guidance_rescale_chunks(max_N, d) * 4 * sizeof(double));
+}
+// every argument of a rescale is checked here, before any launch; coefs != NULL: the ditto_multistep_coef form (w and ke inside)
+static int check_rescale(const char* who, const float* eps2, const float* w, const float* phi, const float* coef_in,
+                         const ditto_multistep_coef* coefs, const int32_t* cu, const int32_t* partner, int B, int G, int S, int S_G,
+                         int max_N, int d, const void* scratch, size_t scratch_bytes) {
+    if (!eps2 || !phi || !cu || !scratch) return fail(DITTO_ERR_ARG, "%s: null eps2 / phi / cu / scratch", who);
+    if (!coefs == !coef_in) return fail(DITTO_ERR_ARG, "%s: exactly one of coef_in (fp32 [B], with w) and coefs (device [B]) is needed", who);
+    if (coef_in && !w) return fail(DITTO_ERR_ARG, "%s: guidance rescale needs w (fp32 [B])", who);
+    if ((uintptr_t)coefs % 16) return fail(DITTO_ERR_ARG, "%s: coefs must be 16-byte aligned", who);
+    if ((uintptr_t)scratch % 256) return fail(DITTO_ERR_ARG, "%s: the rescale scratch must be 256-byte aligned", who);
+    if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
+    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
+    if (partner && (G < 0 || G > B || S_G < 0 || S_G > S || (G > 0) != (S_G > 0) || G > S_G))
+        return fail(DITTO_ERR_SHAPE, "%s: need 0 <= G <= B, G <= S_G <= S, and S_G == 0 exactly when G == 0 (B %d, G %d, S %d, S_G %d)",
+                    who, B, G, S, S_G);
+    if (scratch_bytes < rescale_bytes(B, max_N, d))
+        return fail(DITTO_ERR_SIZE, "%s: the rescale scratch needs %zu bytes (ditto_guidance_rescale_bytes)", who, rescale_bytes(B, max_N, d));
+    return DITTO_OK;
+}
+static RescaleArgs rescale_args(const float* eps2, const float* w, const float* phi, const float* coef_in,
+                                const ditto_multistep_coef* coefs, const int32_t* cu, const int32_t* prompt_len, const int32_t* partner,
+                                int B, int G, int S, int S_G, int d, void* scratch, size_t scratch_bytes) {
+    RescaleArgs a{};
+    char* p = (char*)scratch;
+    a.eps2 = eps2; a.phi = phi; a.cu = cu; a.prompt_len = prompt_len; a.partner = partner;
+    a.B = B; a.G = G; a.S = S; a.S_G = S_G; a.d = d;
+    if (coefs) {   // the whole struct is copied, ke scaled: the per-utterance multistep update reads coefs_out[b]
+        a.w = &coefs->w; a.coef_in = &coefs->ke; a.coef_out = &((ditto_multistep_coef*)p)->ke;
+        a.cstride = 8; a.koff = 2; a.copy = 8;
+    } else {
+        a.w = w; a.coef_in = coef_in; a.coef_out = (float*)p;
+        a.cstride = 1; a.koff = 0; a.copy = 1;
+    }
+    a.scale = (float*)(p + al((size_t)B * sizeof(ditto_multistep_coef)));
+    a.partial = (double*)(p + rescale_head_bytes(B));
+    const size_t slots = (scratch_bytes - rescale_head_bytes(B)) / ((size_t)B * 4 * sizeof(double));
+    a.slots = slots > 0x7fffffff ? 0x7fffffff : (int)slots;
+    return a;
+}
+
 // the packed guided step with one scalar step tag (tags NULL) or one tag per utterance (guided_tags.hip)
 static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
                               const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const uint32_t* tags,
-                              bool per_utt, const float* w, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
+                              bool per_utt, const float* w, const float* a, const float* ce_in, const float* cz, int B, int S, int max_N,
                               int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                               size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
-                              const int32_t* prompt_len = nullptr, bool prompted = false) {
+                              const int32_t* prompt_len = nullptr, bool prompted = false, const RescaleReq* rs = nullptr) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
     if (prompted && !prompt_len) return fail(DITTO_ERR_ARG, "%s: null prompt_len (int32 [B])", who);
-    if (int rc = check_guided_update(who, x2, x2, noise, seeds, w, a, ce, cz, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
+    if (rs)   // guidance rescale: the statistics between the forward and the update, the update then reads ce[b] s_b from the scratch
+        if (int rc = check_rescale(who, x2, w, rs->phi, ce_in, nullptr, cu_speech, nullptr, B, 0, S, 0, max_N, m->cfg.hidden_dim,
+                                   rs->scratch, rs->scratch_bytes))
+            return rc;
+    if (int rc = check_guided_update(who, x2, x2, noise, seeds, w, a, ce_in, cz, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
     if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
     if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
     if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
@@ -1506,6 +1555,13 @@ static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const
                                   BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
             return rc;
         ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        const float* ce = ce_in;
+        if (rs) {
+            const RescaleArgs ra = rescale_args(eps, w, rs->phi, ce_in, nullptr, cu_speech, prompted ? prompt_len : nullptr, nullptr, B, 0,
+                                                S, 0, m->cfg.hidden_dim, rs->scratch, rs->scratch_bytes);
+            HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
+            ce = ra.coef_out;
+        }
         if (prompted)
             HIP_TRY(launch_guided_update_prompt(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, B, S, max_N,
                                                 m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
@@ -1621,16 +1677,21 @@ int ditto_multistep_update_packed(float* x2, const float* eps2, float* q, const 
     return DITTO_OK;
 }
 
-int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
-                                            const int32_t* cu_text, const int32_t* prompt_len, float* q,
-                                            const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, const float* w, int B,
-                                            int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
-                                            void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
-    const char* who = "ditto_guided_step_packed_multistep_opts";
+static int guided_step_multistep(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                 const int32_t* cu_text, const int32_t* prompt_len, float* q, const ditto_multistep_coef* step,
+                                 const ditto_multistep_coef* coefs_in, const float* w, int B, int S, int max_N, int S_T, int max_T, int cfg,
+                                 const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                 ditto_stream_t stream, const ditto_call_opts* opts, const RescaleReq* rs = nullptr) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (int rc = check_multistep(who, x2, x2, q, step, coefs, w, cu_speech, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
+    if (int rc = check_multistep(who, x2, x2, q, step, coefs_in, w, cu_speech, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
     if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
     if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
+    if (rs) {
+        if (!coefs_in) return fail(DITTO_ERR_ARG, "%s: guidance rescale needs coefs (device [B])", who);
+        if (int rc = check_rescale(who, x2, nullptr, rs->phi, nullptr, coefs_in, cu_speech, nullptr, B, 0, S, 0, max_N, m->cfg.hidden_dim,
+                                   rs->scratch, rs->scratch_bytes))
+            return rc;
+    }
     return with_opts(opts, [&]() -> int {
         const int nb = cfg ? 2 * B : B, rows = cfg ? 2 * S : S;          // the forward of guided_step_packed: [x; x] x [text; null]
         float* eps;
@@ -1638,10 +1699,26 @@ int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const vo
                                   BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
             return rc;
         ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        const ditto_multistep_coef* coefs = coefs_in;
+        if (rs) {                                                        // ke[b] s_b: the per-utterance update reads the scratch's copy
+            const RescaleArgs ra = rescale_args(eps, nullptr, rs->phi, nullptr, coefs_in, cu_speech, prompt_len, nullptr, B, 0, S, 0,
+                                                m->cfg.hidden_dim, rs->scratch, rs->scratch_bytes);
+            HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
+            coefs = (const ditto_multistep_coef*)rs->scratch;
+        }
         HIP_TRY(launch_multistep_update_packed(x2, eps, q, step, coefs, w, cu_speech, prompt_len, B, S, max_N, m->cfg.hidden_dim, cfg != 0,
                                                (hipStream_t)stream));
         return DITTO_OK;
     });
+}
+
+int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                            const int32_t* cu_text, const int32_t* prompt_len, float* q,
+                                            const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, const float* w, int B,
+                                            int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
+                                            void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_multistep("ditto_guided_step_packed_multistep_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q, step, coefs,
+                                 w, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
 }
 
 // ---- guidance in a limited interval: a step in which G of the B utterances are guided (guided_mixed.hip) ----
@@ -1670,28 +1747,100 @@ int ditto_guided_update_packed_mixed(float* x2, const float* eps2, const float* 
     return DITTO_OK;
 }
 
-int ditto_guided_step_packed_mixed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
-                                        const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
-                                        const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce,
-                                        const float* cz, int B, int G, int S, int S_G, int max_N, int S_T, int max_T,
-                                        const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
-                                        ditto_stream_t stream, const ditto_call_opts* opts) {
-    const char* who = "ditto_guided_step_packed_mixed_opts";
+static int guided_step_mixed(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                             const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
+                             const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce_in, const float* cz,
+                             int B, int G, int S, int S_G, int max_N, int S_T, int max_T, const float* rope_cos, const float* rope_sin,
+                             void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
+                             const RescaleReq* rs = nullptr) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (int rc = check_mixed(who, x2, x2, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, B, G, S, S_G, max_N, m->cfg.hidden_dim))
+    if (int rc = check_mixed(who, x2, x2, noise, seeds, tags, w, a, ce_in, cz, cu_speech, partner, B, G, S, S_G, max_N, m->cfg.hidden_dim))
         return rc;
     if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
     if (S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
+    if (rs)
+        if (int rc = check_rescale(who, x2, w, rs->phi, ce_in, nullptr, cu_speech, partner, B, G, S, S_G, max_N, m->cfg.hidden_dim,
+                                   rs->scratch, rs->scratch_bytes))
+            return rc;
     return with_opts(opts, [&]() -> int {
         float* eps;                                                   // the forward over [x; the guided ones' copies] x [text; their null]
         if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
                                   BatchLayout::packed(B + G, S + S_G, max_N, S_T, max_T, cu_speech, cu_text), &eps))
             return rc;
         ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        const float* ce = ce_in;
+        if (rs) {
+            const RescaleArgs ra = rescale_args(eps, w, rs->phi, ce_in, nullptr, cu_speech, prompt_len, partner, B, G, S, S_G,
+                                                m->cfg.hidden_dim, rs->scratch, rs->scratch_bytes);
+            HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
+            ce = ra.coef_out;
+        }
         HIP_TRY(launch_guided_update_mixed(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, prompt_len, B, G, S, S_G, max_N,
                                            m->cfg.hidden_dim, (hipStream_t)stream));
         return DITTO_OK;
     });
+}
+
+int ditto_guided_step_packed_mixed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                        const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
+                                        const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce,
+                                        const float* cz, int B, int G, int S, int S_G, int max_N, int S_T, int max_T,
+                                        const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                        ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_mixed("ditto_guided_step_packed_mixed_opts", m, x2, cond, t, cu_speech, cu_text, partner, prompt_len, noise, seeds,
+                             tags, w, a, ce, cz, B, G, S, S_G, max_N, S_T, max_T, rope_cos, rope_sin, workspace, workspace_bytes, stream,
+                             opts);
+}
+
+// ---- guidance rescale (Lin et al. 2024, section 3.4; guided_rescale.hip): the statistics alone, and the steps that use them ----
+size_t ditto_guidance_rescale_bytes(int B, int max_N, int d) {
+    if (B <= 0 || max_N <= 0 || d <= 0 || d % 64) {
+        fail(DITTO_ERR_SHAPE, "ditto_guidance_rescale_bytes: B and max_N must be positive and d %% 64 == 0");
+        return 0;
+    }
+    return rescale_bytes(B, max_N, d);
+}
+
+int ditto_guidance_rescale_packed(const float* eps2, const float* w, const float* phi, const float* coef_in,
+                                  const ditto_multistep_coef* coefs, const int32_t* cu, const int32_t* prompt_len, const int32_t* partner,
+                                  int B, int G, int S, int S_G, int max_N, int d, void* scratch, size_t scratch_bytes,
+                                  ditto_stream_t stream) {
+    if (int rc = check_rescale("ditto_guidance_rescale_packed", eps2, w, phi, coef_in, coefs, cu, partner, B, G, S, S_G, max_N, d, scratch,
+                               scratch_bytes))
+        return rc;
+    const RescaleArgs ra = rescale_args(eps2, w, phi, coef_in, coefs, cu, prompt_len, partner, B, G, S, S_G, d, scratch, scratch_bytes);
+    HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_packed_rescale_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                          const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
+                                          const int64_t* seeds, uint32_t step, const uint32_t* tags, const float* w, const float* phi,
+                                          const float* a, const float* ce, const float* cz, int B, int G, int S, int S_G, int max_N,
+                                          int S_T, int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
+                                          size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
+                                          const ditto_call_opts* opts) {
+    const char* who = "ditto_guided_step_packed_rescale_opts";
+    const RescaleReq rs{phi, scratch, scratch_bytes};
+    if (!w) return fail(DITTO_ERR_ARG, "%s: guidance rescale needs w (fp32 [B])", who);
+    if (partner)   // some utterances guided: the mixed entry's forward and update
+        return guided_step_mixed(who, m, x2, cond, t, cu_speech, cu_text, partner, prompt_len, noise, seeds, tags, w, a, ce, cz, B, G, S, S_G,
+                                 max_N, S_T, max_T, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts, &rs);
+    return guided_step_packed(who, m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, tags, tags != nullptr, w, a, ce, cz, B, S, max_N,
+                              S_T, max_T, 1, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts, prompt_len, prompt_len != nullptr,
+                              &rs);
+}
+
+int ditto_guided_step_packed_multistep_rescale_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                                    const int32_t* cu_speech, const int32_t* cu_text, const int32_t* prompt_len, float* q,
+                                                    const ditto_multistep_coef* coefs, const float* phi, int B, int S, int max_N, int S_T,
+                                                    int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
+                                                    size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
+                                                    const ditto_call_opts* opts) {
+    const RescaleReq rs{phi, scratch, scratch_bytes};
+    return guided_step_multistep("ditto_guided_step_packed_multistep_rescale_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q,
+                                 nullptr, coefs, nullptr, B, S, max_N, S_T, max_T, 1, rope_cos, rope_sin, workspace, workspace_bytes, stream,
+                                 opts, &rs);
 }
 
 // ---- span-masked training over a packed batch with prompts (span_train.hip) ----

@@ -50,13 +50,7 @@ __global__ __launch_bounds__(256) void multistep_update_kernel(float* __restrict
                                                                const float* __restrict__ w, const int32_t* __restrict__ cu,
                                                                const int32_t* __restrict__ prompt_len, int S, int d) {
     const int b = blockIdx.y;
-    GuidedSpan sp;
-    if (prompt_len) {
-        const PromptSpan ps = prompt_span(cu, prompt_len, b, S, d);     // (guided_update.h)
-        sp = {ps.base4 + ps.p4, ps.n4 - ps.p4};                         // the generated rows [cu[b] + P_b, cu[b+1])
-    } else {
-        sp = guided_span(cu, b, S, d);
-    }
+    const GuidedSpan sp = generated_span(cu, prompt_len, b, S, d);      // (guided_update.h) the rows [cu[b] + P_b, cu[b+1])
     ditto_multistep_coef k = step;
     if (PER_UTT) k = coefs[b];
     else k.w = CFG ? w[b] : 0.f;

@@ -40,6 +40,43 @@ __device__ __forceinline__ PromptSpan prompt_span(const int32_t* cu, const int32
     return {(size_t)r0 * d / 4, (size_t)nb * d / 4, (size_t)p * d / 4};
 }
 
+// the generated rows of utterance b, [cu[b] + P_b, cu[b+1]) (prompt_len NULL: the whole utterance): what the multistep update and the
+// guidance-rescale statistics run over
+__device__ __forceinline__ GuidedSpan generated_span(const int32_t* cu, const int32_t* prompt_len, int b, int S, int d) {
+    if (prompt_len) {
+        const PromptSpan ps = prompt_span(cu, prompt_len, b, S, d);
+        return {ps.base4 + ps.p4, ps.n4 - ps.p4};
+    }
+    return guided_span(cu, b, S, d);
+}
+
+// utterance b of a step in which G of the B utterances are guided (guided_mixed.hip): its generated rows and, with a partner, the
+// same rows of its unconditional copy behind row S.  Clamps: guided_span's and prompt_span's; the partner into [-1, G - 1]; the copy's
+// span has b's own length n_b, its first row clamped into [S, S + S_G - n_b] (no copy at all when n_b > S_G: g = -1).  The offset
+// cu[B + g + 1] is not read.  Statement for statement the head of guided_update_mixed_kernel, which keeps its own text: routed through
+// this helper its scalar instructions come out in another order, and that kernel is held to its machine code
+// (tests/test_gpu_rescale_kernel.py holds these clamps to the values documented for that kernel).
+struct MixedSpan { size_t base4, n4; int urow, g; };     // urow: the copy's first generated row (g >= 0 only)
+__device__ __forceinline__ MixedSpan mixed_span(const int32_t* cu, const int32_t* partner, const int32_t* prompt_len, int b, int B,
+                                                int G, int S, int S_G, int d) {
+    int r0 = cu[b];
+    r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
+    int n = cu[b + 1] - r0;
+    n = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);                      // guided_span's clamp
+    int g = partner[b];
+    g = g < -1 ? -1 : (g > G - 1 ? G - 1 : g);
+    int u0 = 0;
+    if (n > S_G) g = -1;
+    if (g >= 0) {
+        u0 = cu[B + g];
+        u0 = u0 < S ? S : (u0 > S + S_G - n ? S + S_G - n : u0);
+    }
+    int p = prompt_len ? prompt_len[b] : 0;
+    p = p < 0 ? 0 : (p > n - 1 ? n - 1 : p);                        // prompt_span's clamp
+    const size_t d4 = (size_t)d / 4;
+    return {(size_t)(r0 + p) * d4, (size_t)(n - p) * d4, u0 + p, g};
+}
+
 // quads [i0, n4) of one utterance at a grid stride: xc / ec (xu / eu) = its first quad in the conditional (unconditional) half, nz in
 // the noise buffer.  PADDED: quads from valid4 on are written as 0 and read nothing.  draw: whether a Philox utterance draws at all.
 // i0 and stride come from the __global__ function: read here, blockDim / gridDim compile to a vector load of the implicit arguments.

@@ -304,6 +304,27 @@ hipError_t launch_span_noise_packed(const float* x0, const float* noise, const i
 hipError_t launch_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
                                   const int32_t* prompt_len, double n_elems, float* grad, float* loss, float* partial, int B, int S,
                                   int max_N, int d, hipStream_t s);
+// ---------------- guided_rescale.hip ----------------
+// guidance rescale (Lin et al. 2024, section 3.4): coef_out[b] = coef_in[b] * s32_b with s_b = 1 + phi_b (sigma_c / sigma_e - 1) over
+// utterance b's generated rows of eps2 (e = fmaf(w, c - u, u), sums in fp64), 1 where b is unguided, phi_b == 0 or sigma_e == 0.
+// The statistics are cut into partials of DITTO_RESCALE_CHUNK_QUADS 16-byte quads of the utterance's own generated region, so that
+// s32_b depends on the utterance's rows, w_b and phi_b only: the constant is part of the bits.
+#define DITTO_RESCALE_CHUNK_QUADS 4096
+struct RescaleArgs {
+    const float* eps2;               // [2S, d] (partner NULL: u at row offset S) or [S + S_G, d] (u at the partner copy's rows)
+    const float* w;                  // guidance scale of utterance b at w[b * cstride]
+    const float* phi;                // fp32 [B], clamped into [0, 1]
+    const float* coef_in;            // the coefficient of utterance b at coef_in[b * cstride]
+    float* coef_out;                 // ... and where its product goes; `copy` words from koff words in front of it are copied along
+    float* scale;                    // fp32 [B]: s32
+    double* partial;                 // [B, slots, 4]: sum c, sum c^2, sum e, sum e^2 of every chunk
+    const int32_t* cu; const int32_t* prompt_len; const int32_t* partner;
+    int B, G, S, S_G, d;
+    int cstride, koff, copy;         // arrays: 1, 0, 1; ditto_multistep_coef [B]: 8, 2 (ke), 8 with w = &coefs->w
+    int slots;                       // partials per utterance the scratch holds (an utterance with more chunks uses the first `slots`)
+};
+size_t guidance_rescale_chunks(int max_N, int d);   // chunks of the longest generated region: the scratch's slots and the grid's columns
+hipError_t launch_guidance_rescale(const RescaleArgs& a, int max_N, hipStream_t s);
 // ---------------- regroup_packed.hip ----------------
 // the buffers a regroup's segments name by index, sizes in 16-byte units (a null pointer: no such buffer)
 #define DITTO_REGROUP_BUFS 6

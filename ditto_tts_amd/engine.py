@@ -278,12 +278,16 @@ class DenoiseEngine:
     def guided_step_packed_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, a: torch.Tensor, ce: torch.Tensor,
                             cz: torch.Tensor, w: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             seeds: Optional[torch.Tensor] = None, step: int = 0, cu_seqlens=None, max_seqlen: Optional[int] = None,
-                            offsets=None, opts: Optional[hip.CallOpts] = None, prompt_len: Optional[torch.Tensor] = None):
+                            offsets=None, opts: Optional[hip.CallOpts] = None, prompt_len: Optional[torch.Tensor] = None,
+                            phi: Optional[torch.Tensor] = None, rescale_scratch: Optional[torch.Tensor] = None):
         """guided_step_ over a packed batch, IN PLACE on x2 fp32 [2S, d] ([x; x], w given) or [S, d]
         (ditto_guided_step_packed_opts).  `offsets`: guided_offsets_packed(...) built once per sampling call (else built here from
         `cu_seqlens`); `cond`: prepare_text_packed over [text; null] (2B utterances) or text.  noise: packed fp32 [S, d].
         `prompt_len` (device int32 [B], validated by the caller: varlen.validate_prompt_lengths): the first prompt_len[b] rows of
-        utterance b are a speech prompt the update leaves alone (ditto_guided_step_packed_prompt_opts)."""
+        utterance b are a speech prompt the update leaves alone (ditto_guided_step_packed_prompt_opts).
+        `phi` (device fp32 [B] in [0, 1], with w): guidance rescale — ditto_guided_step_packed_rescale_opts computes each utterance's
+        s32 from this step's eps and the same update runs with ce s32; `rescale_scratch`: rescale_scratch(B, max_N) built once per
+        sampling call (else taken here)."""
         sd, noise = self._guided_args("guided_step_packed_", x2, 2, B, a, ce, cz, w, noise, seeds)
         cfg = w is not None
         nb = 2 * B if cfg else B
@@ -300,9 +304,20 @@ class DenoiseEngine:
         tt = self._t64(t, nb)
         ws = self.workspace_packed(nb, rows, cond.T)
         c, s = self.rope_tables(max_N)
+        if prompt_len is not None and not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous()
+                                           and prompt_len.shape == (B,)):
+            raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        if phi is not None:
+            if not cfg:
+                raise ValueError("guidance rescale needs the guidance scales w")
+            phi, rs = self._rescale_args(phi, rescale_scratch, B, max_N)
+            hip.check(self.lib.ditto_guided_step_packed_rescale_opts(
+                self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), None,
+                _ptr(prompt_len), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, None, w.data_ptr(), phi.data_ptr(), a.data_ptr(),
+                ce.data_ptr(), cz.data_ptr(), B, 0, S, 0, max_N, cond.T, cond.max_len, c.data_ptr(), s.data_ptr(), ws.data_ptr(),
+                ws.numel(), rs.data_ptr(), rs.numel(), _stream(), None if opts is None else C.byref(opts)))
+            return x2
         if prompt_len is not None:
-            if not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous() and prompt_len.shape == (B,)):
-                raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
             entry, head = self.lib.ditto_guided_step_packed_prompt_opts, (prompt_len.data_ptr(),)
         else:
             entry, head = self.lib.ditto_guided_step_packed_opts, ()
@@ -313,15 +328,24 @@ class DenoiseEngine:
         return x2
 
     def guided_step_packed_multistep_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
-                                      coef: hip.MultistepCoef, w: Optional[torch.Tensor] = None, cu_seqlens=None,
+                                      coef: Optional[hip.MultistepCoef], w: Optional[torch.Tensor] = None, cu_seqlens=None,
                                       max_seqlen: Optional[int] = None, offsets=None, opts: Optional[hip.CallOpts] = None,
-                                      prompt_len: Optional[torch.Tensor] = None):
+                                      prompt_len: Optional[torch.Tensor] = None, coefs: Optional[torch.Tensor] = None,
+                                      phi: Optional[torch.Tensor] = None, rescale_scratch: Optional[torch.Tensor] = None):
         """guided_step_packed_ with the update of the second-order multistep solver (ditto_guided_step_packed_multistep_opts), IN
         PLACE on x2 and on the history `q` fp32 [S, d]: the previous step's x0 prediction, read only when coef.use_prev and
         rewritten by every step.  `coef`: the step every utterance stands at (sampler.multistep_schedule; its w is ignored, the
-        guidance scales are `w` fp32 [B]).  x2, cond, t, offsets, opts, prompt_len: as guided_step_packed_."""
+        guidance scales are `w` fp32 [B]).  x2, cond, t, offsets, opts, prompt_len: as guided_step_packed_.
+        `coefs` (instead of coef and w: device fp32 [B, 8], one ditto_multistep_coef per utterance, its guidance scale inside) with
+        `phi` (device fp32 [B]): guidance rescale under guidance — ditto_guided_step_packed_multistep_rescale_opts, the per-utterance
+        update with ke s32; `rescale_scratch` as in guided_step_packed_."""
+        if (coefs is None) != (phi is None) or (coefs is None) == (coef is None):
+            raise ValueError("guided_step_packed_multistep_: coef (with w), or coefs with phi")
         self._guided_args("guided_step_packed_multistep_", x2, 2, B, None, None, None, w, None, None)
-        cfg = w is not None
+        cfg = w is not None or coefs is not None
+        if coefs is not None and not (coefs.is_cuda and coefs.dtype == torch.float32 and coefs.is_contiguous()
+                                      and coefs.shape == (B, 8) and coefs.data_ptr() % 16 == 0):
+            raise ValueError(f"coefs must be a contiguous, 16-byte aligned fp32 CUDA tensor of shape [{B}, 8]")
         nb = 2 * B if cfg else B
         rows = x2.shape[0]
         if cfg and rows % 2:
@@ -341,11 +365,52 @@ class DenoiseEngine:
         tt = self._t64(t, nb)
         ws = self.workspace_packed(nb, rows, cond.T)
         c, s = self.rope_tables(max_N)
+        if coefs is not None:
+            phi, rs = self._rescale_args(phi, rescale_scratch, B, max_N)
+            hip.check(self.lib.ditto_guided_step_packed_multistep_rescale_opts(
+                self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(),
+                _ptr(prompt_len), q.data_ptr(), coefs.data_ptr(), phi.data_ptr(), B, S, max_N, cond.T, cond.max_len, c.data_ptr(),
+                s.data_ptr(), ws.data_ptr(), ws.numel(), rs.data_ptr(), rs.numel(), _stream(), None if opts is None else C.byref(opts)))
+            return x2
         hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
             self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
             q.data_ptr(), C.byref(coef), None, _ptr(w), B, S, max_N, cond.T, cond.max_len, int(cfg), c.data_ptr(), s.data_ptr(),
             ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
         return x2
+
+    # ------------------------------------------------------------------ guidance rescale (csrc/guided_rescale.hip)
+    def rescale_scratch(self, B: int, max_N: int) -> torch.Tensor:
+        """the scratch of a guidance rescale over B utterances of at most max_N rows (ditto_guidance_rescale_bytes): uint8, zeroed"""
+        need = int(self.lib.ditto_guidance_rescale_bytes(int(B), int(max_N), self.cfg.hidden_dim))
+        if need == 0:
+            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
+        return torch.zeros(need, dtype=torch.uint8, device=self.device)
+
+    def _rescale_args(self, phi, scratch, B, max_N):
+        if not (phi.is_cuda and phi.dtype == torch.float32 and phi.is_contiguous() and phi.shape == (B,)):
+            raise ValueError(f"phi must be a contiguous fp32 CUDA tensor of shape [{B}]")
+        if scratch is None:
+            scratch = self.rescale_scratch(B, max_N)
+        if not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.data_ptr() % 256 == 0):
+            raise ValueError("rescale_scratch must be a contiguous, 256-byte aligned uint8 CUDA tensor")
+        return phi, scratch
+
+    def guidance_rescale_packed(self, eps2: torch.Tensor, offsets: torch.Tensor, phi: torch.Tensor, B: int, S: int, max_N: int, *,
+                                w: Optional[torch.Tensor] = None, coef_in: Optional[torch.Tensor] = None,
+                                coefs: Optional[torch.Tensor] = None, prompt_len: Optional[torch.Tensor] = None,
+                                partner: Optional[torch.Tensor] = None, G: int = 0, S_G: int = 0,
+                                scratch: Optional[torch.Tensor] = None):
+        """The guidance-rescale statistics alone (ditto_guidance_rescale_packed) over eps2 fp32 [2S, d] (partner None: the
+        unconditional half at row offset S) or [S + S_G, d] (partner device int32 [B]: the mixed layout of guided_mixed.hip);
+        `offsets`: the device int32 offsets the step's update reads.  Either `coef_in` and `w` (fp32 [B]) or `coefs` (fp32 [B, 8]:
+        ditto_multistep_coef).  Returns (coef_out — fp32 [B], or [B, 8] with ke scaled —, scale fp32 [B]): views of `scratch`."""
+        phi, scratch = self._rescale_args(phi, scratch, B, max_N)
+        hip.check(self.lib.ditto_guidance_rescale_packed(
+            eps2.data_ptr(), _ptr(w), phi.data_ptr(), _ptr(coef_in), _ptr(coefs), offsets.data_ptr(), _ptr(prompt_len), _ptr(partner),
+            B, int(G), S, int(S_G), max_N, int(eps2.shape[1]), scratch.data_ptr(), scratch.numel(), _stream()))
+        o_scale, _ = hip.rescale_scratch_layout(B)
+        out = scratch[:32 * B].view(torch.float32).view(B, 8) if coefs is not None else scratch[:4 * B].view(torch.float32)
+        return out, scratch[o_scale:o_scale + 4 * B].view(torch.float32)
 
     # ------------------------------------------------------------------ span-masked training (csrc/span_train.hip)
     def _span_args(self, who, buf, cu_seqlens, prompt_lengths, seeds, noise):

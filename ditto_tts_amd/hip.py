@@ -127,6 +127,16 @@ class MultistepCoef(C.Structure):
                 ("use_prev", C.c_int32), ("reserved", C.c_int32)]
 
 
+RESCALE_CHUNK_QUADS = 4096    # DITTO_RESCALE_CHUNK_QUADS: 16-byte quads per partial of the guidance-rescale statistics (part of its bits)
+
+
+def rescale_scratch_layout(B: int):
+    """(byte offset of scale fp32 [B], byte offset of the partials) in the scratch of ditto_guidance_rescale_bytes; coef_out — fp32 [B]
+    or ditto_multistep_coef [B] — stands at byte 0."""
+    al = lambda n: (n + 255) // 256 * 256
+    return al(32 * B), al(32 * B) + al(4 * B)
+
+
 REGROUP_BUFS = 6
 REGROUP_SEG_WORDS = 8      # ditto_regroup_seg as int32 / uint32 words: kind, source, dest, aux, src_off, dst_off, n, dup_off (16-byte units)
 REGROUP_COPY, REGROUP_DRAW = 0, 1
@@ -222,6 +232,13 @@ SYMBOLS = {
     # guidance in a limited interval: a step in which G of the B utterances are guided (partner device int32 [B])
     "ditto_guided_update_packed_mixed": (_i, [_vp] * 12 + [_i] * 6 + [_vp]),
     "ditto_guided_step_packed_mixed_opts": (_i, [_vp] * 15 + [_i] * 7 + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    # guidance rescale (Lin et al. 2024): per-utterance statistics of eps that patch ce / ke, and the steps that use them
+    "ditto_guidance_rescale_bytes": (_sz, [_i, _i, _i]),
+    "ditto_guidance_rescale_packed": (_i, [_vp] * 8 + [_i] * 6 + [_vp, _sz, _vp]),
+    "ditto_guided_step_packed_rescale_opts": (_i, [_vp] * 10 + [C.c_uint32] + [_vp] * 6 + [_i] * 7 + [_vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                                                                                  C.POINTER(CallOpts)]),
+    "ditto_guided_step_packed_multistep_rescale_opts": (_i, [_vp] * 10 + [_i] * 5 + [_vp, _vp, _vp, _sz, _vp, _sz, _vp,
+                                                                                    C.POINTER(CallOpts)]),
     "ditto_span_noise_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ditto_span_mse_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),

@@ -137,6 +137,32 @@ def guidance_vector(guidance, B: int) -> Optional[torch.Tensor]:
     return g.contiguous()
 
 
+def rescale_vector(guidance_rescale, B: int) -> Optional[torch.Tensor]:
+    """`guidance_rescale` (None, a number in [0, 1], or a sequence of B of them) as a CPU fp32 tensor [B] of blend factors phi, or
+    None (no rescale): guidance rescale, Lin et al. 2024 section 3.4."""
+    if guidance_rescale is None:
+        return None
+    v = guidance_rescale
+    if isinstance(v, torch.Tensor) and v.dtype != torch.bool and not v.is_complex() and v.dim() == 1:
+        v = v.detach().cpu().tolist()
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        v = [v] * B
+    if not isinstance(v, (list, tuple)) or not all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in v):
+        raise ValueError(f"guidance_rescale: None, a number or a sequence of {B} numbers is needed, got {guidance_rescale!r}")
+    if len(v) != B:
+        raise ValueError(f"guidance_rescale: {B} values expected (one per utterance), got {len(v)}")
+    if not all(math.isfinite(x) and 0.0 <= x <= 1.0 for x in v):
+        raise ValueError(f"guidance_rescale: every value must lie in [0, 1], got {guidance_rescale!r}")
+    return torch.tensor([float(x) for x in v], dtype=torch.float32)
+
+
+def _padded_rescale(guidance_rescale):
+    """the padded layouts have no guidance rescale"""
+    if guidance_rescale is not None:
+        raise NotImplementedError("guidance_rescale= is served over packed batches: pack the batch and call "
+                                  "sample_guided_packed(guidance_rescale=)")
+
+
 def _padded_solver(solver):
     """the padded layouts run the strided (DDIM) solver only"""
     if solver not in SOLVERS:
@@ -321,12 +347,13 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
                                cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None, prompt_lengths=None,
-                               solver="ddim"):
+                               solver="ddim", guidance_rescale=None):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
         DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step, with optional
         classifier-free guidance: the step runs ONE forward on the doubled batch [x; x] x [text; null_text] and combines
         eps_u + w (eps_c - eps_u).  sample_guided with one uniform `cfg_scale` over a dense batch: one library call per step."""
         _padded_solver(solver)
+        _padded_rescale(guidance_rescale)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         if speech_lengths is not None or text_lengths is not None:
@@ -338,7 +365,7 @@ class SpeechGenerator:
 
     # ---------------------------------------------------------------- guided strided loop over a variable-length batch
     def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval=None,
-                     begin_plain=None):
+                     begin_plain=None, rescale=None):
         """The strided loop of sample_guided and sample_guided_packed.  `begin(eng, cfg, seeds)` is the layout's own prologue: it
         builds the conditioning and the state x2 (rows [x_T; room for the unconditional half] under guidance, else x_T) and returns
         (x2, max length, step) with `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)` the layout's library call bound to
@@ -347,7 +374,9 @@ class SpeechGenerator:
         `begin_plain(eng, x2)`'s step — the layout's non-CFG call on the conditional half of x2, built only when a step needs it.
         The unconditional half is filled from the conditional one before the first guided step, and again before the first one
         behind unguided steps; in between every guided update writes both halves itself.  With no guided step at all the call is
-        the one without guidance."""
+        the one without guidance.
+        `rescale` (rescale_vector's phi [B], packed batches): every guided step computes each utterance's guidance-rescale factor
+        from its eps and updates with ce s32 (the step's phi= argument); unguided steps rescale nothing."""
         if seeds is not None and noises is not None:
             raise ValueError("seeds= excludes noises=")
         gv = guidance_vector(guidance, B)
@@ -368,6 +397,7 @@ class SpeechGenerator:
         # every step's coefficients in one upload: coef[i] = (a, ce, sigma) x B
         coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
         w = gv.to(eng.device) if cfg else None
+        rs = {} if rescale is None or not cfg else dict(phi=rescale.to(eng.device), rescale_scratch=eng.rescale_scratch(B, N))
         t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
         z = torch.empty_like(x2[:rows]) if seeds is None else None
         opts = plain_opts = None
@@ -395,13 +425,17 @@ class SpeechGenerator:
             if stale:                                        # [x; x], once; then every guided update writes both halves itself
                 x2[rows:].copy_(x2[:rows])
                 stale = False
-            step(t=t_tensor, a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val, opts=opts)
+            step(t=t_tensor, a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val, opts=opts, **rs)
         return x2[:rows].clone() if cfg else x2
 
-    def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval=None, begin_plain=None):
+    def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval=None, begin_plain=None,
+                        rescale=None):
         """_guided_loop for solver="dpmpp2m": the same prologue (`begin`, whose step is engine.guided_step_packed_multistep_ bound to
         x2, its conditioning and offsets), then one library call per step of multistep_schedule over x2 and the history q — one
-        buffer [S, d] per call, written by step 0 before any step reads it.  Each step's coefficients travel as a host struct."""
+        buffer [S, d] per call, written by step 0 before any step reads it.  Each step's coefficients travel as a host struct.
+        `rescale` (rescale_vector's phi [B]): the guided steps read their coefficients from DEVICE memory instead — one
+        ditto_multistep_coef per utterance and step, uploaded once, the guidance scale inside — so that the rescale can patch each
+        utterance's ke before the per-utterance update runs."""
         from .hip import CallOpts, MultistepCoef
         gv = guidance_vector(guidance, B)
         if gv is not None and null_text_emb is None:
@@ -420,6 +454,14 @@ class SpeechGenerator:
         stale = cfg
         q = torch.empty_like(x2[:rows])
         w = gv.to(eng.device) if cfg else None
+        coefs = None
+        if rescale is not None and cfg:
+            table = torch.zeros(len(schedule), B, 8, dtype=torch.float32)
+            for i, row in enumerate(schedule):
+                table[i, :, :5] = torch.tensor(row[1:6], dtype=torch.float32)
+                table[i, :, 5] = gv
+                table.view(torch.int32)[i, :, 6] = int(row[6])                      # use_prev
+            coefs, phi, rs = table.to(eng.device), rescale.to(eng.device), eng.rescale_scratch(B, N)
         t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
         opts = None if batch_class is None else CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
         plain_opts = None if batch_class is None else CallOpts(class_rows=int(batch_class) * N)
@@ -433,13 +475,16 @@ class SpeechGenerator:
             if stale:
                 x2[rows:].copy_(x2[:rows])
                 stale = False
-            step(t=t_tensor, q=q, coef=coef, w=w, opts=opts)
+            if coefs is not None:
+                step(t=t_tensor, q=q, coef=None, coefs=coefs[i], phi=phi, rescale_scratch=rs, opts=opts)
+            else:
+                step(t=t_tensor, q=q, coef=coef, w=w, opts=opts)
         return x2[:rows].clone() if cfg else x2
 
     @torch.no_grad()
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
                       null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
-                      cond_by_audio=False, batch_class=None, prompt_lengths=None, solver="ddim"):
+                      cond_by_audio=False, batch_class=None, prompt_lengths=None, solver="ddim", guidance_rescale=None):
         """The strided (DDIM) loop of sample_latents_strided with what serving needs: per-utterance `speech_lengths` /
         `text_lengths` (a padded batch; rows past an utterance's length are exactly 0 in the result and padding never reaches a
         valid row), per-utterance `guidance` (None: no CFG; a number; or [B] numbers), and per-utterance `seeds`.  One library
@@ -453,8 +498,9 @@ class SpeechGenerator:
         callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
         count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
         The padded layout has no speech prompts (`prompt_lengths` raises NotImplementedError): pack the batch and call
-        sample_guided_packed; so does solver="dpmpp2m".  Returns fp32 [B, N, d]."""
+        sample_guided_packed; so do solver="dpmpp2m" and `guidance_rescale`.  Returns fp32 [B, N, d]."""
         _padded_solver(solver)
+        _padded_rescale(guidance_rescale)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         B, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
@@ -489,7 +535,7 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
-                             batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None):
+                             batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None, guidance_rescale=None):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -513,12 +559,22 @@ class SpeechGenerator:
         limited interval (Kynkaanniemi et al. 2024) — step i is guided if and only if t_lo <= tau_i <= t_hi (guided_steps); the
         other steps use the conditional prediction alone, run the forward over the B conditional utterances only and cost the
         unguided step.  One interval per call, either solver; it needs `guidance` and `null_text_emb`.  Seeds, tags and noise are
-        those of the call without it.  Returns fp32 [S, d]."""
+        those of the call without it.
+        `guidance_rescale` (None, a number in [0, 1], or one per utterance): guidance rescale (Lin et al. 2024, section 3.4) — at
+        every guided step the guided prediction e = u + w (c - u) of utterance b is multiplied by s_b = 1 + phi_b (sigma_c / sigma_e -
+        1), the standard deviations taken over the utterance's generated rows of this step's eps (csrc/guided_rescale.hip; fp64
+        sums, an utterance's factor depends on its own rows only).  The step is ditto_guided_step_packed_rescale_opts (2M:
+        ..._multistep_rescale_opts): the same forward, two small launches, and the same update with ce s_b (ke s_b).  It needs
+        `guidance` and `null_text_emb`; phi_b = 0 gives utterance b the bits of the call without the argument; steps outside a
+        `guidance_interval` rescale nothing.  None: the call as it was.  Returns fp32 [S, d]."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         interval = None if guidance_interval is None else validate_guidance_interval(guidance_interval, self.diffusion_steps)
         if interval is not None and (guidance is None or null_text_emb is None):
             raise ValueError("guidance_interval needs guidance= and null_text_emb=")
+        if guidance_rescale is not None and (guidance is None or null_text_emb is None):
+            raise ValueError("guidance_rescale needs guidance= and null_text_emb=")
+        rescale = rescale_vector(guidance_rescale, len(cu_seqlens) - 1)
         multistep = solver == "dpmpp2m"
         if multistep and (eta != 0 or noises is not None):
             raise ValueError('solver="dpmpp2m" is deterministic: eta must be 0 and noises= cannot be given')
@@ -583,8 +639,9 @@ class SpeechGenerator:
             return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets)
 
         if multistep:
-            return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval, begin_plain)
-        return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval, begin_plain)
+            return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval, begin_plain, rescale)
+        return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval, begin_plain,
+                                 rescale)
 
     def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim"):
         """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an

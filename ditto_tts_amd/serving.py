@@ -16,6 +16,9 @@ Guidance intervals (submit(guidance_interval=)): a request is guided only at the
 step's guided set G may be a part of the batch.  The unconditional copies of G are compacted behind the S speech rows, a change of G
 is a regroup like any membership change, and the step is ditto_guided_step_packed_mixed_opts (G everyone / nobody: the entries above
 with cfg 1 / 0).
+Guidance rescale (submit(guidance_rescale=)): each request's blend factor phi rides in the step block; a step in which a guided
+request has phi > 0 runs the ..._rescale_opts form of its entry — the same forward and update, with the two statistics launches of
+csrc/guided_rescale.hip in between — over a scratch sized once from the capacities.
 They serve the reference's sampling loop (reference src/model/SpeechGenerator.py:130-164) to a request stream.
 """
 from __future__ import annotations
@@ -48,10 +51,11 @@ class Request:
     `row` and conditioning rows `trow` / `nrow` in the batch's CURRENT buffers once admitted).  `prompt` ([P, d] or None): the
     speech prompt that stands in front of the `n_frames` generated rows; the utterance occupies `rows` = P + n_frames rows."""
     __slots__ = ("handle", "text", "null", "T", "T_null", "n_frames", "seed", "w", "n_steps", "eta", "x_T", "schedule", "i", "b",
-                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm")
+                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm", "phi")
 
-    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None, interval=None):
+    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None, interval=None, phi=0.0):
         self.handle, self.text, self.null = handle, text, null
+        self.phi = float(phi)                        # guidance rescale: the blend factor in [0, 1]; 0 = none
         # `interval`: None, or (t_lo, t_hi) — guided only at the steps whose timestep lies in it.  `in_g`: whether the batch's current
         # layout holds its unconditional copy (None before its first regroup); `ntm`: the tmod row of its null text there
         self.interval, self.in_g, self.ntm = interval, None, None
@@ -110,9 +114,10 @@ class StepArgs:
     """One step over the batch in flight: per-utterance lists in slot order.  `coef` (solver "dpmpp2m" only, else None): each
     utterance's (a, kx, ke, b, g, use_prev) of its own multistep_schedule; a, ce, cz and tags are then None.  Under guidance
     `in_g` [B] says who is guided at this step (each request's guided_now(), asked once), `partner` [B] is its partner_table,
-    `G` the number of guided utterances and `S_G` their rows (None, None, 0, 0 unguided)."""
+    `G` the number of guided utterances and `S_G` their rows (None, None, 0, 0 unguided).  `phi` [B]: each utterance's guidance-rescale
+    blend factor (0: none)."""
     __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt", "coef", "in_g",
-                 "partner", "G", "S_G")
+                 "partner", "G", "S_G", "phi")
 
 
 def _cumulate(lengths) -> List[int]:
@@ -138,7 +143,7 @@ def _is_int(v) -> bool:
 class GuidedStream:
     """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None)
     h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None,
-                      prompt=None, guidance_interval=None)
+                      prompt=None, guidance_interval=None, guidance_rescale=None)
     done = stream.step()          # [(handle, latents fp32 [n_frames, d] on the GPU), ...]
     stream.pending, stream.active, stream.drain()
 
@@ -155,7 +160,9 @@ class GuidedStream:
     multistep_schedule (sample_guided_packed(solver="dpmpp2m")); requests then need eta = 0 and their seeds give x_T only.
     `guidance_interval` (a guided "ddim" stream; None or (t_lo, t_hi)): the request is guided only at the steps of its schedule
     whose timestep lies in the interval (sample_guided_packed(guidance_interval=)); at the others it takes no part in the
-    unconditional forward.  It counts against the capacities like any guided request, at every step."""
+    unconditional forward.  It counts against the capacities like any guided request, at every step.
+    `guidance_rescale` (a guided stream, either solver; None or a number in [0, 1]): the request's guidance-rescale blend factor
+    (sample_guided_packed(guidance_rescale=)), applied at the steps at which it is guided."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
                  text_dim: int, hidden_dim: int, solver: str = "ddim"):
@@ -203,7 +210,7 @@ class GuidedStream:
         return t.detach()
 
     def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None,
-               prompt=None, guidance_interval=None) -> StreamHandle:
+               prompt=None, guidance_interval=None, guidance_rescale=None) -> StreamHandle:
         """Queue one utterance.  Everything is validated here, on the host: a bad request raises ValueError and leaves the stream as
         it was; so does one that could never fit the capacities."""
         text = self._text(text_emb, "text_emb")
@@ -234,6 +241,14 @@ class GuidedStream:
                 raise NotImplementedError(f"guidance_interval= is served by \"ddim\" streams; this stream's solver is {self.solver}")
             from .sampler import validate_guidance_interval
             interval = validate_guidance_interval(guidance_interval, int(self._acp.shape[0]))
+        phi = 0.0
+        if guidance_rescale is not None:
+            if not self.guided:
+                raise ValueError("this stream is unguided: guidance_rescale= belongs in a guided stream")
+            if (isinstance(guidance_rescale, bool) or not isinstance(guidance_rescale, (int, float)) or not math.isfinite(guidance_rescale)
+                    or not 0.0 <= guidance_rescale <= 1.0):
+                raise ValueError(f"guidance_rescale: a number in [0, 1] is needed, got {guidance_rescale!r}")
+            phi = float(guidance_rescale)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)))
         elif not _is_int(seed) or not -2 ** 63 <= seed < 2 ** 63:
@@ -248,7 +263,7 @@ class GuidedStream:
                 raise ValueError(f"prompt: a floating-point tensor [P >= 1, {self.hidden_dim}] is needed")
             prompt = prompt.detach()
         req = Request(StreamHandle(self._next_id), text, null, n_frames, seed, None if guidance is None else float(guidance), n_steps,
-                      float(eta), x_T, schedule, prompt, interval)
+                      float(eta), x_T, schedule, prompt, interval, phi)
         if req.rows > self.max_rows:
             raise ValueError(f"a request of {req.rows} rows ({req.P} prompt + {req.n_frames} frames) can never fit max_rows = "
                              f"{self.max_rows}")
@@ -326,6 +341,7 @@ class GuidedStream:
         s.seeds = [r.seed for r in members]
         s.handles = [r.handle for r in members]
         s.prompt = [r.P for r in members]
+        s.phi = [r.phi for r in members]
         return s
 
 
@@ -435,6 +451,22 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
     return segs, tail
 
 
+def step_block_layout(max_utterances: int, guided: bool, multistep: bool) -> dict:
+    """Byte offsets of the per-step argument block (host arithmetic): t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w
+    fp32 [maxB] | tags uint32 [maxB] | prompt_len int32 [maxB] | partner int32 [maxB] | (multistep) ditto_multistep_coef [maxB] |
+    phi fp32 [maxB] — the guidance-rescale blend factors, appended behind everything else: the fields in front keep the offsets
+    they had before it existed.  "f_stride": bytes of one fp32 / int32 field; "bytes": the whole block."""
+    maxB, nbB = int(max_utterances), (2 if guided else 1) * int(max_utterances)
+    lay = {"t": 0, "seeds": _pad(nbB * 8, 16)}
+    o_f = lay["seeds"] + _pad(maxB * 8, 16)
+    lay["f_stride"] = _pad(maxB * 4, 16)
+    for k, name in enumerate(("a", "ce", "cz", "w", "tags", "prompt", "partner", "coef")):
+        lay[name] = o_f + k * lay["f_stride"]
+    lay["phi"] = _pad(lay["coef"] + (C.sizeof(hip.MultistepCoef) * maxB if multistep else 0), 16)
+    lay["bytes"] = lay["phi"] + lay["f_stride"]
+    return lay
+
+
 class DeviceBatch:
     """The packed batch of a GuidedStream on one GPU.  Buffers (sized once from the capacities): two state buffers [2 max_rows, d]
     ([max_rows, d] unguided) and two conditioning images (a regroup reads one and writes the other), a staging image for the
@@ -469,15 +501,13 @@ class DeviceBatch:
             self.x_T = torch.zeros(self.maxS, d, dtype=torch.float32, device=dev)
             self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
             self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
-            # the step block: t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w fp32 [maxB] | tags uint32 [maxB] |
-            # prompt_len int32 [maxB] | partner int32 [maxB] | (multistep) ditto_multistep_coef [maxB]
-            self.o_t, self.o_seeds = 0, _pad(nbB * 8, 16)
-            self.o_f = self.o_seeds + _pad(self.maxB * 8, 16)
-            self.f_stride = _pad(self.maxB * 4, 16)
-            (self.o_a, self.o_ce, self.o_cz, self.o_w, self.o_tags, self.o_prompt, self.o_partner,
-             self.o_coef) = (self.o_f + k * self.f_stride for k in range(8))
-            self.block_bytes = self.o_coef + (C.sizeof(hip.MultistepCoef) * self.maxB if self.multistep else 0)
+            lay = step_block_layout(self.maxB, self.guided, self.multistep)
+            self.f_stride, self.block_bytes = lay["f_stride"], lay["bytes"]
+            (self.o_t, self.o_seeds, self.o_a, self.o_ce, self.o_cz, self.o_w, self.o_tags, self.o_prompt, self.o_partner, self.o_coef,
+             self.o_phi) = (lay[k] for k in ("t", "seeds", "a", "ce", "cz", "w", "tags", "prompt", "partner", "coef", "phi"))
             self.block = _Upload(self.block_bytes, dev)
+            # the guidance-rescale scratch, once, for maxB utterances of at most maxS generated rows
+            self.rescale = engine.rescale_scratch(self.maxB, self.maxS) if self.guided else None
             self.max_seg = 8 * self.maxB + 8
             self.table = _Upload(self.max_seg * 4 * hip.REGROUP_SEG_WORDS + 2 * self.cu_pad * 4, dev)
             engine.workspace_packed(nbB, self.halves * self.maxS, self.maxT)
@@ -507,6 +537,7 @@ class DeviceBatch:
         buf[self.o_prompt:self.o_prompt + B * 4].view(np.int32)[:] = a.prompt
         if self.guided:
             buf[self.o_partner:self.o_partner + B * 4].view(np.int32)[:] = a.partner
+            buf[self.o_phi:self.o_phi + B * 4].view(np.float32)[:] = a.phi
         self.block.send(buf)
 
     def _block_ptr(self, off: int) -> int:
@@ -593,7 +624,10 @@ class DeviceBatch:
           * some utterances guided, some not (guidance intervals): ditto_guided_step_packed_mixed_opts over the B utterances and
             the G copies, with the partner table;
           * else ditto_guided_step_packed_tags_opts (a prompted utterance in flight: ..._tags_prompt_opts) — with cfg 1 over
-            [x; x] when everyone is guided, with cfg 0 over the conditional rows when nobody is (or the stream is unguided)."""
+            [x; x] when everyone is guided, with cfg 0 over the conditional rows when nobody is (or the stream is unguided).
+        A step in which a guided utterance has phi > 0 runs the guidance-rescale form of its entry
+        (ditto_guided_step_packed_multistep_rescale_opts; ditto_guided_step_packed_rescale_opts with the partner table when only
+        some are guided, without it when everyone is): phi from the step block, the scratch built once."""
         if not self._block_sent:
             self._send_block(a)
         self._block_sent = False
@@ -608,6 +642,18 @@ class DeviceBatch:
         prompt = at(self.o_prompt) if any(a.prompt) else None
         noise = (None, at(self.o_seeds), at(self.o_tags))                 # no buffer: Philox of the seeds at each utterance's tag
         coef = (at(self.o_a), at(self.o_ce), at(self.o_cz))
+        if cfg and any(p > 0 and g for p, g in zip(a.phi, a.in_g)):
+            tail_rs = tail[:4] + (self.rescale.data_ptr(), self.rescale.numel()) + tail[4:]
+            if self.multistep:
+                hip.check(self.lib.ditto_guided_step_packed_multistep_rescale_opts(
+                    *head, prompt, self.q[self.cur].data_ptr(), at(self.o_coef), at(self.o_phi), a.B, a.S, a.max_N, a.S_T, a.max_T,
+                    *tail_rs))
+            else:
+                mixed = a.G < a.B
+                hip.check(self.lib.ditto_guided_step_packed_rescale_opts(
+                    *head, at(self.o_partner) if mixed else None, prompt, *noise[:2], 0, noise[2], at(self.o_w), at(self.o_phi), *coef,
+                    a.B, a.G if mixed else 0, a.S, a.S_G if mixed else 0, a.max_N, a.S_T, a.max_T, *tail_rs))
+            return
         if self.multistep:
             hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
                 *head, prompt, self.q[self.cur].data_ptr(), None, at(self.o_coef), None, a.B, a.S, a.max_N, a.S_T, a.max_T,

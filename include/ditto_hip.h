@@ -653,6 +653,52 @@ int ditto_guided_step_packed_mixed_opts(ditto_model_t m, float* x2, const void* 
                                         const float* cz, int B, int G, int S, int S_G, int max_N, int S_T, int max_T,
                                         const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                                         ditto_stream_t stream, const ditto_call_opts* opts);
+/* ---- Guidance rescale (Lin et al. 2024, "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4) for packed guided
+ * sampling: at a strong scale the guided prediction e = u + w (c - u) has a much larger standard deviation than the conditional
+ * prediction c; e is scaled back so that its per-utterance standard deviation matches that of c, blended by phi.  The reference has no
+ * guided sampler: this is pinned by its own formula.  Per guided utterance b, over its GENERATED rows [cu[b] + P_b, cu[b+1]) and all d
+ * columns only (c, u fp32; e_i = fmaf(w_b, c_i - u_i, u_i), the update kernels' expression):
+ *     sigma_c, sigma_e   population standard deviations of c and e, mean and variance accumulated in fp64
+ *     r = sigma_c / sigma_e,   s = 1 + phi_b (r - 1) in fp64,   s32 = (float)s          phi_b clamped into [0, 1] on the device
+ *     coef_out[b] = coef_in[b] * s32                                                   one fp32 multiply
+ *   s32 = 1 and coef_out[b] a bit copy of coef_in[b] where phi_b == 0, the utterance is unguided (partner[b] < 0), sigma_e^2 <= 0 or r
+ *   is not finite; an unguided or phi_b == 0 utterance has none of its eps read.  Nothing is read outside the generated rows of the
+ *   rescaled utterances.  x' is linear in e, so the update with the rescaled prediction is the EXISTING update with coef_out in the
+ *   place of ce (strided update) or ke (2M update); the noise term cz z is not scaled.
+ *   Bits: the sums are cut into partials of 4096 16-byte quads of the utterance's own generated region (a constant of the library),
+ *   each in a fixed order, summed per utterance in an order that depends on its chunk count only — no atomics.  s32 of an utterance is a
+ *   function of its own generated rows, w_b and phi_b: not of its position, its neighbours, B, S, max_N or the grid.
+ * Layouts (those of the update entries): partner NULL — eps2 [2S, d], u at row offset S, G and S_G unused; partner device int32 [B] —
+ *   eps2 [S + S_G, d], cu [B + G + 1], u at the copy's rows, everything clamped as in ditto_guided_update_packed_mixed.  prompt_len NULL
+ *   or device int32 [B], clamped as in ditto_guided_update_packed_prompt.
+ * ditto_guidance_rescale_bytes: the scratch of B utterances whose longest generated region is at most max_N rows (host arithmetic; 0 on
+ *   a bad shape).  Layout, each part 256-byte aligned: [coef_out: B ditto_multistep_coef, or fp32 [B] at its start | scale fp32 [B] at
+ *   byte al256(32 B) | the partials, 4 doubles per chunk].  A larger scratch is used in full; max_N only sizes the grid.
+ * ditto_guidance_rescale_packed: the two launches alone over the caller's eps2.  Exactly one of coef_in (device fp32 [B], with w device
+ *   fp32 [B]; coef_out is fp32 [B]) and coefs (device ditto_multistep_coef [B], 16-byte aligned: w and ke inside; coef_out is a copy of
+ *   the structs with ke scaled) is given.  phi device fp32 [B]; scratch 256-byte aligned, >= ditto_guidance_rescale_bytes(B, max_N, d).
+ * ditto_guided_step_packed_rescale_opts: the forward, the rescale, then the existing update with ce s32 — chosen as the existing entries
+ *   choose it: partner NULL: ditto_guided_step_packed_opts with cfg 1 (tags NULL: the scalar `step`), its _tags, _prompt or
+ *   _tags_prompt form by tags / prompt_len; partner given: ditto_guided_step_packed_mixed_opts (tags needed with seeds).
+ * ditto_guided_step_packed_multistep_rescale_opts: ditto_guided_step_packed_multistep_opts with cfg 1 and device coefs [B], ke s32. */
+size_t ditto_guidance_rescale_bytes(int B, int max_N, int d);
+int ditto_guidance_rescale_packed(const float* eps2, const float* w, const float* phi, const float* coef_in,
+                                  const ditto_multistep_coef* coefs, const int32_t* cu, const int32_t* prompt_len, const int32_t* partner,
+                                  int B, int G, int S, int S_G, int max_N, int d, void* scratch, size_t scratch_bytes,
+                                  ditto_stream_t stream);
+int ditto_guided_step_packed_rescale_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                          const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
+                                          const int64_t* seeds, uint32_t step, const uint32_t* tags, const float* w, const float* phi,
+                                          const float* a, const float* ce, const float* cz, int B, int G, int S, int S_G, int max_N,
+                                          int S_T, int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
+                                          size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
+                                          const ditto_call_opts* opts);
+int ditto_guided_step_packed_multistep_rescale_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                                    const int32_t* cu_speech, const int32_t* cu_text, const int32_t* prompt_len, float* q,
+                                                    const ditto_multistep_coef* coefs, const float* phi, int B, int S, int max_N, int S_T,
+                                                    int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
+                                                    size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
+                                                    const ditto_call_opts* opts);
 /* Span-masked training over a packed batch with prompts (cu, prompt_len and their clamp as above; every buffer fp32 [S, d]).  z is
  *   either `noise`, a packed buffer whose prompt rows are not read, or Philox of (seeds[b], tag) at the generated-local quad index:
  *   exactly one of the two is given.
