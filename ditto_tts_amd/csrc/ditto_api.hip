@@ -1536,9 +1536,11 @@ static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const
                               bool per_utt, const float* w, const float* a, const float* ce_in, const float* cz, int B, int S, int max_N,
                               int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                               size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
-                              const int32_t* prompt_len = nullptr, bool prompted = false, const RescaleReq* rs = nullptr) {
+                              const int32_t* prompt_len = nullptr, bool prompted = false, const RescaleReq* rs = nullptr,
+                              const int32_t* suffix_len = nullptr, bool windowed = false) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
     if (prompted && !prompt_len) return fail(DITTO_ERR_ARG, "%s: null prompt_len (int32 [B])", who);
+    if (windowed && !suffix_len) return fail(DITTO_ERR_ARG, "%s: null suffix_len (int32 [B])", who);
     if (rs)   // guidance rescale: the statistics between the forward and the update, the update then reads ce[b] s_b from the scratch
         if (int rc = check_rescale(who, x2, w, rs->phi, ce_in, nullptr, cu_speech, nullptr, B, 0, S, 0, max_N, m->cfg.hidden_dim,
                                    rs->scratch, rs->scratch_bytes))
@@ -1562,7 +1564,10 @@ static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const
             HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
             ce = ra.coef_out;
         }
-        if (prompted)
+        if (windowed)
+            HIP_TRY(launch_guided_update_window(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, suffix_len,
+                                                B, S, max_N, m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
+        else if (prompted)
             HIP_TRY(launch_guided_update_prompt(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, B, S, max_N,
                                                 m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
         else if (per_utt)
@@ -1681,8 +1686,10 @@ static int guided_step_multistep(const char* who, ditto_model_t m, float* x2, co
                                  const int32_t* cu_text, const int32_t* prompt_len, float* q, const ditto_multistep_coef* step,
                                  const ditto_multistep_coef* coefs_in, const float* w, int B, int S, int max_N, int S_T, int max_T, int cfg,
                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
-                                 ditto_stream_t stream, const ditto_call_opts* opts, const RescaleReq* rs = nullptr) {
+                                 ditto_stream_t stream, const ditto_call_opts* opts, const RescaleReq* rs = nullptr,
+                                 const int32_t* suffix_len = nullptr, bool windowed = false) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    if (windowed && !suffix_len) return fail(DITTO_ERR_ARG, "%s: null suffix_len (int32 [B])", who);
     if (int rc = check_multistep(who, x2, x2, q, step, coefs_in, w, cu_speech, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
     if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
     if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
@@ -1706,8 +1713,12 @@ static int guided_step_multistep(const char* who, ditto_model_t m, float* x2, co
             HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
             coefs = (const ditto_multistep_coef*)rs->scratch;
         }
-        HIP_TRY(launch_multistep_update_packed(x2, eps, q, step, coefs, w, cu_speech, prompt_len, B, S, max_N, m->cfg.hidden_dim, cfg != 0,
-                                               (hipStream_t)stream));
+        if (windowed)
+            HIP_TRY(launch_multistep_update_window(x2, eps, q, step, coefs, w, cu_speech, prompt_len, suffix_len, B, S, max_N,
+                                                   m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
+        else
+            HIP_TRY(launch_multistep_update_packed(x2, eps, q, step, coefs, w, cu_speech, prompt_len, B, S, max_N, m->cfg.hidden_dim,
+                                                   cfg != 0, (hipStream_t)stream));
         return DITTO_OK;
     });
 }
@@ -1872,6 +1883,112 @@ int ditto_span_mse_packed(const float* eps, const float* noise, const int64_t* s
                     span_mse_partials(B, max_N, d) * sizeof(float));
     HIP_TRY(launch_span_mse_packed(eps, noise, seeds, tag, cu, prompt_len, (double)n_elems, grad_eps, loss, (float*)workspace, B, S, max_N,
                                    d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+// ---- speech infilling: the update and step entries over the window [cu[b] + P_b, cu[b+1] - Q_b) (guided_window.hip, span_window.hip) ----
+static int guided_update_window(const char* who, float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
+                                const uint32_t* tags, bool per_utt, const float* w, const float* a, const float* ce, const float* cz,
+                                const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d,
+                                int cfg, ditto_stream_t stream) {
+    if (!cu || !suffix_len) return fail(DITTO_ERR_ARG, "%s: null cu / suffix_len", who);
+    if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
+    if (int rc = check_guided_update(who, x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_guided_update_window(x2, eps2, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu, prompt_len, suffix_len, B, S, max_N,
+                                        d, cfg != 0, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_update_packed_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
+                                      const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                      const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg,
+                                      ditto_stream_t stream) {
+    return guided_update_window("ditto_guided_update_packed_window", x2, eps2, noise, seeds, step, nullptr, false, w, a, ce, cz, cu,
+                                prompt_len, suffix_len, B, S, max_N, d, cfg, stream);
+}
+
+int ditto_guided_update_packed_tags_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                           const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                           const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg,
+                                           ditto_stream_t stream) {
+    return guided_update_window("ditto_guided_update_packed_tags_window", x2, eps2, noise, seeds, 0, tags, true, w, a, ce, cz, cu,
+                                prompt_len, suffix_len, B, S, max_N, d, cfg, stream);
+}
+
+int ditto_guided_step_packed_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                         const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len,
+                                         const float* noise, const int64_t* seeds, uint32_t step, const float* w, const float* a,
+                                         const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
+                                         const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                         ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_packed("ditto_guided_step_packed_window_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false,
+                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
+                              prompt_len, false, nullptr, suffix_len, true);
+}
+
+int ditto_guided_step_packed_tags_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                              const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len,
+                                              const float* noise, const int64_t* seeds, const uint32_t* tags, const float* w,
+                                              const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T,
+                                              int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
+                                              size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_packed("ditto_guided_step_packed_tags_window_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true,
+                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
+                              prompt_len, false, nullptr, suffix_len, true);
+}
+
+int ditto_multistep_update_window(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
+                                  const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, const int32_t* prompt_len,
+                                  const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_multistep_update_window: null suffix_len");
+    if (int rc = check_multistep("ditto_multistep_update_window", x2, eps2, q, step, coefs, w, cu, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed("ditto_multistep_update_window", B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_multistep_update_window(x2, eps2, q, step, coefs, w, cu, prompt_len, suffix_len, B, S, max_N, d, cfg != 0,
+                                           (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_step_packed_multistep_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                                   const int32_t* cu_speech, const int32_t* cu_text, const int32_t* prompt_len,
+                                                   const int32_t* suffix_len, float* q, const ditto_multistep_coef* step,
+                                                   const ditto_multistep_coef* coefs, const float* w, int B, int S, int max_N, int S_T,
+                                                   int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
+                                                   size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    return guided_step_multistep("ditto_guided_step_packed_multistep_window_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q, step,
+                                 coefs, w, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
+                                 nullptr, suffix_len, true);
+}
+
+static int check_span_window(const char* who, const void* in, const float* noise, const int64_t* seeds, const int32_t* cu,
+                             const int32_t* suffix_len, const void* out, int B, int S, int max_N, int d) {
+    if (!in || !out || !cu || !suffix_len) return fail(DITTO_ERR_ARG, "%s: null pointer", who);
+    if (!noise == !seeds) return fail(DITTO_ERR_ARG, "%s: exactly one of noise (a packed buffer) and seeds (Philox) is needed", who);
+    if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
+    return check_packed(who, B, S, max_N, S, max_N);
+}
+
+int ditto_span_noise_window(const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca, const float* cs,
+                            const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, float* x_in, int B, int S,
+                            int max_N, int d, ditto_stream_t stream) {
+    if (!ca || !cs) return fail(DITTO_ERR_ARG, "ditto_span_noise_window: null ca / cs");
+    if (int rc = check_span_window("ditto_span_noise_window", x0, noise, seeds, cu, suffix_len, x_in, B, S, max_N, d)) return rc;
+    HIP_TRY(launch_span_noise_window(x0, noise, seeds, tag, ca, cs, cu, prompt_len, suffix_len, x_in, B, S, max_N, d,
+                                     (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
+                          const int32_t* prompt_len, const int32_t* suffix_len, size_t n_elems, float* grad_eps, float* loss,
+                          void* workspace, size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream) {
+    if (!loss || !workspace) return fail(DITTO_ERR_ARG, "ditto_span_mse_window: null loss / workspace");
+    if (int rc = check_span_window("ditto_span_mse_window", eps, noise, seeds, cu, suffix_len, grad_eps, B, S, max_N, d)) return rc;
+    if (n_elems == 0 || n_elems > (size_t)S * d) return fail(DITTO_ERR_SHAPE, "ditto_span_mse_window: n_elems must lie in [1, S d]");
+    if ((uintptr_t)workspace % 4 || workspace_bytes < span_mse_partials(B, max_N, d) * sizeof(float))
+        return fail(DITTO_ERR_SIZE, "ditto_span_mse_window: the workspace needs %zu bytes (B x min(1024, ceil(max_N d / 1024)) floats)",
+                    span_mse_partials(B, max_N, d) * sizeof(float));
+    HIP_TRY(launch_span_mse_window(eps, noise, seeds, tag, cu, prompt_len, suffix_len, (double)n_elems, grad_eps, loss, (float*)workspace,
+                                   B, S, max_N, d, (hipStream_t)stream));
     return DITTO_OK;
 }
 

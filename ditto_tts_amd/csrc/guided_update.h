@@ -50,6 +50,23 @@ __device__ __forceinline__ GuidedSpan generated_span(const int32_t* cu, const in
     return guided_span(cu, b, S, d);
 }
 
+// prompt_span plus a clean SUFFIX (speech infilling): the last suffix_len[b] rows of the utterance are clean latents too, and the rows
+// in between, [cu[b] + P_b, cu[b+1] - Q_b), are the generated window: g4 quads from quad p4 on.  P_b clamped into [0, n_b - 1] like
+// prompt_span's (prompt_len NULL: 0), Q_b into [0, n_b - 1 - P_b]: at least one row is generated, and a bad value gives wrong rows,
+// never an access outside the utterance's own.  Q_b = 0 is prompt_span: p4 + g4 == n4 (guided_window.hip, span_window.hip)
+struct WindowSpan { size_t base4, n4, p4, g4; };
+__device__ __forceinline__ WindowSpan window_span(const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int b, int S,
+                                                  int d) {
+    int r0 = cu[b];
+    r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
+    const int n = cu[b + 1] - r0, nb = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);
+    int p = prompt_len ? prompt_len[b] : 0;
+    p = p < 0 ? 0 : (p > nb - 1 ? nb - 1 : p);
+    int q = suffix_len[b];
+    q = q < 0 ? 0 : (q > nb - 1 - p ? nb - 1 - p : q);
+    return {(size_t)r0 * d / 4, (size_t)nb * d / 4, (size_t)p * d / 4, (size_t)(nb - p - q) * d / 4};
+}
+
 // utterance b of a step in which G of the B utterances are guided (guided_mixed.hip): its generated rows and, with a partner, the
 // same rows of its unconditional copy behind row S.  Clamps: guided_span's and prompt_span's; the partner into [-1, G - 1]; the copy's
 // span has b's own length n_b, its first row clamped into [S, S + S_G - n_b] (no copy at all when n_b > S_G: g = -1).  The offset

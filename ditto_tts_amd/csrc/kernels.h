@@ -304,6 +304,25 @@ hipError_t launch_span_noise_packed(const float* x0, const float* noise, const i
 hipError_t launch_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
                                   const int32_t* prompt_len, double n_elems, float* grad, float* loss, float* partial, int B, int S,
                                   int max_N, int d, hipStream_t s);
+hipError_t launch_span_mse_finish(const float* partial, size_t n_partial, float inv_n, float* loss, hipStream_t s);
+// ---------------- guided_window.hip, span_window.hip ----------------
+// speech infilling: the prompt / multistep / span launches over the window [cu[b] + P_b, cu[b+1] - Q_b) — suffix_len device int32 [B]
+// (required), Q_b clamped into [0, n_b - 1 - P_b]; prompt_len may be null (P = 0).  The context rows on both sides are neither read
+// nor written by the updates; the span kernels copy x0 / write a zero gradient there.  suffix_len all 0: the counterpart's bits
+hipError_t launch_guided_update_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
+                                       const unsigned* tags, bool per_utt, const float* w, const float* a, const float* ce,
+                                       const float* cz, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
+                                       int S, int max_N, int d, bool cfg, hipStream_t s);
+hipError_t launch_multistep_update_window(float* x2, const float* eps2, float* q, const ::ditto_multistep_coef* step,
+                                          const ::ditto_multistep_coef* coefs, const float* w, const int32_t* cu,
+                                          const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, bool cfg,
+                                          hipStream_t s);
+hipError_t launch_span_noise_window(const float* x0, const float* noise, const int64_t* seeds, unsigned tag, const float* ca,
+                                    const float* cs, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len,
+                                    float* x_in, int B, int S, int max_N, int d, hipStream_t s);
+hipError_t launch_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
+                                  const int32_t* prompt_len, const int32_t* suffix_len, double n_elems, float* grad, float* loss,
+                                  float* partial, int B, int S, int max_N, int d, hipStream_t s);
 // ---------------- guided_rescale.hip ----------------
 // guidance rescale (Lin et al. 2024, section 3.4): coef_out[b] = coef_in[b] * s32_b with s_b = 1 + phi_b (sigma_c / sigma_e - 1) over
 // utterance b's generated rows of eps2 (e = fmaf(w, c - u, u), sums in fp64), 1 where b is unguided, phi_b == 0 or sigma_e == 0.

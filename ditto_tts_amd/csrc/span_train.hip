@@ -97,6 +97,12 @@ __global__ __launch_bounds__(256) void span_mse_finish_kernel(const float* __res
 
 size_t span_mse_partials(int B, int max_N, int d) { return (size_t)B * guided_grid(max_N, d, B).x; }
 
+// span_mse_finish_kernel for the other files' partials (span_window.hip): a kernel is launched from the file that defines it
+hipError_t launch_span_mse_finish(const float* partial, size_t n_partial, float inv_n, float* loss, hipStream_t s) {
+    hipLaunchKernelGGL(span_mse_finish_kernel, dim3(1), dim3(256), 0, s, partial, n_partial, inv_n, loss);
+    return hipGetLastError();
+}
+
 hipError_t launch_span_noise_packed(const float* x0, const float* noise, const int64_t* seeds, unsigned tag, const float* ca,
                                     const float* cs, const int32_t* cu, const int32_t* prompt_len, float* x_in, int B, int S, int max_N,
                                     int d, hipStream_t s) {

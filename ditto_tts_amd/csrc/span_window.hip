@@ -1,0 +1,115 @@
+// span_window.hip — span-masked training with the span ANYWHERE in the utterance (gfx950): infilling objectives mask a window and keep
+// clean context on both sides.  The two kernels of span_train.hip with the window p4 <= i < p4 + g4 in the place of i >= p4 — the
+// same walk over the whole utterance, the same lane-to-quad assignment, the same partial layout and the same reduction tree, so that
+// suffix_len all 0 gives span_train.hip's bits, the loss included.  Kernels of their own: span_train.hip keeps its machine code.
+#include "common.h"
+#include "guided_update.h"
+#include "kernels.h"
+#include "philox.h"
+
+namespace ditto {
+
+// x_in = x0 on both context regions (a bit copy), fmaf(ca[b], x0, cs[b] z) on the window.  z: the packed buffer `noise` [S, d] (its
+// context rows are never read), or SEEDED Philox of (seeds[b], tag) at the window-local quad index i - p4 — ditto_noise_normal's
+// numbers for an utterance of G_b rows.
+template <bool SEEDED>
+__global__ __launch_bounds__(256) void span_noise_window_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                const int64_t* __restrict__ seeds, unsigned tag,
+                                                                const float* __restrict__ ca, const float* __restrict__ cs,
+                                                                const int32_t* __restrict__ cu, const int32_t* __restrict__ prompt_len,
+                                                                const int32_t* __restrict__ suffix_len, float* __restrict__ x_in, int S,
+                                                                int d) {
+    const int b = blockIdx.y;
+    const WindowSpan r = window_span(cu, prompt_len, suffix_len, b, S, d);
+    const size_t end4 = r.p4 + r.g4;
+    const float a = ca[b], s = cs[b];
+    const unsigned long long seed = SEEDED ? (unsigned long long)seeds[b] : 0ull;
+    const f32x4* xp = reinterpret_cast<const f32x4*>(x0) + r.base4;
+    const f32x4* zp = reinterpret_cast<const f32x4*>(noise) + r.base4;
+    f32x4* op = reinterpret_cast<f32x4*>(x_in) + r.base4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < r.n4; i += stride) {
+        f32x4 o = xp[i];
+        if (i >= r.p4 && i < end4) {
+            const f32x4 z = SEEDED ? normal4(seed, tag, i - r.p4) : zp[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = fmaf(a, o[e], s * z[e]);
+        }
+        op[i] = o;
+    }
+}
+
+// grad_eps = scale2 (eps - z) on the window, exactly 0 on both context regions (eps is not read there); partial[b gridDim.x +
+// blockIdx.x] = this workgroup's sum of (eps - z)^2, lanes in span_mse_packed_kernel's tree
+template <bool SEEDED>
+__global__ __launch_bounds__(256) void span_mse_window_kernel(const float* __restrict__ eps, const float* __restrict__ noise,
+                                                              const int64_t* __restrict__ seeds, unsigned tag,
+                                                              const int32_t* __restrict__ cu, const int32_t* __restrict__ prompt_len,
+                                                              const int32_t* __restrict__ suffix_len, float scale2,
+                                                              float* __restrict__ grad, float* __restrict__ partial, int S, int d) {
+    __shared__ float red[256];
+    const int b = blockIdx.y;
+    const WindowSpan r = window_span(cu, prompt_len, suffix_len, b, S, d);
+    const size_t end4 = r.p4 + r.g4;
+    const unsigned long long seed = SEEDED ? (unsigned long long)seeds[b] : 0ull;
+    const f32x4* ep = reinterpret_cast<const f32x4*>(eps) + r.base4;
+    const f32x4* zp = reinterpret_cast<const f32x4*>(noise) + r.base4;
+    f32x4* gp = reinterpret_cast<f32x4*>(grad) + r.base4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    float acc = 0.f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < r.n4; i += stride) {
+        f32x4 g = {0.f, 0.f, 0.f, 0.f};
+        if (i >= r.p4 && i < end4) {
+#pragma clang fp contract(off)      // eps - z must not fuse with the Box-Muller product r cos: the seeded mode gives the buffer mode's bits
+            const f32x4 e = ep[i];
+            const f32x4 z = SEEDED ? normal4(seed, tag, i - r.p4) : zp[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float df = e[k] - z[k];
+                acc = fmaf(df, df, acc);
+                g[k] = scale2 * df;
+            }
+        }
+        gp[i] = g;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = red[0];
+}
+
+hipError_t launch_span_noise_window(const float* x0, const float* noise, const int64_t* seeds, unsigned tag, const float* ca,
+                                    const float* cs, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len,
+                                    float* x_in, int B, int S, int max_N, int d, hipStream_t s) {
+    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !suffix_len || (!noise == !seeds)) return hipErrorInvalidValue;
+    if (seeds)
+        hipLaunchKernelGGL(span_noise_window_kernel<true>, guided_grid(max_N, d, B), dim3(256), 0, s, x0, noise, seeds, tag, ca, cs, cu,
+                           prompt_len, suffix_len, x_in, S, d);
+    else
+        hipLaunchKernelGGL(span_noise_window_kernel<false>, guided_grid(max_N, d, B), dim3(256), 0, s, x0, noise, seeds, tag, ca, cs, cu,
+                           prompt_len, suffix_len, x_in, S, d);
+    return hipGetLastError();
+}
+
+hipError_t launch_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
+                                  const int32_t* prompt_len, const int32_t* suffix_len, double n_elems, float* grad, float* loss,
+                                  float* partial, int B, int S, int max_N, int d, hipStream_t s) {
+    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !suffix_len || (!noise == !seeds) || !(n_elems >= 1.0))
+        return hipErrorInvalidValue;
+    const float scale2 = (float)(2.0 / n_elems), inv_n = (float)(1.0 / n_elems);
+    const dim3 grid = guided_grid(max_N, d, B);
+    if (seeds)
+        hipLaunchKernelGGL(span_mse_window_kernel<true>, grid, dim3(256), 0, s, eps, noise, seeds, tag, cu, prompt_len, suffix_len,
+                           scale2, grad, partial, S, d);
+    else
+        hipLaunchKernelGGL(span_mse_window_kernel<false>, grid, dim3(256), 0, s, eps, noise, seeds, tag, cu, prompt_len, suffix_len,
+                           scale2, grad, partial, S, d);
+    if (hipError_t e = hipGetLastError()) return e;
+    return launch_span_mse_finish(partial, span_mse_partials(B, max_N, d), inv_n, loss, s);   // (span_train.hip)
+}
+
+}  // namespace ditto

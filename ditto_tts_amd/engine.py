@@ -279,7 +279,8 @@ class DenoiseEngine:
                             cz: torch.Tensor, w: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             seeds: Optional[torch.Tensor] = None, step: int = 0, cu_seqlens=None, max_seqlen: Optional[int] = None,
                             offsets=None, opts: Optional[hip.CallOpts] = None, prompt_len: Optional[torch.Tensor] = None,
-                            phi: Optional[torch.Tensor] = None, rescale_scratch: Optional[torch.Tensor] = None):
+                            phi: Optional[torch.Tensor] = None, rescale_scratch: Optional[torch.Tensor] = None,
+                            suffix_len: Optional[torch.Tensor] = None):
         """guided_step_ over a packed batch, IN PLACE on x2 fp32 [2S, d] ([x; x], w given) or [S, d]
         (ditto_guided_step_packed_opts).  `offsets`: guided_offsets_packed(...) built once per sampling call (else built here from
         `cu_seqlens`); `cond`: prepare_text_packed over [text; null] (2B utterances) or text.  noise: packed fp32 [S, d].
@@ -287,7 +288,10 @@ class DenoiseEngine:
         utterance b are a speech prompt the update leaves alone (ditto_guided_step_packed_prompt_opts).
         `phi` (device fp32 [B] in [0, 1], with w): guidance rescale — ditto_guided_step_packed_rescale_opts computes each utterance's
         s32 from this step's eps and the same update runs with ce s32; `rescale_scratch`: rescale_scratch(B, max_N) built once per
-        sampling call (else taken here)."""
+        sampling call (else taken here).
+        `suffix_len` (device int32 [B], validated by the caller: varlen.validate_suffix_lengths): speech infilling — the last
+        suffix_len[b] rows of utterance b are clean context too and the update runs over the window in between
+        (ditto_guided_step_packed_window_opts; prompt_len may be None).  Not together with phi."""
         sd, noise = self._guided_args("guided_step_packed_", x2, 2, B, a, ce, cz, w, noise, seeds)
         cfg = w is not None
         nb = 2 * B if cfg else B
@@ -307,6 +311,11 @@ class DenoiseEngine:
         if prompt_len is not None and not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous()
                                            and prompt_len.shape == (B,)):
             raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        if suffix_len is not None and not (suffix_len.is_cuda and suffix_len.dtype == torch.int32 and suffix_len.is_contiguous()
+                                           and suffix_len.shape == (B,)):
+            raise ValueError(f"suffix_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        if suffix_len is not None and phi is not None:
+            raise NotImplementedError("guidance rescale has no windowed form (suffix_len with phi)")
         if phi is not None:
             if not cfg:
                 raise ValueError("guidance rescale needs the guidance scales w")
@@ -317,7 +326,9 @@ class DenoiseEngine:
                 ce.data_ptr(), cz.data_ptr(), B, 0, S, 0, max_N, cond.T, cond.max_len, c.data_ptr(), s.data_ptr(), ws.data_ptr(),
                 ws.numel(), rs.data_ptr(), rs.numel(), _stream(), None if opts is None else C.byref(opts)))
             return x2
-        if prompt_len is not None:
+        if suffix_len is not None:
+            entry, head = self.lib.ditto_guided_step_packed_window_opts, (_ptr(prompt_len), suffix_len.data_ptr())
+        elif prompt_len is not None:
             entry, head = self.lib.ditto_guided_step_packed_prompt_opts, (prompt_len.data_ptr(),)
         else:
             entry, head = self.lib.ditto_guided_step_packed_opts, ()
@@ -331,14 +342,16 @@ class DenoiseEngine:
                                       coef: Optional[hip.MultistepCoef], w: Optional[torch.Tensor] = None, cu_seqlens=None,
                                       max_seqlen: Optional[int] = None, offsets=None, opts: Optional[hip.CallOpts] = None,
                                       prompt_len: Optional[torch.Tensor] = None, coefs: Optional[torch.Tensor] = None,
-                                      phi: Optional[torch.Tensor] = None, rescale_scratch: Optional[torch.Tensor] = None):
+                                      phi: Optional[torch.Tensor] = None, rescale_scratch: Optional[torch.Tensor] = None,
+                                      suffix_len: Optional[torch.Tensor] = None):
         """guided_step_packed_ with the update of the second-order multistep solver (ditto_guided_step_packed_multistep_opts), IN
         PLACE on x2 and on the history `q` fp32 [S, d]: the previous step's x0 prediction, read only when coef.use_prev and
         rewritten by every step.  `coef`: the step every utterance stands at (sampler.multistep_schedule; its w is ignored, the
         guidance scales are `w` fp32 [B]).  x2, cond, t, offsets, opts, prompt_len: as guided_step_packed_.
         `coefs` (instead of coef and w: device fp32 [B, 8], one ditto_multistep_coef per utterance, its guidance scale inside) with
         `phi` (device fp32 [B]): guidance rescale under guidance — ditto_guided_step_packed_multistep_rescale_opts, the per-utterance
-        update with ke s32; `rescale_scratch` as in guided_step_packed_."""
+        update with ke s32; `rescale_scratch` as in guided_step_packed_.
+        `suffix_len`: as in guided_step_packed_ (ditto_guided_step_packed_multistep_window_opts; the context rows of q are untouched)."""
         if (coefs is None) != (phi is None) or (coefs is None) == (coef is None):
             raise ValueError("guided_step_packed_multistep_: coef (with w), or coefs with phi")
         self._guided_args("guided_step_packed_multistep_", x2, 2, B, None, None, None, w, None, None)
@@ -362,6 +375,11 @@ class DenoiseEngine:
         if prompt_len is not None and not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous()
                                            and prompt_len.shape == (B,)):
             raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        if suffix_len is not None and not (suffix_len.is_cuda and suffix_len.dtype == torch.int32 and suffix_len.is_contiguous()
+                                           and suffix_len.shape == (B,)):
+            raise ValueError(f"suffix_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        if suffix_len is not None and phi is not None:
+            raise NotImplementedError("guidance rescale has no windowed form (suffix_len with phi)")
         tt = self._t64(t, nb)
         ws = self.workspace_packed(nb, rows, cond.T)
         c, s = self.rope_tables(max_N)
@@ -371,6 +389,12 @@ class DenoiseEngine:
                 self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(),
                 _ptr(prompt_len), q.data_ptr(), coefs.data_ptr(), phi.data_ptr(), B, S, max_N, cond.T, cond.max_len, c.data_ptr(),
                 s.data_ptr(), ws.data_ptr(), ws.numel(), rs.data_ptr(), rs.numel(), _stream(), None if opts is None else C.byref(opts)))
+            return x2
+        if suffix_len is not None:
+            hip.check(self.lib.ditto_guided_step_packed_multistep_window_opts(
+                self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(),
+                _ptr(prompt_len), suffix_len.data_ptr(), q.data_ptr(), C.byref(coef), None, _ptr(w), B, S, max_N, cond.T, cond.max_len,
+                int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
             return x2
         hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
             self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
@@ -413,10 +437,11 @@ class DenoiseEngine:
         return out, scratch[o_scale:o_scale + 4 * B].view(torch.float32)
 
     # ------------------------------------------------------------------ span-masked training (csrc/span_train.hip)
-    def _span_args(self, who, buf, cu_seqlens, prompt_lengths, seeds, noise):
+    def _span_args(self, who, buf, cu_seqlens, prompt_lengths, seeds, noise, suffix_lengths=None):
         """the checks of span_noise_packed / span_mse_packed: (device offsets, device prompt lengths, B, max_N, generated rows,
-        seeds int64 [B] or None, noise fp32 [S, d] or None)"""
-        from .varlen import validate_prompt_lengths
+        seeds int64 [B] or None, noise fp32 [S, d] or None, device suffix lengths or None).  With `suffix_lengths` the prompt lengths
+        may be None (device None: P = 0)."""
+        from .varlen import validate_prompt_lengths, validate_suffix_lengths
         if not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and buf.dim() == 2 and buf.shape[1] % 64 == 0):
             raise ValueError(f"{who} needs a contiguous fp32 CUDA tensor [S, d] with d % 64 == 0")
         if (seeds is None) == (noise is None):
@@ -424,34 +449,51 @@ class DenoiseEngine:
         S = int(buf.shape[0])
         B = len(cu_seqlens) - 1
         cu, max_N = self._cu(cu_seqlens, B, S, None, "cu_seqlens")
-        pl = validate_prompt_lengths(prompt_lengths, cu)
+        ql = None if suffix_lengths is None else validate_suffix_lengths(suffix_lengths, cu, prompt_lengths)
+        pl = None if (prompt_lengths is None and ql is not None) else validate_prompt_lengths(prompt_lengths, cu)
         if noise is not None:
             noise = self._f32(noise, "noise")
             if noise.shape != buf.shape:
                 raise ValueError(f"noise must have shape {list(buf.shape)}")
         sd = self._t64(seeds, B) if seeds is not None else None
-        return cu.to(self.device), pl.to(self.device), B, max_N, S - int(pl.sum()), sd, noise
+        gen = S - (0 if pl is None else int(pl.sum())) - (0 if ql is None else int(ql.sum()))
+        return (cu.to(self.device), None if pl is None else pl.to(self.device), B, max_N, gen, sd, noise,
+                None if ql is None else ql.to(self.device))
 
     def span_noise_packed(self, x0: torch.Tensor, cu_seqlens, prompt_lengths, ca: torch.Tensor, cs: torch.Tensor, seeds=None,
-                          tag: int = 0, noise=None) -> torch.Tensor:
-        """x_in fp32 [S, d]: x0 on each utterance's prompt rows, ca[b] x0 + cs[b] z on its generated rows (ditto_span_noise_packed)"""
-        cud, pld, B, max_N, _, sd, noise = self._span_args("span_noise_packed", x0, cu_seqlens, prompt_lengths, seeds, noise)
+                          tag: int = 0, noise=None, suffix_lengths=None) -> torch.Tensor:
+        """x_in fp32 [S, d]: x0 on each utterance's prompt rows, ca[b] x0 + cs[b] z on its generated rows (ditto_span_noise_packed).
+        `suffix_lengths`: the last Q_b rows stay clean too (ditto_span_noise_window; prompt_lengths may then be None)."""
+        cud, pld, B, max_N, _, sd, noise, qld = self._span_args("span_noise_packed", x0, cu_seqlens, prompt_lengths, seeds, noise,
+                                                                suffix_lengths)
         for name, v in (("ca", ca), ("cs", cs)):
             if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
                 raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
         out = torch.empty_like(x0)
+        if qld is not None:
+            hip.check(self.lib.ditto_span_noise_window(x0.data_ptr(), _ptr(noise), _ptr(sd), int(tag) & 0xFFFFFFFF, ca.data_ptr(),
+                                                       cs.data_ptr(), cud.data_ptr(), _ptr(pld), qld.data_ptr(), out.data_ptr(), B,
+                                                       x0.shape[0], max_N, x0.shape[1], _stream()))
+            return out
         hip.check(self.lib.ditto_span_noise_packed(x0.data_ptr(), _ptr(noise), _ptr(sd), int(tag) & 0xFFFFFFFF, ca.data_ptr(),
                                                    cs.data_ptr(), cud.data_ptr(), pld.data_ptr(), out.data_ptr(), B, x0.shape[0], max_N,
                                                    x0.shape[1], _stream()))
         return out
 
-    def span_mse_packed(self, eps: torch.Tensor, cu_seqlens, prompt_lengths, seeds=None, tag: int = 0, noise=None):
-        """(loss fp32 [], grad_eps fp32 [S, d]) of the MSE over the generated rows (ditto_span_mse_packed)"""
-        cud, pld, B, max_N, gen_rows, sd, noise = self._span_args("span_mse_packed", eps, cu_seqlens, prompt_lengths, seeds, noise)
+    def span_mse_packed(self, eps: torch.Tensor, cu_seqlens, prompt_lengths, seeds=None, tag: int = 0, noise=None, suffix_lengths=None):
+        """(loss fp32 [], grad_eps fp32 [S, d]) of the MSE over the generated rows (ditto_span_mse_packed; with `suffix_lengths`
+        ditto_span_mse_window: the rows between the two contexts, normalised by d x their number)"""
+        cud, pld, B, max_N, gen_rows, sd, noise, qld = self._span_args("span_mse_packed", eps, cu_seqlens, prompt_lengths, seeds, noise,
+                                                                       suffix_lengths)
         S, d = int(eps.shape[0]), int(eps.shape[1])
         grad = torch.empty_like(eps)
         loss = torch.empty((), dtype=torch.float32, device=eps.device)
         part = torch.empty(B * min(1024, (max_N * d // 4 + 255) // 256), dtype=torch.float32, device=eps.device)
+        if qld is not None:
+            hip.check(self.lib.ditto_span_mse_window(eps.data_ptr(), _ptr(noise), _ptr(sd), int(tag) & 0xFFFFFFFF, cud.data_ptr(),
+                                                     _ptr(pld), qld.data_ptr(), gen_rows * d, grad.data_ptr(), loss.data_ptr(),
+                                                     part.data_ptr(), part.numel() * 4, B, S, max_N, d, _stream()))
+            return loss, grad
         hip.check(self.lib.ditto_span_mse_packed(eps.data_ptr(), _ptr(noise), _ptr(sd), int(tag) & 0xFFFFFFFF, cud.data_ptr(),
                                                  pld.data_ptr(), gen_rows * d, grad.data_ptr(), loss.data_ptr(), part.data_ptr(),
                                                  part.numel() * 4, B, S, max_N, d, _stream()))

@@ -241,6 +241,18 @@ SYMBOLS = {
                                                                                     C.POINTER(CallOpts)]),
     "ditto_span_noise_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ditto_span_mse_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    # speech infilling: the prompt / multistep / span entries over a window, one more pointer (suffix_len int32 [B]) behind prompt_len
+    "ditto_guided_update_packed_window": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                               _vp]),
+    "ditto_guided_update_packed_tags_window": (_i, [_vp] * 12 + [_i] * 5 + [_vp]),
+    "ditto_guided_step_packed_window_opts": (_i, [_vp] * 10 + [C.c_uint32] + [_vp] * 4 + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp,
+                                                                                                 C.POINTER(CallOpts)]),
+    "ditto_guided_step_packed_tags_window_opts": (_i, [_vp] * 15 + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_multistep_update_window": (_i, [_vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_guided_step_packed_multistep_window_opts": (_i, [_vp] * 9 + [C.POINTER(MultistepCoef), _vp, _vp] + [_i] * 6
+                                                       + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_span_noise_window": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ditto_span_mse_window": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),
     "ditto_regroup_cond_layout": (_i, [C.POINTER(Config), _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),

@@ -212,9 +212,9 @@ class _SpanLossFn(torch.autograd.Function):
     """DiTTO.span_loss_packed: the loss and its gradient with respect to eps in one launch of ditto_span_mse_packed"""
 
     @staticmethod
-    def forward(ctx, eps, eng, cu_seqlens, prompt_lengths, seeds, tag, noise):
+    def forward(ctx, eps, eng, cu_seqlens, prompt_lengths, seeds, tag, noise, suffix_lengths=None):
         loss, grad = eng.span_mse_packed(eps.detach().float().contiguous(), cu_seqlens, prompt_lengths, seeds=seeds, tag=tag,
-                                         noise=noise)
+                                         noise=noise, suffix_lengths=suffix_lengths)
         ctx.save_for_backward(grad)
         ctx.eps_dtype = eps.dtype
         return loss
@@ -222,7 +222,7 @@ class _SpanLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return (grad * g).to(ctx.eps_dtype), None, None, None, None, None, None
+        return (grad * g).to(ctx.eps_dtype), None, None, None, None, None, None, None
 
 
 class DiTTO(nn.Module):
@@ -465,28 +465,34 @@ class DiTTO(nn.Module):
         out = torch.zeros(B * N, d, dtype=eps_p.dtype, device=dev).index_copy(0, rows, eps_p)
         return out.reshape(B, N, d)
 
-    def span_noise_packed(self, x0, cu_seqlens, prompt_lengths, t, *, seeds=None, tag=0, noise=None):
+    def span_noise_packed(self, x0, cu_seqlens, prompt_lengths, t, *, seeds=None, tag=0, noise=None, suffix_lengths=None):
         """The forward diffusion of a packed batch with SPEECH PROMPTS (span-masked training): x0 [S, d] clean latents, utterance b
         in rows [cu_seqlens[b], cu_seqlens[b+1]); its first prompt_lengths[b] rows (0 <= P_b < N_b) stay clean — bit copies — and
         the rest become x_in = ca[b] x0 + cs[b] z.  (ca, cs) is the pair q_sample uses for t[b], bug-for-bug: sqrt(c) and
         sqrt(1 - c) with c read from the same mis-named buffer.  z: `noise` (packed [S, d]; its prompt rows are ignored), or
         Philox of (`seeds`[b], `tag`) at the index local to the generated rows — span_loss_packed regenerates it from the same
         (seeds, tag), so it never exists in memory.  One kernel (csrc/span_train.hip).  Returns fp32 [S, d].
+        `suffix_lengths` (list / tuple / int tensor [B], Q_b >= 0, P_b + Q_b <= N_b - 1): the span ANYWHERE — the last Q_b rows stay
+        clean as well and the window in between is noised, the Philox index local to it (infilling objectives;
+        csrc/span_window.hip).  `prompt_lengths` may then be None (P = 0).  None: the call as it was.
         The padded collate (train_forward) has no prompts: pack the batch first."""
         _require_cuda(x0, "x0")
         eng = self.engine(x0.device)
         c = self.alphas_cumprod.to(x0.device).float()[t.to(x0.device).long()]
         return eng.span_noise_packed(x0.detach().float().contiguous(), cu_seqlens, prompt_lengths, c.sqrt().contiguous(),
-                                     (1.0 - c).sqrt().contiguous(), seeds=seeds, tag=tag, noise=noise)
+                                     (1.0 - c).sqrt().contiguous(), seeds=seeds, tag=tag, noise=noise,
+                                     suffix_lengths=suffix_lengths)
 
-    def span_loss_packed(self, eps, cu_seqlens, prompt_lengths, *, seeds=None, tag=0, noise=None):
+    def span_loss_packed(self, eps, cu_seqlens, prompt_lengths, *, seeds=None, tag=0, noise=None, suffix_lengths=None):
         """The span-masked MSE of a packed batch with speech prompts: mean over the GENERATED rows' elements of (eps - z)^2, z as in
         span_noise_packed (the same `noise`, or the same `seeds` and `tag`).  A scalar attached to autograd: backward() hands
         grad_output * (2 / n)(eps - z) — exactly 0 on the prompt rows, whatever eps holds there — to eps's producer
         (train_forward_packed).  Loss and gradient come from one kernel that reads eps once; the reduction is ordered, so the same
-        call twice gives the same bits."""
+        call twice gives the same bits.
+        `suffix_lengths`: as in span_noise_packed — the mean runs over the window's d x sum of G_b elements and the gradient is
+        exactly 0 on both contexts.  None: the call as it was."""
         _require_cuda(eps, "eps")
-        return _SpanLossFn.apply(eps, self.engine(eps.device), cu_seqlens, prompt_lengths, seeds, tag, noise)
+        return _SpanLossFn.apply(eps, self.engine(eps.device), cu_seqlens, prompt_lengths, seeds, tag, noise, suffix_lengths)
 
     def cosine_beta_schedule(self, timesteps, s=0.008):
         """Reference src/model/DiTTO.py:96-104 (a dozen-element host-side table, torch ops as in the reference)."""

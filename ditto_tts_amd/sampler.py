@@ -163,6 +163,13 @@ def _padded_rescale(guidance_rescale):
                                   "sample_guided_packed(guidance_rescale=)")
 
 
+def _padded_suffix(suffix_lengths):
+    """the padded layouts have no speech infilling"""
+    if suffix_lengths is not None:
+        raise NotImplementedError("speech infilling is served over packed batches: pack the batch and call "
+                                  "sample_guided_packed(suffix_lengths=)")
+
+
 def _padded_solver(solver):
     """the padded layouts run the strided (DDIM) solver only"""
     if solver not in SOLVERS:
@@ -347,13 +354,14 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
                                cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None, prompt_lengths=None,
-                               solver="ddim", guidance_rescale=None):
+                               solver="ddim", guidance_rescale=None, suffix_lengths=None):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
         DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step, with optional
         classifier-free guidance: the step runs ONE forward on the doubled batch [x; x] x [text; null_text] and combines
         eps_u + w (eps_c - eps_u).  sample_guided with one uniform `cfg_scale` over a dense batch: one library call per step."""
         _padded_solver(solver)
         _padded_rescale(guidance_rescale)
+        _padded_suffix(suffix_lengths)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         if speech_lengths is not None or text_lengths is not None:
@@ -484,7 +492,8 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
                       null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
-                      cond_by_audio=False, batch_class=None, prompt_lengths=None, solver="ddim", guidance_rescale=None):
+                      cond_by_audio=False, batch_class=None, prompt_lengths=None, solver="ddim", guidance_rescale=None,
+                      suffix_lengths=None):
         """The strided (DDIM) loop of sample_latents_strided with what serving needs: per-utterance `speech_lengths` /
         `text_lengths` (a padded batch; rows past an utterance's length are exactly 0 in the result and padding never reaches a
         valid row), per-utterance `guidance` (None: no CFG; a number; or [B] numbers), and per-utterance `seeds`.  One library
@@ -498,9 +507,10 @@ class SpeechGenerator:
         callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
         count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
         The padded layout has no speech prompts (`prompt_lengths` raises NotImplementedError): pack the batch and call
-        sample_guided_packed; so do solver="dpmpp2m" and `guidance_rescale`.  Returns fp32 [B, N, d]."""
+        sample_guided_packed; so do solver="dpmpp2m", `guidance_rescale` and `suffix_lengths`.  Returns fp32 [B, N, d]."""
         _padded_solver(solver)
         _padded_rescale(guidance_rescale)
+        _padded_suffix(suffix_lengths)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
         B, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
@@ -535,7 +545,8 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
-                             batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None, guidance_rescale=None):
+                             batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None, guidance_rescale=None,
+                             suffix_lengths=None):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -566,7 +577,16 @@ class SpeechGenerator:
         sums, an utterance's factor depends on its own rows only).  The step is ditto_guided_step_packed_rescale_opts (2M:
         ..._multistep_rescale_opts): the same forward, two small launches, and the same update with ce s_b (ke s_b).  It needs
         `guidance` and `null_text_emb`; phi_b = 0 gives utterance b the bits of the call without the argument; steps outside a
-        `guidance_interval` rescale nothing.  None: the call as it was.  Returns fp32 [S, d]."""
+        `guidance_interval` rescale nothing.  None: the call as it was.
+        `suffix_lengths` (list / tuple / int tensor [B], Q_b >= 0, P_b + Q_b <= N_b - 1): SPEECH INFILLING — the last Q_b rows of
+        utterance b in `audio_emb` are clean latents too (the audio behind the part to re-synthesise); both contexts are written to
+        both halves of x2 before the loop and come back bit-equal.  The G_b = N_b - P_b - Q_b rows in between start from x_T — with
+        `seeds`, ditto_noise_normal(seed_b, 0xFFFFFFFF) over G_b rows; with `cond_by_audio`, those rows of `audio_emb` — and every
+        step is one ditto_guided_step_packed_window_opts call (2M: ..._multistep_window_opts) whose update runs over the window
+        alone.  Works without `prompt_lengths` (P = 0) and with guidance, seeds, noises, batch_class, both solvers and a
+        `guidance_interval`; `guidance_rescale` with it raises NotImplementedError (the statistics run over prompt-to-end rows).  A
+        model fills a window only if it was trained with spans anywhere (DiTTO.span_noise_packed(suffix_lengths=)); the effect on
+        speech quality has not been measured.  None: the call as it was, whatever `prompt_lengths` is.  Returns fp32 [S, d]."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         interval = None if guidance_interval is None else validate_guidance_interval(guidance_interval, self.diffusion_steps)
@@ -574,17 +594,27 @@ class SpeechGenerator:
             raise ValueError("guidance_interval needs guidance= and null_text_emb=")
         if guidance_rescale is not None and (guidance is None or null_text_emb is None):
             raise ValueError("guidance_rescale needs guidance= and null_text_emb=")
+        if guidance_rescale is not None and suffix_lengths is not None:
+            raise NotImplementedError("guidance_rescale= with suffix_lengths=: the rescale statistics have no windowed form")
         rescale = rescale_vector(guidance_rescale, len(cu_seqlens) - 1)
         multistep = solver == "dpmpp2m"
         if multistep and (eta != 0 or noises is not None):
             raise ValueError('solver="dpmpp2m" is deterministic: eta must be 0 and noises= cannot be given')
         require_fused_attention(self.ditto_model.cfg, "packed batches")
-        from .varlen import pack, validate_cu_seqlens, validate_prompt_lengths
+        from .varlen import pack, validate_cu_seqlens, validate_prompt_lengths, validate_suffix_lengths
         S, d = int(audio_emb.shape[0]), int(audio_emb.shape[1])
         B = len(cu_seqlens) - 1
         cu = validate_cu_seqlens(cu_seqlens, B, S, S, "cu_seqlens")
         N = int((cu[1:] - cu[:-1]).max())
         pl = None if prompt_lengths is None else validate_prompt_lengths(prompt_lengths, cu)
+        ql = None if suffix_lengths is None else validate_suffix_lengths(suffix_lengths, cu, prompt_lengths)
+
+        def context_kw(eng):
+            """the step's prompt_len / suffix_len arguments"""
+            kw = {} if pl is None else dict(prompt_len=pl.to(eng.device))
+            if ql is not None:
+                kw["suffix_len"] = ql.to(eng.device)
+            return kw
 
         def entry_of(eng):
             return eng.guided_step_packed_multistep_ if multistep else eng.guided_step_packed_
@@ -594,9 +624,8 @@ class SpeechGenerator:
             the texts alone — what the call without guidance runs"""
             text = text_emb.to(eng.device).float().contiguous()
             ct = validate_cu_seqlens(text_cu_seqlens, B, int(text.shape[0]), int(text.shape[0]), "text_cu_seqlens")
-            kw = {} if pl is None else dict(prompt_len=pl.to(eng.device))
             return functools.partial(entry_of(eng), x2[:S], eng.prepare_text_packed(text, ct), B=B,
-                                     offsets=eng.guided_offsets_packed(cu, S, N, False), **kw)
+                                     offsets=eng.guided_offsets_packed(cu, S, N, False), **context_kw(eng))
 
         def begin(eng, cfg, seeds):
             entry = entry_of(eng)
@@ -616,11 +645,14 @@ class SpeechGenerator:
             cond = eng.prepare_text_packed(text, ct)
             offsets = eng.guided_offsets_packed(cu, S, N, cfg)
             x2 = torch.empty(2 * S if cfg else S, d, dtype=torch.float32, device=eng.device)
-            if pl is not None:
-                x2[:S].copy_(audio_emb)                          # the prompts (and, with cond_by_audio, the start of the rest)
+            if pl is not None or ql is not None:
+                x2[:S].copy_(audio_emb)                          # the contexts (and, with cond_by_audio, the start of the rest)
                 if not cond_by_audio:
-                    gl = (cu[1:] - cu[:-1] - pl).tolist()        # generated rows per utterance, and where they sit in the batch
-                    at = torch.cat([torch.arange(int(cu[b]) + int(pl[b]), int(cu[b + 1])) for b in range(B)]).to(eng.device)
+                    p0 = pl if pl is not None else torch.zeros(B, dtype=torch.int32)
+                    q0 = ql if ql is not None else torch.zeros(B, dtype=torch.int32)
+                    gl = (cu[1:] - cu[:-1] - p0 - q0).tolist()   # generated rows per utterance, and where they sit in the batch
+                    at = torch.cat([torch.arange(int(cu[b]) + int(p0[b]), int(cu[b + 1]) - int(q0[b]))
+                                    for b in range(B)]).to(eng.device)
                     if seeds is not None:                        # x_T of an unprompted utterance of G_b rows with that seed
                         xt = torch.empty(B, max(gl), d, dtype=torch.float32, device=eng.device)
                         eng.noise_normal_(xt, seeds, 0xFFFFFFFF)
@@ -628,7 +660,7 @@ class SpeechGenerator:
                     else:
                         xt = torch.randn(len(at), d, dtype=torch.float32, device=eng.device)
                     x2[:S].index_copy_(0, at, xt)
-                return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets, prompt_len=pl.to(eng.device))
+                return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets, **context_kw(eng))
             if seeds is not None and not cond_by_audio:
                 # x_T: ditto_noise_normal over the padded [B, N, d] (the numbers of sample_guided(seeds=)), packed row by row
                 xt = torch.empty(B, N, d, dtype=torch.float32, device=eng.device)
@@ -643,24 +675,27 @@ class SpeechGenerator:
         return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval, begin_plain,
                                  rescale)
 
-    def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim"):
+    def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim", infill=False):
         """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an
         utterance, step() admits what fits, runs one guided strided step over everything in flight — each utterance at its own
         index of its own strided_schedule — and returns the finished ones.  `max_rows` / `max_utterances` / `max_text_rows`: the
         speech rows, utterances and conditioning rows (text, plus null text under guidance) in flight at once; every buffer is
         sized from them here.  `class_rows`: hip.CallOpts(class_rows=) of every step (else the thread's hip.batch_class scope).
         `solver`: "ddim", or "dpmpp2m" — every request of the stream then runs multistep_schedule (sample_guided_packed(solver=));
-        one solver per stream."""
+        one solver per stream.
+        `infill`: the stream accepts submit(..., suffix=[Q, d]) — speech infilling, clean rows behind the generated frames as
+        `prompt` puts them in front (sample_guided_packed(suffix_lengths=)) — and refuses guidance_interval= / guidance_rescale=.
+        False: the stream as it was."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         from .serving import DeviceBatch, GuidedStream
         require_fused_attention(self.ditto_model.cfg, "request streams (packed batches)")
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
         batch = DeviceBatch(eng, max_rows=max_rows, max_utterances=max_utterances, max_text_rows=max_text_rows, guided=guided,
-                            class_rows=class_rows, solver=solver)
+                            class_rows=class_rows, solver=solver, infill=infill)
         return GuidedStream(batch, self.alphas_cumprod, max_rows=max_rows, max_utterances=max_utterances,
                             max_text_rows=max_text_rows, guided=guided, text_dim=eng.cfg.text_dim, hidden_dim=eng.cfg.hidden_dim,
-                            solver=solver)
+                            solver=solver, infill=infill)
 
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):

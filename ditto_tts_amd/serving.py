@@ -19,6 +19,9 @@ with cfg 1 / 0).
 Guidance rescale (submit(guidance_rescale=)): each request's blend factor phi rides in the step block; a step in which a guided
 request has phi > 0 runs the ..._rescale_opts form of its entry — the same forward and update, with the two statistics launches of
 csrc/guided_rescale.hip in between — over a scratch sized once from the capacities.
+Speech infilling (guided_stream(infill=True), submit(suffix=)): a request may carry clean rows BEHIND its generated frames as well;
+each request's suffix length rides in the step block and a step with a suffixed request in flight runs the ..._window_opts form of
+its entry (csrc/guided_window.hip).  Such a stream has no guidance intervals and no guidance rescale.
 They serve the reference's sampling loop (reference src/model/SpeechGenerator.py:130-164) to a request stream.
 """
 from __future__ import annotations
@@ -49,12 +52,15 @@ class StreamHandle:
 class Request:
     """One utterance of a stream: what was submitted, and where it stands (index `i` of its schedule; its slot `b`, speech row
     `row` and conditioning rows `trow` / `nrow` in the batch's CURRENT buffers once admitted).  `prompt` ([P, d] or None): the
-    speech prompt that stands in front of the `n_frames` generated rows; the utterance occupies `rows` = P + n_frames rows."""
+    speech prompt that stands in front of the `n_frames` generated rows, `suffix` ([Q, d] or None) the clean rows behind them (speech
+    infilling); the utterance occupies `rows` = P + n_frames + Q rows."""
     __slots__ = ("handle", "text", "null", "T", "T_null", "n_frames", "seed", "w", "n_steps", "eta", "x_T", "schedule", "i", "b",
-                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm", "phi")
+                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm", "phi", "suffix", "Q")
 
-    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None, interval=None, phi=0.0):
+    def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None, interval=None, phi=0.0,
+                 suffix=None):
         self.handle, self.text, self.null = handle, text, null
+        self.suffix, self.Q = suffix, 0 if suffix is None else int(suffix.shape[0])
         self.phi = float(phi)                        # guidance rescale: the blend factor in [0, 1]; 0 = none
         # `interval`: None, or (t_lo, t_hi) — guided only at the steps whose timestep lies in it.  `in_g`: whether the batch's current
         # layout holds its unconditional copy (None before its first regroup); `ntm`: the tmod row of its null text there
@@ -75,7 +81,7 @@ class Request:
 
     @property
     def rows(self) -> int:
-        return self.P + self.n_frames
+        return self.P + self.n_frames + self.Q
 
 
 class Plan:
@@ -115,9 +121,9 @@ class StepArgs:
     utterance's (a, kx, ke, b, g, use_prev) of its own multistep_schedule; a, ce, cz and tags are then None.  Under guidance
     `in_g` [B] says who is guided at this step (each request's guided_now(), asked once), `partner` [B] is its partner_table,
     `G` the number of guided utterances and `S_G` their rows (None, None, 0, 0 unguided).  `phi` [B]: each utterance's guidance-rescale
-    blend factor (0: none)."""
+    blend factor (0: none).  `suffix` [B]: each utterance's suffix rows (speech infilling; 0: none)."""
     __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt", "coef", "in_g",
-                 "partner", "G", "S_G", "phi")
+                 "partner", "G", "S_G", "phi", "suffix")
 
 
 def _cumulate(lengths) -> List[int]:
@@ -141,9 +147,9 @@ def _is_int(v) -> bool:
 
 
 class GuidedStream:
-    """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None)
+    """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None, infill=False)
     h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None,
-                      prompt=None, guidance_interval=None, guidance_rescale=None)
+                      prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None)
     done = stream.step()          # [(handle, latents fp32 [n_frames, d] on the GPU), ...]
     stream.pending, stream.active, stream.drain()
 
@@ -162,14 +168,19 @@ class GuidedStream:
     whose timestep lies in the interval (sample_guided_packed(guidance_interval=)); at the others it takes no part in the
     unconditional forward.  It counts against the capacities like any guided request, at every step.
     `guidance_rescale` (a guided stream, either solver; None or a number in [0, 1]): the request's guidance-rescale blend factor
-    (sample_guided_packed(guidance_rescale=)), applied at the steps at which it is guided."""
+    (sample_guided_packed(guidance_rescale=)), applied at the steps at which it is guided.
+    `suffix` (a stream made with infill=True only; floating [Q, d], Q >= 1): speech infilling — clean latents kept BEHIND the
+    `n_frames` generated rows at every step, as `prompt` is kept in front (sample_guided_packed(suffix_lengths=)).  The request
+    occupies P + n_frames + Q of `max_rows`; `x_T` and the result stay [n_frames, d].  An infill stream refuses
+    `guidance_interval` and `guidance_rescale` (NotImplementedError: neither update has a windowed form); with no suffixed request in
+    flight it runs the entries a plain stream runs."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
-                 text_dim: int, hidden_dim: int, solver: str = "ddim"):
+                 text_dim: int, hidden_dim: int, solver: str = "ddim", infill: bool = False):
         from .sampler import SOLVERS
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
-        self.solver = solver
+        self.solver, self.infill = solver, bool(infill)
         for name, v in (("max_rows", max_rows), ("max_utterances", max_utterances), ("max_text_rows", max_text_rows)):
             if not _is_int(v) or v < 1:
                 raise ValueError(f"{name}: a positive int is needed, got {v!r}")
@@ -210,7 +221,7 @@ class GuidedStream:
         return t.detach()
 
     def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None,
-               prompt=None, guidance_interval=None, guidance_rescale=None) -> StreamHandle:
+               prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None) -> StreamHandle:
         """Queue one utterance.  Everything is validated here, on the host: a bad request raises ValueError and leaves the stream as
         it was; so does one that could never fit the capacities."""
         text = self._text(text_emb, "text_emb")
@@ -233,6 +244,11 @@ class GuidedStream:
             if guidance is not None or null_text_emb is not None:
                 raise ValueError("this stream is unguided: a request with guidance= or null_text_emb= belongs in a guided stream")
             null = None
+        if suffix is not None and not self.infill:
+            raise ValueError("suffix= needs a stream made with infill=True (guided_stream(infill=True))")
+        if self.infill and (guidance_interval is not None or guidance_rescale is not None):
+            raise NotImplementedError("an infill stream serves neither guidance_interval= nor guidance_rescale=: the mixed and the "
+                                      "rescale kernels have no windowed form")
         interval = None
         if guidance_interval is not None:
             if not self.guided:
@@ -262,11 +278,16 @@ class GuidedStream:
                     or prompt.shape[1] != self.hidden_dim):
                 raise ValueError(f"prompt: a floating-point tensor [P >= 1, {self.hidden_dim}] is needed")
             prompt = prompt.detach()
+        if suffix is not None:
+            if (not isinstance(suffix, torch.Tensor) or not suffix.dtype.is_floating_point or suffix.dim() != 2 or suffix.shape[0] < 1
+                    or suffix.shape[1] != self.hidden_dim):
+                raise ValueError(f"suffix: a floating-point tensor [Q >= 1, {self.hidden_dim}] is needed")
+            suffix = suffix.detach()
         req = Request(StreamHandle(self._next_id), text, null, n_frames, seed, None if guidance is None else float(guidance), n_steps,
-                      float(eta), x_T, schedule, prompt, interval, phi)
+                      float(eta), x_T, schedule, prompt, interval, phi, suffix)
         if req.rows > self.max_rows:
-            raise ValueError(f"a request of {req.rows} rows ({req.P} prompt + {req.n_frames} frames) can never fit max_rows = "
-                             f"{self.max_rows}")
+            raise ValueError(f"a request of {req.rows} rows ({req.P} prompt + {req.n_frames} frames"
+                             + (f" + {req.Q} suffix" if req.Q else "") + f") can never fit max_rows = {self.max_rows}")
         if req.text_rows > self.max_text_rows:
             raise ValueError(f"a request of {req.text_rows} conditioning rows can never fit max_text_rows = {self.max_text_rows}")
         self._next_id += 1
@@ -342,6 +363,7 @@ class GuidedStream:
         s.handles = [r.handle for r in members]
         s.prompt = [r.P for r in members]
         s.phi = [r.phi for r in members]
+        s.suffix = [r.Q for r in members]
         return s
 
 
@@ -377,11 +399,17 @@ _SRC_X, _SRC_XT, _SRC_COND, _SRC_NEW_COND, _SRC_TABLE, _SRC_Q = range(6)
 _DST_X, _DST_OUT, _DST_COND, _DST_OFFSETS, _DST_Q = range(5)
 
 
+def _suffix_rows(r) -> int:
+    """Q of a request; a record without the field (host arithmetic on a bare record) has no suffix"""
+    return getattr(r, "Q", 0)
+
+
 def speech_segments(r: Request, new: bool, j: int, dst_row: int, xt_row: int, d4: int, dup: int) -> List[List[int]]:
     """The segments that put utterance `r` (slot j) at row `dst_row` of the next state, in 16-byte units (d4 per row).  A survivor
     moves as one range, prompt included.  A newcomer: its prompt, staged at row `xt_row` of the x_T buffer, is copied in front;
     behind it its own x_T (staged after the prompt) is copied, or drawn from its seed — the draw counts its units from 0, so the
-    generated rows get ditto_noise_normal's numbers for an utterance of n_frames rows.  `dup`: the unconditional half's offset."""
+    generated rows get ditto_noise_normal's numbers for an utterance of n_frames rows.  Its suffix (speech infilling), staged behind
+    those two, is one more copy behind the generated rows.  `dup`: the unconditional half's offset."""
     if not new:
         return [[hip.REGROUP_COPY, _SRC_X, _DST_X, 0, r.row * d4, dst_row * d4, r.rows * d4, dup]]
     segs = []
@@ -391,6 +419,10 @@ def speech_segments(r: Request, new: bool, j: int, dst_row: int, xt_row: int, d4
         segs.append([hip.REGROUP_COPY, _SRC_XT, _DST_X, 0, (xt_row + r.P) * d4, (dst_row + r.P) * d4, r.n_frames * d4, dup])
     else:
         segs.append([hip.REGROUP_DRAW, 0, _DST_X, j, 0, (dst_row + r.P) * d4, r.n_frames * d4, dup])
+    Q = _suffix_rows(r)
+    if Q:
+        segs.append([hip.REGROUP_COPY, _SRC_XT, _DST_X, 0, (xt_row + staged_rows(r) - Q) * d4, (dst_row + r.P + r.n_frames) * d4,
+                     Q * d4, dup])
     return segs
 
 
@@ -401,12 +433,12 @@ def history_segment(r: Request, dst_row: int, d4: int) -> List[int]:
 
 
 def staged_rows(r: Request) -> int:
-    """rows of the x_T staging buffer a newcomer takes: its prompt, then its own x_T"""
-    return r.P + (r.n_frames if r.x_T is not None else 0)
+    """rows of the x_T staging buffer a newcomer takes: its prompt, then its own x_T, then its suffix"""
+    return r.P + (r.n_frames if r.x_T is not None else 0) + _suffix_rows(r)
 
 
 def retire_segments(done: List[Request], d4: int) -> List[List[int]]:
-    """the generated rows of the utterances that leave (their prompts stay behind), one behind the other in the output"""
+    """the generated rows of the utterances that leave (their prompts and suffixes stay behind), one behind the other in the output"""
     cu = _cumulate(r.n_frames for r in done)
     return [[hip.REGROUP_COPY, _SRC_X, _DST_OUT, 0, (r.row + r.P) * d4, cu[k] * d4, r.n_frames * d4, 0] for k, r in enumerate(done)]
 
@@ -451,11 +483,12 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
     return segs, tail
 
 
-def step_block_layout(max_utterances: int, guided: bool, multistep: bool) -> dict:
+def step_block_layout(max_utterances: int, guided: bool, multistep: bool, infill: bool = False) -> dict:
     """Byte offsets of the per-step argument block (host arithmetic): t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w
     fp32 [maxB] | tags uint32 [maxB] | prompt_len int32 [maxB] | partner int32 [maxB] | (multistep) ditto_multistep_coef [maxB] |
     phi fp32 [maxB] — the guidance-rescale blend factors, appended behind everything else: the fields in front keep the offsets
-    they had before it existed.  "f_stride": bytes of one fp32 / int32 field; "bytes": the whole block."""
+    they had before it existed.  `infill`: suffix_len int32 [maxB] ("suffix") is appended behind phi in the same way; off (the
+    default), the layout is the one without it.  "f_stride": bytes of one fp32 / int32 field; "bytes": the whole block."""
     maxB, nbB = int(max_utterances), (2 if guided else 1) * int(max_utterances)
     lay = {"t": 0, "seeds": _pad(nbB * 8, 16)}
     o_f = lay["seeds"] + _pad(maxB * 8, 16)
@@ -464,6 +497,9 @@ def step_block_layout(max_utterances: int, guided: bool, multistep: bool) -> dic
         lay[name] = o_f + k * lay["f_stride"]
     lay["phi"] = _pad(lay["coef"] + (C.sizeof(hip.MultistepCoef) * maxB if multistep else 0), 16)
     lay["bytes"] = lay["phi"] + lay["f_stride"]
+    if infill:
+        lay["suffix"] = lay["bytes"]
+        lay["bytes"] += lay["f_stride"]
     return lay
 
 
@@ -472,13 +508,14 @@ class DeviceBatch:
     ([max_rows, d] unguided) and two conditioning images (a regroup reads one and writes the other), a staging image for the
     newcomers' conditioning and one for callers' x_T, the device offsets, the per-step argument block and the segment table.
     `solver` "dpmpp2m": two history buffers [max_rows, d] beside the state (double-buffered like it: a regroup moves the
-    survivors' rows of both in its one launch), and the step block carries one ditto_multistep_coef per utterance."""
+    survivors' rows of both in its one launch), and the step block carries one ditto_multistep_coef per utterance.
+    `infill`: the step block carries each utterance's suffix length as well."""
 
     def __init__(self, engine, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool, class_rows=None,
-                 solver: str = "ddim"):
+                 solver: str = "ddim", infill: bool = False):
         from .engine import require_fused_attention
         require_fused_attention(engine.cfg, "request streams (packed batches)")
-        self.multistep = solver != "ddim"
+        self.multistep, self.infill = solver != "ddim", bool(infill)
         self.eng, self.lib, self.guided = engine, engine.lib, bool(guided)
         self.halves = 2 if guided else 1
         self.maxB, self.maxS, self.maxT = int(max_utterances), int(max_rows), int(max_text_rows)
@@ -501,7 +538,8 @@ class DeviceBatch:
             self.x_T = torch.zeros(self.maxS, d, dtype=torch.float32, device=dev)
             self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
             self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
-            lay = step_block_layout(self.maxB, self.guided, self.multistep)
+            lay = step_block_layout(self.maxB, self.guided, self.multistep, self.infill)
+            self.o_suffix = lay.get("suffix")
             self.f_stride, self.block_bytes = lay["f_stride"], lay["bytes"]
             (self.o_t, self.o_seeds, self.o_a, self.o_ce, self.o_cz, self.o_w, self.o_tags, self.o_prompt, self.o_partner, self.o_coef,
              self.o_phi) = (lay[k] for k in ("t", "seeds", "a", "ce", "cz", "w", "tags", "prompt", "partner", "coef", "phi"))
@@ -538,6 +576,8 @@ class DeviceBatch:
         if self.guided:
             buf[self.o_partner:self.o_partner + B * 4].view(np.int32)[:] = a.partner
             buf[self.o_phi:self.o_phi + B * 4].view(np.float32)[:] = a.phi
+        if self.infill:
+            buf[self.o_suffix:self.o_suffix + B * 4].view(np.int32)[:] = a.suffix
         self.block.send(buf)
 
     def _block_ptr(self, off: int) -> int:
@@ -597,13 +637,15 @@ class DeviceBatch:
         for r in plan.newcomers:
             new_image[r.handle.id] = (at // 16, (at + self._tmod_offset(r.text_rows)) // 16)
             at += self._condition(r, at)
-        for r in plan.members:             # the newcomers' prompts and own x_T, staged in the order speech_segments reads them
+        for r in plan.members:             # the newcomers' prompts, own x_T and suffixes, staged in the order speech_segments reads them
             if r.handle.id not in new_image:
                 continue
             if r.P:
                 self.x_T[xt_row:xt_row + r.P].copy_(r.prompt, non_blocking=True)
             if r.x_T is not None:
                 self.x_T[xt_row + r.P:xt_row + r.P + r.n_frames].copy_(r.x_T, non_blocking=True)
+            if r.Q:
+                self.x_T[xt_row + staged_rows(r) - r.Q:xt_row + staged_rows(r)].copy_(r.suffix, non_blocking=True)
             xt_row += staged_rows(r)
         segs, tail = regroup_table(plan, d4=d4, kv16=kv16, tm16=tm16, tmod_old16=self._tmod_off // 16, tmod_new16=tmod_new // 16,
                                    new_image=new_image, multistep=self.multistep, cu_pad=self.cu_pad)
@@ -627,7 +669,10 @@ class DeviceBatch:
             [x; x] when everyone is guided, with cfg 0 over the conditional rows when nobody is (or the stream is unguided).
         A step in which a guided utterance has phi > 0 runs the guidance-rescale form of its entry
         (ditto_guided_step_packed_multistep_rescale_opts; ditto_guided_step_packed_rescale_opts with the partner table when only
-        some are guided, without it when everyone is): phi from the step block, the scratch built once."""
+        some are guided, without it when everyone is): phi from the step block, the scratch built once.
+        A step with a suffixed utterance in flight (an infill stream: no intervals, no rescale) runs the window form of its entry,
+        ditto_guided_step_packed_tags_window_opts or ditto_guided_step_packed_multistep_window_opts, the suffix lengths from the
+        step block; with none in flight, the entries above."""
         if not self._block_sent:
             self._send_block(a)
         self._block_sent = False
@@ -642,6 +687,16 @@ class DeviceBatch:
         prompt = at(self.o_prompt) if any(a.prompt) else None
         noise = (None, at(self.o_seeds), at(self.o_tags))                 # no buffer: Philox of the seeds at each utterance's tag
         coef = (at(self.o_a), at(self.o_ce), at(self.o_cz))
+        if self.infill and any(a.suffix):
+            if self.multistep:
+                hip.check(self.lib.ditto_guided_step_packed_multistep_window_opts(
+                    *head, prompt, at(self.o_suffix), self.q[self.cur].data_ptr(), None, at(self.o_coef), None, a.B, a.S, a.max_N, a.S_T,
+                    a.max_T, int(self.guided), *tail))
+            else:
+                hip.check(self.lib.ditto_guided_step_packed_tags_window_opts(
+                    *head, prompt, at(self.o_suffix), *noise, at(self.o_w) if cfg else None, *coef, a.B, a.S, a.max_N, a.S_T, a.max_T,
+                    int(cfg), *tail))
+            return
         if cfg and any(p > 0 and g for p, g in zip(a.phi, a.in_g)):
             tail_rs = tail[:4] + (self.rescale.data_ptr(), self.rescale.numel()) + tail[4:]
             if self.multistep:

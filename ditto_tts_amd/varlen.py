@@ -57,6 +57,35 @@ def validate_prompt_lengths(prompt_lengths, cu, name: str = "prompt_lengths") ->
     return t.to(torch.int32)
 
 
+def validate_suffix_lengths(suffix_lengths, cu, prompt_lengths=None, name: str = "suffix_lengths") -> torch.Tensor:
+    """Suffix-context lengths of a packed batch (speech infilling): `suffix_lengths` (list / tuple of ints, or an integer tensor) as a
+    CPU int32 tensor [B] with Q_b >= 0 and P_b + Q_b <= N_b - 1 (N_b from the validated offsets `cu` [B + 1], P_b from the validated
+    `prompt_lengths`, None: 0 — at least one row of every utterance is generated).  Anything else raises ValueError naming the
+    utterance."""
+    B = len(cu) - 1
+    if isinstance(suffix_lengths, torch.Tensor):
+        if suffix_lengths.dtype.is_floating_point or suffix_lengths.dtype.is_complex or suffix_lengths.dtype == torch.bool:
+            raise ValueError(f"{name}: an integer tensor is needed, got {suffix_lengths.dtype}")
+        t = suffix_lengths.detach().to("cpu", torch.int64)
+    elif isinstance(suffix_lengths, (list, tuple)):
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in suffix_lengths):
+            raise ValueError(f"{name}: a list / tuple of ints is needed")
+        t = torch.tensor(list(suffix_lengths), dtype=torch.int64)
+    else:
+        raise ValueError(f"{name}: a list, tuple or integer tensor is needed, got {type(suffix_lengths).__name__}")
+    if t.dim() != 1 or t.shape[0] != B:
+        raise ValueError(f"{name}: shape [{B}] expected, got {list(t.shape)}")
+    n = torch.as_tensor(cu).detach().to("cpu", torch.int64)
+    n = n[1:] - n[:-1]
+    p = torch.zeros(B, dtype=torch.int64) if prompt_lengths is None else validate_prompt_lengths(prompt_lengths, cu).to(torch.int64)
+    bad = torch.nonzero((t < 0) | (p + t > n - 1)).reshape(-1)
+    if bad.numel():
+        b = int(bad[0])
+        raise ValueError(f"{name}: utterance {b} has {int(n[b])} rows and a prompt of {int(p[b])}, its suffix must hold 0 .. "
+                         f"{int(n[b]) - 1 - int(p[b])} of them, got {int(t[b])}")
+    return t.to(torch.int32)
+
+
 def _dev_lengths(lengths, B, maxlen, name, device):
     if lengths is None:
         return None

@@ -714,6 +714,61 @@ int ditto_span_noise_packed(const float* x0, const float* noise, const int64_t* 
 int ditto_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
                           const int32_t* prompt_len, size_t n_elems, float* grad_eps, float* loss, void* workspace,
                           size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream);
+/* ---- Speech infilling: generate a WINDOW of each utterance with clean context on both sides.  The first P_b = prompt_len[b] and the
+ * last Q_b = suffix_len[b] rows of utterance b are clean latents; the G_b = n_b - P_b - Q_b rows in between are generated.  The forward
+ * sees context rows like any rows; the entries below leave them alone.  The reference has no such sampler: like the prompts this is
+ * pinned by its own formulas.  Every entry is its _prompt / multistep / span counterpart with one more argument:
+ *   suffix_len: device int32 [B], REQUIRED (NULL: DITTO_ERR_ARG), shared by both halves under cfg.  prompt_len: device int32 [B] or
+ *   NULL (P = 0).  On the device P_b is clamped into [0, n_b - 1] and Q_b into [0, n_b - 1 - P_b]: at least one row is generated, and
+ *   a bad value gives wrong rows, never an access outside the utterance's own rows.
+ * Contract: with suffix_len all 0, every entry gives the bits of its counterpart on every buffer it writes — the loss and the partial
+ *   sums of ditto_span_mse_window included.
+ * ditto_guided_update_packed_window / ditto_guided_update_packed_tags_window: ditto_guided_update_packed_prompt / _tags_prompt over
+ *   rows [cu[b] + P_b, cu[b+1] - Q_b) only.  Context rows of x2 (both halves), of eps2 and of `noise` are neither read nor written,
+ *   on either side: 0 B per context element, 20 B per generated element under cfg.  The Philox quad index is local to the window,
+ *   ((row - cu[b] - P_b) d + col) / 4: a windowed utterance draws what an unprompted one of G_b rows with the same seed draws.
+ * ditto_guided_step_packed_window_opts / ditto_guided_step_packed_tags_window_opts: the step entries with that update; the forward is
+ *   unchanged.
+ * ditto_multistep_update_window / ditto_guided_step_packed_multistep_window_opts: ditto_multistep_update_packed /
+ *   ditto_guided_step_packed_multistep_opts over the window; the context rows of q are untouched too.
+ * ditto_span_noise_window / ditto_span_mse_window: ditto_span_noise_packed / ditto_span_mse_packed with the span anywhere: x_in is a
+ *   bit copy of x0 on both context regions; grad_eps is exactly 0 on both and eps (and `noise`) is not read there; the Philox index
+ *   is window-local; n_elems = d x sum of G_b.  The same walk, partial layout, workspace and reduction order as the counterparts. */
+int ditto_guided_update_packed_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
+                                      const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                      const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg,
+                                      ditto_stream_t stream);
+int ditto_guided_update_packed_tags_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                           const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                           const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg,
+                                           ditto_stream_t stream);
+int ditto_guided_step_packed_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                         const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len,
+                                         const float* noise, const int64_t* seeds, uint32_t step, const float* w, const float* a,
+                                         const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
+                                         const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                         ditto_stream_t stream, const ditto_call_opts* opts);
+int ditto_guided_step_packed_tags_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                              const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len,
+                                              const float* noise, const int64_t* seeds, const uint32_t* tags, const float* w,
+                                              const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T,
+                                              int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
+                                              size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+int ditto_multistep_update_window(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
+                                  const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, const int32_t* prompt_len,
+                                  const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream);
+int ditto_guided_step_packed_multistep_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                                   const int32_t* cu_speech, const int32_t* cu_text, const int32_t* prompt_len,
+                                                   const int32_t* suffix_len, float* q, const ditto_multistep_coef* step,
+                                                   const ditto_multistep_coef* coefs, const float* w, int B, int S, int max_N, int S_T,
+                                                   int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
+                                                   size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+int ditto_span_noise_window(const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca, const float* cs,
+                            const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, float* x_in, int B, int S,
+                            int max_N, int d, ditto_stream_t stream);
+int ditto_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
+                          const int32_t* prompt_len, const int32_t* suffix_len, size_t n_elems, float* grad_eps, float* loss,
+                          void* workspace, size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream);
 /* ditto_regroup_packed: build the next packed batch from the current one plus the newcomers, in ONE launch driven by a DEVICE table
  *   of n_seg segments.  A segment moves `n` 16-byte units (every row of the state, the K/V cache and tmod is a whole number of them)
  *   to unit dst_off of destination buffer `dest` and, when dup_off != 0, also to dst_off + dup_off (a speech segment under CFG: the
