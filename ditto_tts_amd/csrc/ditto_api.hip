@@ -2062,6 +2062,55 @@ int ditto_gemm_fp8(const void* A, int lda, const void* W, const float* wscale, c
     return DITTO_OK;
 }
 
+// ditto_gemm_epilogue_bf16's body for the fp8 GEMM: A, W (and the gated output) are bytes, lda / ldw (and the gated ldo) in bytes
+int ditto_gemm_epilogue_fp8(const ditto_gemm_epilogue_args* a, const float* wscale, int epilogue, int* structure_out,
+                            ditto_stream_t stream) {
+    const char* who = "ditto_gemm_epilogue_fp8";
+    if (structure_out) *structure_out = 0;
+    if (!a || !a->A || !a->W || !a->out) return fail(DITTO_ERR_ARG, "null pointer to %s", who);
+    if (epilogue != 0 && epilogue != 1 && epilogue != 2 && epilogue != 4 && epilogue != 5)
+        return fail(DITTO_ERR_ARG, "%s: epilogue must be 0, 1, 2, 4 or 5", who);
+    const int M = a->M, N = a->N, K = a->K;
+    if (M <= 0 || N <= 0 || K <= 0) return fail(DITTO_ERR_SHAPE, "%s: M, N and K must be positive", who);
+    if (K % 128 || N % 16) return fail(DITTO_ERR_SHAPE, "%s: need K %% 128 == 0 and N %% 16 == 0", who);
+    if (a->lda % 16 || a->lda < K || a->ldw % 16 || (a->ldw && a->ldw < K))
+        return fail(DITTO_ERR_SHAPE, "%s: lda / ldw must cover K bytes in multiples of 16 (ldw 0 = K)", who);
+    if (a->w_rows < 0 || a->w_rows > N) return fail(DITTO_ERR_SHAPE, "%s: w_rows must be in [0, N] (0 = N)", who);
+    const GemmEpilogue e = (GemmEpilogue)epilogue;
+    const bool f32_out = e == EPI_BIAS_RES_F32 || e == EPI_BIAS_F32;
+    const int out_cols = e == EPI_GATED_FP8 ? N / 2 : N;
+    const int ldo_unit = e == EPI_GATED_FP8 ? 8 : (f32_out ? 4 : 8);   // 8-byte pieces of fp8, 16-byte pieces otherwise
+    if (a->ldo < out_cols || a->ldo % ldo_unit)
+        return fail(DITTO_ERR_SHAPE, "%s: ldo must cover %d columns in multiples of %d", who, out_cols, ldo_unit);
+    switch (e) {
+        case EPI_BIAS_RES_F32:
+            if (a->residual && (a->ldr < N || a->ldr % 4)) return fail(DITTO_ERR_SHAPE, "%s: ldr must cover N columns in multiples of 4", who);
+            if (a->out2_bf16 && (a->ldo2 < N || a->ldo2 % 4)) return fail(DITTO_ERR_SHAPE, "%s: ldo2 must cover N columns in multiples of 4", who);
+            break;
+        case EPI_QKV_ROPE:
+            if (!a->rope_cos || !a->rope_sin) return fail(DITTO_ERR_ARG, "%s: the RoPE epilogue needs rope_cos and rope_sin (read unless rope_freq_rev is given)", who);
+            if (N % 64 || a->rope_cols % 64 || a->rope_cols < 0 || a->rope_cols > N)
+                return fail(DITTO_ERR_SHAPE, "%s: the RoPE epilogue needs N %% 64 == 0 and 0 <= rope_cols <= N in multiples of 64", who);
+            if (a->rope_rows_per_batch <= 0) return fail(DITTO_ERR_SHAPE, "%s: epilogue 2 needs rope_rows_per_batch > 0", who);
+            break;
+        case EPI_GATED_FP8:
+            if (!a->bias) return fail(DITTO_ERR_ARG, "%s: the gated epilogue needs a bias", who);
+            if (N % 32) return fail(DITTO_ERR_SHAPE, "%s: the gated epilogue needs N %% 32 == 0", who);
+            break;
+        default: break;
+    }
+    GemmArgs g{};
+    g.A = a->A; g.lda = a->lda; g.W = a->W; g.ldw = a->ldw; g.w_rows = a->w_rows; g.bias = a->bias;
+    g.residual = a->residual; g.ldr = a->ldr; g.out = a->out; g.ldo = a->ldo; g.out2_bf16 = a->out2_bf16; g.ldo2 = a->ldo2;
+    g.rope_cos = a->rope_cos; g.rope_sin = a->rope_sin; g.rope_rows_per_batch = a->rope_rows_per_batch; g.rope_cols = a->rope_cols;
+    g.rope_freq_rev = a->rope_freq_rev;
+    g.M = M; g.N = N; g.K = K; g.fp8 = true; g.wscale = wscale;
+    const hipError_t err = launch_gemm(g, e, (hipStream_t)stream);
+    if (structure_out) *structure_out = t_gemm_structure;
+    HIP_TRY(err);
+    return DITTO_OK;
+}
+
 // plain integer switches: one slot each (ditto_get_option reads them; ditto_set_option validates per name below)
 static int* option_slot(const char* name) {
     static const struct { const char* n; int* p; } tab[] = {

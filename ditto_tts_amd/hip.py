@@ -291,6 +291,7 @@ SYMBOLS = {
     "ditto_quantize_rows_fp8": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "ditto_layernorm_fp8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "ditto_gemm_fp8": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ditto_gemm_epilogue_fp8": (_i, [C.POINTER(GemmEpilogueArgs), _vp, _i, C.POINTER(C.c_int), _vp]),
     "ditto_slp_arena_bytes": (_sz, [C.POINTER(SlpConfig)]),
     "ditto_slp_workspace_bytes": (_sz, [C.POINTER(SlpConfig), _i, _i, _i]),
     "ditto_slp_create": (_i, [C.POINTER(SlpConfig), C.POINTER(SlpWeights), _vp, _sz, _vp, C.POINTER(_vp)]),

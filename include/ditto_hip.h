@@ -948,6 +948,14 @@ int ditto_layernorm_fp8(const float* x, const float* gamma, const float* beta, v
 int ditto_gemm_fp8(const void* A, int lda, const void* W, const float* wscale, const float* bias,
                    const float* residual, void* out, int ldo, int M, int N, int K, int epilogue,
                    ditto_stream_t stream);
+/* Every fp8 GEMM launch as the model fills it (tests/test_gpu_gemm_fp8.py): ditto_gemm_epilogue_bf16's fields with fp8 e4m3
+ * operands and wscale (fp32 [N], may be NULL = 1).  A, W and the gated output are bytes: lda, ldw and the gated ldo count bytes
+ * (lda, ldw multiples of 16; the gated ldo a multiple of 8); every other stride as ditto_gemm_epilogue_bf16.  epilogue 0, 1, 4:
+ * as ditto_gemm_fp8, with ldr, out2_bf16 / ldo2, ldw and w_rows; 2: QKV + RoPE, bf16 out (rope_* as ditto_gemm_epilogue_bf16);
+ * 5: gated MLP, fp8 out [M, N / 2].  Any other epilogue (the packed RoPE, 9, included): DITTO_ERR_ARG, nothing launched.
+ * *structure_out (may be NULL): 256 if a launch happened, 0 otherwise. */
+int ditto_gemm_epilogue_fp8(const ditto_gemm_epilogue_args* args, const float* wscale, int epilogue, int* structure_out,
+                            ditto_stream_t stream);
 
 /* ---- the speech-length predictor's decoder stack ------------------------------------------
  * Second user of the GEMM / attention family: the nn.TransformerDecoder the reference builds at

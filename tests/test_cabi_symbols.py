@@ -82,6 +82,7 @@ def test_null_arguments_are_refused_not_crashed():
     with pytest.raises(hip.DittoHipError):
         hip.check(lib.ditto_gemm_bf16(None, 0, None, None, None, None, 0, 1, 1, 1, 0, None))
     assert lib.ditto_gemm_epilogue_bf16(None, 0, None, None) == hip.ERR_ARG
+    assert lib.ditto_gemm_epilogue_fp8(None, None, 0, None, None) == hip.ERR_ARG
 
 
 def test_config_rejects_what_the_reference_cannot_run():
