@@ -1251,6 +1251,10 @@ int ditto_gemm_lnq_bf16(const void* h, int ldh, int h_is_bf16, const float* gamm
     if (mfma_shape != 32 && mfma_shape != 16) return fail(DITTO_ERR_ARG, "mfma_shape must be 32 (32x32x16) or 16 (16x16x32)");
     if (d == 1024 && (mfma_shape != 32 || h_is_bf16)) return fail(DITTO_ERR_SHAPE, "d = 1024: 32x32x16 and fp32 rows only");
     if ((uintptr_t)w_scratch % 256) return fail(DITTO_ERR_ARG, "w_scratch must be 256-byte aligned");
+    // a lane loads four columns of a row at once (16 bytes of fp32, 8 of bf16; ldh % 4 keeps every row aligned once the base is) and
+    // 16 bytes of gamma / beta, the bias row goes to the LDS in 16-byte pieces, and the output leaves in 16-byte stores
+    if ((uintptr_t)h % (h_is_bf16 ? 8 : 16) || ((uintptr_t)out_bf16 | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)bias) % 16)
+        return fail(DITTO_ERR_ARG, "ditto_gemm_lnq_bf16: h (fp32; 8 bytes for bf16), out, gamma, beta and bias must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(launch_repack_bf16_stage_major(W, w_scratch, d, d, s, mfma_shape == 32 ? 16 : 32));
     HIP_TRY(launch_gemm_lnq(h, ldh, h_is_bf16 != 0, gamma, beta, w_scratch, bias, out_bf16, ldo, M, d, mfma_shape,
@@ -1264,8 +1268,19 @@ int ditto_gemm_ln_bf16(const void* A, int lda, const void* W, const float* bias,
     if (!A || !W || !out || (gamma == nullptr) != (beta == nullptr) || (gamma == nullptr) != (u_bf16 == nullptr))
         return fail(DITTO_ERR_ARG, "bad argument to ditto_gemm_ln_bf16");
     const bool ok = N == 1024 ? gemm_fr64_supports(M, N, K, (size_t)lda, (size_t)K) : gemm_fr_supports(M, N, K, (size_t)lda, (size_t)K);
-    if (!ok || lda % 8)
-        return fail(DITTO_ERR_SHAPE, "ditto_gemm_ln_bf16 needs N == 768 (M >= 128) or N == 1024 (M >= 64), K %% 64 == 0, lda %% 8 == 0");
+    if (!ok || lda % 8 || lda < K)
+        return fail(DITTO_ERR_SHAPE, "ditto_gemm_ln_bf16 needs N == 768 or N == 1024, M >= 64, K %% 64 == 0, K >= 64, lda %% 8 == 0, lda >= K");
+    // Rows leave in 16-byte stores and the fp32 residual arrives in 16-byte loads (ldr = ldo): four fp32 / eight bf16 / sixteen fp8
+    // elements.  A, the bias and gamma | beta go to the LDS in 16-byte pieces, the weight fragments to registers in 16-byte loads.
+    const int ho = g_fr_hb ? 8 : 4, uo = g_fr_u_fp8 ? 16 : 8;
+    if (ldo < N || ldo % ho) return fail(DITTO_ERR_SHAPE, "ditto_gemm_ln_bf16: ldo must cover N columns in multiples of %d", ho);
+    if (u_bf16 && (ldu < N || ldu % uo)) return fail(DITTO_ERR_SHAPE, "ditto_gemm_ln_bf16: ldu must cover N columns in multiples of %d", uo);
+    if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)out | (uintptr_t)residual | (uintptr_t)u_bf16 | (uintptr_t)bias | (uintptr_t)gamma |
+         (uintptr_t)beta) % 16)
+        return fail(DITTO_ERR_ARG, "ditto_gemm_ln_bf16: A, W, out, residual, u, bias, gamma and beta must be 16-byte aligned");
+    // the bf16 residual tile is fetched at 32-bit byte offsets from the residual pointer (csrc/gemm_frd.hip issue_unit)
+    if (g_fr_hb && residual && (size_t)M * (size_t)ldo * 2 >= (1ull << 32))
+        return fail(DITTO_ERR_SHAPE, "ditto_gemm_ln_bf16: fr_hb needs M * ldo * 2 < 2^32");
     GemmParams p{};
     p.A = (const bf16*)A; p.lda = lda; p.W = (const bf16*)W; p.ldw = K; p.w_rows = N; p.bias = bias;
     p.residual = residual; p.ldr = ldo; p.out = out; p.ldo = ldo; p.M = M; p.N = N; p.K = K;

@@ -362,7 +362,10 @@ int ditto_attention_resid_varlen_bf16(const void* q, int ldq, const void* k, int
  *   src/components/DiT.py:148 / :155),   u bf16 [M,ldu] = LayerNorm(out) * gamma + beta  (eps 1e-5; the norm of :152 / the
  *   next block's :105).  gamma = beta = u = NULL: no LayerNorm output.  K % 64 == 0.
  *   W is NOT the nn.Linear image: it is packed stage-major, Wp[K/16][N][16] (Wp[s][n][j] = W[n][16 s + j]), so that
- *   each K-step's 24 / 32 KiB are contiguous (the kernel moves them by LDS-DMA in whole cache lines). */
+ *   each K-step's 24 / 32 KiB are contiguous (the kernel moves them by LDS-DMA in whole cache lines).
+ *   The residual is read at the stride ldo.  Rows move in 16-byte pieces: DITTO_ERR_SHAPE unless lda % 8 == 0, lda >= K, ldo >= N,
+ *   ldo % 4 == 0 ("fr_hb": % 8), and, with a LayerNorm output, ldu >= N, ldu % 8 == 0 ("fr_u_fp8": % 16); DITTO_ERR_ARG unless A, W,
+ *   out, residual, u, bias, gamma and beta are 16-byte aligned. */
 int ditto_gemm_ln_bf16(const void* A, int lda, const void* W, const float* bias, const float* residual, float* out,
                        int ldo, const float* gamma, const float* beta, void* u_bf16, int ldu, int M, int N, int K,
                        ditto_stream_t stream);
@@ -372,7 +375,8 @@ int ditto_gemm_ln_bf16(const void* A, int lda, const void* W, const float* bias,
  * W[d, d]^T + bias, eps 1e-5; the normalised rows live in the LDS only.  h: fp32 [M, ldh] or (h_is_bf16, d = 768) bf16 [M, ldh];
  * W: bf16, nn.Linear layout [d out, d in]; bias may be NULL.  mfma_shape 32 / 16 = v_mfma_f32_32x32x16_bf16 / 16x16x32 (two
  * builds of one kernel; d = 1024: 32 only).  w_scratch: d * d * 2 bytes, 256-byte aligned: receives the stage-major image of W the kernel streams (the model keeps
- * these images in its arena).  Any M >= 1. */
+ * these images in its arena).  Any M >= 1.  ldh % 4 == 0, ldo % 8 == 0; h (fp32: 16 bytes, bf16: 8), out, gamma, beta and bias
+ * 16-byte aligned (DITTO_ERR_ARG otherwise). */
 int ditto_gemm_lnq_bf16(const void* h, int ldh, int h_is_bf16, const float* gamma, const float* beta, const void* W,
                         const float* bias, void* out_bf16, int ldo, int M, int d, int mfma_shape, void* w_scratch,
                         ditto_stream_t stream);

@@ -191,19 +191,27 @@ def linear(Aq, Wq, wscale=None, bias=None):
     return acc, bound + 1e-30
 
 
-def layernorm(x, gamma=None, beta=None):
-    """fp64 LayerNorm (biased variance, eps 1e-5) of fp32 rows and the bound of the module docstring, before the e4m3 store"""
+def layernorm_terms(x):
+    """(t, rstd, em, er) of the module docstring for rows x: t = (x - mean) rstd in fp64, rstd [rows, 1], em the bound on the fp32
+    mean, er the relative bound on the fp32 rstd (gemm_fr_ref.py propagates a row perturbation through the same terms)"""
     x = x.double()
     d = x.shape[1]
     mean = x.mean(dim=1, keepdim=True)
     var = ((x - mean) ** 2).mean(dim=1, keepdim=True)
     rstd = 1.0 / torch.sqrt(var + LN_EPS)
     t = (x - mean) * rstd
-    g = gamma.double() if gamma is not None else torch.ones(d, dtype=torch.float64, device=x.device)
-    y = t * g + (beta.double() if beta is not None else 0.0)
     em = (d + 1) * G * x.abs().mean(dim=1, keepdim=True)
     ev = em * em + (d + 4) * G * (var + em * em)
     er = ev / (2 * (var + LN_EPS)) + (2 + E_RSQRT_ULPS) * G
+    return t, rstd, em, er
+
+
+def layernorm(x, gamma=None, beta=None):
+    """fp64 LayerNorm (biased variance, eps 1e-5) of fp32 rows and the bound of the module docstring, before the e4m3 store"""
+    t, rstd, em, er = layernorm_terms(x)
+    d = x.shape[1]
+    g = gamma.double() if gamma is not None else torch.ones(d, dtype=torch.float64, device=x.device)
+    y = t * g + (beta.double() if beta is not None else 0.0)
     return y, g.abs() * (em * rstd + t.abs() * (er + 2 * G)) + G * y.abs() + 1e-30
 
 
