@@ -1490,14 +1490,26 @@ int ditto_guided_step_opts(ditto_model_t m, float* x2, const void* cond, const i
     });
 }
 
+// the packed update (guided_packed.hip) behind the six ditto_guided_update_packed* entries: every argument but an entry's own required
+// pointers is checked here, before the launch
+static int guided_update_packed_checked(const char* who, float* x2, const float* eps2, const float* noise, const int64_t* seeds,
+                                        uint32_t step, const uint32_t* tags, bool per_utt, const float* w, const float* a,
+                                        const float* ce, const float* cz, const int32_t* cu, const int32_t* prompt_len,
+                                        const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
+    if (!cu) return fail(DITTO_ERR_ARG, "%s: null cu", who);
+    if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
+    if (int rc = check_guided_update(who, x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_guided_update_packed(x2, eps2, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu, prompt_len, suffix_len, B, S, max_N,
+                                        d, cfg != 0, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 int ditto_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step, const float* w,
                                const float* a, const float* ce, const float* cz, const int32_t* cu, int B, int S, int max_N, int d,
                                int cfg, ditto_stream_t stream) {
-    if (!cu) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed: null cu");
-    if (int rc = check_guided_update("ditto_guided_update_packed", x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
-    if (int rc = check_packed("ditto_guided_update_packed", B, S, max_N, S, max_N)) return rc;
-    HIP_TRY(launch_guided_update_packed(x2, eps2, noise, seeds, step, w, a, ce, cz, cu, B, S, max_N, d, cfg != 0, (hipStream_t)stream));
-    return DITTO_OK;
+    return guided_update_packed_checked("ditto_guided_update_packed", x2, eps2, noise, seeds, step, nullptr, false, w, a, ce, cz, cu,
+                                        nullptr, nullptr, B, S, max_N, d, cfg, stream);
 }
 
 // ---- guidance rescale (guided_rescale.hip): the scratch [coef_out | scale | partials], each part 256-byte aligned ----
@@ -1545,17 +1557,16 @@ static RescaleArgs rescale_args(const float* eps2, const float* w, const float* 
     return a;
 }
 
-// the packed guided step with one scalar step tag (tags NULL) or one tag per utterance (guided_tags.hip)
+// the packed guided step with one scalar step tag (per_utt false) or one tag per utterance, over the whole utterance or the window
+// that prompt_len and suffix_len (either may be NULL) leave; an entry that requires one of them refuses its NULL itself
 static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
                               const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const uint32_t* tags,
                               bool per_utt, const float* w, const float* a, const float* ce_in, const float* cz, int B, int S, int max_N,
                               int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                               size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
-                              const int32_t* prompt_len = nullptr, bool prompted = false, const RescaleReq* rs = nullptr,
-                              const int32_t* suffix_len = nullptr, bool windowed = false) {
+                              const int32_t* prompt_len = nullptr, const int32_t* suffix_len = nullptr,
+                              const RescaleReq* rs = nullptr) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (prompted && !prompt_len) return fail(DITTO_ERR_ARG, "%s: null prompt_len (int32 [B])", who);
-    if (windowed && !suffix_len) return fail(DITTO_ERR_ARG, "%s: null suffix_len (int32 [B])", who);
     if (rs)   // guidance rescale: the statistics between the forward and the update, the update then reads ce[b] s_b from the scratch
         if (int rc = check_rescale(who, x2, w, rs->phi, ce_in, nullptr, cu_speech, nullptr, B, 0, S, 0, max_N, m->cfg.hidden_dim,
                                    rs->scratch, rs->scratch_bytes))
@@ -1574,23 +1585,13 @@ static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const
         ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
         const float* ce = ce_in;
         if (rs) {
-            const RescaleArgs ra = rescale_args(eps, w, rs->phi, ce_in, nullptr, cu_speech, prompted ? prompt_len : nullptr, nullptr, B, 0,
+            const RescaleArgs ra = rescale_args(eps, w, rs->phi, ce_in, nullptr, cu_speech, prompt_len, nullptr, B, 0,
                                                 S, 0, m->cfg.hidden_dim, rs->scratch, rs->scratch_bytes);
             HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
             ce = ra.coef_out;
         }
-        if (windowed)
-            HIP_TRY(launch_guided_update_window(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, suffix_len,
-                                                B, S, max_N, m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
-        else if (prompted)
-            HIP_TRY(launch_guided_update_prompt(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, B, S, max_N,
-                                                m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
-        else if (per_utt)
-            HIP_TRY(launch_guided_update_packed_tags(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim,
-                                                     cfg != 0, (hipStream_t)stream));
-        else
-            HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, w, a, ce, cz, cu_speech, B, S, max_N, m->cfg.hidden_dim,
-                                                cfg != 0, (hipStream_t)stream));
+        HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, suffix_len, B,
+                                            S, max_N, m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
         return DITTO_OK;
     });
 }
@@ -1604,17 +1605,12 @@ int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, 
                               ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
 }
 
-// ---- continuous batching: per-utterance step tags (guided_tags.hip) and the device regroup (regroup_packed.hip) ----
+// ---- continuous batching: per-utterance step tags and the device regroup (regroup_packed.hip) ----
 int ditto_guided_update_packed_tags(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
                                     const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu, int B, int S,
                                     int max_N, int d, int cfg, ditto_stream_t stream) {
-    if (!cu) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_tags: null cu");
-    if (seeds && !tags) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_tags: seeds need tags (uint32 [B])");
-    if (int rc = check_guided_update("ditto_guided_update_packed_tags", x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
-    if (int rc = check_packed("ditto_guided_update_packed_tags", B, S, max_N, S, max_N)) return rc;
-    HIP_TRY(launch_guided_update_packed_tags(x2, eps2, noise, seeds, tags, w, a, ce, cz, cu, B, S, max_N, d, cfg != 0,
-                                             (hipStream_t)stream));
-    return DITTO_OK;
+    return guided_update_packed_checked("ditto_guided_update_packed_tags", x2, eps2, noise, seeds, 0, tags, true, w, a, ce, cz, cu, nullptr,
+                                        nullptr, B, S, max_N, d, cfg, stream);
 }
 
 int ditto_guided_step_packed_tags_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1626,32 +1622,21 @@ int ditto_guided_step_packed_tags_opts(ditto_model_t m, float* x2, const void* c
                               ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
 }
 
-// ---- speech prompts: the packed update and step that leave each utterance's first prompt_len[b] rows alone (guided_prompt.hip) ----
-static int guided_update_prompt(const char* who, float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
-                                const uint32_t* tags, bool per_utt, const float* w, const float* a, const float* ce, const float* cz,
-                                const int32_t* cu, const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg,
-                                ditto_stream_t stream) {
-    if (!cu || !prompt_len) return fail(DITTO_ERR_ARG, "%s: null cu / prompt_len", who);
-    if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
-    if (int rc = check_guided_update(who, x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
-    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
-    HIP_TRY(launch_guided_update_prompt(x2, eps2, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu, prompt_len, B, S, max_N, d, cfg != 0,
-                                        (hipStream_t)stream));
-    return DITTO_OK;
-}
-
+// ---- speech prompts: the packed update and step that leave each utterance's first prompt_len[b] rows alone ----
 int ditto_guided_update_packed_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
                                       const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                       const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
-    return guided_update_prompt("ditto_guided_update_packed_prompt", x2, eps2, noise, seeds, step, nullptr, false, w, a, ce, cz, cu,
-                                prompt_len, B, S, max_N, d, cfg, stream);
+    if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_prompt: null prompt_len");
+    return guided_update_packed_checked("ditto_guided_update_packed_prompt", x2, eps2, noise, seeds, step, nullptr, false, w, a, ce, cz,
+                                        cu, prompt_len, nullptr, B, S, max_N, d, cfg, stream);
 }
 
 int ditto_guided_update_packed_tags_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
                                            const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                            const int32_t* prompt_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
-    return guided_update_prompt("ditto_guided_update_packed_tags_prompt", x2, eps2, noise, seeds, 0, tags, true, w, a, ce, cz, cu,
-                                prompt_len, B, S, max_N, d, cfg, stream);
+    if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_tags_prompt: null prompt_len");
+    return guided_update_packed_checked("ditto_guided_update_packed_tags_prompt", x2, eps2, noise, seeds, 0, tags, true, w, a, ce, cz, cu,
+                                        prompt_len, nullptr, B, S, max_N, d, cfg, stream);
 }
 
 int ditto_guided_step_packed_prompt_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1659,9 +1644,10 @@ int ditto_guided_step_packed_prompt_opts(ditto_model_t m, float* x2, const void*
                                          uint32_t step, const float* w, const float* a, const float* ce, const float* cz, int B, int S,
                                          int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
                                          void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_prompt_opts: null prompt_len (int32 [B])");
     return guided_step_packed("ditto_guided_step_packed_prompt_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false,
                               w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len, true);
+                              prompt_len);
 }
 
 int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1670,9 +1656,10 @@ int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const 
                                               int B, int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos,
                                               const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
                                               const ditto_call_opts* opts) {
+    if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_tags_prompt_opts: null prompt_len (int32 [B])");
     return guided_step_packed("ditto_guided_step_packed_tags_prompt_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true,
                               w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len, true);
+                              prompt_len);
 }
 
 // ---- the second-order multistep solver over packed batches (guided_multistep.hip) ----
@@ -1688,23 +1675,30 @@ static int check_multistep(const char* who, const float* x2, const float* eps2, 
     return DITTO_OK;
 }
 
+static int multistep_update_checked(const char* who, float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
+                                    const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, const int32_t* prompt_len,
+                                    const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
+    if (int rc = check_multistep(who, x2, eps2, q, step, coefs, w, cu, B, max_N, d, cfg)) return rc;
+    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
+    HIP_TRY(launch_multistep_update_packed(x2, eps2, q, step, coefs, w, cu, prompt_len, suffix_len, B, S, max_N, d, cfg != 0,
+                                           (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 int ditto_multistep_update_packed(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
                                   const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, const int32_t* prompt_len,
                                   int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
-    if (int rc = check_multistep("ditto_multistep_update_packed", x2, eps2, q, step, coefs, w, cu, B, max_N, d, cfg)) return rc;
-    if (int rc = check_packed("ditto_multistep_update_packed", B, S, max_N, S, max_N)) return rc;
-    HIP_TRY(launch_multistep_update_packed(x2, eps2, q, step, coefs, w, cu, prompt_len, B, S, max_N, d, cfg != 0, (hipStream_t)stream));
-    return DITTO_OK;
+    return multistep_update_checked("ditto_multistep_update_packed", x2, eps2, q, step, coefs, w, cu, prompt_len, nullptr, B, S, max_N, d,
+                                    cfg, stream);
 }
 
 static int guided_step_multistep(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
                                  const int32_t* cu_text, const int32_t* prompt_len, float* q, const ditto_multistep_coef* step,
                                  const ditto_multistep_coef* coefs_in, const float* w, int B, int S, int max_N, int S_T, int max_T, int cfg,
                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
-                                 ditto_stream_t stream, const ditto_call_opts* opts, const RescaleReq* rs = nullptr,
-                                 const int32_t* suffix_len = nullptr, bool windowed = false) {
+                                 ditto_stream_t stream, const ditto_call_opts* opts, const int32_t* suffix_len = nullptr,
+                                 const RescaleReq* rs = nullptr) {
     if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (windowed && !suffix_len) return fail(DITTO_ERR_ARG, "%s: null suffix_len (int32 [B])", who);
     if (int rc = check_multistep(who, x2, x2, q, step, coefs_in, w, cu_speech, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
     if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
     if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
@@ -1728,12 +1722,8 @@ static int guided_step_multistep(const char* who, ditto_model_t m, float* x2, co
             HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
             coefs = (const ditto_multistep_coef*)rs->scratch;
         }
-        if (windowed)
-            HIP_TRY(launch_multistep_update_window(x2, eps, q, step, coefs, w, cu_speech, prompt_len, suffix_len, B, S, max_N,
-                                                   m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
-        else
-            HIP_TRY(launch_multistep_update_packed(x2, eps, q, step, coefs, w, cu_speech, prompt_len, B, S, max_N, m->cfg.hidden_dim,
-                                                   cfg != 0, (hipStream_t)stream));
+        HIP_TRY(launch_multistep_update_packed(x2, eps, q, step, coefs, w, cu_speech, prompt_len, suffix_len, B, S, max_N, m->cfg.hidden_dim,
+                                               cfg != 0, (hipStream_t)stream));
         return DITTO_OK;
     });
 }
@@ -1853,8 +1843,7 @@ int ditto_guided_step_packed_rescale_opts(ditto_model_t m, float* x2, const void
         return guided_step_mixed(who, m, x2, cond, t, cu_speech, cu_text, partner, prompt_len, noise, seeds, tags, w, a, ce, cz, B, G, S, S_G,
                                  max_N, S_T, max_T, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts, &rs);
     return guided_step_packed(who, m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, tags, tags != nullptr, w, a, ce, cz, B, S, max_N,
-                              S_T, max_T, 1, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts, prompt_len, prompt_len != nullptr,
-                              &rs);
+                              S_T, max_T, 1, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts, prompt_len, nullptr, &rs);
 }
 
 int ditto_guided_step_packed_multistep_rescale_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
@@ -1866,69 +1855,90 @@ int ditto_guided_step_packed_multistep_rescale_opts(ditto_model_t m, float* x2, 
     const RescaleReq rs{phi, scratch, scratch_bytes};
     return guided_step_multistep("ditto_guided_step_packed_multistep_rescale_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q,
                                  nullptr, coefs, nullptr, B, S, max_N, S_T, max_T, 1, rope_cos, rope_sin, workspace, workspace_bytes, stream,
-                                 opts, &rs);
+                                 opts, nullptr, &rs);
 }
 
-// ---- span-masked training over a packed batch with prompts (span_train.hip) ----
-static int check_span(const char* who, const void* in, const float* noise, const int64_t* seeds, const int32_t* cu,
-                      const int32_t* prompt_len, const void* out, int B, int S, int max_N, int d) {
-    if (!in || !out || !cu || !prompt_len) return fail(DITTO_ERR_ARG, "%s: null pointer", who);
+// ---- span-masked training over a packed batch (span_train.hip): the span behind a prompt, or a window with context on both sides ----
+static int check_span(const char* who, const void* in, const float* noise, const int64_t* seeds, const int32_t* cu, const void* out, int B,
+                      int S, int max_N, int d) {
+    if (!in || !out || !cu) return fail(DITTO_ERR_ARG, "%s: null pointer", who);
     if (!noise == !seeds) return fail(DITTO_ERR_ARG, "%s: exactly one of noise (a packed buffer) and seeds (Philox) is needed", who);
     if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
     return check_packed(who, B, S, max_N, S, max_N);
 }
 
+static int span_noise_checked(const char* who, const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca,
+                              const float* cs, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, float* x_in, int B,
+                              int S, int max_N, int d, ditto_stream_t stream) {
+    if (!ca || !cs) return fail(DITTO_ERR_ARG, "%s: null ca / cs", who);
+    if (int rc = check_span(who, x0, noise, seeds, cu, x_in, B, S, max_N, d)) return rc;
+    HIP_TRY(launch_span_noise_packed(x0, noise, seeds, tag, ca, cs, cu, prompt_len, suffix_len, x_in, B, S, max_N, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+static int span_mse_checked(const char* who, const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
+                            const int32_t* prompt_len, const int32_t* suffix_len, size_t n_elems, float* grad_eps, float* loss,
+                            void* workspace, size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream) {
+    if (!loss || !workspace) return fail(DITTO_ERR_ARG, "%s: null loss / workspace", who);
+    if (int rc = check_span(who, eps, noise, seeds, cu, grad_eps, B, S, max_N, d)) return rc;
+    if (n_elems == 0 || n_elems > (size_t)S * d) return fail(DITTO_ERR_SHAPE, "%s: n_elems must lie in [1, S d]", who);
+    if ((uintptr_t)workspace % 4 || workspace_bytes < span_mse_partials(B, max_N, d) * sizeof(float))
+        return fail(DITTO_ERR_SIZE, "%s: the workspace needs %zu bytes (B x min(1024, ceil(max_N d / 1024)) floats)", who,
+                    span_mse_partials(B, max_N, d) * sizeof(float));
+    HIP_TRY(launch_span_mse_packed(eps, noise, seeds, tag, cu, prompt_len, suffix_len, (double)n_elems, grad_eps, loss, (float*)workspace,
+                                   B, S, max_N, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 int ditto_span_noise_packed(const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca, const float* cs,
                             const int32_t* cu, const int32_t* prompt_len, float* x_in, int B, int S, int max_N, int d,
                             ditto_stream_t stream) {
-    if (!ca || !cs) return fail(DITTO_ERR_ARG, "ditto_span_noise_packed: null ca / cs");
-    if (int rc = check_span("ditto_span_noise_packed", x0, noise, seeds, cu, prompt_len, x_in, B, S, max_N, d)) return rc;
-    HIP_TRY(launch_span_noise_packed(x0, noise, seeds, tag, ca, cs, cu, prompt_len, x_in, B, S, max_N, d, (hipStream_t)stream));
-    return DITTO_OK;
+    if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_span_noise_packed: null prompt_len");
+    return span_noise_checked("ditto_span_noise_packed", x0, noise, seeds, tag, ca, cs, cu, prompt_len, nullptr, x_in, B, S, max_N, d,
+                              stream);
 }
 
 int ditto_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
                           const int32_t* prompt_len, size_t n_elems, float* grad_eps, float* loss, void* workspace,
                           size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream) {
-    if (!loss || !workspace) return fail(DITTO_ERR_ARG, "ditto_span_mse_packed: null loss / workspace");
-    if (int rc = check_span("ditto_span_mse_packed", eps, noise, seeds, cu, prompt_len, grad_eps, B, S, max_N, d)) return rc;
-    if (n_elems == 0 || n_elems > (size_t)S * d) return fail(DITTO_ERR_SHAPE, "ditto_span_mse_packed: n_elems must lie in [1, S d]");
-    if ((uintptr_t)workspace % 4 || workspace_bytes < span_mse_partials(B, max_N, d) * sizeof(float))
-        return fail(DITTO_ERR_SIZE, "ditto_span_mse_packed: the workspace needs %zu bytes (B x min(1024, ceil(max_N d / 1024)) floats)",
-                    span_mse_partials(B, max_N, d) * sizeof(float));
-    HIP_TRY(launch_span_mse_packed(eps, noise, seeds, tag, cu, prompt_len, (double)n_elems, grad_eps, loss, (float*)workspace, B, S, max_N,
-                                   d, (hipStream_t)stream));
-    return DITTO_OK;
+    if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_span_mse_packed: null prompt_len");
+    return span_mse_checked("ditto_span_mse_packed", eps, noise, seeds, tag, cu, prompt_len, nullptr, n_elems, grad_eps, loss, workspace,
+                            workspace_bytes, B, S, max_N, d, stream);
 }
 
-// ---- speech infilling: the update and step entries over the window [cu[b] + P_b, cu[b+1] - Q_b) (guided_window.hip, span_window.hip) ----
-static int guided_update_window(const char* who, float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
-                                const uint32_t* tags, bool per_utt, const float* w, const float* a, const float* ce, const float* cz,
-                                const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d,
-                                int cfg, ditto_stream_t stream) {
-    if (!cu || !suffix_len) return fail(DITTO_ERR_ARG, "%s: null cu / suffix_len", who);
-    if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
-    if (int rc = check_guided_update(who, x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, cfg)) return rc;
-    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
-    HIP_TRY(launch_guided_update_window(x2, eps2, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu, prompt_len, suffix_len, B, S, max_N,
-                                        d, cfg != 0, (hipStream_t)stream));
-    return DITTO_OK;
+int ditto_span_noise_window(const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca, const float* cs,
+                            const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, float* x_in, int B, int S,
+                            int max_N, int d, ditto_stream_t stream) {
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_span_noise_window: null suffix_len");
+    return span_noise_checked("ditto_span_noise_window", x0, noise, seeds, tag, ca, cs, cu, prompt_len, suffix_len, x_in, B, S, max_N, d,
+                              stream);
 }
 
+int ditto_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
+                          const int32_t* prompt_len, const int32_t* suffix_len, size_t n_elems, float* grad_eps, float* loss,
+                          void* workspace, size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream) {
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_span_mse_window: null suffix_len");
+    return span_mse_checked("ditto_span_mse_window", eps, noise, seeds, tag, cu, prompt_len, suffix_len, n_elems, grad_eps, loss, workspace,
+                            workspace_bytes, B, S, max_N, d, stream);
+}
+
+// ---- speech infilling: the update and step entries over the window [cu[b] + P_b, cu[b+1] - Q_b) ----
 int ditto_guided_update_packed_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
                                       const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                       const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg,
                                       ditto_stream_t stream) {
-    return guided_update_window("ditto_guided_update_packed_window", x2, eps2, noise, seeds, step, nullptr, false, w, a, ce, cz, cu,
-                                prompt_len, suffix_len, B, S, max_N, d, cfg, stream);
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_window: null suffix_len");
+    return guided_update_packed_checked("ditto_guided_update_packed_window", x2, eps2, noise, seeds, step, nullptr, false, w, a, ce, cz,
+                                        cu, prompt_len, suffix_len, B, S, max_N, d, cfg, stream);
 }
 
 int ditto_guided_update_packed_tags_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const uint32_t* tags,
                                            const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                            const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg,
                                            ditto_stream_t stream) {
-    return guided_update_window("ditto_guided_update_packed_tags_window", x2, eps2, noise, seeds, 0, tags, true, w, a, ce, cz, cu,
-                                prompt_len, suffix_len, B, S, max_N, d, cfg, stream);
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_update_packed_tags_window: null suffix_len");
+    return guided_update_packed_checked("ditto_guided_update_packed_tags_window", x2, eps2, noise, seeds, 0, tags, true, w, a, ce, cz, cu,
+                                        prompt_len, suffix_len, B, S, max_N, d, cfg, stream);
 }
 
 int ditto_guided_step_packed_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1937,9 +1947,10 @@ int ditto_guided_step_packed_window_opts(ditto_model_t m, float* x2, const void*
                                          const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
                                          const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                                          ditto_stream_t stream, const ditto_call_opts* opts) {
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_window_opts: null suffix_len (int32 [B])");
     return guided_step_packed("ditto_guided_step_packed_window_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false,
                               w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len, false, nullptr, suffix_len, true);
+                              prompt_len, suffix_len);
 }
 
 int ditto_guided_step_packed_tags_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1948,20 +1959,18 @@ int ditto_guided_step_packed_tags_window_opts(ditto_model_t m, float* x2, const 
                                               const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T,
                                               int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                                               size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_tags_window_opts: null suffix_len (int32 [B])");
     return guided_step_packed("ditto_guided_step_packed_tags_window_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true,
                               w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len, false, nullptr, suffix_len, true);
+                              prompt_len, suffix_len);
 }
 
 int ditto_multistep_update_window(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
                                   const ditto_multistep_coef* coefs, const float* w, const int32_t* cu, const int32_t* prompt_len,
                                   const int32_t* suffix_len, int B, int S, int max_N, int d, int cfg, ditto_stream_t stream) {
     if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_multistep_update_window: null suffix_len");
-    if (int rc = check_multistep("ditto_multistep_update_window", x2, eps2, q, step, coefs, w, cu, B, max_N, d, cfg)) return rc;
-    if (int rc = check_packed("ditto_multistep_update_window", B, S, max_N, S, max_N)) return rc;
-    HIP_TRY(launch_multistep_update_window(x2, eps2, q, step, coefs, w, cu, prompt_len, suffix_len, B, S, max_N, d, cfg != 0,
-                                           (hipStream_t)stream));
-    return DITTO_OK;
+    return multistep_update_checked("ditto_multistep_update_window", x2, eps2, q, step, coefs, w, cu, prompt_len, suffix_len, B, S, max_N,
+                                    d, cfg, stream);
 }
 
 int ditto_guided_step_packed_multistep_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
@@ -1970,41 +1979,10 @@ int ditto_guided_step_packed_multistep_window_opts(ditto_model_t m, float* x2, c
                                                    const ditto_multistep_coef* coefs, const float* w, int B, int S, int max_N, int S_T,
                                                    int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                                                    size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_multistep_window_opts: null suffix_len (int32 [B])");
     return guided_step_multistep("ditto_guided_step_packed_multistep_window_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q, step,
                                  coefs, w, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                                 nullptr, suffix_len, true);
-}
-
-static int check_span_window(const char* who, const void* in, const float* noise, const int64_t* seeds, const int32_t* cu,
-                             const int32_t* suffix_len, const void* out, int B, int S, int max_N, int d) {
-    if (!in || !out || !cu || !suffix_len) return fail(DITTO_ERR_ARG, "%s: null pointer", who);
-    if (!noise == !seeds) return fail(DITTO_ERR_ARG, "%s: exactly one of noise (a packed buffer) and seeds (Philox) is needed", who);
-    if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
-    return check_packed(who, B, S, max_N, S, max_N);
-}
-
-int ditto_span_noise_window(const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca, const float* cs,
-                            const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, float* x_in, int B, int S,
-                            int max_N, int d, ditto_stream_t stream) {
-    if (!ca || !cs) return fail(DITTO_ERR_ARG, "ditto_span_noise_window: null ca / cs");
-    if (int rc = check_span_window("ditto_span_noise_window", x0, noise, seeds, cu, suffix_len, x_in, B, S, max_N, d)) return rc;
-    HIP_TRY(launch_span_noise_window(x0, noise, seeds, tag, ca, cs, cu, prompt_len, suffix_len, x_in, B, S, max_N, d,
-                                     (hipStream_t)stream));
-    return DITTO_OK;
-}
-
-int ditto_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
-                          const int32_t* prompt_len, const int32_t* suffix_len, size_t n_elems, float* grad_eps, float* loss,
-                          void* workspace, size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream) {
-    if (!loss || !workspace) return fail(DITTO_ERR_ARG, "ditto_span_mse_window: null loss / workspace");
-    if (int rc = check_span_window("ditto_span_mse_window", eps, noise, seeds, cu, suffix_len, grad_eps, B, S, max_N, d)) return rc;
-    if (n_elems == 0 || n_elems > (size_t)S * d) return fail(DITTO_ERR_SHAPE, "ditto_span_mse_window: n_elems must lie in [1, S d]");
-    if ((uintptr_t)workspace % 4 || workspace_bytes < span_mse_partials(B, max_N, d) * sizeof(float))
-        return fail(DITTO_ERR_SIZE, "ditto_span_mse_window: the workspace needs %zu bytes (B x min(1024, ceil(max_N d / 1024)) floats)",
-                    span_mse_partials(B, max_N, d) * sizeof(float));
-    HIP_TRY(launch_span_mse_window(eps, noise, seeds, tag, cu, prompt_len, suffix_len, (double)n_elems, grad_eps, loss, (float*)workspace,
-                                   B, S, max_N, d, (hipStream_t)stream));
-    return DITTO_OK;
+                                 suffix_len);
 }
 
 int ditto_regroup_packed(const ditto_regroup_seg* table, int n_seg, const void* const* src, const size_t* src_bytes, void* const* dst,

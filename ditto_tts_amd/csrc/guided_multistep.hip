@@ -1,7 +1,6 @@
 // guided_multistep.hip — the packed guided update of the second-order multistep data-prediction solver, DPM-Solver++(2M) (Lu et al.
 // 2022), for gfx950.  One forward per step like the strided (DDIM) update; the extra state is the previous step's x0 prediction per
-// generated row, kept in a second fp32 buffer q [S, d].  Kernels of their own over guided_update.h's spans and grid, so that
-// guided.hip, guided_packed.hip, guided_tags.hip and guided_prompt.hip keep their machine code.
+// generated row, kept in a second fp32 buffer q [S, d].  Over guided_update.h's span and grid, like guided_packed.hip.
 //   e  = CFG ? fmaf(w, c - u, u) : c                       (guided_update.h's expression)
 //   x0 = fmaf(kx, x, ke * e)                               the data prediction: kx = 1 / alpha, ke = -sigma / alpha
 //   x' = fmaf(a, x, fmaf(b, x0, use_prev ? g * q : 0))     written to the conditional and, under CFG, the unconditional half of x2
@@ -42,39 +41,43 @@ __device__ __forceinline__ void multistep_rows(f32x4* xc, f32x4* xu, const f32x4
 // PER_UTT false: every utterance stands at the step `step` (a kernel argument; its w is not used: w[b] is the guidance scale).
 // PER_UTT true: utterance b at coefs[b], guidance scale included (a request stream: each utterance at its own index of its own
 // schedule).  b = blockIdx.y is uniform over the workgroup: the block comes in through scalar loads and the use_prev branch is
-// uniform.  prompt_len NULL: no prompts; else the rows [cu[b], cu[b] + P_b) of x2, eps2 and q are neither read nor written.
+// uniform.  The update runs over window_span's window [cu[b] + P_b, cu[b+1] - Q_b) (prompt_len, suffix_len: either may be NULL): the
+// clean context rows of x2, eps2 and q are neither read nor written, on either side.
 template <bool CFG, bool PER_UTT>
 __global__ __launch_bounds__(256) void multistep_update_kernel(float* __restrict__ x2, const float* __restrict__ eps2,
                                                                float* __restrict__ q, ditto_multistep_coef step,
                                                                const ditto_multistep_coef* __restrict__ coefs,
                                                                const float* __restrict__ w, const int32_t* __restrict__ cu,
-                                                               const int32_t* __restrict__ prompt_len, int S, int d) {
+                                                               const int32_t* __restrict__ prompt_len,
+                                                               const int32_t* __restrict__ suffix_len, int S, int d) {
     const int b = blockIdx.y;
-    const GuidedSpan sp = generated_span(cu, prompt_len, b, S, d);      // (guided_update.h) the rows [cu[b] + P_b, cu[b+1])
+    const WindowSpan ws = window_span(cu, prompt_len, suffix_len, b, S, d);     // (guided_update.h)
+    const size_t base4 = ws.base4 + ws.p4;
     ditto_multistep_coef k = step;
     if (PER_UTT) k = coefs[b];
     else k.w = CFG ? w[b] : 0.f;
     const size_t half4 = (size_t)S * d / 4;
-    f32x4* xc = reinterpret_cast<f32x4*>(x2) + sp.base4;
-    const f32x4* ec = reinterpret_cast<const f32x4*>(eps2) + sp.base4;
-    f32x4* qp = reinterpret_cast<f32x4*>(q) + sp.base4;
+    f32x4* xc = reinterpret_cast<f32x4*>(x2) + base4;
+    const f32x4* ec = reinterpret_cast<const f32x4*>(eps2) + base4;
+    f32x4* qp = reinterpret_cast<f32x4*>(q) + base4;
     const size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
     if (k.use_prev)
-        multistep_rows<CFG, true>(xc, xc + half4, ec, ec + half4, qp, k, sp.n4, i0, stride);
+        multistep_rows<CFG, true>(xc, xc + half4, ec, ec + half4, qp, k, ws.g4, i0, stride);
     else
-        multistep_rows<CFG, false>(xc, xc + half4, ec, ec + half4, qp, k, sp.n4, i0, stride);
+        multistep_rows<CFG, false>(xc, xc + half4, ec, ec + half4, qp, k, ws.g4, i0, stride);
 }
 
 hipError_t launch_multistep_update_packed(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
                                           const ditto_multistep_coef* coefs, const float* w, const int32_t* cu,
-                                          const int32_t* prompt_len, int B, int S, int max_N, int d, bool cfg, hipStream_t s) {
+                                          const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, bool cfg,
+                                          hipStream_t s) {
     if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !q || !step == !coefs || (step && cfg && !w))
         return hipErrorInvalidValue;
     const dim3 grid = guided_grid(max_N, d, B);
     const ditto_multistep_coef none = {};
     auto go = [&](auto cf, auto pu) {
         hipLaunchKernelGGL((multistep_update_kernel<decltype(cf)::value, decltype(pu)::value>), grid, dim3(256), 0, s, x2, eps2, q,
-                           step ? *step : none, coefs, w, cu, prompt_len, S, d);
+                           step ? *step : none, coefs, w, cu, prompt_len, suffix_len, S, d);
     };
     if (cfg) coefs ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
     else coefs ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});

@@ -1,4 +1,5 @@
-// guided_update.h — the one source of the fused guided (DDIM) update of guided.hip, guided_packed.hip and guided_tags.hip.
+// guided_update.h — the one source of the fused guided (DDIM) update of guided.hip and guided_packed.hip, and of the spans of every
+// packed update, multistep and span-training kernel.
 //   e' = CFG ? fmaf(w[b], c - u, u) : c               c, u = the conditional / unconditional half of eps2 (cfg_combine_kernel's expression)
 //   x' = fmaf(a[b], x, fmaf(ce[b], e', cz[b] * z))    (linear_update_kernel's; z = cz = 0 without noise)
 // written to the conditional and, under CFG, the unconditional half of x2.  NOISE: 0 none, 1 a buffer laid out like x, 2 Philox of
@@ -19,56 +20,56 @@ __device__ __forceinline__ GuidedCoef guided_coef(const float* a, const float* c
     return {a[b], ce[b], NOISE ? cz[b] : 0.f, CFG ? w[b] : 0.f, NOISE == 2 ? (unsigned long long)seeds[b] : 0ull};
 }
 
-// utterance b's rows [cu[b], cu[b+1]) of a packed [S, d] buffer, clamped like attn_span (never outside the S rows, at least one row)
-struct GuidedSpan { size_t base4, n4; };
-__device__ __forceinline__ GuidedSpan guided_span(const int32_t* cu, int b, int S, int d) {
+// utterance b's rows [cu[b], cu[b+1]) of a packed [S, d] buffer, clamped like attn_span: r0 into [0, S - 1], nb into [1, S - r0] (never
+// outside the S rows, at least one row)
+struct UttRows { int r0, nb; };
+__device__ __forceinline__ UttRows utt_rows(const int32_t* cu, int b, int S) {
     int r0 = cu[b];
     r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
     const int n = cu[b + 1] - r0, nb = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);
-    return {(size_t)r0 * d / 4, (size_t)nb * d / 4};
+    return {r0, nb};
 }
 
-// guided_span plus a speech prompt: the first prompt_len[b] rows of the utterance are clean latents.  p4 = the quad where the generated
-// rows begin, P_b clamped into [0, n_b - 1]: a bad prompt length gives wrong rows, never an access outside the utterance's own
-struct PromptSpan { size_t base4, n4, p4; };
-__device__ __forceinline__ PromptSpan prompt_span(const int32_t* cu, const int32_t* prompt_len, int b, int S, int d) {
-    int r0 = cu[b];
-    r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
-    const int n = cu[b + 1] - r0, nb = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);
-    int p = prompt_len[b];
-    p = p < 0 ? 0 : (p > nb - 1 ? nb - 1 : p);
-    return {(size_t)r0 * d / 4, (size_t)nb * d / 4, (size_t)p * d / 4};
-}
-
-// the generated rows of utterance b, [cu[b] + P_b, cu[b+1]) (prompt_len NULL: the whole utterance): what the multistep update and the
-// guidance-rescale statistics run over
-__device__ __forceinline__ GuidedSpan generated_span(const int32_t* cu, const int32_t* prompt_len, int b, int S, int d) {
-    if (prompt_len) {
-        const PromptSpan ps = prompt_span(cu, prompt_len, b, S, d);
-        return {ps.base4 + ps.p4, ps.n4 - ps.p4};
-    }
-    return guided_span(cu, b, S, d);
-}
-
-// prompt_span plus a clean SUFFIX (speech infilling): the last suffix_len[b] rows of the utterance are clean latents too, and the rows
-// in between, [cu[b] + P_b, cu[b+1] - Q_b), are the generated window: g4 quads from quad p4 on.  P_b clamped into [0, n_b - 1] like
-// prompt_span's (prompt_len NULL: 0), Q_b into [0, n_b - 1 - P_b]: at least one row is generated, and a bad value gives wrong rows,
-// never an access outside the utterance's own.  Q_b = 0 is prompt_span: p4 + g4 == n4 (guided_window.hip, span_window.hip)
+// The one span of the packed update, multistep and span-training kernels: utterance b with a clean speech PROMPT of prompt_len[b] rows
+// in front and a clean SUFFIX of suffix_len[b] rows behind (speech infilling); the rows in between, [cu[b] + P_b, cu[b+1] - Q_b), are
+// the generated window: g4 quads from quad p4 on, of the utterance's n4 from quad base4 on.  Either pointer may be NULL: 0 rows.  P_b
+// is clamped into [0, n_b - 1], then Q_b into [0, n_b - 1 - P_b]: at least one row is generated, and a bad value gives wrong rows, never
+// an access outside the utterance's own.  b = blockIdx.y is uniform over the workgroup, so cu, P_b and Q_b come in through scalar loads
+// and the NULL tests are scalar branches.
+//
+// P and Q are run-time values and TAGS is a template parameter, for one reason each.  A NULL length and a length of 0 give the same
+// span, so one kernel serves the unprompted, prompted and windowed entries bit for bit, at two scalar loads per workgroup.  The
+// per-utterance tag form is not such a special case of the scalar one: it skips the Philox draw of an utterance whose cz is 0 and adds
+// cz * 0 = +0 where the scalar form adds cz * z = 0 * z, a zero of z's sign, and fmaf carries that sign into a result that is itself 0.
+// So the two forms differ in bits and stay two instantiations.
 struct WindowSpan { size_t base4, n4, p4, g4; };
 __device__ __forceinline__ WindowSpan window_span(const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int b, int S,
                                                   int d) {
-    int r0 = cu[b];
-    r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
-    const int n = cu[b + 1] - r0, nb = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);
+    const UttRows u = utt_rows(cu, b, S);
     int p = prompt_len ? prompt_len[b] : 0;
-    p = p < 0 ? 0 : (p > nb - 1 ? nb - 1 : p);
-    int q = suffix_len[b];
-    q = q < 0 ? 0 : (q > nb - 1 - p ? nb - 1 - p : q);
-    return {(size_t)r0 * d / 4, (size_t)nb * d / 4, (size_t)p * d / 4, (size_t)(nb - p - q) * d / 4};
+    p = p < 0 ? 0 : (p > u.nb - 1 ? u.nb - 1 : p);
+    int q = suffix_len ? suffix_len[b] : 0;
+    q = q < 0 ? 0 : (q > u.nb - 1 - p ? u.nb - 1 - p : q);
+    return {(size_t)u.r0 * d / 4, (size_t)u.nb * d / 4, (size_t)p * d / 4, (size_t)(u.nb - p - q) * d / 4};
+}
+
+// the generated rows of utterance b without a suffix, [cu[b] + P_b, cu[b+1]) (prompt_len NULL: the whole utterance): what the
+// guidance-rescale statistics run over (guided_rescale.hip, which is held to its machine code: window_span's g4 is another expression)
+struct GuidedSpan { size_t base4, n4; };
+__device__ __forceinline__ GuidedSpan generated_span(const int32_t* cu, const int32_t* prompt_len, int b, int S, int d) {
+    if (prompt_len) {
+        const UttRows u = utt_rows(cu, b, S);
+        int p = prompt_len[b];
+        p = p < 0 ? 0 : (p > u.nb - 1 ? u.nb - 1 : p);
+        const size_t base4 = (size_t)u.r0 * d / 4, n4 = (size_t)u.nb * d / 4, p4 = (size_t)p * d / 4;
+        return {base4 + p4, n4 - p4};
+    }
+    const UttRows u = utt_rows(cu, b, S);
+    return {(size_t)u.r0 * d / 4, (size_t)u.nb * d / 4};
 }
 
 // utterance b of a step in which G of the B utterances are guided (guided_mixed.hip): its generated rows and, with a partner, the
-// same rows of its unconditional copy behind row S.  Clamps: guided_span's and prompt_span's; the partner into [-1, G - 1]; the copy's
+// same rows of its unconditional copy behind row S.  Clamps: utt_rows' and window_span's of P_b; the partner into [-1, G - 1]; the copy's
 // span has b's own length n_b, its first row clamped into [S, S + S_G - n_b] (no copy at all when n_b > S_G: g = -1).  The offset
 // cu[B + g + 1] is not read.  Statement for statement the head of guided_update_mixed_kernel, which keeps its own text: routed through
 // this helper its scalar instructions come out in another order, and that kernel is held to its machine code
@@ -79,7 +80,7 @@ __device__ __forceinline__ MixedSpan mixed_span(const int32_t* cu, const int32_t
     int r0 = cu[b];
     r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
     int n = cu[b + 1] - r0;
-    n = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);                      // guided_span's clamp
+    n = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);                      // utt_rows' clamp
     int g = partner[b];
     g = g < -1 ? -1 : (g > G - 1 ? G - 1 : g);
     int u0 = 0;
@@ -89,7 +90,7 @@ __device__ __forceinline__ MixedSpan mixed_span(const int32_t* cu, const int32_t
         u0 = u0 < S ? S : (u0 > S + S_G - n ? S + S_G - n : u0);
     }
     int p = prompt_len ? prompt_len[b] : 0;
-    p = p < 0 ? 0 : (p > n - 1 ? n - 1 : p);                        // prompt_span's clamp
+    p = p < 0 ? 0 : (p > n - 1 ? n - 1 : p);                        // window_span's clamp of P_b
     const size_t d4 = (size_t)d / 4;
     return {(size_t)(r0 + p) * d4, (size_t)(n - p) * d4, u0 + p, g};
 }

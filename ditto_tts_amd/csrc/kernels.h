@@ -262,30 +262,25 @@ hipError_t launch_cfg_combine(const float* eps2, float* out, float w, size_t ele
 hipError_t launch_guided_update(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
                                 const float* w, const float* a, const float* ce, const float* cz, const int32_t* speech_len,
                                 int B, int N, int d, bool cfg, hipStream_t s);
+// ---------------- guided_packed.hip ----------------
 // packed batch: x2, eps2 [S, d] (CFG: [2S, d] = [conditional; unconditional]); utterance b owns rows [cu[b], cu[b+1]) of each half.
-// The same expressions as launch_guided_update; Philox quad index = the utterance-local one, ((row - cu[b]) d + col) / 4.
+// The same expressions as launch_guided_update over the window [cu[b] + P_b, cu[b+1] - Q_b): prompt_len, suffix_len device int32 [B],
+// either may be null (0 rows), P_b clamped into [0, n_b - 1], then Q_b into [0, n_b - 1 - P_b]; the context rows of x2, eps2 and a
+// noise buffer are neither read nor written.  Philox quad index = the window-local one, ((row - cu[b] - P_b) d + col) / 4, at the
+// scalar `step` (per_utt false) or at tags[b] (per_utt true: device uint32 [B]; an utterance with cz[b] == 0 gets the no-noise
+// instantiation's value)
 hipError_t launch_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
-                                       const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
-                                       int B, int S, int max_N, int d, bool cfg, hipStream_t s);
-// ---------------- guided_tags.hip ----------------
-// launch_guided_update_packed with the Philox step tag of utterance b read from tags[b] (device uint32 [B]); an utterance with
-// cz[b] == 0 gets the no-noise instantiation's value
-hipError_t launch_guided_update_packed_tags(float* x2, const float* eps2, const float* noise, const int64_t* seeds,
-                                            const unsigned* tags, const float* w, const float* a, const float* ce, const float* cz,
-                                            const int32_t* cu, int B, int S, int max_N, int d, bool cfg, hipStream_t s);
-// ---------------- guided_prompt.hip ----------------
-// launch_guided_update_packed (per_utt false) / launch_guided_update_packed_tags (per_utt true) over the rows behind each utterance's
-// speech prompt: prompt_len device int32 [B], clamped into [0, n_b - 1]; the prompt rows of x2 and eps2 are neither read nor written
-hipError_t launch_guided_update_prompt(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
                                        const unsigned* tags, bool per_utt, const float* w, const float* a, const float* ce,
-                                       const float* cz, const int32_t* cu, const int32_t* prompt_len, int B, int S, int max_N, int d,
-                                       bool cfg, hipStream_t s);
+                                       const float* cz, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
+                                       int S, int max_N, int d, bool cfg, hipStream_t s);
 // ---------------- guided_multistep.hip ----------------
 // the DPM-Solver++(2M) update over a packed batch: `step` (host: one step for every utterance, guidance scale w[b]) or `coefs`
-// (device [B]: utterance b's own step and scale); q fp32 [S, d] holds the previous step's x0 prediction; prompt_len may be null
+// (device [B]: utterance b's own step and scale); q fp32 [S, d] holds the previous step's x0 prediction; over the window of
+// launch_guided_update_packed (prompt_len, suffix_len: either may be null)
 hipError_t launch_multistep_update_packed(float* x2, const float* eps2, float* q, const ::ditto_multistep_coef* step,
                                           const ::ditto_multistep_coef* coefs, const float* w, const int32_t* cu,
-                                          const int32_t* prompt_len, int B, int S, int max_N, int d, bool cfg, hipStream_t s);
+                                          const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, bool cfg,
+                                          hipStream_t s);
 // ---------------- guided_mixed.hip ----------------
 // the per-utterance-tag update of a batch in which G of the B utterances are guided at this step: x2, eps2 [S + S_G, d], the guided
 // ones' unconditional copies compacted in rows [S, S + S_G); cu device int32 [B + G + 1] = [cu; S + cu_G[1:]]; partner device int32
@@ -295,32 +290,14 @@ hipError_t launch_guided_update_mixed(float* x2, const float* eps2, const float*
                                       const int32_t* partner, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,
                                       hipStream_t s);
 // ---------------- span_train.hip ----------------
-// span-masked training over a packed batch with prompts: the noising that keeps the prompt rows, the MSE over the generated rows
-// (n_elems of them) with its gradient; `partial`: span_mse_partials(B, max_N, d) floats
+// span-masked training over a packed batch: the noising that keeps the context rows (a bit copy of x0), the MSE over the generated
+// rows (n_elems of them) with its gradient (exactly 0 on the context rows); the window of launch_guided_update_packed (prompt_len,
+// suffix_len: either may be null); `partial`: span_mse_partials(B, max_N, d) floats
 size_t span_mse_partials(int B, int max_N, int d);
 hipError_t launch_span_noise_packed(const float* x0, const float* noise, const int64_t* seeds, unsigned tag, const float* ca,
-                                    const float* cs, const int32_t* cu, const int32_t* prompt_len, float* x_in, int B, int S, int max_N,
-                                    int d, hipStream_t s);
-hipError_t launch_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
-                                  const int32_t* prompt_len, double n_elems, float* grad, float* loss, float* partial, int B, int S,
-                                  int max_N, int d, hipStream_t s);
-hipError_t launch_span_mse_finish(const float* partial, size_t n_partial, float inv_n, float* loss, hipStream_t s);
-// ---------------- guided_window.hip, span_window.hip ----------------
-// speech infilling: the prompt / multistep / span launches over the window [cu[b] + P_b, cu[b+1] - Q_b) — suffix_len device int32 [B]
-// (required), Q_b clamped into [0, n_b - 1 - P_b]; prompt_len may be null (P = 0).  The context rows on both sides are neither read
-// nor written by the updates; the span kernels copy x0 / write a zero gradient there.  suffix_len all 0: the counterpart's bits
-hipError_t launch_guided_update_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,
-                                       const unsigned* tags, bool per_utt, const float* w, const float* a, const float* ce,
-                                       const float* cz, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
-                                       int S, int max_N, int d, bool cfg, hipStream_t s);
-hipError_t launch_multistep_update_window(float* x2, const float* eps2, float* q, const ::ditto_multistep_coef* step,
-                                          const ::ditto_multistep_coef* coefs, const float* w, const int32_t* cu,
-                                          const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, bool cfg,
-                                          hipStream_t s);
-hipError_t launch_span_noise_window(const float* x0, const float* noise, const int64_t* seeds, unsigned tag, const float* ca,
                                     const float* cs, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len,
                                     float* x_in, int B, int S, int max_N, int d, hipStream_t s);
-hipError_t launch_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
+hipError_t launch_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
                                   const int32_t* prompt_len, const int32_t* suffix_len, double n_elems, float* grad, float* loss,
                                   float* partial, int B, int S, int max_N, int d, hipStream_t s);
 // ---------------- guided_rescale.hip ----------------

@@ -1,6 +1,9 @@
-// span_train.hip — span-masked training on a packed batch with speech prompts (gfx950): the forward diffusion that leaves each
-// utterance's prompt rows clean, and the MSE over the generated rows with its gradient.  Elementwise, 16-byte lane accesses, grid
-// (chunks, B) like the guided kernels; no atomics: the loss is reduced through per-workgroup partials summed in index order.
+// span_train.hip — span-masked training on a packed batch (gfx950): the forward diffusion that leaves each utterance's context rows
+// clean, and the MSE over the generated rows with its gradient.  The span is window_span's window [cu[b] + P_b, cu[b+1] - Q_b)
+// (guided_update.h; prompt_len, suffix_len: either may be NULL): a speech prompt in front, and for infilling objectives clean context
+// behind as well.  Both kernels walk the WHOLE utterance, so the lane-to-quad assignment, the partial layout and the reduction tree,
+// and with them the loss's bits, do not depend on where the window lies.  Elementwise, 16-byte lane accesses, grid (chunks, B) like
+// the guided kernels; no atomics: the loss is reduced through per-workgroup partials summed in index order.
 #include "common.h"
 #include "guided_update.h"
 #include "kernels.h"
@@ -8,17 +11,18 @@
 
 namespace ditto {
 
-// x_in = x0 on the prompt rows (a bit copy), fmaf(ca[b], x0, cs[b] z) on the generated rows.  z: the packed buffer `noise` [S, d]
-// (its prompt rows are never read), or SEEDED Philox of (seeds[b], tag) at the generated-local quad index — ditto_noise_normal's
+// x_in = x0 on the context rows (a bit copy), fmaf(ca[b], x0, cs[b] z) on the generated rows.  z: the packed buffer `noise` [S, d]
+// (its context rows are never read), or SEEDED Philox of (seeds[b], tag) at the window-local quad index i - p4 — ditto_noise_normal's
 // numbers for an utterance of G_b rows.  8 B per element seeded, 12 B with a buffer.
 template <bool SEEDED>
 __global__ __launch_bounds__(256) void span_noise_packed_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
                                                                 const int64_t* __restrict__ seeds, unsigned tag,
                                                                 const float* __restrict__ ca, const float* __restrict__ cs,
                                                                 const int32_t* __restrict__ cu, const int32_t* __restrict__ prompt_len,
-                                                                float* __restrict__ x_in, int S, int d) {
+                                                                const int32_t* __restrict__ suffix_len, float* __restrict__ x_in, int S,
+                                                                int d) {
     const int b = blockIdx.y;
-    const PromptSpan r = prompt_span(cu, prompt_len, b, S, d);
+    const WindowSpan r = window_span(cu, prompt_len, suffix_len, b, S, d);
     const float a = ca[b], s = cs[b];
     const unsigned long long seed = SEEDED ? (unsigned long long)seeds[b] : 0ull;
     const f32x4* xp = reinterpret_cast<const f32x4*>(x0) + r.base4;
@@ -27,7 +31,7 @@ __global__ __launch_bounds__(256) void span_noise_packed_kernel(const float* __r
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < r.n4; i += stride) {
         f32x4 o = xp[i];
-        if (i >= r.p4) {
+        if (i - r.p4 < r.g4) {                        // p4 <= i < p4 + g4, in one unsigned compare
             const f32x4 z = SEEDED ? normal4(seed, tag, i - r.p4) : zp[i];
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = fmaf(a, o[e], s * z[e]);
@@ -36,18 +40,18 @@ __global__ __launch_bounds__(256) void span_noise_packed_kernel(const float* __r
     }
 }
 
-// grad_eps = scale2 (eps - z) on the generated rows, exactly 0 on the prompt rows (eps is not read there); partial[b gridDim.x +
+// grad_eps = scale2 (eps - z) on the generated rows, exactly 0 on the context rows (eps is not read there); partial[b gridDim.x +
 // blockIdx.x] = this workgroup's sum of (eps - z)^2, lanes in a fixed tree.  z as in span_noise_packed_kernel: SEEDED, the noise is
 // regenerated and never exists in memory (eps read, grad written: 8 B per element).
 template <bool SEEDED>
 __global__ __launch_bounds__(256) void span_mse_packed_kernel(const float* __restrict__ eps, const float* __restrict__ noise,
                                                               const int64_t* __restrict__ seeds, unsigned tag,
                                                               const int32_t* __restrict__ cu, const int32_t* __restrict__ prompt_len,
-                                                              float scale2, float* __restrict__ grad, float* __restrict__ partial, int S,
-                                                              int d) {
+                                                              const int32_t* __restrict__ suffix_len, float scale2,
+                                                              float* __restrict__ grad, float* __restrict__ partial, int S, int d) {
     __shared__ float red[256];
     const int b = blockIdx.y;
-    const PromptSpan r = prompt_span(cu, prompt_len, b, S, d);
+    const WindowSpan r = window_span(cu, prompt_len, suffix_len, b, S, d);
     const unsigned long long seed = SEEDED ? (unsigned long long)seeds[b] : 0ull;
     const f32x4* ep = reinterpret_cast<const f32x4*>(eps) + r.base4;
     const f32x4* zp = reinterpret_cast<const f32x4*>(noise) + r.base4;
@@ -56,7 +60,7 @@ __global__ __launch_bounds__(256) void span_mse_packed_kernel(const float* __res
     float acc = 0.f;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < r.n4; i += stride) {
         f32x4 g = {0.f, 0.f, 0.f, 0.f};
-        if (i >= r.p4) {
+        if (i - r.p4 < r.g4) {                        // p4 <= i < p4 + g4, in one unsigned compare
 #pragma clang fp contract(off)      // eps - z must not fuse with the Box-Muller product r cos: the seeded mode gives the buffer mode's bits
             const f32x4 e = ep[i];
             const f32x4 z = SEEDED ? normal4(seed, tag, i - r.p4) : zp[i];
@@ -97,38 +101,32 @@ __global__ __launch_bounds__(256) void span_mse_finish_kernel(const float* __res
 
 size_t span_mse_partials(int B, int max_N, int d) { return (size_t)B * guided_grid(max_N, d, B).x; }
 
-// span_mse_finish_kernel for the other files' partials (span_window.hip): a kernel is launched from the file that defines it
-hipError_t launch_span_mse_finish(const float* partial, size_t n_partial, float inv_n, float* loss, hipStream_t s) {
-    hipLaunchKernelGGL(span_mse_finish_kernel, dim3(1), dim3(256), 0, s, partial, n_partial, inv_n, loss);
-    return hipGetLastError();
-}
-
 hipError_t launch_span_noise_packed(const float* x0, const float* noise, const int64_t* seeds, unsigned tag, const float* ca,
-                                    const float* cs, const int32_t* cu, const int32_t* prompt_len, float* x_in, int B, int S, int max_N,
-                                    int d, hipStream_t s) {
-    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !prompt_len || (!noise == !seeds)) return hipErrorInvalidValue;
+                                    const float* cs, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len,
+                                    float* x_in, int B, int S, int max_N, int d, hipStream_t s) {
+    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || (!noise == !seeds)) return hipErrorInvalidValue;
     if (seeds)
         hipLaunchKernelGGL(span_noise_packed_kernel<true>, guided_grid(max_N, d, B), dim3(256), 0, s, x0, noise, seeds, tag, ca, cs, cu,
-                           prompt_len, x_in, S, d);
+                           prompt_len, suffix_len, x_in, S, d);
     else
         hipLaunchKernelGGL(span_noise_packed_kernel<false>, guided_grid(max_N, d, B), dim3(256), 0, s, x0, noise, seeds, tag, ca, cs, cu,
-                           prompt_len, x_in, S, d);
+                           prompt_len, suffix_len, x_in, S, d);
     return hipGetLastError();
 }
 
 hipError_t launch_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
-                                  const int32_t* prompt_len, double n_elems, float* grad, float* loss, float* partial, int B, int S,
-                                  int max_N, int d, hipStream_t s) {
-    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !prompt_len || (!noise == !seeds) || !(n_elems >= 1.0))
+                                  const int32_t* prompt_len, const int32_t* suffix_len, double n_elems, float* grad, float* loss,
+                                  float* partial, int B, int S, int max_N, int d, hipStream_t s) {
+    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || (!noise == !seeds) || !(n_elems >= 1.0))
         return hipErrorInvalidValue;
     const float scale2 = (float)(2.0 / n_elems), inv_n = (float)(1.0 / n_elems);
     const dim3 grid = guided_grid(max_N, d, B);
     if (seeds)
-        hipLaunchKernelGGL(span_mse_packed_kernel<true>, grid, dim3(256), 0, s, eps, noise, seeds, tag, cu, prompt_len, scale2, grad,
-                           partial, S, d);
+        hipLaunchKernelGGL(span_mse_packed_kernel<true>, grid, dim3(256), 0, s, eps, noise, seeds, tag, cu, prompt_len, suffix_len,
+                           scale2, grad, partial, S, d);
     else
-        hipLaunchKernelGGL(span_mse_packed_kernel<false>, grid, dim3(256), 0, s, eps, noise, seeds, tag, cu, prompt_len, scale2, grad,
-                           partial, S, d);
+        hipLaunchKernelGGL(span_mse_packed_kernel<false>, grid, dim3(256), 0, s, eps, noise, seeds, tag, cu, prompt_len, suffix_len,
+                           scale2, grad, partial, S, d);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(span_mse_finish_kernel, dim3(1), dim3(256), 0, s, partial, (size_t)B * grid.x, inv_n, loss);
     return hipGetLastError();

@@ -474,7 +474,7 @@ class DiTTO(nn.Module):
         (seeds, tag), so it never exists in memory.  One kernel (csrc/span_train.hip).  Returns fp32 [S, d].
         `suffix_lengths` (list / tuple / int tensor [B], Q_b >= 0, P_b + Q_b <= N_b - 1): the span ANYWHERE — the last Q_b rows stay
         clean as well and the window in between is noised, the Philox index local to it (infilling objectives;
-        csrc/span_window.hip).  `prompt_lengths` may then be None (P = 0).  None: the call as it was.
+        the same kernel).  `prompt_lengths` may then be None (P = 0).  None: the call as it was.
         The padded collate (train_forward) has no prompts: pack the batch first."""
         _require_cuda(x0, "x0")
         eng = self.engine(x0.device)

@@ -21,7 +21,7 @@ request has phi > 0 runs the ..._rescale_opts form of its entry — the same for
 csrc/guided_rescale.hip in between — over a scratch sized once from the capacities.
 Speech infilling (guided_stream(infill=True), submit(suffix=)): a request may carry clean rows BEHIND its generated frames as well;
 each request's suffix length rides in the step block and a step with a suffixed request in flight runs the ..._window_opts form of
-its entry (csrc/guided_window.hip).  Such a stream has no guidance intervals and no guidance rescale.
+its entry (csrc/guided_packed.hip, csrc/guided_multistep.hip).  Such a stream has no guidance intervals and no guidance rescale.
 They serve the reference's sampling loop (reference src/model/SpeechGenerator.py:130-164) to a request stream.
 """
 from __future__ import annotations

@@ -1,4 +1,4 @@
-"""-m gpu: the guided update that skips each utterance's speech prompt (csrc/guided_prompt.hip) through its two entries,
+"""-m gpu: the guided update that skips each utterance's speech prompt (csrc/guided_packed.hip) through its two entries,
 ditto_guided_update_packed_prompt and ditto_guided_update_packed_tags_prompt.
 
 Expected values come from the EXISTING entries run on the generated rows compacted into a packed batch of G_b-row utterances with the

@@ -1,4 +1,4 @@
-"""-m gpu: the second-order multistep update over a window per utterance (csrc/guided_window.hip) through
+"""-m gpu: the second-order multistep update over a window per utterance (csrc/guided_multistep.hip) through
 ditto_multistep_update_window, in its four instantiations (CFG on / off x one step for the batch / one per utterance).
 
 The scheme of tests/test_gpu_window_update.py: expected values come from the EXISTING ditto_multistep_update_packed run on the window

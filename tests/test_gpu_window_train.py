@@ -1,4 +1,4 @@
-"""-m gpu: span-masked training with the span ANYWHERE (csrc/span_window.hip; DiTTO.span_noise_packed / span_loss_packed with
+"""-m gpu: span-masked training with the span ANYWHERE (csrc/span_train.hip; DiTTO.span_noise_packed / span_loss_packed with
 suffix_lengths=).
 
 Kernel level, both modes (a noise buffer, seeds): x_in is bit-equal to x0 on both contexts and, on the window, torch.equal to the

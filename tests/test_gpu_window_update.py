@@ -1,4 +1,4 @@
-"""-m gpu: the guided update over a window per utterance (csrc/guided_window.hip: speech infilling) through its two entries,
+"""-m gpu: the guided update over a window per utterance (csrc/guided_packed.hip: speech infilling) through its two entries,
 ditto_guided_update_packed_window and ditto_guided_update_packed_tags_window.
 
 Expected values come from the EXISTING unprompted entries run on the window rows compacted into a packed batch of G_b-row utterances

@@ -1,21 +1,21 @@
 """The multistep update kernel compiled for gfx950 (csrc/guided_multistep.hip), from the compiler's resource report and its listing:
 four instantiations (CFG on / off x one step for the batch / one per utterance), no scratch, full occupancy (8 waves per SIMD) like the
 other update kernels, and every global access a 16-byte one — the per-utterance block (coefficients, guidance scale, use_prev) and the
-offsets come in through scalar loads."""
+offsets and both context lengths come in through scalar loads."""
 import os
 import re
 
 import pytest
 
-from test_prompt_isa import _bodies, _compile, _remarks
+from test_prompt_isa import _bodies, _listing, _remarks
 
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 KERNEL = "_ZN5ditto23multistep_update_kernel"
 
 
 @pytest.fixture(scope="module")
-def multistep(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("multistep"), "guided_multistep")
+def multistep():
+    return _listing("guided_multistep")
 
 
 def test_four_instantiations_no_scratch_full_occupancy(multistep):

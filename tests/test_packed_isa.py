@@ -54,7 +54,7 @@ def test_packed_attention_keeps_two_waves_per_simd():
 def test_packed_rowwise_and_update_kernels_use_no_scratch():
     guided = _asm("guided_packed.hip")
     upd = {k: v for k, v in guided.items() if "guided_update_packed_kernel" in k}
-    assert len(upd) == 6 and not any(upd.values()), upd                 # 3 noise sources x CFG on / off
+    assert len(upd) == 12 and not any(upd.values()), upd                # 3 noise sources x CFG on / off x scalar tag / per-utterance tags
     rw = _asm("rowwise.hip")
     adaln = {k: v for k, v in rw.items() if re.search(r"ln_kernelILi\dELi3EE", k)}
     assert len(adaln) == 8 and not any(adaln.values()), adaln           # every row width of the packed AdaLN entry

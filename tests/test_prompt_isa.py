@@ -1,9 +1,13 @@
-"""The speech-prompt kernels compiled for gfx950 (csrc/guided_prompt.hip, csrc/span_train.hip): the instantiation counts, no scratch,
-full occupancy (8 waves per SIMD) for the update kernels, and every global access of the update and noising kernels a 16-byte one —
-the per-utterance scalars, the prompt length among them, come in through scalar loads."""
+"""The speech-prompt kernels compiled for gfx950 (csrc/guided_packed.hip: the update behind a prompt is the packed update kernel;
+csrc/span_train.hip): the instantiation counts, no scratch, full occupancy (8 waves per SIMD) for the update kernel, and every global
+access of the update and noising kernels a 16-byte one — the per-utterance scalars, the prompt length among them, come in through
+scalar loads.  Also the home of the helpers the other *_isa tests compile and read listings with."""
+import functools
 import os
+import pathlib
 import re
 import subprocess
+import tempfile
 
 import pytest
 
@@ -22,6 +26,13 @@ def _compile(tmp, name):
     return open(out).read(), r.stderr
 
 
+@functools.lru_cache(maxsize=None)
+def _listing(name):
+    """_compile, once per source file and session"""
+    with tempfile.TemporaryDirectory() as tmp:
+        return _compile(pathlib.Path(tmp), name)
+
+
 def _bodies(asm, prefix):
     """kernel name -> its instruction text"""
     return {m.group(1): m.group(2) for m in re.finditer(r"^(%s\w+):.*?$(.*?)^\s*s_endpgm" % prefix, asm, re.M | re.S)}
@@ -36,26 +47,29 @@ def _remarks(remarks, prefix):
     return out
 
 
-@pytest.fixture(scope="module")
-def prompt(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("prompt"), "guided_prompt")
+UPDATE = "_ZN5ditto27guided_update_packed_kernel"
 
 
 @pytest.fixture(scope="module")
-def span(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("span"), "span_train")
+def prompt():
+    return _listing("guided_packed")
+
+
+@pytest.fixture(scope="module")
+def span():
+    return _listing("span_train")
 
 
 def test_update_kernel_twelve_instantiations_no_scratch_full_occupancy(prompt):
     _, remarks = prompt
-    res = _remarks(remarks, "_ZN5ditto27guided_update_prompt_kernel")
+    res = _remarks(remarks, UPDATE)
     assert len(res) == 12, remarks                               # 3 noise modes x CFG on / off x scalar tag / per-utterance tags
     assert set(res.values()) == {(0, 8)}, res
 
 
 def test_update_kernel_sixteen_byte_global_accesses_only(prompt):
     asm, _ = prompt
-    bodies = _bodies(asm, "_ZN5ditto27guided_update_prompt_kernel")
+    bodies = _bodies(asm, UPDATE)
     assert len(bodies) == 12, list(bodies)
     for name, body in bodies.items():
         cfg = "ELb1ELb" in name

@@ -1,6 +1,6 @@
-"""The kernels of continuous batching compiled for gfx950 (csrc/guided_tags.hip, csrc/regroup_packed.hip): no scratch, full
-occupancy (8 waves per SIMD), and every global access a 16-byte one — the per-utterance scalars, the tag among them, and the segment
-of a regroup come in through scalar loads."""
+"""The kernels of continuous batching compiled for gfx950 (csrc/guided_packed.hip: the per-utterance-tag update is the TAGS half of
+the packed update kernel's instantiations; csrc/regroup_packed.hip): no scratch, full occupancy (8 waves per SIMD), and every global
+access a 16-byte one — the per-utterance scalars, the tag among them, and the segment of a regroup come in through scalar loads."""
 import os
 import re
 import subprocess
@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from test_prompt_isa import _listing, _remarks
 
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 
@@ -27,9 +28,12 @@ def _bodies(asm, prefix):
     return {m.group(1): m.group(2) for m in re.finditer(r"^(%s\w+):.*?$(.*?)^\s*s_endpgm" % prefix, asm, re.M | re.S)}
 
 
+UPDATE = "_ZN5ditto27guided_update_packed_kernel"
+
+
 @pytest.fixture(scope="module")
-def tags(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("tags"), "guided_tags")
+def tags():
+    return _listing("guided_packed")
 
 
 @pytest.fixture(scope="module")
@@ -39,18 +43,17 @@ def regroup(tmp_path_factory):
 
 def test_tag_kernel_six_instantiations_no_scratch_full_occupancy(tags):
     _, remarks = tags
-    names = re.findall(r"Function Name: (_ZN5ditto32guided_update_packed_tags_kernel\S+)", remarks)
-    assert len(names) == 6, remarks
-    assert re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", remarks) == ["0"] * 6, remarks
-    assert re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", remarks) == ["8"] * 6, remarks
+    res = _remarks(remarks, UPDATE)
+    assert len(res) == 12 and sum("Lb1EEEv" in n for n in res) == 6, remarks      # TAGS, the last template argument: six of the twelve
+    assert set(res.values()) == {(0, 8)}, res
 
 
 def test_tag_kernel_sixteen_byte_global_accesses_only(tags):
     asm, _ = tags
-    bodies = _bodies(asm, "_ZN5ditto32guided_update_packed_tags_kernel")
-    assert len(bodies) == 6, list(bodies)
+    bodies = _bodies(asm, UPDATE)
+    assert len(bodies) == 12 and sum("Lb1EEEv" in n for n in bodies) == 6, list(bodies)
     for name, body in bodies.items():
-        cfg = "Lb1E" in name
+        cfg = "ELb1ELb" in name
         noise_buf = "ILi1E" in name
         loads = re.findall(r"global_load_(\w+)", body)
         stores = re.findall(r"global_store_(\w+)", body)

@@ -33,7 +33,7 @@ def window_clamp(n, p, q):
 
 
 def window_of(cu, S, b, p, q):
-    """(first row, one past the last row) of utterance b's window after guided_span's clamp of the utterance and window_clamp"""
+    """(first row, one past the last row) of utterance b's window after the utterance's own clamp (utt_rows) and window_clamp"""
     r0 = min(max(cu[b], 0), S - 1)
     n = min(max(cu[b + 1] - r0, 1), S - r0)
     p, q = window_clamp(n, p, q)

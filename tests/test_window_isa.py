@@ -1,42 +1,51 @@
-"""The speech-infilling kernels compiled for gfx950 (csrc/guided_window.hip, csrc/span_window.hip), from the compiler's resource report
-and its listing: 12 + 4 update and 2 + 2 span instantiations, no scratch, full occupancy (8 waves per SIMD), and every global access
-of the update kernels a 16-byte one — the per-utterance scalars, both context lengths among them, come in through scalar loads."""
+"""The packed update, multistep and span-training kernels compiled for gfx950 (csrc/guided_packed.hip, csrc/guided_multistep.hip,
+csrc/span_train.hip), from the compiler's resource report and its listing: 12 update, 4 multistep and 2 + 2 span instantiations behind
+the unprompted, per-utterance-tag, speech-prompt and speech-infilling entries alike, no scratch, full occupancy (8 waves per SIMD),
+and every global access of the update and multistep kernels a 16-byte one — the per-utterance scalars, the tag and both context
+lengths among them, come in through scalar loads."""
 import os
 import re
 
 import pytest
 
-from test_prompt_isa import _bodies, _compile, _remarks
+from test_prompt_isa import _bodies, _listing, _remarks
 
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-UPDATE = "_ZN5ditto27guided_update_window_kernel"
-MULTISTEP = "_ZN5ditto30multistep_update_window_kernel"
-NOISE = "_ZN5ditto24span_noise_window_kernel"
-MSE = "_ZN5ditto22span_mse_window_kernel"
+UPDATE = "_ZN5ditto27guided_update_packed_kernel"
+MULTISTEP = "_ZN5ditto23multistep_update_kernel"
+NOISE = "_ZN5ditto24span_noise_packed_kernel"
+MSE = "_ZN5ditto22span_mse_packed_kernel"
 
 
 @pytest.fixture(scope="module")
-def window(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("window"), "guided_window")
+def update():
+    return _listing("guided_packed")
 
 
 @pytest.fixture(scope="module")
-def span(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("span_window"), "span_window")
+def multistep():
+    return _listing("guided_multistep")
 
 
-def test_instantiations_no_scratch_full_occupancy(window, span):
-    upd = _remarks(window[1], UPDATE)
-    ms = _remarks(window[1], MULTISTEP)
+@pytest.fixture(scope="module")
+def span():
+    return _listing("span_train")
+
+
+def test_instantiations_no_scratch_full_occupancy(update, multistep, span):
+    upd = _remarks(update[1], UPDATE)
+    ms = _remarks(multistep[1], MULTISTEP)
     noise = _remarks(span[1], NOISE)
     mse = _remarks(span[1], MSE)
-    assert (len(upd), len(ms), len(noise), len(mse)) == (12, 4, 2, 2), (window[1], span[1])
+    # update: 3 noise modes x CFG on / off x scalar tag / per-utterance tags; span: buffer / seeded each
+    assert (len(upd), len(ms), len(noise), len(mse)) == (12, 4, 2, 2), (update[1], multistep[1], span[1])
+    assert sum("Lb1EEEv" in n for n in upd) == 6, list(upd)             # TAGS, the last template argument, true
     for res in (upd, ms, noise, mse):
         assert set(res.values()) == {(0, 8)}, res
 
 
-def test_update_kernels_sixteen_byte_global_accesses_only(window):
-    asm, _ = window
+def test_update_kernels_sixteen_byte_global_accesses_only(update, multistep):
+    asm, _ = update
     bodies = _bodies(asm, UPDATE)
     assert len(bodies) == 12, list(bodies)
     for name, body in bodies.items():
@@ -44,10 +53,11 @@ def test_update_kernels_sixteen_byte_global_accesses_only(window):
         noise_buf = "ILi1E" in name
         loads = re.findall(r"global_load_(\w+)", body)
         stores = re.findall(r"global_store_(\w+)", body)
+        # x, c (+ u under CFG) (+ the noise buffer); one store (+ the unconditional half under CFG)
         assert set(loads) == {"dwordx4"} and set(stores) == {"dwordx4"}, (name, loads, stores)
         assert loads.count("dwordx4") >= 2 + cfg + noise_buf, (name, loads)
         assert stores.count("dwordx4") >= 1 + cfg, (name, stores)
-    bodies = _bodies(asm, MULTISTEP)
+    bodies = _bodies(multistep[0], MULTISTEP)
     assert len(bodies) == 4, list(bodies)
     for name, body in bodies.items():
         cfg = "ILb1ELb" in name

@@ -114,7 +114,7 @@ def main():
             for name, (r, a) in hip.SYMBOLS.items():
                 if hasattr(old, name):
                     getattr(old, name).restype, getattr(old, name).argtypes = r, a
-            assert old.ditto_abi_version() == new_lib.ditto_abi_version() and not hasattr(old, "ditto_guided_step_packed_window_opts")
+            assert old.ditto_abi_version() == new_lib.ditto_abi_version()
             arms += [("c_parent_ms", old), ("c_parent_again_ms", old)]
         plain_audio = audio[:SG].contiguous()
         runs, outputs = {k: [] for k, _ in arms}, {}
