@@ -366,6 +366,28 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 size_t attention_workspace_bytes(int B, int H, int Sq, int Skv, int dh);
 // the GEMM-composed path's scratch at any head_dim (force_generic / causal)
 size_t attention_generic_workspace_bytes(int B, int H, int Sq, int Skv, int dh);
+// ---------------- attention_slp.hip : the length predictor's variable-length attention ----------------
+// The GEMM-composed path with a.q_len / a.kv_len (device int32 [B], either may be null; values clamped to [1, Sq] / [1, Skv]):
+// a row sees min(causal rule of its own lengths, kv_len) keys, query rows at or past q_len give zero output rows, and V rows at
+// or past kv_len are never multiplied (NaN there is legal).  bf16 output, no dropout; workspace as attention_generic_workspace_bytes.
+hipError_t launch_attention_composed_len(const AttnArgs& a, hipStream_t s);
+// One query row per (utterance, head) over keys 0 .. len[b] - 1: out[b, h*dh + c] bf16.  q [B, ldq]; k / v rows of utterance b
+// start at k + b * ks_b / v + b * vs_b (elements) with row strides ldk / ldv; head h at columns [h*dh, (h+1)*dh), dh % 64 == 0,
+// dh <= 2048.  len: device int32 [B] (clamped to [1, Skv]) or null = Skv.  All strides multiples of 8, pointers 16-byte aligned.
+struct LastRowAttnArgs {
+    const void* q; int ldq;
+    const void* k; int ldk; long long ks_b;
+    const void* v; int ldv; long long vs_b;
+    const int32_t* len;
+    void* out; int ldo;
+    int B, H, Skv, dh;
+    float scale;
+    void* workspace; size_t workspace_bytes;   // attention_last_row_workspace_bytes, 256-byte aligned
+};
+hipError_t launch_attention_last_row(const LastRowAttnArgs& a, hipStream_t s);
+size_t attention_last_row_workspace_bytes(int B, int H, int Skv, int dh);   // depends on g_slp_lr_chunk
+extern int g_slp_lr_chunk;   // keys per workgroup of the last-row kernel (ditto_set_option("slp_lr_chunk")), 1 .. 1024
+extern int g_slp_last_row;   // ditto_slp_forward_varlen without `decoded`: 1 = last layer on the last rows only, 0 = composed
 // slp.hip: y = LN(x) * gamma + beta as fp32 and / or bf16 (either may be null)
 hipError_t launch_layernorm_dual(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_bf16,
                                  int M, int d, hipStream_t s);

@@ -16,6 +16,8 @@
 // are unchanged while every contraction length is a multiple of the GEMM K-tile.  Attention runs on the GEMM-composed
 // path of attention.hip (scores fp32 -> masked row softmax -> P V) — the stack runs once per utterance, in front of
 // hundreds of denoise steps, and is not on the timed path.
+// Variable-length batches (ditto_slp_forward_varlen, below the dense entry, which it leaves untouched): the composed path
+// with per-utterance lengths, and the last layer on the B last rows only — both in attention_slp.hip.
 #include <memory>
 #include <new>
 
@@ -165,6 +167,47 @@ SlpWs plan_slp_ws(const ditto_slp_config& c, int B, int S, int T) {
     w.attn = take(w.attn_bytes);
     w.total = off;
     return w;
+}
+// ---- variable-length batches (ditto_slp_forward_varlen) ----
+DITTO_DEV int slp_len(const int32_t* len, int b, int full) {   // clamped like the packed entries' offsets
+    if (!len) return full;
+    const int v = len[b];
+    return v < 1 ? 1 : (v > full ? full : v);
+}
+// row len[b] - 1 of every utterance -> row b of of [B, d] (fp32, from xf) and ob [B, d] (bf16, from xb); either pair may be null
+__global__ __launch_bounds__(256) void gather_last_rows_kernel(const float* __restrict__ xf, const bf16* __restrict__ xb,
+                                                               const int32_t* __restrict__ len, int S, int d,
+                                                               float* __restrict__ of, bf16* __restrict__ ob) {
+    const int b = blockIdx.x;
+    const size_t row = (size_t)b * S + slp_len(len, b, S) - 1;
+    for (int i = threadIdx.x; i < d; i += 256) {
+        if (of) of[(size_t)b * d + i] = xf[row * d + i];
+        if (ob) ob[(size_t)b * d + i] = xb[row * d + i];
+    }
+}
+// decoded[b, s, :] = s < len[b] ? x[b, s, :] : 0   (rows past the length are never read: they may hold NaN)
+__global__ __launch_bounds__(256) void copy_rows_len_kernel(const float* __restrict__ x, const int32_t* __restrict__ len,
+                                                            int S, int d, float* __restrict__ out) {
+    const int row = blockIdx.x, b = row / S, sidx = row % S;
+    const bool valid = sidx < slp_len(len, b, S);
+    const f32x4* src = reinterpret_cast<const f32x4*>(x + (size_t)row * d);
+    f32x4* dst = reinterpret_cast<f32x4*>(out + (size_t)row * d);
+    for (int i = threadIdx.x; i < (d >> 2); i += 256) dst[i] = valid ? src[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// the dense workspace plus the [B, .] matrices of the last-row path
+struct SlpWsLen { SlpWs w; size_t xl, rl, xlb, ql, aol, hl, lr, lr_bytes, total; };
+SlpWsLen plan_slp_ws_len(const ditto_slp_config& c, int B, int S, int T) {
+    SlpWsLen p;
+    p.w = plan_slp_ws(c, B, S, T);
+    const size_t d = c.d_model, dp = (size_t)c.nhead * dhp_of(c), ff = c.dim_feedforward;
+    size_t off = p.w.total;
+    auto take = [&](size_t b) { size_t o = off; off += al(b); return o; };
+    p.xl = take(B * d * 4); p.rl = take(B * d * 4); p.xlb = take(B * d * 2); p.ql = take(B * dp * 2);
+    p.aol = take(B * dp * 2); p.hl = take(B * ff * 2);
+    p.lr_bytes = attention_last_row_workspace_bytes(B, c.nhead, S > T ? S : T, dhp_of(c));
+    p.lr = take(p.lr_bytes);
+    p.total = off;
+    return p;
 }
 int check_slp_cfg(const ditto_slp_config* c) {
     if (!c) return fail(DITTO_ERR_ARG, "null ditto_slp_config");
@@ -365,6 +408,167 @@ int ditto_slp_forward(ditto_slp_t m, const float* z_audio, const float* z_text, 
     hipLaunchKernelGGL(last_row_linear_kernel, dim3((B * c.num_classes + 3) / 4), dim3(256), 0, s, x, m->Wh, m->bh, logits,
                        B, S, d, c.num_classes);
     HIP_TRY(hipGetLastError());
+    return DITTO_OK;
+}
+
+size_t ditto_slp_varlen_workspace_bytes(const ditto_slp_config* cfg, int B, int S, int T) {
+    if (check_slp_cfg(cfg)) return 0;
+    if (B <= 0 || S <= 0 || T <= 0) { fail(DITTO_ERR_SHAPE, "B, S, T must be positive"); return 0; }
+    return plan_slp_ws_len(*cfg, B, S, T).total;
+}
+
+int ditto_slp_forward_varlen(ditto_slp_t m, const float* z_audio, const float* z_text, const int32_t* audio_len,
+                             const int32_t* text_len, int B, int S, int T, float* logits, float* decoded, void* workspace,
+                             size_t workspace_bytes, ditto_stream_t stream) {
+    if (!m || !z_audio || !z_text || !logits || !workspace)
+        return fail(DITTO_ERR_ARG, "null argument to ditto_slp_forward_varlen");
+    if (B <= 0 || S <= 0 || T <= 0) return fail(DITTO_ERR_SHAPE, "B, S, T must be positive");
+    const ditto_slp_config& c = m->cfg;
+    const SlpWsLen p = plan_slp_ws_len(c, B, S, T);
+    const SlpWs& w = p.w;
+    if (workspace_bytes < p.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, p.total);
+    if ((uintptr_t)workspace % 256) return fail(DITTO_ERR_ARG, "workspace must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    char* W = (char*)workspace;
+    const int d = c.d_model, H = c.nhead, dhp = m->dhp, dp = H * dhp, ff = c.dim_feedforward;
+    const int M = B * S, Mt = B * T;
+    float* x = (float*)(W + w.x);
+    float* r = (float*)(W + w.r);
+    void *xb = W + w.xb, *qkv = W + w.qkv, *ao = W + w.ao, *memb = W + w.memb, *kv = W + w.kv, *h = W + w.h;
+    float *xl = (float*)(W + p.xl), *rl = (float*)(W + p.rl);
+    void *xlb = W + p.xlb, *ql = W + p.ql, *aol = W + p.aol, *hl = W + p.hl;
+    const float scale = 1.0f / sqrtf((float)(d / H));   // of the TRUE head width (F.multi_head_attention_forward)
+    const bool last_rows = !decoded && g_slp_last_row != 0;
+
+    auto gemm = [&](const void* A, int lda, const void* Wt, const float* bias, const float* resid, void* out, int ldo,
+                    int Mr, int N, int K, GemmEpilogue e) {
+        GemmArgs g{};
+        g.A = A; g.lda = lda; g.W = Wt; g.bias = bias; g.residual = resid; g.ldr = ldo; g.out = out; g.ldo = ldo;
+        g.M = Mr; g.N = N; g.K = K;
+        return launch_gemm(g, e, s);
+    };
+    // the composed path with lengths: its own route (launch_attention refuses lengths on the GEMM-composed path)
+    auto attn = [&](const void* q, int ldq, const void* k, const void* v, int ldkv, int Skv, bool causal,
+                    const int32_t* kvl) {
+        AttnArgs a{};
+        a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldkv; a.v = v; a.ldv = ldkv; a.out_bf16 = ao; a.ldo = dp;
+        a.B = B; a.H = H; a.Sq = S; a.Skv = Skv; a.dh = dhp; a.scale = scale;
+        a.workspace = W + w.attn; a.workspace_bytes = w.attn_bytes;
+        a.force_generic = true; a.causal = causal; a.q_len = audio_len; a.kv_len = kvl;
+        return launch_attention_composed_len(a, s);
+    };
+    auto attn_last = [&](const void* k, const void* v, int ldkv, int Skv, const int32_t* len) {
+        LastRowAttnArgs a{};
+        a.q = ql; a.ldq = dp; a.k = k; a.ldk = ldkv; a.ks_b = (long long)Skv * ldkv; a.v = v; a.ldv = ldkv;
+        a.vs_b = (long long)Skv * ldkv; a.len = len; a.out = aol; a.ldo = dp; a.B = B; a.H = H; a.Skv = Skv; a.dh = dhp;
+        a.scale = scale; a.workspace = W + p.lr; a.workspace_bytes = p.lr_bytes;
+        return launch_attention_last_row(a, s);
+    };
+    auto gather = [&](const float* xf, const void* xh, float* of, void* oh) {
+        hipLaunchKernelGGL(gather_last_rows_kernel, dim3(B), dim3(256), 0, s, xf, (const bf16*)xh, audio_len, S, d, of,
+                           (bf16*)oh);
+        return hipGetLastError();
+    };
+
+    HIP_TRY(launch_cast_bf16(z_audio, xb, (size_t)M * d, s));
+    HIP_TRY(launch_cast_bf16(z_text, memb, (size_t)Mt * d, s));
+    const float* xin = z_audio;
+    const bf16* qkv_b = (const bf16*)qkv;
+    const bf16* kv_b = (const bf16*)kv;
+    for (int l = 0; l < c.num_layers; ++l) {
+        const SlpLayer& L = m->layers[l];
+        const bool last = l + 1 == c.num_layers;
+        if (last && last_rows) {
+            // only row len_b - 1 of every utterance reaches length_predictor: K and V for all rows (the k | v row sections
+            // of Wqkv), everything else on the [B, d] matrix of last rows
+            HIP_TRY(gemm(xb, d, (const bf16*)L.Wqkv + (size_t)dp * d, L.bqkv + dp, nullptr, qkv, 2 * dp, M, 2 * dp, d,
+                         EPI_BIAS_BF16));
+            HIP_TRY(gather(xin, xb, xl, xlb));
+            HIP_TRY(gemm(xlb, d, L.Wqkv, L.bqkv, nullptr, ql, dp, B, dp, d, EPI_BIAS_BF16));
+            HIP_TRY(attn_last(qkv_b, qkv_b + dp, 2 * dp, S, audio_len));
+            HIP_TRY(gemm(aol, dp, L.Wo, L.bo, xl, rl, d, B, d, dp, EPI_BIAS_RES_F32));
+            HIP_TRY(launch_layernorm_dual(rl, L.g1, L.be1, xl, xlb, B, d, s));
+            HIP_TRY(gemm(xlb, d, L.Wcq, L.bcq, nullptr, ql, dp, B, dp, d, EPI_BIAS_BF16));
+            HIP_TRY(gemm(memb, d, L.Wckv, L.bckv, nullptr, kv, 2 * dp, Mt, 2 * dp, d, EPI_BIAS_BF16));
+            HIP_TRY(attn_last(kv_b, kv_b + dp, 2 * dp, T, text_len));
+            HIP_TRY(gemm(aol, dp, L.Wco, L.bco, xl, rl, d, B, d, dp, EPI_BIAS_RES_F32));
+            HIP_TRY(launch_layernorm_dual(rl, L.g2, L.be2, xl, xlb, B, d, s));
+            HIP_TRY(gemm(xlb, d, L.W1, L.b1, nullptr, hl, ff, B, ff, d, EPI_BIAS_RELU_BF16));
+            HIP_TRY(gemm(hl, ff, L.W2, L.b2, xl, rl, d, B, d, ff, EPI_BIAS_RES_F32));
+            HIP_TRY(launch_layernorm_dual(rl, L.g3, L.be3, xl, nullptr, B, d, s));
+            break;
+        }
+        // self-attention block (_sa_block, causal over the utterance's own positions)
+        HIP_TRY(gemm(xb, d, L.Wqkv, L.bqkv, nullptr, qkv, 3 * dp, M, 3 * dp, d, EPI_BIAS_BF16));
+        HIP_TRY(attn(qkv_b, 3 * dp, qkv_b + dp, qkv_b + 2 * dp, 3 * dp, S, true, audio_len));
+        HIP_TRY(gemm(ao, dp, L.Wo, L.bo, xin, r, d, M, d, dp, EPI_BIAS_RES_F32));
+        HIP_TRY(launch_layernorm_dual(r, L.g1, L.be1, x, xb, M, d, s));
+        // cross-attention block (_mha_block) on the utterance's own text rows
+        HIP_TRY(gemm(xb, d, L.Wcq, L.bcq, nullptr, qkv, dp, M, dp, d, EPI_BIAS_BF16));
+        HIP_TRY(gemm(memb, d, L.Wckv, L.bckv, nullptr, kv, 2 * dp, Mt, 2 * dp, d, EPI_BIAS_BF16));
+        HIP_TRY(attn(qkv_b, dp, kv_b, kv_b + dp, 2 * dp, T, false, text_len));
+        HIP_TRY(gemm(ao, dp, L.Wco, L.bco, x, r, d, M, d, dp, EPI_BIAS_RES_F32));
+        HIP_TRY(launch_layernorm_dual(r, L.g2, L.be2, x, xb, M, d, s));
+        // feed-forward block (_ff_block)
+        HIP_TRY(gemm(xb, d, L.W1, L.b1, nullptr, h, ff, M, ff, d, EPI_BIAS_RELU_BF16));
+        HIP_TRY(gemm(h, ff, L.W2, L.b2, x, r, d, M, d, ff, EPI_BIAS_RES_F32));
+        HIP_TRY(launch_layernorm_dual(r, L.g3, L.be3, x, last ? nullptr : xb, M, d, s));
+        xin = x;
+    }
+    if (!last_rows) {
+        if (decoded) {   // rows past the length hold whatever the padding made of them: zeroed here, never copied
+            hipLaunchKernelGGL(copy_rows_len_kernel, dim3(M), dim3(256), 0, s, x, audio_len, S, d, decoded);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(gather(x, nullptr, xl, nullptr));
+    }
+    hipLaunchKernelGGL(last_row_linear_kernel, dim3((B * c.num_classes + 3) / 4), dim3(256), 0, s, xl, m->Wh, m->bh, logits,
+                       B, 1, d, c.num_classes);
+    HIP_TRY(hipGetLastError());
+    return DITTO_OK;
+}
+
+int ditto_attention_causal_varlen_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out,
+                                       int ldo, const int32_t* q_len, const int32_t* kv_len, int B, int H, int Sq, int Skv,
+                                       int dh, float scale, int causal, void* workspace, size_t workspace_bytes,
+                                       ditto_stream_t stream) {
+    if (!q || !k || !v || !out || !workspace)
+        return fail(DITTO_ERR_ARG, "null pointer to ditto_attention_causal_varlen_bf16");
+    if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0) return fail(DITTO_ERR_SHAPE, "B, H, Sq, Skv must be positive");
+    if (dh <= 0 || dh % 64) return fail(DITTO_ERR_SHAPE, "head_dim must be a multiple of 64");
+    if (workspace_bytes < attention_generic_workspace_bytes(B, H, Sq, Skv, dh))
+        return fail(DITTO_ERR_SIZE, "attention workspace too small");
+    AttnArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out_bf16 = out; a.ldo = ldo;
+    a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.dh = dh; a.scale = scale;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.force_generic = true; a.causal = causal != 0; a.q_len = q_len; a.kv_len = kv_len;
+    HIP_TRY(launch_attention_composed_len(a, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+size_t ditto_attention_last_row_workspace_bytes(int B, int H, int Skv, int dh) {
+    if (B <= 0 || H <= 0 || Skv <= 0 || dh <= 0 || dh % 64 || dh > 2048) return 0;
+    return attention_last_row_workspace_bytes(B, H, Skv, dh);
+}
+
+int ditto_attention_last_row_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                  const int32_t* len, int B, int H, int Skv, int dh, float scale, void* workspace,
+                                  size_t workspace_bytes, ditto_stream_t stream) {
+    if (!q || !k || !v || !out || !workspace) return fail(DITTO_ERR_ARG, "null pointer to ditto_attention_last_row_bf16");
+    if (B <= 0 || H <= 0 || Skv <= 0) return fail(DITTO_ERR_SHAPE, "B, H, Skv must be positive");
+    if (dh <= 0 || dh % 64 || dh > 2048) return fail(DITTO_ERR_SHAPE, "head_dim must be a multiple of 64, at most 2048");
+    if ((ldq | ldk | ldv) % 8 || ldq < H * dh || ldk < H * dh || ldv < H * dh || ldo < H * dh)
+        return fail(DITTO_ERR_SHAPE, "row strides must be multiples of 8 and at least H * head_dim");
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (uintptr_t)workspace % 256)
+        return fail(DITTO_ERR_ARG, "q, k, v must be 16-byte aligned and the workspace 256-byte aligned");
+    if (workspace_bytes < attention_last_row_workspace_bytes(B, H, Skv, dh))
+        return fail(DITTO_ERR_SIZE, "attention workspace too small");
+    LastRowAttnArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.ks_b = (long long)Skv * ldk; a.v = v; a.ldv = ldv;
+    a.vs_b = (long long)Skv * ldv; a.len = len; a.out = out; a.ldo = ldo; a.B = B; a.H = H; a.Skv = Skv; a.dh = dh;
+    a.scale = scale; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    HIP_TRY(launch_attention_last_row(a, (hipStream_t)stream));
     return DITTO_OK;
 }
 

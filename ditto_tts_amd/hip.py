@@ -297,6 +297,12 @@ SYMBOLS = {
     "ditto_slp_create": (_i, [C.POINTER(SlpConfig), C.POINTER(SlpWeights), _vp, _sz, _vp, C.POINTER(_vp)]),
     "ditto_slp_destroy": (None, [_vp]),
     "ditto_slp_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ditto_slp_varlen_workspace_bytes": (_sz, [C.POINTER(SlpConfig), _i, _i, _i]),
+    "ditto_slp_forward_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ditto_attention_causal_varlen_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i,
+                                                _vp, _sz, _vp]),
+    "ditto_attention_last_row_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ditto_attention_last_row_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "ditto_attention_causal_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ditto_attention_causal_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "ditto_layernorm_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

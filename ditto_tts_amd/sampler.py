@@ -712,6 +712,27 @@ class SpeechGenerator:
         return obj
 
     @torch.no_grad()
+    def predict_frames(self, z_text, z_audio, *, frame_rate, audio_lengths=None, text_lengths=None,
+                       seconds_of_class=None):
+        """Frames to generate for every utterance of a (variable-length) batch, from the speech-length predictor: a list of B
+        ints, ready for `stream.submit(text_emb, n_frames, ...)` and `sample_guided_packed`.
+
+        z_text [B,T,d] / z_audio [B,S,d] are the encoder outputs `SLP.decode` takes, `audio_lengths` / `text_lengths` its
+        per-utterance lengths (see there, also for what `text_lengths=None` means to a reference-trained checkpoint).
+        class -> seconds is `seconds_of_class(c)` when given, else MIN_AUDIO_DURATION + c: the inverse of the reference's label
+        `int(duration - 10)` (src/utils/MLS.py:77).  n_frames = round(seconds * frame_rate); `frame_rate` (latent frames per
+        second of the codec in use) has no default: nothing here knows the codec."""
+        slp = self._need("slp", self.slp)
+        if isinstance(frame_rate, bool) or not isinstance(frame_rate, (int, float)) or not frame_rate > 0:
+            raise ValueError(f"frame_rate must be a positive number of latent frames per second, got {frame_rate!r}")
+        classes = slp.predict_class(z_text, z_audio, audio_lengths=audio_lengths, text_lengths=text_lengths)
+        if seconds_of_class is None:
+            from .shipped_config import config_classes
+            t0 = config_classes()[1].MIN_AUDIO_DURATION
+            seconds_of_class = lambda c: t0 + c   # noqa: E731
+        return [int(round(float(seconds_of_class(int(c))) * frame_rate)) for c in classes.tolist()]
+
+    @torch.no_grad()
     def generate_speech_from_audio_tensor(self, audio_tensor, padding_mask_audio, text_prompt, is_tokenized=False,
                                           is_slp=False, cond_by_audio=False):
         """Reference :93-111, using the caller-provided codec (`ditto_model.nac`) and vocoder."""

@@ -5,7 +5,9 @@ state_dict keys (`transformer.layers.{i}.*`, `length_predictor.*`; `text_encoder
 modules are injected), so `SpeechGenerator`'s `slp_info["model_state_dict"]` loads unchanged
 (src/model/SpeechGenerator.py:54-62).  What runs on the GPU is everything after the two pretrained encoders
 (src/model/SpeechLP.py:50-54): causal-mask TransformerDecoder over the audio embeddings with cross-attention to the text
-embeddings, and `length_predictor` on the last position — ditto_slp_forward (csrc/slp.hip).
+embeddings, and `length_predictor` on the last position — ditto_slp_forward (csrc/slp.hip); with per-utterance lengths
+(`decode(..., audio_lengths=, text_lengths=)`) ditto_slp_forward_varlen, which predicts every utterance of a padded batch
+from its own rows.
 
 Out of scope: ByT5 and EnCodec themselves (pretrained HF checkpoints, no network).  They are injected
 (`text_encoder=`, `audio_encoder=`); without them `forward(text, audio)` raises and `decode(z_text, z_audio)` is the
@@ -21,6 +23,7 @@ import torch.nn as nn
 from . import hip
 from .engine import _stream
 from .modules import _ParamWatch
+from .varlen import validate_lengths
 
 
 class SlpEngine:
@@ -73,8 +76,13 @@ class SlpEngine:
         except Exception:
             pass
 
-    def forward(self, z_text: torch.Tensor, z_audio: torch.Tensor, return_decoded: bool = False):
-        """z_text [B,T,d], z_audio [B,S,d] (CUDA) -> logits fp32 [B,num_classes] (and the decoded sequence [B,S,d])."""
+    def forward(self, z_text: torch.Tensor, z_audio: torch.Tensor, return_decoded: bool = False, *,
+                audio_lengths=None, text_lengths=None):
+        """z_text [B,T,d], z_audio [B,S,d] (CUDA) -> logits fp32 [B,num_classes] (and the decoded sequence [B,S,d]).
+
+        `audio_lengths` / `text_lengths` (validated CPU int32 [B] of varlen.validate_lengths, or None = all rows): with
+        either given the call is ditto_slp_forward_varlen — utterance b is predicted from its own S_b audio rows and T_b
+        text rows, whatever the padding holds; with both None it is the dense entry, unchanged."""
         if z_audio.dim() != 3 or z_text.dim() != 3 or z_audio.shape[0] != z_text.shape[0]:
             raise ValueError(f"expected z_text [B,T,d] and z_audio [B,S,d], got {tuple(z_text.shape)} / "
                              f"{tuple(z_audio.shape)}")
@@ -85,9 +93,15 @@ class SlpEngine:
         T = z_text.shape[1]
         if S == 0 or T == 0:
             raise ValueError("empty audio / text sequence")
+        varlen = audio_lengths is not None or text_lengths is not None
+        if audio_lengths is not None:   # host check before the device sees anything (a no-op on SLP.decode's validated tensors)
+            audio_lengths = validate_lengths(audio_lengths, B, S, "audio_lengths")
+        if text_lengths is not None:
+            text_lengths = validate_lengths(text_lengths, B, T, "text_lengths")
         za = z_audio.detach().to(device=self.device, dtype=torch.float32).contiguous()
         zt = z_text.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        need = self.lib.ditto_slp_workspace_bytes(C.byref(self.cfg), B, S, T)
+        ws_bytes = self.lib.ditto_slp_varlen_workspace_bytes if varlen else self.lib.ditto_slp_workspace_bytes
+        need = ws_bytes(C.byref(self.cfg), B, S, T)
         if need == 0:
             raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
         if self._ws is None or self._ws.numel() < need:
@@ -95,10 +109,19 @@ class SlpEngine:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         logits = torch.empty(B, self.cfg.num_classes, dtype=torch.float32, device=self.device)
         decoded = torch.empty(B, S, d, dtype=torch.float32, device=self.device) if return_decoded else None
+        dec_ptr = None if decoded is None else decoded.data_ptr()
         with torch.cuda.device(self.device):
-            hip.check(self.lib.ditto_slp_forward(self.handle, za.data_ptr(), zt.data_ptr(), B, S, T, logits.data_ptr(),
-                                                 None if decoded is None else decoded.data_ptr(),
-                                                 self._ws.data_ptr(), self._ws.numel(), _stream()))
+            if varlen:
+                al = None if audio_lengths is None else audio_lengths.to(self.device, torch.int32)
+                tl = None if text_lengths is None else text_lengths.to(self.device, torch.int32)
+                hip.check(self.lib.ditto_slp_forward_varlen(
+                    self.handle, za.data_ptr(), zt.data_ptr(), None if al is None else al.data_ptr(),
+                    None if tl is None else tl.data_ptr(), B, S, T, logits.data_ptr(), dec_ptr, self._ws.data_ptr(),
+                    self._ws.numel(), _stream()))
+            else:
+                hip.check(self.lib.ditto_slp_forward(self.handle, za.data_ptr(), zt.data_ptr(), B, S, T,
+                                                     logits.data_ptr(), dec_ptr, self._ws.data_ptr(), self._ws.numel(),
+                                                     _stream()))
         return (logits, decoded) if return_decoded else logits
 
 
@@ -149,17 +172,45 @@ class SLP(nn.Module):
             self._engine.repack(sd())
         return self._engine
 
-    def decode(self, z_text: torch.Tensor, z_audio: torch.Tensor, return_decoded: bool = False):
-        """src/model/SpeechLP.py:50-54 on encoder outputs: z_text [B,T,d], z_audio [B,S,d] -> length logits [B,C]."""
+    def decode(self, z_text: torch.Tensor, z_audio: torch.Tensor, return_decoded: bool = False, *,
+               audio_lengths=None, text_lengths=None):
+        """src/model/SpeechLP.py:50-54 on encoder outputs: z_text [B,T,d], z_audio [B,S,d] -> length logits [B,C].
+
+        Variable-length batches.  `audio_lengths` / `text_lengths` (list, tuple or integer tensor [B], values in [1, S] /
+        [1, T]; either may be given alone, the other then means "all rows") make `logits[b]` what
+        `decode(z_text[b:b+1, :T_b], z_audio[b:b+1, :S_b])` gives for that utterance alone: the causal mask runs over its
+        own S_b positions, cross-attention over its own T_b text rows, and `length_predictor` reads its row S_b - 1.
+        What `z_audio[b, S_b:]` and `z_text[b, T_b:]` hold reaches nothing, NaN and Inf included.  With
+        `return_decoded=True`, `decoded[b, :S_b]` is the utterance's decoded sequence and `decoded[b, S_b:]` is exactly 0.
+        With both None the call is the dense entry: unchanged code, unchanged bits.
+
+        Reference-trained checkpoints: the reference collates every text to `max_length` and trains WITHOUT a mask
+        (src/utils/MLS.py), so such a checkpoint saw its text padding and `text_lengths=None` on text padded the same
+        way is the behaviour it was trained for.  Masked text (`text_lengths` given) is what a length predictor should
+        be trained with: its prediction then does not depend on how far a batch happened to be padded."""
         if self.training:
             raise NotImplementedError("ditto_tts_amd: the SLP decoder stack is inference-only (eval mode: no dropout); "
                                       "call .eval() — training it (src/TrainSLP.py) is out of scope")
+        if audio_lengths is not None or text_lengths is not None:   # on the host, before anything reaches the device
+            if z_audio.dim() != 3 or z_text.dim() != 3 or z_audio.shape[0] != z_text.shape[0]:
+                raise ValueError(f"expected z_text [B,T,d] and z_audio [B,S,d], got {tuple(z_text.shape)} / "
+                                 f"{tuple(z_audio.shape)}")
+            B = z_audio.shape[0]
+            if audio_lengths is not None:
+                audio_lengths = validate_lengths(audio_lengths, B, z_audio.shape[1], "audio_lengths")
+            if text_lengths is not None:
+                text_lengths = validate_lengths(text_lengths, B, z_text.shape[1], "text_lengths")
         if z_audio.device.type != "cuda":
             raise RuntimeError("z_audio is not on a CUDA (ROCm) device; ditto_tts_amd has no CPU path")
-        out = self.engine(z_audio.device).forward(z_text, z_audio, return_decoded)
+        out = self.engine(z_audio.device).forward(z_text, z_audio, return_decoded, audio_lengths=audio_lengths,
+                                                  text_lengths=text_lengths)
         if return_decoded:
             return out[0].to(z_audio.dtype), out[1].to(z_audio.dtype)
         return out.to(z_audio.dtype)
+
+    def predict_class(self, z_text: torch.Tensor, z_audio: torch.Tensor, *, audio_lengths=None, text_lengths=None):
+        """The predicted length class of every utterance: argmax of `decode`'s logits, int64 [B]."""
+        return self.decode(z_text, z_audio, audio_lengths=audio_lengths, text_lengths=text_lengths).argmax(-1)
 
     @torch.no_grad()
     def forward(self, text, audio):

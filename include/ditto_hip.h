@@ -998,6 +998,37 @@ void ditto_slp_destroy(ditto_slp_t m);
  * decoded (optional, may be NULL): fp32 [B,S,d], the decoder output for every position (z_audio_decoded, :52). */
 int ditto_slp_forward(ditto_slp_t m, const float* z_audio, const float* z_text, int B, int S, int T, float* logits,
                       float* decoded, void* workspace, size_t workspace_bytes, ditto_stream_t stream);
+/* ---- variable-length batches ----
+ * As ditto_slp_forward on a padded batch whose utterance b has audio_len[b] valid audio rows and text_len[b] valid text
+ * rows (device int32 [B]; either may be NULL = all rows; values are clamped to [1, S] / [1, T] in the kernels):
+ * logits[b] is what utterance b gives alone — the causal mask over its own positions, cross-attention over its own
+ * text rows, length_predictor on its row audio_len[b] - 1.  The contents of the padding rows reach nothing, NaN and Inf
+ * included.  decoded (optional): fp32 [B,S,d], rows at or past audio_len[b] exactly 0.
+ * Without `decoded` and with the option "slp_last_row" at 1 (the default) the LAST layer computes K and V for all rows
+ * and everything else for the B last rows only, its two attentions by the last-row kernel below; with 0 every layer
+ * runs the GEMM-composed attention with lengths.  Workspace: ditto_slp_varlen_workspace_bytes (it depends on the
+ * option "slp_lr_chunk": query it after setting that). */
+size_t ditto_slp_varlen_workspace_bytes(const ditto_slp_config* cfg, int B, int S, int T);
+int ditto_slp_forward_varlen(ditto_slp_t m, const float* z_audio, const float* z_text, const int32_t* audio_len,
+                             const int32_t* text_len, int B, int S, int T, float* logits, float* decoded,
+                             void* workspace, size_t workspace_bytes, ditto_stream_t stream);
+/* the GEMM-composed attention with lengths on its own (unit tests): as ditto_attention_causal_bf16 with q_len / kv_len
+ * (device int32 [B], either may be NULL) and `causal` 0 / 1.  Utterance b's query i sees keys
+ * j < kv_len[b] (and, causal, j <= i + kv_len[b] - q_len[b]); output rows at or past q_len[b] are zero; k / v rows at or
+ * past kv_len[b] and q rows at or past q_len[b] may hold anything.  Workspace: ditto_attention_causal_workspace_bytes. */
+int ditto_attention_causal_varlen_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
+                                       void* out, int ldo, const int32_t* q_len, const int32_t* kv_len, int B, int H,
+                                       int Sq, int Skv, int dh, float scale, int causal, void* workspace,
+                                       size_t workspace_bytes, ditto_stream_t stream);
+/* last-row attention on its own (unit tests): ONE query per (utterance, head), q bf16 [B, ldq], over keys
+ * 0 .. len[b] - 1 of k / v bf16 [B * Skv, ldk / ldv] (len device int32 [B], clamped to [1, Skv]; NULL = Skv); out bf16
+ * [B, ldo].  head_dim % 64 == 0, at most 2048; strides multiples of 8, q / k / v 16-byte aligned.  fp32 scores and
+ * accumulation; the keys are split into chunks of "slp_lr_chunk" keys (ditto_get_option), one workgroup each, merged
+ * in chunk order without atomics: the same bits every run.  Keys at or past len[b] are never loaded. */
+size_t ditto_attention_last_row_workspace_bytes(int B, int H, int Skv, int dh);
+int ditto_attention_last_row_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out,
+                                  int ldo, const int32_t* len, int B, int H, int Skv, int dh, float scale,
+                                  void* workspace, size_t workspace_bytes, ditto_stream_t stream);
 /* the masked attention of that stack on its own (unit parity tests): as ditto_attention_bf16 with the causal mask
  * key j <= query i + (Skv - Sq); always the GEMM-composed path (any head_dim % 64 == 0, workspace required). */
 size_t ditto_attention_causal_workspace_bytes(int B, int H, int Sq, int Skv, int dh);
