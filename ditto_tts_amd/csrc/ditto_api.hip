@@ -1922,6 +1922,23 @@ int ditto_span_mse_window(const float* eps, const float* noise, const int64_t* s
                             workspace_bytes, B, S, max_N, d, stream);
 }
 
+int ditto_span_vloss_window(const float* pred, const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca,
+                            const float* cs, const float* lw, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len,
+                            size_t n_elems, float* grad_pred, float* loss, void* workspace, size_t workspace_bytes, int B, int S,
+                            int max_N, int d, ditto_stream_t stream) {
+    const char* who = "ditto_span_vloss_window";
+    if (!loss || !workspace) return fail(DITTO_ERR_ARG, "%s: null loss / workspace", who);
+    if (!x0 || !ca || !cs) return fail(DITTO_ERR_ARG, "%s: null x0 / ca / cs", who);
+    if (int rc = check_span(who, pred, noise, seeds, cu, grad_pred, B, S, max_N, d)) return rc;
+    if (n_elems == 0 || n_elems > (size_t)S * d) return fail(DITTO_ERR_SHAPE, "%s: n_elems must lie in [1, S d]", who);
+    if ((uintptr_t)workspace % 4 || workspace_bytes < span_mse_partials(B, max_N, d) * sizeof(float))
+        return fail(DITTO_ERR_SIZE, "%s: the workspace needs %zu bytes (B x min(1024, ceil(max_N d / 1024)) floats)", who,
+                    span_mse_partials(B, max_N, d) * sizeof(float));
+    HIP_TRY(launch_span_vloss_packed(pred, x0, noise, seeds, tag, ca, cs, lw, cu, prompt_len, suffix_len, (double)n_elems, grad_pred, loss,
+                                     (float*)workspace, B, S, max_N, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 // ---- speech infilling: the update and step entries over the window [cu[b] + P_b, cu[b+1] - Q_b) ----
 int ditto_guided_update_packed_window(float* x2, const float* eps2, const float* noise, const int64_t* seeds, uint32_t step,
                                       const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,

@@ -300,6 +300,12 @@ hipError_t launch_span_noise_packed(const float* x0, const float* noise, const i
 hipError_t launch_span_mse_packed(const float* eps, const float* noise, const int64_t* seeds, unsigned tag, const int32_t* cu,
                                   const int32_t* prompt_len, const int32_t* suffix_len, double n_elems, float* grad, float* loss,
                                   float* partial, int B, int S, int max_N, int d, hipStream_t s);
+// the v objective: target = fmaf(ca[b], z, -(cs[b] x0)), the squared error weighted by lw[b] (null: 1); launch_span_mse_packed's
+// grid, partials and finish launch, and its bits where ca = 1, cs = 0 and lw is null
+hipError_t launch_span_vloss_packed(const float* pred, const float* x0, const float* noise, const int64_t* seeds, unsigned tag,
+                                    const float* ca, const float* cs, const float* lw, const int32_t* cu, const int32_t* prompt_len,
+                                    const int32_t* suffix_len, double n_elems, float* grad, float* loss, float* partial, int B, int S,
+                                    int max_N, int d, hipStream_t s);
 // ---------------- guided_rescale.hip ----------------
 // guidance rescale (Lin et al. 2024, section 3.4): coef_out[b] = coef_in[b] * s32_b with s_b = 1 + phi_b (sigma_c / sigma_e - 1) over
 // utterance b's generated rows of eps2 (e = fmaf(w, c - u, u), sums in fp64), 1 where b is unguided, phi_b == 0 or sigma_e == 0.

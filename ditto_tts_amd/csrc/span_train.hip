@@ -83,6 +83,59 @@ __global__ __launch_bounds__(256) void span_mse_packed_kernel(const float* __res
     if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = red[0];
 }
 
+// span_mse_packed_kernel for the v objective (Salimans & Ho 2022): target = fmaf(ca[b], z, -(cs[b] x0)), diff = pred - target,
+// grad = (scale2 lw[b]) diff on the generated rows and exactly 0 on the context rows (pred, x0 and noise are not read there);
+// partial[b gridDim.x + blockIdx.x] = lw[b] x this workgroup's sum of diff^2, the same lanes in the same tree — an utterance has one
+// weight, so it multiplies the workgroup's sum once.  lw NULL: weight 1.  With ca = 1, cs = 0, weight 1 and a finite x0 the target
+// is fmaf(1, z, -0) = z and every product by 1 is exact: grad and partials are span_mse_packed_kernel's bits.  One stream more than
+// that kernel (x0): 12 B per element SEEDED, 16 B with a noise buffer.
+template <bool SEEDED>
+__global__ __launch_bounds__(256) void span_vloss_packed_kernel(const float* __restrict__ pred, const float* __restrict__ x0,
+                                                                const float* __restrict__ noise, const int64_t* __restrict__ seeds,
+                                                                unsigned tag, const float* __restrict__ ca, const float* __restrict__ cs,
+                                                                const float* __restrict__ lw, const int32_t* __restrict__ cu,
+                                                                const int32_t* __restrict__ prompt_len,
+                                                                const int32_t* __restrict__ suffix_len, float scale2,
+                                                                float* __restrict__ grad, float* __restrict__ partial, int S, int d) {
+    __shared__ float red[256];
+    const int b = blockIdx.y;
+    const WindowSpan r = window_span(cu, prompt_len, suffix_len, b, S, d);
+    const float a = ca[b], s = cs[b], wt = lw ? lw[b] : 1.f;
+    const float gscale = scale2 * wt;
+    const unsigned long long seed = SEEDED ? (unsigned long long)seeds[b] : 0ull;
+    const f32x4* pp = reinterpret_cast<const f32x4*>(pred) + r.base4;
+    const f32x4* xp = reinterpret_cast<const f32x4*>(x0) + r.base4;
+    const f32x4* zp = reinterpret_cast<const f32x4*>(noise) + r.base4;
+    f32x4* gp = reinterpret_cast<f32x4*>(grad) + r.base4;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    float acc = 0.f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < r.n4; i += stride) {
+        f32x4 g = {0.f, 0.f, 0.f, 0.f};
+        if (i - r.p4 < r.g4) {                        // p4 <= i < p4 + g4, in one unsigned compare
+#pragma clang fp contract(off)      // only the written fmafs fuse: the Box-Muller product r cos and cs x0 round on their own
+            const f32x4 p = pp[i];
+            const f32x4 x = xp[i];
+            const f32x4 z = SEEDED ? normal4(seed, tag, i - r.p4) : zp[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float sx = s * x[k];
+                const float df = p[k] - fmaf(a, z[k], -sx);
+                acc = fmaf(df, df, acc);
+                g[k] = gscale * df;
+            }
+        }
+        gp[i] = g;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = red[0] * wt;
+}
+
 // loss = inv_n * (the partials summed in index order): lane l sums its contiguous share in order, lane 0 the 256 shares in order
 __global__ __launch_bounds__(256) void span_mse_finish_kernel(const float* __restrict__ partial, size_t n_partial, float inv_n,
                                                               float* __restrict__ loss) {
@@ -127,6 +180,25 @@ hipError_t launch_span_mse_packed(const float* eps, const float* noise, const in
     else
         hipLaunchKernelGGL(span_mse_packed_kernel<false>, grid, dim3(256), 0, s, eps, noise, seeds, tag, cu, prompt_len, suffix_len,
                            scale2, grad, partial, S, d);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(span_mse_finish_kernel, dim3(1), dim3(256), 0, s, partial, (size_t)B * grid.x, inv_n, loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_span_vloss_packed(const float* pred, const float* x0, const float* noise, const int64_t* seeds, unsigned tag,
+                                    const float* ca, const float* cs, const float* lw, const int32_t* cu, const int32_t* prompt_len,
+                                    const int32_t* suffix_len, double n_elems, float* grad, float* loss, float* partial, int B, int S,
+                                    int max_N, int d, hipStream_t s) {
+    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !x0 || !ca || !cs || (!noise == !seeds) || !(n_elems >= 1.0))
+        return hipErrorInvalidValue;
+    const float scale2 = (float)(2.0 / n_elems), inv_n = (float)(1.0 / n_elems);
+    const dim3 grid = guided_grid(max_N, d, B);       // span_mse_packed's grid: the same partial layout and workspace
+    if (seeds)
+        hipLaunchKernelGGL(span_vloss_packed_kernel<true>, grid, dim3(256), 0, s, pred, x0, noise, seeds, tag, ca, cs, lw, cu, prompt_len,
+                           suffix_len, scale2, grad, partial, S, d);
+    else
+        hipLaunchKernelGGL(span_vloss_packed_kernel<false>, grid, dim3(256), 0, s, pred, x0, noise, seeds, tag, ca, cs, lw, cu, prompt_len,
+                           suffix_len, scale2, grad, partial, S, d);
     if (hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(span_mse_finish_kernel, dim3(1), dim3(256), 0, s, partial, (size_t)B * grid.x, inv_n, loss);
     return hipGetLastError();

@@ -499,6 +499,30 @@ class DenoiseEngine:
                                                  part.numel() * 4, B, S, max_N, d, _stream()))
         return loss, grad
 
+    def span_vloss_packed(self, pred: torch.Tensor, x0: torch.Tensor, cu_seqlens, prompt_lengths, ca: torch.Tensor, cs: torch.Tensor,
+                          lw=None, seeds=None, tag: int = 0, noise=None, suffix_lengths=None):
+        """(loss fp32 [], grad_pred fp32 [S, d]) of the v objective over the generated rows (ditto_span_vloss_window): target =
+        ca[b] z - cs[b] x0, squared error weighted by lw[b] (fp32 CUDA [B], or None: 1).  prompt_lengths and suffix_lengths may each
+        be None."""
+        if prompt_lengths is None and suffix_lengths is None:
+            prompt_lengths = [0] * (len(cu_seqlens) - 1)
+        cud, pld, B, max_N, gen_rows, sd, noise, qld = self._span_args("span_vloss_packed", pred, cu_seqlens, prompt_lengths, seeds, noise,
+                                                                       suffix_lengths)
+        if not (x0.is_cuda and x0.dtype == torch.float32 and x0.is_contiguous() and x0.shape == pred.shape):
+            raise ValueError(f"x0 must be a contiguous fp32 CUDA tensor of shape {list(pred.shape)}")
+        for name, v in (("ca", ca), ("cs", cs), ("lw", lw)):
+            if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B,)):
+                raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{B}]")
+        S, d = int(pred.shape[0]), int(pred.shape[1])
+        grad = torch.empty_like(pred)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        part = torch.empty(B * min(1024, (max_N * d // 4 + 255) // 256), dtype=torch.float32, device=pred.device)
+        hip.check(self.lib.ditto_span_vloss_window(pred.data_ptr(), x0.data_ptr(), _ptr(noise), _ptr(sd), int(tag) & 0xFFFFFFFF,
+                                                   ca.data_ptr(), cs.data_ptr(), _ptr(lw), cud.data_ptr(), _ptr(pld), _ptr(qld),
+                                                   gen_rows * d, grad.data_ptr(), loss.data_ptr(), part.data_ptr(), part.numel() * 4,
+                                                   B, S, max_N, d, _stream()))
+        return loss, grad
+
     def _lengths(self, speech_lengths, cond: TextCond, B: int, N: int, halves: int = 1):
         """(speech, text) device int32 [halves * B] of a varlen call, or None for a dense one.  `speech_lengths`: the B
         utterances' (list / tuple / int tensor), repeated by each half of a guided [x; x] (halves 2); the text lengths are the

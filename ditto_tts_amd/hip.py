@@ -253,6 +253,8 @@ SYMBOLS = {
                                                        + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_span_noise_window": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ditto_span_mse_window": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    # the v objective's span loss: x0, (ca, cs) and per-utterance weights beside ditto_span_mse_window's arguments
+    "ditto_span_vloss_window": (_i, [_vp] * 4 + [C.c_uint32] + [_vp] * 6 + [_sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),
     "ditto_regroup_cond_layout": (_i, [C.POINTER(Config), _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),

@@ -225,6 +225,43 @@ class _SpanLossFn(torch.autograd.Function):
         return (grad * g).to(ctx.eps_dtype), None, None, None, None, None, None, None
 
 
+class _SpanVLossFn(torch.autograd.Function):
+    """DiTTO.span_loss_packed(prediction="v"): the weighted v loss and its gradient with respect to the prediction in one launch of
+    ditto_span_vloss_window"""
+
+    @staticmethod
+    def forward(ctx, pred, eng, x0, ca, cs, lw, cu_seqlens, prompt_lengths, seeds, tag, noise, suffix_lengths):
+        loss, grad = eng.span_vloss_packed(pred.detach().float().contiguous(), x0, cu_seqlens, prompt_lengths, ca, cs, lw, seeds=seeds,
+                                           tag=tag, noise=noise, suffix_lengths=suffix_lengths)
+        ctx.save_for_backward(grad)
+        ctx.pred_dtype = pred.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return ((grad * g).to(ctx.pred_dtype),) + (None,) * 11
+
+
+def loss_weight_vector(loss_weights, B: int):
+    """`loss_weights` (None, or a list / tuple / tensor of B finite numbers >= 0) as a CPU fp32 tensor [B], or None"""
+    if loss_weights is None:
+        return None
+    if isinstance(loss_weights, torch.Tensor):
+        if loss_weights.dtype == torch.bool or loss_weights.is_complex():
+            raise ValueError(f"loss_weights: a real tensor is needed, got {loss_weights.dtype}")
+        w = loss_weights.detach().to("cpu", torch.float32)
+    elif isinstance(loss_weights, (list, tuple)) and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in loss_weights):
+        w = torch.tensor([float(v) for v in loss_weights], dtype=torch.float32)
+    else:
+        raise ValueError(f"loss_weights: None, a list / tuple of {B} numbers or a tensor [{B}] is needed")
+    if w.dim() != 1 or w.shape[0] != B:
+        raise ValueError(f"loss_weights: shape [{B}] expected, got {list(w.shape)}")
+    if not (torch.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("loss_weights: every weight must be finite and >= 0")
+    return w.contiguous()
+
+
 class DiTTO(nn.Module):
     """Full DiT noise predictor — reference src/model/DiTTO.py:7-126.
 
@@ -483,16 +520,50 @@ class DiTTO(nn.Module):
                                      (1.0 - c).sqrt().contiguous(), seeds=seeds, tag=tag, noise=noise,
                                      suffix_lengths=suffix_lengths)
 
-    def span_loss_packed(self, eps, cu_seqlens, prompt_lengths, *, seeds=None, tag=0, noise=None, suffix_lengths=None):
+    def span_loss_packed(self, eps, cu_seqlens, prompt_lengths, *, seeds=None, tag=0, noise=None, suffix_lengths=None,
+                         prediction="eps", x0=None, t=None, loss_weights=None):
         """The span-masked MSE of a packed batch with speech prompts: mean over the GENERATED rows' elements of (eps - z)^2, z as in
         span_noise_packed (the same `noise`, or the same `seeds` and `tag`).  A scalar attached to autograd: backward() hands
         grad_output * (2 / n)(eps - z) — exactly 0 on the prompt rows, whatever eps holds there — to eps's producer
         (train_forward_packed).  Loss and gradient come from one kernel that reads eps once; the reduction is ordered, so the same
         call twice gives the same bits.
         `suffix_lengths`: as in span_noise_packed — the mean runs over the window's d x sum of G_b elements and the gradient is
-        exactly 0 on both contexts.  None: the call as it was."""
+        exactly 0 on both contexts.  None: the call as it was.
+        `prediction`: "eps" (default: the call as it was; `x0`, `t` and `loss_weights` then raise ValueError), or "v" — the network
+        is trained to predict v = ca z - cs x0 (Salimans & Ho 2022), the parameterisation a near-zero terminal SNR needs (Lin et al.
+        2024): the mean over the generated elements of lw_b (pred - v)^2 from one kernel (ditto_span_vloss_window) that regenerates z
+        as above and reads `x0` (the clean latents span_noise_packed was given, [S, d]) beside the prediction.  `t` (the timesteps
+        span_noise_packed was given, [B]) picks (ca, cs) exactly as that call does — sqrt(c) and sqrt(1 - c) of the same mis-named
+        buffer, bug for bug — so x_in = ca x0 + cs z and v = ca z - cs x0 are consistent whatever c is: ca^2 + cs^2 = 1.  Both are
+        required.  `loss_weights` (None, or a list / tuple / tensor of B finite values >= 0): a per-utterance weight on the squared
+        error and its gradient, which makes timestep weightings one host line — e.g. min-SNR-gamma for v (Hang et al. 2023), with
+        snr = c / (1 - c): [min(s, gamma) / (s + 1) for s in snr].  The gradient is exactly 0 on the context rows and on every row
+        of an utterance whose weight is 0.  A model trained this way is sampled with sample_guided_packed(prediction="v") over the
+        table it was trained on."""
+        if prediction not in ("eps", "v"):
+            raise ValueError(f"prediction: one of ('eps', 'v') is needed, got {prediction!r}")
+        if prediction == "eps":
+            for name, v in (("x0", x0), ("t", t), ("loss_weights", loss_weights)):
+                if v is not None:
+                    raise ValueError(f'{name}= belongs to prediction="v": the eps loss takes no clean latents, timesteps or weights')
+            _require_cuda(eps, "eps")
+            return _SpanLossFn.apply(eps, self.engine(eps.device), cu_seqlens, prompt_lengths, seeds, tag, noise, suffix_lengths)
+        for name, v in (("x0", x0), ("t", t)):
+            if v is None:
+                raise ValueError(f'prediction="v" needs {name}= (what span_noise_packed was given)')
+        B = len(cu_seqlens) - 1
+        lw = loss_weight_vector(loss_weights, B)
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.shape[0] != B or t.dtype.is_floating_point:
+            raise ValueError(f"t: an integer tensor [{B}] is needed")
+        if not isinstance(x0, torch.Tensor) or x0.shape != eps.shape:
+            raise ValueError(f"x0: a tensor of the prediction's shape {list(eps.shape)} is needed")
         _require_cuda(eps, "eps")
-        return _SpanLossFn.apply(eps, self.engine(eps.device), cu_seqlens, prompt_lengths, seeds, tag, noise, suffix_lengths)
+        _require_cuda(x0, "x0")
+        eng = self.engine(eps.device)
+        c = self.alphas_cumprod.to(eps.device).float()[t.to(eps.device).long()]           # span_noise_packed's lines, to the letter
+        return _SpanVLossFn.apply(eps, eng, x0.detach().float().contiguous(), c.sqrt().contiguous(), (1.0 - c).sqrt().contiguous(),
+                                  None if lw is None else lw.to(eps.device), cu_seqlens, prompt_lengths, seeds, tag, noise,
+                                  suffix_lengths)
 
     def cosine_beta_schedule(self, timesteps, s=0.008):
         """Reference src/model/DiTTO.py:96-104 (a dozen-element host-side table, torch ops as in the reference)."""

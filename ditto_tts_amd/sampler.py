@@ -52,7 +52,34 @@ def strided_schedule(alphas_cumprod: torch.Tensor, n_steps: int, eta: float = 0.
     return out
 
 
+def strided_schedule_v(alphas_cumprod: torch.Tensor, n_steps: int, eta: float = 0.0):
+    """strided_schedule for a network that predicts v = alpha z - sigma x0 (Salimans & Ho 2022; Lin et al. 2024 section 3.2) instead of
+    the noise: a list of (tau_i, a_v, cv, sigma), x' = a_v x + cv v + sigma z at step i, over the same timesteps and with the same
+    sigma.  With x0 = alpha x - sigma_t v and eps = sigma_t x + alpha v (alpha = sqrt(abar), sigma_t = sqrt(1 - abar) at tau_i),
+    alpha' = sqrt(abar') and c' = sqrt(clamp(1 - abar' - sigma^2, 0)): a_v = alpha' alpha + c' sigma_t and cv = c' alpha - alpha'
+    sigma_t — each a sum of two products of numbers in [0, 1], so |a_v|, |cv| <= sqrt(2) at every step.  It is NOT computed as
+    a + ce sigma_t from the eps form: at tau_0 of the cosine table 1 / alpha is ~100 and that is a difference of two numbers of that
+    size.  The row layout is strided_schedule's: the fused updates are linear in the network's output, so a v step is the eps
+    step's launch with (a_v, cv) in place of (a, ce).  float64, returned as Python floats."""
+    T = int(alphas_cumprod.shape[0])
+    if not 1 <= n_steps <= T:
+        raise ValueError("n_steps must be in [1, diffusion_steps]")
+    stride = T / n_steps
+    taus = [int(round(T - 1 - i * stride)) for i in range(n_steps)]
+    ac = alphas_cumprod.double().cpu()
+    out = []
+    for i, t_val in enumerate(taus):
+        ab_t = ac[t_val]
+        ab_p = ac[taus[i + 1]] if i + 1 < n_steps else torch.tensor(1.0, dtype=torch.float64)
+        sigma = eta * torch.sqrt((1 - ab_p) / (1 - ab_t)) * torch.sqrt(1 - ab_t / ab_p)       # strided_schedule's, to the bit
+        al_t, sg_t, al_p = torch.sqrt(ab_t), torch.sqrt(1 - ab_t), torch.sqrt(ab_p)
+        c_p = torch.sqrt(torch.clamp(1 - ab_p - sigma ** 2, min=0.0))
+        out.append((t_val, float(al_p * al_t + c_p * sg_t), float(c_p * al_t - al_p * sg_t), float(sigma)))
+    return out
+
+
 SOLVERS = ("ddim", "dpmpp2m")
+PREDICTIONS = ("eps", "v")
 
 
 def multistep_schedule(alphas_cumprod: torch.Tensor, n_steps: int):
@@ -86,6 +113,29 @@ def multistep_schedule(alphas_cumprod: torch.Tensor, n_steps: int):
             b, g = c * (1.0 + 0.5 / r), -c * 0.5 / r
         out.append((t_val, sigma[i + 1] / sigma[i], kx, ke, b, g, i > 0))
     return out
+
+
+def multistep_schedule_v(alphas_cumprod: torch.Tensor, n_steps: int):
+    """multistep_schedule for a network that predicts v (strided_schedule_v): the same rows except the data prediction, x0 = kx x +
+    ke v with kx = alpha_i and ke = -sigma_i — no division by alpha.  a, b, g and use_prev act on x, x0 and the history and do not
+    depend on the parameterisation."""
+    ac = alphas_cumprod.double().cpu()
+    return [(t_val, a, math.sqrt(float(ac[t_val])), -math.sqrt(1.0 - float(ac[t_val])), b, g, use_prev)
+            for t_val, a, _, _, b, g, use_prev in multistep_schedule(alphas_cumprod, n_steps)]
+
+
+def validate_prediction(prediction):
+    """`prediction`: what the network's output is — "eps" (the noise, the reference's objective) or "v" (v = alpha z - sigma x0)"""
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction: one of {PREDICTIONS} is needed, got {prediction!r}")
+    return prediction
+
+
+def _padded_prediction(prediction):
+    """the padded layouts sample eps-predicting networks only"""
+    if validate_prediction(prediction) != "eps":
+        raise NotImplementedError(f"prediction={prediction!r} is served over packed batches: pack the batch and call "
+                                  "sample_guided_packed(prediction=)")
 
 
 def validate_guidance_interval(interval, diffusion_steps: int):
@@ -354,7 +404,7 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
                                cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None, prompt_lengths=None,
-                               solver="ddim", guidance_rescale=None, suffix_lengths=None):
+                               solver="ddim", guidance_rescale=None, suffix_lengths=None, prediction="eps"):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
         DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step, with optional
         classifier-free guidance: the step runs ONE forward on the doubled batch [x; x] x [text; null_text] and combines
@@ -364,6 +414,7 @@ class SpeechGenerator:
         _padded_suffix(suffix_lengths)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
+        _padded_prediction(prediction)
         if speech_lengths is not None or text_lengths is not None:
             raise NotImplementedError("sample_latents_strided has no varlen form: a variable-length batch runs sample_guided "
                                       "(guided strided loop) or the ancestral sample_latents")
@@ -373,7 +424,7 @@ class SpeechGenerator:
 
     # ---------------------------------------------------------------- guided strided loop over a variable-length batch
     def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval=None,
-                     begin_plain=None, rescale=None):
+                     begin_plain=None, rescale=None, prediction="eps"):
         """The strided loop of sample_guided and sample_guided_packed.  `begin(eng, cfg, seeds)` is the layout's own prologue: it
         builds the conditioning and the state x2 (rows [x_T; room for the unconditional half] under guidance, else x_T) and returns
         (x2, max length, step) with `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)` the layout's library call bound to
@@ -384,13 +435,14 @@ class SpeechGenerator:
         behind unguided steps; in between every guided update writes both halves itself.  With no guided step at all the call is
         the one without guidance.
         `rescale` (rescale_vector's phi [B], packed batches): every guided step computes each utterance's guidance-rescale factor
-        from its eps and updates with ce s32 (the step's phi= argument); unguided steps rescale nothing."""
+        from its eps and updates with ce s32 (the step's phi= argument); unguided steps rescale nothing.
+        `prediction` "v" (packed batches): the rows of strided_schedule_v — (a_v, cv) travel where (a, ce) do, to the same launches."""
         if seeds is not None and noises is not None:
             raise ValueError("seeds= excludes noises=")
         gv = guidance_vector(guidance, B)
         if gv is not None and null_text_emb is None:
             raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
-        schedule = strided_schedule(self.alphas_cumprod, n_steps, eta)
+        schedule = (strided_schedule_v if prediction == "v" else strided_schedule)(self.alphas_cumprod, n_steps, eta)
         guided = guided_steps(schedule, interval)
         cfg = gv is not None and any(guided)
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)   # "cuda" -> cuda:0: the engine the other loops use
@@ -437,18 +489,19 @@ class SpeechGenerator:
         return x2[:rows].clone() if cfg else x2
 
     def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval=None, begin_plain=None,
-                        rescale=None):
+                        rescale=None, prediction="eps"):
         """_guided_loop for solver="dpmpp2m": the same prologue (`begin`, whose step is engine.guided_step_packed_multistep_ bound to
         x2, its conditioning and offsets), then one library call per step of multistep_schedule over x2 and the history q — one
         buffer [S, d] per call, written by step 0 before any step reads it.  Each step's coefficients travel as a host struct.
         `rescale` (rescale_vector's phi [B]): the guided steps read their coefficients from DEVICE memory instead — one
         ditto_multistep_coef per utterance and step, uploaded once, the guidance scale inside — so that the rescale can patch each
-        utterance's ke before the per-utterance update runs."""
+        utterance's ke before the per-utterance update runs.
+        `prediction` "v": the rows of multistep_schedule_v, (kx, ke) = (alpha, -sigma), to the same launches."""
         from .hip import CallOpts, MultistepCoef
         gv = guidance_vector(guidance, B)
         if gv is not None and null_text_emb is None:
             raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
-        schedule = multistep_schedule(self.alphas_cumprod, n_steps)
+        schedule = (multistep_schedule_v if prediction == "v" else multistep_schedule)(self.alphas_cumprod, n_steps)
         guided = guided_steps(schedule, interval)           # (interval, begin_plain: as in _guided_loop)
         cfg = gv is not None and any(guided)
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
@@ -493,7 +546,7 @@ class SpeechGenerator:
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
                       null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
                       cond_by_audio=False, batch_class=None, prompt_lengths=None, solver="ddim", guidance_rescale=None,
-                      suffix_lengths=None):
+                      suffix_lengths=None, prediction="eps"):
         """The strided (DDIM) loop of sample_latents_strided with what serving needs: per-utterance `speech_lengths` /
         `text_lengths` (a padded batch; rows past an utterance's length are exactly 0 in the result and padding never reaches a
         valid row), per-utterance `guidance` (None: no CFG; a number; or [B] numbers), and per-utterance `seeds`.  One library
@@ -507,12 +560,13 @@ class SpeechGenerator:
         callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
         count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
         The padded layout has no speech prompts (`prompt_lengths` raises NotImplementedError): pack the batch and call
-        sample_guided_packed; so do solver="dpmpp2m", `guidance_rescale` and `suffix_lengths`.  Returns fp32 [B, N, d]."""
+        sample_guided_packed; so do solver="dpmpp2m", `guidance_rescale`, `suffix_lengths` and prediction="v".  Returns fp32 [B, N, d]."""
         _padded_solver(solver)
         _padded_rescale(guidance_rescale)
         _padded_suffix(suffix_lengths)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
+        _padded_prediction(prediction)
         B, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
 
         def begin(eng, cfg, seeds):
@@ -546,7 +600,7 @@ class SpeechGenerator:
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
                              batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None, guidance_rescale=None,
-                             suffix_lengths=None):
+                             suffix_lengths=None, prediction="eps"):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -586,9 +640,18 @@ class SpeechGenerator:
         alone.  Works without `prompt_lengths` (P = 0) and with guidance, seeds, noises, batch_class, both solvers and a
         `guidance_interval`; `guidance_rescale` with it raises NotImplementedError (the statistics run over prompt-to-end rows).  A
         model fills a window only if it was trained with spans anywhere (DiTTO.span_noise_packed(suffix_lengths=)); the effect on
-        speech quality has not been measured.  None: the call as it was, whatever `prompt_lengths` is.  Returns fp32 [S, d]."""
+        speech quality has not been measured.  None: the call as it was, whatever `prompt_lengths` is.
+        `prediction`: "eps" (default: the call as it was) or "v" — the network's output is v = alpha z - sigma x0 (Salimans & Ho
+        2022), the parameterisation a near-zero terminal SNR needs (Lin et al. 2024 section 3.2: x0 = alpha x - sigma v divides by
+        nothing, where the eps form's 1 / alpha is ~100 at the cosine table's last timestep).  The loops, launches and kernels are
+        the same: the updates are linear in the network's output and so is CFG, so a v step is the eps step with the coefficients
+        of strided_schedule_v / multistep_schedule_v.  Every other argument works as above; `guidance_rescale` matches the standard
+        deviations of the network's outputs as they are (v).  The model must have been trained on v (DiTTO.span_loss_packed(
+        prediction="v")) and on this object's alphas_cumprod table; nothing here has been run with a trained model.
+        Returns fp32 [S, d]."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
+        validate_prediction(prediction)
         interval = None if guidance_interval is None else validate_guidance_interval(guidance_interval, self.diffusion_steps)
         if interval is not None and (guidance is None or null_text_emb is None):
             raise ValueError("guidance_interval needs guidance= and null_text_emb=")
@@ -671,11 +734,13 @@ class SpeechGenerator:
             return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets)
 
         if multistep:
-            return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval, begin_plain, rescale)
+            return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval, begin_plain, rescale,
+                                        prediction)
         return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval, begin_plain,
-                                 rescale)
+                                 rescale, prediction)
 
-    def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim", infill=False):
+    def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim", infill=False,
+                      prediction="eps"):
         """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an
         utterance, step() admits what fits, runs one guided strided step over everything in flight — each utterance at its own
         index of its own strided_schedule — and returns the finished ones.  `max_rows` / `max_utterances` / `max_text_rows`: the
@@ -685,9 +750,13 @@ class SpeechGenerator:
         one solver per stream.
         `infill`: the stream accepts submit(..., suffix=[Q, d]) — speech infilling, clean rows behind the generated frames as
         `prompt` puts them in front (sample_guided_packed(suffix_lengths=)) — and refuses guidance_interval= / guidance_rescale=.
-        False: the stream as it was."""
+        False: the stream as it was.
+        `prediction`: "eps", or "v" — every request's per-step coefficients come from strided_schedule_v / multistep_schedule_v
+        (sample_guided_packed(prediction=)); one parameterisation per stream, as a stream serves one model.  Admission, tags and
+        launches are unchanged."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
+        validate_prediction(prediction)
         from .serving import DeviceBatch, GuidedStream
         require_fused_attention(self.ditto_model.cfg, "request streams (packed batches)")
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
@@ -695,7 +764,7 @@ class SpeechGenerator:
                             class_rows=class_rows, solver=solver, infill=infill)
         return GuidedStream(batch, self.alphas_cumprod, max_rows=max_rows, max_utterances=max_utterances,
                             max_text_rows=max_text_rows, guided=guided, text_dim=eng.cfg.text_dim, hidden_dim=eng.cfg.hidden_dim,
-                            solver=solver, infill=infill)
+                            solver=solver, infill=infill, prediction=prediction)
 
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):

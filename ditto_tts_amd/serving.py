@@ -173,14 +173,17 @@ class GuidedStream:
     `n_frames` generated rows at every step, as `prompt` is kept in front (sample_guided_packed(suffix_lengths=)).  The request
     occupies P + n_frames + Q of `max_rows`; `x_T` and the result stay [n_frames, d].  An infill stream refuses
     `guidance_interval` and `guidance_rescale` (NotImplementedError: neither update has a windowed form); with no suffixed request in
-    flight it runs the entries a plain stream runs."""
+    flight it runs the entries a plain stream runs.
+    `prediction` (one per stream): "eps", or "v" — the requests' coefficients come from strided_schedule_v / multistep_schedule_v
+    (sample_guided_packed(prediction="v")); nothing else changes."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
-                 text_dim: int, hidden_dim: int, solver: str = "ddim", infill: bool = False):
-        from .sampler import SOLVERS
+                 text_dim: int, hidden_dim: int, solver: str = "ddim", infill: bool = False, prediction: str = "eps"):
+        from .sampler import SOLVERS, validate_prediction
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         self.solver, self.infill = solver, bool(infill)
+        self.prediction = validate_prediction(prediction)
         for name, v in (("max_rows", max_rows), ("max_utterances", max_utterances), ("max_text_rows", max_text_rows)):
             if not _is_int(v) or v < 1:
                 raise ValueError(f"{name}: a positive int is needed, got {v!r}")
@@ -208,9 +211,10 @@ class GuidedStream:
     def _schedule(self, n_steps: int, eta: float):
         key = (n_steps, eta)
         if key not in self._schedules:
-            from .sampler import multistep_schedule, strided_schedule
-            self._schedules[key] = (strided_schedule(self._acp, n_steps, eta) if self.solver == "ddim" else
-                                    multistep_schedule(self._acp, n_steps))
+            from .sampler import multistep_schedule, multistep_schedule_v, strided_schedule, strided_schedule_v
+            v = self.prediction == "v"                                 # the same row layouts: (a_v, cv) for (a, ce), v-form (kx, ke)
+            self._schedules[key] = ((strided_schedule_v if v else strided_schedule)(self._acp, n_steps, eta) if self.solver == "ddim"
+                                    else (multistep_schedule_v if v else multistep_schedule)(self._acp, n_steps))
         return self._schedules[key]
 
     def _text(self, t, name):

@@ -773,6 +773,23 @@ int ditto_span_noise_window(const float* x0, const float* noise, const int64_t* 
 int ditto_span_mse_window(const float* eps, const float* noise, const int64_t* seeds, uint32_t tag, const int32_t* cu,
                           const int32_t* prompt_len, const int32_t* suffix_len, size_t n_elems, float* grad_eps, float* loss,
                           void* workspace, size_t workspace_bytes, int B, int S, int max_N, int d, ditto_stream_t stream);
+/* ditto_span_vloss_window: the span loss of a network that predicts v = alpha z - sigma x0 (Salimans & Ho 2022) instead of the noise,
+ *   over the window of ditto_span_mse_window — except that suffix_len may be NULL here as prompt_len may (both NULL: the whole
+ *   utterance).  Per generated element of utterance b: target = fmaf(ca[b], z, -(cs[b] x0)), diff = pred - target; loss[0] = (1 /
+ *   n_elems) sum of lw[b] diff^2 and grad_pred = (2 / n_elems) lw[b] diff; grad_pred is exactly 0 on both context regions, where pred,
+ *   x0 and `noise` are not read.  z: `noise` or Philox of (seeds[b], tag) at the window-local quad index, exactly one of the two, as
+ *   above.  ca, cs: device fp32 [B], the pair ditto_span_noise_window noised x0 with (x_in = ca x0 + cs z, so ca^2 + cs^2 = 1 makes
+ *   target the v of that x_in).  lw: device fp32 [B] per-utterance loss weights, or NULL (all 1): a timestep weighting such as
+ *   min-SNR-gamma is one host line.  x0: fp32 [S, d], one stream more than the MSE reads (12 B per generated element with seeds, 16 B
+ *   with `noise`).  The walk, the partial layout, the workspace size and the ordered two-launch reduction are ditto_span_mse_window's:
+ *   no atomics, a repeated call gives the same bits.
+ * Contract: with ca = 1, cs = 0, lw NULL and a finite x0, grad_pred, loss and the partials in `workspace` are bit-equal to
+ *   ditto_span_mse_window's on the same pred / noise / seeds (fmaf(1, z, -0) = z).  The reference has no v objective: like the
+ *   samplers above this is pinned by its own formulas. */
+int ditto_span_vloss_window(const float* pred, const float* x0, const float* noise, const int64_t* seeds, uint32_t tag, const float* ca,
+                            const float* cs, const float* lw, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len,
+                            size_t n_elems, float* grad_pred, float* loss, void* workspace, size_t workspace_bytes, int B, int S,
+                            int max_N, int d, ditto_stream_t stream);
 /* ditto_regroup_packed: build the next packed batch from the current one plus the newcomers, in ONE launch driven by a DEVICE table
  *   of n_seg segments.  A segment moves `n` 16-byte units (every row of the state, the K/V cache and tmod is a whole number of them)
  *   to unit dst_off of destination buffer `dest` and, when dup_off != 0, also to dst_off + dup_off (a speech segment under CFG: the
