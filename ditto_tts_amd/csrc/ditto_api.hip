@@ -1134,6 +1134,102 @@ int ditto_layernorm_bf16(const float* x, const float* gamma, const float* beta, 
     return DITTO_OK;
 }
 
+// ---- the forward row kernels on their own (unit tests): one launch_* each, after the checks that keep the launch inside what the
+// caller described
+static bool misaligned(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) != 0; }
+
+static int check_adaln_rows(const char* who, const float* x, const float* ttab, const float* tmod, int steps, const void* h_out,
+                            int h_is_bf16, const void* raw_bf16, int ldraw, const float* g1, const float* be1, const void* u1_bf16,
+                            long long rows, int d) {
+    if (!x || !ttab || !tmod || !h_out) return fail(DITTO_ERR_ARG, "null pointer to %s", who);
+    if (u1_bf16 && (!g1 || !be1)) return fail(DITTO_ERR_ARG, "%s: u1_bf16 needs g1 and be1", who);
+    if (rows <= 0 || rows > 0x7FFFFFFF || d <= 0) return fail(DITTO_ERR_SHAPE, "%s: the row count and d must be positive", who);
+    if (d % 4 || d > 2048) return fail(DITTO_ERR_SHAPE, "%s: d must be a multiple of 4 and <= 2048", who);
+    if (steps <= 0) return fail(DITTO_ERR_SHAPE, "%s: steps (the rows of ttab) must be positive", who);
+    if (raw_bf16 && (ldraw < d || ldraw % 4)) return fail(DITTO_ERR_SHAPE, "%s: ldraw must cover d columns in multiples of 4", who);
+    if (misaligned(x, 16) || misaligned(ttab, 16) || misaligned(tmod, 16) || misaligned(h_out, h_is_bf16 ? 8 : 16) ||
+        misaligned(raw_bf16, 8) || misaligned(g1, 16) || misaligned(be1, 16) || misaligned(u1_bf16, 8))
+        return fail(DITTO_ERR_ARG, "%s: fp32 rows must be 16-byte aligned, bf16 rows 8-byte aligned", who);
+    return DITTO_OK;
+}
+
+int ditto_adaln_rows(const float* x, const float* ttab, const float* tmod, const int64_t* t, int steps, void* h_out,
+                     int h_is_bf16, void* raw_bf16, int ldraw, const float* g1, const float* be1, void* u1_bf16, int B, int N,
+                     int d, ditto_stream_t stream) {
+    const char* who = "ditto_adaln_rows";
+    if (B <= 0 || N <= 0) return fail(DITTO_ERR_SHAPE, "%s: B and N must be positive", who);
+    if (int rc = check_adaln_rows(who, x, ttab, tmod, steps, h_out, h_is_bf16, raw_bf16, ldraw, g1, be1, u1_bf16, (long long)B * N, d))
+        return rc;
+    HIP_TRY(launch_adaln(x, ttab, tmod, t, steps, (float*)h_out, raw_bf16, ldraw, B, N, d, (hipStream_t)stream, h_is_bf16 != 0,
+                         u1_bf16 ? g1 : nullptr, u1_bf16 ? be1 : nullptr, u1_bf16));
+    return DITTO_OK;
+}
+
+int ditto_adaln_rows_packed(const float* x, const float* ttab, const float* tmod, const int64_t* t, int steps,
+                            const int32_t* utt, void* h_out, int h_is_bf16, void* raw_bf16, int ldraw, const float* g1,
+                            const float* be1, void* u1_bf16, int S, int d, ditto_stream_t stream) {
+    const char* who = "ditto_adaln_rows_packed";
+    if (!utt) return fail(DITTO_ERR_ARG, "%s: null utt", who);
+    if (int rc = check_adaln_rows(who, x, ttab, tmod, steps, h_out, h_is_bf16, raw_bf16, ldraw, g1, be1, u1_bf16, S, d)) return rc;
+    HIP_TRY(launch_adaln_packed(x, ttab, tmod, t, steps, utt, (float*)h_out, raw_bf16, ldraw, S, d, (hipStream_t)stream,
+                                h_is_bf16 != 0, u1_bf16 ? g1 : nullptr, u1_bf16 ? be1 : nullptr, u1_bf16));
+    return DITTO_OK;
+}
+
+int ditto_splitk_finish(const float* partial, int nsplit, size_t stride, const float* bias, const float* residual, float* out,
+                        void* out2_bf16, int ldo2, const float* gamma, const float* beta, void* u_bf16, int ldu, int M, int N,
+                        ditto_stream_t stream) {
+    const char* who = "ditto_splitk_finish";
+    if (!partial || !out) return fail(DITTO_ERR_ARG, "null pointer to %s", who);
+    if (u_bf16 && (!gamma || !beta)) return fail(DITTO_ERR_ARG, "%s: u_bf16 needs gamma and beta", who);
+    if (nsplit <= 0 || M <= 0 || N <= 0) return fail(DITTO_ERR_SHAPE, "%s: nsplit, M and N must be positive", who);
+    if (N % 4) return fail(DITTO_ERR_SHAPE, "%s: N must be a multiple of 4", who);
+    if (nsplit > 1 && (stride < (size_t)M * N || stride % 4))
+        return fail(DITTO_ERR_SHAPE, "%s: stride must cover M * N elements in multiples of 4", who);
+    if (out2_bf16 && (ldo2 < N || ldo2 % 4)) return fail(DITTO_ERR_SHAPE, "%s: ldo2 must cover N columns in multiples of 4", who);
+    if (u_bf16 && N > 2048) return fail(DITTO_ERR_SHAPE, "%s: the fused LayerNorm needs N <= 2048", who);
+    if (u_bf16 && (ldu < N || ldu % 4)) return fail(DITTO_ERR_SHAPE, "%s: ldu must cover N columns in multiples of 4", who);
+    if (misaligned(partial, 16) || misaligned(bias, 16) || misaligned(residual, 16) || misaligned(out, 16) ||
+        misaligned(out2_bf16, 8) || misaligned(gamma, 16) || misaligned(beta, 16) || misaligned(u_bf16, 8))
+        return fail(DITTO_ERR_ARG, "%s: fp32 rows must be 16-byte aligned, bf16 rows 8-byte aligned", who);
+    HIP_TRY(launch_splitk_finish(partial, nsplit, stride, bias, residual, out, out2_bf16, ldo2, M, N, (hipStream_t)stream,
+                                 u_bf16 ? gamma : nullptr, u_bf16 ? beta : nullptr, u_bf16, ldu));
+    return DITTO_OK;
+}
+
+int ditto_text_mod(const float* text, const int32_t* text_len, const float* wx, const float* bx, float* pooled, float* tmod,
+                   int B, int T, int dt, int d, ditto_stream_t stream) {
+    if (!text || !wx || !bx || !pooled || !tmod) return fail(DITTO_ERR_ARG, "null pointer to ditto_text_mod");
+    if (B <= 0 || T <= 0 || dt <= 0 || d <= 0 || B > 65535) return fail(DITTO_ERR_SHAPE, "ditto_text_mod: B (<= 65535), T, dt and d must be positive");
+    HIP_TRY(launch_text_mod(text, wx, bx, pooled, tmod, B, T, dt, d, (hipStream_t)stream, text_len));
+    return DITTO_OK;
+}
+
+int ditto_text_mod_packed(const float* text, const int32_t* cu_text, int S_T, int max_T, const float* wx, const float* bx,
+                          float* pooled, float* tmod, int B, int dt, int d, ditto_stream_t stream) {
+    if (!text || !cu_text || !wx || !bx || !pooled || !tmod) return fail(DITTO_ERR_ARG, "null pointer to ditto_text_mod_packed");
+    if (B <= 0 || S_T <= 0 || max_T <= 0 || dt <= 0 || d <= 0 || B > 65535)
+        return fail(DITTO_ERR_SHAPE, "ditto_text_mod_packed: B (<= 65535), S_T, max_T, dt and d must be positive");
+    HIP_TRY(launch_text_mod_packed(text, cu_text, S_T, max_T, wx, bx, pooled, tmod, B, dt, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_time_table(const float* emb, const float* w0, const float* b0, const float* w2, const float* b2, const float* wt,
+                     const float* bt, float* ttab, int steps, int td, int d, ditto_stream_t stream) {
+    if (!emb || !w0 || !b0 || !w2 || !b2 || !wt || !bt || !ttab) return fail(DITTO_ERR_ARG, "null pointer to ditto_time_table");
+    if (steps <= 0 || td <= 0 || d <= 0) return fail(DITTO_ERR_SHAPE, "ditto_time_table: steps, td and d must be positive");
+    if (td > 4096) return fail(DITTO_ERR_SHAPE, "ditto_time_table: td must be <= 4096 (three td-vectors are staged in the LDS)");
+    HIP_TRY(launch_time_table(emb, w0, b0, w2, b2, wt, bt, ttab, steps, td, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_packed_row_map(const int32_t* cu, int B, int S, int max_len, int32_t* utt, int32_t* pos, ditto_stream_t stream) {
+    if (!cu || !utt || !pos) return fail(DITTO_ERR_ARG, "null pointer to ditto_packed_row_map");
+    if (B <= 0 || S <= 0 || max_len <= 0) return fail(DITTO_ERR_SHAPE, "ditto_packed_row_map: B, S and max_len must be positive");
+    HIP_TRY(launch_packed_row_map(cu, B, S, max_len, utt, pos, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
 int ditto_gemm_bf16(const void* A, int lda, const void* W, const float* bias, const float* residual, void* out,
                     int ldo, int M, int N, int K, int epilogue, ditto_stream_t stream) {
     if (!A || !W || !out) return fail(DITTO_ERR_ARG, "null pointer to ditto_gemm_bf16");

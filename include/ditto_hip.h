@@ -1057,6 +1057,50 @@ int ditto_attention_causal_bf16(const void* q, int ldq, const void* k, int ldk, 
 int ditto_layernorm_dual(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_bf16, int M,
                          int d, ditto_stream_t stream);
 
+/* ---- the forward row kernels on their own (unit tests: tests/test_gpu_rowwise.py) ----------------------------------
+ * Each entry is one launch of csrc/rowwise.hip with every pointer of the launch visible; nothing is allocated and no
+ * model handle is involved.  Every entry checks its arguments first: DITTO_ERR_ARG for a missing or misaligned pointer
+ * (fp32 rows move as 16-byte pieces, bf16 rows as 8-byte pieces), DITTO_ERR_SHAPE for a size the kernel cannot serve.
+ *
+ * ditto_adaln_rows: the GlobalAdaLN entry of the forward (src/components/DiT.py:23,34-39) over x fp32 [B * N, d]:
+ *   h = LayerNorm(x) (no affine, eps 1e-5) * (1 + ttab[ts, :d] + tmod[b, :d]) + ttab[ts, d:] + tmod[b, d:],  b = row / N,
+ *   ts = t[b] (device int64 [B], clamped into [0, steps)) or, t NULL, b itself (ttab then holds one row per utterance).
+ *   ttab fp32 [steps, 2d], tmod fp32 [B, 2d].  h_out: fp32 [B * N, d], or bf16 when h_is_bf16.  raw_bf16 (optional): bf16(x)
+ *   at row stride ldraw >= d, ldraw % 4 == 0.  u1_bf16 (optional, needs g1 and be1 fp32 [d]): LayerNorm(h) * g1 + be1 as bf16
+ *   [B * N, d], from the fp32 h in registers (block 0's norm1, src/components/DiT.py:105).  d % 4 == 0, d <= 2048.
+ * ditto_adaln_rows_packed: the same over S packed rows with b = utt[row] (device int32 [S], ditto_packed_row_map). */
+int ditto_adaln_rows(const float* x, const float* ttab, const float* tmod, const int64_t* t, int steps, void* h_out,
+                     int h_is_bf16, void* raw_bf16, int ldraw, const float* g1, const float* be1, void* u1_bf16, int B, int N,
+                     int d, ditto_stream_t stream);
+int ditto_adaln_rows_packed(const float* x, const float* ttab, const float* tmod, const int64_t* t, int steps,
+                            const int32_t* utt, void* h_out, int h_is_bf16, void* raw_bf16, int ldraw, const float* g1,
+                            const float* be1, void* u1_bf16, int S, int d, ditto_stream_t stream);
+/* ditto_splitk_finish: out fp32 [M, N] = ((partial[0] + partial[1] + ... in index order) + bias[col]) + residual, each step one
+ *   fp32 addition; partial fp32, split s at element offset s * stride (stride >= M * N, stride % 4 == 0); bias, residual optional;
+ *   residual may alias out.  out2_bf16 (optional): bf16(out) at row stride ldo2 >= N, ldo2 % 4 == 0.  u_bf16 (optional, needs gamma
+ *   and beta fp32 [N], N <= 2048): LayerNorm(out) * gamma + beta as bf16 at row stride ldu >= N, ldu % 4 == 0 — the finish and the
+ *   LayerNorm that follows it as one launch, the same bits as ditto_splitk_finish without u followed by ditto_layernorm_bf16. */
+int ditto_splitk_finish(const float* partial, int nsplit, size_t stride, const float* bias, const float* residual, float* out,
+                        void* out2_bf16, int ldo2, const float* gamma, const float* beta, void* u_bf16, int ldu, int M, int N,
+                        ditto_stream_t stream);
+/* ditto_text_mod: the text half of GlobalAdaLN (src/components/DiT.py:19-22,27,31): pooled fp32 [B, dt] = the mean over the first
+ *   T_b rows of text fp32 [B, T, dt] (T_b = text_len[b], device int32 [B] clamped into [1, T]; text_len NULL: T), then
+ *   tmod fp32 [B, 2d] = wx [2d, dt] silu(pooled) + bx [2d].  Rows at or past T_b are not read.
+ * ditto_text_mod_packed: the same with utterance b's rows at [cu_text[b], cu_text[b + 1]) of text fp32 [S_T, dt]
+ *   (device int32 [B + 1]; lengths clamped into [1, max_T]). */
+int ditto_text_mod(const float* text, const int32_t* text_len, const float* wx, const float* bx, float* pooled, float* tmod,
+                   int B, int T, int dt, int d, ditto_stream_t stream);
+int ditto_text_mod_packed(const float* text, const int32_t* cu_text, int S_T, int max_T, const float* wx, const float* bx,
+                          float* pooled, float* tmod, int B, int dt, int d, ditto_stream_t stream);
+/* ditto_time_table: the table ditto_model_create builds, ttab fp32 [steps, 2d] = wt silu(w2 silu(w0 emb[s] + b0) + b2) + bt
+ *   (src/model/DiTTO.py:75-76, src/components/DiT.py:14-17,30); emb fp32 [steps, td], w0 / w2 fp32 [td, td], wt fp32 [2d, td].
+ *   td <= 4096 (three vectors of td floats are staged in the LDS). */
+int ditto_time_table(const float* emb, const float* w0, const float* b0, const float* w2, const float* b2, const float* wt,
+                     const float* bt, float* ttab, int steps, int td, int d, ditto_stream_t stream);
+/* ditto_packed_row_map: utt[r] = the last utterance b with cu[b] <= r (clamped into [0, B)), pos[r] = r - cu[utt[r]] clamped
+ *   into [0, max_len); cu device int32 [B + 1], utt / pos device int32 [S]. */
+int ditto_packed_row_map(const int32_t* cu, int B, int S, int max_len, int32_t* utt, int32_t* pos, ditto_stream_t stream);
+
 /* ---- profiling aid (bench.py): per-kernel-class HIP-event timing -------------------------
  * When enabled on a handle, ditto_forward brackets every launch with hipEvents on `stream`
  * (eager only; do not enable while capturing a graph).  ditto_profile_read synchronises the

@@ -83,6 +83,13 @@ def test_null_arguments_are_refused_not_crashed():
         hip.check(lib.ditto_gemm_bf16(None, 0, None, None, None, None, 0, 1, 1, 1, 0, None))
     assert lib.ditto_gemm_epilogue_bf16(None, 0, None, None) == hip.ERR_ARG
     assert lib.ditto_gemm_epilogue_fp8(None, None, 0, None, None) == hip.ERR_ARG
+    assert lib.ditto_adaln_rows(None, None, None, None, 1, None, 0, None, 0, None, None, None, 1, 1, 64, None) == hip.ERR_ARG
+    assert lib.ditto_adaln_rows_packed(None, None, None, None, 1, None, None, 0, None, 0, None, None, None, 1, 64, None) == hip.ERR_ARG
+    assert lib.ditto_splitk_finish(None, 1, 64, None, None, None, None, 0, None, None, None, 0, 1, 64, None) == hip.ERR_ARG
+    assert lib.ditto_text_mod(None, None, None, None, None, None, 1, 1, 64, 64, None) == hip.ERR_ARG
+    assert lib.ditto_text_mod_packed(None, None, 1, 1, None, None, None, None, 1, 64, 64, None) == hip.ERR_ARG
+    assert lib.ditto_time_table(None, None, None, None, None, None, None, None, 1, 64, 64, None) == hip.ERR_ARG
+    assert lib.ditto_packed_row_map(None, 1, 1, 1, None, None, None) == hip.ERR_ARG
 
 
 def test_config_rejects_what_the_reference_cannot_run():
