@@ -2098,6 +2098,98 @@ int ditto_guided_step_packed_multistep_window_opts(ditto_model_t m, float* x2, c
                                  suffix_len);
 }
 
+// ---- guidance reuse (guided_reuse.hip): every argument is checked here, before any launch ----
+static int check_reuse(const char* who, const float* delta, const float* w, const int32_t* cu, int B, int S, int max_N, int mode,
+                       int mirror) {
+    if (!delta) return fail(DITTO_ERR_ARG, "%s: null delta (fp32 [S, d])", who);
+    if (!cu) return fail(DITTO_ERR_ARG, "%s: null cu", who);
+    if (!w) return fail(DITTO_ERR_ARG, "%s: guidance reuse needs w (fp32 [B])", who);
+    if (mode != 1 && mode != 2) return fail(DITTO_ERR_ARG, "%s: mode must be 1 (STORE) or 2 (LOAD), not %d", who, mode);
+    if (mode == 1 && mirror) return fail(DITTO_ERR_ARG, "%s: mirror belongs to LOAD (STORE writes both halves anyway)", who);
+    return check_packed(who, B, S, max_N, S, max_N);
+}
+
+int ditto_guided_update_packed_reuse(float* x2, const float* eps, float* delta, const float* noise, const int64_t* seeds, uint32_t step,
+                                     const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                     const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int mode,
+                                     int mirror, ditto_stream_t stream) {
+    const char* who = "ditto_guided_update_packed_reuse";
+    if (int rc = check_guided_update(who, x2, eps, noise, seeds, w, a, ce, cz, B, max_N, d, 1)) return rc;
+    if (int rc = check_reuse(who, delta, w, cu, B, S, max_N, mode, mirror)) return rc;
+    HIP_TRY(launch_guided_update_reuse(x2, eps, delta, noise, seeds, step, w, a, ce, cz, cu, prompt_len, suffix_len, B, S, max_N, d, mode,
+                                       mirror, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_multistep_update_packed_reuse(float* x2, const float* eps, float* q, float* delta, const ditto_multistep_coef* step,
+                                        const float* w, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
+                                        int S, int max_N, int d, int mode, int mirror, ditto_stream_t stream) {
+    const char* who = "ditto_multistep_update_packed_reuse";
+    if (!step) return fail(DITTO_ERR_ARG, "%s: null step (host ditto_multistep_coef)", who);
+    if (int rc = check_multistep(who, x2, eps, q, step, nullptr, w, cu, B, max_N, d, 1)) return rc;
+    if (int rc = check_reuse(who, delta, w, cu, B, S, max_N, mode, mirror)) return rc;
+    HIP_TRY(launch_multistep_update_reuse(x2, eps, q, delta, step, w, cu, prompt_len, suffix_len, B, S, max_N, d, mode, mirror,
+                                          (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+// the forward of a refresh (STORE: guided_step_packed's, the 2B utterances of [x; x] x [text; null]) or of a reuse step (LOAD: the B
+// conditional utterances over S rows with the text-only conditioning), then `update` on its eps
+extern "C++" template <class F> static int reuse_step(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                         const int32_t* cu_speech, const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T,
+                                         int mode, const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                         ditto_stream_t stream, const ditto_call_opts* opts, F&& update) {
+    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
+    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
+    return with_opts(opts, [&]() -> int {
+        const int nb = mode == 1 ? 2 * B : B, rows = mode == 1 ? 2 * S : S;
+        float* eps;
+        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
+                                  BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
+            return rc;
+        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
+        HIP_TRY(update(eps));
+        return DITTO_OK;
+    });
+}
+
+int ditto_guided_step_packed_reuse_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                        const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len, float* delta,
+                                        const float* noise, const int64_t* seeds, uint32_t step, const float* w, const float* a,
+                                        const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int mode,
+                                        int mirror, const float* rope_cos, const float* rope_sin, void* workspace,
+                                        size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    const char* who = "ditto_guided_step_packed_reuse_opts";
+    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    const int d = m->cfg.hidden_dim;
+    if (int rc = check_guided_update(who, x2, x2, noise, seeds, w, a, ce, cz, B, max_N, d, 1)) return rc;
+    if (int rc = check_reuse(who, delta, w, cu_speech, B, S, max_N, mode, mirror)) return rc;
+    return reuse_step(who, m, x2, cond, t, cu_speech, cu_text, B, S, max_N, S_T, max_T, mode, rope_cos, rope_sin, workspace,
+                      workspace_bytes, stream, opts, [&](const float* eps) {
+                          return launch_guided_update_reuse(x2, eps, delta, noise, seeds, step, w, a, ce, cz, cu_speech, prompt_len,
+                                                            suffix_len, B, S, max_N, d, mode, mirror, (hipStream_t)stream);
+                      });
+}
+
+int ditto_guided_step_packed_multistep_reuse_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                                  const int32_t* cu_speech, const int32_t* cu_text, const int32_t* prompt_len,
+                                                  const int32_t* suffix_len, float* q, float* delta, const ditto_multistep_coef* step,
+                                                  const float* w, int B, int S, int max_N, int S_T, int max_T, int mode, int mirror,
+                                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                                  ditto_stream_t stream, const ditto_call_opts* opts) {
+    const char* who = "ditto_guided_step_packed_multistep_reuse_opts";
+    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
+    const int d = m->cfg.hidden_dim;
+    if (!step) return fail(DITTO_ERR_ARG, "%s: null step (host ditto_multistep_coef)", who);
+    if (int rc = check_multistep(who, x2, x2, q, step, nullptr, w, cu_speech, B, max_N, d, 1)) return rc;
+    if (int rc = check_reuse(who, delta, w, cu_speech, B, S, max_N, mode, mirror)) return rc;
+    return reuse_step(who, m, x2, cond, t, cu_speech, cu_text, B, S, max_N, S_T, max_T, mode, rope_cos, rope_sin, workspace,
+                      workspace_bytes, stream, opts, [&](const float* eps) {
+                          return launch_multistep_update_reuse(x2, eps, q, delta, step, w, cu_speech, prompt_len, suffix_len, B, S, max_N,
+                                                               d, mode, mirror, (hipStream_t)stream);
+                      });
+}
+
 int ditto_regroup_packed(const ditto_regroup_seg* table, int n_seg, const void* const* src, const size_t* src_bytes, void* const* dst,
                          const size_t* dst_bytes, int n_bufs, const int64_t* seeds, int n_seeds, size_t max_bytes,
                          ditto_stream_t stream) {

@@ -281,6 +281,18 @@ hipError_t launch_multistep_update_packed(float* x2, const float* eps2, float* q
                                           const ::ditto_multistep_coef* coefs, const float* w, const int32_t* cu,
                                           const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, bool cfg,
                                           hipStream_t s);
+// ---------------- guided_reuse.hip ----------------
+// the two updates above with the guidance direction kept between refresh steps: delta fp32 [S, d], row-aligned with the conditional
+// half.  mode 1 (STORE): eps [2S, d], the CFG update's bits on x2 (both halves) and q, delta = c - u on the window rows.  mode 2
+// (LOAD): eps [S, d], e = fmaf(w[b] - 1, delta, c); x' to the conditional half and, with mirror != 0, to the same rows + S; delta is
+// only read.  The scalar-tag form: `step` is the Philox tag / the host ditto_multistep_coef, w device fp32 [B]
+hipError_t launch_guided_update_reuse(float* x2, const float* eps, float* delta, const float* noise, const int64_t* seeds, unsigned step,
+                                      const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                      const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int mode,
+                                      int mirror, hipStream_t s);
+hipError_t launch_multistep_update_reuse(float* x2, const float* eps, float* q, float* delta, const ::ditto_multistep_coef* step,
+                                         const float* w, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
+                                         int S, int max_N, int d, int mode, int mirror, hipStream_t s);
 // ---------------- guided_mixed.hip ----------------
 // the per-utterance-tag update of a batch in which G of the B utterances are guided at this step: x2, eps2 [S + S_G, d], the guided
 // ones' unconditional copies compacted in rows [S, S + S_G); cu device int32 [B + G + 1] = [cu; S + cu_G[1:]]; partner device int32

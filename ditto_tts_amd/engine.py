@@ -402,6 +402,88 @@ class DenoiseEngine:
             ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
         return x2
 
+    # ------------------------------------------------------------------ guidance reuse (csrc/guided_reuse.hip)
+    def _reuse_args(self, who, x2, cond, t, B, delta, w, mode, mirror, offsets, cu_seqlens, max_seqlen, prompt_len, suffix_len):
+        """The checks both reuse steps share.  STORE (a refresh): x2 [2S, d] = [x; x], cond over [text; null], t [2B], offsets [2B + 1].
+        LOAD (a reuse step): x2 [S, d] — the conditional half, a view of the first S rows of the [2S, d] state when `mirror` —, cond
+        over the text alone, t [B], offsets [B + 1].  Returns (S, nb, device offsets, max_N, t as int64)."""
+        if mode not in (hip.REUSE_STORE, hip.REUSE_LOAD):
+            raise ValueError(f"{who}: mode must be hip.REUSE_STORE or hip.REUSE_LOAD, got {mode!r}")
+        store = mode == hip.REUSE_STORE
+        if store and mirror:
+            raise ValueError(f"{who}: mirror belongs to a reuse step (a refresh writes both halves anyway)")
+        if w is None:
+            raise ValueError(f"{who}: guidance reuse needs the guidance scales w")
+        rows, d = int(x2.shape[0]), int(x2.shape[1])
+        if store and rows % 2:
+            raise ValueError("x2 must hold [x; x] at a refresh step")
+        S = rows // 2 if store else rows
+        if mirror and (x2.storage_offset() + 2 * S * d) * 4 > x2.untyped_storage().nbytes():
+            raise ValueError(f"{who}: mirror writes rows [S, 2S): x2 must be the first {S} rows of a [{2 * S}, {d}] buffer")
+        if not (delta.is_cuda and delta.dtype == torch.float32 and delta.is_contiguous() and delta.shape == (S, d)):
+            raise ValueError(f"delta must be a contiguous fp32 CUDA tensor of shape [{S}, {d}]")
+        nb = 2 * B if store else B
+        self._packed_cond(cond, nb)
+        if offsets is None:
+            offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, store)
+        cud, max_N = offsets
+        if cud.shape != (nb + 1,):
+            raise ValueError(f"offsets: [{nb + 1}] expected")
+        for name, v in (("prompt_len", prompt_len), ("suffix_len", suffix_len)):
+            if v is not None and not (v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.shape == (B,)):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of shape [{B}]")
+        return S, nb, cud, max_N, self._t64(t, nb)
+
+    def guided_step_packed_reuse_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, delta: torch.Tensor,
+                                  a: torch.Tensor, ce: torch.Tensor, cz: torch.Tensor, w: torch.Tensor, mode: int, mirror: bool = False,
+                                  noise: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None, step: int = 0,
+                                  cu_seqlens=None, max_seqlen: Optional[int] = None, offsets=None,
+                                  opts: Optional[hip.CallOpts] = None, prompt_len: Optional[torch.Tensor] = None,
+                                  suffix_len: Optional[torch.Tensor] = None):
+        """One strided (DDIM) step of a loop that reuses the guidance direction (ditto_guided_step_packed_reuse_opts), IN PLACE on
+        x2 and `delta` fp32 [S, d].  mode hip.REUSE_STORE — a refresh: guided_step_packed_'s guided step on x2 [2S, d] (the same
+        forward, the same bits on x2) that also keeps delta = c - u.  mode hip.REUSE_LOAD — a reuse step: the forward over the B
+        conditional utterances of x2 [S, d] alone, with `cond` over the text only, and the update with e = c + (w - 1) delta; with
+        `mirror`, x' is written to rows [S, 2S) of the buffer x2 is the first half of as well (what the next refresh reads).
+        Everything else as guided_step_packed_."""
+        who = "guided_step_packed_reuse_"
+        store = mode == hip.REUSE_STORE
+        sd, noise = self._guided_args(who, x2, 2, B, a, ce, cz, w if store else None, noise, seeds)
+        self._guided_args(who, x2, 2, B, None, None, None, w, None, None)
+        S, nb, cud, max_N, tt = self._reuse_args(who, x2, cond, t, B, delta, w, mode, mirror, offsets, cu_seqlens, max_seqlen,
+                                                 prompt_len, suffix_len)
+        ws = self.workspace_packed(nb, nb // B * S, cond.T)
+        c, s = self.rope_tables(max_N)
+        hip.check(self.lib.ditto_guided_step_packed_reuse_opts(
+            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
+            _ptr(suffix_len), delta.data_ptr(), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, w.data_ptr(), a.data_ptr(), ce.data_ptr(),
+            cz.data_ptr(), B, S, max_N, cond.T, cond.max_len, int(mode), int(bool(mirror)), c.data_ptr(), s.data_ptr(), ws.data_ptr(),
+            ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+        return x2
+
+    def guided_step_packed_multistep_reuse_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
+                                            delta: torch.Tensor, coef: hip.MultistepCoef, w: torch.Tensor, mode: int,
+                                            mirror: bool = False, cu_seqlens=None, max_seqlen: Optional[int] = None, offsets=None,
+                                            opts: Optional[hip.CallOpts] = None, prompt_len: Optional[torch.Tensor] = None,
+                                            suffix_len: Optional[torch.Tensor] = None):
+        """guided_step_packed_reuse_ with the update of the second-order multistep solver
+        (ditto_guided_step_packed_multistep_reuse_opts), IN PLACE on x2, the history `q` fp32 [S, d] and `delta`.  `coef`: the step
+        every utterance stands at, as in guided_step_packed_multistep_ (no per-utterance `coefs` form)."""
+        who = "guided_step_packed_multistep_reuse_"
+        self._guided_args(who, x2, 2, B, None, None, None, w, None, None)
+        S, nb, cud, max_N, tt = self._reuse_args(who, x2, cond, t, B, delta, w, mode, mirror, offsets, cu_seqlens, max_seqlen,
+                                                 prompt_len, suffix_len)
+        if not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.shape == (S, x2.shape[1])):
+            raise ValueError(f"q must be a contiguous fp32 CUDA tensor of shape [{S}, {x2.shape[1]}]")
+        ws = self.workspace_packed(nb, nb // B * S, cond.T)
+        c, s = self.rope_tables(max_N)
+        hip.check(self.lib.ditto_guided_step_packed_multistep_reuse_opts(
+            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
+            _ptr(suffix_len), q.data_ptr(), delta.data_ptr(), C.byref(coef), w.data_ptr(), B, S, max_N, cond.T, cond.max_len, int(mode),
+            int(bool(mirror)), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
+            None if opts is None else C.byref(opts)))
+        return x2
+
     # ------------------------------------------------------------------ guidance rescale (csrc/guided_rescale.hip)
     def rescale_scratch(self, B: int, max_N: int) -> torch.Tensor:
         """the scratch of a guidance rescale over B utterances of at most max_N rows (ditto_guidance_rescale_bytes): uint8, zeroed"""

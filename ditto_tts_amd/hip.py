@@ -121,6 +121,9 @@ class GemmEpilogueArgs(C.Structure):
                 ("M", C.c_int), ("N", C.c_int), ("K", C.c_int)]
 
 
+REUSE_STORE, REUSE_LOAD = 1, 2   # the `mode` of the ditto_*_reuse entries: a refresh step keeps delta = c - u, a reuse step reads it
+
+
 class MultistepCoef(C.Structure):
     """ditto_multistep_coef: one utterance's step of the second-order multistep solver (sampler.multistep_schedule), 32 bytes."""
     _fields_ = [("a", C.c_float), ("kx", C.c_float), ("ke", C.c_float), ("b", C.c_float), ("g", C.c_float), ("w", C.c_float),
@@ -255,6 +258,13 @@ SYMBOLS = {
     "ditto_span_mse_window": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     # the v objective's span loss: x0, (ca, cs) and per-utterance weights beside ditto_span_mse_window's arguments
     "ditto_span_vloss_window": (_i, [_vp] * 4 + [C.c_uint32] + [_vp] * 6 + [_sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    # guidance reuse: delta fp32 [S, d] beside the state, mode 1 = STORE (refresh) / 2 = LOAD (reuse), mirror (LOAD only)
+    "ditto_guided_update_packed_reuse": (_i, [_vp] * 5 + [C.c_uint32] + [_vp] * 7 + [_i] * 6 + [_vp]),
+    "ditto_multistep_update_packed_reuse": (_i, [_vp] * 4 + [C.POINTER(MultistepCoef)] + [_vp] * 4 + [_i] * 6 + [_vp]),
+    "ditto_guided_step_packed_reuse_opts": (_i, [_vp] * 11 + [C.c_uint32] + [_vp] * 4 + [_i] * 7
+                                            + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
+    "ditto_guided_step_packed_multistep_reuse_opts": (_i, [_vp] * 10 + [C.POINTER(MultistepCoef), _vp] + [_i] * 7
+                                                      + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
     "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),
     "ditto_regroup_cond_layout": (_i, [C.POINTER(Config), _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),

@@ -162,6 +162,38 @@ def guided_steps(schedule, interval):
     return [interval[0] <= row[0] <= interval[1] for row in schedule]
 
 
+def validate_guidance_refresh(guidance_refresh):
+    """`guidance_refresh` — None, or an int k >= 1: the unconditional forward runs at every k-th guided step — as None or an int."""
+    if guidance_refresh is None:
+        return None
+    if isinstance(guidance_refresh, bool) or not isinstance(guidance_refresh, int) or guidance_refresh < 1:
+        raise ValueError(f"guidance_refresh: None or an int >= 1 is needed, got {guidance_refresh!r}")
+    return guidance_refresh
+
+
+def refresh_plan(guided, k: int):
+    """The schedule of a loop that reuses the guidance direction between refresh steps (the "CFG cache" of FasterCache, Lv et al.
+    2024, without its frequency reweighting): `guided` is guided_steps' list, k >= 1 the refresh period.  Returns (kinds, mirror),
+    one entry per step.  A counter j runs over the guided steps and is reset to 0 by every unguided one: a guided step is "refresh"
+    (the forward over [x; x] x [text; null]; it keeps delta = c - u) where j % k == 0 and "reuse" (the conditional forward alone,
+    e = c + (w - 1) delta) otherwise; an unguided step is "plain".  So the first guided step of the call is a refresh, and so is the
+    first one behind any unguided run: a direction is never carried across steps that did not use it.  mirror[i]: step i is a reuse
+    step and step i + 1 a refresh — its update writes the unconditional half of the state too, which that refresh reads.
+    Pure host arithmetic."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"refresh_plan: k must be an int >= 1, got {k!r}")
+    kinds, j = [], 0
+    for g in guided:
+        if not g:
+            kinds.append("plain")
+            j = 0
+            continue
+        kinds.append("refresh" if j % k == 0 else "reuse")
+        j += 1
+    mirror = [kinds[i] == "reuse" and i + 1 < len(kinds) and kinds[i + 1] == "refresh" for i in range(len(kinds))]
+    return kinds, mirror
+
+
 def guidance_vector(guidance, B: int) -> Optional[torch.Tensor]:
     """`guidance` (None, a number, or a sequence / tensor of B numbers) as a CPU fp32 tensor [B], or None (no guidance)."""
     if guidance is None:
@@ -424,7 +456,7 @@ class SpeechGenerator:
 
     # ---------------------------------------------------------------- guided strided loop over a variable-length batch
     def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval=None,
-                     begin_plain=None, rescale=None, prediction="eps"):
+                     begin_plain=None, rescale=None, prediction="eps", refresh=None, begin_reuse=None):
         """The strided loop of sample_guided and sample_guided_packed.  `begin(eng, cfg, seeds)` is the layout's own prologue: it
         builds the conditioning and the state x2 (rows [x_T; room for the unconditional half] under guidance, else x_T) and returns
         (x2, max length, step) with `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)` the layout's library call bound to
@@ -436,7 +468,12 @@ class SpeechGenerator:
         the one without guidance.
         `rescale` (rescale_vector's phi [B], packed batches): every guided step computes each utterance's guidance-rescale factor
         from its eps and updates with ce s32 (the step's phi= argument); unguided steps rescale nothing.
-        `prediction` "v" (packed batches): the rows of strided_schedule_v — (a_v, cv) travel where (a, ce) do, to the same launches."""
+        `prediction` "v" (packed batches): the rows of strided_schedule_v — (a_v, cv) travel where (a, ce) do, to the same launches.
+        `refresh` (an int k >= 2, packed batches; None: the loop as it was): refresh_plan's schedule over the guided steps.
+        `begin_reuse(eng, x2, step, delta)` returns (refresh step, reuse step, plain step): the layout's STORE call on x2 with the
+        guided conditioning, its LOAD call on the conditional half with begin_plain's text-only conditioning, and begin_plain's
+        step itself.  delta [rows, d] is allocated once here.  A reuse step leaves the unconditional half behind unless it
+        mirrors, so the copy runs before a refresh whose preceding step did not mirror."""
         if seeds is not None and noises is not None:
             raise ValueError("seeds= excludes noises=")
         gv = guidance_vector(guidance, B)
@@ -452,7 +489,12 @@ class SpeechGenerator:
                 raise ValueError(f"seeds must have shape [{B}]")
         x2, N, step = begin(eng, cfg, seeds)
         rows = x2.shape[0] // 2 if cfg else x2.shape[0]
-        plain = begin_plain(eng, x2) if cfg and not all(guided) else None
+        kinds = mirror = reuse = None
+        if refresh is not None and cfg:
+            kinds, mirror = refresh_plan(guided, refresh)
+            step, reuse, plain = begin_reuse(eng, x2, step, torch.empty_like(x2[:rows]))
+        else:
+            plain = begin_plain(eng, x2) if cfg and not all(guided) else None
         stale = cfg                                          # the unconditional half is behind the conditional one
         # every step's coefficients in one upload: coef[i] = (a, ce, sigma) x B
         coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
@@ -482,6 +524,11 @@ class SpeechGenerator:
                       opts=plain_opts)
                 stale = True
                 continue
+            if kinds is not None and kinds[i] == "reuse":    # the conditional forward alone, e = c + (w - 1) delta
+                reuse(t=t_tensor[:B], a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val,
+                      opts=plain_opts, mirror=mirror[i])
+                stale = not mirror[i]
+                continue
             if stale:                                        # [x; x], once; then every guided update writes both halves itself
                 x2[rows:].copy_(x2[:rows])
                 stale = False
@@ -489,14 +536,15 @@ class SpeechGenerator:
         return x2[:rows].clone() if cfg else x2
 
     def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval=None, begin_plain=None,
-                        rescale=None, prediction="eps"):
+                        rescale=None, prediction="eps", refresh=None, begin_reuse=None):
         """_guided_loop for solver="dpmpp2m": the same prologue (`begin`, whose step is engine.guided_step_packed_multistep_ bound to
         x2, its conditioning and offsets), then one library call per step of multistep_schedule over x2 and the history q — one
         buffer [S, d] per call, written by step 0 before any step reads it.  Each step's coefficients travel as a host struct.
         `rescale` (rescale_vector's phi [B]): the guided steps read their coefficients from DEVICE memory instead — one
         ditto_multistep_coef per utterance and step, uploaded once, the guidance scale inside — so that the rescale can patch each
         utterance's ke before the per-utterance update runs.
-        `prediction` "v": the rows of multistep_schedule_v, (kx, ke) = (alpha, -sigma), to the same launches."""
+        `prediction` "v": the rows of multistep_schedule_v, (kx, ke) = (alpha, -sigma), to the same launches.
+        `refresh`, `begin_reuse`: as in _guided_loop; the history q is the x0 of whichever step wrote it, reuse steps included."""
         from .hip import CallOpts, MultistepCoef
         gv = guidance_vector(guidance, B)
         if gv is not None and null_text_emb is None:
@@ -511,7 +559,12 @@ class SpeechGenerator:
                 raise ValueError(f"seeds must have shape [{B}]")
         x2, N, step = begin(eng, cfg, seeds)
         rows = x2.shape[0] // 2 if cfg else x2.shape[0]
-        plain = begin_plain(eng, x2) if cfg and not all(guided) else None
+        kinds = mirror = reuse = None
+        if refresh is not None and cfg:
+            kinds, mirror = refresh_plan(guided, refresh)
+            step, reuse, plain = begin_reuse(eng, x2, step, torch.empty_like(x2[:rows]))
+        else:
+            plain = begin_plain(eng, x2) if cfg and not all(guided) else None
         stale = cfg
         q = torch.empty_like(x2[:rows])
         w = gv.to(eng.device) if cfg else None
@@ -532,6 +585,10 @@ class SpeechGenerator:
             if cfg and not guided[i]:  # the history q is the x0 of whichever step wrote it, conditional or guided: no special case
                 plain(t=t_tensor[:B], q=q, coef=coef, w=None, opts=plain_opts)
                 stale = True
+                continue
+            if kinds is not None and kinds[i] == "reuse":
+                reuse(t=t_tensor[:B], q=q, coef=coef, w=w, opts=plain_opts, mirror=mirror[i])
+                stale = not mirror[i]
                 continue
             if stale:
                 x2[rows:].copy_(x2[:rows])
@@ -600,7 +657,7 @@ class SpeechGenerator:
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
                              batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None, guidance_rescale=None,
-                             suffix_lengths=None, prediction="eps"):
+                             suffix_lengths=None, prediction="eps", guidance_refresh=None):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -648,6 +705,17 @@ class SpeechGenerator:
         of strided_schedule_v / multistep_schedule_v.  Every other argument works as above; `guidance_rescale` matches the standard
         deviations of the network's outputs as they are (v).  The model must have been trained on v (DiTTO.span_loss_packed(
         prediction="v")) and on this object's alphas_cumprod table; nothing here has been run with a trained model.
+        `guidance_refresh` (None, or an int k >= 1): REUSE OF THE GUIDANCE DIRECTION — the unconditional forward runs at every k-th
+        guided step only (the "CFG cache" of FasterCache, Lv et al. 2024, without its frequency reweighting).  refresh_plan gives
+        the schedule: a refresh step is the guided step above, through ditto_guided_step_packed_reuse_opts (2M:
+        ..._multistep_reuse_opts) in its STORE mode, which also keeps delta = c - u in one more buffer [S, d]; a reuse step runs the
+        forward over the B conditional utterances alone — the forward of a step outside a `guidance_interval` — and updates with
+        e = c + (w - 1) delta (LOAD mode); the first guided step of the call, and the first one behind unguided steps, is a refresh.
+        By row counts the forward work of a fully guided loop falls to (k + 1) / (2 k).  It needs `guidance` and `null_text_emb`;
+        None and 1 are the call as it was (the same entries, the same bits); with `guidance_rescale` it raises NotImplementedError
+        (the statistics need u at every step: a follow-up).  Works with both solvers, prompts, suffixes, an interval,
+        prediction="v", seeds / noises, cond_by_audio and batch_class.  This is an approximation of the guided trajectory, not
+        another route to the same bits: what it costs in speech quality has not been measured with a trained model.
         Returns fp32 [S, d]."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
@@ -659,6 +727,14 @@ class SpeechGenerator:
             raise ValueError("guidance_rescale needs guidance= and null_text_emb=")
         if guidance_rescale is not None and suffix_lengths is not None:
             raise NotImplementedError("guidance_rescale= with suffix_lengths=: the rescale statistics have no windowed form")
+        refresh = validate_guidance_refresh(guidance_refresh)
+        if refresh is not None and (guidance is None or null_text_emb is None):
+            raise ValueError("guidance_refresh needs guidance= and null_text_emb=")
+        if refresh is not None and guidance_rescale is not None:
+            raise NotImplementedError("guidance_refresh= with guidance_rescale=: the rescale statistics need the unconditional "
+                                      "prediction at every step; a rescale that reuses the kept direction is a follow-up")
+        if refresh == 1:
+            refresh = None                                       # every guided step refreshes: the loop as it was
         rescale = rescale_vector(guidance_rescale, len(cu_seqlens) - 1)
         multistep = solver == "dpmpp2m"
         if multistep and (eta != 0 or noises is not None):
@@ -689,6 +765,15 @@ class SpeechGenerator:
             ct = validate_cu_seqlens(text_cu_seqlens, B, int(text.shape[0]), int(text.shape[0]), "text_cu_seqlens")
             return functools.partial(entry_of(eng), x2[:S], eng.prepare_text_packed(text, ct), B=B,
                                      offsets=eng.guided_offsets_packed(cu, S, N, False), **context_kw(eng))
+
+        def begin_reuse(eng, x2, step, delta):
+            """the steps of a loop with guidance_refresh: the STORE entry bound to what `step` (begin's) is bound to, the LOAD
+            entry bound to what begin_plain's step is bound to, and that step itself"""
+            from .hip import REUSE_LOAD, REUSE_STORE
+            entry = eng.guided_step_packed_multistep_reuse_ if multistep else eng.guided_step_packed_reuse_
+            plain = begin_plain(eng, x2)
+            return (functools.partial(entry, *step.args, delta=delta, mode=REUSE_STORE, **step.keywords),
+                    functools.partial(entry, *plain.args, delta=delta, mode=REUSE_LOAD, **plain.keywords), plain)
 
         def begin(eng, cfg, seeds):
             entry = entry_of(eng)
@@ -735,9 +820,9 @@ class SpeechGenerator:
 
         if multistep:
             return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval, begin_plain, rescale,
-                                        prediction)
+                                        prediction, refresh, begin_reuse)
         return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval, begin_plain,
-                                 rescale, prediction)
+                                 rescale, prediction, refresh, begin_reuse)
 
     def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim", infill=False,
                       prediction="eps"):

@@ -790,6 +790,50 @@ int ditto_span_vloss_window(const float* pred, const float* x0, const float* noi
                             const float* cs, const float* lw, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len,
                             size_t n_elems, float* grad_pred, float* loss, void* workspace, size_t workspace_bytes, int B, int S,
                             int max_N, int d, ditto_stream_t stream);
+/* ---- Guidance reuse (the "CFG cache" of FasterCache, Lv et al. 2024, without its frequency reweighting): the unconditional forward
+ * runs at every k-th guided step only, and the steps in between reuse the last guidance direction delta = c - u:
+ *     u + w (c - u) = c + (w - 1)(c - u)  ~  c_now + (w - 1) delta_last
+ * so a reuse step costs the unguided step's forward.  The reference has no guided sampler: this is pinned by its own formulas.  What
+ * the approximation does to the speech of a trained model is not measured by anything in this library.
+ * delta: fp32 [S, d], row-aligned with the conditional half, REQUIRED.  mode: 1 = STORE (a refresh step), 2 = LOAD (a reuse step);
+ *   anything else is DITTO_ERR_ARG.  w: device fp32 [B], REQUIRED.  The window [cu[b] + P_b, cu[b+1] - Q_b), its clamps and the
+ *   window-local Philox index are ditto_guided_update_packed_window's, except that prompt_len and suffix_len may each be NULL (0 rows);
+ *   context rows of x2, eps, delta, q and `noise` are neither read nor written.
+ * ditto_guided_update_packed_reuse: the scalar-tag strided (DDIM) update.
+ *   STORE: eps fp32 [2S, d].  dl = c - u, e = fmaf(w[b], dl, u), x' = fmaf(a[b], x, fmaf(ce[b], e, cz[b] z)); x' goes to both halves of
+ *     x2 [2S, d] — the bits of ditto_guided_update_packed_window with cfg = 1 — and delta = dl on the window rows.  mirror must be 0.
+ *   LOAD: eps fp32 [S, d], the conditional prediction alone.  e = fmaf(w[b] - 1.0f, delta, c), the same x' line and the same draw;
+ *     x' goes to rows [0, S) of x2 and, when mirror != 0, to the same rows + S as well (x2 is [2S, d] then, [S, d] otherwise).  delta
+ *     is read and never written.  With w[b] == 1, e == c exactly and x' is the cfg = 0 entry's.
+ * ditto_multistep_update_packed_reuse: the same two modes in front of ditto_multistep_update_window's x0 / x' / q lines, in the host
+ *   `step` form only (REQUIRED; its w is ignored, w[b] is the scale; use_prev as there).  STORE gives that entry's cfg = 1 bits on x2
+ *   and q.
+ * ditto_guided_step_packed_reuse_opts / ditto_guided_step_packed_multistep_reuse_opts: the forward, then that update on its output.
+ *   STORE: ditto_guided_step_packed_opts' cfg = 1 forward — the 2B utterances of [x; x], cu_speech [2B + 1] over 2S rows, cond over
+ *     [text; null], t int64 [2B], workspace ditto_packed_workspace_bytes(cfg, 2B, 2S, S_T).
+ *   LOAD: the forward over the B conditional utterances alone — x2's first S rows, cu_speech [B + 1], cond over the text only (S_T and
+ *     max_T its own), t int64 [B], workspace ditto_packed_workspace_bytes(cfg, B, S, S_T).
+ * Traffic of the update per generated element: STORE 4 B more than the cfg = 1 update; LOAD 16 B (x, c, delta read, x' written: 4 B
+ *   more than the cfg = 0 update) + 4 B with a noise buffer + 4 B with mirror + 8 B multistep history. */
+int ditto_guided_update_packed_reuse(float* x2, const float* eps, float* delta, const float* noise, const int64_t* seeds, uint32_t step,
+                                     const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
+                                     const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int mode,
+                                     int mirror, ditto_stream_t stream);
+int ditto_multistep_update_packed_reuse(float* x2, const float* eps, float* q, float* delta, const ditto_multistep_coef* step,
+                                        const float* w, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
+                                        int S, int max_N, int d, int mode, int mirror, ditto_stream_t stream);
+int ditto_guided_step_packed_reuse_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                        const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len, float* delta,
+                                        const float* noise, const int64_t* seeds, uint32_t step, const float* w, const float* a,
+                                        const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int mode,
+                                        int mirror, const float* rope_cos, const float* rope_sin, void* workspace,
+                                        size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts);
+int ditto_guided_step_packed_multistep_reuse_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                                  const int32_t* cu_speech, const int32_t* cu_text, const int32_t* prompt_len,
+                                                  const int32_t* suffix_len, float* q, float* delta, const ditto_multistep_coef* step,
+                                                  const float* w, int B, int S, int max_N, int S_T, int max_T, int mode, int mirror,
+                                                  const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
+                                                  ditto_stream_t stream, const ditto_call_opts* opts);
 /* ditto_regroup_packed: build the next packed batch from the current one plus the newcomers, in ONE launch driven by a DEVICE table
  *   of n_seg segments.  A segment moves `n` 16-byte units (every row of the state, the K/V cache and tmod is a whole number of them)
  *   to unit dst_off of destination buffer `dest` and, when dup_off != 0, also to dst_off + dup_off (a speech segment under CFG: the
