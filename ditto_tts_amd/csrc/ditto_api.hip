@@ -1609,7 +1609,12 @@ int ditto_guided_update_packed(float* x2, const float* eps2, const float* noise,
 }
 
 // ---- guidance rescale (guided_rescale.hip): the scratch [coef_out | scale | partials], each part 256-byte aligned ----
-struct RescaleReq { const float* phi; void* scratch; size_t scratch_bytes; };
+// a step's rescale request: the coefficients to scale are fp32 [B] (coef_in, with w) or ditto_multistep_coef [B] (coefs, w and ke inside)
+struct RescaleReq {
+    const float* phi; void* scratch; size_t scratch_bytes;
+    const float *w, *coef_in; const ditto_multistep_coef* coefs;
+    const int32_t *prompt_len, *partner; int G, S_G;   // partner, G, S_G: a mixed step's (else NULL, 0, 0)
+};
 static size_t rescale_head_bytes(int B) { return al((size_t)B * sizeof(ditto_multistep_coef)) + al((size_t)B * sizeof(float)); }
 static size_t rescale_bytes(int B, int max_N, int d) {
     return rescale_head_bytes(B) + al((size_t)B * guidance_rescale_chunks(max_N, d) * 4 * sizeof(double));
@@ -1653,41 +1658,81 @@ static RescaleArgs rescale_args(const float* eps2, const float* w, const float* 
     return a;
 }
 
-// the packed guided step with one scalar step tag (per_utt false) or one tag per utterance, over the whole utterance or the window
-// that prompt_len and suffix_len (either may be NULL) leave; an entry that requires one of them refuses its NULL itself
-static int guided_step_packed(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
-                              const int32_t* cu_text, const float* noise, const int64_t* seeds, uint32_t step, const uint32_t* tags,
-                              bool per_utt, const float* w, const float* a, const float* ce_in, const float* cz, int B, int S, int max_N,
-                              int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
-                              size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
-                              const int32_t* prompt_len = nullptr, const int32_t* suffix_len = nullptr,
-                              const RescaleReq* rs = nullptr) {
-    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (rs)   // guidance rescale: the statistics between the forward and the update, the update then reads ce[b] s_b from the scratch
-        if (int rc = check_rescale(who, x2, w, rs->phi, ce_in, nullptr, cu_speech, nullptr, B, 0, S, 0, max_N, m->cfg.hidden_dim,
-                                   rs->scratch, rs->scratch_bytes))
-            return rc;
-    if (int rc = check_guided_update(who, x2, x2, noise, seeds, w, a, ce_in, cz, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
-    if (per_utt && seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
-    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
-    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
-    return with_opts(opts, [&]() -> int {
-        // under guidance the forward runs over the 2B utterances of [x; x] x [text; null]: cu_speech then holds 2B + 1 offsets over 2S rows
-        const int nb = cfg ? 2 * B : B, rows = cfg ? 2 * S : S;
+// ---- one guided step over a packed batch: what the 13 ditto_guided_step_packed*_opts entries share, by name ----
+struct PackedStep {
+    const char* who; ditto_model_t m; float* x2; const void* cond; const int64_t* t;
+    const int32_t *cu_speech, *cu_text;
+    int B, S, max_N, S_T, max_T;     // the update's: B utterances over the S rows of x
+    int nb, rows;                    // the forward's: 2B over 2S, [x; x] x [text; null] (doubled), B + G over S + S_G (mixed), else B over S
+    Rope rope; Buf ws; ditto_stream_t stream; const ditto_call_opts* opts;
+    // set before B and S are checked (a refused call never reads them), hence the arithmetic that cannot overflow
+    void forward_over(bool doubled) { nb = doubled ? (int)(2u * (unsigned)B) : B; rows = doubled ? (int)(2u * (unsigned)S) : S; }
+};
+// the step entries name these parameters alike: `p` filled from them field by field (nb and rows are the family's to set)
+#define PACKED_STEP(p, entry)                                                                                                        \
+    PackedStep p{};                                                                                                                  \
+    p.who = entry; p.m = m; p.x2 = x2; p.cond = cond; p.t = t; p.cu_speech = cu_speech; p.cu_text = cu_text;                         \
+    p.B = B; p.S = S; p.max_N = max_N; p.S_T = S_T; p.max_T = max_T;                                                                 \
+    p.rope.cos = rope_cos; p.rope.sin = rope_sin; p.ws.p = workspace; p.ws.bytes = workspace_bytes; p.stream = stream; p.opts = opts
+
+// the one body: check(d), the family's argument checks, refuses before any launch; then the step kernels' limits and check2(d), what
+// a family has always checked behind them (a refusal keeps its place); then the forward over p.nb utterances in p.rows rows and
+// update(eps, d), the family's launch on the forward's eps
+extern "C++" template <class Check, class Check2, class Update>
+static int packed_step(const PackedStep& p, Check&& check, Check2&& check2, Update&& update) {
+    if (!p.m) return fail(DITTO_ERR_ARG, "bad argument to %s", p.who);
+    const int d = p.m->cfg.hidden_dim;
+    if (int rc = check(d)) return rc;
+    if (p.B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", p.who);
+    if (p.S <= 0 || p.S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", p.who);
+    if (int rc = check2(d)) return rc;
+    return with_opts(p.opts, [&]() -> int {
         float* eps;
-        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
-                                  BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
+        if (int rc = step_forward(p.who, p.m, p.x2, p.cond, p.t, p.rope, p.ws, p.stream,
+                                  BatchLayout::packed(p.nb, p.rows, p.max_N, p.S_T, p.max_T, p.cu_speech, p.cu_text), &eps))
             return rc;
-        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-        const float* ce = ce_in;
-        if (rs) {
-            const RescaleArgs ra = rescale_args(eps, w, rs->phi, ce_in, nullptr, cu_speech, prompt_len, nullptr, B, 0,
-                                                S, 0, m->cfg.hidden_dim, rs->scratch, rs->scratch_bytes);
-            HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
-            ce = ra.coef_out;
-        }
-        HIP_TRY(launch_guided_update_packed(x2, eps, noise, seeds, step, tags, per_utt, w, a, ce, cz, cu_speech, prompt_len, suffix_len, B,
-                                            S, max_N, m->cfg.hidden_dim, cfg != 0, (hipStream_t)stream));
+        ProfScope ps(p.m, (hipStream_t)p.stream, DITTO_KC_UPDATE);
+        return update(eps, d);
+    });
+}
+extern "C++" template <class Check, class Update> static int packed_step(const PackedStep& p, Check&& check, Update&& update) {
+    return packed_step(p, check, [](int) { return DITTO_OK; }, update);
+}
+
+// guidance rescale inside a step: the request against the step's shapes (before any launch), and the stage between the forward and
+// the update — the statistics of this step's eps; returns the scaled coefficients the update reads instead of its own (NULL: failed)
+static int check_step_rescale(const PackedStep& p, const RescaleReq& r, int d) {
+    return check_rescale(p.who, p.x2, r.w, r.phi, r.coef_in, r.coefs, p.cu_speech, r.partner, p.B, r.G, p.S, r.S_G, p.max_N, d, r.scratch,
+                         r.scratch_bytes);
+}
+static const void* step_rescale(const PackedStep& p, const RescaleReq& r, const float* eps, int d) {
+    const RescaleArgs ra = rescale_args(eps, r.w, r.phi, r.coef_in, r.coefs, p.cu_speech, r.prompt_len, r.partner, p.B, r.G, p.S, r.S_G, d,
+                                        r.scratch, r.scratch_bytes);
+    const hipError_t e = launch_guidance_rescale(ra, p.max_N, (hipStream_t)p.stream);
+    if (e != hipSuccess) fail(DITTO_ERR_HIP, "launch_guidance_rescale: %s", hipGetErrorString(e));
+    return e == hipSuccess ? r.scratch : nullptr;   // the scratch opens with coef_out, in either form
+}
+
+// the strided (DDIM) update of a step: one scalar step tag (per_utt false) or one tag per utterance, over the whole utterance or the
+// window that prompt_len and suffix_len (either may be NULL) leave; partner, G, S_G: a mixed step's
+struct StridedUpdate {
+    const float* noise; const int64_t* seeds; uint32_t step; const uint32_t* tags; bool per_utt;
+    const float *w, *a, *ce, *cz; const int32_t *prompt_len, *suffix_len, *partner; int G, S_G, cfg;
+    const RescaleReq* rs;            // guidance rescale: the update then reads ce[b] s_b from the scratch
+};
+static int strided_step(PackedStep& p, const StridedUpdate& u) {
+    p.forward_over(u.cfg != 0);      // cu_speech then holds 2B + 1 offsets over 2S rows
+    return packed_step(p, [&](int d) -> int {
+        if (u.rs)
+            if (int rc = check_step_rescale(p, *u.rs, d)) return rc;
+        if (int rc = check_guided_update(p.who, p.x2, p.x2, u.noise, u.seeds, u.w, u.a, u.ce, u.cz, p.B, p.max_N, d, u.cfg)) return rc;
+        if (u.per_utt && u.seeds && !u.tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", p.who);
+        return DITTO_OK;
+    }, [&](const float* eps, int d) -> int {
+        const float* ce = u.ce;
+        if (u.rs && !(ce = (const float*)step_rescale(p, *u.rs, eps, d))) return DITTO_ERR_HIP;
+        HIP_TRY(launch_guided_update_packed(p.x2, eps, u.noise, u.seeds, u.step, u.tags, u.per_utt, u.w, u.a, ce, u.cz, p.cu_speech,
+                                            u.prompt_len, u.suffix_len, p.B, p.S, p.max_N, d, u.cfg != 0, (hipStream_t)p.stream));
         return DITTO_OK;
     });
 }
@@ -1697,8 +1742,10 @@ int ditto_guided_step_packed_opts(ditto_model_t m, float* x2, const void* cond, 
                                   const float* a, const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int cfg,
                                   const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                                   ditto_stream_t stream, const ditto_call_opts* opts) {
-    return guided_step_packed("ditto_guided_step_packed_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false, w, a,
-                              ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
+    PACKED_STEP(p, "ditto_guided_step_packed_opts");
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.step = step; u.w = w; u.a = a; u.ce = ce; u.cz = cz; u.cfg = cfg;
+    return strided_step(p, u);
 }
 
 // ---- continuous batching: per-utterance step tags and the device regroup (regroup_packed.hip) ----
@@ -1714,8 +1761,10 @@ int ditto_guided_step_packed_tags_opts(ditto_model_t m, float* x2, const void* c
                                        const float* w, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
                                        int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                                        size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
-    return guided_step_packed("ditto_guided_step_packed_tags_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true, w, a,
-                              ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
+    PACKED_STEP(p, "ditto_guided_step_packed_tags_opts");
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.tags = tags; u.per_utt = true; u.w = w; u.a = a; u.ce = ce; u.cz = cz; u.cfg = cfg;
+    return strided_step(p, u);
 }
 
 // ---- speech prompts: the packed update and step that leave each utterance's first prompt_len[b] rows alone ----
@@ -1741,9 +1790,10 @@ int ditto_guided_step_packed_prompt_opts(ditto_model_t m, float* x2, const void*
                                          int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
                                          void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
     if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_prompt_opts: null prompt_len (int32 [B])");
-    return guided_step_packed("ditto_guided_step_packed_prompt_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false,
-                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len);
+    PACKED_STEP(p, "ditto_guided_step_packed_prompt_opts");
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.step = step; u.w = w; u.a = a; u.ce = ce; u.cz = cz; u.cfg = cfg; u.prompt_len = prompt_len;
+    return strided_step(p, u);
 }
 
 int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -1753,9 +1803,11 @@ int ditto_guided_step_packed_tags_prompt_opts(ditto_model_t m, float* x2, const 
                                               const float* rope_sin, void* workspace, size_t workspace_bytes, ditto_stream_t stream,
                                               const ditto_call_opts* opts) {
     if (!prompt_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_tags_prompt_opts: null prompt_len (int32 [B])");
-    return guided_step_packed("ditto_guided_step_packed_tags_prompt_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true,
-                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len);
+    PACKED_STEP(p, "ditto_guided_step_packed_tags_prompt_opts");
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.tags = tags; u.per_utt = true; u.w = w; u.a = a; u.ce = ce; u.cz = cz; u.cfg = cfg;
+    u.prompt_len = prompt_len;
+    return strided_step(p, u);
 }
 
 // ---- the second-order multistep solver over packed batches (guided_multistep.hip) ----
@@ -1788,38 +1840,22 @@ int ditto_multistep_update_packed(float* x2, const float* eps2, float* q, const 
                                     cfg, stream);
 }
 
-static int guided_step_multistep(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
-                                 const int32_t* cu_text, const int32_t* prompt_len, float* q, const ditto_multistep_coef* step,
-                                 const ditto_multistep_coef* coefs_in, const float* w, int B, int S, int max_N, int S_T, int max_T, int cfg,
-                                 const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
-                                 ditto_stream_t stream, const ditto_call_opts* opts, const int32_t* suffix_len = nullptr,
-                                 const RescaleReq* rs = nullptr) {
-    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (int rc = check_multistep(who, x2, x2, q, step, coefs_in, w, cu_speech, B, max_N, m->cfg.hidden_dim, cfg)) return rc;
-    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
-    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
-    if (rs) {
-        if (!coefs_in) return fail(DITTO_ERR_ARG, "%s: guidance rescale needs coefs (device [B])", who);
-        if (int rc = check_rescale(who, x2, nullptr, rs->phi, nullptr, coefs_in, cu_speech, nullptr, B, 0, S, 0, max_N, m->cfg.hidden_dim,
-                                   rs->scratch, rs->scratch_bytes))
-            return rc;
-    }
-    return with_opts(opts, [&]() -> int {
-        const int nb = cfg ? 2 * B : B, rows = cfg ? 2 * S : S;          // the forward of guided_step_packed: [x; x] x [text; null]
-        float* eps;
-        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
-                                  BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
-            return rc;
-        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-        const ditto_multistep_coef* coefs = coefs_in;
-        if (rs) {                                                        // ke[b] s_b: the per-utterance update reads the scratch's copy
-            const RescaleArgs ra = rescale_args(eps, nullptr, rs->phi, nullptr, coefs_in, cu_speech, prompt_len, nullptr, B, 0, S, 0,
-                                                m->cfg.hidden_dim, rs->scratch, rs->scratch_bytes);
-            HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
-            coefs = (const ditto_multistep_coef*)rs->scratch;
-        }
-        HIP_TRY(launch_multistep_update_packed(x2, eps, q, step, coefs, w, cu_speech, prompt_len, suffix_len, B, S, max_N, m->cfg.hidden_dim,
-                                               cfg != 0, (hipStream_t)stream));
+// the multistep update of a step, over the forward of strided_step: [x; x] x [text; null] under guidance
+struct MultistepUpdate {
+    float* q; const ditto_multistep_coef *step, *coefs; const float* w; const int32_t *prompt_len, *suffix_len; int cfg;
+    const RescaleReq* rs;            // guidance rescale: the per-utterance update then reads ke[b] s_b from the scratch's copy of coefs
+};
+static int multistep_step(PackedStep& p, const MultistepUpdate& u) {
+    p.forward_over(u.cfg != 0);
+    return packed_step(p, [&](int d) -> int {
+        return check_multistep(p.who, p.x2, p.x2, u.q, u.step, u.coefs, u.w, p.cu_speech, p.B, p.max_N, d, u.cfg);
+    }, [&](int d) -> int {
+        return u.rs ? check_step_rescale(p, *u.rs, d) : DITTO_OK;
+    }, [&](const float* eps, int d) -> int {
+        const ditto_multistep_coef* coefs = u.coefs;
+        if (u.rs && !(coefs = (const ditto_multistep_coef*)step_rescale(p, *u.rs, eps, d))) return DITTO_ERR_HIP;
+        HIP_TRY(launch_multistep_update_packed(p.x2, eps, u.q, u.step, coefs, u.w, p.cu_speech, u.prompt_len, u.suffix_len, p.B, p.S,
+                                               p.max_N, d, u.cfg != 0, (hipStream_t)p.stream));
         return DITTO_OK;
     });
 }
@@ -1829,8 +1865,10 @@ int ditto_guided_step_packed_multistep_opts(ditto_model_t m, float* x2, const vo
                                             const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, const float* w, int B,
                                             int S, int max_N, int S_T, int max_T, int cfg, const float* rope_cos, const float* rope_sin,
                                             void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
-    return guided_step_multistep("ditto_guided_step_packed_multistep_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q, step, coefs,
-                                 w, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts);
+    PACKED_STEP(p, "ditto_guided_step_packed_multistep_opts");
+    MultistepUpdate u{};
+    u.q = q; u.step = step; u.coefs = coefs; u.w = w; u.prompt_len = prompt_len; u.cfg = cfg;
+    return multistep_step(p, u);
 }
 
 // ---- guidance in a limited interval: a step in which G of the B utterances are guided (guided_mixed.hip) ----
@@ -1859,36 +1897,21 @@ int ditto_guided_update_packed_mixed(float* x2, const float* eps2, const float* 
     return DITTO_OK;
 }
 
-static int guided_step_mixed(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
-                             const int32_t* cu_text, const int32_t* partner, const int32_t* prompt_len, const float* noise,
-                             const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce_in, const float* cz,
-                             int B, int G, int S, int S_G, int max_N, int S_T, int max_T, const float* rope_cos, const float* rope_sin,
-                             void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
-                             const RescaleReq* rs = nullptr) {
-    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    if (int rc = check_mixed(who, x2, x2, noise, seeds, tags, w, a, ce_in, cz, cu_speech, partner, B, G, S, S_G, max_N, m->cfg.hidden_dim))
-        return rc;
-    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
-    if (S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
-    if (rs)
-        if (int rc = check_rescale(who, x2, w, rs->phi, ce_in, nullptr, cu_speech, partner, B, G, S, S_G, max_N, m->cfg.hidden_dim,
-                                   rs->scratch, rs->scratch_bytes))
+// the mixed step: the forward over [x; the guided ones' copies] x [text; their null], the tagged strided update over partner
+static int mixed_step(PackedStep& p, const StridedUpdate& u) {
+    return packed_step(p, [&](int d) -> int {
+        if (int rc = check_mixed(p.who, p.x2, p.x2, u.noise, u.seeds, u.tags, u.w, u.a, u.ce, u.cz, p.cu_speech, u.partner, p.B, u.G, p.S,
+                                 u.S_G, p.max_N, d))
             return rc;
-    return with_opts(opts, [&]() -> int {
-        float* eps;                                                   // the forward over [x; the guided ones' copies] x [text; their null]
-        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
-                                  BatchLayout::packed(B + G, S + S_G, max_N, S_T, max_T, cu_speech, cu_text), &eps))
-            return rc;
-        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-        const float* ce = ce_in;
-        if (rs) {
-            const RescaleArgs ra = rescale_args(eps, w, rs->phi, ce_in, nullptr, cu_speech, prompt_len, partner, B, G, S, S_G,
-                                                m->cfg.hidden_dim, rs->scratch, rs->scratch_bytes);
-            HIP_TRY(launch_guidance_rescale(ra, max_N, (hipStream_t)stream));
-            ce = ra.coef_out;
-        }
-        HIP_TRY(launch_guided_update_mixed(x2, eps, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, prompt_len, B, G, S, S_G, max_N,
-                                           m->cfg.hidden_dim, (hipStream_t)stream));
+        p.nb = p.B + u.G; p.rows = p.S + u.S_G;   // G <= B and S_G <= S from here on
+        return DITTO_OK;
+    }, [&](int d) -> int {
+        return u.rs ? check_step_rescale(p, *u.rs, d) : DITTO_OK;
+    }, [&](const float* eps, int d) -> int {
+        const float* ce = u.ce;
+        if (u.rs && !(ce = (const float*)step_rescale(p, *u.rs, eps, d))) return DITTO_ERR_HIP;
+        HIP_TRY(launch_guided_update_mixed(p.x2, eps, u.noise, u.seeds, u.tags, u.w, u.a, ce, u.cz, p.cu_speech, u.partner, u.prompt_len,
+                                           p.B, u.G, p.S, u.S_G, p.max_N, d, (hipStream_t)p.stream));
         return DITTO_OK;
     });
 }
@@ -1899,9 +1922,11 @@ int ditto_guided_step_packed_mixed_opts(ditto_model_t m, float* x2, const void* 
                                         const float* cz, int B, int G, int S, int S_G, int max_N, int S_T, int max_T,
                                         const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                                         ditto_stream_t stream, const ditto_call_opts* opts) {
-    return guided_step_mixed("ditto_guided_step_packed_mixed_opts", m, x2, cond, t, cu_speech, cu_text, partner, prompt_len, noise, seeds,
-                             tags, w, a, ce, cz, B, G, S, S_G, max_N, S_T, max_T, rope_cos, rope_sin, workspace, workspace_bytes, stream,
-                             opts);
+    PACKED_STEP(p, "ditto_guided_step_packed_mixed_opts");
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.tags = tags; u.w = w; u.a = a; u.ce = ce; u.cz = cz;
+    u.prompt_len = prompt_len; u.partner = partner; u.G = G; u.S_G = S_G;
+    return mixed_step(p, u);
 }
 
 // ---- guidance rescale (Lin et al. 2024, section 3.4; guided_rescale.hip): the statistics alone, and the steps that use them ----
@@ -1933,13 +1958,16 @@ int ditto_guided_step_packed_rescale_opts(ditto_model_t m, float* x2, const void
                                           size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
                                           const ditto_call_opts* opts) {
     const char* who = "ditto_guided_step_packed_rescale_opts";
-    const RescaleReq rs{phi, scratch, scratch_bytes};
     if (!w) return fail(DITTO_ERR_ARG, "%s: guidance rescale needs w (fp32 [B])", who);
-    if (partner)   // some utterances guided: the mixed entry's forward and update
-        return guided_step_mixed(who, m, x2, cond, t, cu_speech, cu_text, partner, prompt_len, noise, seeds, tags, w, a, ce, cz, B, G, S, S_G,
-                                 max_N, S_T, max_T, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts, &rs);
-    return guided_step_packed(who, m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, tags, tags != nullptr, w, a, ce, cz, B, S, max_N,
-                              S_T, max_T, 1, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts, prompt_len, nullptr, &rs);
+    PACKED_STEP(p, who);
+    RescaleReq rs{};
+    rs.phi = phi; rs.scratch = scratch; rs.scratch_bytes = scratch_bytes; rs.w = w; rs.coef_in = ce; rs.prompt_len = prompt_len;
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.step = step; u.tags = tags; u.per_utt = tags != nullptr; u.w = w; u.a = a; u.ce = ce; u.cz = cz;
+    u.cfg = 1; u.prompt_len = prompt_len; u.rs = &rs;
+    if (!partner) return strided_step(p, u);
+    rs.partner = u.partner = partner; rs.G = u.G = G; rs.S_G = u.S_G = S_G;   // some utterances guided: the mixed entry's forward and update
+    return mixed_step(p, u);
 }
 
 int ditto_guided_step_packed_multistep_rescale_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
@@ -1948,10 +1976,12 @@ int ditto_guided_step_packed_multistep_rescale_opts(ditto_model_t m, float* x2, 
                                                     int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
                                                     size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
                                                     const ditto_call_opts* opts) {
-    const RescaleReq rs{phi, scratch, scratch_bytes};
-    return guided_step_multistep("ditto_guided_step_packed_multistep_rescale_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q,
-                                 nullptr, coefs, nullptr, B, S, max_N, S_T, max_T, 1, rope_cos, rope_sin, workspace, workspace_bytes, stream,
-                                 opts, nullptr, &rs);
+    PACKED_STEP(p, "ditto_guided_step_packed_multistep_rescale_opts");
+    RescaleReq rs{};
+    rs.phi = phi; rs.scratch = scratch; rs.scratch_bytes = scratch_bytes; rs.coefs = coefs; rs.prompt_len = prompt_len;
+    MultistepUpdate u{};
+    u.q = q; u.coefs = coefs; u.prompt_len = prompt_len; u.cfg = 1; u.rs = &rs;
+    return multistep_step(p, u);
 }
 
 // ---- span-masked training over a packed batch (span_train.hip): the span behind a prompt, or a window with context on both sides ----
@@ -2061,9 +2091,11 @@ int ditto_guided_step_packed_window_opts(ditto_model_t m, float* x2, const void*
                                          const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                                          ditto_stream_t stream, const ditto_call_opts* opts) {
     if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_window_opts: null suffix_len (int32 [B])");
-    return guided_step_packed("ditto_guided_step_packed_window_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, step, nullptr, false,
-                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len, suffix_len);
+    PACKED_STEP(p, "ditto_guided_step_packed_window_opts");
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.step = step; u.w = w; u.a = a; u.ce = ce; u.cz = cz; u.cfg = cfg;
+    u.prompt_len = prompt_len; u.suffix_len = suffix_len;
+    return strided_step(p, u);
 }
 
 int ditto_guided_step_packed_tags_window_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
@@ -2073,9 +2105,11 @@ int ditto_guided_step_packed_tags_window_opts(ditto_model_t m, float* x2, const 
                                               int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                                               size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
     if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_tags_window_opts: null suffix_len (int32 [B])");
-    return guided_step_packed("ditto_guided_step_packed_tags_window_opts", m, x2, cond, t, cu_speech, cu_text, noise, seeds, 0, tags, true,
-                              w, a, ce, cz, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                              prompt_len, suffix_len);
+    PACKED_STEP(p, "ditto_guided_step_packed_tags_window_opts");
+    StridedUpdate u{};
+    u.noise = noise; u.seeds = seeds; u.tags = tags; u.per_utt = true; u.w = w; u.a = a; u.ce = ce; u.cz = cz; u.cfg = cfg;
+    u.prompt_len = prompt_len; u.suffix_len = suffix_len;
+    return strided_step(p, u);
 }
 
 int ditto_multistep_update_window(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,
@@ -2093,9 +2127,10 @@ int ditto_guided_step_packed_multistep_window_opts(ditto_model_t m, float* x2, c
                                                    int max_T, int cfg, const float* rope_cos, const float* rope_sin, void* workspace,
                                                    size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
     if (!suffix_len) return fail(DITTO_ERR_ARG, "ditto_guided_step_packed_multistep_window_opts: null suffix_len (int32 [B])");
-    return guided_step_multistep("ditto_guided_step_packed_multistep_window_opts", m, x2, cond, t, cu_speech, cu_text, prompt_len, q, step,
-                                 coefs, w, B, S, max_N, S_T, max_T, cfg, rope_cos, rope_sin, workspace, workspace_bytes, stream, opts,
-                                 suffix_len);
+    PACKED_STEP(p, "ditto_guided_step_packed_multistep_window_opts");
+    MultistepUpdate u{};
+    u.q = q; u.step = step; u.coefs = coefs; u.w = w; u.prompt_len = prompt_len; u.suffix_len = suffix_len; u.cfg = cfg;
+    return multistep_step(p, u);
 }
 
 // ---- guidance reuse (guided_reuse.hip): every argument is checked here, before any launch ----
@@ -2133,42 +2168,22 @@ int ditto_multistep_update_packed_reuse(float* x2, const float* eps, float* q, f
     return DITTO_OK;
 }
 
-// the forward of a refresh (STORE: guided_step_packed's, the 2B utterances of [x; x] x [text; null]) or of a reuse step (LOAD: the B
-// conditional utterances over S rows with the text-only conditioning), then `update` on its eps
-extern "C++" template <class F> static int reuse_step(const char* who, ditto_model_t m, float* x2, const void* cond, const int64_t* t,
-                                         const int32_t* cu_speech, const int32_t* cu_text, int B, int S, int max_N, int S_T, int max_T,
-                                         int mode, const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
-                                         ditto_stream_t stream, const ditto_call_opts* opts, F&& update) {
-    if (B > 32767) return fail(DITTO_ERR_SHAPE, "%s: more than 32767 utterances", who);
-    if (S <= 0 || S > 0x3fffffff) return fail(DITTO_ERR_SHAPE, "%s: S must lie in [1, 2^30)", who);
-    return with_opts(opts, [&]() -> int {
-        const int nb = mode == 1 ? 2 * B : B, rows = mode == 1 ? 2 * S : S;
-        float* eps;
-        if (int rc = step_forward(who, m, x2, cond, t, {rope_cos, rope_sin}, {workspace, workspace_bytes}, stream,
-                                  BatchLayout::packed(nb, rows, max_N, S_T, max_T, cu_speech, cu_text), &eps))
-            return rc;
-        ProfScope ps(m, (hipStream_t)stream, DITTO_KC_UPDATE);
-        HIP_TRY(update(eps));
-        return DITTO_OK;
-    });
-}
-
 int ditto_guided_step_packed_reuse_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
                                         const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len, float* delta,
                                         const float* noise, const int64_t* seeds, uint32_t step, const float* w, const float* a,
                                         const float* ce, const float* cz, int B, int S, int max_N, int S_T, int max_T, int mode,
                                         int mirror, const float* rope_cos, const float* rope_sin, void* workspace,
                                         size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
-    const char* who = "ditto_guided_step_packed_reuse_opts";
-    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    const int d = m->cfg.hidden_dim;
-    if (int rc = check_guided_update(who, x2, x2, noise, seeds, w, a, ce, cz, B, max_N, d, 1)) return rc;
-    if (int rc = check_reuse(who, delta, w, cu_speech, B, S, max_N, mode, mirror)) return rc;
-    return reuse_step(who, m, x2, cond, t, cu_speech, cu_text, B, S, max_N, S_T, max_T, mode, rope_cos, rope_sin, workspace,
-                      workspace_bytes, stream, opts, [&](const float* eps) {
-                          return launch_guided_update_reuse(x2, eps, delta, noise, seeds, step, w, a, ce, cz, cu_speech, prompt_len,
-                                                            suffix_len, B, S, max_N, d, mode, mirror, (hipStream_t)stream);
-                      });
+    PACKED_STEP(p, "ditto_guided_step_packed_reuse_opts");
+    p.forward_over(mode == 1);
+    return packed_step(p, [&](int d) -> int {
+        if (int rc = check_guided_update(p.who, x2, x2, noise, seeds, w, a, ce, cz, B, max_N, d, 1)) return rc;
+        return check_reuse(p.who, delta, w, cu_speech, B, S, max_N, mode, mirror);
+    }, [&](const float* eps, int d) -> int {
+        HIP_TRY(launch_guided_update_reuse(x2, eps, delta, noise, seeds, step, w, a, ce, cz, cu_speech, prompt_len, suffix_len, B, S, max_N,
+                                           d, mode, mirror, (hipStream_t)stream));
+        return DITTO_OK;
+    });
 }
 
 int ditto_guided_step_packed_multistep_reuse_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
@@ -2177,17 +2192,17 @@ int ditto_guided_step_packed_multistep_reuse_opts(ditto_model_t m, float* x2, co
                                                   const float* w, int B, int S, int max_N, int S_T, int max_T, int mode, int mirror,
                                                   const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes,
                                                   ditto_stream_t stream, const ditto_call_opts* opts) {
-    const char* who = "ditto_guided_step_packed_multistep_reuse_opts";
-    if (!m) return fail(DITTO_ERR_ARG, "bad argument to %s", who);
-    const int d = m->cfg.hidden_dim;
-    if (!step) return fail(DITTO_ERR_ARG, "%s: null step (host ditto_multistep_coef)", who);
-    if (int rc = check_multistep(who, x2, x2, q, step, nullptr, w, cu_speech, B, max_N, d, 1)) return rc;
-    if (int rc = check_reuse(who, delta, w, cu_speech, B, S, max_N, mode, mirror)) return rc;
-    return reuse_step(who, m, x2, cond, t, cu_speech, cu_text, B, S, max_N, S_T, max_T, mode, rope_cos, rope_sin, workspace,
-                      workspace_bytes, stream, opts, [&](const float* eps) {
-                          return launch_multistep_update_reuse(x2, eps, q, delta, step, w, cu_speech, prompt_len, suffix_len, B, S, max_N,
-                                                               d, mode, mirror, (hipStream_t)stream);
-                      });
+    PACKED_STEP(p, "ditto_guided_step_packed_multistep_reuse_opts");
+    p.forward_over(mode == 1);
+    return packed_step(p, [&](int d) -> int {
+        if (!step) return fail(DITTO_ERR_ARG, "%s: null step (host ditto_multistep_coef)", p.who);
+        if (int rc = check_multistep(p.who, x2, x2, q, step, nullptr, w, cu_speech, B, max_N, d, 1)) return rc;
+        return check_reuse(p.who, delta, w, cu_speech, B, S, max_N, mode, mirror);
+    }, [&](const float* eps, int d) -> int {
+        HIP_TRY(launch_multistep_update_reuse(x2, eps, q, delta, step, w, cu_speech, prompt_len, suffix_len, B, S, max_N, d, mode, mirror,
+                                              (hipStream_t)stream));
+        return DITTO_OK;
+    });
 }
 
 int ditto_regroup_packed(const ditto_regroup_seg* table, int n_seg, const void* const* src, const size_t* src_bytes, void* const* dst,

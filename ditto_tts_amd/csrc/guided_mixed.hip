@@ -5,7 +5,7 @@
 // offsets: what the forward over the B + G utterances reads).  partner[b]: the copy of utterance b, or -1.
 //   with a partner:  e = fmaf(w, c - u, u), u read at the copy's rows; x' goes to b's rows and to the copy's   (the CFG instantiation)
 //   without:         e = c; nothing of rows [S, S + S_G) is read or written                                     (the non-CFG one)
-// guided_update.h's arithmetic over the generated rows, tags per utterance, no draw at cz == 0 (guided_tags.hip, guided_prompt.hip):
+// guided_update.h's arithmetic over the generated rows, tags per utterance, no draw at cz == 0 (guided_packed.hip):
 // a kernel of its own, so that those keep their machine code.  HBM traffic per generated element: 20 B guided, 12 B (+ 4 B of a
 // noise buffer) not; 0 B per prompt element.
 #include "guided_update.h"
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void guided_update_mixed_kernel(float* __restr
     int r0 = cu[b];
     r0 = r0 < 0 ? 0 : (r0 > S - 1 ? S - 1 : r0);
     int n = cu[b + 1] - r0;
-    n = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);                      // guided_span's clamp
+    n = n < 1 ? 1 : (n > S - r0 ? S - r0 : n);                      // utt_rows' clamp
     int g = partner[b];
     g = g < -1 ? -1 : (g > G - 1 ? G - 1 : g);
     int u0 = 0;
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void guided_update_mixed_kernel(float* __restr
         u0 = u0 < S ? S : (u0 > S + S_G - n ? S + S_G - n : u0);
     }
     int p = prompt_len ? prompt_len[b] : 0;
-    p = p < 0 ? 0 : (p > n - 1 ? n - 1 : p);                        // prompt_span's clamp
+    p = p < 0 ? 0 : (p > n - 1 ? n - 1 : p);                        // window_span's clamp
     const size_t d4 = (size_t)d / 4, base4 = (size_t)(r0 + p) * d4, n4 = (size_t)(n - p) * d4;
     const GuidedCoef k = guided_coef<NOISE, true>(a, ce, cz, w, seeds, b);
     const unsigned tag = NOISE == 2 ? tags[b] : 0u;

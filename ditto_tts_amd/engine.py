@@ -275,6 +275,40 @@ class DenoiseEngine:
         cu, max_N = self._cu(cu_seqlens, len(cu_seqlens) - 1, S, max_seqlen, "cu_seqlens")
         return (doubled_cu_seqlens(cu) if cfg else cu).to(self.device), max_N
 
+    def _packed_step_args(self, who, x2, cond, t, B, doubled, offsets, cu_seqlens, max_seqlen, prompt_len, suffix_len, mirror, opts):
+        """The checks every packed guided step shares, after _guided_args' on x2.  `doubled`: x2 [2S, d] = [x; x], cond over
+        [text; null], t [2B], offsets [2B + 1] (under guidance, or a refresh of the reuse steps); else x2 [S, d], cond over the text
+        alone, t [B], offsets [B + 1].  `mirror` (None outside the reuse steps): x2 is a view of the first S rows of a [2S, d] state.
+        Returns (S, nb, max_N, head, tail): the first six and the last six arguments of the step's library call — handle, x2, cond,
+        t, speech offsets, text offsets; rope cos, rope sin, workspace, its bytes, stream, opts."""
+        rows, d = int(x2.shape[0]), int(x2.shape[1])
+        if doubled and rows % 2:
+            raise ValueError("x2 must hold [x; x] " + ("under guidance" if mirror is None else "at a refresh step"))
+        S = rows // 2 if doubled else rows
+        if mirror and (x2.storage_offset() + 2 * S * d) * 4 > x2.untyped_storage().nbytes():
+            raise ValueError(f"{who}: mirror writes rows [S, 2S): x2 must be the first {S} rows of a [{2 * S}, {d}] buffer")
+        nb = 2 * B if doubled else B
+        self._packed_cond(cond, nb)
+        if offsets is None:
+            offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, doubled)
+        cud, max_N = offsets
+        if cud.shape != (nb + 1,):
+            raise ValueError(f"offsets: [{nb + 1}] expected")
+        for name, v in (("prompt_len", prompt_len), ("suffix_len", suffix_len)):
+            if v is not None and not (v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.shape == (B,)):
+                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of shape [{B}]")
+        tt = self._t64(t, nb)
+        self._step_keep = tt, cud   # until the next step: a t converted or offsets built here must outlive the caller's own allocations
+        ws = self.workspace_packed(nb, rows, cond.T)
+        c, s = self.rope_tables(max_N)
+        return S, nb, max_N, (self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr()), \
+            (c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts))
+
+    @staticmethod
+    def _rows_like(name, v, S, d):
+        if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (S, d)):
+            raise ValueError(f"{name} must be a contiguous fp32 CUDA tensor of shape [{S}, {d}]")
+
     def guided_step_packed_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, a: torch.Tensor, ce: torch.Tensor,
                             cz: torch.Tensor, w: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                             seeds: Optional[torch.Tensor] = None, step: int = 0, cu_seqlens=None, max_seqlen: Optional[int] = None,
@@ -294,48 +328,27 @@ class DenoiseEngine:
         (ditto_guided_step_packed_window_opts; prompt_len may be None).  Not together with phi."""
         sd, noise = self._guided_args("guided_step_packed_", x2, 2, B, a, ce, cz, w, noise, seeds)
         cfg = w is not None
-        nb = 2 * B if cfg else B
-        rows = x2.shape[0]
-        if cfg and rows % 2:
-            raise ValueError("x2 must hold [x; x] under guidance")
-        S = rows // 2 if cfg else rows
-        self._packed_cond(cond, nb)
-        if offsets is None:
-            offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, cfg)
-        cud, max_N = offsets
-        if cud.shape != (nb + 1,):
-            raise ValueError(f"offsets: [{nb + 1}] expected")
-        tt = self._t64(t, nb)
-        ws = self.workspace_packed(nb, rows, cond.T)
-        c, s = self.rope_tables(max_N)
-        if prompt_len is not None and not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous()
-                                           and prompt_len.shape == (B,)):
-            raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
-        if suffix_len is not None and not (suffix_len.is_cuda and suffix_len.dtype == torch.int32 and suffix_len.is_contiguous()
-                                           and suffix_len.shape == (B,)):
-            raise ValueError(f"suffix_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        S, _, max_N, head, tail = self._packed_step_args("guided_step_packed_", x2, cond, t, B, cfg, offsets, cu_seqlens, max_seqlen,
+                                                         prompt_len, suffix_len, None, opts)
         if suffix_len is not None and phi is not None:
             raise NotImplementedError("guidance rescale has no windowed form (suffix_len with phi)")
+        step = int(step) & 0xFFFFFFFF
         if phi is not None:
             if not cfg:
                 raise ValueError("guidance rescale needs the guidance scales w")
             phi, rs = self._rescale_args(phi, rescale_scratch, B, max_N)
             hip.check(self.lib.ditto_guided_step_packed_rescale_opts(
-                self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), None,
-                _ptr(prompt_len), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, None, w.data_ptr(), phi.data_ptr(), a.data_ptr(),
-                ce.data_ptr(), cz.data_ptr(), B, 0, S, 0, max_N, cond.T, cond.max_len, c.data_ptr(), s.data_ptr(), ws.data_ptr(),
-                ws.numel(), rs.data_ptr(), rs.numel(), _stream(), None if opts is None else C.byref(opts)))
+                *head, None, _ptr(prompt_len), _ptr(noise), _ptr(sd), step, None, w.data_ptr(), phi.data_ptr(), a.data_ptr(),
+                ce.data_ptr(), cz.data_ptr(), B, 0, S, 0, max_N, cond.T, cond.max_len, *tail[:4], rs.data_ptr(), rs.numel(), *tail[4:]))
             return x2
         if suffix_len is not None:
-            entry, head = self.lib.ditto_guided_step_packed_window_opts, (_ptr(prompt_len), suffix_len.data_ptr())
+            entry, spans = self.lib.ditto_guided_step_packed_window_opts, (_ptr(prompt_len), suffix_len.data_ptr())
         elif prompt_len is not None:
-            entry, head = self.lib.ditto_guided_step_packed_prompt_opts, (prompt_len.data_ptr(),)
+            entry, spans = self.lib.ditto_guided_step_packed_prompt_opts, (prompt_len.data_ptr(),)
         else:
-            entry, head = self.lib.ditto_guided_step_packed_opts, ()
-        hip.check(entry(
-            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), *head, _ptr(noise),
-            _ptr(sd), int(step) & 0xFFFFFFFF, _ptr(w), a.data_ptr(), ce.data_ptr(), cz.data_ptr(), B, S, max_N, cond.T, cond.max_len,
-            int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+            entry, spans = self.lib.ditto_guided_step_packed_opts, ()
+        hip.check(entry(*head, *spans, _ptr(noise), _ptr(sd), step, _ptr(w), a.data_ptr(), ce.data_ptr(), cz.data_ptr(), B, S, max_N,
+                        cond.T, cond.max_len, int(cfg), *tail))
         return x2
 
     def guided_step_packed_multistep_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
@@ -359,80 +372,35 @@ class DenoiseEngine:
         if coefs is not None and not (coefs.is_cuda and coefs.dtype == torch.float32 and coefs.is_contiguous()
                                       and coefs.shape == (B, 8) and coefs.data_ptr() % 16 == 0):
             raise ValueError(f"coefs must be a contiguous, 16-byte aligned fp32 CUDA tensor of shape [{B}, 8]")
-        nb = 2 * B if cfg else B
-        rows = x2.shape[0]
-        if cfg and rows % 2:
-            raise ValueError("x2 must hold [x; x] under guidance")
-        S = rows // 2 if cfg else rows
-        if not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.shape == (S, x2.shape[1])):
-            raise ValueError(f"q must be a contiguous fp32 CUDA tensor of shape [{S}, {x2.shape[1]}]")
-        self._packed_cond(cond, nb)
-        if offsets is None:
-            offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, cfg)
-        cud, max_N = offsets
-        if cud.shape != (nb + 1,):
-            raise ValueError(f"offsets: [{nb + 1}] expected")
-        if prompt_len is not None and not (prompt_len.is_cuda and prompt_len.dtype == torch.int32 and prompt_len.is_contiguous()
-                                           and prompt_len.shape == (B,)):
-            raise ValueError(f"prompt_len must be a contiguous int32 CUDA tensor of shape [{B}]")
-        if suffix_len is not None and not (suffix_len.is_cuda and suffix_len.dtype == torch.int32 and suffix_len.is_contiguous()
-                                           and suffix_len.shape == (B,)):
-            raise ValueError(f"suffix_len must be a contiguous int32 CUDA tensor of shape [{B}]")
+        S, _, max_N, head, tail = self._packed_step_args("guided_step_packed_multistep_", x2, cond, t, B, cfg, offsets, cu_seqlens,
+                                                         max_seqlen, prompt_len, suffix_len, None, opts)
+        self._rows_like("q", q, S, x2.shape[1])
         if suffix_len is not None and phi is not None:
             raise NotImplementedError("guidance rescale has no windowed form (suffix_len with phi)")
-        tt = self._t64(t, nb)
-        ws = self.workspace_packed(nb, rows, cond.T)
-        c, s = self.rope_tables(max_N)
         if coefs is not None:
             phi, rs = self._rescale_args(phi, rescale_scratch, B, max_N)
             hip.check(self.lib.ditto_guided_step_packed_multistep_rescale_opts(
-                self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(),
-                _ptr(prompt_len), q.data_ptr(), coefs.data_ptr(), phi.data_ptr(), B, S, max_N, cond.T, cond.max_len, c.data_ptr(),
-                s.data_ptr(), ws.data_ptr(), ws.numel(), rs.data_ptr(), rs.numel(), _stream(), None if opts is None else C.byref(opts)))
+                *head, _ptr(prompt_len), q.data_ptr(), coefs.data_ptr(), phi.data_ptr(), B, S, max_N, cond.T, cond.max_len, *tail[:4],
+                rs.data_ptr(), rs.numel(), *tail[4:]))
             return x2
         if suffix_len is not None:
-            hip.check(self.lib.ditto_guided_step_packed_multistep_window_opts(
-                self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(),
-                _ptr(prompt_len), suffix_len.data_ptr(), q.data_ptr(), C.byref(coef), None, _ptr(w), B, S, max_N, cond.T, cond.max_len,
-                int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
-            return x2
-        hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
-            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
-            q.data_ptr(), C.byref(coef), None, _ptr(w), B, S, max_N, cond.T, cond.max_len, int(cfg), c.data_ptr(), s.data_ptr(),
-            ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+            entry, spans = self.lib.ditto_guided_step_packed_multistep_window_opts, (_ptr(prompt_len), suffix_len.data_ptr())
+        else:
+            entry, spans = self.lib.ditto_guided_step_packed_multistep_opts, (_ptr(prompt_len),)
+        hip.check(entry(*head, *spans, q.data_ptr(), C.byref(coef), None, _ptr(w), B, S, max_N, cond.T, cond.max_len, int(cfg), *tail))
         return x2
 
     # ------------------------------------------------------------------ guidance reuse (csrc/guided_reuse.hip)
-    def _reuse_args(self, who, x2, cond, t, B, delta, w, mode, mirror, offsets, cu_seqlens, max_seqlen, prompt_len, suffix_len):
-        """The checks both reuse steps share.  STORE (a refresh): x2 [2S, d] = [x; x], cond over [text; null], t [2B], offsets [2B + 1].
-        LOAD (a reuse step): x2 [S, d] — the conditional half, a view of the first S rows of the [2S, d] state when `mirror` —, cond
-        over the text alone, t [B], offsets [B + 1].  Returns (S, nb, device offsets, max_N, t as int64)."""
+    @staticmethod
+    def _reuse_mode(who, mode, mirror, w) -> bool:
+        """The checks of both reuse steps' mode; True at STORE (a refresh: the doubled state), False at LOAD (a reuse step)"""
         if mode not in (hip.REUSE_STORE, hip.REUSE_LOAD):
             raise ValueError(f"{who}: mode must be hip.REUSE_STORE or hip.REUSE_LOAD, got {mode!r}")
-        store = mode == hip.REUSE_STORE
-        if store and mirror:
+        if mode == hip.REUSE_STORE and mirror:
             raise ValueError(f"{who}: mirror belongs to a reuse step (a refresh writes both halves anyway)")
         if w is None:
             raise ValueError(f"{who}: guidance reuse needs the guidance scales w")
-        rows, d = int(x2.shape[0]), int(x2.shape[1])
-        if store and rows % 2:
-            raise ValueError("x2 must hold [x; x] at a refresh step")
-        S = rows // 2 if store else rows
-        if mirror and (x2.storage_offset() + 2 * S * d) * 4 > x2.untyped_storage().nbytes():
-            raise ValueError(f"{who}: mirror writes rows [S, 2S): x2 must be the first {S} rows of a [{2 * S}, {d}] buffer")
-        if not (delta.is_cuda and delta.dtype == torch.float32 and delta.is_contiguous() and delta.shape == (S, d)):
-            raise ValueError(f"delta must be a contiguous fp32 CUDA tensor of shape [{S}, {d}]")
-        nb = 2 * B if store else B
-        self._packed_cond(cond, nb)
-        if offsets is None:
-            offsets = self.guided_offsets_packed(cu_seqlens, S, max_seqlen, store)
-        cud, max_N = offsets
-        if cud.shape != (nb + 1,):
-            raise ValueError(f"offsets: [{nb + 1}] expected")
-        for name, v in (("prompt_len", prompt_len), ("suffix_len", suffix_len)):
-            if v is not None and not (v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and v.shape == (B,)):
-                raise ValueError(f"{name} must be a contiguous int32 CUDA tensor of shape [{B}]")
-        return S, nb, cud, max_N, self._t64(t, nb)
+        return mode == hip.REUSE_STORE
 
     def guided_step_packed_reuse_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, delta: torch.Tensor,
                                   a: torch.Tensor, ce: torch.Tensor, cz: torch.Tensor, w: torch.Tensor, mode: int, mirror: bool = False,
@@ -447,18 +415,15 @@ class DenoiseEngine:
         `mirror`, x' is written to rows [S, 2S) of the buffer x2 is the first half of as well (what the next refresh reads).
         Everything else as guided_step_packed_."""
         who = "guided_step_packed_reuse_"
-        store = mode == hip.REUSE_STORE
-        sd, noise = self._guided_args(who, x2, 2, B, a, ce, cz, w if store else None, noise, seeds)
+        sd, noise = self._guided_args(who, x2, 2, B, a, ce, cz, w if mode == hip.REUSE_STORE else None, noise, seeds)
         self._guided_args(who, x2, 2, B, None, None, None, w, None, None)
-        S, nb, cud, max_N, tt = self._reuse_args(who, x2, cond, t, B, delta, w, mode, mirror, offsets, cu_seqlens, max_seqlen,
-                                                 prompt_len, suffix_len)
-        ws = self.workspace_packed(nb, nb // B * S, cond.T)
-        c, s = self.rope_tables(max_N)
+        store = self._reuse_mode(who, mode, mirror, w)
+        S, _, max_N, head, tail = self._packed_step_args(who, x2, cond, t, B, store, offsets, cu_seqlens, max_seqlen, prompt_len,
+                                                         suffix_len, bool(mirror), opts)
+        self._rows_like("delta", delta, S, x2.shape[1])
         hip.check(self.lib.ditto_guided_step_packed_reuse_opts(
-            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
-            _ptr(suffix_len), delta.data_ptr(), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, w.data_ptr(), a.data_ptr(), ce.data_ptr(),
-            cz.data_ptr(), B, S, max_N, cond.T, cond.max_len, int(mode), int(bool(mirror)), c.data_ptr(), s.data_ptr(), ws.data_ptr(),
-            ws.numel(), _stream(), None if opts is None else C.byref(opts)))
+            *head, _ptr(prompt_len), _ptr(suffix_len), delta.data_ptr(), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, w.data_ptr(),
+            a.data_ptr(), ce.data_ptr(), cz.data_ptr(), B, S, max_N, cond.T, cond.max_len, int(mode), int(bool(mirror)), *tail))
         return x2
 
     def guided_step_packed_multistep_reuse_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
@@ -471,17 +436,14 @@ class DenoiseEngine:
         every utterance stands at, as in guided_step_packed_multistep_ (no per-utterance `coefs` form)."""
         who = "guided_step_packed_multistep_reuse_"
         self._guided_args(who, x2, 2, B, None, None, None, w, None, None)
-        S, nb, cud, max_N, tt = self._reuse_args(who, x2, cond, t, B, delta, w, mode, mirror, offsets, cu_seqlens, max_seqlen,
-                                                 prompt_len, suffix_len)
-        if not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.shape == (S, x2.shape[1])):
-            raise ValueError(f"q must be a contiguous fp32 CUDA tensor of shape [{S}, {x2.shape[1]}]")
-        ws = self.workspace_packed(nb, nb // B * S, cond.T)
-        c, s = self.rope_tables(max_N)
+        store = self._reuse_mode(who, mode, mirror, w)
+        S, _, max_N, head, tail = self._packed_step_args(who, x2, cond, t, B, store, offsets, cu_seqlens, max_seqlen, prompt_len,
+                                                         suffix_len, bool(mirror), opts)
+        self._rows_like("delta", delta, S, x2.shape[1])
+        self._rows_like("q", q, S, x2.shape[1])
         hip.check(self.lib.ditto_guided_step_packed_multistep_reuse_opts(
-            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr(), _ptr(prompt_len),
-            _ptr(suffix_len), q.data_ptr(), delta.data_ptr(), C.byref(coef), w.data_ptr(), B, S, max_N, cond.T, cond.max_len, int(mode),
-            int(bool(mirror)), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
-            None if opts is None else C.byref(opts)))
+            *head, _ptr(prompt_len), _ptr(suffix_len), q.data_ptr(), delta.data_ptr(), C.byref(coef), w.data_ptr(), B, S, max_N, cond.T,
+            cond.max_len, int(mode), int(bool(mirror)), *tail))
         return x2
 
     # ------------------------------------------------------------------ guidance rescale (csrc/guided_rescale.hip)

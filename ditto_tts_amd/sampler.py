@@ -455,31 +455,31 @@ class SpeechGenerator:
                                   noises=noises, cond_by_audio=cond_by_audio)
 
     # ---------------------------------------------------------------- guided strided loop over a variable-length batch
-    def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval=None,
-                     begin_plain=None, rescale=None, prediction="eps", refresh=None, begin_reuse=None):
-        """The strided loop of sample_guided and sample_guided_packed.  `begin(eng, cfg, seeds)` is the layout's own prologue: it
-        builds the conditioning and the state x2 (rows [x_T; room for the unconditional half] under guidance, else x_T) and returns
-        (x2, max length, step) with `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)` the layout's library call bound to
-        x2, its conditioning and its lengths or offsets.
+    def _step_loop(self, B, guidance, null_text_emb, seeds, batch_class, begin, interval, begin_plain, rescale, refresh, begin_reuse,
+                   make_schedule, solver):
+        """The loop of sample_guided and sample_guided_packed, whatever the solver.  `begin(eng, cfg, seeds)` is the layout's own
+        prologue: it builds the conditioning and the state x2 (rows [x_T; room for the unconditional half] under guidance, else
+        x_T) and returns (x2, max length, step) with `step(t=, opts=, ...)` the layout's library call bound to x2, its conditioning
+        and its lengths or offsets.
+        `make_schedule()` gives the solver's rows, the timestep first; `solver(eng, schedule, x, N, w, phi, seeds)` runs once behind
+        the prologue — x the conditional half of x2, w the guidance scales and phi the rescale factors on the device, each None
+        when unused —, allocates what the solver keeps over the call and returns `kwargs(i, kind)`: the solver's keyword arguments
+        of step i for kind "plain", "reuse" or "step", asked for once per step and in step order.
         `interval` (a guidance interval, packed batches): step i is guided where guided_steps says so; the others run
         `begin_plain(eng, x2)`'s step — the layout's non-CFG call on the conditional half of x2, built only when a step needs it.
         The unconditional half is filled from the conditional one before the first guided step, and again before the first one
         behind unguided steps; in between every guided update writes both halves itself.  With no guided step at all the call is
         the one without guidance.
-        `rescale` (rescale_vector's phi [B], packed batches): every guided step computes each utterance's guidance-rescale factor
-        from its eps and updates with ce s32 (the step's phi= argument); unguided steps rescale nothing.
-        `prediction` "v" (packed batches): the rows of strided_schedule_v — (a_v, cv) travel where (a, ce) do, to the same launches.
+        `rescale` (rescale_vector's phi [B], packed batches): guided steps rescale (the solver's "step" arguments), the others not.
         `refresh` (an int k >= 2, packed batches; None: the loop as it was): refresh_plan's schedule over the guided steps.
         `begin_reuse(eng, x2, step, delta)` returns (refresh step, reuse step, plain step): the layout's STORE call on x2 with the
         guided conditioning, its LOAD call on the conditional half with begin_plain's text-only conditioning, and begin_plain's
         step itself.  delta [rows, d] is allocated once here.  A reuse step leaves the unconditional half behind unless it
         mirrors, so the copy runs before a refresh whose preceding step did not mirror."""
-        if seeds is not None and noises is not None:
-            raise ValueError("seeds= excludes noises=")
         gv = guidance_vector(guidance, B)
         if gv is not None and null_text_emb is None:
             raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
-        schedule = (strided_schedule_v if prediction == "v" else strided_schedule)(self.alphas_cumprod, n_steps, eta)
+        schedule = make_schedule()
         guided = guided_steps(schedule, interval)
         cfg = gv is not None and any(guided)
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)   # "cuda" -> cuda:0: the engine the other loops use
@@ -495,109 +495,97 @@ class SpeechGenerator:
             step, reuse, plain = begin_reuse(eng, x2, step, torch.empty_like(x2[:rows]))
         else:
             plain = begin_plain(eng, x2) if cfg and not all(guided) else None
-        stale = cfg                                          # the unconditional half is behind the conditional one
-        # every step's coefficients in one upload: coef[i] = (a, ce, sigma) x B
-        coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
-        w = gv.to(eng.device) if cfg else None
-        rs = {} if rescale is None or not cfg else dict(phi=rescale.to(eng.device), rescale_scratch=eng.rescale_scratch(B, N))
+        kwargs = solver(eng, schedule, x2[:rows], N, gv.to(eng.device) if cfg else None,
+                        rescale.to(eng.device) if rescale is not None and cfg else None, seeds)
         t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
-        z = torch.empty_like(x2[:rows]) if seeds is None else None
         opts = plain_opts = None
         if batch_class is not None:
             from .hip import CallOpts
             opts = CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
             plain_opts = CallOpts(class_rows=int(batch_class) * N)             # what the call without guidance pins
-        for i, (t_val, _, _, sigma) in enumerate(schedule):
-            t_tensor.fill_(t_val)
-            noise = sd = None
-            if sigma != 0.0:
-                if seeds is not None:
-                    sd = seeds
-                elif noises is None:
-                    z.normal_()
-                    noise = z
-                else:
-                    z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
-                    noise = z
+        stale = cfg                                          # the unconditional half is behind the conditional one
+        for i, row in enumerate(schedule):
+            t_tensor.fill_(row[0])
             if cfg and not guided[i]:                        # outside the interval: the non-CFG step on the conditional half
-                plain(t=t_tensor[:B], a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=None, noise=noise, seeds=sd, step=t_val,
-                      opts=plain_opts)
+                plain(t=t_tensor[:B], opts=plain_opts, **kwargs(i, "plain"))
                 stale = True
-                continue
-            if kinds is not None and kinds[i] == "reuse":    # the conditional forward alone, e = c + (w - 1) delta
-                reuse(t=t_tensor[:B], a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val,
-                      opts=plain_opts, mirror=mirror[i])
+            elif kinds is not None and kinds[i] == "reuse":  # the conditional forward alone, e = c + (w - 1) delta
+                reuse(t=t_tensor[:B], opts=plain_opts, mirror=mirror[i], **kwargs(i, "reuse"))
                 stale = not mirror[i]
-                continue
-            if stale:                                        # [x; x], once; then every guided update writes both halves itself
-                x2[rows:].copy_(x2[:rows])
-                stale = False
-            step(t=t_tensor, a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=w, noise=noise, seeds=sd, step=t_val, opts=opts, **rs)
+            else:
+                if stale:                                    # [x; x], once; then every guided update writes both halves itself
+                    x2[rows:].copy_(x2[:rows])
+                    stale = False
+                step(t=t_tensor, opts=opts, **kwargs(i, "step"))
         return x2[:rows].clone() if cfg else x2
+
+    def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval=None,
+                     begin_plain=None, rescale=None, prediction="eps", refresh=None, begin_reuse=None):
+        """_step_loop for the strided (DDIM) update: `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)`.  Every step's
+        coefficients go up in one upload; step i's z (when sigma != 0) is Philox of `seeds` inside the kernel, `noises[i]`, else
+        z.normal_() from torch's generator, one draw per noisy step in step order.
+        `rescale`: every guided step computes each utterance's guidance-rescale factor from its eps and updates with ce s32 (the
+        step's phi= argument).
+        `prediction` "v" (packed batches): the rows of strided_schedule_v — (a_v, cv) travel where (a, ce) do, to the same launches."""
+        if seeds is not None and noises is not None:
+            raise ValueError("seeds= excludes noises=")
+
+        def solver(eng, schedule, x, N, w, phi, seeds):
+            # coef[i] = (a, ce, sigma) x B
+            coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
+            rs = {} if phi is None else dict(phi=phi, rescale_scratch=eng.rescale_scratch(B, N))
+            z = torch.empty_like(x) if seeds is None else None
+
+            def kwargs(i, kind):
+                noise = sd = None
+                if schedule[i][3] != 0.0:
+                    if seeds is not None:
+                        sd = seeds
+                    elif noises is None:
+                        noise = z.normal_()
+                    else:
+                        noise = z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
+                return dict(a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=None if kind == "plain" else w, noise=noise, seeds=sd,
+                            step=schedule[i][0], **(rs if kind == "step" else {}))
+            return kwargs
+
+        return self._step_loop(B, guidance, null_text_emb, seeds, batch_class, begin, interval, begin_plain, rescale, refresh, begin_reuse,
+                               lambda: (strided_schedule_v if prediction == "v" else strided_schedule)(self.alphas_cumprod, n_steps, eta),
+                               solver)
 
     def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval=None, begin_plain=None,
                         rescale=None, prediction="eps", refresh=None, begin_reuse=None):
-        """_guided_loop for solver="dpmpp2m": the same prologue (`begin`, whose step is engine.guided_step_packed_multistep_ bound to
-        x2, its conditioning and offsets), then one library call per step of multistep_schedule over x2 and the history q — one
-        buffer [S, d] per call, written by step 0 before any step reads it.  Each step's coefficients travel as a host struct.
+        """_step_loop for solver="dpmpp2m": `begin`'s step is engine.guided_step_packed_multistep_ bound to x2, its conditioning and
+        offsets; one library call per step of multistep_schedule over x2 and the history q — one buffer [S, d] per call, written
+        by step 0 before any step reads it, the x0 of whichever step wrote it (conditional, guided or reuse: no special case).
+        Each step's coefficients travel as a host struct.
         `rescale` (rescale_vector's phi [B]): the guided steps read their coefficients from DEVICE memory instead — one
         ditto_multistep_coef per utterance and step, uploaded once, the guidance scale inside — so that the rescale can patch each
         utterance's ke before the per-utterance update runs.
-        `prediction` "v": the rows of multistep_schedule_v, (kx, ke) = (alpha, -sigma), to the same launches.
-        `refresh`, `begin_reuse`: as in _guided_loop; the history q is the x0 of whichever step wrote it, reuse steps included."""
-        from .hip import CallOpts, MultistepCoef
-        gv = guidance_vector(guidance, B)
-        if gv is not None and null_text_emb is None:
-            raise ValueError("classifier-free guidance needs null_text_emb (the unconditional text embedding)")
-        schedule = (multistep_schedule_v if prediction == "v" else multistep_schedule)(self.alphas_cumprod, n_steps)
-        guided = guided_steps(schedule, interval)           # (interval, begin_plain: as in _guided_loop)
-        cfg = gv is not None and any(guided)
-        eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
-        if seeds is not None:
-            seeds = seeds.to(eng.device).long().contiguous()
-            if seeds.shape != (B,):
-                raise ValueError(f"seeds must have shape [{B}]")
-        x2, N, step = begin(eng, cfg, seeds)
-        rows = x2.shape[0] // 2 if cfg else x2.shape[0]
-        kinds = mirror = reuse = None
-        if refresh is not None and cfg:
-            kinds, mirror = refresh_plan(guided, refresh)
-            step, reuse, plain = begin_reuse(eng, x2, step, torch.empty_like(x2[:rows]))
-        else:
-            plain = begin_plain(eng, x2) if cfg and not all(guided) else None
-        stale = cfg
-        q = torch.empty_like(x2[:rows])
-        w = gv.to(eng.device) if cfg else None
-        coefs = None
-        if rescale is not None and cfg:
-            table = torch.zeros(len(schedule), B, 8, dtype=torch.float32)
-            for i, row in enumerate(schedule):
-                table[i, :, :5] = torch.tensor(row[1:6], dtype=torch.float32)
-                table[i, :, 5] = gv
-                table.view(torch.int32)[i, :, 6] = int(row[6])                      # use_prev
-            coefs, phi, rs = table.to(eng.device), rescale.to(eng.device), eng.rescale_scratch(B, N)
-        t_tensor = torch.empty(2 * B if cfg else B, device=eng.device, dtype=torch.long)
-        opts = None if batch_class is None else CallOpts(class_rows=(2 if cfg else 1) * int(batch_class) * N)
-        plain_opts = None if batch_class is None else CallOpts(class_rows=int(batch_class) * N)
-        for i, (t_val, a, kx, ke, b, g, use_prev) in enumerate(schedule):
-            t_tensor.fill_(t_val)
-            coef = MultistepCoef(a, kx, ke, b, g, 0.0, int(use_prev), 0)
-            if cfg and not guided[i]:  # the history q is the x0 of whichever step wrote it, conditional or guided: no special case
-                plain(t=t_tensor[:B], q=q, coef=coef, w=None, opts=plain_opts)
-                stale = True
-                continue
-            if kinds is not None and kinds[i] == "reuse":
-                reuse(t=t_tensor[:B], q=q, coef=coef, w=w, opts=plain_opts, mirror=mirror[i])
-                stale = not mirror[i]
-                continue
-            if stale:
-                x2[rows:].copy_(x2[:rows])
-                stale = False
-            if coefs is not None:
-                step(t=t_tensor, q=q, coef=None, coefs=coefs[i], phi=phi, rescale_scratch=rs, opts=opts)
-            else:
-                step(t=t_tensor, q=q, coef=coef, w=w, opts=opts)
-        return x2[:rows].clone() if cfg else x2
+        `prediction` "v": the rows of multistep_schedule_v, (kx, ke) = (alpha, -sigma), to the same launches."""
+        from .hip import MultistepCoef
+
+        def solver(eng, schedule, x, N, w, phi, seeds):
+            q = torch.empty_like(x)
+            coefs = rs = None
+            if phi is not None:
+                table = torch.zeros(len(schedule), B, 8, dtype=torch.float32)
+                for i, row in enumerate(schedule):
+                    table[i, :, :5] = torch.tensor(row[1:6], dtype=torch.float32)
+                    table[i, :, 5] = guidance_vector(guidance, B)
+                    table.view(torch.int32)[i, :, 6] = int(row[6])                      # use_prev
+                coefs, rs = table.to(eng.device), eng.rescale_scratch(B, N)
+
+            def kwargs(i, kind):
+                if kind == "step" and coefs is not None:
+                    return dict(q=q, coef=None, coefs=coefs[i], phi=phi, rescale_scratch=rs)
+                _, a, kx, ke, b, g, use_prev = schedule[i]
+                return dict(q=q, coef=MultistepCoef(a, kx, ke, b, g, 0.0, int(use_prev), 0), w=None if kind == "plain" else w)
+            return kwargs
+
+        return self._step_loop(B, guidance, null_text_emb, seeds, batch_class, begin, interval, begin_plain, rescale, refresh, begin_reuse,
+                               lambda: (multistep_schedule_v if prediction == "v" else multistep_schedule)(self.alphas_cumprod, n_steps),
+                               solver)
 
     @torch.no_grad()
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
