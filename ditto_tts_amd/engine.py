@@ -279,8 +279,8 @@ class DenoiseEngine:
         """The checks every packed guided step shares, after _guided_args' on x2.  `doubled`: x2 [2S, d] = [x; x], cond over
         [text; null], t [2B], offsets [2B + 1] (under guidance, or a refresh of the reuse steps); else x2 [S, d], cond over the text
         alone, t [B], offsets [B + 1].  `mirror` (None outside the reuse steps): x2 is a view of the first S rows of a [2S, d] state.
-        Returns (S, nb, max_N, head, tail): the first six and the last six arguments of the step's library call — handle, x2, cond,
-        t, speech offsets, text offsets; rope cos, rope sin, workspace, its bytes, stream, opts."""
+        Returns (S, nb, max_N, head, tail): the arguments every step entry starts and ends with, by the names include/ditto_hip.h
+        gives them (hip.call) — m, x2, cond, t, cu_speech, cu_text; rope_cos, rope_sin, workspace, workspace_bytes, stream, opts."""
         rows, d = int(x2.shape[0]), int(x2.shape[1])
         if doubled and rows % 2:
             raise ValueError("x2 must hold [x; x] " + ("under guidance" if mirror is None else "at a refresh step"))
@@ -301,8 +301,11 @@ class DenoiseEngine:
         self._step_keep = tt, cud   # until the next step: a t converted or offsets built here must outlive the caller's own allocations
         ws = self.workspace_packed(nb, rows, cond.T)
         c, s = self.rope_tables(max_N)
-        return S, nb, max_N, (self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), cud.data_ptr(), cond.cu_seqlens.data_ptr()), \
-            (c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), None if opts is None else C.byref(opts))
+        head = dict(m=self.handle, x2=x2.data_ptr(), cond=cond.buf.data_ptr(), t=tt.data_ptr(), cu_speech=cud.data_ptr(),
+                    cu_text=cond.cu_seqlens.data_ptr())
+        tail = dict(rope_cos=c.data_ptr(), rope_sin=s.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws.numel(), stream=_stream(),
+                    opts=None if opts is None else C.byref(opts))
+        return S, nb, max_N, head, tail
 
     @staticmethod
     def _rows_like(name, v, S, d):
@@ -332,23 +335,24 @@ class DenoiseEngine:
                                                          prompt_len, suffix_len, None, opts)
         if suffix_len is not None and phi is not None:
             raise NotImplementedError("guidance rescale has no windowed form (suffix_len with phi)")
-        step = int(step) & 0xFFFFFFFF
+        update = dict(noise=_ptr(noise), seeds=_ptr(sd), step=int(step) & 0xFFFFFFFF, w=_ptr(w), a=a.data_ptr(), ce=ce.data_ptr(),
+                      cz=cz.data_ptr())
+        shape = dict(B=B, S=S, max_N=max_N, S_T=cond.T, max_T=cond.max_len)
         if phi is not None:
             if not cfg:
                 raise ValueError("guidance rescale needs the guidance scales w")
             phi, rs = self._rescale_args(phi, rescale_scratch, B, max_N)
-            hip.check(self.lib.ditto_guided_step_packed_rescale_opts(
-                *head, None, _ptr(prompt_len), _ptr(noise), _ptr(sd), step, None, w.data_ptr(), phi.data_ptr(), a.data_ptr(),
-                ce.data_ptr(), cz.data_ptr(), B, 0, S, 0, max_N, cond.T, cond.max_len, *tail[:4], rs.data_ptr(), rs.numel(), *tail[4:]))
+            hip.check(hip.call("ditto_guided_step_packed_rescale_opts", **head, partner=None, prompt_len=_ptr(prompt_len), **update,
+                               tags=None, phi=phi.data_ptr(), **shape, G=0, S_G=0, **tail, scratch=rs.data_ptr(),
+                               scratch_bytes=rs.numel()))
             return x2
         if suffix_len is not None:
-            entry, spans = self.lib.ditto_guided_step_packed_window_opts, (_ptr(prompt_len), suffix_len.data_ptr())
+            entry, spans = "ditto_guided_step_packed_window_opts", dict(prompt_len=_ptr(prompt_len), suffix_len=suffix_len.data_ptr())
         elif prompt_len is not None:
-            entry, spans = self.lib.ditto_guided_step_packed_prompt_opts, (prompt_len.data_ptr(),)
+            entry, spans = "ditto_guided_step_packed_prompt_opts", dict(prompt_len=prompt_len.data_ptr())
         else:
-            entry, spans = self.lib.ditto_guided_step_packed_opts, ()
-        hip.check(entry(*head, *spans, _ptr(noise), _ptr(sd), step, _ptr(w), a.data_ptr(), ce.data_ptr(), cz.data_ptr(), B, S, max_N,
-                        cond.T, cond.max_len, int(cfg), *tail))
+            entry, spans = "ditto_guided_step_packed_opts", {}
+        hip.check(hip.call(entry, **head, **spans, **update, **shape, cfg=int(cfg), **tail))
         return x2
 
     def guided_step_packed_multistep_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
@@ -377,17 +381,19 @@ class DenoiseEngine:
         self._rows_like("q", q, S, x2.shape[1])
         if suffix_len is not None and phi is not None:
             raise NotImplementedError("guidance rescale has no windowed form (suffix_len with phi)")
+        shape = dict(B=B, S=S, max_N=max_N, S_T=cond.T, max_T=cond.max_len)
         if coefs is not None:
             phi, rs = self._rescale_args(phi, rescale_scratch, B, max_N)
-            hip.check(self.lib.ditto_guided_step_packed_multistep_rescale_opts(
-                *head, _ptr(prompt_len), q.data_ptr(), coefs.data_ptr(), phi.data_ptr(), B, S, max_N, cond.T, cond.max_len, *tail[:4],
-                rs.data_ptr(), rs.numel(), *tail[4:]))
+            hip.check(hip.call("ditto_guided_step_packed_multistep_rescale_opts", **head, prompt_len=_ptr(prompt_len), q=q.data_ptr(),
+                               coefs=coefs.data_ptr(), phi=phi.data_ptr(), **shape, **tail, scratch=rs.data_ptr(),
+                               scratch_bytes=rs.numel()))
             return x2
         if suffix_len is not None:
-            entry, spans = self.lib.ditto_guided_step_packed_multistep_window_opts, (_ptr(prompt_len), suffix_len.data_ptr())
+            entry, spans = "ditto_guided_step_packed_multistep_window_opts", dict(prompt_len=_ptr(prompt_len), suffix_len=suffix_len.data_ptr())
         else:
-            entry, spans = self.lib.ditto_guided_step_packed_multistep_opts, (_ptr(prompt_len),)
-        hip.check(entry(*head, *spans, q.data_ptr(), C.byref(coef), None, _ptr(w), B, S, max_N, cond.T, cond.max_len, int(cfg), *tail))
+            entry, spans = "ditto_guided_step_packed_multistep_opts", dict(prompt_len=_ptr(prompt_len))
+        hip.check(hip.call(entry, **head, **spans, q=q.data_ptr(), step=C.byref(coef), coefs=None, w=_ptr(w), **shape, cfg=int(cfg),
+                           **tail))
         return x2
 
     # ------------------------------------------------------------------ guidance reuse (csrc/guided_reuse.hip)
@@ -421,9 +427,10 @@ class DenoiseEngine:
         S, _, max_N, head, tail = self._packed_step_args(who, x2, cond, t, B, store, offsets, cu_seqlens, max_seqlen, prompt_len,
                                                          suffix_len, bool(mirror), opts)
         self._rows_like("delta", delta, S, x2.shape[1])
-        hip.check(self.lib.ditto_guided_step_packed_reuse_opts(
-            *head, _ptr(prompt_len), _ptr(suffix_len), delta.data_ptr(), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, w.data_ptr(),
-            a.data_ptr(), ce.data_ptr(), cz.data_ptr(), B, S, max_N, cond.T, cond.max_len, int(mode), int(bool(mirror)), *tail))
+        hip.check(hip.call("ditto_guided_step_packed_reuse_opts", **head, prompt_len=_ptr(prompt_len), suffix_len=_ptr(suffix_len),
+                           delta=delta.data_ptr(), noise=_ptr(noise), seeds=_ptr(sd), step=int(step) & 0xFFFFFFFF, w=w.data_ptr(),
+                           a=a.data_ptr(), ce=ce.data_ptr(), cz=cz.data_ptr(), B=B, S=S, max_N=max_N, S_T=cond.T, max_T=cond.max_len,
+                           mode=int(mode), mirror=int(bool(mirror)), **tail))
         return x2
 
     def guided_step_packed_multistep_reuse_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
@@ -441,9 +448,9 @@ class DenoiseEngine:
                                                          suffix_len, bool(mirror), opts)
         self._rows_like("delta", delta, S, x2.shape[1])
         self._rows_like("q", q, S, x2.shape[1])
-        hip.check(self.lib.ditto_guided_step_packed_multistep_reuse_opts(
-            *head, _ptr(prompt_len), _ptr(suffix_len), q.data_ptr(), delta.data_ptr(), C.byref(coef), w.data_ptr(), B, S, max_N, cond.T,
-            cond.max_len, int(mode), int(bool(mirror)), *tail))
+        hip.check(hip.call("ditto_guided_step_packed_multistep_reuse_opts", **head, prompt_len=_ptr(prompt_len),
+                           suffix_len=_ptr(suffix_len), q=q.data_ptr(), delta=delta.data_ptr(), step=C.byref(coef), w=w.data_ptr(), B=B, S=S,
+                           max_N=max_N, S_T=cond.T, max_T=cond.max_len, mode=int(mode), mirror=int(bool(mirror)), **tail))
         return x2
 
     # ------------------------------------------------------------------ guidance rescale (csrc/guided_rescale.hip)
@@ -727,11 +734,12 @@ class DenoiseEngine:
         lens = lengths if lengths is not None else self.guided_lengths(speech_lengths, cond, B, N, cfg)
         ws = self.workspace(nb, N, cond.T)
         c, s = self.rope_tables(N)
-        hip.check(self.lib.ditto_guided_step_opts(
-            self.handle, x2.data_ptr(), cond.buf.data_ptr(), tt.data_ptr(), None if lens is None else lens[0].data_ptr(),
-            None if lens is None else lens[1].data_ptr(), _ptr(noise), _ptr(sd), int(step) & 0xFFFFFFFF, _ptr(w), a.data_ptr(),
-            ce.data_ptr(), cz.data_ptr(), B, N, cond.T, int(cfg), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
-            None if opts is None else C.byref(opts)))
+        hip.check(hip.call("ditto_guided_step_opts", m=self.handle, x2=x2.data_ptr(), cond=cond.buf.data_ptr(), t=tt.data_ptr(),
+                           speech_len=None if lens is None else lens[0].data_ptr(), text_len=None if lens is None else lens[1].data_ptr(),
+                           noise=_ptr(noise), seeds=_ptr(sd), step=int(step) & 0xFFFFFFFF, w=_ptr(w), a=a.data_ptr(), ce=ce.data_ptr(),
+                           cz=cz.data_ptr(), B=B, N=N, T=cond.T, cfg=int(cfg), rope_cos=c.data_ptr(), rope_sin=s.data_ptr(),
+                           workspace=ws.data_ptr(), workspace_bytes=ws.numel(), stream=_stream(),
+                           opts=None if opts is None else C.byref(opts)))
         return x2
 
     def denoise_steps_(self, x: torch.Tensor, cond: TextCond, t_begin: int, t_end: int, noises: Optional[torch.Tensor],

@@ -7,6 +7,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+
+from .build import INCLUDE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DITTO_HIP_LIB") or os.path.join(HERE, "libditto_hip.so")   # override: diagnostic builds (tools/)
@@ -128,6 +131,7 @@ class MultistepCoef(C.Structure):
     """ditto_multistep_coef: one utterance's step of the second-order multistep solver (sampler.multistep_schedule), 32 bytes."""
     _fields_ = [("a", C.c_float), ("kx", C.c_float), ("ke", C.c_float), ("b", C.c_float), ("g", C.c_float), ("w", C.c_float),
                 ("use_prev", C.c_int32), ("reserved", C.c_int32)]
+    _as_parameter_ = property(C.byref)   # given bare as a host `step` (a c_void_p parameter), it goes by reference
 
 
 RESCALE_CHUNK_QUADS = 4096    # DITTO_RESCALE_CHUNK_QUADS: 16-byte quads per partial of the guidance-rescale statistics (part of its bits)
@@ -147,195 +151,69 @@ REGROUP_COPY, REGROUP_DRAW = 0, 1
 # ditto_layer_grads / ditto_grads have the layout of the weight structs (one pointer per state_dict key)
 LayerGrads, Grads = LayerWeights, Weights
 
-# every symbol include/ditto_hip.h declares: name -> (restype, argtypes)
-_vp, _i, _sz, _f, _u64 = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_uint64
-SYMBOLS = {
-    "ditto_abi_version": (_i, []),
-    "ditto_last_error": (C.c_char_p, []),
-    "ditto_arena_bytes": (_sz, [C.POINTER(Config)]),
-    "ditto_cond_bytes": (_sz, [C.POINTER(Config), _i, _i]),
-    "ditto_workspace_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
-    "ditto_model_create": (_i, [C.POINTER(Config), C.POINTER(Weights), _vp, _sz, _vp, C.POINTER(_vp)]),
-    "ditto_model_destroy": (_i, [_vp]),
-    "ditto_rope_tables": (_i, [_vp, _i, _vp, _vp, _vp]),
-    "ditto_text_precompute": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
-    "ditto_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_forward_opts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_call_opts_push": (_i, [C.POINTER(CallOpts)]),
-    "ditto_call_opts_pop": (_i, []),
-    "ditto_call_opts_current": (_i, [C.POINTER(CallOpts)]),
-    "ditto_block_forward": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_block_forward_taps": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_global_adaln_scratch_bytes": (_sz, [_i, _i, _i, _i]),
-    "ditto_global_adaln": (_i, [_vp] * 7 + [_i] * 6 + [_vp, _vp, _sz, _vp]),
-    "ditto_apply_rope_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ditto_p_sample_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
-    "ditto_p_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_p_sample_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_denoise_steps": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_denoise_steps_opts": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp,
-                                      C.POINTER(CallOpts)]),
-    "ditto_noise_normal": (_i, [_vp, _vp, C.c_uint32, _i, _sz, _vp]),
-    "ditto_p_sample_seeded": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_p_sample_seeded_opts": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp,
-                                        C.POINTER(CallOpts)]),
-    "ditto_q_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
-    "ditto_layernorm_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "ditto_gemm_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_gemm_epilogue_bf16": (_i, [C.POINTER(GemmEpilogueArgs), _i, C.POINTER(C.c_int), _vp]),
-    "ditto_gemm_ln_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ditto_gemm_tn_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "ditto_attention_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
-    "ditto_attention_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ditto_attention_resid_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
-    # variable-length batches (per-utterance q / kv lengths, device int32 [B]; q pre-scaled, head_dim 64)
-    "ditto_text_precompute_varlen": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _vp]),
-    "ditto_forward_varlen_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_p_sample_varlen_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp,
-                                        C.POINTER(CallOpts)]),
-    "ditto_p_sample_seeded_varlen_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _i, _i, _i, _vp, _vp,
-                                               _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_attention_varlen_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_attention_resid_varlen_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_vq_argmin": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ditto_embedding_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ditto_code_embed_mean": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "ditto_linear_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
-    "ditto_cfg_combine": (_i, [_vp, _vp, _f, _sz, _vp]),
-    # guided strided step (fused CFG + DDIM update over a variable-length batch)
-    "ditto_guided_update": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ditto_guided_step_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp,
-                                    _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    # packed batches (utterances concatenated along the rows, device int32 offsets [B + 1])
-    "ditto_packed_workspace_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
-    "ditto_packed_cond_bytes": (_sz, [C.POINTER(Config), _i, _i]),
-    "ditto_text_precompute_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _sz, _vp]),
-    "ditto_forward_packed_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp,
-                                       C.POINTER(CallOpts)]),
-    "ditto_attention_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "ditto_attention_resid_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "ditto_guided_update_packed": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_guided_step_packed_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
-                                           _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    # continuous batching: per-utterance Philox step tags (device uint32 [B]) and the device regroup of a packed batch
-    "ditto_guided_update_packed_tags": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_guided_step_packed_tags_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
-                                                _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    # speech prompts: the packed update / step that leave each utterance's first prompt_len[b] rows alone; span-masked training
-    "ditto_guided_update_packed_prompt": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_guided_update_packed_tags_prompt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_guided_step_packed_prompt_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _i, _i, _i,
-                                                  _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_guided_step_packed_tags_prompt_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
-                                                       _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    # the second-order multistep solver: a step shared by the batch (host struct) or one per utterance (device [B])
-    "ditto_multistep_update_packed": (_i, [_vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_guided_step_packed_multistep_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _i, _i,
-                                                     _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    # guidance in a limited interval: a step in which G of the B utterances are guided (partner device int32 [B])
-    "ditto_guided_update_packed_mixed": (_i, [_vp] * 12 + [_i] * 6 + [_vp]),
-    "ditto_guided_step_packed_mixed_opts": (_i, [_vp] * 15 + [_i] * 7 + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    # guidance rescale (Lin et al. 2024): per-utterance statistics of eps that patch ce / ke, and the steps that use them
-    "ditto_guidance_rescale_bytes": (_sz, [_i, _i, _i]),
-    "ditto_guidance_rescale_packed": (_i, [_vp] * 8 + [_i] * 6 + [_vp, _sz, _vp]),
-    "ditto_guided_step_packed_rescale_opts": (_i, [_vp] * 10 + [C.c_uint32] + [_vp] * 6 + [_i] * 7 + [_vp, _vp, _vp, _sz, _vp, _sz, _vp,
-                                                                                                  C.POINTER(CallOpts)]),
-    "ditto_guided_step_packed_multistep_rescale_opts": (_i, [_vp] * 10 + [_i] * 5 + [_vp, _vp, _vp, _sz, _vp, _sz, _vp,
-                                                                                    C.POINTER(CallOpts)]),
-    "ditto_span_noise_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ditto_span_mse_packed": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
-    # speech infilling: the prompt / multistep / span entries over a window, one more pointer (suffix_len int32 [B]) behind prompt_len
-    "ditto_guided_update_packed_window": (_i, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
-                                               _vp]),
-    "ditto_guided_update_packed_tags_window": (_i, [_vp] * 12 + [_i] * 5 + [_vp]),
-    "ditto_guided_step_packed_window_opts": (_i, [_vp] * 10 + [C.c_uint32] + [_vp] * 4 + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp,
-                                                                                                 C.POINTER(CallOpts)]),
-    "ditto_guided_step_packed_tags_window_opts": (_i, [_vp] * 15 + [_i] * 6 + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_multistep_update_window": (_i, [_vp, _vp, _vp, C.POINTER(MultistepCoef), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_guided_step_packed_multistep_window_opts": (_i, [_vp] * 9 + [C.POINTER(MultistepCoef), _vp, _vp] + [_i] * 6
-                                                       + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_span_noise_window": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ditto_span_mse_window": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
-    # the v objective's span loss: x0, (ca, cs) and per-utterance weights beside ditto_span_mse_window's arguments
-    "ditto_span_vloss_window": (_i, [_vp] * 4 + [C.c_uint32] + [_vp] * 6 + [_sz, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
-    # guidance reuse: delta fp32 [S, d] beside the state, mode 1 = STORE (refresh) / 2 = LOAD (reuse), mirror (LOAD only)
-    "ditto_guided_update_packed_reuse": (_i, [_vp] * 5 + [C.c_uint32] + [_vp] * 7 + [_i] * 6 + [_vp]),
-    "ditto_multistep_update_packed_reuse": (_i, [_vp] * 4 + [C.POINTER(MultistepCoef)] + [_vp] * 4 + [_i] * 6 + [_vp]),
-    "ditto_guided_step_packed_reuse_opts": (_i, [_vp] * 11 + [C.c_uint32] + [_vp] * 4 + [_i] * 7
-                                            + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_guided_step_packed_multistep_reuse_opts": (_i, [_vp] * 10 + [C.POINTER(MultistepCoef), _vp] + [_i] * 7
-                                                      + [_vp, _vp, _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_regroup_packed": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_sz), _i, _vp, _i, _sz, _vp]),
-    "ditto_regroup_cond_layout": (_i, [C.POINTER(Config), _i, C.POINTER(_sz), C.POINTER(_sz)]),
-    "ditto_train_arena_bytes": (_sz, [C.POINTER(Config)]),
-    "ditto_tape_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
-    "ditto_train_workspace_bytes": (_sz, [C.POINTER(Config), _i, _i, _i]),
-    "ditto_train_attach": (_i, [_vp, C.POINTER(Weights), _vp, _sz, _vp]),
-    "ditto_train_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _vp, _sz, _vp, _sz, _vp]),
-    "ditto_train_backward": (_i, [_vp, C.POINTER(Weights), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _sz,
-                                  C.POINTER(Grads), _vp, _sz, _vp]),
-    "ditto_train_forward_opts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _vp, _sz, _vp, _sz, _vp,
-                                      C.POINTER(CallOpts)]),
-    "ditto_train_backward_opts": (_i, [_vp, C.POINTER(Weights), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _sz,
-                                       C.POINTER(Grads), _vp, _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_train_backward_layers": (_i, [_vp, C.POINTER(Weights), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _sz,
-                                         C.POINTER(Grads), _vp, _sz, _vp, C.POINTER(CallOpts), _i, _i]),
-    # training on packed variable-length batches
-    "ditto_tape_bytes_packed": (_sz, [C.POINTER(Config), _i, _i, _i]),
-    "ditto_train_workspace_bytes_packed": (_sz, [C.POINTER(Config), _i, _i, _i, _i, _i]),
-    "ditto_train_forward_packed_opts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _u64, _vp, _vp, _sz, _vp,
-                                             _sz, _vp, C.POINTER(CallOpts)]),
-    "ditto_train_backward_packed_layers": (_i, [_vp, C.POINTER(Weights), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f,
-                                                _u64, _vp, _sz, C.POINTER(Grads), _vp, _sz, _vp, C.POINTER(CallOpts), _i, _i]),
-    "ditto_train_tape_forget": (_i, [_vp, _vp]),
-    "ditto_attention_bwd_packed_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ditto_attention_train_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f,
-                                               _u64, _i, _vp]),
-    "ditto_attention_bwd_packed_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp,
-                                             _i, _i, _i, _i, _i, _i, _i, _f, _f, _u64, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_layernorm_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
-    "ditto_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
-    "ditto_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ditto_attention_bwd_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i,
-                                      _i, _i, _i, _i, _i, _f, _f, _u64, _i, _vp, _sz, _vp]),
-    "ditto_attention_dropout_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _u64, _i,
-                                          _vp, _sz, _vp]),
-    "ditto_quantize_rows_fp8": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "ditto_layernorm_fp8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "ditto_gemm_fp8": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ditto_gemm_epilogue_fp8": (_i, [C.POINTER(GemmEpilogueArgs), _vp, _i, C.POINTER(C.c_int), _vp]),
-    "ditto_slp_arena_bytes": (_sz, [C.POINTER(SlpConfig)]),
-    "ditto_slp_workspace_bytes": (_sz, [C.POINTER(SlpConfig), _i, _i, _i]),
-    "ditto_slp_create": (_i, [C.POINTER(SlpConfig), C.POINTER(SlpWeights), _vp, _sz, _vp, C.POINTER(_vp)]),
-    "ditto_slp_destroy": (None, [_vp]),
-    "ditto_slp_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_slp_varlen_workspace_bytes": (_sz, [C.POINTER(SlpConfig), _i, _i, _i]),
-    "ditto_slp_forward_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ditto_attention_causal_varlen_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i,
-                                                _vp, _sz, _vp]),
-    "ditto_attention_last_row_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ditto_attention_last_row_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
-    "ditto_attention_causal_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ditto_attention_causal_bf16": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
-    "ditto_layernorm_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "ditto_gemm_lnq_bf16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    # the forward row kernels on their own (unit tests)
-    "ditto_adaln_rows": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ditto_adaln_rows_packed": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
-    "ditto_splitk_finish": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ditto_text_mod": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ditto_text_mod_packed": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ditto_time_table": (_i, [_vp] * 8 + [_i, _i, _i, _vp]),
-    "ditto_packed_row_map": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "ditto_set_option": (_i, [C.c_char_p, _i]),
-    "ditto_get_option": (_i, [C.c_char_p, C.POINTER(C.c_int)]),
-    "ditto_full_row_plan": (_i, [C.POINTER(Config), _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "ditto_full_row_plan_opts": (_i, [C.POINTER(Config), _i, _i, C.POINTER(CallOpts), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                      C.POINTER(C.c_int)]),
-    "ditto_profile_enable": (_i, [_vp, _i]),
-    "ditto_profile_read": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
-    "ditto_kernel_class_name": (C.c_char_p, [_i]),
-}
+# ---- the C ABI.  include/ditto_hip.h is its single description: csrc/ is compiled against it, and the prototypes below are parsed
+# from it once, here.  One type rule, no per-function exceptions: a scalar by its spelling (_SCALARS); `const char*` = c_char_p; a
+# pointer to a struct of _STRUCTS = POINTER(that class); every other pointer = c_void_p (it takes a device address as an int, None,
+# C.byref(...), a ctypes array or pointer); `void` returns None.  ditto_multistep_coef is deliberately not in _STRUCTS: the header
+# uses it both for a host struct (`step`) and for device arrays (`coefs`); a bare MultistepCoef goes by reference (_as_parameter_).
+_SCALARS = {"int": C.c_int, "size_t": C.c_size_t, "float": C.c_float, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "ditto_stream_t": C.c_void_p, "ditto_model_t": C.c_void_p, "ditto_slp_t": C.c_void_p}
+_STRUCTS = {"ditto_config": Config, "ditto_weights": Weights, "ditto_grads": Grads, "ditto_call_opts": CallOpts,
+            "ditto_gemm_epilogue_args": GemmEpilogueArgs, "ditto_slp_config": SlpConfig, "ditto_slp_weights": SlpWeights}
+_POINTEES = {"void", "char", "int", "float", "size_t", "int32_t", "int64_t", "uint32_t", "uint64_t"}   # beside the header's own types
+
+
+def _ctype(decl: str, known, what: str):
+    """the ctypes type of the type `decl` (`known`: the type names the header itself declares); TypeError naming `what`"""
+    words = decl.replace("*", " * ").split()
+    base, stars = [w for w in words if w not in ("const", "*")], words.count("*")
+    if len(base) == 1:
+        base = base[0]
+        if stars == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        if stars == 1 and base == "char":
+            return C.c_char_p
+        if stars == 1 and base in _STRUCTS:
+            return C.POINTER(_STRUCTS[base])
+        if stars >= 1 and base != "char" and (base in _POINTEES or base in _SCALARS or base in known):
+            return C.c_void_p
+    raise TypeError(f"include/ditto_hip.h: no ctypes type for `{decl.strip()}` in `{what}`")
+
+
+def parse_prototypes(text: str) -> dict:
+    """name -> (restype, [(parameter name, ctype), ...]) of every function the C header `text` declares.  Every statement beside
+    comments, preprocessor lines and `struct / enum {...}` bodies is a typedef or a prototype; one that is neither, or has a type the
+    rule above does not cover, raises TypeError naming it: nothing falls back to c_void_p."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    known = set(re.findall(r"typedef\s+(?:struct|enum)\s+\w*\s*\{[^{}]*\}\s*(\w+)\s*;", text))
+    text = re.sub(r"(?:typedef\s+)?(?:struct|enum)\s*\w*\s*\{[^{}]*\}\s*\w*\s*;", "", text)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    protos = {}
+    for stmt in (" ".join(s.split()) for s in text.split(";")):
+        if not stmt:
+            continue
+        td = re.fullmatch(r"typedef [\w\s*]+?(\w+)", stmt)
+        if td:
+            known.add(td.group(1))
+            continue
+        fn = re.fullmatch(r"([\w\s*]+?)(\w+) ?\(([^()]*)\)", stmt)
+        if not fn:
+            raise TypeError(f"include/ditto_hip.h: neither a typedef nor a prototype: `{stmt}`")
+        ret, name, params = fn.groups()
+        params = [] if params.strip() in ("", "void") else [re.fullmatch(r"(.*?)(\w+)", q.strip()) for q in params.split(",")]
+        if None in params or name in protos:
+            raise TypeError(f"include/ditto_hip.h: cannot read the parameters of `{stmt}`")
+        protos[name] = (None if ret.split() == ["void"] else _ctype(ret, known, stmt),
+                        [(q.group(2), _ctype(q.group(1), known, stmt)) for q in params])
+    return protos
+
+
+with open(os.path.join(INCLUDE, "ditto_hip.h")) as _f:
+    PROTOTYPES = parse_prototypes(_f.read())
+# name -> (restype, argtypes): what lib() binds and the tools and tests read
+SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in PROTOTYPES.items()}
+_ORDER = {name: tuple(p for p, _ in params) for name, (_, params) in PROTOTYPES.items()}
 
 _lib = None
 
@@ -371,6 +249,20 @@ def lib() -> C.CDLL:
 def check(rc: int):
     if rc != OK:
         raise DittoHipError(rc, lib().ditto_last_error().decode(errors="replace"))
+
+
+def call(name: str, **kw) -> int:
+    """The entry `name` with its arguments BY THE HEADER'S PARAMETER NAMES, in any order; returns its status.  No defaults: every
+    parameter of the prototype is given (None = NULL).  A missing or an unknown name is a TypeError naming the entry and the
+    parameter, raised before the library is entered."""
+    order = _ORDER.get(name)
+    if order is None:
+        raise TypeError(f"{name}: include/ditto_hip.h declares no such entry")
+    if len(kw) != len(order) or not all(p in kw for p in order):
+        missing, unknown = [p for p in order if p not in kw], [p for p in kw if p not in order]
+        raise TypeError(f"{name}: " + "; ".join(f"{what} {', '.join(ps)}" for what, ps in
+                                                 (("missing", missing), ("no parameter named", unknown)) if ps))
+    return getattr(lib(), name)(*[kw[p] for p in order])
 
 
 def set_option(name: str, value: int):

@@ -683,47 +683,45 @@ class DeviceBatch:
         eng, at = self.eng, self._block_ptr
         cfg = self.guided and a.G > 0
         ws = eng.workspace_packed(a.B + a.G, a.S + a.S_G, a.S_T)         # the forward: the B utterances and the G copies
-        # the arguments every entry shares: in front (model, state, conditioning, t, speech and text offsets) and behind
-        head = (eng.handle, self.x[self.cur].data_ptr(), self.cond[self.cur].data_ptr(), at(self.o_t), self.offsets.data_ptr(),
-                self.offsets.data_ptr() + 4 * self.cu_pad)
-        tail = (self.rope[0].data_ptr(), self.rope[1].data_ptr(), ws.data_ptr(), ws.numel(), _stream(),
-                None if self.opts is None else C.byref(self.opts))
+        # by the names include/ditto_hip.h gives them (hip.call).  What every entry shares: the model, the state, the conditioning, t,
+        # the speech and text offsets, the rope tables, the workspace, the stream and the options
+        args = dict(m=eng.handle, x2=self.x[self.cur].data_ptr(), cond=self.cond[self.cur].data_ptr(), t=at(self.o_t),
+                    cu_speech=self.offsets.data_ptr(), cu_text=self.offsets.data_ptr() + 4 * self.cu_pad, max_N=a.max_N, S_T=a.S_T,
+                    max_T=a.max_T, rope_cos=self.rope[0].data_ptr(), rope_sin=self.rope[1].data_ptr(), workspace=ws.data_ptr(),
+                    workspace_bytes=ws.numel(), stream=_stream(), opts=None if self.opts is None else C.byref(self.opts))
         prompt = at(self.o_prompt) if any(a.prompt) else None
-        noise = (None, at(self.o_seeds), at(self.o_tags))                 # no buffer: Philox of the seeds at each utterance's tag
-        coef = (at(self.o_a), at(self.o_ce), at(self.o_cz))
+        noise = dict(noise=None, seeds=at(self.o_seeds), tags=at(self.o_tags))   # no buffer: Philox of the seeds at each utterance's tag
+        coef = dict(a=at(self.o_a), ce=at(self.o_ce), cz=at(self.o_cz))
+        history = dict(q=self.q[self.cur].data_ptr(), coefs=at(self.o_coef)) if self.multistep else None
         if self.infill and any(a.suffix):
             if self.multistep:
-                hip.check(self.lib.ditto_guided_step_packed_multistep_window_opts(
-                    *head, prompt, at(self.o_suffix), self.q[self.cur].data_ptr(), None, at(self.o_coef), None, a.B, a.S, a.max_N, a.S_T,
-                    a.max_T, int(self.guided), *tail))
+                hip.check(hip.call("ditto_guided_step_packed_multistep_window_opts", **args, prompt_len=prompt, suffix_len=at(self.o_suffix),
+                                   **history, step=None, w=None, B=a.B, S=a.S, cfg=int(self.guided)))
             else:
-                hip.check(self.lib.ditto_guided_step_packed_tags_window_opts(
-                    *head, prompt, at(self.o_suffix), *noise, at(self.o_w) if cfg else None, *coef, a.B, a.S, a.max_N, a.S_T, a.max_T,
-                    int(cfg), *tail))
+                hip.check(hip.call("ditto_guided_step_packed_tags_window_opts", **args, prompt_len=prompt, suffix_len=at(self.o_suffix),
+                                   **noise, w=at(self.o_w) if cfg else None, **coef, B=a.B, S=a.S, cfg=int(cfg)))
             return
         if cfg and any(p > 0 and g for p, g in zip(a.phi, a.in_g)):
-            tail_rs = tail[:4] + (self.rescale.data_ptr(), self.rescale.numel()) + tail[4:]
+            rescale = dict(phi=at(self.o_phi), scratch=self.rescale.data_ptr(), scratch_bytes=self.rescale.numel())
             if self.multistep:
-                hip.check(self.lib.ditto_guided_step_packed_multistep_rescale_opts(
-                    *head, prompt, self.q[self.cur].data_ptr(), at(self.o_coef), at(self.o_phi), a.B, a.S, a.max_N, a.S_T, a.max_T,
-                    *tail_rs))
+                hip.check(hip.call("ditto_guided_step_packed_multistep_rescale_opts", **args, prompt_len=prompt, **history, **rescale,
+                                   B=a.B, S=a.S))
             else:
                 mixed = a.G < a.B
-                hip.check(self.lib.ditto_guided_step_packed_rescale_opts(
-                    *head, at(self.o_partner) if mixed else None, prompt, *noise[:2], 0, noise[2], at(self.o_w), at(self.o_phi), *coef,
-                    a.B, a.G if mixed else 0, a.S, a.S_G if mixed else 0, a.max_N, a.S_T, a.max_T, *tail_rs))
+                hip.check(hip.call("ditto_guided_step_packed_rescale_opts", **args, partner=at(self.o_partner) if mixed else None,
+                                   prompt_len=prompt, **noise, step=0, w=at(self.o_w), **coef, **rescale, B=a.B, G=a.G if mixed else 0,
+                                   S=a.S, S_G=a.S_G if mixed else 0))
             return
         if self.multistep:
-            hip.check(self.lib.ditto_guided_step_packed_multistep_opts(
-                *head, prompt, self.q[self.cur].data_ptr(), None, at(self.o_coef), None, a.B, a.S, a.max_N, a.S_T, a.max_T,
-                int(self.guided), *tail))
+            hip.check(hip.call("ditto_guided_step_packed_multistep_opts", **args, prompt_len=prompt, **history, step=None, w=None, B=a.B,
+                               S=a.S, cfg=int(self.guided)))
         elif 0 < a.G < a.B:
-            hip.check(self.lib.ditto_guided_step_packed_mixed_opts(
-                *head, at(self.o_partner), prompt, *noise, at(self.o_w), *coef, a.B, a.G, a.S, a.S_G, a.max_N, a.S_T, a.max_T, *tail))
+            hip.check(hip.call("ditto_guided_step_packed_mixed_opts", **args, partner=at(self.o_partner), prompt_len=prompt, **noise,
+                               w=at(self.o_w), **coef, B=a.B, G=a.G, S=a.S, S_G=a.S_G))
         else:
-            entry = self.lib.ditto_guided_step_packed_tags_opts if prompt is None else self.lib.ditto_guided_step_packed_tags_prompt_opts
-            hip.check(entry(*head, *(() if prompt is None else (prompt,)), *noise, at(self.o_w) if cfg else None, *coef, a.B, a.S,
-                            a.max_N, a.S_T, a.max_T, int(cfg), *tail))
+            entry, spans = ("ditto_guided_step_packed_tags_opts", {}) if prompt is None else \
+                ("ditto_guided_step_packed_tags_prompt_opts", dict(prompt_len=prompt))
+            hip.check(hip.call(entry, **args, **spans, **noise, w=at(self.o_w) if cfg else None, **coef, B=a.B, S=a.S, cfg=int(cfg)))
 
     def retire(self, done: List[Request]) -> List[torch.Tensor]:
         """the generated rows of the utterances that leave, copied out of the state in one launch; the batch keeps its layout (with

@@ -28,6 +28,94 @@ def test_header_symbols_exported_and_bound():
     assert lib.ditto_abi_version() == 10
 
 
+def test_prototypes_are_parsed_from_the_header():
+    """hip.PROTOTYPES (and SYMBOLS, its view) come from include/ditto_hip.h by one type rule: the same functions as the name
+    scan above, distinct parameter names, and the declarations that are awkward to parse."""
+    P, vp, i, sz = hip.PROTOTYPES, C.c_void_p, C.c_int, C.c_size_t
+    assert sorted(P) == declared_functions() and len(P) == 142
+    for name, (res, params) in P.items():
+        names = [n for n, _ in params]
+        assert len(set(names)) == len(names) and all(n.isidentifier() for n in names), name
+        assert hip.SYMBOLS[name] == (res, [t for _, t in params])
+    assert P["ditto_last_error"] == (C.c_char_p, [])                                  # returns const char*, (void)
+    assert P["ditto_abi_version"] == (i, [])
+    assert P["ditto_slp_destroy"] == (None, [("m", vp)])                              # returns void
+    assert P["ditto_set_option"][1] == [("name", C.c_char_p), ("value", i)]
+    assert P["ditto_regroup_packed"][1] == [("table", vp), ("n_seg", i), ("src", vp), ("src_bytes", vp), ("dst", vp),   # const void* const*,
+                                            ("dst_bytes", vp), ("n_bufs", i), ("seeds", vp), ("n_seeds", i),            # const size_t*
+                                            ("max_bytes", sz), ("stream", vp)]
+    assert P["ditto_noise_normal"][1][2] == ("step", C.c_uint32)                      # uint32_t step
+    assert P["ditto_guided_step_packed_multistep_opts"][1][8:10] == [("step", vp), ("coefs", vp)]   # host struct and device array
+    co = hip.MultistepCoef(0.5, 1.0, 0.0, 0.0, 0.0, 0.0, 0, 0)                         # ... so a bare host struct goes by reference
+    same = C.CFUNCTYPE(vp, vp)(lambda p: p)
+    assert same(co) == same(C.byref(co)) == C.addressof(co)
+    assert P["ditto_train_forward"][1][9:11] == [("dropout_p", C.c_float), ("seed", C.c_uint64)]
+    res, params = P["ditto_model_create"]                                             # spans two lines; struct pointers, a handle out
+    assert res is i and [n for n, _ in params] == ["cfg", "w", "arena", "arena_bytes", "stream", "out"]
+    assert [t for _, t in params] == [C.POINTER(hip.Config), C.POINTER(hip.Weights), vp, sz, vp, vp]
+    assert P["ditto_train_backward"][1][14] == ("grads", C.POINTER(hip.Grads))
+    assert P["ditto_slp_create"][1][:2] == [("cfg", C.POINTER(hip.SlpConfig)), ("w", C.POINTER(hip.SlpWeights))]
+    assert P["ditto_gemm_epilogue_bf16"][1][0] == ("args", C.POINTER(hip.GemmEpilogueArgs))
+    res, params = P["ditto_guided_step_packed_rescale_opts"]                          # the longest: seven lines
+    assert len(params) == 32 and params[-2:] == [("stream", vp), ("opts", C.POINTER(hip.CallOpts))]
+    assert [n for n, _ in params[:6]] == "m x2 cond t cu_speech cu_text".split()
+    assert [n for n, _ in params[-8:-2]] == "rope_cos rope_sin workspace workspace_bytes scratch scratch_bytes".split()
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int ditto_x(ditto_new_t a);", ("ditto_x", "ditto_new_t")),                      # a scalar type the rule does not know
+    ("typedef void* ditto_stream_t;\nint ditto_y(ditto_stream_t s, const ditto_thing* p);", ("ditto_y", "ditto_thing")),
+    ("int ditto_z(int (*cb)(int), void* p);", ("ditto_z",)),                          # a function pointer
+    ("int ditto_u(int);", ("ditto_u",)),                                              # a parameter without a name
+    ("long ditto_v(void);", ("ditto_v", "long"))])
+def test_a_prototype_the_rule_cannot_type_raises_and_is_named(text, names):
+    with pytest.raises(TypeError) as e:
+        hip.parse_prototypes(text)
+    assert all(n in str(e.value) for n in names), str(e.value)
+
+
+def test_parser_reads_declaration_forms():
+    got = hip.parse_prototypes("""
+        #define X 1
+        typedef struct ditto_s { int a; /* x; */ float b; } ditto_s;
+        enum { A = 0, B };
+        /* int ditto_not_this(int a); */
+        size_t ditto_f(const ditto_s* s,   // trailing
+                       const void* const* pp, float f);
+        void ditto_g(void);""")
+    assert got == {"ditto_f": (C.c_size_t, [("s", C.c_void_p), ("pp", C.c_void_p), ("f", C.c_float)]), "ditto_g": (None, [])}
+
+
+def test_call_by_name_orders_by_the_header_and_takes_no_defaults(monkeypatch):
+    lib = hip.lib()
+    c = hip.make_config(PRESETS["C2"]["cfg"])
+    got = {}
+    for how in ("positional", "by_name"):
+        a, b, h = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        if how == "positional":
+            rc = lib.ditto_full_row_plan_opts(C.byref(c), 32, 1024, None, C.byref(a), C.byref(b), C.byref(h))
+        else:                                                                         # in another order than the header's
+            rc = hip.call("ditto_full_row_plan_opts", stream_bf16=C.byref(h), fc2=C.byref(b), N=1024, outproj=C.byref(a), opts=None,
+                          B=32, cfg=C.byref(c))
+        got[how] = (rc, a.value, b.value, h.value)
+    assert got["by_name"] == got["positional"] == (hip.OK, 1, 1, 1)
+    refused = dict(x=None, eps=None, noise=None, t=None, betas=None, alphas=None, alphas_cumprod=None, B=1, elems_per_utt=4, stream=None)
+    assert hip.call("ditto_p_sample_update", **refused) == lib.ditto_p_sample_update(*refused.values()) == hip.ERR_ARG
+    assert b"ditto_p_sample_update" in lib.ditto_last_error()
+    # a wrong set of names never reaches the library: the bound function is replaced by a counter
+    calls = []
+    monkeypatch.setattr(lib, "ditto_p_sample_update", lambda *a: calls.append(a) or hip.OK)
+    assert hip.call("ditto_p_sample_update", **refused) == hip.OK and len(calls) == 1 and calls[0] == tuple(refused.values())
+    missing = {k: v for k, v in refused.items() if k != "betas"}
+    for kw, said in ((missing, "missing betas"), (dict(refused, gamma=None), "no parameter named gamma"),
+                     (dict(missing, beta=None), "missing betas; no parameter named beta")):
+        with pytest.raises(TypeError, match="ditto_p_sample_update: " + said):
+            hip.call("ditto_p_sample_update", **kw)
+    with pytest.raises(TypeError, match="ditto_p_sample_updat: include/ditto_hip.h declares no such entry"):
+        hip.call("ditto_p_sample_updat", **refused)
+    assert len(calls) == 1
+
+
 def test_struct_layout_matches_header():
     # 14 model-level pointers + layers pointer; 18 per-layer pointers; 7 int32 config fields
     assert C.sizeof(hip.Config) == 28

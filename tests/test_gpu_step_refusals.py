@@ -5,6 +5,8 @@ Every call here passes workspace_bytes = 0.  The step's forward refuses that las
 refusal is the one reported (the always-on rows: the arguments reach the forward), and with one defect the defect's own refusal has
 to come first — its return code, a distinctive part of ditto_last_error and the entry's name in it.  The expected codes and texts are
 written by hand from the entries' argument checks.  Launches: creating the model and preparing the text conditioning, nothing else."""
+import ctypes as C
+
 import pytest
 import torch
 
@@ -22,31 +24,24 @@ G, S_G = 1, LENS[0]                                   # the mixed step: utteranc
 ARG, SHAPE, SIZE = hip.ERR_ARG, hip.ERR_SHAPE, hip.ERR_SIZE
 GUARD = (SIZE, "workspace too small")
 
-HEAD = "m x cond t cu cut"
-SHAPES = "B S max_N S_T max_T"
-TAIL = "rc rs ws wsb stream opts"
-RTAIL = "rc rs ws wsb scratch scratch_bytes stream opts"
-COEF = "w a ce cz"
-# the parameters of every entry, in the order of include/ditto_hip.h
-ENTRIES = {
-    "ditto_guided_step_packed_opts": f"{HEAD} noise seeds step {COEF} {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_tags_opts": f"{HEAD} noise seeds tags {COEF} {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_prompt_opts": f"{HEAD} pl noise seeds step {COEF} {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_tags_prompt_opts": f"{HEAD} pl noise seeds tags {COEF} {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_window_opts": f"{HEAD} pl ql noise seeds step {COEF} {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_tags_window_opts": f"{HEAD} pl ql noise seeds tags {COEF} {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_multistep_opts": f"{HEAD} pl q mstep coefs w {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_multistep_window_opts": f"{HEAD} pl ql q mstep coefs w {SHAPES} cfg {TAIL}",
-    "ditto_guided_step_packed_mixed_opts": f"{HEAD} partner pl noise seeds tags {COEF} B G S S_G max_N S_T max_T {TAIL}",
-    "ditto_guided_step_packed_rescale_opts": f"{HEAD} partner pl noise seeds step tags w phi a ce cz B G S S_G max_N S_T max_T {RTAIL}",
-    "ditto_guided_step_packed_multistep_rescale_opts": f"{HEAD} pl q coefs phi {SHAPES} {RTAIL}",
-    "ditto_guided_step_packed_reuse_opts": f"{HEAD} pl ql delta noise seeds step {COEF} {SHAPES} mode mirror {TAIL}",
-    "ditto_guided_step_packed_multistep_reuse_opts": f"{HEAD} pl ql q delta mstep w {SHAPES} mode mirror {TAIL}",
-}
+# the names this file gives to parameters the header spells out; the host struct `step` of the multistep entries is "mstep" here,
+# beside the strided entries' Philox tag `step`
+ALIAS = {"x2": "x", "cu_speech": "cu", "cu_text": "cut", "prompt_len": "pl", "suffix_len": "ql", "rope_cos": "rc", "rope_sin": "rs",
+         "workspace": "ws", "workspace_bytes": "wsb"}
+
+
+def _by_name(entry, args):
+    """`args` (this file's names) as the keyword arguments of hip.call: the parameter names of include/ditto_hip.h"""
+    return {name: args["mstep" if name == "step" and ctype is C.c_void_p else ALIAS.get(name, name)]
+            for name, ctype in hip.PROTOTYPES[entry][1]}
+
+
 STRIDED = [f"ditto_guided_step_packed_{k}opts" for k in ("", "tags_", "prompt_", "tags_prompt_", "window_", "tags_window_")]
 MIXED, RESCALE, MS_RESCALE = (f"ditto_guided_step_packed_{k}_opts" for k in ("mixed", "rescale", "multistep_rescale"))
 REUSE, MS_REUSE = "ditto_guided_step_packed_reuse_opts", "ditto_guided_step_packed_multistep_reuse_opts"
 MULTISTEP = ["ditto_guided_step_packed_multistep_opts", "ditto_guided_step_packed_multistep_window_opts"]
+assert sorted(STRIDED + MULTISTEP + [MIXED, RESCALE, MS_RESCALE, REUSE, MS_REUSE]) == \
+    sorted(n for n in hip.PROTOTYPES if n.startswith("ditto_guided_step_packed"))                 # the 13 entries of the header
 
 BIG = dict(B=32768, S=40000)                          # past the step kernels' 32767 utterances, within every other limit
 POSITIVE = "S_T and max_T must be positive"           # check_packed
@@ -203,7 +198,7 @@ def test_first_refusal(valid, entry, variant, over, code, text):
         args[k] = val
     if args["B"] != B:                                                               # the scratch a batch of that size would need
         args["scratch_bytes"] = int(lib.ditto_guidance_rescale_bytes(max(args["B"], 1), MAX_N, D))
-    rc = getattr(lib, entry)(*(args[k] for k in ENTRIES[entry].split()))
+    rc = hip.call(entry, **_by_name(entry, args))
     msg = lib.ditto_last_error().decode()
     print(f"{entry} {over}: rc {rc}, {msg!r}")
     assert rc == code and text in msg, (rc, msg)
