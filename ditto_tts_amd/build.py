@@ -37,7 +37,7 @@ def _sources():
 
 def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(INCLUDE, "ditto_hip.h"))
+    hdrs += [os.path.join(INCLUDE, "ditto_hip.h"), os.path.join(INCLUDE, "ditto_optim.h")]
     return hdrs
 
 

@@ -339,6 +339,11 @@ struct RescaleArgs {
 };
 size_t guidance_rescale_chunks(int max_N, int d);   // chunks of the longest generated region: the scratch's slots and the grid's columns
 hipError_t launch_guidance_rescale(const RescaleArgs& a, int max_N, hipStream_t s);
+// ---------------- optim.hip ----------------
+// the fused training optimizer (include/ditto_optim.h): a segment's gradients are cut into partials of DITTO_OPTIM_CHUNK_QUADS
+// 16-byte quads of the segment itself, so that the global norm depends on the table and the gradients only, never on the grid: the
+// constant is part of the bits (and of ditto_optim_seg.slot0, which the host fills in).
+#define DITTO_OPTIM_CHUNK_QUADS 4096
 // ---------------- regroup_packed.hip ----------------
 // the buffers a regroup's segments name by index, sizes in 16-byte units (a null pointer: no such buffer)
 #define DITTO_REGROUP_BUFS 6

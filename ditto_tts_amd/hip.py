@@ -215,6 +215,38 @@ with open(os.path.join(INCLUDE, "ditto_hip.h")) as _f:
 SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in PROTOTYPES.items()}
 _ORDER = {name: tuple(p for p, _ in params) for name, (_, params) in PROTOTYPES.items()}
 
+
+# The fused optimizer's entries (include/ditto_optim.h, csrc/optim.hip) are exported by the same library but are a table of their
+# own: PROTOTYPES / SYMBOLS stay exactly the functions of ditto_hip.h.  lib() binds them and call() reaches them by parameter name.
+with open(os.path.join(INCLUDE, "ditto_optim.h")) as _f:
+    OPTIM_PROTOTYPES = parse_prototypes(_f.read())
+OPTIM_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in OPTIM_PROTOTYPES.items()}
+_ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in OPTIM_PROTOTYPES.items()})
+OPTIM_CHUNK_QUADS = 4096      # DITTO_OPTIM_CHUNK_QUADS: 16-byte quads per chunk of a segment (part of the norm's bits)
+
+
+class OptimSeg(C.Structure):
+    """ditto_optim_seg: one parameter tensor of the optimizer's device table, 72 bytes."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p),
+                ("n", C.c_uint64), ("slot0", C.c_uint32), ("reserved", C.c_uint32), ("lr", C.c_double), ("weight_decay", C.c_double)]
+
+
+class OptimHyper(C.Structure):
+    """ditto_optim_hyper: the hyper-parameters all segments share (a host struct)."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_norm", C.c_double),
+                ("ema_decay", C.c_double), ("skip_nonfinite", C.c_int32), ("reserved", C.c_int32)]
+    _as_parameter_ = property(C.byref)
+
+
+OPTIM_STATE_BYTES = 128       # ditto_optim_state: two 32-byte slots (beta1^t, beta2^t fp64; step, skipped int64), then the report:
+OPTIM_STATE_NORM64, OPTIM_STATE_NORM32, OPTIM_STATE_CLIP, OPTIM_STATE_SKIP = 64, 72, 76, 80   # byte offsets of norm, norm32, clip, skip
+
+
+def optim_chunks(n: int) -> int:
+    """chunks of a segment of n elements"""
+    return (((int(n) + 3) // 4) + OPTIM_CHUNK_QUADS - 1) // OPTIM_CHUNK_QUADS
+
+
 _lib = None
 
 
@@ -232,7 +264,7 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
         frozen = bool(os.environ.get("DITTO_HIP_LIB"))   # a diagnostic or FROZEN earlier build for same-box A/Bs (tools/):
-        for name, (res, args) in SYMBOLS.items():        # it may predate entry points added since (they are then absent)
+        for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items()):   # it may predate entries added since (then absent)
             try:
                 fn = getattr(l, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:
@@ -257,7 +289,7 @@ def call(name: str, **kw) -> int:
     parameter, raised before the library is entered."""
     order = _ORDER.get(name)
     if order is None:
-        raise TypeError(f"{name}: include/ditto_hip.h declares no such entry")
+        raise TypeError(f"{name}: include/{'ditto_optim.h' if name.startswith('ditto_optim_') else 'ditto_hip.h'} declares no such entry")
     if len(kw) != len(order) or not all(p in kw for p in order):
         missing, unknown = [p for p in order if p not in kw], [p for p in kw if p not in order]
         raise TypeError(f"{name}: " + "; ".join(f"{what} {', '.join(ps)}" for what, ps in
