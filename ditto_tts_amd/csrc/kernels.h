@@ -463,6 +463,7 @@ hipError_t launch_gemm_tn(const void* X, int ldx, const void* Y, int ldy, const 
 hipError_t launch_transpose_bf16(const void* src, int ld, int rows, int cols, void* dst, int ldT, hipStream_t s,
                                  int nz_o = 1, int nz_i = 1, long long s_o = 0, long long s_i = 0, long long d_z = 0);
 hipError_t launch_reduce_partials(const float* partial, int chunks, size_t n, float* out, hipStream_t s);
+size_t colsum_scratch_bytes(int M, int n);
 hipError_t launch_colsum_f32(const float* x, int ld, int M, int n, float* out, float* scratch, hipStream_t s);
 hipError_t launch_colsum_bf16(const void* x, int ld, int M, int n, float* out, float* scratch, hipStream_t s);
 size_t ln_bwd_scratch_bytes(int rows_per_group, int groups, int d);

@@ -193,9 +193,11 @@ static int colsum_chunks(int M, int n) {
     if (chunks > maxc) chunks = maxc;
     return chunks < 1 ? 1 : chunks;
 }
+// the scratch of launch_colsum_*: one partial row of n floats per row chunk (at most 256 of them)
+size_t colsum_scratch_bytes(int M, int n) { return (size_t)colsum_chunks(M, n) * n * 4; }
 template <typename T>
 static hipError_t colsum_launch(const T* x, int ld, int M, int n, float* out, float* scratch, hipStream_t s) {
-    if (n % 4 || ld % 4) return hipErrorInvalidValue;
+    if (M < 1 || n < 4 || n % 4 || ld % 4 || ld < n) return hipErrorInvalidValue;
     const int chunks = colsum_chunks(M, n);
     const int rpc = (M + chunks - 1) / chunks;
     if constexpr (sizeof(T) == 2) {
@@ -394,7 +396,8 @@ size_t ln_bwd_scratch_bytes(int rows_per_group, int groups, int d) {
     return (size_t)groups * ln_bwd_chunks(rows_per_group, groups) * 3 * d * 4;   // 3: the stream form's extra column sum
 }
 // The residual-stream form (one group): dx_accum += dx; dx_bf16 = bf16(dx_accum); dgamma / dbeta / colsum(dx_accum)
-// (the last may be null) written to their own destinations.  scratch: ln_bwd_scratch_bytes(rows, 1, d) * 3 / 2.
+// (each may be null: not written) written to their own destinations.  scratch: ln_bwd_scratch_bytes(rows, 1, d), which counts the
+// three partial rows [dgamma | dbeta | colsum] of d floats per chunk that the kernel writes.
 hipError_t launch_ln_bwd_stream(const void* dy, bool dy_bf16, const void* x, bool x_bf16, const float* gamma, float* dx_accum,
                                 void* dx_bf16, float* dgamma, float* dbeta, float* colsum_or_null, float* scratch, int rows,
                                 int d, hipStream_t s) {
@@ -591,7 +594,7 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const float* __restric
 }
 hipError_t launch_unpack_rows(const float* src, float* dst, int rows, int cols, int blk, int mult, int row_off,
                               hipStream_t s) {
-    if (cols % 4) return hipErrorInvalidValue;
+    if (cols % 4 || rows < 1 || blk < 1 || mult < 1 || row_off < 0) return hipErrorInvalidValue;   // blk 0 divides by zero on the device
     hipLaunchKernelGGL(unpack_rows_kernel, dim3(ew_grid((size_t)rows * cols / 4)), dim3(256), 0, s, src, dst, rows,
                        cols / 4, blk, mult, row_off);
     return hipGetLastError();
@@ -602,6 +605,7 @@ __global__ __launch_bounds__(256) void unpack_vec_kernel(const float* __restrict
     if (r < rows) dst[r] = src[(r / blk) * (blk * mult) + r % blk + row_off];
 }
 hipError_t launch_unpack_vec(const float* src, float* dst, int rows, int blk, int mult, int row_off, hipStream_t s) {
+    if (rows < 1 || blk < 1 || mult < 1 || row_off < 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(unpack_vec_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, src, dst, rows, blk, mult, row_off);
     return hipGetLastError();
 }
@@ -628,6 +632,9 @@ __global__ __launch_bounds__(256) void pack_bf16_t_kernel(const float* __restric
 }
 hipError_t launch_pack_bf16_t(const float* src, void* dst, int rows, int cols, int ldT, int blk, int mult, int row_off,
                               hipStream_t s) {
+    if (rows < 1 || cols < 1 || blk < 1 || mult < 1 || row_off < 0) return hipErrorInvalidValue;
+    // the largest mapped row must be a column of dst: a narrower ldT wrote into the next row, and past the last one
+    if ((long long)((rows - 1) / blk) * ((long long)blk * mult) + (rows - 1) % blk + row_off >= ldT) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pack_bf16_t_kernel, dim3((rows + 31) / 32, (cols + 31) / 32), dim3(256), 0, s, src, (bf16*)dst,
                        rows, cols, ldT, blk, mult, row_off);
     return hipGetLastError();
@@ -713,6 +720,7 @@ unsigned dropout_threshold(float p) {
 // nrows = rows_per_bh * (number of stacked (batch, head) pairs starting at pair bh0)
 hipError_t launch_softmax_drop_rows(const float* S, void* P, int nrows, int rows_per_bh, int Skv, int ld, float scale,
                                     uint64_t seed, int layer, int bh0, float p_drop, hipStream_t s) {
+    if (nrows < 1 || rows_per_bh < 1 || Skv < 1 || Skv > ld) return hipErrorInvalidValue;   // Skv > ld read into the next row
     const unsigned thr = dropout_threshold(p_drop);
     hipLaunchKernelGGL(softmax_drop_rows_kernel, dim3((nrows + 3) / 4), dim3(256), 0, s, S, (bf16*)P, nrows, Skv, ld,
                        scale * 1.4426950408889634f, (unsigned)(seed & 0xFFFFFFFFu), (unsigned)(seed >> 32), layer, bh0,
@@ -721,6 +729,7 @@ hipError_t launch_softmax_drop_rows(const float* S, void* P, int nrows, int rows
 }
 hipError_t launch_softmax_bwd_rows(const float* S, const float* dPd, void* dS, int nrows, int rows_per_bh, int Skv, int ld,
                                    float scale, uint64_t seed, int layer, int bh0, float p_drop, hipStream_t s) {
+    if (nrows < 1 || rows_per_bh < 1 || Skv < 1 || Skv > ld) return hipErrorInvalidValue;
     const unsigned thr = dropout_threshold(p_drop);
     hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((nrows + 3) / 4), dim3(256), 0, s, S, dPd, (bf16*)dS, nrows, Skv, ld,
                        scale, scale * 1.4426950408889634f, (unsigned)(seed & 0xFFFFFFFFu), (unsigned)(seed >> 32), layer,
@@ -823,6 +832,7 @@ __global__ __launch_bounds__(256) void embedding_scatter_add_kernel(const float*
 }
 hipError_t launch_embedding_scatter_add(const float* drows, const int64_t* ids, float* dtable, int B, int V, int d,
                                         hipStream_t s) {
+    if (B < 0 || V < 1 || d < 1) return hipErrorInvalidValue;   // V < 1 clamps an id to row -1
     hipLaunchKernelGGL(embedding_scatter_add_kernel, dim3(1), dim3(256), 0, s, drows, ids, dtable, B, V, d);
     return hipGetLastError();
 }

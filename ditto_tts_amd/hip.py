@@ -225,6 +225,15 @@ _ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in OPTIM_
 OPTIM_CHUNK_QUADS = 4096      # DITTO_OPTIM_CHUNK_QUADS: 16-byte quads per chunk of a segment (part of the norm's bits)
 
 
+# The backward pass's row kernels, one launch each with every buffer's byte size (include/ditto_train_rows.h,
+# csrc/train_rows_api.hip): a third table, built and bound the same way; the tests reach its entries through call() only.
+with open(os.path.join(INCLUDE, "ditto_train_rows.h")) as _f:
+    TRAIN_ROWS_PROTOTYPES = parse_prototypes(_f.read())
+TRAIN_ROWS_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in TRAIN_ROWS_PROTOTYPES.items()}
+_ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in TRAIN_ROWS_PROTOTYPES.items()})
+SMALL_LINEAR_FWD, SMALL_LINEAR_BWD_W, SMALL_LINEAR_BWD_X = range(3)   # the `mode` of ditto_bwd_small_linear
+
+
 class OptimSeg(C.Structure):
     """ditto_optim_seg: one parameter tensor of the optimizer's device table, 72 bytes."""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p),
@@ -264,7 +273,7 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
         frozen = bool(os.environ.get("DITTO_HIP_LIB"))   # a diagnostic or FROZEN earlier build for same-box A/Bs (tools/):
-        for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items()):   # it may predate entries added since (then absent)
+        for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items(), *TRAIN_ROWS_SYMBOLS.items()):   # it may predate entries added since (then absent)
             try:
                 fn = getattr(l, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:
@@ -289,7 +298,8 @@ def call(name: str, **kw) -> int:
     parameter, raised before the library is entered."""
     order = _ORDER.get(name)
     if order is None:
-        raise TypeError(f"{name}: include/{'ditto_optim.h' if name.startswith('ditto_optim_') else 'ditto_hip.h'} declares no such entry")
+        header = "ditto_optim.h" if name.startswith("ditto_optim_") else "ditto_train_rows.h" if name.startswith("ditto_bwd_") else "ditto_hip.h"
+        raise TypeError(f"{name}: include/{header} declares no such entry")
     if len(kw) != len(order) or not all(p in kw for p in order):
         missing, unknown = [p for p in order if p not in kw], [p for p in kw if p not in order]
         raise TypeError(f"{name}: " + "; ".join(f"{what} {', '.join(ps)}" for what, ps in

@@ -28,6 +28,29 @@ def test_header_symbols_exported_and_bound():
     assert lib.ditto_abi_version() == 10
 
 
+def test_train_rows_header_declared_exported_and_bound():
+    """include/ditto_train_rows.h, a table of its own beside ditto_hip.h's: declared = exported = bound"""
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ditto_train_rows.h")).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(ditto_[a-z0-9_]+)\s*\(", txt)))
+    assert len(names) == 15 and all(n.startswith("ditto_bwd_") for n in names)
+    assert sorted(hip.TRAIN_ROWS_PROTOTYPES) == sorted(hip.TRAIN_ROWS_SYMBOLS) == names
+    assert not set(names) & set(hip.SYMBOLS) and not set(names) & set(hip.OPTIM_SYMBOLS)
+    lib = hip.lib()
+    for n in names:
+        fn = getattr(lib, n)                                                         # AttributeError: declared but not exported
+        res, params = hip.TRAIN_ROWS_PROTOTYPES[n]
+        assert fn.restype is res and list(fn.argtypes) == [t for _, t in params], n
+        pnames = [p for p, _ in params]
+        assert len(set(pnames)) == len(pnames), n
+        if res is C.c_int:                                                            # every pointer is followed by its byte size
+            for i, (p, t) in enumerate(params):
+                if t is C.c_void_p and p != "stream":
+                    assert params[i + 1] == (p + "_bytes", C.c_size_t), (n, p)
+    assert hip.TRAIN_ROWS_PROTOTYPES["ditto_bwd_colsum_scratch_bytes"] == (C.c_size_t, [("M", C.c_int), ("n", C.c_int)])
+    assert hip.TRAIN_ROWS_PROTOTYPES["ditto_bwd_reduce_partials"][1][4:6] == [("chunks", C.c_int), ("n", C.c_size_t)]
+    assert hip.TRAIN_ROWS_PROTOTYPES["ditto_bwd_softmax_rows"][1][11] == ("seed", C.c_uint64)
+
+
 def test_prototypes_are_parsed_from_the_header():
     """hip.PROTOTYPES (and SYMBOLS, its view) come from include/ditto_hip.h by one type rule: the same functions as the name
     scan above, distinct parameter names, and the declarations that are awkward to parse."""
