@@ -819,6 +819,63 @@ int ditto_attention_dropout_bf16(const void* q, int ldq, const void* k, int ldk,
     HIP_TRY(launch_attention(a, (hipStream_t)stream));
     return DITTO_OK;
 }
+// The residual training forward as ditto_train_forward's self-attention fills it (AttnArgs above: resid_in, resid_f32, ldr, resid_bf16,
+// optional out_bf16 / ldo, lse_out; packed: cu_* / q_rows / kv_rows), in the manner of train_rows_api.hip: the extent of every buffer is
+// computed here from rows, strides, H and 64, and what does not fit is refused before any HIP call — SHAPE, then ARG, then SIZE.
+int ditto_attention_train_resid_bf16(const void* q, size_t q_bytes, int ldq, const void* k, size_t k_bytes, int ldk, const void* v,
+                                     size_t v_bytes, int ldv, const void* resid_in, size_t resid_in_bytes, void* resid_out,
+                                     size_t resid_out_bytes, int ldr, int resid_bf16, void* out, size_t out_bytes, int ldo,
+                                     float* lse_out, size_t lse_out_bytes, const int32_t* cu_q, size_t cu_q_bytes, const int32_t* cu_kv,
+                                     size_t cu_kv_bytes, int B, int H, int Sq, int Skv, int max_q, int max_kv, int dh, float scale,
+                                     float dropout_p, uint64_t seed, int layer, ditto_stream_t stream) {
+    const char* who = "ditto_attention_train_resid_bf16";
+    const bool packed = cu_q || cu_kv;
+    if (dh != 64) return fail(DITTO_ERR_SHAPE, "%s: head_dim %d: the fused training forward is head_dim 64 only", who, dh);
+    if (B < 1 || H < 1 || Sq < 1 || Skv < 1 || max_q < 1 || max_kv < 1 || B > 65535 || H > 4096 || layer < 0)
+        return fail(DITTO_ERR_SHAPE, "%s: B %d, H %d, Sq %d, Skv %d, max_q %d, max_kv %d, layer %d: need 1 <= B <= 65535, 1 <= H <= 4096, "
+                    "positive lengths, layer >= 0", who, B, H, Sq, Skv, max_q, max_kv, layer);
+    if (packed ? (max_q > Sq || max_kv > Skv || B > Sq || B > Skv) : (max_q != Sq || max_kv != Skv))
+        return fail(DITTO_ERR_SHAPE, "%s: Sq %d, Skv %d, max_q %d, max_kv %d, B %d: packed needs max_q <= Sq, max_kv <= Skv and a row per "
+                    "utterance; dense needs max_q == Sq, max_kv == Skv", who, Sq, Skv, max_q, max_kv, B);
+    const int d = H * 64;
+    const bool has_out = out != nullptr;
+    if ((ldq | ldk | ldv | ldr) % 8 || ldq < d || ldk < d || ldv < d || ldr < d || (has_out && (ldo % 8 || ldo < d)))
+        return fail(DITTO_ERR_SHAPE, "%s: ldq %d, ldk %d, ldv %d, ldr %d, ldo %d: row strides must be multiples of 8 covering H * 64 = %d columns",
+                    who, ldq, ldk, ldv, ldr, ldo, d);
+    const long long rq = packed ? Sq : (long long)B * Sq, rk = packed ? Skv : (long long)B * Skv;
+    const long long wgs = (long long)B * H * ((max_q + 127) / 128);
+    if (rq > 0x7FFFFFFFLL || rk > 0x7FFFFFFFLL || wgs > 0x7FFFFFFFLL)
+        return fail(DITTO_ERR_SHAPE, "%s: %lld query rows, %lld key rows, %lld workgroups: each must fit an int", who, rq, rk, wgs);
+    if (resid_bf16 & ~1) return fail(DITTO_ERR_ARG, "%s: resid_bf16 %d is 0 / 1", who, resid_bf16);
+    if (!cu_q != !cu_kv) return fail(DITTO_ERR_ARG, "%s: cu_q and cu_kv are given together (packed) or both null (dense)", who);
+    if (!(dropout_p >= 0.f && dropout_p < 1.f) || !std::isfinite(scale))
+        return fail(DITTO_ERR_ARG, "%s: dropout_p %g outside [0, 1) or scale %g not finite", who, dropout_p, scale);
+    if ((g_attn_flags & 8192) && (resid_bf16 || has_out || packed))
+        return fail(DITTO_ERR_ARG, "%s: under attn_flags 8192 (the older training-forward kernel) there is no bf16 stream, no O beside the "
+                    "stream and no packed batch", who);
+    const size_t esz = resid_bf16 ? 2 : 4, ralign = resid_bf16 ? 8 : 16;
+    const size_t qext = ((size_t)(rq - 1) * ldq + d) * 2, kext = ((size_t)(rk - 1) * ldk + d) * 2, vext = ((size_t)(rk - 1) * ldv + d) * 2;
+    const size_t rext = ((size_t)(rq - 1) * ldr + d) * esz, oext = has_out ? ((size_t)(rq - 1) * ldo + d) * 2 : 0;
+    if (int rc = check_bufs(who, {{"q", q, q_bytes, qext, 16, false},
+                                  {"k", k, k_bytes, kext, 16, false},
+                                  {"v", v, v_bytes, vext, 16, false},
+                                  {"resid_in", resid_in, resid_in_bytes, rext, ralign, true},
+                                  {"resid_out", resid_out, resid_out_bytes, rext, ralign, false},
+                                  {"out", out, out_bytes, oext, 8, true},
+                                  {"lse_out", lse_out, lse_out_bytes, (size_t)rq * H * 4, 4, false},
+                                  {"cu_q", cu_q, cu_q_bytes, ((size_t)B + 1) * 4, 4, true},
+                                  {"cu_kv", cu_kv, cu_kv_bytes, ((size_t)B + 1) * 4, 4, true}}))
+        return rc;
+    AttnArgs a{};
+    a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv;
+    a.resid_f32 = (float*)resid_out; a.resid_in = (const float*)resid_in; a.ldr = ldr; a.resid_bf16 = resid_bf16 != 0;
+    a.out_bf16 = out; a.ldo = has_out ? ldo : 0;
+    a.B = B; a.H = H; a.Sq = max_q; a.Skv = max_kv; a.dh = dh; a.scale = scale;
+    if (packed) { a.cu_q = cu_q; a.cu_kv = cu_kv; a.q_rows = Sq; a.kv_rows = Skv; }
+    a.dropout_p = dropout_p; a.seed = seed; a.layer = layer; a.lse_out = lse_out;
+    HIP_TRY(launch_attention(a, (hipStream_t)stream));
+    return DITTO_OK;
+}
 
 
 size_t ditto_attention_bwd_packed_workspace_bytes(int B, int H, int Sq) {

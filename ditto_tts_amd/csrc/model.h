@@ -20,6 +20,27 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// one device buffer of an entry that takes every pointer with its byte size (train_rows_api.hip, ditto_attention_train_resid_bf16):
+// refused when null (unless `optional`), misaligned or shorter than `need` bytes — DITTO_ERR_ARG before DITTO_ERR_SIZE, no HIP call
+struct ArgBuf {
+    const char* name;
+    const void* p;
+    size_t have, need, align;
+    bool optional;
+};
+inline int check_bufs(const char* who, std::initializer_list<ArgBuf> bufs) {
+    for (const ArgBuf& b : bufs) {
+        if (!b.p) {
+            if (!b.optional) return fail(DITTO_ERR_ARG, "%s: null %s", who, b.name);
+            continue;
+        }
+        if ((uintptr_t)b.p % b.align) return fail(DITTO_ERR_ARG, "%s: %s must be %zu-byte aligned", who, b.name, b.align);
+    }
+    for (const ArgBuf& b : bufs)
+        if (b.p && b.have < b.need) return fail(DITTO_ERR_SIZE, "%s: %s too small: %zu < %zu bytes", who, b.name, b.have, b.need);
+    return DITTO_OK;
+}
+
 struct LayerPack {
     const void *Wqkv, *Wcq, *Wco, *W1g, *W2;
     const void *WcqP = nullptr, *WcqP32 = nullptr;   // stage-major images of the cross q-projection for gemm_lnq.hip (d == 768 bf16): k-group 16 / 32

@@ -12,25 +12,7 @@
 namespace ditto {
 namespace {
 
-// one device buffer of an entry: refused when null (unless `optional`), misaligned or shorter than `need` bytes
-struct Buf {
-    const char* name;
-    const void* p;
-    size_t have, need, align;
-    bool optional;
-};
-int check_bufs(const char* who, std::initializer_list<Buf> bufs) {
-    for (const Buf& b : bufs) {
-        if (!b.p) {
-            if (!b.optional) return fail(DITTO_ERR_ARG, "%s: null %s", who, b.name);
-            continue;
-        }
-        if ((uintptr_t)b.p % b.align) return fail(DITTO_ERR_ARG, "%s: %s must be %zu-byte aligned", who, b.name, b.align);
-    }
-    for (const Buf& b : bufs)
-        if (b.p && b.have < b.need) return fail(DITTO_ERR_SIZE, "%s: %s too small: %zu < %zu bytes", who, b.name, b.have, b.need);
-    return DITTO_OK;
-}
+// (ArgBuf, check_bufs — one device buffer of an entry and its refusals: model.h)
 bool ln_dim(int d) { return d >= 4 && d <= 2048 && d % 4 == 0; }
 // the packed row of the last of `rows` rows, or -1 when the map's arguments are out of range or it leaves int
 long long last_packed_row(int rows, int blk, int mult, int row_off) {

@@ -1001,6 +1001,22 @@ int ditto_attention_dropout_bf16(const void* q, int ldq, const void* k, int ldk,
                                  int ldo, float* lse_out, int B, int H, int Sq, int Skv, int dh, float scale,
                                  float dropout_p, uint64_t seed, int layer, void* workspace, size_t workspace_bytes,
                                  ditto_stream_t stream);
+/* the RESIDUAL form of the training-forward attention (head_dim 64, q UNSCALED), as ditto_train_forward's self-attention launches it
+ * (src/components/DiT.py:139: no out-projection): resid_out[row, h*64 + c] = resid_in[...] + O, resid_in == NULL = in place; the stream
+ * is fp32 [rows, ldr] or (resid_bf16 = 1) bf16 [rows, ldr].  `out` (optional) receives O itself as bf16 [rows, ldo] beside the stream;
+ * lse_out (required) the log2-domain log-sum-exp.  Dense (cu_q == cu_kv == NULL): rows = B * Sq / B * Skv, max_q == Sq, max_kv == Skv,
+ * lse_out fp32 [B, H, Sq].  Packed (both given, device int32 [B + 1]): Sq / Skv are the rows of the buffers in all, max_q / max_kv the
+ * longest lengths, lse_out fp32 [H, Sq], as ditto_attention_train_packed_bf16.  Every device pointer is followed by its byte size: the
+ * extent the launch reads or writes in each buffer is computed on the host, and what does not fit is refused before any HIP call
+ * (DITTO_ERR_SHAPE: dh != 64, a stride that is no multiple of 8 or narrower than H * 64, an extent out of range; then DITTO_ERR_ARG: a
+ * null or misaligned pointer, a flag or dropout_p out of range, the bf16 stream / `out` / a packed batch under attn_flags 8192; then
+ * DITTO_ERR_SIZE: a buffer shorter than its extent).  No arithmetic is added: one launch_attention, exported for unit parity tests. */
+int ditto_attention_train_resid_bf16(const void* q, size_t q_bytes, int ldq, const void* k, size_t k_bytes, int ldk, const void* v,
+                                     size_t v_bytes, int ldv, const void* resid_in, size_t resid_in_bytes, void* resid_out,
+                                     size_t resid_out_bytes, int ldr, int resid_bf16, void* out, size_t out_bytes, int ldo,
+                                     float* lse_out, size_t lse_out_bytes, const int32_t* cu_q, size_t cu_q_bytes, const int32_t* cu_kv,
+                                     size_t cu_kv_bytes, int B, int H, int Sq, int Skv, int max_q, int max_kv, int dh, float scale,
+                                     float dropout_p, uint64_t seed, int layer, ditto_stream_t stream);
 
 /* fp8 building blocks, exported for unit parity tests (all e4m3, OCP):
  * ditto_quantize_rows_fp8: fp32 [rows, cols] -> fp8 [rows, cols] + scales fp32 [rows] (amax/448 per row);

@@ -152,6 +152,27 @@ static void refusals_before_any_gpu_call() {
     EXPECT(ditto_gemm_bf16(nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 1, 0, nullptr) != DITTO_OK, "gemm(null)");
     EXPECT(ditto_attention_bf16(p, 64, p, 64, p, 64, p, 64, 1, 1, 64, 64, 96, 0.1f, nullptr, 0, nullptr) == DITTO_ERR_SHAPE, "attention head_dim 96");
     EXPECT(ditto_attention_bf16(p, 768, p, 768, p, 768, p, 768, 1, 1, 64, 64, 768, 0.1f, nullptr, 0, nullptr) == DITTO_ERR_SIZE, "generic attention without workspace");
+    {   // the residual training forward: extents computed on the host (here with sizes that overflow an int), SHAPE, then ARG, then SIZE
+        void* a16 = reinterpret_cast<void*>((uintptr_t)1 << 20);   // 16-byte aligned, never dereferenced
+        float* l4 = reinterpret_cast<float*>(a16);
+        const int32_t* cu = reinterpret_cast<const int32_t*>(a16);
+        const size_t big = (size_t)1 << 40;
+        auto call = [&](size_t q_bytes, int ldq, void* rin, float* lse, const int32_t* cq, int B, int Sq, int max_q, int dh, float pdrop) {
+            return ditto_attention_train_resid_bf16(a16, q_bytes, ldq, a16, big, 768, a16, big, 768, rin, big, a16, big, 768, 0, nullptr, 0, 0, lse,
+                                                    big, cq, cq ? big : 0, cq, cq ? big : 0, B, 12, Sq, cq ? Sq : 1024, max_q, cq ? max_q : 1024,
+                                                    dh, 0.125f, pdrop, 7, 0, nullptr);
+        };
+        EXPECT(call(big, 768, a16, l4, nullptr, 2, 1024, 1024, 128, 0.1f) == DITTO_ERR_SHAPE, "train_resid head_dim 128");
+        EXPECT(call(big, 772, a16, l4, nullptr, 2, 1024, 1024, 64, 0.1f) == DITTO_ERR_SHAPE, "train_resid ldq %% 8");
+        EXPECT(call(big, 768, a16, l4, nullptr, 65535, 1 << 20, 1 << 20, 64, 0.1f) == DITTO_ERR_SHAPE, "train_resid B * Sq past an int");
+        EXPECT(call(big, 768, a16, l4, cu, 2, 2000, 2001, 64, 0.1f) == DITTO_ERR_SHAPE, "train_resid packed max_q > Sq");
+        EXPECT(call(big, 768, a16, nullptr, nullptr, 2, 1024, 1024, 64, 0.1f) == DITTO_ERR_ARG, "train_resid null lse_out");
+        EXPECT(call(big, 768, reinterpret_cast<void*>(((uintptr_t)1 << 20) + 8), l4, nullptr, 2, 1024, 1024, 64, 0.1f) == DITTO_ERR_ARG,
+               "train_resid misaligned resid_in");
+        EXPECT(call(big, 768, a16, l4, nullptr, 2, 1024, 1024, 64, 1.0f) == DITTO_ERR_ARG, "train_resid dropout_p 1");
+        EXPECT(call(((size_t)2047 * 768 + 768) * 2 - 1, 768, a16, l4, nullptr, 2, 1024, 1024, 64, 0.1f) == DITTO_ERR_SIZE, "train_resid q one byte short");
+        EXPECT(call(big, 1 << 30, a16, l4, nullptr, 16, 1 << 20, 1 << 20, 64, 0.1f) == DITTO_ERR_SIZE, "train_resid extent of 2^55 bytes accepted");
+    }
     // the full-row GEMM addresses A with 32-bit byte offsets: refuse M * lda * 2 >= 2^32 for the lda actually passed
     float* fo = reinterpret_cast<float*>(p);
     EXPECT(ditto_gemm_ln_bf16(p, 3072, p, nullptr, nullptr, fo, 768, nullptr, nullptr, nullptr, 0, 699392, 768, 3072, nullptr) == DITTO_ERR_SHAPE, "gemm_ln accepted wrapping A offsets");

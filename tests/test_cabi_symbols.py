@@ -55,7 +55,7 @@ def test_prototypes_are_parsed_from_the_header():
     """hip.PROTOTYPES (and SYMBOLS, its view) come from include/ditto_hip.h by one type rule: the same functions as the name
     scan above, distinct parameter names, and the declarations that are awkward to parse."""
     P, vp, i, sz = hip.PROTOTYPES, C.c_void_p, C.c_int, C.c_size_t
-    assert sorted(P) == declared_functions() and len(P) == 142
+    assert sorted(P) == declared_functions() and len(P) == 143
     for name, (res, params) in P.items():
         names = [n for n, _ in params]
         assert len(set(names)) == len(names) and all(n.isidentifier() for n in names), name
@@ -76,6 +76,10 @@ def test_prototypes_are_parsed_from_the_header():
     res, params = P["ditto_model_create"]                                             # spans two lines; struct pointers, a handle out
     assert res is i and [n for n, _ in params] == ["cfg", "w", "arena", "arena_bytes", "stream", "out"]
     assert [t for _, t in params] == [C.POINTER(hip.Config), C.POINTER(hip.Weights), vp, sz, vp, vp]
+    res, params = P["ditto_attention_train_resid_bf16"]                               # every device pointer is followed by its byte size
+    for n in "q k v resid_in resid_out out lse_out cu_q cu_kv".split():
+        at = [p for p, _ in params].index(n)
+        assert params[at] == (n, vp) and params[at + 1] == (n + "_bytes", sz)
     assert P["ditto_train_backward"][1][14] == ("grads", C.POINTER(hip.Grads))
     assert P["ditto_slp_create"][1][:2] == [("cfg", C.POINTER(hip.SlpConfig)), ("w", C.POINTER(hip.SlpWeights))]
     assert P["ditto_gemm_epilogue_bf16"][1][0] == ("args", C.POINTER(hip.GemmEpilogueArgs))

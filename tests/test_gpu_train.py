@@ -7,11 +7,13 @@ tensor (bf16 operands, fp32 accumulation, bf16-rounded activation gradients betw
 Train-mode dropout: the HIP path draws the cross-attention keep-mask from a counter-based hash, restated in the
 oracle (hash_dropout_mask), so train-mode VALUES are compared, not only structure."""
 import ctypes as C
+from types import SimpleNamespace
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import attn_train_fwd_ref as F_REF
 from ditto_tts_amd import hip
 from ditto_tts_amd.config import DiTTOConfig
 from ditto_tts_amd.modules import DiTTO
@@ -105,6 +107,13 @@ def test_attention_dropout_forward_and_backward_vs_autograd(B, H, Sq, Skv, dh, p
     if fused:   # log2-domain log-sum-exp of the scaled scores
         want = torch.logsumexp(torch.matmul(qh, kh.transpose(-2, -1)).detach() * scale, dim=-1) / 0.6931471805599453
         assert max_abs(lse, want) < 2e-3 * (1 + float(want.abs().max()))
+        # ... and every slot within the elementwise bound derived from the kernel's arithmetic (attn_train_fwd_ref.py)
+        ref = F_REF.reference(SimpleNamespace(q=bf16(q.detach()).view(B * Sq, d), k=bf16(k.detach()).view(B * Skv, d),
+                                              v=bf16(v.detach()).view(B * Skv, d), segs=F_REF.dense_segs(B, Sq, Skv), H=H, scale=scale,
+                                              p=0.0, keep=None))
+        r = F_REF.worst_ratio(lse.cpu().permute(1, 0, 2).reshape(H, B * Sq), ref.L, ref.e_L)
+        print(f"lse worst ratio against the elementwise bound: {r:.3f} (bound at most {float(ref.e_L.max()):.3e} log2 units)")
+        assert r <= 1.0 and float(ref.e_L.max()) <= 2.0 ** -7
     dq = torch.empty_like(qd); dk = torch.empty_like(kd); dv = torch.empty_like(vd)
     hip.check(lib.ditto_attention_bwd_bf16(qd.data_ptr(), d, kd.data_ptr(), d, vd.data_ptr(), d, dod.data_ptr(), d,
                                            o.data_ptr(), d, lse.data_ptr() if fused else None,

@@ -7,11 +7,13 @@ composed from the oracle's public pieces so that utterance b gets ITS slice of t
 Tolerances are those tests/test_gpu_train.py states for the same quantities on the same kernels: forward rel-L2 <= 2e-2, per-tensor
 parameter gradient < 3e-2, kernel-level attention forward < 1.5e-2, dq / dk / dv < 2e-2."""
 import ctypes as C
+from types import SimpleNamespace
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import attn_train_fwd_ref as F_REF
 from ditto_tts_amd import hip
 from ditto_tts_amd.config import DiTTOConfig
 from ditto_tts_amd.modules import DiTTO
@@ -103,6 +105,12 @@ def test_packed_attention_forward_and_backward_vs_autograd(self_attn, QL, KL, H,
     print(f"packed attention fwd self={self_attn} p={p}: O rel_l2 {r:.3e}")
     assert r < 1.5e-2
     assert max_abs(lse[:, :Sq], want_lse) < 2e-3 * (1 + float(want_lse.abs().max()))
+    # ... and every slot within the elementwise bound derived from the kernel's arithmetic (attn_train_fwd_ref.py)
+    ref = F_REF.reference(SimpleNamespace(q=bf16(q), k=bf16(k), v=bf16(v), segs=F_REF.packed_segs(QL, KL), H=H, scale=scale, p=0.0,
+                                          keep=None))
+    r = F_REF.worst_ratio(lse[:, :Sq].cpu(), ref.L, ref.e_L)
+    print(f"lse worst ratio against the elementwise bound: {r:.3f} (bound at most {float(ref.e_L.max()):.3e} log2 units)")
+    assert r <= 1.0 and float(ref.e_L.max()) <= 2.0 ** -7
     assert torch.all(o[Sq:].float() == SENT) and torch.all(lse[:, Sq:] == SENT)
     nb = lib.ditto_attention_bwd_packed_workspace_bytes(B, H, RQ)
     ws = torch.empty(nb, dtype=torch.uint8, device=DEV)

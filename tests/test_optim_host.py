@@ -1,5 +1,5 @@
 """The fused optimizer on a GPU-less host: include/ditto_optim.h is parsed into a table of its own, exported and bound, and leaves
-ditto_hip.h's 142 functions alone; the C entries' argument refusals (no launch is made: every call here fails its checks first); the
+ditto_hip.h's 143 functions alone; the C entries' argument refusals (no launch is made: every call here fails its checks first); the
 constructor's refusals; the state's key layout beside torch.optim.AdamW's; the table builder's chunk bases on hand-written sizes."""
 import ctypes as C
 import os
@@ -20,7 +20,7 @@ def _declared():
     return sorted(set(re.findall(r"\b(ditto_optim_[a-z0-9_]+)\s*\(", txt)))
 
 
-def test_header_is_parsed_exported_and_bound_beside_the_142():
+def test_header_is_parsed_exported_and_bound_beside_ditto_hip_h():
     names = _declared()
     assert names == ["ditto_optim_adamw_step", "ditto_optim_grad_norm", "ditto_optim_scratch_bytes", "ditto_optim_swap"]
     assert sorted(hip.OPTIM_PROTOTYPES) == names
@@ -32,7 +32,7 @@ def test_header_is_parsed_exported_and_bound_beside_the_142():
         fn = getattr(lib, n)                                     # exported ...
         assert fn.restype == res and list(fn.argtypes) == [t for _, t in params], n      # ... and bound
         assert n not in hip.SYMBOLS and n not in hip.PROTOTYPES
-    assert len(hip.PROTOTYPES) == 142 and len(hip.SYMBOLS) == 142
+    assert len(hip.PROTOTYPES) == 143 and len(hip.SYMBOLS) == 143
     assert lib.ditto_abi_version() == 10
     assert hip.OPTIM_PROTOTYPES["ditto_optim_scratch_bytes"] == (C.c_size_t, [("n_chunks", C.c_size_t)])
     assert [q for q, _ in hip.OPTIM_PROTOTYPES["ditto_optim_adamw_step"][1]] == [
