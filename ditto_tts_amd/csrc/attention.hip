@@ -780,7 +780,7 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
             // probabilities, attn64v2's that of their bf16 roundings): C2 B = 32 112 against 127 us in isolation (-12 %), Sq = Skv =
             // 4096 397 against 463 (profiles/r06_attn_probe.txt).  attn_flags 131072 = never, 262144 = wherever the strides allow.
             {
-                const long rows_cls = opt_class_rows() > 0 ? opt_class_rows() : (long)a.B * a.Sq;
+                const long rows_cls = class_rows((long)a.B * a.Sq);
                 const long wgs = (rows_cls / 256) * a.H;
                 const bool wide_ok = a.ldo % 8 == 0 && (!a.resid_f32 || a.ldr % 8 == 0);   // 16-byte row pieces in the epilogue
                 if (wide_ok && !(g_attn_flags & 131072) && (wgs >= (a.resid_f32 ? g_attn64p_min_wgs : g_attn64p_min_wgs_plain) || (g_attn_flags & 262144)))

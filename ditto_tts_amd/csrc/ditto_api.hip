@@ -55,15 +55,11 @@ ArenaPlan plan_arena(const ditto_config& c) {
         q.bqkv = take(3 * dp * 4); q.bcq = take(dp * 4); q.bco = take(d * 4); q.b1g = take(8 * d * 4); q.b2 = take(d * 4);
         q.g1 = take(d * 4); q.be1 = take(d * 4); q.g2 = take(d * 4); q.be2 = take(d * 4); q.g3 = take(d * 4);
         q.be3 = take(d * 4);
-        // stage-major bf16 copies of the N = d projections for the full-row kernels (gemm_fr.hip: d == 768, bf16 linears;
-        // gemm_fr64.hip: d == 1024 — the cross out-projection is bf16 in the fp8 configuration too, fc2 only without it)
-        const bool fp8c = (c.flags & DITTO_CFG_FP8_LINEAR) != 0;
-        const bool pad = dp != d;                                    // padded heads: the tiled GEMMs + LayerNorm launches only
-        const bool fr_o = !pad && ((d == 768 && !fp8c) || d == 1024), fr_2 = !pad && (d == 768 || d == 1024) && !fp8c;
-        q.WcoP = fr_o ? take(d * d * 2) : 0; q.W2P = fr_2 ? take(4 * d * d * 2) : 0;
-        // ... and of the cross q-projection for the fused norm2 + q-projection kernel (gemm_lnq.hip, d == 768): both MFMA shapes' images
-        const bool lnq = !pad && ((d == 768 && !fp8c) || d == 1024);   // (the q-projection is a bf16 GEMM in the fp8 configuration too)
-        q.WcqP = lnq ? take(d * d * 2) : 0; q.WcqP32 = lnq && d == 768 ? take(d * d * 2) : 0;
+        // stage-major bf16 copies of the N = d projections for the full-row kernels (gemm_fr.hip, gemm_fr64.hip) and of the cross
+        // q-projection for the fused norm2 + q-projection kernel (gemm_lnq.hip; d == 768: both MFMA shapes' images): model.h stage_packs
+        const StagePacks have = stage_packs(c);
+        q.WcoP = have.o ? take(d * d * 2) : 0; q.W2P = have.fc2 ? take(4 * d * d * 2) : 0;
+        q.WcqP = have.lnq ? take(d * d * 2) : 0; q.WcqP32 = have.lnq && d == 768 ? take(d * d * 2) : 0;
     }
     p.Wkv = take(L * 2 * dp * d * 2); p.bkv = take(L * 2 * dp * 4);
     p.Wfin = take(d * 2 * d * 2); p.bfin = take(d * 4);
@@ -78,65 +74,6 @@ ArenaPlan plan_arena(const ditto_config& c) {
 // ditto_text_precompute scratch (front of the same workspace) over `rows` text rows of B utterances: bf16(text) | pooled fp32
 static inline size_t text_scratch_bytes(const ditto_config& c, int B, size_t rows) {
     return al(rows * c.text_dim * 2) + al((size_t)B * c.text_dim * 4);
-}
-
-// Small batches leave the long-K GEMMs of the step on a few dozen workgroups, each walking all of K alone (B = 1:
-// fc2 is 48 tiles x 48 K-tiles = 41 us for 4.8 GFLOP).  Those run split-K: `splits` workgroups per output tile write
-// fp32 partials, launch_splitk_finish adds them in order together with bias and residual.  Target: g_splitk_wgs
-// workgroups in flight, at least 4 K-tiles per split.  Measured in-model (tools/step_ab.py, C2): B = 1 fc2 40.6 ->
-// 24.2 us, step 1.87 -> 1.68 ms at 256; B = 2 2.12 -> 2.06 ms; B >= 4 never splits.
-// OFF by default (ditto_set_option("splitk_wgs", 256) / DITTO_SPLITK_WGS=256 turn it on): the K-partition depends on
-// the batch size, so with it an utterance's result is no longer bit-identical across batch compositions — the
-// property tests/test_gpu_model.py::test_full_size_c2_properties holds the default path to.
-static int g_splitk_wgs = [] { const char* e = getenv("DITTO_SPLITK_WGS"); return e ? atoi(e) : 0; }();
-// "residual_bf16": the residual stream h between the segments of a block lives in HBM as bf16 (fp32 only inside accumulators
-// and LayerNorm statistics) wherever the launch takes the full-row class at d = 768 / head_dim 64 (ditto_forward decides)
-// "ll_mask": the low-latency class's launch fusions (they change no bit): bit 0 = fc2's split-K finish also writes the NEXT
-// block's norm1, bit 1 = the cross out-projection runs as two K-splits whose finish also writes norm3
-// (bit 2, round 5: split-KV attention + ordered merge — measured slower at B = 1, 1.59 -> 1.72 ms, profiles/r05_splitkv_ab.txt — was deleted in round 6)
-int g_ll_mask = [] { const char* e = getenv("DITTO_LL_MASK"); const int v = e ? atoi(e) : 3; return v < 0 || v > 3 ? 3 : v; }();
-// "lnq": norm2 fused into the cross-attention q-projection (gemm_lnq.hip) for launches of the full-row class at d = 768:
-// 0 = off (LayerNorm launch + tiled GEMM), 32 / 16 = on, with that MFMA shape (32x32x16 / 16x16x32)
-// "lnq_min_rows": > 0: the fused norm2 + q-projection also runs BELOW the full-row class, from that many (class) rows on (A/B)
-// Default 8192 since round 5: with the kernel on two waves per SIMD the fused launch wins from 128 of its 64-row tiles on
-// (profiles/r05_small_batch_lnq8.txt, same process: B = 8 4.02 -> 3.95 ms, B = 16 6.63 -> 6.47; B = 4 2.61 -> 2.63, hence not lower).
-int g_lnq_min_rows = [] { const char* e = getenv("DITTO_LNQ_MIN_ROWS"); return e ? atoi(e) : 8192; }();
-int g_lnq = [] { const char* e = getenv("DITTO_LNQ"); const int v = e ? atoi(e) : 32; return v == 0 || v == 16 || v == 32 ? v : 32; }();   // validated like ditto_set_option
-int g_resid_bf16 = [] { const char* e = getenv("DITTO_RESIDUAL_BF16"); return e ? (atoi(e) != 0) : 1; }();   // normalised to 0 / 1
-// "qkv_split" (round 5): 0 = off; n > 0 = the QKV GEMM's last 256 columns as a second launch where that leaves whole rounds of
-// 256 x 256 tiles (run_block), for launches of at most n rounds of such tiles.  Default 3 = B = 8 and B = 16 at N = 1024
-// (profiles/r05_qkv_split_ab.txt, same process: QKV 48.6 -> 44.4 us / 75.6 -> 72.3, step 3.87 -> 3.83 / 6.44 -> 6.42 ms; B = 24 and
-// B = 32 — 3.4 and 4.5 rounds — do not gain: the small-tile tail launch costs what the half round did).  Bit-identical either way.
-int g_qkv_split = [] { const char* e = getenv("DITTO_QKV_SPLIT"); return e ? atoi(e) : 3; }();
-int small_batch_k_splits(int M, int N, int K) {
-    if (g_splitk_wgs < 0) return 1;                        // -1: never split
-    const int ktiles = K / 64;
-    if (g_splitk_wgs == 0) {
-        // Default since round 4: the LOW-LATENCY CLASS.  A batch of at most 2048 rows (1-2 utterances at N = 1024: the reference's
-        // own call pattern, Experiments.ipynb:125-132) leaves its long-K GEMMs (fc2: 48 tiles x 48 K-tiles at B = 1; the final
-        // projection) on a fifth of the chip; they run split over K with an ordered fp32 reduce (bias + residual in the reduce):
-        // fc2 40.8 -> 24.2 us, step 1.83 -> 1.63 ms at C2 B = 1.  The number of splits depends on K ONLY, so inside the class an
-        // utterance's bits do not depend on its batch neighbours; like the full-row class (kernels.h fr_rule_rows) the class is a
-        // function of the launch's rows and a caller that splits one batch pins it ("fr_class_rows"): the rows of the UNSPLIT batch.
-        const long rows = opt_class_rows() > 0 ? opt_class_rows() : M;
-        if (rows > 2048 || ktiles < 24) return 1;
-        const int ns = ktiles / 12;                        // K = 3072: 4, 1536: 2, 4096: 5, 2048: 2
-        return ns > 8 ? 8 : ns;
-    }
-    const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);   // > 0: the explicit rule of rounds 1-3 (a workgroup target)
-    if (tiles > 256 || ktiles < 16) return 1;
-    long ns = g_splitk_wgs / tiles;
-    if (ns > ktiles / 4) ns = ktiles / 4;
-    if (ns > 8) ns = 8;
-    return ns < 2 ? 1 : (int)ns;
-}
-
-// The cross out-projection (K = d) in the low-latency class: two K-splits (its 48 tiles at B = 1 become 96 workgroups of half the
-// depth) whose finish also writes norm3 — the LayerNorm launch behind it disappears.  Same class rule as above, K only.
-int small_batch_k_splits_outproj(int M, int K) {
-    if (g_splitk_wgs != 0 || !(g_ll_mask & 2)) return 1;
-    const long rows = opt_class_rows() > 0 ? opt_class_rows() : M;
-    return (rows <= 2048 && K / 64 >= 12) ? 2 : 1;
 }
 
 WsPlan plan_ws(const ditto_config& c, int B, int N, int T) {
@@ -198,19 +135,6 @@ int check_cfg(const ditto_config* c) {
         return fail(DITTO_ERR_SHAPE, "fp8 linear layers need hidden_dim %% 128 == 0");
     if (c->flags & ~DITTO_CFG_FP8_LINEAR) return fail(DITTO_ERR_ARG, "unknown config flag");
     return DITTO_OK;
-}
-
-// A pinned kernel class (fr_class_rows > 0: "decide as the unsplit batch of that many rows would") that says full-row while THIS
-// launch cannot run a full-row kernel (fewer rows than one 64-row tile) would silently take the tiled GEMMs, whose last bits
-// differ: the promise of the pin — sharding changes no bit — would be broken without a sign.  Fail instead.
-int check_class_pin(int M, int d, bool fp8, bool has_fr) {   // has_fr: the model has full-row kernels at all (not on padded heads)
-    if (!has_fr || opt_class_rows() <= 0 || !opt_fr_mask() || M >= 64) return DITTO_OK;
-    const bool wants = d == 768 ? (!fp8 && fr_rule_rows(opt_class_rows()) != 0) : (d == 1024 && fr_pays_64(M));
-    if (!wants) return DITTO_OK;
-    return fail(DITTO_ERR_SHAPE, "kernel class pinned to a batch of %d rows (full-row GEMM + LayerNorm kernels), but this launch has "
-                                 "%d rows, fewer than one 64-row tile: it cannot take that class and its bits would differ from the "
-                                 "unsplit batch's.  Give every shard at least 64 rows, or run the whole batch unfused "
-                                 "(ditto_set_option(\"fr_mask\", 0)).", opt_class_rows(), M);
 }
 
 int check_call_opts(const ditto_call_opts* o) {
@@ -286,7 +210,6 @@ struct Buf { void* p; size_t bytes; };     // a caller-owned workspace
 struct BlockChain {
     bool ln1_done = false;                                   // this block's norm1 output is already in u
     const float *next_g1 = nullptr, *next_be1 = nullptr;     // fc2's launch also writes the NEXT block's norm1 into u
-    bool hb = false;                                         // h holds BF16 rows (the bf16 residual stream)
     float *tap_self = nullptr, *tap_cross = nullptr;         // fp32 copies of h after the self- / cross-attention segment
     char* xcat = nullptr;                                    // last block: fc2 also writes bf16(h_L) into xcat's second half
 };
@@ -298,11 +221,11 @@ template <class F> static int with_opts(const ditto_call_opts* opts, F&& f) {
     return f();
 }
 
-// One DiT block (reference src/components/DiT.py:100-157) on the fp32 residual stream `h`, in place.
+// One DiT block (reference src/components/DiT.py:100-157) on the residual stream `h`, in place; WHICH launches: `fp` (forward_plan.hip)
 static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv_layer, Rope rope, const BatchLayout& lay,
-                     const BlockChain& ch, hipStream_t s) {
+                     const ForwardPlan& fp, const BlockChain& ch, hipStream_t s) {
     float* const h = ws.h; void* const u = ws.u; char* const qkv = ws.qkv; void* const act = ws.act;
-    const bool hb = ch.hb;
+    const bool hb = fp.hb, fr_out = fp.fr_out, fr_fc2 = fp.fr_fc2;
     const ditto_config& c = m->cfg;
     const int d = c.hidden_dim, H = c.num_heads, dh = d / H, M = lay.M, kv_ld = c.num_layers * 2 * cfg_dp(c);
     const float scale = 1.0f / sqrtf((float)dh);
@@ -314,19 +237,12 @@ static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv
     const bool pad = dp != d;
     const bool fp8 = (c.flags & DITTO_CFG_FP8_LINEAR) != 0;   // u / act hold fp8 bytes for the fp8 GEMMs
     const LayerPack& lp = m->layers[l];
-    // full-row GEMM with the residual add and the FOLLOWING LayerNorm fused (gemm_fr.hip): bit 0 = cross out-proj + norm3,
-    // bit 1 = fc2 + the next block's norm1 (ch.ln1_done tells that block its norm1 output is already in u)
-    // (the stage-major weight copies exist exactly where a kernel exists: d = 768 bf16, d = 1024 — there the out-projection
-    // also in the fp8 configuration, with the LayerNorm output written as fp8)
-    const bool fr_out = lp.WcoP && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
-    const bool fr_fc2 = !fp8 && lp.W2P && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
+    // fr_out / fr_fc2: full-row GEMM with the residual add and the FOLLOWING LayerNorm fused (gemm_fr.hip): cross out-proj + norm3 (at
+    // d = 1024 also in the fp8 configuration, with the LayerNorm output written as fp8), fc2 + the next block's norm1 (ch.ln1_done)
     // tiles per utterance: the K-loop rotation period (gemm_fr.hip).  A varlen batch runs unrotated (here and in gemm_lnq's): the
     // rotation is a function of the PADDED N, and an utterance's bits must not depend on the padding
     const bool varlen = lay.varlen();
     const int fr_rot = lay.rot_period(128);
-    if (int rc = ditto::check_class_pin(M, d, fp8, !pad)) return rc;
-    // hb: `h` holds BF16 rows (the bf16 residual stream; ditto_forward decides, and only where both fused launches run)
-    if (hb && (!fr_out || !fr_fc2 || dh != 64 || ch.tap_self || ch.tap_cross)) return fail(DITTO_ERR_ARG, "internal: bf16 stream outside its class");
     // variable-length batches: the attention kernels bound every utterance by its own lengths (attention_varlen.hip); every other
     // launch is row-wise and computes the padding rows too (their results never reach a valid row)
     if (varlen && (dh != 64 || pad)) {
@@ -355,16 +271,7 @@ static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv
                               // would the 256 x 192 kernel (whole tile rounds at M = 32768; gemm_tile 192) buy this class?
             HIP_TRY(launch_gemm(g, EPI_BIAS_BF16, s));
 #else
-            // Whole rounds (round 5, "qkv_split"): where the 256 x 256 tiles of the QKV GEMM leave a fractional round of the CUs but
-            // the tiles of all but its LAST 256 columns make whole rounds (d = 768: 9 column tiles, M a multiple of 8192 rows:
-            // B = 8 is 288 tiles = 1.125 rounds, i.e. two rounds' time), those last columns — all of them v columns, plain bias
-            // epilogue — run as a second launch on the small-tile kernel.  Every tiled kernel multiplies with the same MFMA in
-            // the same K order: the same bits as the single launch (test).
-            const int q_tm = (M + 255) / 256, q_tn = (3 * dp) / 256;
-            const bool q_split = g_qkv_split && !fp8 && fused_rope && g_gemm_tile == 0 && (3 * dp) % 256 == 0 && 3 * dp >= 2048 + 256 &&
-                                 2 * d <= 3 * dp - 256 && (long)q_tm * q_tn >= 144 && ((long)q_tm * q_tn) % 256 != 0 &&
-                                 ((long)q_tm * (q_tn - 1)) % 256 == 0 && (long)q_tm * q_tn <= (long)g_qkv_split * 256;
-            if (q_split) {
+            if (fp.q_split) {   // "qkv_split": the last 256 columns (all v columns, plain bias epilogue) as a second launch
                 GemmArgs gm = g, gt = g;
                 gm.N = 3 * dp - 256;
                 HIP_TRY(launch_gemm(gm, qkv_epi, s));
@@ -377,12 +284,6 @@ static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv
             }
 #endif
         }
-        // norm2 + q-projection in one launch (gemm_lnq.hip) for the full-row class at d = 768; else LayerNorm launch + tiled GEMM
-        const int rows_cls = opt_class_rows() > 0 ? opt_class_rows() : M;
-        // (d = 1024, BASELINE config C5: the same kernel at that width, 32x32x16 only, from 192 tiles of 64 rows on — the rule of
-        // its full-row GEMM)
-        const bool lnq = opt_lnq() && lp.WcqP && ((d == 768 && (fr_pays(M) || (g_lnq_min_rows > 0 && rows_cls >= g_lnq_min_rows))) ||
-                                              (d == 1024 && fr_pays_64(M)));
         {
             ProfScope ps(m, s, DITTO_KC_ATTN_SELF);
             AttnArgs a{};
@@ -401,10 +302,9 @@ static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv
         }
         if (ch.tap_self) HIP_TRY(hipMemcpyAsync(ch.tap_self, h, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
         // ---- cross-attention (src/components/DiT.py:141-148), K/V from the per-utterance cache ----
-        if (lnq) {
+        if (fp.lnq) {   // norm2 + q-projection in one launch (gemm_lnq.hip); else LayerNorm launch + tiled GEMM
             ProfScope ps(m, s, DITTO_KC_GEMM_QPROJ);
-            const int shape = d == 768 ? opt_lnq() : 32;
-            HIP_TRY(launch_gemm_lnq(h, d, hb, lp.g2, lp.be2, shape == 16 ? lp.WcqP32 : lp.WcqP, lp.bcq, qkv, d, M, d, shape,
+            HIP_TRY(launch_gemm_lnq(h, d, hb, lp.g2, lp.be2, fp.lnq == 16 ? lp.WcqP32 : lp.WcqP, lp.bcq, qkv, d, M, d, fp.lnq,
                                     lay.rot_period(64), s));
         } else {
             {
@@ -441,8 +341,7 @@ static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv
             GemmArgs g{};
             g.A = u; g.lda = dp; g.W = lp.Wco; g.bias = lp.bco; g.residual = h; g.ldr = d; g.out = h; g.ldo = d;
             g.M = M; g.N = d; g.K = dp;
-            const int nso = fp8 ? 1 : small_batch_k_splits_outproj(M, dp);
-            if (nso > 1 && ws.splitk && ws.splitk_bytes >= (size_t)nso * M * d * 4) {
+            if (const int nso = fp.ns_out; nso > 1) {
                 // low-latency class: K-splits + a finish that adds bias + residual AND writes norm3 (into qkv: u is the A operand)
                 g.bias = nullptr; g.residual = nullptr; g.out = ws.splitk; g.k_splits = nso; g.split_stride = (size_t)M * d;
                 HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
@@ -482,16 +381,14 @@ static int run_block(ditto_model* m, int l, const Ws& ws, const char* kv, int kv
             g.A = act; g.lda = 4 * d; g.W = lp.W2; g.bias = lp.b2; g.residual = h; g.ldr = d; g.out = h; g.ldo = d;
             g.M = M; g.N = d; g.K = 4 * d; g.fp8 = fp8; g.wscale = fp8 ? lp.s2 : nullptr;
             void* out2 = ch.xcat ? ch.xcat + (size_t)d * 2 : nullptr;   // bf16(h_L) for proj_out
-            const int ns = fp8 ? 1 : small_batch_k_splits(M, d, 4 * d);
-            if (ns > 1 && ws.splitk && ws.splitk_bytes >= (size_t)ns * M * d * 4) {
+            if (const int ns = fp.ns_fc2; ns > 1) {
                 g.bias = nullptr; g.residual = nullptr; g.out = ws.splitk; g.k_splits = ns;
                 g.split_stride = (size_t)M * d;
                 HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
-                // (ch.next_g1 set: the finish also writes the NEXT block's norm1 into u — ditto_forward decided it, chain_ll)
+                // (ch.next_g1 set: the finish also writes the NEXT block's norm1 into u — the plan's chain_ll)
                 HIP_TRY(launch_splitk_finish(ws.splitk, ns, (size_t)M * d, lp.b2, h, h, out2, 2 * d, M, d, s, ch.next_g1, ch.next_be1,
                                              ch.next_g1 ? u : nullptr, d));
             } else {
-                if (ch.next_g1) return fail(DITTO_ERR_ARG, "internal: norm1 chaining without a kernel that writes it");
                 if (out2) { g.out2_bf16 = out2; g.ldo2 = 2 * d; }
                 HIP_TRY(launch_gemm(g, EPI_BIAS_RES_F32, s));
             }
@@ -618,11 +515,10 @@ int ditto_model_create(const ditto_config* cfg, const ditto_weights* w, void* ar
                                hipMemcpyDeviceToDevice, s));
         HIP_TRY(launch_pack_bf16(lw.cross_out_proj_weight, A + q.Wco, d, d, d, 0, BIG, 1, 0, s));
         }   // !pad
-        const bool fr_o = !pad && ((d == 768 && !fp8) || d == 1024), fr_2 = !pad && (d == 768 || d == 1024) && !fp8;   // as plan_arena
-        const bool lnq_w = !pad && ((d == 768 && !fp8) || d == 1024);
-        if (fr_o) HIP_TRY(launch_pack_bf16_stage_major(lw.cross_out_proj_weight, A + q.WcoP, d, d, s));
-        if (fr_2) HIP_TRY(launch_pack_bf16_stage_major(lw.mlp_fc2_weight, A + q.W2P, d, 4 * d, s));
-        if (lnq_w) {   // from the PACKED q-projection (it carries the folded scale * log2(e))
+        const StagePacks have = stage_packs(*cfg);
+        if (have.o) HIP_TRY(launch_pack_bf16_stage_major(lw.cross_out_proj_weight, A + q.WcoP, d, d, s));
+        if (have.fc2) HIP_TRY(launch_pack_bf16_stage_major(lw.mlp_fc2_weight, A + q.W2P, d, 4 * d, s));
+        if (have.lnq) {   // from the PACKED q-projection (it carries the folded scale * log2(e))
             HIP_TRY(launch_repack_bf16_stage_major(A + q.Wcq, A + q.WcqP, d, d, s, 16));
             if (d == 768) HIP_TRY(launch_repack_bf16_stage_major(A + q.Wcq, A + q.WcqP32, d, d, s, 32));
         }
@@ -641,9 +537,9 @@ int ditto_model_create(const ditto_config* cfg, const ditto_weights* w, void* ar
         lp.bqkv = (const float*)(A + q.bqkv); lp.bcq = (const float*)(A + q.bcq); lp.bco = (const float*)(A + q.bco);
         lp.b1g = (const float*)(A + q.b1g); lp.b2 = (const float*)(A + q.b2);
         lp.sqkv = (const float*)(A + q.sqkv); lp.s1g = (const float*)(A + q.s1g); lp.s2 = (const float*)(A + q.s2);
-        if (fr_o) lp.WcoP = A + q.WcoP;
-        if (fr_2) lp.W2P = A + q.W2P;
-        if (lnq_w) { lp.WcqP = A + q.WcqP; lp.WcqP32 = d == 768 ? A + q.WcqP32 : nullptr; }
+        if (have.o) lp.WcoP = A + q.WcoP;
+        if (have.fc2) lp.W2P = A + q.W2P;
+        if (have.lnq) { lp.WcqP = A + q.WcqP; lp.WcqP32 = d == 768 ? A + q.WcqP32 : nullptr; }
         lp.g1 = (const float*)(A + q.g1); lp.be1 = (const float*)(A + q.be1); lp.g2 = (const float*)(A + q.g2);
         lp.be2 = (const float*)(A + q.be2); lp.g3 = (const float*)(A + q.g3); lp.be3 = (const float*)(A + q.be3);
     }
@@ -812,26 +708,9 @@ static int forward_impl(const char* who, ditto_model_t m, const float* x, const 
     const Ws ws = slice_ws(w, wsb.p);
     const char* kv = (const char*)cond;
     const float* tmod = (const float*)(kv + lay.tmod_offset(c));
-    // fc2 on the full-row kernel also emits the NEXT block's norm1 (fr_mask bit 1): that block then skips its LayerNorm
-    const bool fp8c = (c.flags & DITTO_CFG_FP8_LINEAR) != 0;
-    const bool chain_ln1 = (opt_fr_mask() & 2) && !fp8c && m->layers[0].W2P && fr_fc2_ok(M, d);
-    // bf16 residual stream ("residual_bf16"): only where EVERY consumer of h has the bf16 form — d = 768, head_dim 64, both fused
-    // launches of a block on gemm_frd.hip (the full-row class); any other launch keeps the fp32 stream
-    const bool hb_class = opt_resid_bf16() && !fp8c && d == 768 && d / c.num_heads == 64 && chain_ln1 && (opt_fr_mask() & 1) &&
-                          m->layers[0].WcoP && fr_outproj_ok(M, d) &&
-                          (g_fr_tile == 130 || (g_fr_tile == 0 && fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M) == 130));
-    // (only gemm_frd.hip has the bf16 form: a launch of fewer than 128 rows under a PINNED class would run the 64-row kernel)
-    if (hb_class && M < 128)
-        return fail(DITTO_ERR_SHAPE, "kernel class pinned to a batch of %d rows (bf16 residual stream on the 128-row full-row kernel), "
-                                     "but this launch has %d rows: it cannot take that class.  Give every shard at least 128 rows, or "
-                                     "ditto_set_option(\"residual_bf16\", 0).", opt_class_rows(), M);
-    const bool hb = hb_class;
-    // low-latency class: fc2 runs split over K and its finish launch also writes the next block's norm1 (the same bits as the
-    // LayerNorm launch it replaces); decided exactly as run_block will decide the split
-    const int ns_fc2 = fp8c ? 1 : small_batch_k_splits(M, d, 4 * d);
-    const bool chain_ll = !chain_ln1 && (g_ll_mask & 1) && ns_fc2 > 1 && ws.splitk_bytes >= (size_t)ns_fc2 * M * d * 4;
-    // block 0's norm1 rides in the GlobalAdaLN kernel (same statistics order as the LayerNorm kernel: the same bits)
-    const bool ln1_in_adaln = !fp8c && !(g_gemm_flags & 32768);      // gemm_flags bit 15: A/B, the separate launch
+    ForwardPlan fp;   // the kernel class of every launch below, and its two class errors, before anything is enqueued
+    if (int rc = plan_forward(c, M, ws.splitk_bytes, PLAN_FORWARD, &fp)) return rc;
+    const bool hb = fp.hb, ln1_in_adaln = fp.ln1_in_adaln;
     {   // GlobalAdaLN (src/components/DiT.py:25-40) + bf16 copy of the raw input for proj_in
         ProfScope ps(m, s, DITTO_KC_ADALN);
         const float *g1 = ln1_in_adaln ? m->layers[0].g1 : nullptr, *be1 = ln1_in_adaln ? m->layers[0].be1 : nullptr;
@@ -843,21 +722,20 @@ static int forward_impl(const char* who, ditto_model_t m, const float* x, const 
             HIP_TRY(launch_adaln(x, m->ttab, tmod, t, c.diffusion_steps, ws.h, ws.xcat, 2 * d, lay.B, lay.N, d, s, hb, g1, be1, u1));
         }
     }
-    const bool chain = chain_ln1 || chain_ll;
+    const bool chain = fp.chain_ln1 || fp.chain_ll;
     for (int l = 0; l < L; ++l) {
         BlockChain ch;
         ch.ln1_done = l > 0 ? chain : ln1_in_adaln;
         if (chain && l + 1 < L) { ch.next_g1 = m->layers[l + 1].g1; ch.next_be1 = m->layers[l + 1].be1; }
-        ch.hb = hb; ch.xcat = l == L - 1 ? ws.xcat : nullptr;
-        if (int rc = run_block(m, l, ws, kv, l, rope, lay, ch, s)) return rc;
+        ch.xcat = l == L - 1 ? ws.xcat : nullptr;
+        if (int rc = run_block(m, l, ws, kv, l, rope, lay, fp, ch, s)) return rc;
     }
     {   // eps = proj_in(x_raw) + proj_out(h_L)  (src/model/DiTTO.py:83,93-94), one K = 2d GEMM
         ProfScope ps(m, s, DITTO_KC_GEMM_FINAL);
         GemmArgs g{};
         g.A = ws.xcat; g.lda = 2 * d; g.W = m->Wfin; g.bias = m->bfin; g.out = eps_out; g.ldo = d; g.M = M; g.N = d;
         g.K = 2 * d;
-        const int ns = small_batch_k_splits(M, d, 2 * d);
-        if (ns > 1 && ws.splitk_bytes >= (size_t)ns * M * d * 4) {
+        if (const int ns = fp.ns_fin; ns > 1) {
             float* part = ws.splitk;
             g.bias = nullptr; g.out = part; g.k_splits = ns; g.split_stride = (size_t)M * d;
             HIP_TRY(launch_gemm(g, EPI_BIAS_F32, s));
@@ -943,7 +821,9 @@ int ditto_block_forward_taps(ditto_model_t m, int layer, float* h, const void* c
     if (workspace_bytes < w.total) return fail(DITTO_ERR_SIZE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
     Ws ws = slice_ws(w, workspace); ws.h = h;
     BlockChain ch; ch.tap_self = tap_self; ch.tap_cross = tap_cross;
-    return run_block(m, layer, ws, (const char*)cond, cond_layer, {rope_cos, rope_sin}, BatchLayout::dense(B, N, T), ch, (hipStream_t)stream);
+    ForwardPlan fp;   // a lone block: no norm1 chain, the fp32 stream
+    if (int rc = plan_forward(c, B * N, ws.splitk_bytes, PLAN_BLOCK, &fp)) return rc;
+    return run_block(m, layer, ws, (const char*)cond, cond_layer, {rope_cos, rope_sin}, BatchLayout::dense(B, N, T), fp, ch, (hipStream_t)stream);
 }
 
 size_t ditto_global_adaln_scratch_bytes(int B, int d, int time_dim, int text_dim) {
@@ -2502,16 +2382,10 @@ int ditto_full_row_plan_opts(const ditto_config* cfg, int B, int N, const ditto_
         if (int rc = check_cfg(cfg)) return rc;
         if (!outproj || !fc2 || B <= 0 || N <= 0) return fail(DITTO_ERR_ARG, "bad argument to ditto_full_row_plan");
         if ((long long)B * N > 0x7fffffffLL) return fail(DITTO_ERR_SHAPE, "B * N exceeds 2^31 - 1 rows");
-        const int d = cfg->hidden_dim, M = B * N;
-        const bool fp8c = (cfg->flags & DITTO_CFG_FP8_LINEAR) != 0;          // plan_arena packs the stage-major copies for these:
-        if (int rc = check_class_pin(M, d, fp8c, !cfg_padded(*cfg))) return rc;   // what the forward itself would answer
-        const bool padc = cfg_padded(*cfg);                                   // padded heads: the tiled path only
-        const bool have_o = !padc && ((d == 768 && !fp8c) || d == 1024), have_2 = !padc && (d == 768 || d == 1024) && !fp8c;
-        *outproj = have_o && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
-        *fc2 = have_2 && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
-        if (stream_bf16)   // ditto_forward's hb_class
-            *stream_bf16 = opt_resid_bf16() && !fp8c && d == 768 && d / cfg->num_heads == 64 && *outproj && *fc2 && M >= 128 &&
-                           (g_fr_tile == 130 || (g_fr_tile == 0 && fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M) == 130));
+        ForwardPlan fp;   // the forward's own plan (the scratch-dependent K-splits are not part of the answer)
+        if (int rc = plan_forward(*cfg, B * N, 0, PLAN_QUERY, &fp)) return rc;
+        *outproj = fp.fr_out; *fc2 = fp.fr_fc2;
+        if (stream_bf16) *stream_bf16 = fp.hb;
         return DITTO_OK;
     });
 }

@@ -267,17 +267,9 @@ int ditto_train_attach(ditto_model_t m, const ditto_weights* w, void* train_aren
 // the self-attention epilogue, read and written by the two full-row launches, read by the LayerNorms and by the LayerNorm
 // backward — and the self-attention's output O as bf16 beside h1 (second half of its fp32-sized slot: the backward's
 // delta = rowsum(dO . O) needs O, and the difference of two bf16 rows is not it).  Exactly where the inference forward has the
-// stream (ditto_api.hip hb_class): d = 768, head_dim 64, both fused launches on gemm_frd.hip; and with du travelling as bf16.
+// stream: d = 768, head_dim 64, both fused launches on gemm_frd.hip; and with du travelling as bf16 (forward_plan.hip, PLAN_TRAIN).
 // Decided ONCE per step, by the forward, and recorded in the handle against the tape's address (ditto_model::tapes): the backward
 // reads the tape as it was written, whatever the options say by then.
-static bool train_stream_bf16(ditto_model_t m, int M) {
-    const ditto_config& c = m->cfg;
-    const int d = c.hidden_dim;
-    if ((g_train_flags & (8 | 16)) || (g_attn_flags & 8192) || d != 768 || d / c.num_heads != 64) return false;
-    if (!m->layers[0].WcoP || !m->layers[0].W2P || (opt_fr_mask() & 3) != 3) return false;
-    return fr_outproj_ok(M, d) && fr_fc2_ok(M, d) && fr_launch_kernel(M, d) == 130 && fr_launch_kernel(M, 4 * d) == 130;
-}
-
 int ditto_train_forward(ditto_model_t m, const float* x, const float* text, const int64_t* t, int B, int N, int T,
                         const float* rope_cos, const float* rope_sin, float dropout_p, uint64_t seed, float* eps_out,
                         void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, ditto_stream_t stream) {
@@ -332,7 +324,10 @@ static int train_forward_impl(const char* who, ditto_model_t m, const float* x, 
     }
     if (packed) HIP_TRY(launch_text_mod_packed(text, lay.cu_t, Mt, T, m->wx, m->bx, pooled, tmod, B, c.text_dim, d, s));
     else HIP_TRY(launch_text_mod(text, m->wx, m->bx, pooled, tmod, B, T, c.text_dim, d, s));
-    const bool hb = train_stream_bf16(m, M);
+    // As in the inference forward, fr_out and fr_fc2 also write norm3 / the next norm1: into the tape slots the backward reads (u3, u1)
+    ForwardPlan fp;
+    if (int rc = plan_forward(c, M, 0, PLAN_TRAIN, &fp)) return rc;
+    const bool hb = fp.hb, fr_out = fp.fr_out, fr_fc2 = fp.fr_fc2;
     int32_t *utt = packed ? (int32_t*)(ws + wp.utt) : nullptr, *pos = packed ? (int32_t*)(ws + wp.pos) : nullptr;
     {   // a tape whose forward fails half-way must not look written: drop any older record of this address now, record at the end
         std::lock_guard<std::mutex> lk(m->tape_mu);
@@ -349,12 +344,6 @@ static int train_forward_impl(const char* who, ditto_model_t m, const float* x, 
     else
         HIP_TRY(launch_adaln(x, m->ttab, tmod, t, c.diffusion_steps, hs(0), xcat, 2 * d, B, N, d, s));
 
-    // As in the inference forward (ditto_api.hip run_block): from 160 row tiles on, the cross out-projection + norm3 and
-    // fc2 + the next block's norm1 run on the full-row kernel (fr_mask); the LayerNorm outputs land in the tape slots the
-    // backward reads (u3, the next block's u1).
-    const bool fr_have = d == 768 && m->layers[0].WcoP != nullptr && m->layers[0].W2P != nullptr;
-    const bool fr_out = fr_have && (opt_fr_mask() & 1) && fr_outproj_ok(M, d);
-    const bool fr_fc2 = fr_have && (opt_fr_mask() & 2) && fr_fc2_ok(M, d);
     const int fr_rot = lay.rot_period(128);
     for (int l = 0; l < L; ++l) {
         const LayerPack& lp = m->layers[l];

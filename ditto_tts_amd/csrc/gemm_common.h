@@ -505,8 +505,7 @@ hipError_t launch_gemm_fr64(const FrParams& fp, hipStream_t s);
 hipError_t launch_gemm_frd(const FrParams& fp, hipStream_t s);
 bool gemm_fr64_supports(int M, int N, int K, size_t lda, size_t ldw);   // N = 768 or 1024
 // The two full-row launches of a DiT block over M rows of width d, each judged on the operand strides IT runs with (the
-// kernel builds 32-bit byte offsets from M * lda: fc2 reads A at lda = 4d).  One predicate for the inference forward, the
-// LayerNorm chaining decision and the training forward, so that the three cannot disagree.
+// kernel builds 32-bit byte offsets from M * lda: fc2 reads A at lda = 4d).  Read by plan_forward (forward_plan.hip) alone.
 // d = 768: launch_gemm_fr's choice of gemm_frd.hip or gemm_fr64.hip; d = 1024: gemm_fr64.hip only.
 inline bool fr_outproj_ok(int M, int d) {
     if (d == 1024) return fr_pays_64(M) && gemm_fr64_supports(M, d, d, (size_t)d, (size_t)d);
@@ -514,7 +513,7 @@ inline bool fr_outproj_ok(int M, int d) {
 }
 inline bool fr_fc2_ok(int M, int d) {
     if (d == 1024)   // (not where the tiled fc2 runs whole rounds of 256 x 256 tiles: kernels.h gemm256_whole_rounds; by CLASS rows)
-        return fr_pays_64(M) && !gemm256_whole_rounds(opt_class_rows() > 0 ? opt_class_rows() : M, d, 4 * d) &&
+        return fr_pays_64(M) && !gemm256_whole_rounds(class_rows(M), d, 4 * d) &&
                gemm_fr64_supports(M, d, 4 * d, (size_t)4 * d, (size_t)4 * d);
     return fr_pays(M) && gemm_fr_supports(M, d, 4 * d, (size_t)4 * d, (size_t)4 * d);
 }

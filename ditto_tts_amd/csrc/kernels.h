@@ -113,6 +113,7 @@ inline int opt_class_rows() { return t_opts.class_rows >= 0 ? t_opts.class_rows 
 inline int opt_fr_mask() { return t_opts.fr_mask >= 0 ? t_opts.fr_mask : g_fr_mask; }
 inline int opt_resid_bf16() { return t_opts.resid_bf16 >= 0 ? t_opts.resid_bf16 : g_resid_bf16; }
 inline int opt_lnq() { return t_opts.lnq >= 0 ? t_opts.lnq : g_lnq; }
+inline long class_rows(long M) { return opt_class_rows() > 0 ? opt_class_rows() : M; }   // the rows every class rule judges a launch of M rows by
 // Which N = 768 full-row kernel a batch of `rows` rows takes, 0 = none (the tiled GEMMs + LayerNorm launches).  Measured in the
 // model at C2 shapes, tools/step_ab.py --batch b with the class pinned (ms per step, unfused / 64-row / 128-row direct):
 //   b = 10: 4.68 / 4.85 / 5.18   11: 5.78 / 5.34 / 5.65   12: 5.78 / 5.37   13: 6.15 / 5.73 / 6.01   14: 6.73 / 6.19 / 6.55
@@ -142,7 +143,7 @@ inline int fr_rule_rows(int rows) {
     if (t64 >= 176 && ((rows + 255) / 256) * 4 != 256) return 64;
     return 0;
 }
-inline bool fr_pays(int M) { return fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M) != 0; }
+inline bool fr_pays(int M) { return fr_rule_rows(class_rows(M)) != 0; }
 
 // gemm.hip's tile rule for narrow outputs (N < 2048, not a multiple of 192): the 256 x 256 persistent kernel where its tiles make
 // whole rounds of the 256 CUs.  Also read by fr_fc2_ok (gemm_common.h): at d = 1024 that GEMM + a LayerNorm launch beats the
@@ -154,10 +155,7 @@ inline bool gemm256_whole_rounds(int M, int N, int K) {
 }
 
 // d = 1024 runs the 64-row kernel only (gemm_fr64.hip, one workgroup per CU): it needs three quarters of the CUs busy.
-inline bool fr_pays_64(int M) {
-    const int rows = opt_class_rows() > 0 ? opt_class_rows() : M;
-    return (rows + 63) / 64 >= 192;
-}
+inline bool fr_pays_64(int M) { return (class_rows(M) + 63) / 64 >= 192; }
 
 extern int g_train_flags;   // gemm.hip: training-step A/B switches: bit 0 = the rotation's backward as its own pass (not in the dq / dk epilogues), bit 1 = fc2 dgrad and gated backward as two launches, bit 2 = training forward's gated GEMM on the general epilogue
 extern int g_fr_dgrad;   // gemm.hip: training backward, long-K dgrads on the full-row kernel: bit 0 fc1|gate (K = 8d), bit 1 QKV (K = 3d)
@@ -175,7 +173,7 @@ extern int g_fr64_maxk;
 inline int fr_launch_kernel(int M, int K) {
     int k = g_fr_tile;
     if (k == 0) {
-        k = fr_rule_rows(opt_class_rows() > 0 ? opt_class_rows() : M);
+        k = fr_rule_rows(class_rows(M));
         if (k == 0) k = 130;
     } else if (k == 64 && K > g_fr64_maxk) {
         k = 130;

@@ -70,16 +70,34 @@ ArenaPlan plan_arena(const ditto_config& c);
 inline int cfg_dhp(const ditto_config& c) { const int dh = c.hidden_dim / c.num_heads; return (dh + 63) / 64 * 64; }
 inline int cfg_dp(const ditto_config& c) { return c.num_heads * cfg_dhp(c); }
 inline bool cfg_padded(const ditto_config& c) { return cfg_dp(c) != c.hidden_dim; }
+// Which stage-major bf16 weight copies a model has (plan_arena, ditto_model_create and plan_forward read it): the full-row kernels'
+// of the cross out-projection (o) and fc2, gemm_lnq.hip's of the cross q-projection.  None on padded heads; d == 768: bf16 linears
+// only; d == 1024: the out- and q-projection are bf16 GEMMs in the fp8 configuration too.
+struct StagePacks { bool o, fc2, lnq; };
+inline StagePacks stage_packs(const ditto_config& c) {
+    const bool fp8 = (c.flags & DITTO_CFG_FP8_LINEAR) != 0, wide = !cfg_padded(c) && (c.hidden_dim == 768 || c.hidden_dim == 1024);
+    return {wide && (c.hidden_dim == 1024 || !fp8), wide && !fp8, wide && (c.hidden_dim == 1024 || !fp8)};
+}
 
 struct WsPlan { size_t h, u, qkv, act, xcat, eps, attn, attn_bytes, splitk, splitk_bytes, utt, pos, total; };   // utt, pos: a packed batch's int32 row maps (0: none)
-// K-splits of a long-K, few-tile GEMM [M, N] x K at small batch (1 = none): ditto_api.hip
-int small_batch_k_splits(int M, int N, int K);
-int small_batch_k_splits_outproj(int M, int K);
 WsPlan plan_ws(const ditto_config& c, int B, int N, int T);
 int check_cfg(const ditto_config* c);
 void set_wgrad_wgs(int v);   // ditto_train.hip: split-K target of the wgrad GEMMs (ditto_set_option("wgrad_wgs"))
 int get_wgrad_wgs();
-int check_class_pin(int M, int d, bool fp8, bool has_fr);   // ditto_api.hip: a pinned full-row class that this launch cannot take -> error
+
+// The kernel class of ONE forward, decided once (forward_plan.hip) and only read by the code that launches (ditto_api.hip
+// forward_impl / run_block, ditto_train.hip) or answers for it (ditto_full_row_plan_opts)
+struct ForwardPlan {
+    bool fr_out, fr_fc2, hb;          // cross out-projection + norm3 / fc2 + the next norm1 on the full-row kernels; h holds BF16 rows
+    int lnq;                          // norm2 + q-projection in one launch, with this MFMA shape (32 / 16); 0 = LayerNorm launch + tiled GEMM
+    bool q_split;                     // the QKV GEMM's last 256 columns as a second launch ("qkv_split")
+    int ns_out, ns_fc2, ns_fin;       // K-splits of the tiled out-projection, fc2 and final projection (1 = none; they fit the scratch)
+    bool chain_ln1, chain_ll;         // a block's norm1 is written by the previous block's full-row fc2 / by its split-K finish
+    bool ln1_in_adaln;                // block 0's norm1 rides in the GlobalAdaLN kernel
+};
+enum PlanFor { PLAN_FORWARD, PLAN_BLOCK, PLAN_QUERY, PLAN_TRAIN };   // who asks: plan_forward lists what each is answered differently
+int plan_forward(const ditto_config& c, int M, size_t splitk_bytes, PlanFor who, ForwardPlan* out);
+extern int g_splitk_wgs, g_ll_mask, g_lnq_min_rows, g_qkv_split;   // forward_plan.hip: the options only the plan reads
 
 // ditto_call_opts (ABI 9): validated by check_call_opts, then in force for the length of ONE call through a CallScope on the
 // calling thread (kernels.h t_opts); fields left at -1 inherit what is in force around the call (an enclosing

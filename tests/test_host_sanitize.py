@@ -1,5 +1,6 @@
-"""Host-side sanitizer pass.  The HOST code of the three files that do the plan / arena /
-workspace offset arithmetic and the argument validation — csrc/ditto_api.hip, csrc/ditto_train.hip, csrc/slp.hip — is
+"""Host-side sanitizer pass.  The HOST code of the files that do the plan / arena /
+workspace offset arithmetic and the argument validation — csrc/ditto_api.hip, csrc/ditto_train.hip, csrc/forward_plan.hip,
+csrc/slp.hip — is
 rebuilt with -fsanitize=address,undefined (device code unchanged: GPU sanitizers are not available on this pool) and
 linked with the ordinary kernel objects into tests/host_sanitize/driver.cpp, which drives every *_bytes query, the
 ditto_model_create / ditto_slp_create argument validation and the error paths over a grid of (d, L, h, B, N, T)
@@ -15,7 +16,7 @@ from ditto_tts_amd import build as B
 
 HERE = os.path.join(ROOT, "tests", "host_sanitize")
 OUT = os.path.join(ROOT, "build", "host_sanitize")
-SAN_FILES = ("ditto_api.hip", "ditto_train.hip", "slp.hip")
+SAN_FILES = ("ditto_api.hip", "ditto_train.hip", "forward_plan.hip", "slp.hip")
 SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined",
              "-fno-omit-frame-pointer", "-g", "-O1"]
 
