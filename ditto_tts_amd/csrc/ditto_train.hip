@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "../../include/ditto_text_grad.h"
 #include "batch_layout.h"
 #include "gemm_common.h"
 #include "model.h"
@@ -156,6 +157,17 @@ TrainWsPlan plan_train_ws(const ditto_config& c, int B, int N, int T, size_t M, 
     if (packed) { w.utt = take(M * 4); w.pos = take(M * 4); }
     w.total = off;
     return w;
+}
+
+// the text gradient's two buffers, behind the plain backward's `base` bytes: one layer's K|V weight rows transposed to bf16
+// [text_dim, 2d] (the dgrad GEMM's "weight") and dpooled fp32 [B, text_dim]
+struct TextGradWsPlan { size_t WkvT, dpooled, total; };
+TextGradWsPlan plan_text_grad_ws(const ditto_config& c, int B, size_t base) {
+    TextGradWsPlan p;
+    p.WkvT = al(base);
+    p.dpooled = p.WkvT + al((size_t)c.text_dim * 2 * c.hidden_dim * 2);
+    p.total = p.dpooled + al((size_t)B * c.text_dim * 4);
+    return p;
 }
 
 int check_train(const ditto_model* m) {
@@ -490,7 +502,7 @@ static int train_backward_impl(const char* who, ditto_model_t m, const ditto_wei
                                const int64_t* t, const BatchLayout& lay, const float* rope_cos, const float* rope_sin,
                                float dropout_p, uint64_t seed, const void* tape, size_t tape_bytes, const ditto_grads* grads,
                                void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
-                               int layer_from, int layer_to) {
+                               int layer_from, int layer_to, float* d_text = nullptr) {
     if (int rc = check_call_opts(opts)) return rc;
     CallScope scope(opts);
     if (int rc = check_train(m)) return rc;
@@ -508,7 +520,11 @@ static int train_backward_impl(const char* who, ditto_model_t m, const ditto_wei
     const TapePlan tp = plan_tape(c, lay);
     const TrainWsPlan wp = plan_train_ws(c, lay);
     if (tape_bytes < tp.total) return fail(DITTO_ERR_SIZE, "tape too small: %zu < %zu", tape_bytes, tp.total);
-    if (workspace_bytes < wp.total) return fail(DITTO_ERR_SIZE, "train workspace too small: %zu < %zu", workspace_bytes, wp.total);
+    // the text gradient (d_text given: packed batches, ditto_train_backward_packed_text_layers) keeps its two buffers BEHIND the plain
+    // backward's workspace, so that a step without it plans, sizes and launches exactly what it always did
+    const TextGradWsPlan xp = plan_text_grad_ws(c, B, wp.total);
+    const size_t ws_need = d_text ? xp.total : wp.total;
+    if (workspace_bytes < ws_need) return fail(DITTO_ERR_SIZE, "train workspace too small: %zu < %zu", workspace_bytes, ws_need);
     hipStream_t s = (hipStream_t)stream;
     const int d = c.hidden_dim, L = c.num_layers, H = c.num_heads, dhd = d / H, M = lay.M, Mt = lay.Mt, td = c.time_dim;
     const float scale = 1.0f / sqrtf((float)dhd);
@@ -600,6 +616,7 @@ static int train_backward_impl(const char* who, ditto_model_t m, const ditto_wei
 
     // ---- eps = [bf16(x) | bf16(h_L)] Wfin^T + (b_in + b_out)   (src/model/DiTTO.py:83,93-94) ----
     if (layer_from == L - 1) {   // the head of the backward belongs to the call that starts at the top layer
+    if (d_text) HIP_TRY(hipMemsetAsync(d_text, 0, (size_t)Mt * c.text_dim * 4, s));   // the layers below accumulate into it
     HIP_TRY(launch_cast_bf16(grad_eps, dyb, (size_t)M * d, s));
     HIP_TRY(launch_colsum_f32(grad_eps, d, M, d, grads->proj_in_bias, red, s));
     HIP_TRY(hipMemcpyAsync(grads->proj_out_bias, grads->proj_in_bias, (size_t)d * 4, hipMemcpyDeviceToDevice, s));
@@ -662,6 +679,16 @@ static int train_backward_impl(const char* who, ditto_model_t m, const ditto_wei
         HIP_TRY(launch_colsum_bf16(dkv, 2 * d, Mt, 2 * d, G.cross_in_proj_bias + d, red, s));
         TRY_RC(wgrad(big1, d, d, tb + q.u2, d, d, M, G.cross_in_proj_weight));
         TRY_RC(wgrad(dkv, 2 * d, 2 * d, tb + tp.text, c.text_dim, d, Mt, G.cross_in_proj_weight + (size_t)d * d));
+        if (d_text) {
+            // d_text += dkv Wkv: the transpose of the forward's K/V projection of bf16(text) (K|V rows of the fp32 master weight,
+            // transposed to bf16 [text_dim, 2d] for this layer), accumulated in fp32 through the residual epilogue, in layer order
+            char* WkvT = ws + xp.WkvT;
+            HIP_TRY(launch_pack_bf16_t(w->layers[l].cross_in_proj_weight + (size_t)d * d, WkvT, 2 * d, c.text_dim, 2 * d, 1 << 30, 1, 0, s));
+            GemmArgs g{};
+            g.A = dkv; g.lda = 2 * d; g.W = WkvT; g.residual = d_text; g.ldr = c.text_dim; g.out = d_text; g.ldo = c.text_dim;
+            g.M = Mt; g.N = c.text_dim; g.K = 2 * d;
+            HIP_TRY(launch_gemm(g, EPI_BIAS_RES_F32, s));
+        }
         TRY_RC(dgrad(big1, d, lt.WcqT, d, du, !du_bf16));
         du_is_bf16 = du_bf16;
         TRY_RC(ln_back(h1, lp.g2, G.norm2_weight, G.norm2_bias, nullptr));
@@ -719,6 +746,11 @@ static int train_backward_impl(const char* who, ditto_model_t m, const ditto_wei
         HIP_TRY(hipMemsetAsync(grads->t_embedding_weight, 0, (size_t)c.diffusion_steps * td * 4, s));
         HIP_TRY(launch_embedding_scatter_add(de0, t, grads->t_embedding_weight, B, c.diffusion_steps, td, s));
     }
+    if (d_text) {   // the AdaLN text pool: tmod[b] = Wx silu(mean_rows text_b) + bx; added last, after the layers' terms
+        float* dpooled = (float*)(ws + xp.dpooled);
+        HIP_TRY(launch_small_linear_bwd_x(dmod, w->ada_text_mlp_weight, pooled, dpooled, B, c.text_dim, 2 * d, true, s));
+        HIP_TRY(launch_text_pool_bwd_packed(dpooled, lay.cu_t, d_text, B, Mt, T, c.text_dim, s));
+    }
 #undef TRY_RC
     return DITTO_OK;
 }
@@ -740,6 +772,28 @@ int ditto_train_backward_packed_layers(ditto_model_t m, const ditto_weights* w, 
     return train_backward_impl("ditto_train_backward_packed_layers", m, w, grad_eps, x, t,
                                BatchLayout::packed(B, S, max_N, S_T, max_T, cu_speech, cu_text), rope_cos, rope_sin, dropout_p, seed,
                                tape, tape_bytes, grads, workspace, workspace_bytes, stream, opts, layer_from, layer_to);
+}
+
+size_t ditto_train_workspace_bytes_packed_text(const ditto_config* cfg, int B, int S, int max_N, int S_T, int max_T) {
+    const size_t plain = ditto_train_workspace_bytes_packed(cfg, B, S, max_N, S_T, max_T);
+    return plain ? plan_text_grad_ws(*cfg, B, plain).total : 0;
+}
+int ditto_train_backward_packed_text_layers(ditto_model_t m, const ditto_weights* w, const float* grad_eps, const float* x,
+                                            const int64_t* t, const int32_t* cu_speech, const int32_t* cu_text, int B, int S, int max_N,
+                                            int S_T, int max_T, const float* rope_cos, const float* rope_sin, float dropout_p,
+                                            uint64_t seed, const void* tape, size_t tape_bytes, const ditto_grads* grads,
+                                            void* workspace, size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts,
+                                            int layer_from, int layer_to, float* d_text, size_t d_text_bytes) {
+    const char* who = "ditto_train_backward_packed_text_layers";
+    if (!m || !w || !w->layers) return fail(DITTO_ERR_ARG, "%s: null model or weights", who);
+    if (!d_text) return fail(DITTO_ERR_ARG, "%s: null d_text (ditto_train_backward_packed_layers is the backward without a text gradient)", who);
+    if ((uintptr_t)d_text % 16) return fail(DITTO_ERR_ARG, "%s: d_text must be 16-byte aligned", who);
+    if (B <= 0 || S_T <= 0) return fail(DITTO_ERR_SHAPE, "%s: B and S_T must be positive", who);
+    if (d_text_bytes < (size_t)S_T * m->cfg.text_dim * 4)
+        return fail(DITTO_ERR_SIZE, "%s: d_text too small: %zu < %zu bytes", who, d_text_bytes, (size_t)S_T * m->cfg.text_dim * 4);
+    return train_backward_impl(who, m, w, grad_eps, x, t, BatchLayout::packed(B, S, max_N, S_T, max_T, cu_speech, cu_text), rope_cos,
+                               rope_sin, dropout_p, seed, tape, tape_bytes, grads, workspace, workspace_bytes, stream, opts, layer_from,
+                               layer_to, d_text);
 }
 
 int ditto_train_tape_forget(ditto_model_t m, const void* tape) {

@@ -496,4 +496,14 @@ hipError_t launch_small_linear_bwd_x(const float* dy, const float* W, const floa
 hipError_t launch_embedding_scatter_add(const float* drows, const int64_t* ids, float* dtable, int B, int V, int d,
                                         hipStream_t s);
 
+// ---------------- text_grad.hip : the text side of training for classifier-free guidance (include/ditto_text_grad.h) ----------------
+// d_text [S_T, dt] += dpooled[b] / T_b on the rows [cu_t[b], cu_t[b+1]) (clamped as launch_text_mod_packed's pool reads them)
+hipError_t launch_text_pool_bwd_packed(const float* dpooled, const int32_t* cu_t, float* d_text, int B, int S_T, int max_T, int dt,
+                                       hipStream_t s);
+// condition dropout over the device table [cu_out (B + 1) | cu_text (B + 1) | drop (B)]: forward and backward, one launch each
+hipError_t launch_text_select_packed(const float* text, const float* null_rows, const int32_t* table, float* text_eff, int B, int S_T,
+                                     int S_out, int T0, int dt, hipStream_t s);
+hipError_t launch_text_select_packed_bwd(const float* d_text_eff, const int32_t* table, float* d_text, float* d_null, int B, int S_T,
+                                         int S_out, int T0, int dt, hipStream_t s);
+
 }  // namespace ditto

@@ -15,6 +15,9 @@ from .varlen import doubled_cu_seqlens, validate_cu_seqlens, validate_lengths
 from .config import DiTTOConfig
 
 
+TEXT_GRAD_KEY = "<text_emb>"      # train_backward_packed(text_grad=True): the text gradient's key beside the state_dict names (none of them)
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -905,22 +908,56 @@ class DenoiseEngine:
         return out, state
 
     def train_backward_packed(self, state: Mapping[str, torch.Tensor], grad_eps, st, opts: Optional[hip.CallOpts] = None,
-                              piece_cb=None, layers_per_piece: int = 1) -> Dict[str, torch.Tensor]:
+                              piece_cb=None, layers_per_piece: int = 1, text_grad: bool = False) -> Dict[str, torch.Tensor]:
         """Backward of train_forward_packed (`st`: its second result): fp32 gradients keyed by the reference state_dict names.
         `piece_cb`: as train_backward — pieces of `layers_per_piece` layers, top first (ditto_train_backward_packed_layers),
-        bit-identical to the single call."""
+        bit-identical to the single call.
+        `text_grad`: the gradient with respect to the text rows too, fp32 [S_T, text_dim] under the key TEXT_GRAD_KEY
+        (ditto_train_backward_packed_text_layers: the same parameter gradients, bit for bit; it is no piece of `piece_cb`'s).
+        False: the call as it was — the same entry, workspace and launches."""
         g = self._f32(grad_eps, "grad_output")
         if tuple(g.shape) != (st["S"], self.cfg.hidden_dim):
             raise ValueError(f"grad_output: [{st['S']}, {self.cfg.hidden_dim}] expected, got {list(g.shape)}")
-        ws = self._grow_ws(self.lib.ditto_train_workspace_bytes_packed(C.byref(self._ccfg), st["B"], st["S"], st["max_N"], st["S_T"],
-                                                                       st["max_T"]), "_train_ws")
+        size = self.lib.ditto_train_workspace_bytes_packed_text if text_grad else self.lib.ditto_train_workspace_bytes_packed
+        ws = self._grow_ws(size(C.byref(self._ccfg), st["B"], st["S"], st["max_N"], st["S_T"], st["max_T"]), "_train_ws")
         c, s = st["rope"]
         tape = st["tape"]
-        return self._train_backward(
-            state, None, "ditto_train_backward_packed_layers", g,
+        d_text = torch.empty(st["S_T"], self.cfg.text_dim, dtype=torch.float32, device=self.device) if text_grad else None
+        grads = self._train_backward(
+            state, None, "ditto_train_backward_packed_text_layers" if text_grad else "ditto_train_backward_packed_layers", g,
             (st["xf"].data_ptr(), st["tt"].data_ptr(), st["cu"].data_ptr(), st["cu_t"].data_ptr(), st["B"], st["S"], st["max_N"],
              st["S_T"], st["max_T"], c.data_ptr(), s.data_ptr(), st["dropout_p"], st["seed"], tape.data_ptr(), tape.numel()),
-            ws, opts, piece_cb, layers_per_piece)
+            ws, opts, piece_cb, layers_per_piece, after=(d_text.data_ptr(), d_text.numel() * 4) if text_grad else ())
+        if text_grad:
+            grads[TEXT_GRAD_KEY] = d_text
+        return grads
+
+    # ---- condition dropout (classifier-free guidance training): every utterance's text is its own rows or the null embedding's
+    def text_select_packed(self, text: torch.Tensor, null_rows: torch.Tensor, table: torch.Tensor, S_out: int):
+        """ditto_text_select_packed: text fp32 [S_T, dt], null_rows fp32 [T0, dt], `table` CPU int32 [3B + 2]
+        (varlen.cond_dropout_layout) -> (text_eff fp32 [S_out, dt], the table on the device, for the backward)."""
+        B = (int(table.numel()) - 2) // 3
+        tdev = table.to(self.device)
+        out = torch.empty(S_out, text.shape[1], dtype=torch.float32, device=self.device)
+        hip.check(hip.call("ditto_text_select_packed", text=text.data_ptr(), text_bytes=text.numel() * 4, null_rows=null_rows.data_ptr(),
+                           null_rows_bytes=null_rows.numel() * 4, table=tdev.data_ptr(), table_bytes=tdev.numel() * 4,
+                           table_host=table.data_ptr(), table_host_bytes=table.numel() * 4, text_eff=out.data_ptr(),
+                           text_eff_bytes=out.numel() * 4, B=B, S_T=int(text.shape[0]), S_out=int(S_out), T0=int(null_rows.shape[0]),
+                           dt=int(text.shape[1]), stream=_stream()))
+        return out, tdev
+
+    def text_select_packed_bwd(self, d_text_eff: torch.Tensor, table: torch.Tensor, table_dev: torch.Tensor, S_T: int, T0: int):
+        """ditto_text_select_packed_bwd: d_text_eff fp32 [S_out, dt] -> (d_text fp32 [S_T, dt], d_null fp32 [T0, dt])"""
+        g = self._f32(d_text_eff, "grad_output")
+        B, dt = (int(table.numel()) - 2) // 3, int(g.shape[1])
+        d_text = torch.empty(S_T, dt, dtype=torch.float32, device=self.device)
+        d_null = torch.empty(T0, dt, dtype=torch.float32, device=self.device)
+        hip.check(hip.call("ditto_text_select_packed_bwd", d_text_eff=g.data_ptr(), d_text_eff_bytes=g.numel() * 4,
+                           table=table_dev.data_ptr(), table_bytes=table_dev.numel() * 4, table_host=table.data_ptr(),
+                           table_host_bytes=table.numel() * 4, d_text=d_text.data_ptr(), d_text_bytes=d_text.numel() * 4,
+                           d_null=d_null.data_ptr(), d_null_bytes=d_null.numel() * 4, B=B, S_T=int(S_T), S_out=int(g.shape[0]),
+                           T0=int(T0), dt=dt, stream=_stream()))
+        return d_text, d_null
 
     def train_forward(self, x, text_emb, t, dropout_p: float, seed: int, opts: Optional[hip.CallOpts] = None):
         """DiTTO.forward in train mode: returns (eps fp32 [B,N,d], tape).  The library records against the tape how it wrote it
@@ -961,10 +998,10 @@ class DenoiseEngine:
             (xf.data_ptr(), tt.data_ptr(), B, N, T, c.data_ptr(), s.data_ptr(), float(dropout_p), int(seed), tape.data_ptr(),
              tape.numel()), ws, opts, piece_cb, layers_per_piece)
 
-    def _train_backward(self, state, plain, layers, g, mid, ws, opts, piece_cb, layers_per_piece):
+    def _train_backward(self, state, plain, layers, g, mid, ws, opts, piece_cb, layers_per_piece, after=()):
         """The backward of either layout.  `plain`: the name of the whole backward's entry (through _call; None: the layers entry
         over every layer), `layers`: the name of the entry that takes a layer range, `mid`: the layout's own arguments, between
-        grad_output and the gradient struct."""
+        grad_output and the gradient struct, `after`: the entry's arguments behind the layer range (the text gradient's buffer)."""
         L = self.cfg.num_layers
         w, keep = self._struct(state)
         no_grad = ("rotary_inv_freq",)
@@ -980,7 +1017,7 @@ class DenoiseEngine:
             if plain is not None:
                 self._call(plain, *args, opts=opts)
             else:
-                hip.check(getattr(self.lib, layers)(*args, o, L - 1, 0))
+                hip.check(getattr(self.lib, layers)(*args, o, L - 1, 0, *after))
             if piece_cb is not None:
                 # a frozen pre-ABI-9 library (DITTO_HIP_LIB) has no entry that takes a layer range: one call, then every tensor as
                 # one piece (the caller's exchange then simply runs after the backward instead of under it)
@@ -992,7 +1029,7 @@ class DenoiseEngine:
         hi = L - 1
         while hi >= 0:
             lo = max(hi - step + 1, 0)
-            hip.check(getattr(self.lib, layers)(*args, o, hi, lo))
+            hip.check(getattr(self.lib, layers)(*args, o, hi, lo, *after))
             piece = [grads[k] for k in head] if hi == L - 1 else []
             piece += [grads[f"blocks.{l}.{k}"] for l in range(hi, lo - 1, -1) for k in hip.LAYER_KEY.values()]
             if lo == 0:

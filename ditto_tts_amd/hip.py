@@ -233,6 +233,13 @@ TRAIN_ROWS_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params
 _ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in TRAIN_ROWS_PROTOTYPES.items()})
 SMALL_LINEAR_FWD, SMALL_LINEAR_BWD_W, SMALL_LINEAR_BWD_X = range(3)   # the `mode` of ditto_bwd_small_linear
 
+# The text side of training for classifier-free guidance — the packed backward with the text gradient, condition dropout's select
+# forward and backward (include/ditto_text_grad.h, csrc/text_grad.hip, csrc/ditto_train.hip): a fourth table, built and bound the same way.
+with open(os.path.join(INCLUDE, "ditto_text_grad.h")) as _f:
+    TEXT_GRAD_PROTOTYPES = parse_prototypes(_f.read())
+TEXT_GRAD_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in TEXT_GRAD_PROTOTYPES.items()}
+_ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in TEXT_GRAD_PROTOTYPES.items()})
+
 
 class OptimSeg(C.Structure):
     """ditto_optim_seg: one parameter tensor of the optimizer's device table, 72 bytes."""
@@ -273,7 +280,8 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
         frozen = bool(os.environ.get("DITTO_HIP_LIB"))   # a diagnostic or FROZEN earlier build for same-box A/Bs (tools/):
-        for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items(), *TRAIN_ROWS_SYMBOLS.items()):   # it may predate entries added since (then absent)
+        for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items(), *TRAIN_ROWS_SYMBOLS.items(),
+                                  *TEXT_GRAD_SYMBOLS.items()):   # it may predate entries added since (then absent)
             try:
                 fn = getattr(l, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:
@@ -298,7 +306,8 @@ def call(name: str, **kw) -> int:
     parameter, raised before the library is entered."""
     order = _ORDER.get(name)
     if order is None:
-        header = "ditto_optim.h" if name.startswith("ditto_optim_") else "ditto_train_rows.h" if name.startswith("ditto_bwd_") else "ditto_hip.h"
+        header = "ditto_optim.h" if name.startswith("ditto_optim_") else "ditto_train_rows.h" if name.startswith("ditto_bwd_") else \
+            "ditto_text_grad.h" if name.startswith("ditto_text_select_") else "ditto_hip.h"
         raise TypeError(f"{name}: include/{header} declares no such entry")
     if len(kw) != len(order) or not all(p in kw for p in order):
         missing, unknown = [p for p in order if p not in kw], [p for p in kw if p not in order]

@@ -17,6 +17,10 @@ path unchanged: `model.train()`, `loss.backward()`, any torch optimizer over `mo
 reach every live parameter; `blocks.i.attn.out_proj.*` get none (dead in the reference too), and neither do `x`
 and `text_emb` (frozen-encoder outputs in the reference) — asking for those raises.  The standalone
 `DiT` / `GlobalAdaLN` modules stay forward-only.
+
+Training for classifier-free guidance: `DiTTO.train_forward_packed` (and the padded `train_forward` over it) does produce the
+gradient of `text_emb`, and takes `null_text_emb=` / `drop=` — condition dropout with a learned null embedding, whose rows the
+guided samplers take as `null_text_emb=`.
 """
 from __future__ import annotations
 
@@ -26,9 +30,9 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .varlen import validate_cu_seqlens, validate_lengths
+from .varlen import cond_dropout_layout, validate_cu_seqlens, validate_lengths
 from .config import DiTTOConfig
-from .engine import DenoiseEngine, TextCond, _stream, require_fused_attention
+from .engine import TEXT_GRAD_KEY, DenoiseEngine, TextCond, _stream, require_fused_attention
 from .synth import cosine_betas
 
 
@@ -48,15 +52,18 @@ def _refuse_autograd(module: nn.Module):
 class _DiTTOTrainFn(torch.autograd.Function):
     """The trainable forward of either layout with its tape, and its backward.  `run(opts)` runs the layout's engine forward and
     returns (eps, backward, release): backward(state, grad_output, piece_cb=, layers_per_piece=) is the engine's backward over
-    what that forward left (tape, inputs, options), release() hands the tape back.  `who`: the DiTTO method the caller used."""
+    what that forward left (tape, inputs, options), release() hands the tape back.  `who`: the DiTTO method the caller used.
+    `text`: the text rows `run` feeds the forward, as a differentiable input (packed batches: backward(..., text_grad=True) is asked
+    for their gradient when autograd needs it), or None (the dense layout, which produces none)."""
 
     @staticmethod
-    def forward(ctx, model, who, run, keys, *params):
+    def forward(ctx, model, who, run, keys, text, *params):
         # the options in force where forward() is CALLED (a hip.batch_class / hip.call_opts scope of this thread) are this
         # step's options: autograd runs backward() on its own worker thread, where no such scope exists, so they travel with `run`
         out, ctx.run_backward, ctx.release_tape = run(hip.current_opts() if hip._has_call_opts() else None)
         ctx.model, ctx.who, ctx.keys = model, who, keys
         ctx.sig = model._watch.sig
+        ctx.text_dtype = None if text is None else text.dtype
         return out
 
     @staticmethod
@@ -68,9 +75,11 @@ class _DiTTOTrainFn(torch.autograd.Function):
             raise RuntimeError(f"backward through the same {ctx.who} twice (the activation tape was released)")
         sd = {k: v for k, v in model.state_dict(keep_vars=True).items() if not k.startswith("nac.")}
         sync = getattr(model, "_grad_sync", None)      # dist.GradSync: the gradient exchange overlapped with this backward
+        # the text gradient only when autograd has a use for it: without, the backward is the call it always was
+        want_text = {"text_grad": True} if ctx.text_dtype is not None and ctx.needs_input_grad[4] else {}
         try:
             grads = ctx.run_backward(sd, grad_out, piece_cb=sync.reduce if sync is not None else None,
-                                  layers_per_piece=getattr(model, "_grad_sync_layers", 1))
+                                  layers_per_piece=getattr(model, "_grad_sync_layers", 1), **want_text)
         except BaseException:
             if sync is not None:
                 sync.abort()                           # no stale tensors in the next step's buckets
@@ -79,7 +88,30 @@ class _DiTTOTrainFn(torch.autograd.Function):
             sync.finish()                              # the compute stream waits for the exchange: the gradients returned are the means
         ctx.release_tape()
         ctx.run_backward = ctx.release_tape = None
-        return (None,) * (len(ctx.needs_input_grad) - len(ctx.keys)) + tuple(grads.get(k) for k in ctx.keys)
+        d_text = grads.get(TEXT_GRAD_KEY)
+        if d_text is not None and d_text.dtype != ctx.text_dtype:
+            d_text = d_text.to(ctx.text_dtype)
+        return (None,) * 4 + (d_text,) + tuple(grads.get(k) for k in ctx.keys)
+
+
+class _CondDropoutFn(torch.autograd.Function):
+    """Condition dropout over a packed batch: the effective text [S_T', text_dim] — every utterance's own rows, or the null embedding's
+    when dropped — by one launch of ditto_text_select_packed, and its backward by one of ditto_text_select_packed_bwd: kept rows'
+    gradients are copies, dropped utterances' text rows get exact zeros, and the null rows the sum over the dropped utterances in
+    ascending order (no atomics: the same bits every time)."""
+
+    @staticmethod
+    def forward(ctx, eng, text, null_rows, table, S_out):
+        out, tdev = eng.text_select_packed(eng._f32(text, "text_emb"), eng._f32(null_rows, "null_text_emb"), table, S_out)
+        ctx.eng, ctx.table, ctx.table_dev = eng, table, tdev
+        ctx.shape = (int(text.shape[0]), int(null_rows.shape[0]), text.dtype, null_rows.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        S_T, T0, text_dtype, null_dtype = ctx.shape
+        d_text, d_null = ctx.eng.text_select_packed_bwd(g, ctx.table, ctx.table_dev, S_T, T0)
+        return None, d_text.to(text_dtype), d_null.to(null_dtype), None, None
 
 
 class _ParamWatch:
@@ -383,22 +415,35 @@ class DiTTO(nn.Module):
 
     @staticmethod
     def _refuse_input_grads(x, text_emb):
+        """(packed training produces text_emb's gradient: train_forward_packed passes x for both)"""
         if torch.is_grad_enabled() and (x.requires_grad or text_emb.requires_grad):
             raise NotImplementedError("ditto_tts_amd: gradients with respect to x / text_emb are not produced (the "
                                       "reference feeds frozen-encoder outputs, src/TrainDiTTO.py:66-73); detach them")
 
+    @staticmethod
+    def condition_dropout_mask(B: int, p_uncond: float, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """Who trains unconditionally this step: a CPU bool tensor [B], True with probability `p_uncond` per utterance, drawn from
+        torch's CPU generator (`generator`, else the default one: torch.manual_seed reproduces it, as it does the cross-attention
+        dropout seed).  The `drop=` of train_forward_packed / train_forward."""
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError(f"B: a positive int is needed, got {B!r}")
+        if not 0.0 <= float(p_uncond) <= 1.0:
+            raise ValueError(f"p_uncond: a probability in [0, 1] is needed, got {p_uncond!r}")
+        return torch.rand(B, generator=generator) < float(p_uncond)
+
     def _live_params(self):
         return [(n, p) for n, p in self.named_parameters() if not n.startswith("nac.") and ".attn.out_proj." not in n]
 
-    def _train(self, x, named, who, step):
+    def _train(self, x, named, who, step, text=None):
         """The trainable forward of either layout under autograd (`named`: _live_params(); `who`: the calling method, for
-        messages).  step(eng, p_drop, seed, opts) runs the engine's training forward and returns what _DiTTOTrainFn's `run` does."""
+        messages).  step(eng, p_drop, seed, opts) runs the engine's training forward and returns what _DiTTOTrainFn's `run` does.
+        `text`: the text rows `step` feeds it, when their gradient can be produced (packed batches)."""
         # cross-attention dropout is active in train mode only (nn.MultiheadAttention(dropout=0.1),
         # reference src/components/DiT.py:90-91); its mask seed comes from torch's CPU generator
         p_drop = float(self.blocks[0].cross_attn.dropout) if self.training else 0.0
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p_drop > 0 else 0
         out = _DiTTOTrainFn.apply(self, who, lambda opts: step(self.engine(x.device, train=True), p_drop, seed, opts),
-                                  tuple(n for n, _ in named), *[p for _, p in named])
+                                  tuple(n for n, _ in named), text, *[p for _, p in named])
         return out if x.dtype == torch.float32 else out.to(x.dtype)
 
     # ------------------------------------------------------------------ reference surface
@@ -446,17 +491,29 @@ class DiTTO(nn.Module):
         out = eng.forward_packed(x, cond, t, cu_seqlens, max_seqlen)
         return out if x.dtype == torch.float32 else out.to(x.dtype)
 
-    def train_forward_packed(self, x, cu_seqlens, text_emb, text_cu_seqlens, t, *, max_seqlen=None, max_text_seqlen=None):
+    def train_forward_packed(self, x, cu_seqlens, text_emb, text_cu_seqlens, t, *, null_text_emb=None, drop=None, max_seqlen=None,
+                             max_text_seqlen=None):
         """The TRAINABLE forward over a packed batch (arguments and validation of forward_packed): eps [S, d] attached to autograd.
         Utterance b's rows are what forward(x[cu[b]:cu[b+1]][None], text_emb[cu_t[b]:cu_t[b+1]][None], t[b:b+1]) gives under
         autograd for it alone — attention over its own keys, the AdaLN text pool over its own text rows, RoPE from its own first row,
         cross-attention dropout (train mode) from the counter hash at utterance-local indices — and backward() leaves in every live
         parameter's .grad the gradient of the caller's loss over the S rows (no padding row exists: F.mse_loss(eps, noise_packed)
-        is the mean over real elements).  No gradient for x / text_emb or `.attn.out_proj.*`, as forward.  head_dim 64, bf16
-        linears."""
+        is the mean over real elements).  No gradient for x or `.attn.out_proj.*`, as forward.  head_dim 64, bf16 linears.
+        `text_emb.requires_grad` is served: text_emb.grad [S_T, text_dim] arrives from backward() — per layer dkv_l Wkv_l, and the
+        AdaLN pool's dpooled[b] / T_b on every row of utterance b — summed in a fixed order (the same bits every time) and without
+        changing one bit of a parameter's gradient.
+        CONDITION DROPOUT (training for classifier-free guidance): `null_text_emb` [T0, text_dim] — usually an nn.Parameter the caller
+        owns and hands its optimizer; it is not registered here, the state_dict keys stay the reference's — and `drop`, a sequence or
+        CPU bool tensor [B] (condition_dropout_mask draws one); both or neither.  A dropped utterance runs with the T0 null rows as
+        its text: its own K/V, its own pool over T0 rows, its own cross-attention dropout stream; null_text_emb.grad is the sum over
+        the dropped utterances, in utterance order, and their rows of text_emb.grad are exactly 0.  The trained rows are what
+        stream.submit(null_text_emb=...) takes, and sample_guided_packed(null_text_emb=...) once per utterance (null.repeat(B, 1) with
+        null_text_cu_seqlens = the multiples of T0).  With neither, the call is what it was."""
         require_fused_attention(self.cfg, "packed batches")
         self._refuse_fp8_training()
-        self._refuse_input_grads(x, text_emb)
+        self._refuse_input_grads(x, x)      # x's gradient stays refused; text_emb's is produced below
+        if (null_text_emb is None) != (drop is None):
+            raise ValueError("train_forward_packed: null_text_emb= and drop= are given together or not at all")
         if x.dim() != 2 or text_emb.dim() != 2:
             raise ValueError("train_forward_packed: x [S, d] and text_emb [S_T, text_dim] expected")
         B = len(cu_seqlens) - 1
@@ -466,23 +523,38 @@ class DiTTO(nn.Module):
                             int(text_emb.shape[0]) if max_text_seqlen is None else int(max_text_seqlen), "text_cu_seqlens")
         if x.shape[1] != self.cfg.hidden_dim or text_emb.shape[1] != self.cfg.text_dim or tuple(t.shape) != (B,):
             raise ValueError(f"train_forward_packed: x [S, {self.cfg.hidden_dim}], text_emb [S_T, {self.cfg.text_dim}] and t [{B}] expected")
+        layout = None
+        if drop is not None:
+            if not isinstance(null_text_emb, torch.Tensor) or null_text_emb.dim() != 2 or null_text_emb.shape[1] != self.cfg.text_dim \
+                    or null_text_emb.shape[0] < 1 or not null_text_emb.dtype.is_floating_point:
+                raise ValueError(f"train_forward_packed: null_text_emb [T0 >= 1, {self.cfg.text_dim}] (floating point) expected, got "
+                                 f"{list(null_text_emb.shape) if isinstance(null_text_emb, torch.Tensor) else type(null_text_emb).__name__}")
+            layout = cond_dropout_layout(text_cu_seqlens, drop, int(null_text_emb.shape[0]))
         _require_cuda(x, "x")      # the arguments are sound: now the device (there is no CPU path)
+        text_in = text_emb.to(x.device)
+        if layout is not None:     # the effective text, its offsets and its longest utterance replace the caller's
+            text_cu_seqlens, table, max_text_seqlen = layout
+            text_in = _CondDropoutFn.apply(self.engine(x.device), text_in, null_text_emb.to(x.device), table, int(text_cu_seqlens[-1]))
 
         def step(eng, p_drop, seed, opts):
-            out, st = eng.train_forward_packed(x, cu_seqlens, text_emb.to(x.device), text_cu_seqlens, t, p_drop, seed,
+            out, st = eng.train_forward_packed(x, cu_seqlens, text_in, text_cu_seqlens, t, p_drop, seed,
                                                max_seqlen=max_seqlen, max_text_seqlen=max_text_seqlen, opts=opts)
             return (out, lambda sd, g, **pieces: eng.train_backward_packed(sd, g, st, opts=opts, **pieces),
                     lambda: eng.release_tape_packed(st["tape"]))
-        return self._train(x, self._live_params(), "DiTTO.train_forward_packed", step)
+        return self._train(x, self._live_params(), "DiTTO.train_forward_packed", step, text=text_in)
 
-    def train_forward(self, x, text_emb, t, *, speech_lengths, text_lengths):
+    def train_forward(self, x, text_emb, t, *, speech_lengths, text_lengths, null_text_emb=None, drop=None):
         """The trainable forward for a batch in the reference's padded collate (src/utils/MLS.py:136-151): x [B, N, d], text_emb
         [B, T, text_dim], utterance b valid on its first speech_lengths[b] / text_lengths[b] rows.  The valid rows are gathered into
         the packed layout, train_forward_packed runs on them, and eps [B, N, d] is scattered into zeros: padded eps rows are exactly
         0, padding contents (NaN included) reach nothing, and gradient arriving on padded rows is dropped.  Speech prompts
-        (span_noise_packed / span_loss_packed) exist in the packed layout only: pack the batch first."""
+        (span_noise_packed / span_loss_packed) exist in the packed layout only: pack the batch first.
+        `null_text_emb` / `drop`: condition dropout, passed through to train_forward_packed after packing (text_emb's gradient
+        arrives through the gather: padded text rows get zeros)."""
         require_fused_attention(self.cfg, "variable-length batches")
         self._refuse_fp8_training()
+        if (null_text_emb is None) != (drop is None):
+            raise ValueError("train_forward: null_text_emb= and drop= are given together or not at all")
         if x.dim() != 3 or text_emb.dim() != 3 or text_emb.shape[0] != x.shape[0]:
             raise ValueError("train_forward: x [B, N, d] and text_emb [B, T, text_dim] expected")
         B, N, d = x.shape
@@ -498,7 +570,8 @@ class DiTTO(nn.Module):
         trows = torch.nonzero((torch.arange(T, device=dev)[None, :] < tld[:, None]).reshape(-1)).reshape(-1)
         xp = x.reshape(B * N, d).index_select(0, rows)
         tp = text_emb.to(dev).reshape(B * T, text_emb.shape[2]).index_select(0, trows)
-        eps_p = self.train_forward_packed(xp, cu, tp, cu_t, t, max_seqlen=int(sl.max()), max_text_seqlen=int(tl.max()))
+        eps_p = self.train_forward_packed(xp, cu, tp, cu_t, t, null_text_emb=null_text_emb, drop=drop, max_seqlen=int(sl.max()),
+                                          max_text_seqlen=int(tl.max()))
         out = torch.zeros(B * N, d, dtype=eps_p.dtype, device=dev).index_copy(0, rows, eps_p)
         return out.reshape(B, N, d)
 

@@ -195,6 +195,51 @@ def cu_from_lengths(lengths) -> torch.Tensor:
     return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(lens, 0)]).to(torch.int32)
 
 
+def validate_drop(drop, B: int, name: str = "drop") -> torch.Tensor:
+    """`drop` (a list / tuple of bools or 0 / 1 ints, or a CPU bool / integer tensor) as a CPU bool tensor [B].  Anything else raises
+    ValueError — a tensor on a device included: who is dropped decides the batch's layout, on the host, before anything is allocated."""
+    if isinstance(drop, torch.Tensor):
+        if drop.device.type != "cpu":
+            raise ValueError(f"{name}: a CPU tensor is needed (the host lays the batch out), got one on {drop.device}")
+        if drop.dtype.is_floating_point or drop.dtype.is_complex:
+            raise ValueError(f"{name}: a bool or integer tensor is needed, got {drop.dtype}")
+        t = drop.detach().to(torch.int64)
+    elif isinstance(drop, (list, tuple)):
+        if not all(isinstance(v, (bool, int)) for v in drop):
+            raise ValueError(f"{name}: a list / tuple of bools is needed")
+        t = torch.tensor([int(v) for v in drop], dtype=torch.int64)
+    else:
+        raise ValueError(f"{name}: a list, tuple or CPU bool tensor is needed, got {type(drop).__name__}")
+    if t.dim() != 1 or t.shape[0] != B:
+        raise ValueError(f"{name}: shape [{B}] expected, got {list(t.shape)}")
+    if B and (int(t.min()) < 0 or int(t.max()) > 1):
+        raise ValueError(f"{name}: every entry must be False / True (0 / 1)")
+    return t.to(torch.bool)
+
+
+def cond_dropout_layout(text_cu_seqlens, drop, T0: int):
+    """Condition dropout's layout, on the host: utterance b of a packed text batch (offsets `text_cu_seqlens` [B + 1]) keeps its own
+    rows, or — drop[b] — runs with the T0 rows of the null embedding as its text.  Returns (cu_out, table, max_T'):
+    cu_out  CPU int32 [B + 1], the offsets of the effective text (its rows: S_T' = cu_out[-1]);
+    table   CPU int32 [3B + 2] = [cu_out | text_cu_seqlens | drop], what ditto_text_select_packed and its backward read;
+    max_T'  the longest effective text.
+    A pure function of its arguments: no device, no library call."""
+    if isinstance(T0, bool) or not isinstance(T0, int) or T0 < 1:
+        raise ValueError(f"T0: the null embedding needs at least one row, got {T0!r}")
+    n = len(text_cu_seqlens) - 1
+    total = int(text_cu_seqlens[-1]) if n >= 0 and len(text_cu_seqlens) else 0
+    ct = validate_cu_seqlens(text_cu_seqlens, n, total, max(total, 1), "text_cu_seqlens").to(torch.int64)
+    if n < 1:
+        raise ValueError("text_cu_seqlens: at least one utterance is needed")
+    d = validate_drop(drop, n)
+    lens = torch.where(d, torch.full((n,), T0, dtype=torch.int64), ct[1:] - ct[:-1])
+    cu_out = torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(lens, 0)])
+    if int(cu_out[-1]) >= 2 ** 31:
+        raise ValueError(f"cond_dropout_layout: {int(cu_out[-1])} effective text rows exceed int32 offsets")
+    table = torch.cat([cu_out, ct, d.to(torch.int64)]).to(torch.int32).contiguous()
+    return cu_out.to(torch.int32), table, int(lens.max())
+
+
 def doubled_cu_seqlens(cu) -> torch.Tensor:
     """The offsets of [x; x] (classifier-free guidance: the batch followed by itself): [cu; S + cu[1:]]"""
     c = torch.as_tensor(cu).to(torch.int64)
