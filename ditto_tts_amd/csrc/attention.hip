@@ -686,10 +686,12 @@ static size_t generic_fwd_bytes(int Sq, int Skv, int dh) {   // one (batch, head
     const size_t ld = (size_t)((Skv + 63) / 64) * 64;
     return align256((size_t)Sq * ld * 4) + align256((size_t)Sq * ld * 2) + align256((size_t)dh * ld * 2);
 }
-// the generic path multiplies a CHUNK of (batch, head) pairs per launch (batched GEMMs): as many as fit 2 GiB
+// the generic path multiplies a CHUNK of (batch, head) pairs per launch (batched GEMMs): as many as fit the budget, 2 GiB unless
+// ditto_set_option("attn_generic_kib") says otherwise (TEST HOOK: a small budget makes the launchers' chunk loop run at test sizes)
+int g_attn_generic_kib = 2097152;
 static int generic_chunk(int B, int H, int Sq, int Skv, int dh) {
     const size_t one = generic_fwd_bytes(Sq, Skv, dh);
-    size_t n = ((size_t)2 << 30) / one;
+    size_t n = ((size_t)g_attn_generic_kib << 10) / one;
     if (n < 1) n = 1;
     if (n > (size_t)B * H) n = (size_t)B * H;
     return (int)n;

@@ -2212,7 +2212,7 @@ static int* option_slot(const char* name) {
         {"train_flags", &g_train_flags}, {"fr_u_fp8", &g_fr_u_fp8}, {"fr_hb", &g_fr_hb}, {"fr_tile", &g_fr_tile}, {"fr64_maxk", &g_fr64_maxk},
         {"fr_stagger", &g_fr_stagger}, {"fr_rot", &g_fr_rot}, {"pp_nb", &g_pp_nb}, {"pp_stagger", &g_pp_stagger},
         {"splitk_wgs", &g_splitk_wgs}, {"residual_bf16", &g_resid_bf16}, {"lnq", &g_lnq}, {"lnq_ring", &g_lnq_ring}, {"lnq_waves", &g_lnq_waves}, {"qkv_split", &g_qkv_split}, {"ll_mask", &g_ll_mask}, {"lnq_min_rows", &g_lnq_min_rows}, {"attn64p_min_wgs", &g_attn64p_min_wgs}, {"attn64p_min_wgs_plain", &g_attn64p_min_wgs_plain},
-        {"slp_lr_chunk", &g_slp_lr_chunk}, {"slp_last_row", &g_slp_last_row}};
+        {"slp_lr_chunk", &g_slp_lr_chunk}, {"slp_last_row", &g_slp_last_row}, {"attn_generic_kib", &g_attn_generic_kib}};
     for (auto& e : tab) if (!strcmp(name, e.n)) return e.p;
     return nullptr;
 }
@@ -2241,6 +2241,11 @@ int ditto_set_option(const char* name, int value) {
     if (!strcmp(name, "slp_last_row")) {   // ditto_slp_forward_varlen: 1 = last layer on the last rows only, 0 = composed (A/B)
         if (value != 0 && value != 1) return fail(DITTO_ERR_ARG, "slp_last_row must be 0 or 1");
         g_slp_last_row = value;
+        return DITTO_OK;
+    }
+    if (!strcmp(name, "attn_generic_kib")) {   // test hook: scratch budget of the GEMM-composed attention, KiB (attention.hip generic_chunk)
+        if (value < 1) return fail(DITTO_ERR_ARG, "attn_generic_kib must be >= 1 (default 2097152 = 2 GiB)");
+        g_attn_generic_kib = value;
         return DITTO_OK;
     }
     if (!strcmp(name, "attn_flags")) {

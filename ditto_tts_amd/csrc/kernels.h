@@ -386,7 +386,8 @@ struct AttnArgs {
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 size_t attention_workspace_bytes(int B, int H, int Sq, int Skv, int dh);
 // the GEMM-composed path's scratch at any head_dim (force_generic / causal)
-size_t attention_generic_workspace_bytes(int B, int H, int Sq, int Skv, int dh);
+size_t attention_generic_workspace_bytes(int B, int H, int Sq, int Skv, int dh);   // depends on g_attn_generic_kib
+extern int g_attn_generic_kib;   // that path's scratch budget in KiB (ditto_set_option("attn_generic_kib")), >= 1; default 2 GiB
 // ---------------- attention_slp.hip : the length predictor's variable-length attention ----------------
 // The GEMM-composed path with a.q_len / a.kv_len (device int32 [B], either may be null; values clamped to [1, Sq] / [1, Skv]):
 // a row sees min(causal rule of its own lengths, kv_len) keys, query rows at or past q_len give zero output rows, and V rows at

@@ -453,7 +453,11 @@ int ditto_gemm_tn_bf16(const void* X, int ldx, const void* Y, int ldy, float* ou
  * "ll_mask" (default 3): the other launch forms of the low-latency class, each a function of the class and of K / Skv only:
  * bit 0 = fc2's split-K finish also writes the next block's norm1 (no bit changes), bit 1 = the cross out-projection as two
  * K-splits whose finish writes norm3.  Bit 1 changes a summation order: it is part of what defines the class (pin it with
- * class_rows as usual).  (ABI 9's bit 2, split-KV attention, measured slower and was removed in ABI 10.) */
+ * class_rows as usual).  (ABI 9's bit 2, split-KV attention, measured slower and was removed in ABI 10.)
+ * "attn_generic_kib": TEST HOOK: scratch budget, in KiB, of the GEMM-composed attention (head_dim != 64, the causal entries):
+ * the path runs as many (batch, head) pairs per launch as fit it, at least one.  Default 2097152 (2 GiB); values below 1 are
+ * refused.  ditto_attention_workspace_bytes, ditto_attention_causal_workspace_bytes and the length predictor's workspace sizes
+ * follow it, so query them after setting it. */
 int ditto_set_option(const char* name, int value);
 /* Reads a switch back (callers that change one temporarily restore what they found: ditto_tts_amd/hip.py batch_class). */
 int ditto_get_option(const char* name, int* value);

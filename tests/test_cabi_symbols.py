@@ -283,6 +283,30 @@ def test_attention_kernel_thresholds_are_validated_options():
         hip.set_option("attn64p_min_wgs_plain", b)
 
 
+def test_composed_attention_budget_is_a_validated_option():
+    """"attn_generic_kib": the scratch budget of the GEMM-composed attention (default 2 GiB).  Every size query of that path follows
+    it — whole pairs that fit, at least one, at most B H — and values below 1 are refused.  Host arithmetic only: no GPU call."""
+    l = hip.lib()
+    B, H, Sq, Skv, dh = 3, 2, 40, 70, 128
+    one = 40 * 128 * 4 + 40 * 128 * 2 + 128 * 128 * 2       # fp32 scores, bf16 probabilities, V^T at Skv rounded up to 64
+    queries = (l.ditto_attention_causal_workspace_bytes, l.ditto_attention_workspace_bytes)
+    assert hip.get_option("attn_generic_kib") == 2097152
+    assert all(f(B, H, Sq, Skv, dh) == B * H * one for f in queries)
+    try:
+        for room in (5, 3, 1):
+            hip.set_option("attn_generic_kib", (room * one + 1023) // 1024)
+            assert all(f(B, H, Sq, Skv, dh) == room * one for f in queries)
+        hip.set_option("attn_generic_kib", 1)                # less than one pair: the floor of one pair stays
+        assert all(f(B, H, Sq, Skv, dh) == one for f in queries)
+        for bad in (0, -1):
+            with pytest.raises(hip.DittoHipError):
+                hip.set_option("attn_generic_kib", bad)
+        assert hip.get_option("attn_generic_kib") == 1
+    finally:
+        hip.set_option("attn_generic_kib", 2097152)
+    assert l.ditto_attention_workspace_bytes(B, H, Sq, Skv, 64) == 0     # the fused head_dim-64 kernels need none, whatever the budget
+
+
 def test_call_options_are_per_call_and_per_thread():
     """ABI 9: the switches that decide which bits an utterance gets — kernel class pin, residual-stream
     type, fused launches — are a ditto_call_opts ARGUMENT or a scope of the CALLING THREAD (ditto_call_opts_push / _pop), not
