@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "batch_layout.h"
+#include "ditto_refresh.h"
 #include "gemm_common.h"
 
 using namespace ditto;
@@ -2081,6 +2082,48 @@ int ditto_guided_step_packed_multistep_reuse_opts(ditto_model_t m, float* x2, co
     }, [&](const float* eps, int d) -> int {
         HIP_TRY(launch_multistep_update_reuse(x2, eps, q, delta, step, w, cu_speech, prompt_len, suffix_len, B, S, max_N, d, mode, mirror,
                                               (hipStream_t)stream));
+        return DITTO_OK;
+    });
+}
+
+// ---- guidance reuse in a request stream (guided_refresh.hip; include/ditto_refresh.h): a step of refreshing, reusing and plain utterances ----
+static int check_refresh(const char* who, const float* x2, const float* eps2, const float* delta, const float* noise,
+                         const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce, const float* cz,
+                         const int32_t* cu, const int32_t* partner, const int32_t* kind, int B, int G, int S, int S_G, int max_N, int d) {
+    if (!delta) return fail(DITTO_ERR_ARG, "%s: null delta (fp32 [S, d])", who);
+    if (!kind) return fail(DITTO_ERR_ARG, "%s: null kind (int32 [B])", who);
+    return check_mixed(who, x2, eps2, noise, seeds, tags, w, a, ce, cz, cu, partner, B, G, S, S_G, max_N, d);
+}
+
+int ditto_guided_update_packed_refresh(float* x2, const float* eps2, float* delta, const float* noise, const int64_t* seeds,
+                                       const uint32_t* tags, const float* w, const float* a, const float* ce, const float* cz,
+                                       const int32_t* cu, const int32_t* partner, const int32_t* kind, const int32_t* prompt_len, int B,
+                                       int G, int S, int S_G, int max_N, int d, ditto_stream_t stream) {
+    if (int rc = check_refresh("ditto_guided_update_packed_refresh", x2, eps2, delta, noise, seeds, tags, w, a, ce, cz, cu, partner, kind,
+                               B, G, S, S_G, max_N, d))
+        return rc;
+    HIP_TRY(launch_guided_update_refresh(x2, eps2, delta, noise, seeds, tags, w, a, ce, cz, cu, partner, kind, prompt_len, B, G, S, S_G,
+                                         max_N, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+// the mixed step's forward — over [x; the refreshing ones' copies] x [text; their null], over the B utterances alone when G == 0 —
+// then the three-kind update
+int ditto_guided_step_packed_refresh_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                          const int32_t* cu_text, const int32_t* partner, const int32_t* kind, const int32_t* prompt_len,
+                                          float* delta, const float* noise, const int64_t* seeds, const uint32_t* tags, const float* w,
+                                          const float* a, const float* ce, const float* cz, int B, int G, int S, int S_G, int max_N,
+                                          int S_T, int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
+                                          size_t workspace_bytes, ditto_stream_t stream, const ditto_call_opts* opts) {
+    PACKED_STEP(p, "ditto_guided_step_packed_refresh_opts");
+    return packed_step(p, [&](int d) -> int {
+        if (int rc = check_refresh(p.who, x2, x2, delta, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, kind, B, G, S, S_G, max_N, d))
+            return rc;
+        p.nb = B + G; p.rows = S + S_G;   // G <= B and S_G <= S from here on
+        return DITTO_OK;
+    }, [&](const float* eps, int d) -> int {
+        HIP_TRY(launch_guided_update_refresh(x2, eps, delta, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, kind, prompt_len, B, G, S,
+                                             S_G, max_N, d, (hipStream_t)stream));
         return DITTO_OK;
     });
 }

@@ -299,6 +299,14 @@ hipError_t launch_guided_update_mixed(float* x2, const float* eps2, const float*
                                       const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                       const int32_t* partner, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,
                                       hipStream_t s);
+// ---------------- guided_refresh.hip ----------------
+// the mixed update above for a stream that reuses the guidance direction: kind device int32 [B] — 1 refresh (the partner branch above,
+// which also keeps delta = c - u), 2 reuse (e = fmaf(w[b] - 1, delta, c), nothing behind row S touched), else plain; delta fp32 [S, d],
+// row-aligned with rows [0, S) of x2
+hipError_t launch_guided_update_refresh(float* x2, const float* eps2, float* delta, const float* noise, const int64_t* seeds,
+                                        const unsigned* tags, const float* w, const float* a, const float* ce, const float* cz,
+                                        const int32_t* cu, const int32_t* partner, const int32_t* kind, const int32_t* prompt_len, int B,
+                                        int G, int S, int S_G, int max_N, int d, hipStream_t s);
 // ---------------- span_train.hip ----------------
 // span-masked training over a packed batch: the noising that keeps the context rows (a bit copy of x0), the MSE over the generated
 // rows (n_elems of them) with its gradient (exactly 0 on the context rows); the window of launch_guided_update_packed (prompt_len,

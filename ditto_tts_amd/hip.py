@@ -240,6 +240,14 @@ with open(os.path.join(INCLUDE, "ditto_text_grad.h")) as _f:
 TEXT_GRAD_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in TEXT_GRAD_PROTOTYPES.items()}
 _ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in TEXT_GRAD_PROTOTYPES.items()})
 
+# Guidance reuse in a request stream — the three-kind update and its step (include/ditto_refresh.h, csrc/guided_refresh.hip,
+# csrc/ditto_api.hip): a fifth table, built and bound the same way.
+with open(os.path.join(INCLUDE, "ditto_refresh.h")) as _f:
+    REFRESH_PROTOTYPES = parse_prototypes(_f.read())
+REFRESH_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in REFRESH_PROTOTYPES.items()}
+_ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in REFRESH_PROTOTYPES.items()})
+KIND_PLAIN, KIND_REFRESH, KIND_REUSE = 0, 1, 2   # the `kind` of the ditto_*_refresh entries, per utterance
+
 
 class OptimSeg(C.Structure):
     """ditto_optim_seg: one parameter tensor of the optimizer's device table, 72 bytes."""
@@ -281,7 +289,7 @@ def lib() -> C.CDLL:
         l = C.CDLL(LIB_PATH)
         frozen = bool(os.environ.get("DITTO_HIP_LIB"))   # a diagnostic or FROZEN earlier build for same-box A/Bs (tools/):
         for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items(), *TRAIN_ROWS_SYMBOLS.items(),
-                                  *TEXT_GRAD_SYMBOLS.items()):   # it may predate entries added since (then absent)
+                                  *TEXT_GRAD_SYMBOLS.items(), *REFRESH_SYMBOLS.items()):   # it may predate entries added since (then absent)
             try:
                 fn = getattr(l, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:
@@ -307,7 +315,8 @@ def call(name: str, **kw) -> int:
     order = _ORDER.get(name)
     if order is None:
         header = "ditto_optim.h" if name.startswith("ditto_optim_") else "ditto_train_rows.h" if name.startswith("ditto_bwd_") else \
-            "ditto_text_grad.h" if name.startswith("ditto_text_select_") else "ditto_hip.h"
+            "ditto_text_grad.h" if name.startswith("ditto_text_select_") else \
+            "ditto_refresh.h" if "_packed_refresh" in name else "ditto_hip.h"
         raise TypeError(f"{name}: include/{header} declares no such entry")
     if len(kw) != len(order) or not all(p in kw for p in order):
         missing, unknown = [p for p in order if p not in kw], [p for p in kw if p not in order]

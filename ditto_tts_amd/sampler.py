@@ -813,7 +813,7 @@ class SpeechGenerator:
                                  rescale, prediction, refresh, begin_reuse)
 
     def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim", infill=False,
-                      prediction="eps"):
+                      prediction="eps", refresh=False):
         """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an
         utterance, step() admits what fits, runs one guided strided step over everything in flight — each utterance at its own
         index of its own strided_schedule — and returns the finished ones.  `max_rows` / `max_utterances` / `max_text_rows`: the
@@ -826,18 +826,24 @@ class SpeechGenerator:
         False: the stream as it was.
         `prediction`: "eps", or "v" — every request's per-step coefficients come from strided_schedule_v / multistep_schedule_v
         (sample_guided_packed(prediction=)); one parameterisation per stream, as a stream serves one model.  Admission, tags and
-        launches are unchanged."""
+        launches are unchanged.
+        `refresh`: the stream accepts submit(..., guidance_refresh=k) — reuse of the guidance direction between refresh steps, each
+        request on refresh_plan's schedule of its own guided steps (sample_guided_packed(guidance_refresh=)) — and holds the kept
+        directions beside the state.  A guided "ddim" stream without infill only: guided=False is a ValueError, solver="dpmpp2m"
+        and infill=True are NotImplementedError (follow-ups, like guidance_rescale with it).  False: the stream as it was.  What
+        the approximation costs in speech quality has not been measured with a trained model."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         validate_prediction(prediction)
-        from .serving import DeviceBatch, GuidedStream
+        from .serving import DeviceBatch, GuidedStream, validate_refresh_stream
+        refresh = validate_refresh_stream(refresh, bool(guided), solver, bool(infill))
         require_fused_attention(self.ditto_model.cfg, "request streams (packed batches)")
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
         batch = DeviceBatch(eng, max_rows=max_rows, max_utterances=max_utterances, max_text_rows=max_text_rows, guided=guided,
-                            class_rows=class_rows, solver=solver, infill=infill)
+                            class_rows=class_rows, solver=solver, infill=infill, refresh=refresh)
         return GuidedStream(batch, self.alphas_cumprod, max_rows=max_rows, max_utterances=max_utterances,
                             max_text_rows=max_text_rows, guided=guided, text_dim=eng.cfg.text_dim, hidden_dim=eng.cfg.hidden_dim,
-                            solver=solver, infill=infill, prediction=prediction)
+                            solver=solver, infill=infill, prediction=prediction, refresh=refresh)
 
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):

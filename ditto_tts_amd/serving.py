@@ -22,6 +22,12 @@ csrc/guided_rescale.hip in between — over a scratch sized once from the capaci
 Speech infilling (guided_stream(infill=True), submit(suffix=)): a request may carry clean rows BEHIND its generated frames as well;
 each request's suffix length rides in the step block and a step with a suffixed request in flight runs the ..._window_opts form of
 its entry (csrc/guided_packed.hip, csrc/guided_multistep.hip).  Such a stream has no guidance intervals and no guidance rescale.
+Guidance reuse (guided_stream(refresh=True), submit(guidance_refresh=k)): a request runs the unconditional forward at every k-th of
+its guided steps only and reuses the kept direction delta = c - u in between (sampler.refresh_plan, computed per request at submit).
+A step's set G is then the REFRESHING requests; the batch holds the directions in two more buffers that a regroup carries along, and
+a step with a k > 1 request in flight is ditto_guided_step_packed_refresh_opts (csrc/guided_refresh.hip): refreshing, reusing and
+plain utterances in one forward and one update.  "ddim" streams without infill; what the approximation costs in speech quality is
+not measured by anything here.
 They serve the reference's sampling loop (reference src/model/SpeechGenerator.py:130-164) to a request stream.
 """
 from __future__ import annotations
@@ -55,11 +61,14 @@ class Request:
     speech prompt that stands in front of the `n_frames` generated rows, `suffix` ([Q, d] or None) the clean rows behind them (speech
     infilling); the utterance occupies `rows` = P + n_frames + Q rows."""
     __slots__ = ("handle", "text", "null", "T", "T_null", "n_frames", "seed", "w", "n_steps", "eta", "x_T", "schedule", "i", "b",
-                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm", "phi", "suffix", "Q")
+                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm", "phi", "suffix", "Q", "kinds", "period")
 
     def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None, interval=None, phi=0.0,
-                 suffix=None):
+                 suffix=None, kinds=None, period=1):
         self.handle, self.text, self.null = handle, text, null
+        # guidance reuse: `kinds` — hip.KIND_* of every step of its schedule (refresh_plan's list; None: from guided_now()) —
+        # and the refresh `period` k it was made with (1: every guided step refreshes)
+        self.kinds, self.period = kinds, int(period)
         self.suffix, self.Q = suffix, 0 if suffix is None else int(suffix.shape[0])
         self.phi = float(phi)                        # guidance rescale: the blend factor in [0, 1]; 0 = none
         # `interval`: None, or (t_lo, t_hi) — guided only at the steps whose timestep lies in it.  `in_g`: whether the batch's current
@@ -79,6 +88,13 @@ class Request:
         """whether the step it stands at applies the guidance: always without an interval, else t_lo <= tau <= t_hi"""
         return self.interval is None or self.interval[0] <= self.schedule[self.i][0] <= self.interval[1]
 
+    def kind_now(self) -> int:
+        """hip.KIND_* of the step it stands at: plain where it is not guided, else refresh (it runs the unconditional forward and
+        keeps the direction) or reuse (guidance reuse, between two refresh steps)"""
+        if self.kinds is not None:
+            return self.kinds[self.i]
+        return hip.KIND_REFRESH if self.guided_now() else hip.KIND_PLAIN
+
     @property
     def rows(self) -> int:
         return self.P + self.n_frames + self.Q
@@ -92,12 +108,15 @@ class Plan:
     copies are compacted behind the S rows in batch order: `partner` [B] (the copy's index in [0, |G|), or -1), `cu_g` [|G| + 1] the
     copies' offsets, `offsets` = [cu; S + cu_g[1:]] and `text_offsets` = [cu_text; T + cu_null_g[1:]] what the step's forward
     reads.  The null conditioning of a member outside G is parked behind G's: `null_row` / `null_tm` [B] are each member's null K/V
-    row (counted from the T text rows) and tmod row (counted from the B text ones) — G's first, in order, then the parked ones."""
+    row (counted from the T text rows) and tmod row (counted from the B text ones) — G's first, in order, then the parked ones.
+    `kind` [B] (guidance reuse; else None): hip.KIND_* of each member's coming step — G is then the refreshing members, and a
+    survivor about to reuse takes its kept direction along."""
     __slots__ = ("members", "newcomers", "cu", "cu_text", "cu_null", "in_g", "partner", "cu_g", "offsets", "text_offsets", "null_row",
-                 "null_tm")
+                 "null_tm", "kind")
 
-    def __init__(self, members, newcomers, guided, in_g=None):
+    def __init__(self, members, newcomers, guided, in_g=None, kind=None):
         self.members, self.newcomers = list(members), list(newcomers)
+        self.kind = None if kind is None else list(kind)
         self.cu, self.cu_text = _cumulate(r.rows for r in members), _cumulate(r.T for r in members)
         self.cu_null = _cumulate(r.T_null for r in members) if guided else None
         self.in_g = self.partner = self.cu_g = self.null_row = self.null_tm = None
@@ -121,9 +140,11 @@ class StepArgs:
     utterance's (a, kx, ke, b, g, use_prev) of its own multistep_schedule; a, ce, cz and tags are then None.  Under guidance
     `in_g` [B] says who is guided at this step (each request's guided_now(), asked once), `partner` [B] is its partner_table,
     `G` the number of guided utterances and `S_G` their rows (None, None, 0, 0 unguided).  `phi` [B]: each utterance's guidance-rescale
-    blend factor (0: none).  `suffix` [B]: each utterance's suffix rows (speech infilling; 0: none)."""
+    blend factor (0: none).  `suffix` [B]: each utterance's suffix rows (speech infilling; 0: none).
+    `kind` [B] (None unguided): hip.KIND_* of each utterance's step — plain, refresh or reuse; `in_g` is kind == refresh, "has an
+    unconditional copy in this step's forward".  `period` [B]: each utterance's refresh period k (1: it never reuses)."""
     __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt", "coef", "in_g",
-                 "partner", "G", "S_G", "phi", "suffix")
+                 "partner", "G", "S_G", "phi", "suffix", "kind", "period")
 
 
 def _cumulate(lengths) -> List[int]:
@@ -146,10 +167,26 @@ def _is_int(v) -> bool:
     return isinstance(v, int) and not isinstance(v, bool)
 
 
+def validate_refresh_stream(refresh, guided: bool, solver: str, infill: bool) -> bool:
+    """`refresh` of a stream as a bool; a stream that cannot serve guidance reuse is refused here, before anything is made"""
+    if not refresh:
+        return False
+    if not guided:
+        raise ValueError("refresh=True needs a guided stream: guidance reuse keeps the direction of classifier-free guidance")
+    if solver != "ddim":
+        raise NotImplementedError(f"refresh=True is served by \"ddim\" streams; this stream's solver is {solver}: there is no mixed "
+                                  "multistep update (a follow-up)")
+    if infill:
+        raise NotImplementedError("refresh=True with infill=True: there is no mixed multistep update and the three-kind update has "
+                                  "no windowed form (a follow-up)")
+    return True
+
+
 class GuidedStream:
-    """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None, infill=False)
+    """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None, infill=False,
+                              refresh=False)
     h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None,
-                      prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None)
+                      prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None, guidance_refresh=None)
     done = stream.step()          # [(handle, latents fp32 [n_frames, d] on the GPU), ...]
     stream.pending, stream.active, stream.drain()
 
@@ -175,13 +212,22 @@ class GuidedStream:
     `guidance_interval` and `guidance_rescale` (NotImplementedError: neither update has a windowed form); with no suffixed request in
     flight it runs the entries a plain stream runs.
     `prediction` (one per stream): "eps", or "v" — the requests' coefficients come from strided_schedule_v / multistep_schedule_v
-    (sample_guided_packed(prediction="v")); nothing else changes."""
+    (sample_guided_packed(prediction="v")); nothing else changes.
+    `guidance_refresh` (a stream made with refresh=True only — guided, "ddim", no infill; None or an int k >= 1): reuse of the
+    guidance direction (sample_guided_packed(guidance_refresh=)) — the request takes part in the unconditional forward at every
+    k-th of its guided steps only and reuses the direction it kept there in between.  Its step kinds are refresh_plan of its own
+    guided steps, fixed at submit: interval-aware, the counter reset by an unguided step, the first guided step a refresh.  None
+    and 1: every guided step refreshes, the request as it was.  k > 1 with guidance_rescale > 0 raises NotImplementedError, as in
+    the closed call; so does any guidance_rescale > 0 in a refresh=True stream, where the request could share a step with a
+    reusing one.  An approximation of the guided trajectory: its effect on speech quality has not been measured."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
-                 text_dim: int, hidden_dim: int, solver: str = "ddim", infill: bool = False, prediction: str = "eps"):
+                 text_dim: int, hidden_dim: int, solver: str = "ddim", infill: bool = False, prediction: str = "eps",
+                 refresh: bool = False):
         from .sampler import SOLVERS, validate_prediction
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
+        self.refresh = validate_refresh_stream(refresh, bool(guided), solver, bool(infill))
         self.solver, self.infill = solver, bool(infill)
         self.prediction = validate_prediction(prediction)
         for name, v in (("max_rows", max_rows), ("max_utterances", max_utterances), ("max_text_rows", max_text_rows)):
@@ -225,7 +271,7 @@ class GuidedStream:
         return t.detach()
 
     def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None,
-               prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None) -> StreamHandle:
+               prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None, guidance_refresh=None) -> StreamHandle:
         """Queue one utterance.  Everything is validated here, on the host: a bad request raises ValueError and leaves the stream as
         it was; so does one that could never fit the capacities."""
         text = self._text(text_emb, "text_emb")
@@ -269,6 +315,23 @@ class GuidedStream:
                     or not 0.0 <= guidance_rescale <= 1.0):
                 raise ValueError(f"guidance_rescale: a number in [0, 1] is needed, got {guidance_rescale!r}")
             phi = float(guidance_rescale)
+        period = 1
+        if guidance_refresh is not None:
+            if not self.refresh:
+                raise ValueError("guidance_refresh= needs a stream made with refresh=True (guided_stream(refresh=True))")
+            from .sampler import validate_guidance_refresh
+            period = validate_guidance_refresh(guidance_refresh)
+            if period > 1 and phi > 0:
+                raise NotImplementedError("guidance_refresh= with guidance_rescale=: the rescale statistics need the unconditional "
+                                          "prediction at every step; a rescale that reuses the kept direction is a follow-up")
+        if self.refresh and phi > 0:                               # it could share a step with a reusing request
+            raise NotImplementedError("a stream made with refresh=True serves no guidance_rescale= > 0: the three-kind update of a step "
+                                      "with a reusing request in flight has no rescale form (a follow-up)")
+        kinds = None
+        if self.guided:                                            # the list the closed call runs: refresh_plan of its own guided steps
+            from .sampler import guided_steps, refresh_plan
+            code = {"plain": hip.KIND_PLAIN, "refresh": hip.KIND_REFRESH, "reuse": hip.KIND_REUSE}
+            kinds = [code[k] for k in refresh_plan(guided_steps(schedule, interval), period)[0]]
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)))
         elif not _is_int(seed) or not -2 ** 63 <= seed < 2 ** 63:
@@ -288,7 +351,7 @@ class GuidedStream:
                 raise ValueError(f"suffix: a floating-point tensor [Q >= 1, {self.hidden_dim}] is needed")
             suffix = suffix.detach()
         req = Request(StreamHandle(self._next_id), text, null, n_frames, seed, None if guidance is None else float(guidance), n_steps,
-                      float(eta), x_T, schedule, prompt, interval, phi, suffix)
+                      float(eta), x_T, schedule, prompt, interval, phi, suffix, kinds, period)
         if req.rows > self.max_rows:
             raise ValueError(f"a request of {req.rows} rows ({req.P} prompt + {req.n_frames} frames"
                              + (f" + {req.Q} suffix" if req.Q else "") + f") can never fit max_rows = {self.max_rows}")
@@ -318,7 +381,7 @@ class GuidedStream:
         in_g = args.in_g
         # a change of the guided set is a membership change of the unconditional region: the same one regroup serves it
         if newcomers or self._dirty or any(r.in_g != f for r, f in zip(members, in_g or ())):
-            self.batch.regroup(Plan(members, newcomers, self.guided, in_g), args)
+            self.batch.regroup(Plan(members, newcomers, self.guided, in_g, args.kind if self.refresh else None), args)
             for r, f in zip(members, in_g or ()):
                 r.in_g = f
             self._dirty = False
@@ -359,7 +422,9 @@ class GuidedStream:
             s.a = s.ce = s.cz = s.tags = None
             s.coef = [tuple(q[1:]) for q in rows]
         s.w = [r.w for r in members] if self.guided else None
-        s.in_g = [r.guided_now() for r in members] if self.guided else None
+        s.kind = [r.kind_now() for r in members] if self.guided else None
+        s.period = [r.period for r in members]
+        s.in_g = [k == hip.KIND_REFRESH for k in s.kind] if self.guided else None
         s.partner = partner_table(s.in_g) if self.guided else None
         s.G = sum(s.in_g) if self.guided else 0
         s.S_G = sum(r.rows for r, f in zip(members, s.in_g) if f) if self.guided else 0
@@ -436,6 +501,14 @@ def history_segment(r: Request, dst_row: int, d4: int) -> List[int]:
     return [hip.REGROUP_COPY, _SRC_Q, _DST_Q, 0, (r.row + r.P) * d4, (dst_row + r.P) * d4, r.n_frames * d4, 0]
 
 
+def direction_segment(r: Request, dst_row: int, d4: int) -> List[int]:
+    """The segment that carries a survivor's kept guidance direction — delta = c - u of its last refresh step, on its generated rows
+    — from the current direction buffer to row `dst_row` of the next one: for a survivor whose coming step is a reuse step.  One
+    that refreshes writes its direction anew, a plain one and a newcomer have none.  A refresh stream has no multistep history,
+    so the direction buffers take the history's source and destination slots."""
+    return [hip.REGROUP_COPY, _SRC_Q, _DST_Q, 0, (r.row + r.P) * d4, (dst_row + r.P) * d4, r.n_frames * d4, 0]
+
+
 def staged_rows(r: Request) -> int:
     """rows of the x_T staging buffer a newcomer takes: its prompt, then its own x_T, then its suffix"""
     return r.P + (r.n_frames if r.x_T is not None else 0) + _suffix_rows(r)
@@ -457,7 +530,9 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
     S + cu_g[partner[j]] through the segment's dup_off — a member entering G gets its copy from its conditional rows (the two are
     equal after any update), one leaving G just has none.  Conditioning: text K/V and tmod in batch order; null K/V and tmod at
     plan.null_row / plan.null_tm — G's rows compacted behind the texts where the forward reads them, the others parked behind G's.
-    The offsets [offsets | text_offsets] ride behind the segments in the same upload."""
+    The offsets [offsets | text_offsets] ride behind the segments in the same upload.
+    Guidance reuse (plan.kind given): G is the refreshing members, and a survivor whose coming step is a reuse step gets one more
+    segment, direction_segment."""
     guided = plan.in_g is not None
     B, S, Tt = len(plan.members), plan.cu[-1], plan.cu_text[-1]
     segs, xt_row = [], 0
@@ -469,6 +544,8 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
             xt_row += staged_rows(r)
         elif multistep:
             segs.append(history_segment(r, plan.cu[j], d4))
+        elif plan.kind is not None and plan.kind[j] == hip.KIND_REUSE:
+            segs.append(direction_segment(r, plan.cu[j], d4))
         if new:
             base, own_tmod = new_image[r.handle.id]
             source, kv_t, kv_n, tm_t, tm_n = _SRC_NEW_COND, base, base + r.T * kv16, own_tmod, own_tmod + tm16
@@ -487,12 +564,13 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
     return segs, tail
 
 
-def step_block_layout(max_utterances: int, guided: bool, multistep: bool, infill: bool = False) -> dict:
+def step_block_layout(max_utterances: int, guided: bool, multistep: bool, infill: bool = False, refresh: bool = False) -> dict:
     """Byte offsets of the per-step argument block (host arithmetic): t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w
     fp32 [maxB] | tags uint32 [maxB] | prompt_len int32 [maxB] | partner int32 [maxB] | (multistep) ditto_multistep_coef [maxB] |
     phi fp32 [maxB] — the guidance-rescale blend factors, appended behind everything else: the fields in front keep the offsets
     they had before it existed.  `infill`: suffix_len int32 [maxB] ("suffix") is appended behind phi in the same way; off (the
-    default), the layout is the one without it.  "f_stride": bytes of one fp32 / int32 field; "bytes": the whole block."""
+    default), the layout is the one without it.  `refresh`: kind int32 [maxB] ("kind", guidance reuse) is appended behind everything
+    else in the same way.  "f_stride": bytes of one fp32 / int32 field; "bytes": the whole block."""
     maxB, nbB = int(max_utterances), (2 if guided else 1) * int(max_utterances)
     lay = {"t": 0, "seeds": _pad(nbB * 8, 16)}
     o_f = lay["seeds"] + _pad(maxB * 8, 16)
@@ -504,6 +582,9 @@ def step_block_layout(max_utterances: int, guided: bool, multistep: bool, infill
     if infill:
         lay["suffix"] = lay["bytes"]
         lay["bytes"] += lay["f_stride"]
+    if refresh:
+        lay["kind"] = lay["bytes"]
+        lay["bytes"] += lay["f_stride"]
     return lay
 
 
@@ -513,11 +594,15 @@ class DeviceBatch:
     newcomers' conditioning and one for callers' x_T, the device offsets, the per-step argument block and the segment table.
     `solver` "dpmpp2m": two history buffers [max_rows, d] beside the state (double-buffered like it: a regroup moves the
     survivors' rows of both in its one launch), and the step block carries one ditto_multistep_coef per utterance.
-    `infill`: the step block carries each utterance's suffix length as well."""
+    `infill`: the step block carries each utterance's suffix length as well.
+    `refresh` (guidance reuse): two direction buffers [max_rows, d] beside the state, double-buffered like it — a regroup moves the
+    reusing survivors' rows in its one launch, through the slots the history takes in a "dpmpp2m" stream —, and the step block
+    carries each utterance's kind."""
 
     def __init__(self, engine, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool, class_rows=None,
-                 solver: str = "ddim", infill: bool = False):
+                 solver: str = "ddim", infill: bool = False, refresh: bool = False):
         from .engine import require_fused_attention
+        self.refresh = validate_refresh_stream(refresh, bool(guided), solver, bool(infill))
         require_fused_attention(engine.cfg, "request streams (packed batches)")
         self.multistep, self.infill = solver != "ddim", bool(infill)
         self.eng, self.lib, self.guided = engine, engine.lib, bool(guided)
@@ -535,6 +620,7 @@ class DeviceBatch:
         with torch.cuda.device(dev):
             self.x = [torch.zeros(self.halves * self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)]
             self.q = [torch.zeros(self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)] if self.multistep else None
+            self.delta = [torch.zeros(self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)] if self.refresh else None
             self.cond = [torch.zeros(cond_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
             # every newcomer's own image [K/V rows | tmod], 256-byte aligned, one behind the other
             self.new_cond = torch.zeros(self.maxT * self.kv_row + self.maxB * (_pad(self.halves * self.tmod_row, 256) + 256),
@@ -542,8 +628,8 @@ class DeviceBatch:
             self.x_T = torch.zeros(self.maxS, d, dtype=torch.float32, device=dev)
             self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
             self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
-            lay = step_block_layout(self.maxB, self.guided, self.multistep, self.infill)
-            self.o_suffix = lay.get("suffix")
+            lay = step_block_layout(self.maxB, self.guided, self.multistep, self.infill, self.refresh)
+            self.o_suffix, self.o_kind = lay.get("suffix"), lay.get("kind")
             self.f_stride, self.block_bytes = lay["f_stride"], lay["bytes"]
             (self.o_t, self.o_seeds, self.o_a, self.o_ce, self.o_cz, self.o_w, self.o_tags, self.o_prompt, self.o_partner, self.o_coef,
              self.o_phi) = (lay[k] for k in ("t", "seeds", "a", "ce", "cz", "w", "tags", "prompt", "partner", "coef", "phi"))
@@ -582,6 +668,8 @@ class DeviceBatch:
             buf[self.o_phi:self.o_phi + B * 4].view(np.float32)[:] = a.phi
         if self.infill:
             buf[self.o_suffix:self.o_suffix + B * 4].view(np.int32)[:] = a.suffix
+        if self.refresh:
+            buf[self.o_kind:self.o_kind + B * 4].view(np.int32)[:] = a.kind
         self.block.send(buf)
 
     def _block_ptr(self, off: int) -> int:
@@ -605,6 +693,9 @@ class DeviceBatch:
         if self.multistep:             # the history moves with the state: _SRC_Q, _DST_Q
             src.append(self.q[self.cur])
             dst.append(self.q[nxt])
+        elif self.refresh:             # so do the kept directions, in the same slots (a refresh stream has no history)
+            src.append(self.delta[self.cur])
+            dst.append(self.delta[nxt])
         n = hip.REGROUP_BUFS
         sp, sb, dp, db = (C.c_void_p * n)(), (C.c_size_t * n)(), (C.c_void_p * n)(), (C.c_size_t * n)()
         for k, t in enumerate(src):
@@ -676,7 +767,10 @@ class DeviceBatch:
         some are guided, without it when everyone is): phi from the step block, the scratch built once.
         A step with a suffixed utterance in flight (an infill stream: no intervals, no rescale) runs the window form of its entry,
         ditto_guided_step_packed_tags_window_opts or ditto_guided_step_packed_multistep_window_opts, the suffix lengths from the
-        step block; with none in flight, the entries above."""
+        step block; with none in flight, the entries above.
+        A step with a request of refresh period k > 1 in flight (a refresh stream: "ddim", no infill, no rescale beside k > 1) runs
+        ditto_guided_step_packed_refresh_opts over the B utterances and the G copies of the refreshing ones — G = 0 and G = B
+        included — with the kinds from the step block and the current direction buffer; with none in flight, the entries above."""
         if not self._block_sent:
             self._send_block(a)
         self._block_sent = False
@@ -700,6 +794,11 @@ class DeviceBatch:
             else:
                 hip.check(hip.call("ditto_guided_step_packed_tags_window_opts", **args, prompt_len=prompt, suffix_len=at(self.o_suffix),
                                    **noise, w=at(self.o_w) if cfg else None, **coef, B=a.B, S=a.S, cfg=int(cfg)))
+            return
+        if self.refresh and any(k > 1 for k in a.period):
+            hip.check(hip.call("ditto_guided_step_packed_refresh_opts", **args, partner=at(self.o_partner), kind=at(self.o_kind),
+                               prompt_len=prompt, delta=self.delta[self.cur].data_ptr(), **noise, w=at(self.o_w), **coef, B=a.B, G=a.G,
+                               S=a.S, S_G=a.S_G))
             return
         if cfg and any(p > 0 and g for p, g in zip(a.phi, a.in_g)):
             rescale = dict(phi=at(self.o_phi), scratch=self.rescale.data_ptr(), scratch_bytes=self.rescale.numel())

@@ -818,7 +818,10 @@ int ditto_span_vloss_window(const float* pred, const float* x0, const float* noi
  *   LOAD: the forward over the B conditional utterances alone — x2's first S rows, cu_speech [B + 1], cond over the text only (S_T and
  *     max_T its own), t int64 [B], workspace ditto_packed_workspace_bytes(cfg, B, S, S_T).
  * Traffic of the update per generated element: STORE 4 B more than the cfg = 1 update; LOAD 16 B (x, c, delta read, x' written: 4 B
- *   more than the cfg = 0 update) + 4 B with a noise buffer + 4 B with mirror + 8 B multistep history. */
+ *   more than the cfg = 0 update) + 4 B with a noise buffer + 4 B with mirror + 8 B multistep history.
+ * In a request stream every utterance follows its own refresh schedule: ditto_guided_update_packed_refresh and
+ *   ditto_guided_step_packed_refresh_opts serve refreshing, reusing and plain utterances in one launch, over the layout of
+ *   ditto_guided_update_packed_mixed.  They are declared and documented in include/ditto_refresh.h. */
 int ditto_guided_update_packed_reuse(float* x2, const float* eps, float* delta, const float* noise, const int64_t* seeds, uint32_t step,
                                      const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                      const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, int mode,
