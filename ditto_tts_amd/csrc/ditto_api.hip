@@ -1511,7 +1511,7 @@ static int check_rescale(const char* who, const float* eps2, const float* w, con
     if ((uintptr_t)scratch % 256) return fail(DITTO_ERR_ARG, "%s: the rescale scratch must be 256-byte aligned", who);
     if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
     if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
-    if (partner && (G < 0 || G > B || S_G < 0 || S_G > S || (G > 0) != (S_G > 0) || G > S_G))
+    if (partner && !mixed_layout_ok(B, G, S, S_G))
         return fail(DITTO_ERR_SHAPE, "%s: need 0 <= G <= B, G <= S_G <= S, and S_G == 0 exactly when G == 0 (B %d, G %d, S %d, S_G %d)",
                     who, B, G, S, S_G);
     if (scratch_bytes < rescale_bytes(B, max_N, d))
@@ -1760,7 +1760,7 @@ static int check_mixed(const char* who, const float* x2, const float* eps2, cons
     if (seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
     if (int rc = check_guided_update(who, x2, eps2, noise, seeds, w, a, ce, cz, B, max_N, d, 1)) return rc;
     if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
-    if (G < 0 || G > B || S_G < 0 || S_G > S || (G > 0) != (S_G > 0) || G > S_G)
+    if (!mixed_layout_ok(B, G, S, S_G))
         return fail(DITTO_ERR_SHAPE, "%s: need 0 <= G <= B, G <= S_G <= S, and S_G == 0 exactly when G == 0 (B %d, G %d, S %d, S_G %d)",
                     who, B, G, S, S_G);
     return DITTO_OK;

@@ -1,5 +1,5 @@
-// guided.hip — the fused update of one guided strided (DDIM) step over a variable-length PADDED batch (gfx950); the arithmetic, the
-// grid and the dispatch are guided_update.h's.
+// guided.hip — the fused update of one guided strided (DDIM) step over a variable-length PADDED batch (gfx950); the row loop
+// (update_rows with the DDIM line, its one PADDED user), the grid and the dispatch are guided_update.h's.
 //
 // One launch replaces the chain the strided sampler runs after each forward: two copies of x into the doubled batch,
 // cfg_combine (which also allocates), the step's N(0,1) draw, linear_update and the zeroing of padded rows.
@@ -27,11 +27,12 @@ __global__ __launch_bounds__(256) void guided_update_kernel(float* __restrict__ 
         valid4 = (size_t)nb * d / 4;
     }
     const GuidedCoef k = guided_coef<NOISE, CFG>(a, ce, cz, w, seeds, b);
-    guided_rows<NOISE, CFG, true>(reinterpret_cast<f32x4*>(x2) + (size_t)b * n4, reinterpret_cast<f32x4*>(x2) + (size_t)(B + b) * n4,
-                                  reinterpret_cast<const f32x4*>(eps2) + (size_t)b * n4,
-                                  reinterpret_cast<const f32x4*>(eps2) + (size_t)(B + b) * n4,
-                                  reinterpret_cast<const f32x4*>(noise) + (size_t)b * n4, k, step, true, n4, valid4,
-                                  blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+    f32x4 *xc = reinterpret_cast<f32x4*>(x2) + (size_t)b * n4, *xu = reinterpret_cast<f32x4*>(x2) + (size_t)(B + b) * n4;
+    const f32x4 *ec = reinterpret_cast<const f32x4*>(eps2) + (size_t)b * n4,
+                *eu = reinterpret_cast<const f32x4*>(eps2) + (size_t)(B + b) * n4;
+    const DdimLine<NOISE> ddim = {reinterpret_cast<const f32x4*>(noise) + (size_t)b * n4, k, step, true};
+    update_rows<CFG ? EPS_CFG : EPS_COND, true>(xc, xu, ec, eu, ddim, nullptr, k.w, false, n4, valid4,
+                                                blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 hipError_t launch_guided_update(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,

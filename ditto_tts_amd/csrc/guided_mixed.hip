@@ -5,9 +5,9 @@
 // offsets: what the forward over the B + G utterances reads).  partner[b]: the copy of utterance b, or -1.
 //   with a partner:  e = fmaf(w, c - u, u), u read at the copy's rows; x' goes to b's rows and to the copy's   (the CFG instantiation)
 //   without:         e = c; nothing of rows [S, S + S_G) is read or written                                     (the non-CFG one)
-// guided_update.h's arithmetic over the generated rows, tags per utterance, no draw at cz == 0 (guided_packed.hip):
-// a kernel of its own, so that those keep their machine code.  HBM traffic per generated element: 20 B guided, 12 B (+ 4 B of a
-// noise buffer) not; 0 B per prompt element.
+// guided_update.h's row loop (update_rows, EPS_CFG or EPS_COND, the DDIM line) over the generated rows, tags per utterance, no draw
+// at cz == 0 (guided_packed.hip); a launch of its own for the layout and the branch on the partner.  HBM traffic per generated
+// element: 20 B guided, 12 B (+ 4 B of a noise buffer) not; 0 B per prompt element.
 #include "guided_update.h"
 #include "kernels.h"
 
@@ -51,10 +51,10 @@ __global__ __launch_bounds__(256) void guided_update_mixed_kernel(float* __restr
     const size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
     if (g >= 0) {
         const size_t ub4 = (size_t)(u0 + p) * d4;
-        guided_rows<NOISE, true, false>(xc, reinterpret_cast<f32x4*>(x2) + ub4, ec, reinterpret_cast<const f32x4*>(eps2) + ub4, nz, k,
-                                        tag, k.cz != 0.f, n4, n4, i0, stride);
+        update_rows<EPS_CFG, false>(xc, reinterpret_cast<f32x4*>(x2) + ub4, ec, reinterpret_cast<const f32x4*>(eps2) + ub4,
+                                    DdimLine<NOISE>{nz, k, tag, k.cz != 0.f}, nullptr, k.w, false, n4, n4, i0, stride);
     } else {
-        guided_rows<NOISE, false, false>(xc, xc, ec, ec, nz, k, tag, k.cz != 0.f, n4, n4, i0, stride);
+        update_rows<EPS_COND, false>(xc, xc, ec, ec, DdimLine<NOISE>{nz, k, tag, k.cz != 0.f}, nullptr, k.w, false, n4, n4, i0, stride);
     }
 }
 
@@ -63,15 +63,14 @@ hipError_t launch_guided_update_mixed(float* x2, const float* eps2, const float*
                                       const int32_t* partner, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,
                                       hipStream_t s) {
     // (the conditions of check_mixed, ditto_api.hip, which both public entries pass through first)
-    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !partner || !w || (seeds && !tags) || G < 0 || G > B ||
-        S_G < 0 || S_G > S || (G > 0) != (S_G > 0) || G > S_G)
+    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !partner || !w || (seeds && !tags) ||
+        !mixed_layout_ok(B, G, S, S_G))
         return hipErrorInvalidValue;
     const dim3 grid = guided_grid(max_N, d, B);
-    auto go = [&](auto nz) {
+    noise_dispatch(noise, seeds, [&](auto nz) {
         hipLaunchKernelGGL((guided_update_mixed_kernel<decltype(nz)::value>), grid, dim3(256), 0, s, x2, eps2, noise, seeds, tags, w, a,
                            ce, cz, cu, partner, prompt_len, B, G, S, S_G, d);
-    };
-    seeds ? go(std::integral_constant<int, 2>{}) : noise ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 0>{});
+    });
     return hipGetLastError();
 }
 

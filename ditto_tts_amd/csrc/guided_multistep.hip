@@ -1,7 +1,8 @@
 // guided_multistep.hip — the packed guided update of the second-order multistep data-prediction solver, DPM-Solver++(2M) (Lu et al.
 // 2022), for gfx950.  One forward per step like the strided (DDIM) update; the extra state is the previous step's x0 prediction per
 // generated row, kept in a second fp32 buffer q [S, d].  Over guided_update.h's span and grid, like guided_packed.hip.
-//   e  = CFG ? fmaf(w, c - u, u) : c                       (guided_update.h's expression)
+// The row loop is guided_update.h's update_rows with its MultistepLine:
+//   e  = CFG ? fmaf(w, c - u, u) : c                       (EPS_CFG / EPS_COND)
 //   x0 = fmaf(kx, x, ke * e)                               the data prediction: kx = 1 / alpha, ke = -sigma / alpha
 //   x' = fmaf(a, x, fmaf(b, x0, use_prev ? g * q : 0))     written to the conditional and, under CFG, the unconditional half of x2
 //   q  = x0
@@ -12,31 +13,6 @@
 #include "kernels.h"
 
 namespace ditto {
-
-// quads [i0, n4) of one utterance's generated rows at a grid stride.  PREV false: q is written and never read — the first step of
-// an utterance meets an uninitialised history
-template <bool CFG, bool PREV>
-__device__ __forceinline__ void multistep_rows(f32x4* xc, f32x4* xu, const f32x4* ec, const f32x4* eu, f32x4* qp,
-                                               const ditto_multistep_coef& k, size_t n4, size_t i0, size_t stride) {
-    for (size_t i = i0; i < n4; i += stride) {
-        const f32x4 xv = xc[i];
-        const f32x4 c = ec[i];
-        f32x4 u = c;
-        if (CFG) u = eu[i];
-        f32x4 qv = {0.f, 0.f, 0.f, 0.f};
-        if (PREV) qv = qp[i];
-        f32x4 o, p;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float ev = CFG ? fmaf(k.w, c[e] - u[e], u[e]) : c[e];
-            p[e] = fmaf(k.kx, xv[e], k.ke * ev);
-            o[e] = fmaf(k.a, xv[e], fmaf(k.b, p[e], PREV ? k.g * qv[e] : 0.f));
-        }
-        xc[i] = o;
-        if (CFG) xu[i] = o;
-        qp[i] = p;
-    }
-}
 
 // PER_UTT false: every utterance stands at the step `step` (a kernel argument; its w is not used: w[b] is the guidance scale).
 // PER_UTT true: utterance b at coefs[b], guidance scale included (a request stream: each utterance at its own index of its own
@@ -61,10 +37,11 @@ __global__ __launch_bounds__(256) void multistep_update_kernel(float* __restrict
     const f32x4* ec = reinterpret_cast<const f32x4*>(eps2) + base4;
     f32x4* qp = reinterpret_cast<f32x4*>(q) + base4;
     const size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    constexpr int MODE = CFG ? EPS_CFG : EPS_COND;
     if (k.use_prev)
-        multistep_rows<CFG, true>(xc, xc + half4, ec, ec + half4, qp, k, ws.g4, i0, stride);
+        update_rows<MODE, false>(xc, xc + half4, ec, ec + half4, MultistepLine<true>{qp, k}, nullptr, k.w, false, ws.g4, ws.g4, i0, stride);
     else
-        multistep_rows<CFG, false>(xc, xc + half4, ec, ec + half4, qp, k, ws.g4, i0, stride);
+        update_rows<MODE, false>(xc, xc + half4, ec, ec + half4, MultistepLine<false>{qp, k}, nullptr, k.w, false, ws.g4, ws.g4, i0, stride);
 }
 
 hipError_t launch_multistep_update_packed(float* x2, const float* eps2, float* q, const ditto_multistep_coef* step,

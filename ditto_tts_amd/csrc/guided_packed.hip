@@ -1,6 +1,6 @@
-// guided_packed.hip — the fused update of one guided strided (DDIM) step over a PACKED batch (gfx950): guided_update.h's arithmetic
-// with the utterances concatenated along the rows instead of padded.  One kernel behind the six ditto_guided_update_packed* entries:
-// a scalar step tag or one per utterance, over the whole utterance, the rows behind a speech prompt, or an infilling window.
+// guided_packed.hip — the fused update of one guided strided (DDIM) step over a PACKED batch (gfx950): guided_update.h's row loop
+// (update_rows with the DDIM line) with the utterances concatenated along the rows instead of padded.  One kernel behind the six
+// ditto_guided_update_packed* entries: a scalar step tag or one per utterance, over the whole utterance, the rows behind a speech prompt, or an infilling window.
 #include "guided_update.h"
 #include "kernels.h"
 
@@ -30,10 +30,11 @@ __global__ __launch_bounds__(256) void guided_update_packed_kernel(float* __rest
     const size_t base4 = ws.base4 + ws.p4, half4 = (size_t)S * d / 4;
     const GuidedCoef k = guided_coef<NOISE, CFG>(a, ce, cz, w, seeds, b);
     const unsigned tag = TAGS ? (NOISE == 2 ? tags[b] : 0u) : step;
-    guided_rows<NOISE, CFG, false>(reinterpret_cast<f32x4*>(x2) + base4, reinterpret_cast<f32x4*>(x2) + half4 + base4,
-                                   reinterpret_cast<const f32x4*>(eps2) + base4, reinterpret_cast<const f32x4*>(eps2) + half4 + base4,
-                                   reinterpret_cast<const f32x4*>(noise) + base4, k, tag, TAGS ? k.cz != 0.f : true, ws.g4, ws.g4,
-                                   blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+    f32x4 *xc = reinterpret_cast<f32x4*>(x2) + base4, *xu = reinterpret_cast<f32x4*>(x2) + half4 + base4;
+    const f32x4 *ec = reinterpret_cast<const f32x4*>(eps2) + base4, *eu = reinterpret_cast<const f32x4*>(eps2) + half4 + base4;
+    const DdimLine<NOISE> ddim = {reinterpret_cast<const f32x4*>(noise) + base4, k, tag, TAGS ? k.cz != 0.f : true};
+    update_rows<CFG ? EPS_CFG : EPS_COND, false>(xc, xu, ec, eu, ddim, nullptr, k.w, false, ws.g4, ws.g4,
+                                                 blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 hipError_t launch_guided_update_packed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, unsigned step,

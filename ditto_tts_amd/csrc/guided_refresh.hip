@@ -9,8 +9,8 @@
 // The B utterances sit in rows [0, S) of x2 / eps2 and the G refreshing ones have their unconditional copies compacted behind them in
 // rows [S, S + S_G), as in guided_mixed.hip; delta fp32 [S, d] is row-aligned with rows [0, S).  guided_update.h's grid and span: grid
 // (chunks, B), 256 threads, 16-byte lane accesses, b = blockIdx.y uniform over the workgroup, d % 64 == 0; tags per utterance, no
-// Philox draw where cz[b] == 0; prompt rows of x2, eps2, delta and a noise buffer are neither read nor written.  A kernel of its own,
-// so that the mixed and the reuse kernels keep their machine code.  HBM traffic per generated element: refresh 24 B (x, c, u read; x',
+// Philox draw where cz[b] == 0; prompt rows of x2, eps2, delta and a noise buffer are neither read nor written.  The three kinds are
+// update_rows' EPS_STORE, EPS_LOAD and EPS_COND with the DDIM line.  HBM traffic per generated element: refresh 24 B (x, c, u read; x',
 // the copy and delta written), reuse 16 B (x, c, delta read; x' written), plain 12 B; + 4 B each with a noise buffer; 0 B per prompt
 // element.
 #include "guided_update.h"
@@ -19,36 +19,6 @@
 namespace ditto {
 
 enum { KIND_PLAIN = 0, KIND_REFRESH = 1, KIND_REUSE = 2 };
-
-// quads [i0, n4) of one refreshing (REFRESH true) or reusing utterance at a grid stride: guided_rows' loop with the direction kept
-// (dp written) or read back (dp read).  xu / eu: the copy's quads, REFRESH only
-template <int NOISE, bool REFRESH>
-__device__ __forceinline__ void direction_rows(f32x4* xc, f32x4* xu, const f32x4* ec, const f32x4* eu, f32x4* dp, const f32x4* nz,
-                                               const GuidedCoef& k, unsigned tag, bool draw, size_t n4, size_t i0, size_t stride) {
-    const float wm1 = k.w - 1.0f;
-    for (size_t i = i0; i < n4; i += stride) {
-        const f32x4 xv = xc[i];
-        const f32x4 c = ec[i];
-        f32x4 u = c, dl;
-        if (REFRESH) u = eu[i];
-        else dl = dp[i];
-        f32x4 zv = {0.f, 0.f, 0.f, 0.f};
-        if (NOISE == 1) zv = nz[i];
-        if (NOISE == 2 && draw) zv = normal4(k.seed, tag, i);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (REFRESH) dl[e] = c[e] - u[e];
-            const float ev = REFRESH ? fmaf(k.w, dl[e], u[e]) : fmaf(wm1, dl[e], c[e]);
-            o[e] = fmaf(k.a, xv[e], fmaf(k.ce, ev, k.cz * zv[e]));
-        }
-        xc[i] = o;
-        if (REFRESH) {
-            xu[i] = o;
-            dp[i] = dl;
-        }
-    }
-}
 
 // mixed_span's clamps (guided_update.h): b's generated rows lie inside [0, S) — so do delta's and the noise buffer's, which share
 // their offset — and a copy's inside [S, S + S_G).  A bad cu / partner / kind / prompt_len gives wrong rows, never an access outside
@@ -70,20 +40,19 @@ __global__ __launch_bounds__(256) void guided_update_refresh_kernel(float* __res
     if (kd == KIND_REFRESH && sp.g < 0) kd = KIND_PLAIN;
     const GuidedCoef k = guided_coef<NOISE, true>(a, ce, cz, w, seeds, b);
     const unsigned tag = NOISE == 2 ? tags[b] : 0u;
-    const bool draw = k.cz != 0.f;
     f32x4* xc = reinterpret_cast<f32x4*>(x2) + sp.base4;
     const f32x4* ec = reinterpret_cast<const f32x4*>(eps2) + sp.base4;
     f32x4* dp = reinterpret_cast<f32x4*>(delta) + sp.base4;
-    const f32x4* nz = reinterpret_cast<const f32x4*>(noise) + sp.base4;
+    const DdimLine<NOISE> ddim = {reinterpret_cast<const f32x4*>(noise) + sp.base4, k, tag, k.cz != 0.f};
     const size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
     if (kd == KIND_REFRESH) {
         const size_t ub4 = (size_t)sp.urow * (size_t)(d / 4);
-        direction_rows<NOISE, true>(xc, reinterpret_cast<f32x4*>(x2) + ub4, ec, reinterpret_cast<const f32x4*>(eps2) + ub4, dp, nz, k,
-                                    tag, draw, sp.n4, i0, stride);
+        update_rows<EPS_STORE, false>(xc, reinterpret_cast<f32x4*>(x2) + ub4, ec, reinterpret_cast<const f32x4*>(eps2) + ub4, ddim, dp,
+                                      k.w, false, sp.n4, sp.n4, i0, stride);
     } else if (kd == KIND_REUSE) {
-        direction_rows<NOISE, false>(xc, xc, ec, ec, dp, nz, k, tag, draw, sp.n4, i0, stride);
+        update_rows<EPS_LOAD, false>(xc, xc, ec, ec, ddim, dp, k.w, false, sp.n4, sp.n4, i0, stride);
     } else {
-        guided_rows<NOISE, false, false>(xc, xc, ec, ec, nz, k, tag, draw, sp.n4, sp.n4, i0, stride);
+        update_rows<EPS_COND, false>(xc, xc, ec, ec, ddim, dp, k.w, false, sp.n4, sp.n4, i0, stride);
     }
 }
 
@@ -92,15 +61,14 @@ hipError_t launch_guided_update_refresh(float* x2, const float* eps2, float* del
                                         const int32_t* cu, const int32_t* partner, const int32_t* kind, const int32_t* prompt_len, int B,
                                         int G, int S, int S_G, int max_N, int d, hipStream_t s) {
     // (the conditions of check_refresh, ditto_api.hip, which both public entries pass through first)
-    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !partner || !kind || !delta || !w || (seeds && !tags) || G < 0 ||
-        G > B || S_G < 0 || S_G > S || (G > 0) != (S_G > 0) || G > S_G)
+    if (d % 64 || B <= 0 || S <= 0 || max_N <= 0 || B > 65535 || !cu || !partner || !kind || !delta || !w || (seeds && !tags) ||
+        !mixed_layout_ok(B, G, S, S_G))
         return hipErrorInvalidValue;
     const dim3 grid = guided_grid(max_N, d, B);
-    auto go = [&](auto nz) {
+    noise_dispatch(noise, seeds, [&](auto nz) {
         hipLaunchKernelGGL((guided_update_refresh_kernel<decltype(nz)::value>), grid, dim3(256), 0, s, x2, eps2, delta, noise, seeds,
                            tags, w, a, ce, cz, cu, partner, kind, prompt_len, B, G, S, S_G, d);
-    };
-    seeds ? go(std::integral_constant<int, 2>{}) : noise ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 0>{});
+    });
     return hipGetLastError();
 }
 

@@ -167,7 +167,7 @@ hipError_t launch_guidance_rescale(const RescaleArgs& a, int max_N, hipStream_t 
     // (the conditions of check_rescale, ditto_api.hip, which every public entry passes through first)
     if (a.d % 64 || a.B <= 0 || a.B > 65535 || a.S <= 0 || max_N <= 0 || !a.eps2 || !a.w || !a.phi || !a.coef_in || !a.coef_out ||
         !a.scale || !a.partial || !a.cu || a.slots < 1 || a.cstride < 1 || a.koff < 0 || a.copy < 1 || a.koff >= a.copy ||
-        a.copy > 64 || (a.partner && (a.G < 0 || a.G > a.B || a.S_G < 0 || a.S_G > a.S || (a.G > 0) != (a.S_G > 0) || a.G > a.S_G)))
+        a.copy > 64 || (a.partner && !mixed_layout_ok(a.B, a.G, a.S, a.S_G)))
         return hipErrorInvalidValue;
     size_t gx = guidance_rescale_chunks(max_N, a.d);
     if (gx > (size_t)a.slots) gx = (size_t)a.slots;

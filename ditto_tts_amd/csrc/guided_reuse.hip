@@ -5,12 +5,13 @@
 // delta fp32 [S, d] is row-aligned with the conditional half.  Over guided_update.h's span and grid, like guided_packed.hip and
 // guided_multistep.hip: grid (chunks, B), 256 threads, 16-byte lane accesses, b = blockIdx.y uniform over the workgroup, d % 64 == 0;
 // the context rows of x2, eps, delta, q and a noise buffer are neither read nor written.
-//   STORE (a refresh step; eps [2S, d]):   dl = c - u,  e = fmaf(w, dl, u),  delta = dl       guided_update.h's CFG expression: x' (and
-//                                          q) get the bits of the CFG instantiations of the existing kernels, written to both halves
-//   LOAD  (a reuse step;  eps [S, d]):     e = fmaf(w - 1, delta, c)                          delta is read and never written; x' goes
+//   STORE (a refresh step; eps [2S, d]):   dl = c - u,  e = fmaf(w, dl, u),  delta = dl       update_rows' EPS_STORE, which is EPS_CFG
+//                                          with dl kept: x' (and q) have the CFG kernels' bits, written to both halves
+//   LOAD  (a reuse step;  eps [S, d]):     e = fmaf(w - 1, delta, c)                          EPS_LOAD: delta is read and never written; x' goes
 //                                          to the conditional half and, with the run-time `mirror`, to the row + S of the other
-// then the DDIM line x' = fmaf(a, x, fmaf(ce, e, cz z)) with the scalar-tag noise (every utterance draws, window-local Philox index),
-// or the multistep lines of guided_multistep.hip.  HBM-bound, per generated element: STORE the CFG update's bytes + 4 (20 + 4 DDIM
+// then guided_update.h's DDIM line x' = fmaf(a, x, fmaf(ce, e, cz z)) with the scalar-tag noise (every utterance draws, window-local
+// Philox index), or its multistep lines.  The multistep kernel runs update_rows; the DDIM kernel keeps the same loop written out, for
+// the reason given above it.  HBM-bound, per generated element: STORE the CFG update's bytes + 4 (20 + 4 DDIM
 // without a noise buffer, 28 + 4 multistep with history); LOAD x, c and delta read (12 B) and x' written (4 B), 4 B more than the unguided
 // update, + 4 B noise buffer, + 4 B mirror, + 8 B multistep history (q read and written).
 #include "ditto_hip.h"
@@ -19,13 +20,15 @@
 
 namespace ditto {
 
-enum { REUSE_STORE = 1, REUSE_LOAD = 2 };
+enum { REUSE_STORE = 1, REUSE_LOAD = 2 };                                      // the entries' `mode`
+template <int MODE> constexpr int reuse_eps_mode = MODE == REUSE_STORE ? EPS_STORE : EPS_LOAD;
 
-// the guided prediction of one element from the direction dv: c - u of this step at a refresh, the kept one at a reuse
-template <int MODE> __device__ __forceinline__ float reuse_eps(float w, float wm1, float c, float u, float dv) {
-    return MODE == REUSE_STORE ? fmaf(w, dv, u) : fmaf(wm1, dv, c);
-}
-
+// The one kernel that keeps a row loop of its own: update_rows<EPS_STORE / EPS_LOAD> with the DDIM line, written out as it stood
+// before the other loops were folded.  Routed through update_rows its six instantiations compile to the same optimised IR, but the
+// return block of an inlined loop lands behind the loop where a loop written in the __global__ function has it in front, and the
+// code that follows differs: the Philox LOAD kernel came out at 294 instructions for 287 and 34 VGPRs for 32, and measured 0.4 %
+// and 0.5 % slower than its parent in two runs beside an A/A spread of +-0.25 % (the five others stayed inside theirs; every digest
+// was equal).  tests/test_gpu_reuse_update.py and tests/test_gpu_refresh_update.py hold this text to update_rows' bits.
 template <int NOISE, int MODE>
 __global__ __launch_bounds__(256) void guided_update_reuse_kernel(float* __restrict__ x2, const float* __restrict__ eps,
                                                                   float* __restrict__ delta, const float* __restrict__ noise,
@@ -60,41 +63,12 @@ __global__ __launch_bounds__(256) void guided_update_reuse_kernel(float* __restr
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float dv = MODE == REUSE_STORE ? c[e] - u[e] : dl[e];
-            const float ev = reuse_eps<MODE>(k.w, wm1, c[e], u[e], dv);
+            const float ev = MODE == REUSE_STORE ? fmaf(k.w, dv, u[e]) : fmaf(wm1, dv, c[e]);
             dl[e] = dv;
             o[e] = fmaf(k.a, xv[e], fmaf(k.ce, ev, k.cz * zv[e]));
         }
         xc[i] = o;
         if (both) xu[i] = o;
-        if (MODE == REUSE_STORE) dp[i] = dl;
-    }
-}
-
-// guided_multistep.hip's p, o, q lines behind the same two modes.  PREV false: q is written and never read
-template <int MODE, bool PREV>
-__device__ __forceinline__ void multistep_reuse_rows(f32x4* xc, f32x4* xu, const f32x4* ec, const f32x4* eu, f32x4* qp, f32x4* dp,
-                                                     const ditto_multistep_coef& k, bool both, size_t n4, size_t i0, size_t stride) {
-    const float wm1 = k.w - 1.0f;
-    for (size_t i = i0; i < n4; i += stride) {
-        const f32x4 xv = xc[i];
-        const f32x4 c = ec[i];
-        f32x4 u = c, dl;
-        if (MODE == REUSE_STORE) u = eu[i];
-        else dl = dp[i];
-        f32x4 qv = {0.f, 0.f, 0.f, 0.f};
-        if (PREV) qv = qp[i];
-        f32x4 o, p;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float dv = MODE == REUSE_STORE ? c[e] - u[e] : dl[e];
-            const float ev = reuse_eps<MODE>(k.w, wm1, c[e], u[e], dv);
-            dl[e] = dv;
-            p[e] = fmaf(k.kx, xv[e], k.ke * ev);
-            o[e] = fmaf(k.a, xv[e], fmaf(k.b, p[e], PREV ? k.g * qv[e] : 0.f));
-        }
-        xc[i] = o;
-        if (both) xu[i] = o;
-        qp[i] = p;
         if (MODE == REUSE_STORE) dp[i] = dl;
     }
 }
@@ -114,12 +88,13 @@ __global__ __launch_bounds__(256) void multistep_update_reuse_kernel(float* __re
     const f32x4* ec = reinterpret_cast<const f32x4*>(eps) + base4;
     f32x4* qp = reinterpret_cast<f32x4*>(q) + base4;
     f32x4* dp = reinterpret_cast<f32x4*>(delta) + base4;
-    const bool both = MODE == REUSE_STORE || mirror != 0;
+    const bool both = mirror != 0;                                              // LOAD only; uniform: a scalar branch
     const size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    constexpr int EPS = reuse_eps_mode<MODE>;
     if (k.use_prev)
-        multistep_reuse_rows<MODE, true>(xc, xc + half4, ec, ec + half4, qp, dp, k, both, ws.g4, i0, stride);
+        update_rows<EPS, false>(xc, xc + half4, ec, ec + half4, MultistepLine<true>{qp, k}, dp, k.w, both, ws.g4, ws.g4, i0, stride);
     else
-        multistep_reuse_rows<MODE, false>(xc, xc + half4, ec, ec + half4, qp, dp, k, both, ws.g4, i0, stride);
+        update_rows<EPS, false>(xc, xc + half4, ec, ec + half4, MultistepLine<false>{qp, k}, dp, k.w, both, ws.g4, ws.g4, i0, stride);
 }
 
 static bool reuse_args_ok(const void* x2, const void* eps, const void* delta, const float* w, const int32_t* cu, int B, int S, int max_N,
@@ -137,11 +112,9 @@ hipError_t launch_guided_update_reuse(float* x2, const float* eps, float* delta,
         hipLaunchKernelGGL((guided_update_reuse_kernel<decltype(nz)::value, decltype(md)::value>), guided_grid(max_N, d, B), dim3(256), 0,
                            s, x2, eps, delta, noise, seeds, step, w, a, ce, cz, cu, prompt_len, suffix_len, S, d, mirror);
     };
-    auto by_mode = [&](auto nz) {
+    noise_dispatch(noise, seeds, [&](auto nz) {
         mode == REUSE_STORE ? go(nz, std::integral_constant<int, REUSE_STORE>{}) : go(nz, std::integral_constant<int, REUSE_LOAD>{});
-    };
-    seeds ? by_mode(std::integral_constant<int, 2>{}) : noise ? by_mode(std::integral_constant<int, 1>{})
-                                                               : by_mode(std::integral_constant<int, 0>{});
+    });
     return hipGetLastError();
 }
 

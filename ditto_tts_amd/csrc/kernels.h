@@ -295,6 +295,10 @@ hipError_t launch_multistep_update_reuse(float* x2, const float* eps, float* q, 
 // the per-utterance-tag update of a batch in which G of the B utterances are guided at this step: x2, eps2 [S + S_G, d], the guided
 // ones' unconditional copies compacted in rows [S, S + S_G); cu device int32 [B + G + 1] = [cu; S + cu_G[1:]]; partner device int32
 // [B]: b's copy in [0, G), or -1 (e = c, nothing behind row S touched); prompt_len may be null
+// the shape rule of this layout, stated once: 0 <= G <= B, G <= S_G <= S, and S_G == 0 exactly when G == 0
+inline bool mixed_layout_ok(int B, int G, int S, int S_G) {
+    return 0 <= G && G <= B && G <= S_G && S_G <= S && (S_G == 0) == (G == 0);
+}
 hipError_t launch_guided_update_mixed(float* x2, const float* eps2, const float* noise, const int64_t* seeds, const unsigned* tags,
                                       const float* w, const float* a, const float* ce, const float* cz, const int32_t* cu,
                                       const int32_t* partner, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,

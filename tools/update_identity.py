@@ -3,18 +3,21 @@
 parent commit (--parent-lib), in ONE process on one GPU: first the bits, then the time.
 
 Bits.  Every entry that runs one of the merged kernels — the six ditto_guided_update_packed*, ditto_multistep_update_packed / _window,
-ditto_span_noise_packed / _window and ditto_span_mse_packed / _window (gradient and loss) — on fixed hashed inputs at the `small` and
+ditto_span_noise_packed / _window and ditto_span_mse_packed / _window (gradient and loss) — and ditto_guided_update_packed_reuse, whose
+kernels the fold of the row loops left with another machine code, on fixed hashed inputs at the `small` and
 `stride` shapes of tests/test_gpu_window_update.py, with that test's P and Q where the entry takes them: every noise mode x CFG on /
 off for the updates (the tag form is the entry's), CFG x one step / per-utterance steps x with / without history for the multistep
-update, buffer / seeded for the span entries.  sha256 of every output buffer from both libraries; the listing goes to --out-identity
+update, buffer / seeded for the span entries, every noise mode x STORE / LOAD / LOAD with mirror for the reuse update (x2 and the
+direction buffer).  sha256 of every output buffer from both libraries; the listing goes to --out-identity
 and the exit status is 1 when any digest differs.
 
 Time (skipped with --no-bench).  tools/bench_window.py's shapes: C2, B = 32, the lengths of tools/bench_varlen.py as generated frames
 with a 150-row prefix and suffix around each.  Each entry alone (CFG and Philox noise for the updates, a step with history for the
-multistep ones, seeded span entries) from this library, the parent's, and the parent's a second time as the A/A pair, the order of the
+multistep ones, seeded span entries, the reuse update at every noise mode x STORE / LOAD) from this library, the parent's, and the parent's a second time as the A/A pair, the order of the
 three rotating round by round; and the whole sample_guided_packed call (25 steps) the same way, one model alive at a time.  Per arm:
 the three medians, merged / parent, and the per-round parent / parent ratios (and their reciprocals) whose range is the spread a
-merged / parent ratio has to lie in.  One JSON object to --out-bench."""
+merged / parent ratio has to lie in.  --arms TEXT times only the entries whose name contains TEXT and leaves the whole call out.
+One JSON object to --out-bench."""
 import argparse
 import ctypes as C
 import gc
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--kernel-iters", type=int, default=200)
     ap.add_argument("--n-steps", type=int, default=25)
+    ap.add_argument("--arms", default="", help="time only the entries whose name contains this, and not the whole call")
     ap.add_argument("--out-identity", default=os.path.join(ROOT, "profiles", "update_merge_identity.txt"))
     ap.add_argument("--out-bench", default=os.path.join(ROOT, "profiles", "update_merge_bench.json"))
     args = ap.parse_args()
@@ -93,6 +97,7 @@ def main():
             self.eps = hash_normal((2 * S, d), tag + "_eps", 2).to(dev)
             self.z = hash_normal((S, d), tag + "_z", 3).to(dev)
             self.q = hash_normal((S, d), tag + "_q", 4).to(dev)
+            self.delta = hash_normal((S, d), tag + "_delta", 5).to(dev)
             k = torch.arange(B, dtype=torch.float32)
             self.a, self.ce, cz = (0.9 + 0.003 * k).to(dev), (-0.2 + 0.01 * k).to(dev), 0.4 + 0.01 * k
             if B > 3:
@@ -110,6 +115,13 @@ def main():
                     self.a.data_ptr(), self.ce.data_ptr(), self.cz.data_ptr(), self.cu.data_ptr())
             name = "ditto_guided_update_packed" + ("_tags" if tags else "") + kind
             ok(lib, getattr(lib, name)(*head, *context(kind, self.P, self.Q), *self.dims, int(cfg), st))
+
+        def reuse(self, lib, noise, mode, mirror, x, delta):
+            """mode 1 STORE (eps [2S, d], delta written), 2 LOAD (eps' first S rows, delta read; mirror: x' to the other half too)"""
+            ok(lib, lib.ditto_guided_update_packed_reuse(
+                x.data_ptr(), self.eps.data_ptr(), delta.data_ptr(), ptr(self.z) if noise == "buffer" else None,
+                ptr(self.seeds) if noise == "philox" else None, 49, self.w.data_ptr(), self.a.data_ptr(), self.ce.data_ptr(),
+                self.cz.data_ptr(), self.cu.data_ptr(), self.P.data_ptr(), self.Q.data_ptr(), *self.dims, mode, int(mirror), st))
 
         def multistep(self, lib, kind, cfg, table, coef, x, q):
             step = None if table is not None else hip.MultistepCoef(*coef[:5], 0.0, int(coef[5]), 0)
@@ -150,6 +162,12 @@ def main():
                             x = torch.cat([bt.x, bt.x]) if cfg else bt.x.clone()
                             bt.update(lib, tags, kind, noise, cfg, x)
                             out[f"{shape}/guided_update_packed{'_tags' if tags else ''}{kind}/{noise}/cfg{int(cfg)}/x2"] = sha(x)
+            for noise in ("none", "buffer", "philox"):
+                for mode, mirror in ((1, False), (2, False), (2, True)):
+                    x, delta = torch.cat([bt.x, bt.x]), bt.delta.clone()
+                    bt.reuse(lib, noise, mode, mirror, x, delta)
+                    key = f"{shape}/guided_update_packed_reuse/{noise}/{'store' if mode == 1 else 'load'}/mirror{int(mirror)}"
+                    out[key + "/x2"], out[key + "/delta"] = sha(x), sha(delta)
             for kind in ("", "_window"):
                 for cfg in (False, True):
                     for per_utt in (False, True):
@@ -229,6 +247,12 @@ def main():
     for kind in ("_packed", "_window"):
         arms[f"span_noise{kind}/seeded"] = lambda lib, kind=kind: bt.span_noise(lib, kind, True, out1)
         arms[f"span_mse{kind}/seeded"] = lambda lib, kind=kind: bt.span_mse(lib, kind, True, out1, loss)
+    delta = bt.delta.clone()
+    for noise in ("none", "buffer", "philox"):
+        for mode in (1, 2):
+            arms[f"guided_update_packed_reuse/{noise}/{'store' if mode == 1 else 'load'}"] = (
+                lambda lib, noise=noise, mode=mode: bt.reuse(lib, noise, mode, False, x2, delta))
+    arms = {k: v for k, v in arms.items() if args.arms in k}
     trio = [("merged", new), ("parent", old), ("parent_again", old)]
     for name, fn in arms.items():
         runs = {k: [] for k, _ in trio}
@@ -240,36 +264,37 @@ def main():
         q.copy_(bt.q)
 
     # the whole sample_guided_packed call, one model alive at a time (tools/bench_window.py's arm (c))
-    state = synthetic_state_dict(cfg, seed=1)
-    cg, ct = cumulate(GL), cumulate(TL)
-    audio = hash_normal((cg[-1], d), "bench_window_audio", 1).to(dev)
-    text = hash_normal((ct[-1], cfg.text_dim), "bench_window_text", 2).to(dev)
-    seeds, null = torch.arange(B, device=dev) + 1000, torch.zeros(1, cfg.text_dim, device=dev)
-    runs, outputs = {k: [] for k, _ in trio}, {}
-    with torch.no_grad():
-        for rnd in range(args.rounds):
-            for k, lib in trio[rnd % 3:] + trio[:rnd % 3]:
-                hip._lib = lib
-                try:
-                    m = DiTTO(cfg.hidden_dim, cfg.num_layers, cfg.num_heads, cfg.time_dim, cfg.text_dim, cfg.diffusion_steps)
-                    m.load_state_dict(state)
-                    g = SpeechGenerator(ditto_model=m.to(dev).eval(), device=dev)
-                    assert g.ditto_model.engine(torch.device("cuda:0")).lib is lib
-                finally:
-                    hip._lib = new
-                f = lambda: g.sample_guided_packed(text, ct, audio, cg, n_steps=args.n_steps, eta=1.0, seeds=seeds, guidance=5.0,  # noqa: E731
-                                                   null_text_emb=null)
-                runs[k].append(timed(f, 1, 1))
-                if rnd == 0:
-                    outputs[k] = f().cpu()
-                del g, m, f
-                gc.collect()
-                torch.cuda.empty_cache()
-    assert torch.equal(outputs["merged"], outputs["parent"])
-    res["sample_guided_packed"] = dict(summary(runs), n_steps=args.n_steps, output_equals_parent=True)
-    res["outside_aa_spread"] = [k for k, v in list(res["kernels"].items()) + [("sample_guided_packed", res["sample_guided_packed"])]
-                                if not v["inside_aa_spread"]]
-    for k, v in list(res["kernels"].items()) + [("sample_guided_packed", res["sample_guided_packed"])]:
+    legs = dict(res["kernels"])
+    if not args.arms:
+        state = synthetic_state_dict(cfg, seed=1)
+        cg, ct = cumulate(GL), cumulate(TL)
+        audio = hash_normal((cg[-1], d), "bench_window_audio", 1).to(dev)
+        text = hash_normal((ct[-1], cfg.text_dim), "bench_window_text", 2).to(dev)
+        seeds, null = torch.arange(B, device=dev) + 1000, torch.zeros(1, cfg.text_dim, device=dev)
+        runs, outputs = {k: [] for k, _ in trio}, {}
+        with torch.no_grad():
+            for rnd in range(args.rounds):
+                for k, lib in trio[rnd % 3:] + trio[:rnd % 3]:
+                    hip._lib = lib
+                    try:
+                        m = DiTTO(cfg.hidden_dim, cfg.num_layers, cfg.num_heads, cfg.time_dim, cfg.text_dim, cfg.diffusion_steps)
+                        m.load_state_dict(state)
+                        g = SpeechGenerator(ditto_model=m.to(dev).eval(), device=dev)
+                        assert g.ditto_model.engine(torch.device("cuda:0")).lib is lib
+                    finally:
+                        hip._lib = new
+                    f = lambda: g.sample_guided_packed(text, ct, audio, cg, n_steps=args.n_steps, eta=1.0, seeds=seeds, guidance=5.0,  # noqa: E731
+                                                       null_text_emb=null)
+                    runs[k].append(timed(f, 1, 1))
+                    if rnd == 0:
+                        outputs[k] = f().cpu()
+                    del g, m, f
+                    gc.collect()
+                    torch.cuda.empty_cache()
+        assert torch.equal(outputs["merged"], outputs["parent"])
+        res["sample_guided_packed"] = legs["sample_guided_packed"] = dict(summary(runs), n_steps=args.n_steps, output_equals_parent=True)
+    res["outside_aa_spread"] = [k for k, v in legs.items() if not v["inside_aa_spread"]]
+    for k, v in legs.items():
         print(f"{v['median_ms']['merged'] * 1e3:10.2f} us merged {v['median_ms']['parent'] * 1e3:10.2f} us parent  ratio "
               f"{v['merged_over_parent']:.4f}  A/A [{v['aa_round_ratio_min']:.4f}, {v['aa_round_ratio_max']:.4f}]  "
               f"{'inside' if v['inside_aa_spread'] else 'OUTSIDE'}  {k}")
