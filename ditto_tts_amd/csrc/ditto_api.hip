@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "batch_layout.h"
+#include "ditto_project.h"
 #include "ditto_refresh.h"
 #include "gemm_common.h"
 
@@ -2124,6 +2125,150 @@ int ditto_guided_step_packed_refresh_opts(ditto_model_t m, float* x2, const void
     }, [&](const float* eps, int d) -> int {
         HIP_TRY(launch_guided_update_refresh(x2, eps, delta, noise, seeds, tags, w, a, ce, cz, cu_speech, partner, kind, prompt_len, B, G, S,
                                              S_G, max_N, d, (hipStream_t)stream));
+        return DITTO_OK;
+    });
+}
+
+// ---- projected guidance (APG, Sadat et al. 2024; guided_project.hip; include/ditto_project.h): the scratch [pcoef | partials], each
+// part 256-byte aligned; the statistics alone, the two updates, and the steps that chain them behind the forward ----
+static size_t project_head_bytes(int B) { return al((size_t)B * 4 * sizeof(float)); }
+static size_t project_bytes(int B, int max_N, int d) {
+    return project_head_bytes(B) + al((size_t)B * guidance_rescale_chunks(max_N, d) * 4 * sizeof(double));
+}
+// what every project entry shares: the rows, the shapes and cu
+static int check_project_rows(const char* who, const float* x2, const float* eps2, const float* dir, const int32_t* cu, int B, int S,
+                              int max_N, int d) {
+    if (!x2 || !eps2 || !dir || !cu) return fail(DITTO_ERR_ARG, "%s: null x2 / eps2 / dir / cu", who);
+    if (((uintptr_t)x2 | (uintptr_t)eps2 | (uintptr_t)dir) % 16) return fail(DITTO_ERR_ARG, "%s: x2, eps2 and dir must be 16-byte aligned", who);
+    if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
+    return check_packed(who, B, S, max_N, S, max_N);
+}
+// every argument of launch 1 and the finish is checked here, before any launch
+static int check_project(const char* who, const float* x2, const float* eps2, const float* dir, const ditto_project_coef* proj,
+                         const int32_t* cu, int B, int S, int max_N, int d, const void* scratch, size_t scratch_bytes) {
+    if (!proj || !scratch) return fail(DITTO_ERR_ARG, "%s: null proj / scratch", who);
+    if ((uintptr_t)proj % 16) return fail(DITTO_ERR_ARG, "%s: proj must be 16-byte aligned", who);
+    if ((uintptr_t)scratch % 256) return fail(DITTO_ERR_ARG, "%s: the project scratch must be 256-byte aligned", who);
+    if (int rc = check_project_rows(who, x2, eps2, dir, cu, B, S, max_N, d)) return rc;
+    if (scratch_bytes < project_bytes(B, max_N, d))
+        return fail(DITTO_ERR_SIZE, "%s: the project scratch needs %zu bytes (ditto_guidance_project_bytes)", who, project_bytes(B, max_N, d));
+    return DITTO_OK;
+}
+static ProjectArgs project_args(const float* x2, const float* eps2, float* dir, const ditto_project_coef* proj, const int32_t* cu,
+                                const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int d, void* scratch,
+                                size_t scratch_bytes) {
+    ProjectArgs a{};
+    a.x2 = x2; a.eps2 = eps2; a.dir = dir; a.proj = proj; a.cu = cu; a.prompt_len = prompt_len; a.suffix_len = suffix_len;
+    a.B = B; a.S = S; a.d = d;
+    a.pcoef = (float*)scratch;
+    a.partial = (double*)((char*)scratch + project_head_bytes(B));
+    const size_t slots = (scratch_bytes - project_head_bytes(B)) / ((size_t)B * 4 * sizeof(double));
+    a.slots = slots > 0x7fffffff ? 0x7fffffff : (int)slots;
+    return a;
+}
+static int check_project_ddim(const char* who, const float* pcoef, const float* noise, const int64_t* seeds, const float* a,
+                              const float* ce, const float* cz) {
+    if (!pcoef || (uintptr_t)pcoef % 16) return fail(DITTO_ERR_ARG, "%s: pcoef (fp32 [B, 4]) must be given and 16-byte aligned", who);
+    if (noise && seeds) return fail(DITTO_ERR_ARG, "%s: noise and seeds are exclusive (a noise buffer, or Philox from seeds)", who);
+    if ((uintptr_t)noise % 16) return fail(DITTO_ERR_ARG, "%s: noise must be 16-byte aligned", who);
+    if (!a || !ce || ((noise || seeds) && !cz)) return fail(DITTO_ERR_ARG, "%s: null a / ce / cz", who);
+    return DITTO_OK;
+}
+static int check_project_multistep(const char* who, const float* pcoef, const float* q, const ditto_multistep_coef* step,
+                                   const ditto_multistep_coef* coefs) {
+    if (!pcoef || (uintptr_t)pcoef % 16) return fail(DITTO_ERR_ARG, "%s: pcoef (fp32 [B, 4]) must be given and 16-byte aligned", who);
+    if (!q || (uintptr_t)q % 16) return fail(DITTO_ERR_ARG, "%s: q (fp32 [S, d]) must be given and 16-byte aligned", who);
+    if (!step == !coefs) return fail(DITTO_ERR_ARG, "%s: exactly one of step (host) and coefs (device [B]) is needed", who);
+    if ((uintptr_t)coefs % 16) return fail(DITTO_ERR_ARG, "%s: coefs must be 16-byte aligned", who);
+    return DITTO_OK;
+}
+
+size_t ditto_guidance_project_bytes(int B, int max_N, int d) {
+    if (B <= 0 || max_N <= 0 || d <= 0 || d % 64) {
+        fail(DITTO_ERR_SHAPE, "ditto_guidance_project_bytes: B and max_N must be positive and d %% 64 == 0");
+        return 0;
+    }
+    return project_bytes(B, max_N, d);
+}
+
+int ditto_guidance_project_packed(const float* x2, const float* eps2, float* dir, const ditto_project_coef* proj, const int32_t* cu,
+                                  const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d, void* scratch,
+                                  size_t scratch_bytes, ditto_stream_t stream) {
+    if (int rc = check_project("ditto_guidance_project_packed", x2, eps2, dir, proj, cu, B, S, max_N, d, scratch, scratch_bytes)) return rc;
+    HIP_TRY(launch_guidance_project(project_args(x2, eps2, dir, proj, cu, prompt_len, suffix_len, B, S, d, scratch, scratch_bytes), max_N,
+                                    (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_update_packed_project(float* x2, const float* eps2, const float* dir, const float* pcoef, const float* noise,
+                                       const int64_t* seeds, uint32_t step, const uint32_t* tags, const float* a, const float* ce,
+                                       const float* cz, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
+                                       int S, int max_N, int d, ditto_stream_t stream) {
+    const char* who = "ditto_guided_update_packed_project";
+    if (int rc = check_project_ddim(who, pcoef, noise, seeds, a, ce, cz)) return rc;
+    if (int rc = check_project_rows(who, x2, eps2, dir, cu, B, S, max_N, d)) return rc;
+    HIP_TRY(launch_guided_update_project(x2, eps2, dir, pcoef, noise, seeds, step, tags, a, ce, cz, cu, prompt_len, suffix_len, B, S, max_N,
+                                         d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_multistep_update_packed_project(float* x2, const float* eps2, float* q, const float* dir, const float* pcoef,
+                                          const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, const int32_t* cu,
+                                          const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d,
+                                          ditto_stream_t stream) {
+    const char* who = "ditto_multistep_update_packed_project";
+    if (int rc = check_project_multistep(who, pcoef, q, step, coefs)) return rc;
+    if (int rc = check_project_rows(who, x2, eps2, dir, cu, B, S, max_N, d)) return rc;
+    HIP_TRY(launch_multistep_update_project(x2, eps2, q, dir, pcoef, step, coefs, cu, prompt_len, suffix_len, B, S, max_N, d,
+                                            (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+// the forward over [x; x] x [text; null], launch 1 and the finish on its eps, then `update` reading pcoef from the scratch's head
+extern "C++" template <class Check, class Update>
+static int project_step(PackedStep& p, float* dir, const ditto_project_coef* proj, const int32_t* prompt_len, const int32_t* suffix_len,
+                        void* scratch, size_t scratch_bytes, Check&& check, Update&& update) {
+    p.forward_over(true);
+    return packed_step(p, [&](int d) -> int {
+        if (int rc = check_project(p.who, p.x2, p.x2, dir, proj, p.cu_speech, p.B, p.S, p.max_N, d, scratch, scratch_bytes)) return rc;
+        return check();
+    }, [&](const float* eps, int d) -> int {
+        HIP_TRY(launch_guidance_project(project_args(p.x2, eps, dir, proj, p.cu_speech, prompt_len, suffix_len, p.B, p.S, d, scratch,
+                                                     scratch_bytes), p.max_N, (hipStream_t)p.stream));
+        return update(eps, (const float*)scratch, d);
+    });
+}
+
+int ditto_guided_step_packed_project_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                          const int32_t* cu_text, const int32_t* prompt_len, const int32_t* suffix_len, float* dir,
+                                          const ditto_project_coef* proj, const float* noise, const int64_t* seeds, uint32_t step,
+                                          const uint32_t* tags, const float* a, const float* ce, const float* cz, int B, int S, int max_N,
+                                          int S_T, int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
+                                          size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
+                                          const ditto_call_opts* opts) {
+    PACKED_STEP(p, "ditto_guided_step_packed_project_opts");
+    return project_step(p, dir, proj, prompt_len, suffix_len, scratch, scratch_bytes, [&]() -> int {
+        return check_project_ddim(p.who, (const float*)scratch, noise, seeds, a, ce, cz);
+    }, [&](const float* eps, const float* pcoef, int d) -> int {
+        HIP_TRY(launch_guided_update_project(x2, eps, dir, pcoef, noise, seeds, step, tags, a, ce, cz, cu_speech, prompt_len, suffix_len, B,
+                                             S, max_N, d, (hipStream_t)stream));
+        return DITTO_OK;
+    });
+}
+
+int ditto_guided_step_packed_multistep_project_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t,
+                                                    const int32_t* cu_speech, const int32_t* cu_text, const int32_t* prompt_len,
+                                                    const int32_t* suffix_len, float* q, float* dir, const ditto_project_coef* proj,
+                                                    const ditto_multistep_coef* step, const ditto_multistep_coef* coefs, int B, int S,
+                                                    int max_N, int S_T, int max_T, const float* rope_cos, const float* rope_sin,
+                                                    void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                                                    ditto_stream_t stream, const ditto_call_opts* opts) {
+    PACKED_STEP(p, "ditto_guided_step_packed_multistep_project_opts");
+    return project_step(p, dir, proj, prompt_len, suffix_len, scratch, scratch_bytes, [&]() -> int {
+        return check_project_multistep(p.who, (const float*)scratch, q, step, coefs);
+    }, [&](const float* eps, const float* pcoef, int d) -> int {
+        HIP_TRY(launch_multistep_update_project(x2, eps, q, dir, pcoef, step, coefs, cu_speech, prompt_len, suffix_len, B, S, max_N, d,
+                                                (hipStream_t)stream));
         return DITTO_OK;
     });
 }

@@ -6,6 +6,7 @@
 
 struct ditto_regroup_seg;   // include/ditto_hip.h
 struct ditto_multistep_coef;
+struct ditto_project_coef;  // include/ditto_project.h
 
 namespace ditto {
 
@@ -349,6 +350,30 @@ struct RescaleArgs {
 };
 size_t guidance_rescale_chunks(int max_N, int d);   // chunks of the longest generated region: the scratch's slots and the grid's columns
 hipError_t launch_guidance_rescale(const RescaleArgs& a, int max_N, hipStream_t s);
+// ---------------- guided_project.hip ----------------
+// projected guidance (APG, Sadat et al. 2024; include/ditto_project.h states the arithmetic): launch 1 keeps the x0-space direction
+// m' in `dir` and cuts S_mm, S_mD, S_DD into the rescale's chunks, the finish turns them into pcoef[b] = (fx, fc, fd, 0), and the
+// updates run e = fmaf(fx, x, fmaf(fc, c, fd m')) into the DDIM or the 2M line over launch_guided_update_packed's window
+struct ProjectArgs {
+    const float* x2;                 // [2S, d]: the conditional half is read
+    const float* eps2;               // [2S, d]: c, and u at row offset S
+    float* dir;                      // [S, d]: m, rewritten with m' on the window rows
+    const ::ditto_project_coef* proj;   // [B]
+    float* pcoef;                    // [B, 4]: fx, fc, fd, 0
+    double* partial;                 // [B, slots, 4]: S_mm, S_mD, S_DD, 0 of every chunk
+    const int32_t* cu; const int32_t* prompt_len; const int32_t* suffix_len;
+    int B, S, d;
+    int slots;                       // partials per utterance the scratch holds (an utterance with more chunks uses the first `slots`)
+};
+hipError_t launch_guidance_project(const ProjectArgs& a, int max_N, hipStream_t s);
+hipError_t launch_guided_update_project(float* x2, const float* eps2, const float* dir, const float* pcoef, const float* noise,
+                                        const int64_t* seeds, unsigned step, const unsigned* tags, const float* a, const float* ce,
+                                        const float* cz, const int32_t* cu, const int32_t* prompt_len, const int32_t* suffix_len, int B,
+                                        int S, int max_N, int d, hipStream_t s);
+hipError_t launch_multistep_update_project(float* x2, const float* eps2, float* q, const float* dir, const float* pcoef,
+                                           const ::ditto_multistep_coef* step, const ::ditto_multistep_coef* coefs, const int32_t* cu,
+                                           const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d,
+                                           hipStream_t s);
 // ---------------- optim.hip ----------------
 // the fused training optimizer (include/ditto_optim.h): a segment's gradients are cut into partials of DITTO_OPTIM_CHUNK_QUADS
 // 16-byte quads of the segment itself, so that the global norm depends on the table and the gradients only, never on the grid: the

@@ -87,7 +87,7 @@ def sample_sharded(sample_fn: Callable[[torch.Tensor, torch.Tensor, int], torch.
                    device, root: int = 0, group=None, phases: Optional[dict] = None,
                    sync: Optional[Callable[[], None]] = None, pin_class: bool = True,
                    text_dtype: torch.dtype = torch.float32, speech_lengths=None, text_lengths=None,
-                   prompt_lengths=None, suffix_lengths=None, prediction="eps") -> Optional[torch.Tensor]:
+                   prompt_lengths=None, suffix_lengths=None, prediction="eps", guidance_projection=None) -> Optional[torch.Tensor]:
     """Scatter (text_emb, x_T) from root, run `sample_fn(text_shard, xT_shard, first_global_index)` on every
     rank (the whole denoise loop — no communication inside), gather the final latents on root.
 
@@ -122,6 +122,9 @@ def sample_sharded(sample_fn: Callable[[torch.Tensor, torch.Tensor, int], torch.
             raise ValueError(f"prediction: one of ('eps', 'v') is needed, got {prediction!r}")
         raise NotImplementedError("sample_sharded: v-prediction is not sharded (run SpeechGenerator.sample_guided_packed with "
                                   "prediction=\"v\" per rank)")
+    if guidance_projection is not None:
+        raise NotImplementedError("sample_sharded: projected guidance is served over packed batches: pack the batch and call "
+                                  "SpeechGenerator.sample_guided_packed(guidance_projection=) per rank")
     import time
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     tick = (lambda: (sync() if sync else None, time.perf_counter())[1]) if phases is not None else (lambda: 0.0)

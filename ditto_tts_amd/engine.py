@@ -490,6 +490,81 @@ class DenoiseEngine:
         out = scratch[:32 * B].view(torch.float32).view(B, 8) if coefs is not None else scratch[:4 * B].view(torch.float32)
         return out, scratch[o_scale:o_scale + 4 * B].view(torch.float32)
 
+    # ------------------------------------------------------------------ projected guidance (csrc/guided_project.hip)
+    def project_scratch(self, B: int, max_N: int) -> torch.Tensor:
+        """the scratch of a projected-guidance step over B utterances of at most max_N rows (ditto_guidance_project_bytes): uint8, zeroed"""
+        need = int(self.lib.ditto_guidance_project_bytes(int(B), int(max_N), self.cfg.hidden_dim))
+        if need == 0:
+            raise hip.DittoHipError(hip.ERR_SHAPE, self.lib.ditto_last_error().decode())
+        return torch.zeros(need, dtype=torch.uint8, device=self.device)
+
+    def _project_args(self, proj, direction, scratch, B, S, d, max_N):
+        if not (proj.is_cuda and proj.dtype == torch.float32 and proj.is_contiguous() and proj.shape == (B, 8)
+                and proj.data_ptr() % 16 == 0):
+            raise ValueError(f"proj must be a contiguous, 16-byte aligned fp32 CUDA tensor of shape [{B}, 8] (ditto_project_coef)")
+        self._rows_like("direction", direction, S, d)
+        if scratch is None:
+            scratch = self.project_scratch(B, max_N)
+        if not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.data_ptr() % 256 == 0):
+            raise ValueError("project_scratch must be a contiguous, 256-byte aligned uint8 CUDA tensor")
+        return scratch
+
+    def guidance_project_packed(self, x2: torch.Tensor, eps2: torch.Tensor, direction: torch.Tensor, proj: torch.Tensor,
+                                offsets: torch.Tensor, B: int, S: int, max_N: int, *, prompt_len: Optional[torch.Tensor] = None,
+                                suffix_len: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None):
+        """The direction and statistics of one projected-guidance step alone (ditto_guidance_project_packed; include/ditto_project.h):
+        x2, eps2 fp32 [2S, d], `direction` fp32 [S, d] updated IN PLACE on the window rows, `proj` fp32 [B, 8] (ditto_project_coef per
+        utterance), `offsets` the device int32 offsets the step's update reads.  Returns pcoef fp32 [B, 4] = (fx, fc, fd, 0): a view
+        of `scratch`, which the update entries read."""
+        d = int(eps2.shape[1])
+        scratch = self._project_args(proj, direction, scratch, B, S, d, max_N)
+        hip.check(hip.call("ditto_guidance_project_packed", x2=x2.data_ptr(), eps2=eps2.data_ptr(), dir=direction.data_ptr(),
+                           proj=proj.data_ptr(), cu=offsets.data_ptr(), prompt_len=_ptr(prompt_len), suffix_len=_ptr(suffix_len), B=B, S=S,
+                           max_N=max_N, d=d, scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), stream=_stream()))
+        return scratch[:16 * B].view(torch.float32).view(B, 4)
+
+    def guided_step_packed_project_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, direction: torch.Tensor,
+                                    proj: torch.Tensor, a: torch.Tensor, ce: torch.Tensor, cz: torch.Tensor,
+                                    noise: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None, step: int = 0,
+                                    cu_seqlens=None, max_seqlen: Optional[int] = None, offsets=None,
+                                    opts: Optional[hip.CallOpts] = None, prompt_len: Optional[torch.Tensor] = None,
+                                    suffix_len: Optional[torch.Tensor] = None, project_scratch: Optional[torch.Tensor] = None):
+        """One strided (DDIM) step with projected guidance (APG; ditto_guided_step_packed_project_opts), IN PLACE on x2 fp32 [2S, d]
+        and `direction` fp32 [S, d]: guided_step_packed_'s guided forward, then the direction and its statistics on that eps, then
+        the update with e = fx x + fc c + fd m'.  `proj`: device fp32 [B, 8], one ditto_project_coef per utterance (kx, ke, w, eta,
+        r, beta, use_prev) — the guidance scale travels inside; `project_scratch`: project_scratch(B, max_N) built once per
+        sampling call (else taken here).  Everything else as guided_step_packed_."""
+        who = "guided_step_packed_project_"
+        sd, noise = self._guided_args(who, x2, 2, B, a, ce, cz, a, noise, seeds)   # in w's place: x2 is the doubled state
+        S, _, max_N, head, tail = self._packed_step_args(who, x2, cond, t, B, True, offsets, cu_seqlens, max_seqlen, prompt_len,
+                                                         suffix_len, None, opts)
+        rs = self._project_args(proj, direction, project_scratch, B, S, int(x2.shape[1]), max_N)
+        hip.check(hip.call("ditto_guided_step_packed_project_opts", **head, prompt_len=_ptr(prompt_len), suffix_len=_ptr(suffix_len),
+                           dir=direction.data_ptr(), proj=proj.data_ptr(), noise=_ptr(noise), seeds=_ptr(sd),
+                           step=int(step) & 0xFFFFFFFF, tags=None, a=a.data_ptr(), ce=ce.data_ptr(), cz=cz.data_ptr(), B=B, S=S,
+                           max_N=max_N, S_T=cond.T, max_T=cond.max_len, **tail, scratch=rs.data_ptr(), scratch_bytes=rs.numel()))
+        return x2
+
+    def guided_step_packed_multistep_project_(self, x2: torch.Tensor, cond: TextCond, t: torch.Tensor, B: int, q: torch.Tensor,
+                                              direction: torch.Tensor, proj: torch.Tensor, coef: hip.MultistepCoef, cu_seqlens=None,
+                                              max_seqlen: Optional[int] = None, offsets=None, opts: Optional[hip.CallOpts] = None,
+                                              prompt_len: Optional[torch.Tensor] = None, suffix_len: Optional[torch.Tensor] = None,
+                                              project_scratch: Optional[torch.Tensor] = None):
+        """guided_step_packed_project_ with the update of the second-order multistep solver
+        (ditto_guided_step_packed_multistep_project_opts), IN PLACE on x2, the history `q` fp32 [S, d] and `direction`.  `coef`: the
+        step every utterance stands at, as in guided_step_packed_multistep_ (its w is ignored: the scales travel in `proj`)."""
+        who = "guided_step_packed_multistep_project_"
+        self._guided_args(who, x2, 2, B, None, None, None, None, None, None)
+        S, _, max_N, head, tail = self._packed_step_args(who, x2, cond, t, B, True, offsets, cu_seqlens, max_seqlen, prompt_len,
+                                                         suffix_len, None, opts)
+        self._rows_like("q", q, S, x2.shape[1])
+        rs = self._project_args(proj, direction, project_scratch, B, S, int(x2.shape[1]), max_N)
+        hip.check(hip.call("ditto_guided_step_packed_multistep_project_opts", **head, prompt_len=_ptr(prompt_len),
+                           suffix_len=_ptr(suffix_len), q=q.data_ptr(), dir=direction.data_ptr(), proj=proj.data_ptr(), step=C.byref(coef),
+                           coefs=None, B=B, S=S, max_N=max_N, S_T=cond.T, max_T=cond.max_len, **tail, scratch=rs.data_ptr(),
+                           scratch_bytes=rs.numel()))
+        return x2
+
     # ------------------------------------------------------------------ span-masked training (csrc/span_train.hip)
     def _span_args(self, who, buf, cu_seqlens, prompt_lengths, seeds, noise, suffix_lengths=None):
         """the checks of span_noise_packed / span_mse_packed: (device offsets, device prompt lengths, B, max_N, generated rows,

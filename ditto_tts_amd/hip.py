@@ -180,13 +180,14 @@ def _ctype(decl: str, known, what: str):
     raise TypeError(f"include/ditto_hip.h: no ctypes type for `{decl.strip()}` in `{what}`")
 
 
-def parse_prototypes(text: str) -> dict:
-    """name -> (restype, [(parameter name, ctype), ...]) of every function the C header `text` declares.  Every statement beside
+def parse_prototypes(text: str, known=()) -> dict:
+    """name -> (restype, [(parameter name, ctype), ...]) of every function the C header `text` declares (`known`: type names of a
+    header it includes, beside its own).  Every statement beside
     comments, preprocessor lines and `struct / enum {...}` bodies is a typedef or a prototype; one that is neither, or has a type the
     rule above does not cover, raises TypeError naming it: nothing falls back to c_void_p."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    known = set(re.findall(r"typedef\s+(?:struct|enum)\s+\w*\s*\{[^{}]*\}\s*(\w+)\s*;", text))
+    known = set(known) | set(re.findall(r"typedef\s+(?:struct|enum)\s+\w*\s*\{[^{}]*\}\s*(\w+)\s*;", text))
     text = re.sub(r"(?:typedef\s+)?(?:struct|enum)\s*\w*\s*\{[^{}]*\}\s*\w*\s*;", "", text)
     text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
     protos = {}
@@ -248,6 +249,24 @@ REFRESH_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) i
 _ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in REFRESH_PROTOTYPES.items()})
 KIND_PLAIN, KIND_REFRESH, KIND_REUSE = 0, 1, 2   # the `kind` of the ditto_*_refresh entries, per utterance
 
+# Projected guidance (APG) for packed guided sampling — the direction and its statistics, the two updates and their steps
+# (include/ditto_project.h, csrc/guided_project.hip, csrc/ditto_api.hip): a sixth table, built and bound the same way.
+with open(os.path.join(INCLUDE, "ditto_project.h")) as _f:
+    PROJECT_PROTOTYPES = parse_prototypes(_f.read(), known=("ditto_multistep_coef",))
+PROJECT_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in PROJECT_PROTOTYPES.items()}
+_ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in PROJECT_PROTOTYPES.items()})
+
+
+class ProjectCoef(C.Structure):
+    """ditto_project_coef: one utterance's parameters of a projected-guidance step (a device array [B]), 32 bytes."""
+    _fields_ = [("kx", C.c_float), ("ke", C.c_float), ("w", C.c_float), ("eta", C.c_float), ("r", C.c_float), ("beta", C.c_float),
+                ("use_prev", C.c_int32), ("reserved", C.c_int32)]
+
+
+def project_scratch_layout(B: int):
+    """byte offset of the partials in the scratch of ditto_guidance_project_bytes; pcoef fp32 [B, 4] stands at byte 0"""
+    return (16 * B + 255) // 256 * 256
+
 
 class OptimSeg(C.Structure):
     """ditto_optim_seg: one parameter tensor of the optimizer's device table, 72 bytes."""
@@ -289,7 +308,7 @@ def lib() -> C.CDLL:
         l = C.CDLL(LIB_PATH)
         frozen = bool(os.environ.get("DITTO_HIP_LIB"))   # a diagnostic or FROZEN earlier build for same-box A/Bs (tools/):
         for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items(), *TRAIN_ROWS_SYMBOLS.items(),
-                                  *TEXT_GRAD_SYMBOLS.items(), *REFRESH_SYMBOLS.items()):   # it may predate entries added since (then absent)
+                                  *TEXT_GRAD_SYMBOLS.items(), *REFRESH_SYMBOLS.items(), *PROJECT_SYMBOLS.items()):   # it may predate entries added since (then absent)
             try:
                 fn = getattr(l, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:
@@ -316,7 +335,7 @@ def call(name: str, **kw) -> int:
     if order is None:
         header = "ditto_optim.h" if name.startswith("ditto_optim_") else "ditto_train_rows.h" if name.startswith("ditto_bwd_") else \
             "ditto_text_grad.h" if name.startswith("ditto_text_select_") else \
-            "ditto_refresh.h" if "_packed_refresh" in name else "ditto_hip.h"
+            "ditto_refresh.h" if "_packed_refresh" in name else "ditto_project.h" if "_project" in name else "ditto_hip.h"
         raise TypeError(f"{name}: include/{header} declares no such entry")
     if len(kw) != len(order) or not all(p in kw for p in order):
         missing, unknown = [p for p in order if p not in kw], [p for p in kw if p not in order]

@@ -238,6 +238,63 @@ def rescale_vector(guidance_rescale, B: int) -> Optional[torch.Tensor]:
     return torch.tensor([float(x) for x in v], dtype=torch.float32)
 
 
+def _per_utterance(name, value, B: int, ok, rule: str) -> torch.Tensor:
+    """`value` (a number, or a sequence / 1-d tensor of B numbers, each passing `ok`) as a CPU fp32 tensor [B]"""
+    v = value
+    if isinstance(v, torch.Tensor) and v.dtype != torch.bool and not v.is_complex() and v.dim() == 1:
+        v = v.detach().cpu().tolist()
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        v = [v] * B
+    if not isinstance(v, (list, tuple)) or not all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in v):
+        raise ValueError(f"{name}: None, a number or a sequence of {B} numbers is needed, got {value!r}")
+    if len(v) != B:
+        raise ValueError(f"{name}: {B} values expected (one per utterance), got {len(v)}")
+    if not all(math.isfinite(x) and ok(x) for x in v):
+        raise ValueError(f"{name}: every value must {rule}, got {value!r}")
+    return torch.tensor([float(x) for x in v], dtype=torch.float32)
+
+
+def projection_vectors(guidance_projection, guidance_norm_threshold, guidance_momentum, B: int):
+    """The three keywords of projected guidance (APG, Sadat et al. 2024) as CPU fp32 tensors [B] (eta, r, beta), or None when
+    `guidance_projection` is None: eta in [0, 1] the weight of the part of the direction parallel to the conditional x0 prediction;
+    r > 0 the RMS threshold of the direction (None: 0, off); beta in (-1, 1) its momentum (None: 0).  The last two need the first."""
+    if guidance_projection is None:
+        for name, v in (("guidance_norm_threshold", guidance_norm_threshold), ("guidance_momentum", guidance_momentum)):
+            if v is not None:
+                raise ValueError(f"{name} needs guidance_projection=")
+        return None
+    eta = _per_utterance("guidance_projection", guidance_projection, B, lambda x: 0.0 <= x <= 1.0, "lie in [0, 1]")
+    r = torch.zeros(B) if guidance_norm_threshold is None else _per_utterance(
+        "guidance_norm_threshold", guidance_norm_threshold, B, lambda x: x > 0.0, "be positive")
+    beta = torch.zeros(B) if guidance_momentum is None else _per_utterance(
+        "guidance_momentum", guidance_momentum, B, lambda x: -1.0 < x < 1.0, "lie in (-1, 1)")
+    return eta, r, beta
+
+
+def project_table(projection, gv, x0_rows, guided):
+    """The device table of a projected call, fp32 [n_steps, B, 8]: one ditto_project_coef per step and utterance.  `projection`:
+    projection_vectors' (eta, r, beta); `gv`: guidance_vector's scales; `x0_rows`: the multistep schedule's rows over the call's
+    timesteps, whose (kx, ke) map the network's output to x0 at step i; `guided`: guided_steps' list.  use_prev is 1 from the second
+    guided step on, whatever lies in between: an unguided step leaves the direction alone.  Pure host arithmetic."""
+    eta, r, beta = projection
+    B = int(gv.shape[0])
+    table = torch.zeros(len(x0_rows), B, 8, dtype=torch.float32)
+    seen = False
+    for i, row in enumerate(x0_rows):
+        table[i, :, 0], table[i, :, 1] = row[2], row[3]
+        table[i, :, 2], table[i, :, 3], table[i, :, 4], table[i, :, 5] = gv, eta, r, beta
+        table.view(torch.int32)[i, :, 6] = int(seen and guided[i])
+        seen = seen or guided[i]
+    return table
+
+
+def _padded_projection(guidance_projection, guidance_norm_threshold=None, guidance_momentum=None):
+    """the padded layouts have no projected guidance"""
+    if guidance_projection is not None or guidance_norm_threshold is not None or guidance_momentum is not None:
+        raise NotImplementedError("guidance_projection= is served over packed batches: pack the batch and call "
+                                  "sample_guided_packed(guidance_projection=)")
+
+
 def _padded_rescale(guidance_rescale):
     """the padded layouts have no guidance rescale"""
     if guidance_rescale is not None:
@@ -436,13 +493,15 @@ class SpeechGenerator:
     @torch.no_grad()
     def sample_latents_strided(self, text_emb, audio_emb, n_steps=25, eta=0.0, cfg_scale=None, null_text_emb=None,
                                cond_by_audio=False, noises=None, speech_lengths=None, text_lengths=None, prompt_lengths=None,
-                               solver="ddim", guidance_rescale=None, suffix_lengths=None, prediction="eps"):
+                               solver="ddim", guidance_rescale=None, suffix_lengths=None, prediction="eps",
+                               guidance_projection=None, guidance_norm_threshold=None, guidance_momentum=None):
         """The serving configuration of the paper (App. A: 25 steps, guidance 5.0), which the reference lacks: a
         DDIM-style loop over `n_steps` evenly spaced timesteps, x' = a x + ce eps + cz z per step, with optional
         classifier-free guidance: the step runs ONE forward on the doubled batch [x; x] x [text; null_text] and combines
         eps_u + w (eps_c - eps_u).  sample_guided with one uniform `cfg_scale` over a dense batch: one library call per step."""
         _padded_solver(solver)
         _padded_rescale(guidance_rescale)
+        _padded_projection(guidance_projection, guidance_norm_threshold, guidance_momentum)
         _padded_suffix(suffix_lengths)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
@@ -520,21 +579,28 @@ class SpeechGenerator:
         return x2[:rows].clone() if cfg else x2
 
     def _guided_loop(self, B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval=None,
-                     begin_plain=None, rescale=None, prediction="eps", refresh=None, begin_reuse=None):
+                     begin_plain=None, rescale=None, prediction="eps", refresh=None, begin_reuse=None, projection=None):
         """_step_loop for the strided (DDIM) update: `step(t=, a=, ce=, cz=, w=, noise=, seeds=, step=, opts=)`.  Every step's
         coefficients go up in one upload; step i's z (when sigma != 0) is Philox of `seeds` inside the kernel, `noises[i]`, else
         z.normal_() from torch's generator, one draw per noisy step in step order.
         `rescale`: every guided step computes each utterance's guidance-rescale factor from its eps and updates with ce s32 (the
         step's phi= argument).
-        `prediction` "v" (packed batches): the rows of strided_schedule_v — (a_v, cv) travel where (a, ce) do, to the same launches."""
+        `prediction` "v" (packed batches): the rows of strided_schedule_v — (a_v, cv) travel where (a, ce) do, to the same launches.
+        `projection` (projection_vectors' (eta, r, beta)): `begin`'s step is engine.guided_step_packed_project_; the guided steps get
+        the direction buffer, the scratch — both allocated once here — and their row of project_table instead of w."""
         if seeds is not None and noises is not None:
             raise ValueError("seeds= excludes noises=")
+        x0_rows = (multistep_schedule_v if prediction == "v" else multistep_schedule)(self.alphas_cumprod, n_steps) \
+            if projection is not None else None
 
         def solver(eng, schedule, x, N, w, phi, seeds):
             # coef[i] = (a, ce, sigma) x B
             coef = torch.tensor([[[a] * B, [ce] * B, [sg] * B] for _, a, ce, sg in schedule], dtype=torch.float32).to(eng.device)
             rs = {} if phi is None else dict(phi=phi, rescale_scratch=eng.rescale_scratch(B, N))
             z = torch.empty_like(x) if seeds is None else None
+            if projection is not None and w is not None:
+                proj = project_table(projection, w.cpu(), x0_rows, guided_steps(schedule, interval)).to(eng.device)
+                pj = dict(direction=torch.empty_like(x), project_scratch=eng.project_scratch(B, N))
 
             def kwargs(i, kind):
                 noise = sd = None
@@ -545,6 +611,8 @@ class SpeechGenerator:
                         noise = z.normal_()
                     else:
                         noise = z.copy_((noises(i) if callable(noises) else noises[i]).to(eng.device))
+                if kind == "step" and projection is not None and w is not None:
+                    return dict(a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], noise=noise, seeds=sd, step=schedule[i][0], proj=proj[i], **pj)
                 return dict(a=coef[i, 0], ce=coef[i, 1], cz=coef[i, 2], w=None if kind == "plain" else w, noise=noise, seeds=sd,
                             step=schedule[i][0], **(rs if kind == "step" else {}))
             return kwargs
@@ -554,7 +622,7 @@ class SpeechGenerator:
                                solver)
 
     def _multistep_loop(self, B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval=None, begin_plain=None,
-                        rescale=None, prediction="eps", refresh=None, begin_reuse=None):
+                        rescale=None, prediction="eps", refresh=None, begin_reuse=None, projection=None):
         """_step_loop for solver="dpmpp2m": `begin`'s step is engine.guided_step_packed_multistep_ bound to x2, its conditioning and
         offsets; one library call per step of multistep_schedule over x2 and the history q — one buffer [S, d] per call, written
         by step 0 before any step reads it, the x0 of whichever step wrote it (conditional, guided or reuse: no special case).
@@ -562,7 +630,8 @@ class SpeechGenerator:
         `rescale` (rescale_vector's phi [B]): the guided steps read their coefficients from DEVICE memory instead — one
         ditto_multistep_coef per utterance and step, uploaded once, the guidance scale inside — so that the rescale can patch each
         utterance's ke before the per-utterance update runs.
-        `prediction` "v": the rows of multistep_schedule_v, (kx, ke) = (alpha, -sigma), to the same launches."""
+        `prediction` "v": the rows of multistep_schedule_v, (kx, ke) = (alpha, -sigma), to the same launches.
+        `projection`: as in _guided_loop, with engine.guided_step_packed_multistep_project_."""
         from .hip import MultistepCoef
 
         def solver(eng, schedule, x, N, w, phi, seeds):
@@ -575,11 +644,16 @@ class SpeechGenerator:
                     table[i, :, 5] = guidance_vector(guidance, B)
                     table.view(torch.int32)[i, :, 6] = int(row[6])                      # use_prev
                 coefs, rs = table.to(eng.device), eng.rescale_scratch(B, N)
+            if projection is not None and w is not None:
+                proj = project_table(projection, w.cpu(), schedule, guided_steps(schedule, interval)).to(eng.device)
+                pj = dict(direction=torch.empty_like(x), project_scratch=eng.project_scratch(B, N))
 
             def kwargs(i, kind):
                 if kind == "step" and coefs is not None:
                     return dict(q=q, coef=None, coefs=coefs[i], phi=phi, rescale_scratch=rs)
                 _, a, kx, ke, b, g, use_prev = schedule[i]
+                if kind == "step" and projection is not None and w is not None:
+                    return dict(q=q, coef=MultistepCoef(a, kx, ke, b, g, 0.0, int(use_prev), 0), proj=proj[i], **pj)
                 return dict(q=q, coef=MultistepCoef(a, kx, ke, b, g, 0.0, int(use_prev), 0), w=None if kind == "plain" else w)
             return kwargs
 
@@ -591,7 +665,8 @@ class SpeechGenerator:
     def sample_guided(self, text_emb, audio_emb, *, n_steps=25, eta=0.0, guidance=None, null_text_emb=None,
                       null_text_lengths=None, speech_lengths=None, text_lengths=None, seeds=None, noises=None,
                       cond_by_audio=False, batch_class=None, prompt_lengths=None, solver="ddim", guidance_rescale=None,
-                      suffix_lengths=None, prediction="eps"):
+                      suffix_lengths=None, prediction="eps", guidance_projection=None, guidance_norm_threshold=None,
+                      guidance_momentum=None):
         """The strided (DDIM) loop of sample_latents_strided with what serving needs: per-utterance `speech_lengths` /
         `text_lengths` (a padded batch; rows past an utterance's length are exactly 0 in the result and padding never reaches a
         valid row), per-utterance `guidance` (None: no CFG; a number; or [B] numbers), and per-utterance `seeds`.  One library
@@ -605,9 +680,11 @@ class SpeechGenerator:
         callable, for parity tests), else z.normal_() from torch's generator.  `batch_class`: the unsplit batch's utterance
         count; every step is called with class_rows = (2 with guidance, else 1) * batch_class * N.
         The padded layout has no speech prompts (`prompt_lengths` raises NotImplementedError): pack the batch and call
-        sample_guided_packed; so do solver="dpmpp2m", `guidance_rescale`, `suffix_lengths` and prediction="v".  Returns fp32 [B, N, d]."""
+        sample_guided_packed; so do solver="dpmpp2m", `guidance_rescale`, `suffix_lengths`, prediction="v" and `guidance_projection`
+        (with `guidance_norm_threshold`, `guidance_momentum`).  Returns fp32 [B, N, d]."""
         _padded_solver(solver)
         _padded_rescale(guidance_rescale)
+        _padded_projection(guidance_projection, guidance_norm_threshold, guidance_momentum)
         _padded_suffix(suffix_lengths)
         if prompt_lengths is not None:
             raise NotImplementedError("speech prompts are served over packed batches: sample_guided_packed(prompt_lengths=)")
@@ -645,7 +722,8 @@ class SpeechGenerator:
     def sample_guided_packed(self, text_emb, text_cu_seqlens, audio_emb, cu_seqlens, *, n_steps=25, eta=0.0, guidance=None,
                              null_text_emb=None, null_text_cu_seqlens=None, seeds=None, noises=None, cond_by_audio=False,
                              batch_class=None, prompt_lengths=None, solver="ddim", guidance_interval=None, guidance_rescale=None,
-                             suffix_lengths=None, prediction="eps", guidance_refresh=None):
+                             suffix_lengths=None, prediction="eps", guidance_refresh=None, guidance_projection=None,
+                             guidance_norm_threshold=None, guidance_momentum=None):
         """sample_guided over a PACKED batch: audio_emb [S, d] with utterance b in rows [cu_seqlens[b], cu_seqlens[b+1]), text_emb
         [S_T, text_dim] with its text in rows [text_cu_seqlens[b], text_cu_seqlens[b+1]).  The same loop and semantics as
         sample_guided; no padding is allocated, moved or computed.  Each step is one call of ditto_guided_step_packed_opts over
@@ -704,10 +782,33 @@ class SpeechGenerator:
         (the statistics need u at every step: a follow-up).  Works with both solvers, prompts, suffixes, an interval,
         prediction="v", seeds / noises, cond_by_audio and batch_class.  This is an approximation of the guided trajectory, not
         another route to the same bits: what it costs in speech quality has not been measured with a trained model.
+        `guidance_projection` (None, a number eta in [0, 1], or one per utterance): PROJECTED GUIDANCE — Adaptive Projected Guidance,
+        Sadat, Hilliges & Weber 2024, Algorithm 1 (include/ditto_project.h states the arithmetic).  At every guided step the guidance
+        direction is taken in x0 space, dd = ke (c - u), split into the part parallel to the conditional x0 prediction D_c = kx x + ke c
+        and the part orthogonal to it, and the parallel part — what over-drives amplitude at a strong scale — is weighted by eta:
+        eta = 1 is plain classifier-free guidance, eta = 0 keeps the orthogonal part alone.  `guidance_norm_threshold` (None, r > 0,
+        or one per utterance) caps the direction: it is scaled by min(1, r / rms) with the RMS over the utterance's generated window
+        — not the paper's whole-sample norm, which would make r depend on the utterance's length.  `guidance_momentum` (None, beta
+        in (-1, 1), or one per utterance; the paper uses negative values) keeps a running direction m' = dd + beta m across the guided
+        steps in one more buffer [S, d]; the first guided step starts it.  The last two need the first; all three need `guidance` and
+        `null_text_emb`.  Every guided step is one ditto_guided_step_packed_project_opts call (2M: ..._multistep_project_opts): the
+        same forward, one launch for the direction and its per-utterance fp64 sums, a small finish, and an update that reads x, c and
+        the direction (csrc/guided_project.hip); an utterance's result depends on its own window only.  Works with both solvers,
+        prediction "eps" and "v", prompts, suffixes, seeds / noises, per-utterance guidance and a `guidance_interval` (the steps
+        outside run the unguided entry and leave the direction alone).  With `guidance_rescale` or `guidance_refresh` it raises
+        NotImplementedError (follow-ups: a rescale of the projected prediction, a projection of the kept direction).  None: the call
+        as it was — the same entries, the same bits.  Its effect on speech quality has not been measured with a trained model.
         Returns fp32 [S, d]."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         validate_prediction(prediction)
+        projection = projection_vectors(guidance_projection, guidance_norm_threshold, guidance_momentum, len(cu_seqlens) - 1)
+        if projection is not None and (guidance is None or null_text_emb is None):
+            raise ValueError("guidance_projection needs guidance= and null_text_emb=")
+        if projection is not None and guidance_rescale is not None:
+            raise NotImplementedError("guidance_projection= with guidance_rescale=: a rescale of the projected prediction is a follow-up")
+        if projection is not None and guidance_refresh is not None:
+            raise NotImplementedError("guidance_projection= with guidance_refresh=: a projection of the kept direction is a follow-up")
         interval = None if guidance_interval is None else validate_guidance_interval(guidance_interval, self.diffusion_steps)
         if interval is not None and (guidance is None or null_text_emb is None):
             raise ValueError("guidance_interval needs guidance= and null_text_emb=")
@@ -765,6 +866,8 @@ class SpeechGenerator:
 
         def begin(eng, cfg, seeds):
             entry = entry_of(eng)
+            if projection is not None and cfg:                   # (no guided step at all: the call without guidance)
+                entry = eng.guided_step_packed_multistep_project_ if multistep else eng.guided_step_packed_project_
             if null_text_cu_seqlens is not None and guidance is None:
                 raise ValueError("null_text_cu_seqlens without guidance")
             text = text_emb.to(eng.device).float()
@@ -806,11 +909,12 @@ class SpeechGenerator:
                 x2[:S].copy_(torch.randn_like(audio_emb.float()) if not cond_by_audio else audio_emb)
             return x2, N, functools.partial(entry, x2, cond, B=B, offsets=offsets)
 
+        pj = {} if projection is None else dict(projection=projection)   # None: the loops are called as they were
         if multistep:
             return self._multistep_loop(B, guidance, null_text_emb, n_steps, seeds, batch_class, begin, interval, begin_plain, rescale,
-                                        prediction, refresh, begin_reuse)
+                                        prediction, refresh, begin_reuse, **pj)
         return self._guided_loop(B, guidance, null_text_emb, n_steps, eta, seeds, noises, batch_class, begin, interval, begin_plain,
-                                 rescale, prediction, refresh, begin_reuse)
+                                 rescale, prediction, refresh, begin_reuse, **pj)
 
     def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim", infill=False,
                       prediction="eps", refresh=False):
