@@ -39,7 +39,8 @@ def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs += [os.path.join(INCLUDE, "ditto_hip.h"), os.path.join(INCLUDE, "ditto_optim.h"),
              os.path.join(INCLUDE, "ditto_train_rows.h"), os.path.join(INCLUDE, "ditto_text_grad.h"),
-             os.path.join(INCLUDE, "ditto_refresh.h"), os.path.join(INCLUDE, "ditto_project.h")]
+             os.path.join(INCLUDE, "ditto_refresh.h"), os.path.join(INCLUDE, "ditto_project.h"),
+             os.path.join(INCLUDE, "ditto_project_stream.h")]
     return hdrs
 
 

@@ -23,6 +23,7 @@
 
 #include "batch_layout.h"
 #include "ditto_project.h"
+#include "ditto_project_stream.h"
 #include "ditto_refresh.h"
 #include "gemm_common.h"
 
@@ -2269,6 +2270,104 @@ int ditto_guided_step_packed_multistep_project_opts(ditto_model_t m, float* x2, 
     }, [&](const float* eps, const float* pcoef, int d) -> int {
         HIP_TRY(launch_multistep_update_project(x2, eps, q, dir, pcoef, step, coefs, cu_speech, prompt_len, suffix_len, B, S, max_N, d,
                                                 (hipStream_t)stream));
+        return DITTO_OK;
+    });
+}
+
+// ---- projected guidance in a request stream (guided_project_mixed.hip; include/ditto_project_stream.h): a step of projected, plainly
+// guided and unguided utterances over the mixed layout; the scratch is project_bytes' ----
+// what the three entries share: the rows, the tables, the shapes and the layout
+static int check_project_mixed_rows(const char* who, const float* x2, const float* eps2, const float* dir, const int32_t* cu,
+                                    const int32_t* partner, const int32_t* kind, int B, int G, int S, int S_G, int max_N, int d) {
+    if (!x2 || !eps2 || !dir || !cu || !partner || !kind) return fail(DITTO_ERR_ARG, "%s: null x2 / eps2 / dir / cu / partner / kind", who);
+    if (((uintptr_t)x2 | (uintptr_t)eps2 | (uintptr_t)dir) % 16) return fail(DITTO_ERR_ARG, "%s: x2, eps2 and dir must be 16-byte aligned", who);
+    if (d <= 0 || d % 64) return fail(DITTO_ERR_SHAPE, "%s: d %% 64 must be 0 (d %d)", who, d);
+    if (int rc = check_packed(who, B, S, max_N, S, max_N)) return rc;
+    if (!mixed_layout_ok(B, G, S, S_G))
+        return fail(DITTO_ERR_SHAPE, "%s: need 0 <= G <= B, G <= S_G <= S, and S_G == 0 exactly when G == 0 (B %d, G %d, S %d, S_G %d)",
+                    who, B, G, S, S_G);
+    return DITTO_OK;
+}
+// every argument of launch 1 and the finish
+static int check_project_mixed(const char* who, const float* x2, const float* eps2, const float* dir, const ditto_project_coef* proj,
+                               const int32_t* cu, const int32_t* partner, const int32_t* kind, int B, int G, int S, int S_G, int max_N,
+                               int d, const void* scratch, size_t scratch_bytes) {
+    if (!proj || !scratch) return fail(DITTO_ERR_ARG, "%s: null proj / scratch", who);
+    if ((uintptr_t)proj % 16) return fail(DITTO_ERR_ARG, "%s: proj must be 16-byte aligned", who);
+    if ((uintptr_t)scratch % 256) return fail(DITTO_ERR_ARG, "%s: the project scratch must be 256-byte aligned", who);
+    if (int rc = check_project_mixed_rows(who, x2, eps2, dir, cu, partner, kind, B, G, S, S_G, max_N, d)) return rc;
+    if (scratch_bytes < project_bytes(B, max_N, d))
+        return fail(DITTO_ERR_SIZE, "%s: the project scratch needs %zu bytes (ditto_guidance_project_bytes)", who, project_bytes(B, max_N, d));
+    return DITTO_OK;
+}
+// the update's own: pcoef, the noise and the per-utterance coefficients
+static int check_project_mixed_update(const char* who, const float* pcoef, const float* noise, const int64_t* seeds, const uint32_t* tags,
+                                      const float* w, const float* a, const float* ce, const float* cz) {
+    if (int rc = check_project_ddim(who, pcoef, noise, seeds, a, ce, cz)) return rc;
+    if (!w) return fail(DITTO_ERR_ARG, "%s: null w (fp32 [B])", who);
+    if (seeds && !tags) return fail(DITTO_ERR_ARG, "%s: seeds need tags (uint32 [B])", who);
+    return DITTO_OK;
+}
+static ProjectMixedArgs project_mixed_args(const float* x2, const float* eps2, float* dir, const ditto_project_coef* proj,
+                                           const int32_t* cu, const int32_t* partner, const int32_t* kind, const int32_t* prompt_len,
+                                           int B, int G, int S, int S_G, int d, void* scratch, size_t scratch_bytes) {
+    ProjectMixedArgs a{};
+    a.x2 = x2; a.eps2 = eps2; a.dir = dir; a.proj = proj; a.cu = cu; a.partner = partner; a.kind = kind; a.prompt_len = prompt_len;
+    a.B = B; a.G = G; a.S = S; a.S_G = S_G; a.d = d;
+    a.pcoef = (float*)scratch;
+    a.partial = (double*)((char*)scratch + project_head_bytes(B));
+    const size_t slots = (scratch_bytes - project_head_bytes(B)) / ((size_t)B * 4 * sizeof(double));
+    a.slots = slots > 0x7fffffff ? 0x7fffffff : (int)slots;
+    return a;
+}
+
+int ditto_guidance_project_packed_mixed(const float* x2, const float* eps2, float* dir, const ditto_project_coef* proj,
+                                        const int32_t* cu, const int32_t* partner, const int32_t* kind, const int32_t* prompt_len, int B,
+                                        int G, int S, int S_G, int max_N, int d, void* scratch, size_t scratch_bytes,
+                                        ditto_stream_t stream) {
+    if (int rc = check_project_mixed("ditto_guidance_project_packed_mixed", x2, eps2, dir, proj, cu, partner, kind, B, G, S, S_G, max_N, d,
+                                     scratch, scratch_bytes))
+        return rc;
+    HIP_TRY(launch_guidance_project_mixed(project_mixed_args(x2, eps2, dir, proj, cu, partner, kind, prompt_len, B, G, S, S_G, d, scratch,
+                                                             scratch_bytes), max_N, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+int ditto_guided_update_packed_project_mixed(float* x2, const float* eps2, const float* dir, const float* pcoef, const float* noise,
+                                             const int64_t* seeds, const uint32_t* tags, const float* w, const float* a, const float* ce,
+                                             const float* cz, const int32_t* cu, const int32_t* partner, const int32_t* kind,
+                                             const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N, int d,
+                                             ditto_stream_t stream) {
+    const char* who = "ditto_guided_update_packed_project_mixed";
+    if (int rc = check_project_mixed_update(who, pcoef, noise, seeds, tags, w, a, ce, cz)) return rc;
+    if (int rc = check_project_mixed_rows(who, x2, eps2, dir, cu, partner, kind, B, G, S, S_G, max_N, d)) return rc;
+    HIP_TRY(launch_guided_update_project_mixed(x2, eps2, dir, pcoef, noise, seeds, tags, w, a, ce, cz, cu, partner, kind, prompt_len, B, G,
+                                               S, S_G, max_N, d, (hipStream_t)stream));
+    return DITTO_OK;
+}
+
+// the mixed step's forward — over [x; the guided ones' copies] x [text; their null] — then launch 1 and the finish on its eps, then the
+// three-kind update reading pcoef from the scratch's head
+int ditto_guided_step_packed_project_mixed_opts(ditto_model_t m, float* x2, const void* cond, const int64_t* t, const int32_t* cu_speech,
+                                                const int32_t* cu_text, const int32_t* partner, const int32_t* kind,
+                                                const int32_t* prompt_len, float* dir, const ditto_project_coef* proj, const float* noise,
+                                                const int64_t* seeds, const uint32_t* tags, const float* w, const float* a,
+                                                const float* ce, const float* cz, int B, int G, int S, int S_G, int max_N, int S_T,
+                                                int max_T, const float* rope_cos, const float* rope_sin, void* workspace,
+                                                size_t workspace_bytes, void* scratch, size_t scratch_bytes, ditto_stream_t stream,
+                                                const ditto_call_opts* opts) {
+    PACKED_STEP(p, "ditto_guided_step_packed_project_mixed_opts");
+    return packed_step(p, [&](int d) -> int {
+        if (int rc = check_project_mixed(p.who, x2, x2, dir, proj, cu_speech, partner, kind, B, G, S, S_G, max_N, d, scratch, scratch_bytes))
+            return rc;
+        if (int rc = check_project_mixed_update(p.who, (const float*)scratch, noise, seeds, tags, w, a, ce, cz)) return rc;
+        p.nb = B + G; p.rows = S + S_G;   // G <= B and S_G <= S from here on
+        return DITTO_OK;
+    }, [&](const float* eps, int d) -> int {
+        HIP_TRY(launch_guidance_project_mixed(project_mixed_args(x2, eps, dir, proj, cu_speech, partner, kind, prompt_len, B, G, S, S_G, d,
+                                                                 scratch, scratch_bytes), max_N, (hipStream_t)stream));
+        HIP_TRY(launch_guided_update_project_mixed(x2, eps, dir, (const float*)scratch, noise, seeds, tags, w, a, ce, cz, cu_speech, partner,
+                                                   kind, prompt_len, B, G, S, S_G, max_N, d, (hipStream_t)stream));
         return DITTO_OK;
     });
 }

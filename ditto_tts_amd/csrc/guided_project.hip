@@ -2,7 +2,9 @@
 // 2024, "Eliminating Oversaturation and Artifacts of High Guidance Scales in Diffusion Models", Algorithm 1.  The guidance direction is
 // taken in x0 space (D = kx x + ke out), split into the part parallel to the conditional prediction D_c and the part orthogonal to it,
 // and the parallel part is down-weighted by eta; the direction may be capped in size (r) and carry a momentum (beta) across steps.
-// include/ditto_project.h states the arithmetic; this file is three kernels over guided_update.h's window span:
+// include/ditto_project.h states the arithmetic; this file is three kernels over guided_update.h's window span (their device functions
+// — the chunk cut, one quad's arithmetic, a chunk's lane order, the butterfly, project_rows — live in guided_project.h, which
+// guided_project_mixed.hip, the same over a request stream's layout, includes too):
 //   guidance_project_partial_kernel  grid (chunk columns, B), guided_rescale.hip's cut: chunk j of utterance b = quads [j CHUNK, (j + 1)
 //       CHUNK) of its OWN window.  Lane l reads quads j CHUNK + l, + 256, ... of x, c, u (and m with use_prev), 16 bytes each, forms
 //       dd = ke (c - u), m' = use_prev ? fmaf(beta, m, dd) : dd, D = fmaf(kx, x, ke c) in fp32, stores m' and adds m'^2, m' D, D^2 into
@@ -20,79 +22,9 @@
 // So an utterance's pcoef, m' and x' are functions of its own window and parameters: not of its position, its neighbours, B, S, max_N
 // or the grid.  HBM-bound: launch 1 reads 12 - 16 B and writes 4 B per generated element (9 fp64 instructions per element); launch 2
 // reads 12 B and writes 8 B (+ 4 B noise buffer, + 8 B multistep history).
-#include "ditto_project.h"
-#include "guided_update.h"
-#include "kernels.h"
+#include "guided_project.h"
 
 namespace ditto {
-
-typedef __attribute__((ext_vector_type(2))) double f64x2;
-constexpr int kChunk = DITTO_RESCALE_CHUNK_QUADS;
-static_assert(kChunk % 1024 == 0, "a chunk is whole rounds of 4 quads per lane of 256 lanes");
-static_assert(sizeof(::ditto_project_coef) == 32, "ditto_project_coef is 32 bytes");
-
-__device__ __forceinline__ size_t project_chunks(size_t n4, int slots) {
-    const size_t n = (n4 + kChunk - 1) / kChunk;
-    return n < (size_t)slots ? n : (size_t)slots;
-}
-
-// one quad into the direction and the three sums, element 0 .. 3 in order; returns m'
-template <bool PREV>
-__device__ __forceinline__ f32x4 project_add(const f32x4& x, const f32x4& c, const f32x4& u, const f32x4& m,
-                                             const ::ditto_project_coef& k, double (&acc)[3]) {
-    f32x4 mo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float dd = k.ke * (c[e] - u[e]);
-        const float mv = PREV ? fmaf(k.beta, m[e], dd) : dd;
-        const float dv = fmaf(k.kx, x[e], k.ke * c[e]);
-        const double md = (double)mv, Dd = (double)dv;
-        acc[0] = fma(md, md, acc[0]);
-        acc[1] = fma(md, Dd, acc[1]);
-        acc[2] = fma(Dd, Dd, acc[2]);
-        mo[e] = mv;
-    }
-    return mo;
-}
-
-// the fixed cross-lane order: after it every lane of the wave holds the same three sums
-__device__ __forceinline__ void project_butterfly(double (&acc)[3]) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) acc[k] += __shfl_xor(acc[k], m, 64);
-    }
-}
-
-// one chunk's quads of one lane: a whole chunk keeps 4 rounds of loads in flight, the last chunk runs the same order as far as it goes
-template <bool PREV>
-__device__ __forceinline__ void project_chunk(const f32x4* xc, const f32x4* ec, const f32x4* eu, f32x4* mp, size_t j, size_t n4,
-                                              const ::ditto_project_coef& k, double (&acc)[3]) {
-    const size_t q0 = j * kChunk + threadIdx.x;
-    if ((j + 1) * kChunk <= n4) {
-#pragma unroll 1
-        for (int k0 = 0; k0 < kChunk / 256; k0 += 4) {
-            f32x4 x[4], c[4], u[4], m[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const size_t q = q0 + (size_t)(k0 + r) * 256;
-                x[r] = xc[q];
-                c[r] = ec[q];
-                u[r] = eu[q];
-                if (PREV) m[r] = mp[q];
-                else m[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mp[q0 + (size_t)(k0 + r) * 256] = project_add<PREV>(x[r], c[r], u[r], m[r], k, acc);
-        }
-    } else {
-        for (size_t q = q0; q < n4; q += 256) {
-            f32x4 m = {0.f, 0.f, 0.f, 0.f};
-            if (PREV) m = mp[q];
-            mp[q] = project_add<PREV>(xc[q], ec[q], eu[q], m, k, acc);
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void guidance_project_partial_kernel(ProjectArgs a) {
     __shared__ double red[4][3];
@@ -157,28 +89,6 @@ __global__ __launch_bounds__(64) void guidance_project_finish_kernel(ProjectArgs
         fd = (float)(wr / (double)k.ke);
     }
     if (lane == 0) reinterpret_cast<f32x4*>(a.pcoef)[b] = f32x4{fx, fc, fd, 0.f};
-}
-
-// The row loop of the two project updates: update_rows' shape (quads [i0, n4) of one utterance's window at a grid stride; loads x,
-// c, the direction, then the solver's; stores x', its copy in the unconditional half, then the solver's) with the three-factor e
-template <class LINE>
-__device__ __forceinline__ void project_rows(f32x4* xc, f32x4* xu, const f32x4* ec, const f32x4* mp, LINE solver, const f32x4& f,
-                                             size_t n4, size_t i0, size_t stride) {
-    for (size_t i = i0; i < n4; i += stride) {
-        const f32x4 xv = xc[i];
-        const f32x4 c = ec[i];
-        const f32x4 mv = mp[i];
-        auto s = solver.load(i);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float ev = fmaf(f[0], xv[e], fmaf(f[1], c[e], f[2] * mv[e]));
-            o[e] = solver.line(xv[e], ev, s, e);
-        }
-        xc[i] = o;
-        xu[i] = o;
-        solver.store(i, s);
-    }
 }
 
 // NOISE, TAGS and the Philox index: guided_update_packed_kernel's (guided_packed.hip), to the letter

@@ -374,6 +374,27 @@ hipError_t launch_multistep_update_project(float* x2, const float* eps2, float* 
                                            const ::ditto_multistep_coef* step, const ::ditto_multistep_coef* coefs, const int32_t* cu,
                                            const int32_t* prompt_len, const int32_t* suffix_len, int B, int S, int max_N, int d,
                                            hipStream_t s);
+// ---------------- guided_project_mixed.hip ----------------
+// the same over a request stream's mixed layout (include/ditto_project_stream.h): x2, eps2 [S + S_G, d], cu [B + G + 1], partner and
+// kind device int32 [B] — 3 projected (launch 1, the finish and the three-factor update), 1 guided without projection (the mixed
+// kernel's partner branch), else plain; pcoef[b] = (0, 1, 0, 0) for the last two.  dir fp32 [S, d], row-aligned with rows [0, S)
+struct ProjectMixedArgs {
+    const float* x2;                 // [S + S_G, d]: rows [0, S) are read
+    const float* eps2;               // [S + S_G, d]: c, and u at the copy's rows
+    float* dir;                      // [S, d]: m, rewritten with m' on a projected utterance's generated rows
+    const ::ditto_project_coef* proj;   // [B]: read for kind 3 only
+    float* pcoef;                    // [B, 4]
+    double* partial;                 // [B, slots, 4]
+    const int32_t* cu; const int32_t* partner; const int32_t* kind; const int32_t* prompt_len;
+    int B, G, S, S_G, d;
+    int slots;
+};
+hipError_t launch_guidance_project_mixed(const ProjectMixedArgs& a, int max_N, hipStream_t s);
+hipError_t launch_guided_update_project_mixed(float* x2, const float* eps2, const float* dir, const float* pcoef, const float* noise,
+                                              const int64_t* seeds, const unsigned* tags, const float* w, const float* a,
+                                              const float* ce, const float* cz, const int32_t* cu, const int32_t* partner,
+                                              const int32_t* kind, const int32_t* prompt_len, int B, int G, int S, int S_G, int max_N,
+                                              int d, hipStream_t s);
 // ---------------- optim.hip ----------------
 // the fused training optimizer (include/ditto_optim.h): a segment's gradients are cut into partials of DITTO_OPTIM_CHUNK_QUADS
 // 16-byte quads of the segment itself, so that the global norm depends on the table and the gradients only, never on the grid: the

@@ -257,6 +257,16 @@ PROJECT_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) i
 _ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in PROJECT_PROTOTYPES.items()})
 
 
+# Projected guidance in a request stream — the direction, the three-kind update and the step over the mixed layout
+# (include/ditto_project_stream.h, csrc/guided_project_mixed.hip, csrc/ditto_api.hip): a seventh table, built and bound the same way.
+with open(os.path.join(INCLUDE, "ditto_project_stream.h")) as _f:
+    PROJECT_STREAM_PROTOTYPES = parse_prototypes(_f.read(), known=("ditto_project_coef",))
+PROJECT_STREAM_SYMBOLS = {name: (res, [t for _, t in params]) for name, (res, params) in PROJECT_STREAM_PROTOTYPES.items()}
+_ORDER.update({name: tuple(p for p, _ in params) for name, (_, params) in PROJECT_STREAM_PROTOTYPES.items()})
+# the `kind` of the ditto_*_project_mixed entries, per utterance: plain, guided without projection, projected (2 stays KIND_REUSE's)
+KIND_CFG, KIND_PROJECT = 1, 3
+
+
 class ProjectCoef(C.Structure):
     """ditto_project_coef: one utterance's parameters of a projected-guidance step (a device array [B]), 32 bytes."""
     _fields_ = [("kx", C.c_float), ("ke", C.c_float), ("w", C.c_float), ("eta", C.c_float), ("r", C.c_float), ("beta", C.c_float),
@@ -308,7 +318,8 @@ def lib() -> C.CDLL:
         l = C.CDLL(LIB_PATH)
         frozen = bool(os.environ.get("DITTO_HIP_LIB"))   # a diagnostic or FROZEN earlier build for same-box A/Bs (tools/):
         for name, (res, args) in (*SYMBOLS.items(), *OPTIM_SYMBOLS.items(), *TRAIN_ROWS_SYMBOLS.items(),
-                                  *TEXT_GRAD_SYMBOLS.items(), *REFRESH_SYMBOLS.items(), *PROJECT_SYMBOLS.items()):   # it may predate entries added since (then absent)
+                                  *TEXT_GRAD_SYMBOLS.items(), *REFRESH_SYMBOLS.items(), *PROJECT_SYMBOLS.items(),
+                                  *PROJECT_STREAM_SYMBOLS.items()):   # it may predate entries added since (then absent)
             try:
                 fn = getattr(l, name)  # AttributeError if the .so does not export a declared symbol
             except AttributeError:
@@ -335,7 +346,8 @@ def call(name: str, **kw) -> int:
     if order is None:
         header = "ditto_optim.h" if name.startswith("ditto_optim_") else "ditto_train_rows.h" if name.startswith("ditto_bwd_") else \
             "ditto_text_grad.h" if name.startswith("ditto_text_select_") else \
-            "ditto_refresh.h" if "_packed_refresh" in name else "ditto_project.h" if "_project" in name else "ditto_hip.h"
+            "ditto_refresh.h" if "_packed_refresh" in name else "ditto_project_stream.h" if "_project_mixed" in name else \
+            "ditto_project.h" if "_project" in name else "ditto_hip.h"
         raise TypeError(f"{name}: include/{header} declares no such entry")
     if len(kw) != len(order) or not all(p in kw for p in order):
         missing, unknown = [p for p in order if p not in kw], [p for p in kw if p not in order]

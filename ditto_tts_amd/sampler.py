@@ -917,7 +917,7 @@ class SpeechGenerator:
                                  rescale, prediction, refresh, begin_reuse, **pj)
 
     def guided_stream(self, *, max_rows, max_utterances, max_text_rows, guided=True, class_rows=None, solver="ddim", infill=False,
-                      prediction="eps", refresh=False):
+                      prediction="eps", refresh=False, project=False):
         """A request stream over this model (ditto_tts_amd/serving.py GuidedStream): submit(text_emb, n_frames, ...) queues an
         utterance, step() admits what fits, runs one guided strided step over everything in flight — each utterance at its own
         index of its own strided_schedule — and returns the finished ones.  `max_rows` / `max_utterances` / `max_text_rows`: the
@@ -935,19 +935,26 @@ class SpeechGenerator:
         request on refresh_plan's schedule of its own guided steps (sample_guided_packed(guidance_refresh=)) — and holds the kept
         directions beside the state.  A guided "ddim" stream without infill only: guided=False is a ValueError, solver="dpmpp2m"
         and infill=True are NotImplementedError (follow-ups, like guidance_rescale with it).  False: the stream as it was.  What
-        the approximation costs in speech quality has not been measured with a trained model."""
+        the approximation costs in speech quality has not been measured with a trained model.
+        `project`: the stream accepts submit(..., guidance_projection=, guidance_norm_threshold=, guidance_momentum=) — projected
+        guidance, each request with its own eta, r and beta (sample_guided_packed(guidance_projection=)) — and holds the directions
+        m' beside the state.  A guided "ddim" stream without infill and without refresh only: guided=False is a ValueError, the
+        others are NotImplementedError (follow-ups, like guidance_rescale with it).  False: the stream as it was.  Its effect on
+        speech quality has not been measured with a trained model."""
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         validate_prediction(prediction)
-        from .serving import DeviceBatch, GuidedStream, validate_refresh_stream
+        from .serving import DeviceBatch, GuidedStream, validate_project_stream, validate_refresh_stream
         refresh = validate_refresh_stream(refresh, bool(guided), solver, bool(infill))
+        project = validate_project_stream(project, bool(guided), solver, bool(infill), refresh)
         require_fused_attention(self.ditto_model.cfg, "request streams (packed batches)")
         eng = self.ditto_model.engine(torch.empty(0, device=self.device).device)
         batch = DeviceBatch(eng, max_rows=max_rows, max_utterances=max_utterances, max_text_rows=max_text_rows, guided=guided,
-                            class_rows=class_rows, solver=solver, infill=infill, refresh=refresh)
+                            class_rows=class_rows, solver=solver, infill=infill, refresh=refresh,
+                            project=project)
         return GuidedStream(batch, self.alphas_cumprod, max_rows=max_rows, max_utterances=max_utterances,
                             max_text_rows=max_text_rows, guided=guided, text_dim=eng.cfg.text_dim, hidden_dim=eng.cfg.hidden_dim,
-                            solver=solver, infill=infill, prediction=prediction, refresh=refresh)
+                            solver=solver, infill=infill, prediction=prediction, refresh=refresh, project=project)
 
     # public aliases (the mangled names above are what the reference's own code reaches)
     def p_sample(self, x, t, text_emb, noise=None):

@@ -28,6 +28,16 @@ A step's set G is then the REFRESHING requests; the batch holds the directions i
 a step with a k > 1 request in flight is ditto_guided_step_packed_refresh_opts (csrc/guided_refresh.hip): refreshing, reusing and
 plain utterances in one forward and one update.  "ddim" streams without infill; what the approximation costs in speech quality is
 not measured by anything here.
+Projected guidance (guided_stream(project=True), submit(guidance_projection=, guidance_norm_threshold=, guidance_momentum=)): a request
+carries its own eta, r and beta, and its ditto_project_coef row of every step (sampler.project_table for that utterance alone,
+computed at submit).  A step's kinds are 3 projected, 1 guided without projection, 0 plain; G is the guided ones of either kind; the
+batch holds the directions m' in two more buffers — a regroup carries the one of every projected survivor between two of its guided
+steps — and a step at which a request is projected is ditto_guided_step_packed_project_mixed_opts (csrc/guided_project_mixed.hip).
+"ddim" streams without infill, refresh and guidance rescale.  Measured on one MI355X at C2 in a steady-state stream kept at B = 32
+(profiles/stream_project_bench.json): 17.05 ms per step (16.97 - 17.36) without project=True, 17.02 ms (16.86 - 17.31) with it and
+nobody projected, 17.08 ms (16.97 - 17.32) with every request projected: differences inside the round-to-round range.  Its effect
+on speech quality is not measured by anything here; "dpmpp2m" streams, infill streams, rescale, reuse and the padded entries remain
+follow-ups.
 They serve the reference's sampling loop (reference src/model/SpeechGenerator.py:130-164) to a request stream.
 """
 from __future__ import annotations
@@ -61,11 +71,14 @@ class Request:
     speech prompt that stands in front of the `n_frames` generated rows, `suffix` ([Q, d] or None) the clean rows behind them (speech
     infilling); the utterance occupies `rows` = P + n_frames + Q rows."""
     __slots__ = ("handle", "text", "null", "T", "T_null", "n_frames", "seed", "w", "n_steps", "eta", "x_T", "schedule", "i", "b",
-                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm", "phi", "suffix", "Q", "kinds", "period")
+                 "row", "trow", "nrow", "prompt", "P", "interval", "in_g", "ntm", "phi", "suffix", "Q", "kinds", "period", "pcoef")
 
     def __init__(self, handle, text, null, n_frames, seed, w, n_steps, eta, x_T, schedule, prompt=None, interval=None, phi=0.0,
-                 suffix=None, kinds=None, period=1):
+                 suffix=None, kinds=None, period=1, pcoef=None):
         self.handle, self.text, self.null = handle, text, null
+        # projected guidance: `pcoef` — fp32 [n_steps, 8], the request's ditto_project_coef of every step of its schedule
+        # (sampler.project_table's rows for this utterance alone); None: the request is not projected
+        self.pcoef = pcoef
         # guidance reuse: `kinds` — hip.KIND_* of every step of its schedule (refresh_plan's list; None: from guided_now()) —
         # and the refresh `period` k it was made with (1: every guided step refreshes)
         self.kinds, self.period = kinds, int(period)
@@ -95,6 +108,18 @@ class Request:
             return self.kinds[self.i]
         return hip.KIND_REFRESH if self.guided_now() else hip.KIND_PLAIN
 
+    def project_kind_now(self) -> int:
+        """the kind of the step it stands at in a stream made with project=True: hip.KIND_PROJECT where it is guided and carries a
+        projection, hip.KIND_CFG where it is guided without one, else hip.KIND_PLAIN"""
+        if self.kind_now() == hip.KIND_PLAIN:
+            return hip.KIND_PLAIN
+        return hip.KIND_PROJECT if self.pcoef is not None else hip.KIND_CFG
+
+    def carries_direction(self) -> bool:
+        """whether a regroup in front of the step it stands at has to take its direction m' along: it is projected, has had a
+        guided step (which wrote m') and has one to come (which reads it, whatever lies in between)"""
+        return self.pcoef is not None and any(self.kinds[:self.i]) and any(self.kinds[self.i:])
+
     @property
     def rows(self) -> int:
         return self.P + self.n_frames + self.Q
@@ -110,13 +135,15 @@ class Plan:
     reads.  The null conditioning of a member outside G is parked behind G's: `null_row` / `null_tm` [B] are each member's null K/V
     row (counted from the T text rows) and tmod row (counted from the B text ones) — G's first, in order, then the parked ones.
     `kind` [B] (guidance reuse; else None): hip.KIND_* of each member's coming step — G is then the refreshing members, and a
-    survivor about to reuse takes its kept direction along."""
+    survivor about to reuse takes its kept direction along.
+    `carry` [B] (projected guidance; else None): which members take their direction m' along (Request.carries_direction)."""
     __slots__ = ("members", "newcomers", "cu", "cu_text", "cu_null", "in_g", "partner", "cu_g", "offsets", "text_offsets", "null_row",
-                 "null_tm", "kind")
+                 "null_tm", "kind", "carry")
 
-    def __init__(self, members, newcomers, guided, in_g=None, kind=None):
+    def __init__(self, members, newcomers, guided, in_g=None, kind=None, carry=None):
         self.members, self.newcomers = list(members), list(newcomers)
         self.kind = None if kind is None else list(kind)
+        self.carry = None if carry is None else [bool(f) for f in carry]
         self.cu, self.cu_text = _cumulate(r.rows for r in members), _cumulate(r.T for r in members)
         self.cu_null = _cumulate(r.T_null for r in members) if guided else None
         self.in_g = self.partner = self.cu_g = self.null_row = self.null_tm = None
@@ -142,9 +169,11 @@ class StepArgs:
     `G` the number of guided utterances and `S_G` their rows (None, None, 0, 0 unguided).  `phi` [B]: each utterance's guidance-rescale
     blend factor (0: none).  `suffix` [B]: each utterance's suffix rows (speech infilling; 0: none).
     `kind` [B] (None unguided): hip.KIND_* of each utterance's step — plain, refresh or reuse; `in_g` is kind == refresh, "has an
-    unconditional copy in this step's forward".  `period` [B]: each utterance's refresh period k (1: it never reuses)."""
+    unconditional copy in this step's forward".  `period` [B]: each utterance's refresh period k (1: it never reuses).
+    A stream made with project=True: `kind` [B] is hip.KIND_PLAIN / KIND_CFG / KIND_PROJECT, `in_g` is kind != plain, and `proj` [B]
+    holds each utterance's ditto_project_coef of this step as 8 fp32 words (None: it carries no projection)."""
     __slots__ = ("B", "S", "max_N", "S_T", "max_T", "t", "a", "ce", "cz", "w", "tags", "seeds", "handles", "prompt", "coef", "in_g",
-                 "partner", "G", "S_G", "phi", "suffix", "kind", "period")
+                 "partner", "G", "S_G", "phi", "suffix", "kind", "period", "proj")
 
 
 def _cumulate(lengths) -> List[int]:
@@ -182,11 +211,28 @@ def validate_refresh_stream(refresh, guided: bool, solver: str, infill: bool) ->
     return True
 
 
+def validate_project_stream(project, guided: bool, solver: str, infill: bool, refresh: bool) -> bool:
+    """`project` of a stream as a bool; a stream that cannot serve projected guidance is refused here, before anything is made"""
+    if not project:
+        return False
+    if not guided:
+        raise ValueError("project=True needs a guided stream: projected guidance reshapes the direction of classifier-free guidance")
+    if solver != "ddim":
+        raise NotImplementedError(f"project=True is served by \"ddim\" streams; this stream's solver is {solver}: a regroup has no "
+                                  "slot left for the direction beside the multistep history (a follow-up)")
+    if infill:
+        raise NotImplementedError("project=True with infill=True: the mixed projected update has no windowed form (a follow-up)")
+    if refresh:
+        raise NotImplementedError("project=True with refresh=True: a projection of the kept direction is a follow-up")
+    return True
+
+
 class GuidedStream:
     """stream = sg.guided_stream(max_rows=, max_utterances=, max_text_rows=, guided=True | False, class_rows=None, infill=False,
-                              refresh=False)
+                              refresh=False, project=False)
     h = stream.submit(text_emb [T_b, text_dim], n_frames, seed=, guidance=, null_text_emb=, n_steps=25, eta=0.0, x_T=None,
-                      prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None, guidance_refresh=None)
+                      prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None, guidance_refresh=None,
+                      guidance_projection=None, guidance_norm_threshold=None, guidance_momentum=None)
     done = stream.step()          # [(handle, latents fp32 [n_frames, d] on the GPU), ...]
     stream.pending, stream.active, stream.drain()
 
@@ -219,15 +265,24 @@ class GuidedStream:
     guided steps, fixed at submit: interval-aware, the counter reset by an unguided step, the first guided step a refresh.  None
     and 1: every guided step refreshes, the request as it was.  k > 1 with guidance_rescale > 0 raises NotImplementedError, as in
     the closed call; so does any guidance_rescale > 0 in a refresh=True stream, where the request could share a step with a
-    reusing one.  An approximation of the guided trajectory: its effect on speech quality has not been measured."""
+    reusing one.  An approximation of the guided trajectory: its effect on speech quality has not been measured.
+    `guidance_projection`, `guidance_norm_threshold`, `guidance_momentum` (a stream made with project=True only — guided, "ddim", no
+    infill, no refresh; None, or eta in [0, 1], r > 0, beta in (-1, 1)): projected guidance (sample_guided_packed(guidance_projection=))
+    — sampler.projection_vectors' ranges and errors; the last two need the first.  The request is projected at its guided steps,
+    interval-aware, the momentum kept across unguided ones; requests without the arguments keep their bits.  Any guidance_rescale > 0
+    in such a stream raises NotImplementedError.  Measured at C2, B = 32 in steady state: 17.08 ms per step with every request
+    projected against 17.05 ms in a stream made without project=True (profiles/stream_project_bench.json), inside the round-to-round
+    range.  Its effect on speech quality has not been measured; "dpmpp2m" streams, infill streams, rescale, reuse and the padded
+    entries remain follow-ups."""
 
     def __init__(self, batch, alphas_cumprod: torch.Tensor, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool,
                  text_dim: int, hidden_dim: int, solver: str = "ddim", infill: bool = False, prediction: str = "eps",
-                 refresh: bool = False):
+                 refresh: bool = False, project: bool = False):
         from .sampler import SOLVERS, validate_prediction
         if solver not in SOLVERS:
             raise ValueError(f"solver: one of {SOLVERS} is needed, got {solver!r}")
         self.refresh = validate_refresh_stream(refresh, bool(guided), solver, bool(infill))
+        self.project = validate_project_stream(project, bool(guided), solver, bool(infill), self.refresh)
         self.solver, self.infill = solver, bool(infill)
         self.prediction = validate_prediction(prediction)
         for name, v in (("max_rows", max_rows), ("max_utterances", max_utterances), ("max_text_rows", max_text_rows)):
@@ -238,6 +293,7 @@ class GuidedStream:
         self.text_dim, self.hidden_dim = int(text_dim), int(hidden_dim)
         self._acp = alphas_cumprod.detach().double().cpu()
         self._schedules = {}                       # (n_steps, eta) -> strided_schedule
+        self._x0_rows = {}                         # n_steps -> multistep_schedule: the (kx, ke) of projected guidance
         self._queue: collections.deque = collections.deque()
         self._active: List[Request] = []
         self._dirty = False                        # utterances left since the last regroup: the buffers have holes
@@ -263,6 +319,14 @@ class GuidedStream:
                                     else (multistep_schedule_v if v else multistep_schedule)(self._acp, n_steps))
         return self._schedules[key]
 
+    def _x0_schedule(self, n_steps: int):
+        """the multistep schedule over a request's timesteps, whose (kx, ke) map the network's output to x0: what the closed call
+        hands project_table"""
+        if n_steps not in self._x0_rows:
+            from .sampler import multistep_schedule, multistep_schedule_v
+            self._x0_rows[n_steps] = (multistep_schedule_v if self.prediction == "v" else multistep_schedule)(self._acp, n_steps)
+        return self._x0_rows[n_steps]
+
     def _text(self, t, name):
         if not isinstance(t, torch.Tensor) or not t.dtype.is_floating_point:
             raise ValueError(f"{name}: a floating-point tensor [rows, {self.text_dim}] is needed")
@@ -271,7 +335,8 @@ class GuidedStream:
         return t.detach()
 
     def submit(self, text_emb, n_frames, *, seed=None, guidance=None, null_text_emb=None, n_steps=25, eta=0.0, x_T=None,
-               prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None, guidance_refresh=None) -> StreamHandle:
+               prompt=None, guidance_interval=None, guidance_rescale=None, suffix=None, guidance_refresh=None,
+               guidance_projection=None, guidance_norm_threshold=None, guidance_momentum=None) -> StreamHandle:
         """Queue one utterance.  Everything is validated here, on the host: a bad request raises ValueError and leaves the stream as
         it was; so does one that could never fit the capacities."""
         text = self._text(text_emb, "text_emb")
@@ -327,11 +392,24 @@ class GuidedStream:
         if self.refresh and phi > 0:                               # it could share a step with a reusing request
             raise NotImplementedError("a stream made with refresh=True serves no guidance_rescale= > 0: the three-kind update of a step "
                                       "with a reusing request in flight has no rescale form (a follow-up)")
+        if not self.project and not (guidance_projection is None and guidance_norm_threshold is None and guidance_momentum is None):
+            raise ValueError("guidance_projection=, guidance_norm_threshold= and guidance_momentum= need a stream made with "
+                             "project=True (guided_stream(project=True))")
+        from .sampler import projection_vectors
+        projection = projection_vectors(guidance_projection, guidance_norm_threshold, guidance_momentum, 1)
+        if self.project and phi > 0:                               # it could share a step with a projected request
+            raise NotImplementedError("a stream made with project=True serves no guidance_rescale= > 0: the three-kind update of a step "
+                                      "with a projected request in flight has no rescale form (a follow-up)")
         kinds = None
         if self.guided:                                            # the list the closed call runs: refresh_plan of its own guided steps
             from .sampler import guided_steps, refresh_plan
             code = {"plain": hip.KIND_PLAIN, "refresh": hip.KIND_REFRESH, "reuse": hip.KIND_REUSE}
             kinds = [code[k] for k in refresh_plan(guided_steps(schedule, interval), period)[0]]
+        pcoef = None
+        if projection is not None:                                 # the rows the closed call uploads, for this utterance alone
+            from .sampler import guided_steps, project_table
+            pcoef = project_table(projection, torch.tensor([float(guidance)], dtype=torch.float32), self._x0_schedule(n_steps),
+                                  guided_steps(schedule, interval))[:, 0].contiguous().numpy()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)))
         elif not _is_int(seed) or not -2 ** 63 <= seed < 2 ** 63:
@@ -351,7 +429,7 @@ class GuidedStream:
                 raise ValueError(f"suffix: a floating-point tensor [Q >= 1, {self.hidden_dim}] is needed")
             suffix = suffix.detach()
         req = Request(StreamHandle(self._next_id), text, null, n_frames, seed, None if guidance is None else float(guidance), n_steps,
-                      float(eta), x_T, schedule, prompt, interval, phi, suffix, kinds, period)
+                      float(eta), x_T, schedule, prompt, interval, phi, suffix, kinds, period, pcoef)
         if req.rows > self.max_rows:
             raise ValueError(f"a request of {req.rows} rows ({req.P} prompt + {req.n_frames} frames"
                              + (f" + {req.Q} suffix" if req.Q else "") + f") can never fit max_rows = {self.max_rows}")
@@ -381,7 +459,8 @@ class GuidedStream:
         in_g = args.in_g
         # a change of the guided set is a membership change of the unconditional region: the same one regroup serves it
         if newcomers or self._dirty or any(r.in_g != f for r, f in zip(members, in_g or ())):
-            self.batch.regroup(Plan(members, newcomers, self.guided, in_g, args.kind if self.refresh else None), args)
+            carry = [r not in newcomers and r.carries_direction() for r in members] if self.project else None
+            self.batch.regroup(Plan(members, newcomers, self.guided, in_g, args.kind if self.refresh else None, carry), args)
             for r, f in zip(members, in_g or ()):
                 r.in_g = f
             self._dirty = False
@@ -425,6 +504,10 @@ class GuidedStream:
         s.kind = [r.kind_now() for r in members] if self.guided else None
         s.period = [r.period for r in members]
         s.in_g = [k == hip.KIND_REFRESH for k in s.kind] if self.guided else None
+        s.proj = None
+        if self.project:                                           # in_g = kind != plain: the guided ones, projected or not
+            s.kind = [r.project_kind_now() for r in members]
+            s.proj = [None if r.pcoef is None else r.pcoef[r.i] for r in members]
         s.partner = partner_table(s.in_g) if self.guided else None
         s.G = sum(s.in_g) if self.guided else 0
         s.S_G = sum(r.rows for r, f in zip(members, s.in_g) if f) if self.guided else 0
@@ -532,7 +615,8 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
     plan.null_row / plan.null_tm — G's rows compacted behind the texts where the forward reads them, the others parked behind G's.
     The offsets [offsets | text_offsets] ride behind the segments in the same upload.
     Guidance reuse (plan.kind given): G is the refreshing members, and a survivor whose coming step is a reuse step gets one more
-    segment, direction_segment."""
+    segment, direction_segment.  Projected guidance (plan.carry given): so does every survivor plan.carry names — the buffers flip,
+    so the direction m' moves with its utterance whatever its coming step's kind."""
     guided = plan.in_g is not None
     B, S, Tt = len(plan.members), plan.cu[-1], plan.cu_text[-1]
     segs, xt_row = [], 0
@@ -545,6 +629,8 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
         elif multistep:
             segs.append(history_segment(r, plan.cu[j], d4))
         elif plan.kind is not None and plan.kind[j] == hip.KIND_REUSE:
+            segs.append(direction_segment(r, plan.cu[j], d4))
+        elif plan.carry is not None and plan.carry[j]:
             segs.append(direction_segment(r, plan.cu[j], d4))
         if new:
             base, own_tmod = new_image[r.handle.id]
@@ -564,13 +650,16 @@ def regroup_table(plan: Plan, *, d4: int, kv16: int, tm16: int, tmod_old16: int,
     return segs, tail
 
 
-def step_block_layout(max_utterances: int, guided: bool, multistep: bool, infill: bool = False, refresh: bool = False) -> dict:
+def step_block_layout(max_utterances: int, guided: bool, multistep: bool, infill: bool = False, refresh: bool = False,
+                      project: bool = False) -> dict:
     """Byte offsets of the per-step argument block (host arithmetic): t int64 [halves * maxB] | seeds int64 [maxB] | a | ce | cz | w
     fp32 [maxB] | tags uint32 [maxB] | prompt_len int32 [maxB] | partner int32 [maxB] | (multistep) ditto_multistep_coef [maxB] |
     phi fp32 [maxB] — the guidance-rescale blend factors, appended behind everything else: the fields in front keep the offsets
     they had before it existed.  `infill`: suffix_len int32 [maxB] ("suffix") is appended behind phi in the same way; off (the
     default), the layout is the one without it.  `refresh`: kind int32 [maxB] ("kind", guidance reuse) is appended behind everything
-    else in the same way.  "f_stride": bytes of one fp32 / int32 field; "bytes": the whole block."""
+    else in the same way.  `project`: kind int32 [maxB] ("kind", projected guidance's) and then ditto_project_coef [maxB] ("proj",
+    16-byte aligned) are appended behind everything else in the same way.  "f_stride": bytes of one fp32 / int32 field; "bytes": the
+    whole block."""
     maxB, nbB = int(max_utterances), (2 if guided else 1) * int(max_utterances)
     lay = {"t": 0, "seeds": _pad(nbB * 8, 16)}
     o_f = lay["seeds"] + _pad(maxB * 8, 16)
@@ -585,6 +674,10 @@ def step_block_layout(max_utterances: int, guided: bool, multistep: bool, infill
     if refresh:
         lay["kind"] = lay["bytes"]
         lay["bytes"] += lay["f_stride"]
+    if project:
+        lay["kind"] = lay["bytes"]
+        lay["proj"] = _pad(lay["kind"] + lay["f_stride"], 16)
+        lay["bytes"] = lay["proj"] + _pad(C.sizeof(hip.ProjectCoef) * maxB, 16)
     return lay
 
 
@@ -597,12 +690,16 @@ class DeviceBatch:
     `infill`: the step block carries each utterance's suffix length as well.
     `refresh` (guidance reuse): two direction buffers [max_rows, d] beside the state, double-buffered like it — a regroup moves the
     reusing survivors' rows in its one launch, through the slots the history takes in a "dpmpp2m" stream —, and the step block
-    carries each utterance's kind."""
+    carries each utterance's kind.
+    `project` (projected guidance): two direction buffers [max_rows, d] beside the state, double-buffered like it and moved through the
+    same slots, one scratch (ditto_guidance_project_bytes) sized once from the capacities, and the step block carries each
+    utterance's kind and ditto_project_coef."""
 
     def __init__(self, engine, *, max_rows: int, max_utterances: int, max_text_rows: int, guided: bool, class_rows=None,
-                 solver: str = "ddim", infill: bool = False, refresh: bool = False):
+                 solver: str = "ddim", infill: bool = False, refresh: bool = False, project: bool = False):
         from .engine import require_fused_attention
         self.refresh = validate_refresh_stream(refresh, bool(guided), solver, bool(infill))
+        self.project = validate_project_stream(project, bool(guided), solver, bool(infill), self.refresh)
         require_fused_attention(engine.cfg, "request streams (packed batches)")
         self.multistep, self.infill = solver != "ddim", bool(infill)
         self.eng, self.lib, self.guided = engine, engine.lib, bool(guided)
@@ -621,6 +718,7 @@ class DeviceBatch:
             self.x = [torch.zeros(self.halves * self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)]
             self.q = [torch.zeros(self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)] if self.multistep else None
             self.delta = [torch.zeros(self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)] if self.refresh else None
+            self.dir = [torch.zeros(self.maxS, d, dtype=torch.float32, device=dev) for _ in range(2)] if self.project else None
             self.cond = [torch.zeros(cond_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
             # every newcomer's own image [K/V rows | tmod], 256-byte aligned, one behind the other
             self.new_cond = torch.zeros(self.maxT * self.kv_row + self.maxB * (_pad(self.halves * self.tmod_row, 256) + 256),
@@ -628,14 +726,16 @@ class DeviceBatch:
             self.x_T = torch.zeros(self.maxS, d, dtype=torch.float32, device=dev)
             self.cu_pad = _pad(nbB + 1, 4)                                 # int32 words of one offsets section
             self.offsets = torch.zeros(2 * self.cu_pad, dtype=torch.int32, device=dev)     # [cu (doubled under CFG) | cu_text]
-            lay = step_block_layout(self.maxB, self.guided, self.multistep, self.infill, self.refresh)
-            self.o_suffix, self.o_kind = lay.get("suffix"), lay.get("kind")
+            lay = step_block_layout(self.maxB, self.guided, self.multistep, self.infill, self.refresh, self.project)
+            self.o_suffix, self.o_kind, self.o_proj = lay.get("suffix"), lay.get("kind"), lay.get("proj")
             self.f_stride, self.block_bytes = lay["f_stride"], lay["bytes"]
             (self.o_t, self.o_seeds, self.o_a, self.o_ce, self.o_cz, self.o_w, self.o_tags, self.o_prompt, self.o_partner, self.o_coef,
              self.o_phi) = (lay[k] for k in ("t", "seeds", "a", "ce", "cz", "w", "tags", "prompt", "partner", "coef", "phi"))
             self.block = _Upload(self.block_bytes, dev)
             # the guidance-rescale scratch, once, for maxB utterances of at most maxS generated rows
             self.rescale = engine.rescale_scratch(self.maxB, self.maxS) if self.guided else None
+            # the projected-guidance scratch [pcoef | partials], once, for the same capacities
+            self.project_scratch = engine.project_scratch(self.maxB, self.maxS) if self.project else None
             self.max_seg = 8 * self.maxB + 8
             self.table = _Upload(self.max_seg * 4 * hip.REGROUP_SEG_WORDS + 2 * self.cu_pad * 4, dev)
             engine.workspace_packed(nbB, self.halves * self.maxS, self.maxT)
@@ -670,6 +770,12 @@ class DeviceBatch:
             buf[self.o_suffix:self.o_suffix + B * 4].view(np.int32)[:] = a.suffix
         if self.refresh:
             buf[self.o_kind:self.o_kind + B * 4].view(np.int32)[:] = a.kind
+        if self.project:               # ditto_project_coef: kx, ke, w, eta, r, beta fp32 | use_prev int32 | reserved; zeros where there is none
+            buf[self.o_kind:self.o_kind + B * 4].view(np.int32)[:] = a.kind
+            pj = buf[self.o_proj:self.o_proj + 32 * B].view(np.float32).reshape(B, 8)
+            for j, row in enumerate(a.proj):
+                if row is not None:
+                    pj[j] = row
         self.block.send(buf)
 
     def _block_ptr(self, off: int) -> int:
@@ -696,6 +802,9 @@ class DeviceBatch:
         elif self.refresh:             # so do the kept directions, in the same slots (a refresh stream has no history)
             src.append(self.delta[self.cur])
             dst.append(self.delta[nxt])
+        elif self.project:             # and the projected directions m' (a "ddim" stream without refresh: the slots are free)
+            src.append(self.dir[self.cur])
+            dst.append(self.dir[nxt])
         n = hip.REGROUP_BUFS
         sp, sb, dp, db = (C.c_void_p * n)(), (C.c_size_t * n)(), (C.c_void_p * n)(), (C.c_size_t * n)()
         for k, t in enumerate(src):
@@ -770,7 +879,11 @@ class DeviceBatch:
         step block; with none in flight, the entries above.
         A step with a request of refresh period k > 1 in flight (a refresh stream: "ddim", no infill, no rescale beside k > 1) runs
         ditto_guided_step_packed_refresh_opts over the B utterances and the G copies of the refreshing ones — G = 0 and G = B
-        included — with the kinds from the step block and the current direction buffer; with none in flight, the entries above."""
+        included — with the kinds from the step block and the current direction buffer; with none in flight, the entries above.
+        A step in which a request is projected (a project stream: "ddim", no infill, no refresh, no rescale) runs
+        ditto_guided_step_packed_project_mixed_opts over the B utterances and the G copies of the guided ones, projected or not, with
+        the kinds and the ditto_project_coef rows from the step block, the current direction buffer and the scratch built once;
+        every other step runs the entries above."""
         if not self._block_sent:
             self._send_block(a)
         self._block_sent = False
@@ -799,6 +912,12 @@ class DeviceBatch:
             hip.check(hip.call("ditto_guided_step_packed_refresh_opts", **args, partner=at(self.o_partner), kind=at(self.o_kind),
                                prompt_len=prompt, delta=self.delta[self.cur].data_ptr(), **noise, w=at(self.o_w), **coef, B=a.B, G=a.G,
                                S=a.S, S_G=a.S_G))
+            return
+        if self.project and any(k == hip.KIND_PROJECT for k in a.kind):
+            hip.check(hip.call("ditto_guided_step_packed_project_mixed_opts", **args, partner=at(self.o_partner), kind=at(self.o_kind),
+                               prompt_len=prompt, dir=self.dir[self.cur].data_ptr(), proj=at(self.o_proj), **noise, w=at(self.o_w), **coef,
+                               B=a.B, G=a.G, S=a.S, S_G=a.S_G, scratch=self.project_scratch.data_ptr(),
+                               scratch_bytes=self.project_scratch.numel()))
             return
         if cfg and any(p > 0 and g for p, g in zip(a.phi, a.in_g)):
             rescale = dict(phi=at(self.o_phi), scratch=self.rescale.data_ptr(), scratch_bytes=self.rescale.numel())

@@ -50,6 +50,7 @@
  * an access outside the buffers.
  * Traffic per generated element: launch 1 reads x, c, u (and m with use_prev) and writes m', 16 - 20 B; launch 2 reads x, c, m' and
  * writes both halves, 20 B (+ 4 B noise buffer; + 8 B multistep history).
+ * The same over a request stream's mixed layout, where only some utterances of a step are projected: include/ditto_project_stream.h.
  */
 #ifndef DITTO_PROJECT_H
 #define DITTO_PROJECT_H
